@@ -23,7 +23,9 @@ Workloads (BASELINE.json `configs`, built by bevy_firework_amd/workloads.py):
 itself through `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`, one device per
 rank) and exits non-zero when fewer than N devices are visible: it never falls back to one GPU or to configs[1].
 
-Rank 0 prints ONE JSON line (contract in the task statement) with extra objects:
+Rank 0 prints ONE JSON line (contract in the task statement).  A plain run sets up, warms up, times --steps steps, writes
+--dump-outputs and prints the line; `roofline` and `cpu_baseline` are null there.  --full adds the extra objects, each
+measured after the timed region:
   roofline      HBM roofline of the dominant kernel (fw_k_update*), from HIP events attached to each
                 dispatch on the kernel's own stream; for N=1 also `hbm_resident` (configs[2], 16.8M particles:
                 a working set far beyond the 256 MiB Infinity Cache) and `variable_dt` (configs[1] stepped with
@@ -32,6 +34,12 @@ Rank 0 prints ONE JSON line (contract in the task statement) with extra objects:
                 clone/filter/collect) on a bounded sample: configs[1] on 1 thread (the reference runs one
                 spawner on one core, core.rs:583-586) and, under `many_emitters`, configs[2]'s emitters on all
                 host cores, one spawner per thread like par_iter_mut
+
+--dump-outputs DIR: what the last timed step left, as a caller reads it (SpawnerData.particles), written after the timed
+region as DIR/<name>.npy (float32 / float64; with N > 1 every rank writes DIR/<name>.rank<r>.npy): `counts` (live particles
+of every local spawner and particle type, in spawn order) and one file per particle field over a fixed, seeded sample of at
+most DUMP_MAX_PARTICLES of the particles (all of them when fewer), taken in spawn order.  Inputs are seeded: the same
+arguments give the same inputs on every run, so two builds can be compared file by file.
 """
 import argparse
 import json
@@ -45,6 +53,7 @@ sys.path.insert(0, ROOT)
 SURVEY_BYTES = 156  # 64 B read + 92 B written per particle-update (every plane rewritten)
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured float4 copy)
 INFINITY_CACHE_BYTES = 256 << 20  # MI355X_MICROARCH.md: 256 MiB memory-side cache; a working set below it is not an HBM stream
+DUMP_MAX_PARTICLES = 1 << 19  # x 104 B of float32 fields = 54.5 MB, under the 64 MB cap of --dump-outputs
 # Round 6: scale, base colour and emissive colour are pure functions of (age, lifetime, initial_scale) (core.rs:601-605, 652-655)
 # and the update no longer stores them for any type (FW_TYPE_DERIVED): 36 of SURVEY's 92 written bytes are not moved.
 # `algorithmic_bytes_per_particle` is what the library reports for the path the type is on (fw_debug_update_path);
@@ -61,6 +70,37 @@ def path_bytes(ps):
     h = next(iter(ps.spawners.values()))
     mode, moved, algo = h.update_path(0)
     return mode, algo, moved
+
+
+def dump_outputs(path, handles, rank, world):
+    """--dump-outputs: the particles the last timed step left, read as a caller reads them (module docstring)"""
+    import numpy as np
+
+    from bevy_firework_amd import settings as S
+    from bevy_firework_amd import workloads
+
+    os.makedirs(path, exist_ok=True)
+    suffix = f".rank{rank}" if world > 1 else ""
+    parts = [(h, t, n) for h in handles for t, n in enumerate(h.counts())]
+    counts = np.array([n for _, _, n in parts], dtype=np.float64)
+    total = int(counts.sum())
+    keep = min(total, DUMP_MAX_PARTICLES // world)
+    rng = np.random.default_rng(workloads.SEED + rank)
+    pick = np.arange(total) if keep == total else np.sort(rng.choice(total, keep, replace=False))
+    fields = {f: [] for f in S.PARTICLE_DTYPE.names}
+    off = 0
+    for h, t, n in parts:
+        lo, hi = np.searchsorted(pick, [off, off + n])
+        if hi > lo:
+            p = h.particles(t)
+            assert len(p) == n, (len(p), n)
+            for f, chunks in fields.items():
+                chunks.append(p[f][pick[lo:hi] - off])
+        off += n
+    np.save(os.path.join(path, f"counts{suffix}.npy"), counts)
+    for f, chunks in fields.items():
+        a = np.concatenate(chunks) if chunks else np.zeros((0,) + S.PARTICLE_DTYPE[f].shape)
+        np.save(os.path.join(path, f"{f}{suffix}.npy"), a.astype(np.float32))
 
 
 def cpu_baseline(args, dt, world=1, check=False, workload="auto"):
@@ -174,9 +214,11 @@ def gather_ranks(dist, world, device, elapsed, updated, live, roof):
     return [[float(v) for v in x.tolist()] for x in allt]
 
 
-def assemble_line(args, world, workload, rows, roof, extras, cpu, hist, rccl_ranks, measured_copy, reduce_every):
+def assemble_line(args, world, workload, rows, roof, extras, cpu, hist, rccl_ranks, measured_copy, reduce_every,
+                  algo_bytes=SURVEY_BYTES):
     """rank 0's ONE JSON line from the per-rank rows (gather_ranks), rank 0's roofline object, the extra measurements and the
-    CPU baseline.  Pure bookkeeping: the launch check (tests/test_bench_launch.py) runs it on stand-in numbers."""
+    CPU baseline (roof / cpu None in a run without --full: algo_bytes, the library's figure for the path, then stands in for the
+    roofline's).  Pure bookkeeping: the launch check (tests/test_bench_launch.py) runs it on stand-in numbers."""
     elapsed = max(r[0] for r in rows)  # the slowest rank's clock around the barrier-bracketed region
     updated, live = int(sum(r[1] for r in rows)), int(sum(r[2] for r in rows))
     per_rank_ms = [r[0] / args.steps * 1e3 for r in rows]
@@ -209,7 +251,7 @@ def assemble_line(args, world, workload, rows, roof, extras, cpu, hist, rccl_ran
             "update_mode": os.environ.get("FW_UPDATE_MODE", "fused"),
             "records_in_host_written_device_memory": extras.get("param_bar"),
         },
-        "hbm_gbs_algorithmic_whole_step": value * (roof["algorithmic_bytes_per_particle"] if roof else SURVEY_BYTES) / 1e9,
+        "hbm_gbs_algorithmic_whole_step": value * (roof["algorithmic_bytes_per_particle"] if roof else algo_bytes) / 1e9,
     }
     if roof:
         # HBM-side bytes per launch of this kernel: PMC counters cannot be read from inside the process, so this is the
@@ -323,10 +365,10 @@ def launch_check(args, world, rank):
     dist.all_reduce(t)
     workload = args.workload if args.workload != "auto" else ("configs1" if world == 1 else "configs4")
     # stand-ins: rank r "ran" for 1 + r/10 s, updated 1000 (r + 1) particles, its kernel took 50 + r us per launch
-    roof = roofline_dict(workload, (50.0 + rank) * 1e-6, 100.0 * (rank + 1), 3, "range", 64, 68)
+    roof = roofline_dict(workload, (50.0 + rank) * 1e-6, 100.0 * (rank + 1), 3, "range", 64, 68) if args.full else None
     rows = gather_ranks(dist, world, "cpu", 1.0 + 0.1 * rank, 1000 * (rank + 1), 100 * (rank + 1), roof)
     if rank == 0:
-        cpu = None if args.no_cpu else cpu_baseline(args, 1.0 / 60.0, world, check=True, workload=workload)
+        cpu = None if args.no_cpu or not args.full else cpu_baseline(args, 1.0 / 60.0, world, check=True, workload=workload)
         out = assemble_line(args, world, workload, rows, roof, {}, cpu, [], dist.get_world_size(), 0.0, args.reduce_every)
         out.update({"launch_check": True, "rccl_ranks": dist.get_world_size(), "ranks_seen": int(t.item()),
                     "self_launched": os.environ.get("FW_BENCH_SELF_LAUNCHED") == "1"})
@@ -346,9 +388,12 @@ def main():
     ap.add_argument("--live-per-emitter", type=int, default=8192)
     ap.add_argument("--reduce-every", type=int, default=16, help="frames per bucketed live-count all-reduce")
     ap.add_argument("--cpu-frames", type=int, default=30)
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-events", action="store_true", help="skip the per-kernel HIP events")
-    ap.add_argument("--no-extras", action="store_true", help="N=1: skip the hbm_resident / variable_dt / configs4 figures")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure the roofline objects, the CPU baseline and the other workloads")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-events", action="store_true", help="--full: skip the per-kernel HIP events")
+    ap.add_argument("--no-extras", action="store_true", help="--full, N=1: skip the hbm_resident / variable_dt / configs4 figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed to DIR/<name>.npy")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
@@ -425,12 +470,15 @@ def main():
     elapsed = time.perf_counter() - t0
     updated = ps.updated_total() - before
     live = ps.live_count()
+    algo_bytes = path_bytes(ps)[1]
+    if args.dump_outputs:  # (before the passes below step the system further)
+        dump_outputs(args.dump_outputs, sh.handles, rank, world)
     # Second pass over the same steady state with a hipEvent pair attached to every update dispatch on the kernel's
     # own stream (hipExtLaunchKernel start/stop events: the packet's begin / end timestamps, i.e. the duration
     # rocprofv3 --kernel-trace reports).  A separate pass so that per-dispatch signals cannot touch `value`.
     # (N > 1: every rank times its own share -- the line reports the slowest rank's kernel and all of them under `per_rank`)
     roof, measured_copy = None, 0.0
-    if not args.no_events:
+    if args.full and not args.no_events:
         roof = kernel_roofline(ps, lambda k: ps.step(dt), min(args.steps, 1000), workload)
         if rank == 0:
             measured_copy = ps.measure_copy_bandwidth(1 << 30, 20)  # float4 copy, 1 GiB -> 1 GiB (read + written bytes / s)
@@ -446,7 +494,7 @@ def main():
     # N > 1: the base point of the strong-scaling curve -- ALL emitters of configs[4] on rank 0's GPU alone, measured in
     # the same process right after the timed region (the other ranks wait at the barrier), so the line carries
     # speedup_vs_configs4_one_gpu next to the sharded figure
-    if world > 1 and workload == "configs4" and not args.no_extras:
+    if args.full and world > 1 and workload == "configs4" and not args.no_extras:
         if rank == 0:
             with ParticleSystem(device=local_rank, seed=workloads.SEED, stream=stream.cuda_stream) as p4:
                 for e, (s_, tf_) in enumerate(workloads.many_emitters(args.emitters, args.live_per_emitter)):
@@ -466,7 +514,7 @@ def main():
                                               "workload": f"{args.emitters} emitters x {args.live_per_emitter} live on one GPU "
                                                           "(rank 0's device, same process, after the timed region)"}
         barrier()
-    if rank == 0 and world == 1 and workload == "configs1" and not args.no_events and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and workload == "configs1" and not args.no_events and not args.no_extras:
         # (a) variable dt on the SAME system: a host that steps with the wall-clock delta never repeats dt bit for bit
         jit = [np.float32((1.0 / 60.0) * (1.0 + 0.1 * np.sin(0.7 * k))) for k in range(64)]
         for k in range(32):
@@ -629,11 +677,11 @@ def main():
 
     # the CPU baseline: rank 0, outside the timed region, the other ranks at the barrier below
     cpu = None
-    if rank == 0 and not args.no_cpu:
+    if args.full and rank == 0 and not args.no_cpu:
         cpu = cpu_baseline(args, dt, world, workload=workload)
     if rank == 0:
         out = assemble_line(args, world, workload, rows, roof, extras, cpu, hist, rccl_ranks, measured_copy,
-                            args.reduce_every if dist is not None else None)
+                            args.reduce_every if dist is not None else None, algo_bytes)
         flush_c_stdio()
         print(json.dumps(out), flush=True)
     if dist is not None:

@@ -17,7 +17,7 @@ for title, extra, modes in SETS:
     print(title)
     for dbg, what in modes:
         env = dict(os.environ, FW_DEBUG=str(dbg), **extra)
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--no-cpu", "--no-extras", "--steps", "400"],
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--no-cpu", "--no-extras", "--steps", "400"],
                              env=env, capture_output=True, text=True).stdout
         d = json.loads(out.strip().splitlines()[-1])
         print(f"  FW_DEBUG={dbg:2d}  {d['roofline']['avg_kernel_us']:6.2f} us kernel  {d['ms_per_step'] * 1e3:6.2f} us step  "

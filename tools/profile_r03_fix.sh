@@ -3,7 +3,7 @@
 # "compacting path": range rings take over) + the per-config PMC passes + the range soak
 export FW_ENABLE_KNOBS=1
 R=$PWD; OUT=gpurun_out/profile_r03; mkdir -p $OUT; export TMPDIR=/tmp
-FW_FIFO=0 FW_RANGE=0 timeout 900 python bench.py --no-cpu > $OUT/bench_general_path.json 2>> $OUT/bench.err
+FW_FIFO=0 FW_RANGE=0 timeout 900 python bench.py --full --no-cpu > $OUT/bench_general_path.json 2>> $OUT/bench.err
 FW_FIFO=0 FW_RANGE=0 timeout 200 python tools/launch_gaps.py > $OUT/launch_gaps.txt 2>&1
 FW_FIFO=0 FW_RANGE=0 timeout 200 python tools/tile_timeline.py > $OUT/tile_timeline.txt 2>&1
 FW_FIFO=0 FW_RANGE=0 FW_TL_JITTER=1 timeout 200 python tools/tile_timeline.py > $OUT/tile_timeline_variable_dt.txt 2>&1

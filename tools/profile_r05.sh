@@ -4,10 +4,10 @@ export FW_ENABLE_KNOBS=1   # the library honours its A/B switches only with this
 TAG=r05
 R=$PWD; OUT=gpurun_out/profile_$TAG; mkdir -p $OUT; export TMPDIR=/tmp
 # 1. the bench line itself (default flags), the driver's flags, and the same line with every type on the compacting path
-timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err
-timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu --no-extras > $OUT/bench_20_steps.json 2>> $OUT/bench.err
+timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu --no-extras > $OUT/bench_20_steps.json 2>> $OUT/bench.err
 # 2. rocprofv3 kernel trace + stats of the same command (the kernel of the headline configuration only)
-cd /tmp; timeout 900 rocprofv3 --kernel-trace --stats -d $R/$OUT -o ${TAG}_stats --output-format csv -- python $R/bench.py --no-cpu --no-extras > $R/$OUT/stats_bench.json 2>/dev/null; cd $R
+cd /tmp; timeout 900 rocprofv3 --kernel-trace --stats -d $R/$OUT -o ${TAG}_stats --output-format csv -- python $R/bench.py --full --no-cpu --no-extras > $R/$OUT/stats_bench.json 2>/dev/null; cd $R
 f=$(find $OUT -name "${TAG}_stats_kernel_trace.csv" | head -1); [ -n "$f" ] && python profiles/analyze_trace.py $f 600 > $OUT/trace_summary.txt
 f=$(find $OUT -name "${TAG}_stats_kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $OUT/${TAG}_stats_kernel_stats.csv
 # 3. PMC passes (own runs, kernel-trace only): the headline kernel, then the traffic of the other configs' update kernels

@@ -25,12 +25,12 @@ pmc2() {  # pmc2 <name> <command...>: FETCH_SIZE and WRITE_SIZE in their own pas
 }
 # 1. the bench line itself (default flags) and with the driver's flags
 if has bench; then
-  timeout 1200 python bench.py > $OUT/bench.json 2> $OUT/bench.err
-  timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu --no-extras > $OUT/bench_20_steps.json 2>> $OUT/bench.err
+  timeout 1200 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+  timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu --no-extras > $OUT/bench_20_steps.json 2>> $OUT/bench.err
 fi
 # 2. rocprofv3 kernel trace + stats of the same command (the kernel of the headline configuration only)
 if has stats; then
-  prof ${TAG}_stats 600 python $R/bench.py --no-cpu --no-extras
+  prof ${TAG}_stats 600 python $R/bench.py --full --no-cpu --no-extras
   mv $OUT/${TAG}_stats_trace_summary.txt $OUT/trace_summary.txt 2>/dev/null
 fi
 # 3. PMC passes (own runs, kernel-trace only): the headline kernel

@@ -6,11 +6,11 @@ export FW_ENABLE_KNOBS=1   # the library honours its A/B switches only with this
 TAG=${1:-r02}
 R=$PWD; OUT=gpurun_out/profile_$TAG; mkdir -p $OUT; export TMPDIR=/tmp
 # 1. the bench line itself (default flags)
-timeout 900 python bench.py > $OUT/bench.json 2> $OUT/bench.err
-FW_FIFO=0 FW_RANGE=0 timeout 900 python bench.py --no-cpu > $OUT/bench_general_path.json 2>> $OUT/bench.err   # the same line with every type on the compacting path
+timeout 900 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
+FW_FIFO=0 FW_RANGE=0 timeout 900 python bench.py --full --no-cpu > $OUT/bench_general_path.json 2>> $OUT/bench.err   # the same line with every type on the compacting path
 # 2. rocprofv3 kernel trace + stats of the same command (without the CPU baseline and the extra workloads: the
 #    kernel of the headline configuration only)
-cd /tmp; timeout 900 rocprofv3 --kernel-trace --stats -d $R/$OUT -o ${TAG}_stats --output-format csv -- python $R/bench.py --no-cpu --no-extras > $R/$OUT/stats_bench.json 2>/dev/null; cd $R
+cd /tmp; timeout 900 rocprofv3 --kernel-trace --stats -d $R/$OUT -o ${TAG}_stats --output-format csv -- python $R/bench.py --full --no-cpu --no-extras > $R/$OUT/stats_bench.json 2>/dev/null; cd $R
 python profiles/analyze_trace.py $OUT/${TAG}_stats_kernel_trace.csv 600 > $OUT/trace_summary.txt
 # 3. PMC passes (own runs, kernel-trace only)
 ./tools/pmc.sh $OUT/pmc > /dev/null 2>&1

@@ -9,7 +9,7 @@ for rep in 1 2 3; do
   for nv in "$@"; do
     name=${nv%%=*}; so=${nv#*=}
     export FW_LIB_PATH=$R/$so
-    c1=$(timeout 300 python bench.py --steps 400 --warmup 60 --no-cpu --no-extras 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('%.2f us/step  kernel %.2f us  frac %.3f' % (d['ms_per_step']*1000, d['roofline']['avg_kernel_us'], d['roofline']['frac']))")
+    c1=$(timeout 300 python bench.py --full --steps 400 --warmup 60 --no-cpu --no-extras 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('%.2f us/step  kernel %.2f us  frac %.3f' % (d['ms_per_step']*1000, d['roofline']['avg_kernel_us'], d['roofline']['frac']))")
     echo "rep$rep $name configs[1]: $c1" | tee -a $OUT
     timeout 600 python tools/bench_configs.py c5 c3 2>/dev/null | python -c "
 import json,sys

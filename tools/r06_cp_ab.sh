@@ -19,7 +19,7 @@ for l in sys.stdin:
 for rep in 1 2; do
   for v in "main6   variants/main6/libfirework_hip.so" "planes  "; do
     set -- $v; name=$1; lib=$2
-    one "$name" "$lib" -- python bench.py --no-cpu --no-extras --steps 400
+    one "$name" "$lib" -- python bench.py --full --no-cpu --no-extras --steps 400
     one "$name" "$lib" -- python tools/bench_configs.py c3 c4 c5
     one "$name compacting" "$lib" FW_RANGE=0 -- python tools/bench_configs.py c3
     one "$name compacting" "$lib" FW_RANGE=0 FW_FIFO=0 -- python tools/bench_configs.py c4
