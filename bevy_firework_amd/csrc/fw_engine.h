@@ -13,12 +13,15 @@
 //
 // There is no CPU simulation path in this library.
 //
-// The engine is five translation units (round 5; one 4 300-line file until then), along the seams of the work:
+// The engine is six translation units (round 5; one 4 300-line file until then), along the seams of the work:
 //   fw_engine_mem.cpp    device / pinned memory of a context, exact counts, the error words of the update kernels
 //   fw_engine_paths.cpp  which update path a particle type is on (FIFO ring / range ring / small / compacting): the transitions
-//                        between them with live particles, the capacity policy, the tile table of the compacting launch
+//                        between them with live particles, the capacity policy, the tile table of the compacting launch and
+//                        the workgroup table of the range launch
 //   fw_engine_build.cpp  sync_spawner_data (core.rs:343-365): descriptors -> device tables of one spawner, and back
-//   fw_engine_step.cpp   fw_step: lifetime windows, emission clocks, cohort replay, launch assembly
+//   fw_engine_step.cpp   fw_step and the plan of a frame: mode exits, lifetime windows, emission clocks, ring-op routing, the
+//                        tile table -- everything that can still be rolled back
+//   fw_engine_launch.cpp the enqueue of a planned frame (FwFrame): op tables, cohort replay, every launch, the frame's bookkeeping
 //   fw_engine_api.cpp    every other entry point of include/firework_hip.h (+ the debug hooks)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -446,7 +449,7 @@ using namespace fwh;
 
 // The Global ops of one emission index: a growable array that owns its storage -- or, in a frame that will most likely hand the
 // kernels an op TABLE (small types: fw_k_update_small reads its ops from pinned host memory), writes straight into the pinned
-// parameter slot the kernels will read (fw_step: `pre_slot`): 96 bytes per emitter that are written once instead of written,
+// parameter slot the kernels will read (FwFrame::pre_slot): 96 bytes per emitter that are written once instead of written,
 // read and written again.
 struct OpList {
     FwOp *p = nullptr;
@@ -572,8 +575,7 @@ struct fw_ctx {
     bool consumed_pending[kParamRing] = {};
     // Global-only frames with more ops than fit the kernel arguments: the kernel reads the op table straight from the
     // pinned ring slot (no copy, no events); a slot is free again once the launch after its frame has started, which
-    // that launch reports through a pinned word (FwUpdateArgs::done_tag).  FW_OPS_ZEROCOPY=0: staged copy + events.
-    bool ops_zerocopy = true;
+    // that launch reports through a pinned word (FwUpdateArgs::done_tag).
     unsigned long long *h_done = nullptr;      // pinned; written by workgroup 0 of every update launch
     unsigned long long *h_err = nullptr;       // pinned; FwGlobals::err_host (h_done + 4: the same allocation); [1]: the device's
                                                // error flags are set (fw_flag)
@@ -634,7 +636,6 @@ struct fw_ctx {
     float tf_prev_theta = 0.0f; // theta the PREVIOUS forecast frame's lists were made for (0: it made none)
     uint64_t tf_frames = 0;     // frames that ran fw_k_fc_resolve + the streaming schedule instead of the look-back
     bool use_static_new = true;  // static output slots for new particles when all of them survive (FW_STATIC_NEW)
-    uint32_t snap_every = kSnapEvery;  // frames between live-count snapshots (FW_SNAP_EVERY)
     bool use_stream = true;    // FW_STREAM=0: forecast frames keep the count-park-store kernel (A/B)
     // AABB fused into the update (fw_ctx_track_aabbs): per-tile boxes of the last update, valid while nothing touched
     // the state or the tile table since
@@ -809,7 +810,6 @@ struct fw_ctx {
     // costs 1-2 % where everything fits the cache, and gain from ~300 MB on (-10..16 % at 480-650 MB))
     uint64_t nt_wo_bytes = 280ull << 20, nt_wo_bytes_range = 64ull << 20;
     unsigned long long *d_rts = nullptr;  // FW_DEBUG & 8: per-workgroup timestamps of the last range launch
-    bool range_idle_last = true;   // FW_RANGE_IDLE_LAST=0: provisioned-but-idle workgroups stay next to their segment's active ones
     std::vector<uint32_t> range_scratch;
     size_t rparam_bytes = 0;
     uint64_t rslot_frame[kParamRing] = {};    // frame that last used the slot (+1; 0 = free)
@@ -893,6 +893,91 @@ fw_status dev_reserve(fw_ctx *ctx, DevArray<T> &a, size_t need, size_t used) {
     return FW_OK;
 }
 
+// The epoch of frame f: the tag of every word its launches publish (snapshot rows, cohort reports, forecast sums) -- 30 bits, never 0
+inline uint32_t frame_epoch(uint64_t f) {
+    const uint32_t e = (uint32_t)((f + 1) & 0x3FFFFFFFu);
+    return e ? e : 1u;
+}
+
+// Cohort reports (SegHost::h_report): the update of frame f leaves {epoch, size of the cohort it added} in row f % kReportRing.
+inline bool report_landed(const SegHost &S, uint64_t f) {
+    const volatile unsigned long long *row = S.h_report + (f % kReportRing);
+    return (uint32_t)(*row >> 32) == frame_epoch(f);
+}
+// ... spins a while for the row; false: still missing (what a wait for the stream costs, and what a row missing after it means,
+// is the caller's to decide)
+inline bool wait_report(const SegHost &S, uint64_t f) {
+    const volatile unsigned long long *row = S.h_report + (f % kReportRing);
+    const uint32_t ep = frame_epoch(f);
+    for (int spin = 0; (uint32_t)(*row >> 32) != ep && spin < 100000; spin++) __builtin_ia32_pause();
+    return (uint32_t)(*row >> 32) == ep;
+}
+
+// age of a particle born in frame f before this frame's update (fw_ctx::birth_age: one entry per frame, contiguous)
+inline float birth_age_before(const fw_ctx *ctx, uint64_t f) {
+    if (ctx->birth_age.empty() || f < ctx->birth_age.front().frame) return INFINITY;  // (long graduated)
+    const size_t i = (size_t)(f - ctx->birth_age.front().frame);
+    return i < ctx->birth_age.size() ? ctx->birth_age[i].age : 0.0f;  // this frame's own cohort: born with age 0
+}
+
+struct OpHdr {  // FwUpdateArgs::seg_op_first: per segment {first op, one past its last, particles they spawn in all, 0}
+    uint32_t o0, o1, n, pad;
+};
+
+// One frame of fw_step, on the stack: what its plan (fw_engine_step.cpp) hands its enqueue (fw_engine_launch.cpp), and what the
+// phases of the enqueue hand each other.  The plan can still be rolled back; nothing of the enqueue can.
+struct FwFrame {
+    float dt = 0.f;
+    uint32_t dt_bits = 0;
+    uint32_t p = 0;  // parity of the frame's input buffers
+    uint32_t n_seg = 0, total_tiles = 0;
+    bool new_static = false;  // cleared by any Global op whose particles might not survive this step
+    // (noted by the first pass over the segments: whether a particle type collides, whether a compacting segment has an
+    // instance buffer attached, and what decides the tile size of the ring launches)
+    bool any_coll = false, any_inst_general = false;
+    struct {
+        uint64_t fifo_parts = 0, range_parts = 0;
+        bool fifo_dev = false, fifo_coll = false, fifo_inst = false, range_dev = false, range_coll = false, range_inst = false;
+    } ring_stats;
+    // the op table the spawner loop writes in place, in a parameter slot taken before it (fw_engine_step.cpp: take_op_slot)
+    int pre_slot = -1;
+    OpHdr *pre_hdr = nullptr;
+    size_t pre_tracked = 0;  // ops of levels[0].g whose headers are up to date
+    bool pre_hdr_ok = false;
+    size_t n_g = 0, n_n = 0;  // the frame's Global / Nested ops
+    bool nested_frame = false;  // some emission level holds a Nested op
+    bool fuse = false;          // ... and they all run inside the FIFO launch (plan_fuse)
+    FwNestOp fuse_plan[FW_FIFO_NEST_MAX];
+    uint32_t n_fuse = 0;
+    int frame_mode = FW_MODE_FUSED;
+    bool legacy = false;    // the separate spawn / nest passes run
+    bool fc_frame = false;  // the general launch leaves a survivor forecast for the next frame
+    FwUpdateArgs a{};
+    FwInlineOps inl;
+    int spawn_form = FW_SPAWN_NONE;
+    int slot = -1;  // the parameter slot the main stream's launches read, recycled by an event at the end of the frame
+    // the op table of the small launch (fw_k_update_small): the frame's table in Global-only frames, one of its own in frames that
+    // run the separate passes
+    const uint4 *small_hdr = nullptr;
+    const FwOp *small_ops = nullptr;
+    int small_tslot = -1;  // ... the parameter slot it lives in, in the latter case
+    int snap = -1;         // the snapshot row the frame's launches fill (-1: none)
+    bool timed = false;    // a launch of the frame carries a timing pair
+    bool fifo_launched = false, range_launched = false, small_launched = false;
+    std::chrono::steady_clock::time_point prof_t;
+    // FW_HOST_PROF: the time since the previous point goes to column i
+    void prof(fw_ctx *ctx, int i) {
+        if (!ctx->host_prof) return;
+        const auto now = std::chrono::steady_clock::now();
+        if (ctx->frame < ctx->host_prof_skip) {
+            prof_t = now;
+            return;
+        }
+        ctx->prof_ns[i] += std::chrono::duration<double, std::nano>(now - prof_t).count();
+        prof_t = now;
+    }
+};
+
 // ---- shared functions (definitions: see the list of translation units above)
 fw_status sync(fw_ctx *ctx);
 fw_status join_side(fw_ctx *ctx);
@@ -903,6 +988,10 @@ fw_status ensure_tile_arrays(fw_ctx *ctx);
 fw_status ensure_range_arrays(fw_ctx *ctx);
 uint32_t ring_head_exact(const SegHost &S, uint32_t count);
 fw_status ensure_param_ring(fw_ctx *ctx, size_t bytes);
+fw_status wait_slot_free(fw_ctx *ctx, uint64_t &tag);
+fw_status acquire_slot(fw_ctx *ctx, int *out);
+fw_status ensure_ring(fw_ctx *ctx, FwFrame &fr, size_t bytes);
+fw_status enqueue_frame(fw_ctx *ctx, FwFrame &fr);
 fw_status upload_seg(fw_ctx *ctx, uint32_t si);
 fw_status alloc_seg_buffers(fw_ctx *ctx, SegHost &s, uint32_t capacity, bool want_destroyed);
 fw_status refresh_rold(fw_ctx *ctx);
@@ -937,6 +1026,7 @@ uint32_t pad4(uint32_t n);
 fw_status build_spawner(fw_ctx *ctx, int h, const fw_spawner_desc *d, const std::vector<uint64_t> *carry_serial);
 fw_status release_spawner_segments(fw_ctx *ctx, SpawnerHost &sp);
 fw_status update_tile_table(fw_ctx *ctx);
+fw_status upload_range_table(fw_ctx *ctx, uint32_t n_seg);
 bool poll_device_error(fw_ctx *ctx);
 fw_status poisoned_status(fw_ctx *ctx);
 fw_status poison_segment(fw_ctx *ctx, uint32_t si, const std::string &what);

@@ -201,7 +201,7 @@ fw_status build_spawner(fw_ctx *ctx, int h, const fw_spawner_desc *d, const std:
         dt.o_bc_v = put(T.base.values, 4 * T.base.n);
         dt.o_em_t = put(T.emis.times, pad4(T.emis.n));
         dt.o_em_v = put(T.emis.values, 4 * T.emis.n);
-        if (keys.size() > 0x3FFFFFFFu) return fail(ctx, FW_EINVAL, "curve keys exceed 2^30 floats");
+        if (keys.size() >= (1u << 30)) return fail(ctx, FW_EINVAL, "curve keys exceed 2^30 floats");
         const bool bigkeys = keys.size() > FW_KEYS_MAX;  // beyond the LDS staging area of the streaming kernels
         uint32_t type_idx;
         if (!ctx->free_types.empty()) {

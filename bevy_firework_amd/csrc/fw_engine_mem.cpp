@@ -251,6 +251,31 @@ fw_status ensure_param_ring(fw_ctx *ctx, size_t bytes) {
     return FW_OK;
 }
 
+// A parameter slot the kernels read in place is tagged with the frame that used it last (+1; 0 = free): free once a launch AFTER
+// that frame has started, which the pinned "frame started" word (h_done) tells
+fw_status wait_slot_free(fw_ctx *ctx, uint64_t &tag) {
+    if (!tag) return FW_OK;
+    const volatile unsigned long long *done = ctx->h_done;
+    for (int spin = 0; *done < tag && spin < 200000; spin++) __builtin_ia32_pause();
+    if (*done < tag) FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    tag = 0;
+    return FW_OK;
+}
+
+// A parameter slot of the ring (pinned host memory the kernels read in place, or stage from): free once the frame that used
+// it last has been consumed.
+fw_status acquire_slot(fw_ctx *ctx, int *out) {
+    const int slot = (int)(ctx->ring_seq++ % kParamRing);
+    if (ctx->consumed_pending[slot]) {
+        FW_HIP(ctx, hipEventSynchronize(ctx->ev_consumed[slot]));
+        ctx->consumed_pending[slot] = false;
+    }
+    fw_status st = wait_slot_free(ctx, ctx->slot_frame[slot]);  // (zero-copy use)
+    if (st) return st;
+    *out = slot;
+    return FW_OK;
+}
+
 fw_status upload_seg(fw_ctx *ctx, uint32_t si) {
     const SegHost &s = ctx->segs[si];
     FwSeg d{};

@@ -1,4 +1,4 @@
-// fw_engine_paths.cpp -- which update path a particle type is on: transitions with live particles, capacity policy, the tile table, live-count snapshots
+// fw_engine_paths.cpp -- which update path a particle type is on: transitions with live particles, capacity policy, the tile and range tables, live-count snapshots
 // (host engine of libfirework_hip.so: fw_engine.h lists its translation units; there is no CPU simulation path in this library)
 #include "fw_engine.h"
 
@@ -473,6 +473,97 @@ fw_status update_tile_table(fw_ctx *ctx) {
                                    ctx->stream));
     FW_HIP(ctx, hipEventRecord(ctx->ev_tab[slot], ctx->stream));
     ctx->tab_pending[slot] = true;
+    return FW_OK;
+}
+
+// The workgroup table of the range launch (fw_ctx::h_rdesc -> d_rdesc), from the roles each range segment provides for
+// (SegHost::r_old / r_new / r_young).
+// Workgroup order of a segment: its OLD workgroups (k ascending: whoever an old tile waits for has a lower workgroup
+// index), then its NEW ones, then the YOUNG ones; segment after segment, so the latency-bound old tiles of one
+// segment overlap the streaming of its neighbours.  A segment with many NEW workgroups (one large emitter: a
+// thousand of them, each ~5x the arithmetic of a YOUNG one and no memory traffic to speak of) gets them spread
+// over the first three quarters of its YOUNG ones instead of as a block: 374-384 -> 364-375 us at 1 x 16M,
+// nothing elsewhere (profiles/r03/range_spread_new.txt).  (Old and young workgroups interleaved within a segment --
+// so that a context with ONE large segment would not start with a front of old tiles -- was measured: 381 -> 384 us
+// at 1 x 16M, 96 -> 100 us at 512 x 8192: no.)  Look-back words are indexed per segment (old_first + k).
+fw_status upload_range_table(fw_ctx *ctx, uint32_t n_seg) {
+    if (ctx->rtab_pending) {  // (one staging buffer: the previous upload must have left it)
+        FW_HIP(ctx, hipEventSynchronize(ctx->ev_rtab));
+        ctx->rtab_pending = false;
+    }
+    size_t t = 0;
+    bool ok = true;
+    auto put = [&](uint32_t si, uint32_t role, uint32_t k) {
+        if (t >= ctx->rdesc_cap) {
+            ok = false;
+            return;
+        }
+        const SegHost &S = ctx->segs[si];
+        FwRangeDesc &D = ctx->h_rdesc[t++];
+        D.seg = si, D.role_k = (role << 30) | k, D.old_first = S.r_status_base;
+        D.type_idx = S.type_idx | (S.nospin ? FW_TYPE_IDX_NOSPIN : 0u) | ((S.derived && S.inst == nullptr) ? FW_TYPE_IDX_NOLIFE : 0u);
+        D.keys_off = S.keys_off, D.keys_len = S.keys_len, D.n_old = S.r_old, D.pad = 0;
+    };
+    // Workgroups that are provisioned but probably idle -- the spares of every role, and the upper part of the OLD range
+    // (its bound counts everybody older than lifetime.min as alive) -- go to the END of the table, behind every
+    // segment's probably-active ones: an idle workgroup still holds a slot for ~2.5 us (descriptor, record, count),
+    // and there it does so while the launch drains and slots are free anyway.  An OLD tile stays behind the lower
+    // tiles of its segment, so the look-back order holds; a "probably idle" workgroup that does have work simply
+    // does it there.
+    auto main_old = [](const SegHost &S) { return std::min(S.r_old, std::max(1u, (S.r_need[0] * 5u + 7u) / 8u)); };
+    auto main_new = [](const SegHost &S) { return std::min(S.r_new, S.r_need[1]); };
+    auto main_young = [](const SegHost &S) { return std::min(S.r_young, S.r_need[2]); };
+    auto put_old = [&](uint32_t si) {
+        const uint32_t n = main_old(ctx->segs[si]);
+        for (uint32_t k = 0; k < n && ok; k++) put(si, FW_RANGE_OLD, k);
+    };
+    auto put_rest = [&](uint32_t si) {
+        const SegHost &S = ctx->segs[si];
+        const uint32_t n_new = main_new(S), n_young = main_young(S);
+        if (!ctx->range_spread_new || n_new <= 8) {
+            for (uint32_t k = 0; k < n_new && ok; k++) put(si, FW_RANGE_NEW, k);
+            for (uint32_t k = 0; k < n_young && ok; k++) put(si, FW_RANGE_YOUNG, k);
+        } else {  // many NEW workgroups (one large segment): spread over the first three quarters of the YOUNG ones
+            const uint64_t span = (uint64_t)n_new + (uint64_t)n_young * 3 / 4;
+            uint32_t kn = 0, ky = 0;
+            for (uint64_t i = 0; i < span && ok; i++) {
+                if (kn < n_new && (uint64_t)kn * span / n_new <= i) put(si, FW_RANGE_NEW, kn++);
+                else if (ky < n_young) put(si, FW_RANGE_YOUNG, ky++);
+            }
+            while (kn < n_new && ok) put(si, FW_RANGE_NEW, kn++);
+            while (ky < n_young && ok) put(si, FW_RANGE_YOUNG, ky++);
+        }
+    };
+    auto put_tail = [&](uint32_t si) {
+        const SegHost &S = ctx->segs[si];
+        for (uint32_t k = main_old(S); k < S.r_old && ok; k++) put(si, FW_RANGE_OLD, k);
+        for (uint32_t k = main_new(S); k < S.r_new && ok; k++) put(si, FW_RANGE_NEW, k);
+        for (uint32_t k = main_young(S); k < S.r_young && ok; k++) put(si, FW_RANGE_YOUNG, k);
+    };
+    auto &rs = ctx->range_scratch;  // the range segments, in segment order
+    rs.clear();
+    uint32_t status_base = 0;
+    for (uint32_t si = 0; si < n_seg; si++) {
+        SegHost &S = ctx->segs[si];
+        if (!S.in_use || !S.range) continue;
+        S.r_status_base = status_base, status_base += S.r_old;
+        rs.push_back(si);
+    }
+    // (the OLD workgroups of a segment dispatched n segments ahead of its other ones: measured, no gain --
+    // profiles/r03/range_old_ahead.txt)
+    const size_t nr = rs.size();
+    // (XCD-aware order -- the runs of eight consecutive segments interleaved entry by entry, so that the workgroups of one
+    // segment share an XCD and its L2 -- was built and measured in round 4: nothing at one GPU's share of configs[4]
+    // (86.4 against 86.5 us), 2.5 % slower at configs[2]: profiles/r04/range_xcd_order_ab.txt)
+    for (size_t i = 0; i < nr && ok; i++) put_old(rs[i]), put_rest(rs[i]);
+    for (size_t i = 0; i < nr && ok; i++) put_tail(rs[i]);
+    if (!ok) return poison_segment(ctx, kNoSeg, "range table overflow");
+    ctx->r_total = (uint32_t)t;
+    if (t) FW_HIP(ctx, hipMemcpyAsync(ctx->d_rdesc, ctx->h_rdesc, t * sizeof(FwRangeDesc), hipMemcpyHostToDevice, ctx->stream));
+    FW_HIP(ctx, hipEventRecord(ctx->ev_rtab, ctx->stream));
+    ctx->rtab_pending = true;
+    ctx->r_force = false;
+    ctx->r_uploads++;
     return FW_OK;
 }
 
