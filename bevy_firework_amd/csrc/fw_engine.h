@@ -58,6 +58,89 @@ inline hipError_t fw_memset_done(void *p, int v, size_t bytes) {
     return e;
 }
 
+// ---- owning handles of the HIP resources a context holds.  Move-only; each releases what it holds when it is reset, assigned
+// or destroyed, with the call that matches how it was allocated.  They convert to the raw handle, which is what the kernels,
+// the launches and FwGlobals see.  None of them reads the environment or the device: a buffer gets memory through alloc_buf /
+// grow_buf only (below fw_ctx).
+enum class Mem : uint8_t {
+    device,  // hipMalloc
+    fine,    // hipExtMallocWithFlags(hipDeviceMallocFinegrained): device memory the host writes through the large BAR
+    pinned,  // hipHostMalloc
+};
+
+template <typename T>
+class HipBuf {
+public:
+    HipBuf() : n_(0), kind_(0) {}
+    HipBuf(HipBuf &&o) noexcept : p_(o.p_), n_(o.n_), kind_(o.kind_) { o.p_ = nullptr, o.n_ = 0; }
+    HipBuf &operator=(HipBuf &&o) noexcept {
+        if (this != &o) reset(), p_ = o.p_, n_ = o.n_, kind_ = o.kind_, o.p_ = nullptr, o.n_ = 0;
+        return *this;
+    }
+    ~HipBuf() { reset(); }
+    operator T *() const { return p_; }
+    T *get() const { return p_; }
+    size_t cap() const { return n_; }  // elements
+    void reset() {
+        if (p_) (void)((Mem)kind_ == Mem::pinned ? hipHostFree(p_) : hipFree(p_));
+        p_ = nullptr, n_ = 0;
+    }
+    // (what alloc_buf hands over: memory of n elements allocated as `kind`)
+    void adopt(void *p, size_t n, Mem kind) { reset(), p_ = static_cast<T *>(p), n_ = n, kind_ = (size_t)kind; }
+
+private:
+    T *p_ = nullptr;
+    size_t n_ : 62, kind_ : 2;  // (16 bytes: SegHost holds three)
+};
+
+class HipEvent {
+public:
+    HipEvent() = default;
+    HipEvent(HipEvent &&o) noexcept : e_(o.e_) { o.e_ = nullptr; }
+    HipEvent &operator=(HipEvent &&o) noexcept {
+        if (this != &o) reset(), e_ = o.e_, o.e_ = nullptr;
+        return *this;
+    }
+    ~HipEvent() { reset(); }
+    operator hipEvent_t() const { return e_; }
+    hipError_t create(unsigned flags = hipEventDisableTiming) {
+        reset();
+        return hipEventCreateWithFlags(&e_, flags);
+    }
+    void reset() {
+        if (e_) (void)hipEventDestroy(e_);
+        e_ = nullptr;
+    }
+
+private:
+    hipEvent_t e_ = nullptr;
+};
+
+// a stream the context created (destroyed with it) or the caller's (fw_ctx_create(.., stream, ..): never destroyed here)
+class HipStream {
+public:
+    HipStream() = default;
+    HipStream(const HipStream &) = delete;
+    HipStream &operator=(const HipStream &) = delete;
+    ~HipStream() { reset(); }
+    operator hipStream_t() const { return s_; }
+    bool owned() const { return own_; }
+    hipError_t create() {
+        reset();
+        own_ = true;
+        return hipStreamCreateWithFlags(&s_, hipStreamNonBlocking);
+    }
+    void borrow(hipStream_t s) { reset(), s_ = s; }
+    void reset() {
+        if (s_ && own_) (void)hipStreamDestroy(s_);
+        s_ = nullptr, own_ = false;
+    }
+
+private:
+    hipStream_t s_ = nullptr;
+    bool own_ = false;
+};
+
 constexpr int kParamRing = 8;    // per-frame parameter buffers in flight
 #ifndef FW_BAR_PARAM_KB
 #define FW_BAR_PARAM_KB 64
@@ -263,6 +346,14 @@ struct Ring {
     }
 };
 
+// The particle memory of a segment, as alloc_seg_buffers makes it: ONE allocation (a ring, updated in place: buf[0] == buf[1]; two
+// buffers otherwise) and the destroyed-record buffer.  Held by the caller until nothing else can fail, then handed to SegHost::take.
+struct SegBufs {
+    HipBuf<char> mem, destroyed;
+    char *buf[2] = {nullptr, nullptr};  // (views into mem)
+    uint32_t capacity = 0;
+};
+
 struct alignas(64) SegHost {
     // Lifetime window: a particle is destroyed by the update in which age >= lifetime (core.rs:590-592), and
     // lifetime <= life_bound, so everything alive was spawned less than life_bound of simulated time ago.  The sum of
@@ -312,8 +403,8 @@ struct alignas(64) SegHost {
     uint32_t keys_cap = 0;                // ... and the floats reserved for it (returned to fw_ctx::free_keys with the type)
     bool bigkeys = false;                 // more keys than the streaming kernels stage in LDS (FW_KEYS_MAX floats)
     std::vector<int32_t> lplane_emission;  // [n_lplanes] the emission entry each last_emitted_age plane belongs to
-    char *buf[2] = {nullptr, nullptr};
-    char *destroyed = nullptr;
+    char *buf[2] = {nullptr, nullptr};     // (views into `mem`, at the end of the record)
+    HipBuf<char> destroyed;                // the destroyed records
     uint32_t inst_cap = 0;
     // colours of the type at age 0: what both colour planes are filled with when the buffers are allocated, so that a
     // constant gradient's plane never has to be written by the update (FwOutWin::wr5 / wr6)
@@ -344,7 +435,7 @@ struct alignas(64) SegHost {
     // their first update (FwFifoSeg::mat).  fifo_dev: the type receives Nested children -- its live count is known to the
     // device only, and the size of each frame's cohort reaches the host through a pinned ring (h_report[frame %
     // kReportRing] = {epoch, added}) long before the host needs it: when the cohort's age reaches the lifetime.
-    unsigned long long *h_report = nullptr;
+    HipBuf<unsigned long long> h_report;  // (pinned)
     // Range ring (fw_kernels.h: FwRangeRec): a type whose lifetime is a RANGE, Global emission only, no collisions, in a
     // spawner without Nested entries.  ONE buffer (buf[0] == buf[1]) used as a ring: [old survivors | young]; the young
     // part -- slot of its first particle, its size, its spawn cohorts -- is host-known exactly (the host made every spawn
@@ -414,6 +505,12 @@ struct alignas(64) SegHost {
     // where the lifetime of particle i is when the type cannot turn: a plane index (compacting / range segments), or
     // 0xFFFFFFFF = the one value fifo_life (a FIFO ring)
     uint32_t life_plane() const { return (nospin && !fifo) ? n_lplanes : 0xFFFFFFFFu; }
+    HipBuf<char> mem;  // the particle allocation (SegBufs; no frame reads it)
+    // the segment's particle memory becomes `b` (what it held is released)
+    void take(SegBufs &&b) {
+        mem = std::move(b.mem), destroyed = std::move(b.destroyed);
+        buf[0] = b.buf[0], buf[1] = b.buf[1], capacity = b.capacity;
+    }
 };
 
 struct alignas(64) SpawnerHost {
@@ -436,12 +533,6 @@ struct alignas(64) SpawnerHost {
     int32_t starts_enabled = 1;
     std::vector<TypeHost> types;
     std::vector<uint32_t> seg;  // per type
-};
-
-template <typename T>
-struct DevArray {
-    T *d = nullptr;
-    size_t cap = 0;
 };
 
 }  // namespace fwh
@@ -504,8 +595,7 @@ struct fw_ctx {
     // device staging of the record-format copies (read_particles / write_particles / pack_instances): ONE allocation that
     // only ever grows, instead of a hipMalloc + hipFree pair per call (each a device-wide synchronisation and an address-
     // space change; profiles/r02/shared_gpu.txt)
-    void *d_stage = nullptr;
-    size_t stage_bytes = 0;
+    HipBuf<char> d_stage;
     bool seg_kind_changed = false;       // a ring left its mode inside the current fw_step (realloc_segment)
     bool derive_ready_any = false;       // some SegHost::derive_ready is set
     // undo log of fw_step's host half: spawn_particles is all-or-nothing per frame in the reference, so a frame that
@@ -524,7 +614,7 @@ struct fw_ctx {
     std::vector<SpUndo> undo_sp;
     int device = 0;
     uint32_t seed = 0;
-    hipStream_t stream = nullptr, copy_stream = nullptr;
+    HipStream stream, copy_stream;
     // Rings next to compacting segments: the ring launch and the general launch of a frame touch disjoint segments, so the
     // ring launch goes to a stream of its own and the two run concurrently (in one stream the second launch waits for the
     // first to drain: 1M ring particles + one small compacting emitter cost 39.8 us per frame, 29.4 with everything on the
@@ -532,13 +622,12 @@ struct fw_ctx {
     // work on it) looks at ring data -- no event in a steady-state frame.  Not used while a ring has an attached instance
     // buffer, belongs to a spawner with Nested entries (fw_k_spawn / fw_k_nest on the main stream feed it) or a live-count
     // ring is registered.  FW_FIFO_STREAM=0: everything on the one stream.
-    hipStream_t fifo_stream = nullptr;
-    hipEvent_t ev_side = nullptr, ev_main = nullptr;
+    HipStream fifo_stream;
+    HipEvent ev_side, ev_main;
     bool use_fifo_stream = true;
     bool side_dirty = false;      // ring launches on the side stream that the main stream has not waited for
     bool fifo_last_side = false;  // where the previous frame's ring launch went
     bool main_reads_ring = false; // work enqueued on the main stream since then reads ring data (must finish first)
-    bool own_stream = false;
     std::string err;
     int update_mode = FW_MODE_FUSED;
     uint32_t spin_limit = 1u << 16;
@@ -555,28 +644,37 @@ struct fw_ctx {
     size_t keys_end = 0;                                      // floats handed out so far
     std::vector<std::pair<uint32_t, uint32_t>> free_keys;     // {offset, length} of windows of released types
 
+    // the kernels' view of the context: its pointers are views of the owners below (and of d_segs .. d_colliders), each written
+    // where its owner is (re)allocated
     FwGlobals g{};
-    DevArray<FwSeg> d_segs;
-    DevArray<FwType> d_types;
-    DevArray<FwTypeColl> d_type_coll;
-    DevArray<float> d_keys;
-    DevArray<FwEmit> d_emits;
-    DevArray<unsigned long long> d_emit_serial;
-    DevArray<uint32_t> d_nest_start;             // FwGlobals::nest_start: START tickets of the Nested entries (one per emit slot)
+    struct {
+        HipBuf<uint32_t> count, spawned, appended, rold;  // [2][max_seg]
+        HipBuf<uint32_t> ndestroyed, range_ticket;        // [max_seg]
+        HipBuf<uint32_t> tile_cnt, tile_off, err;
+        HipBuf<unsigned long long> tile_status, dbg_ts, nest_status, nest_ticket, stats;
+        HipBuf<float> tile_box;
+    } gm;
+    HipBuf<FwSeg> d_segs;
+    HipBuf<FwType> d_types;
+    HipBuf<FwTypeColl> d_type_coll;
+    HipBuf<float> d_keys;
+    HipBuf<FwEmit> d_emits;
+    HipBuf<unsigned long long> d_emit_serial;
+    HipBuf<uint32_t> d_nest_start;               // FwGlobals::nest_start: START tickets of the Nested entries (one per emit slot)
     std::vector<uint32_t> nest_ticket_base;      // ... and the value each has at the start of the next launch that uses it
     uint32_t max_seg = 0;
-    size_t tiles_cap = 0, nest_tiles_cap = 0, nest_ops_cap = 0;
+    size_t tiles_cap = 0;
 
     // per-frame parameter ring (pinned host + device copies)
     size_t param_bytes = 0;
-    char *h_param[kParamRing] = {};
-    char *d_param[kParamRing] = {};
-    hipEvent_t ev_copied[kParamRing] = {}, ev_consumed[kParamRing] = {};
+    HipBuf<char> h_param[kParamRing];  // (pinned)
+    HipBuf<char> d_param[kParamRing];
+    HipEvent ev_copied[kParamRing], ev_consumed[kParamRing];
     bool consumed_pending[kParamRing] = {};
     // Global-only frames with more ops than fit the kernel arguments: the kernel reads the op table straight from the
     // pinned ring slot (no copy, no events); a slot is free again once the launch after its frame has started, which
     // that launch reports through a pinned word (FwUpdateArgs::done_tag).
-    unsigned long long *h_done = nullptr;      // pinned; written by workgroup 0 of every update launch
+    HipBuf<unsigned long long> h_done;         // pinned; written by workgroup 0 of every update launch
     unsigned long long *h_err = nullptr;       // pinned; FwGlobals::err_host (h_done + 4: the same allocation); [1]: the device's
                                                // error flags are set (fw_flag)
     std::string poison_msg;                    // what poll_device_error saw
@@ -586,24 +684,24 @@ struct fw_ctx {
     // live-count snapshots written by the update kernel into pinned host memory
     // Live-count snapshots: the update kernel stores {epoch, count} of each segment into a pinned row with one 8-byte
     // store; the host recognises a finished row by its tag -- no event, no packet between launches.
-    unsigned long long *h_snap = nullptr;  // [kSnapRing][max_seg]
+    HipBuf<unsigned long long> h_snap;  // [kSnapRing][max_seg] (pinned)
     bool snap_pending[kSnapRing] = {};
     bool snap_seen[kSnapRing] = {};
     uint32_t snap_epoch[kSnapRing] = {};
     std::vector<uint64_t> snap_cum[kSnapRing];  // cum_spawn of every segment when the frame was enqueued
 
     // device-resident segment -> tile table
-    uint32_t *d_tile_first = nullptr;
-    size_t tile_first_cap = 0;
+    HipBuf<uint32_t> d_tile_first;
+    size_t tile_first_cap = 0;  // (of d_tile_first, d_tile_keys, h_tab and h_keys)
     std::vector<uint32_t> tiles_dev;
     uint32_t total_tiles_dev = 0;
-    uint32_t *h_tab[kTabRing] = {};
-    uint2 *d_tile_keys = nullptr;  // per segment: {keys_off, keys_len}
-    uint2 *h_keys[kTabRing] = {};
-    uint4 *d_tile_desc = nullptr;  // per tile: {segment, first tile, tile count, 0}
-    uint4 *h_desc[kTabRing] = {};
+    HipBuf<uint32_t> h_tab[kTabRing];  // (pinned staging: h_keys, h_desc too)
+    HipBuf<uint2> d_tile_keys;  // per segment: {keys_off, keys_len}
+    HipBuf<uint2> h_keys[kTabRing];
+    HipBuf<uint4> d_tile_desc;  // per tile: {segment, first tile, tile count, 0}
+    HipBuf<uint4> h_desc[kTabRing];
     size_t tile_desc_cap = 0;
-    hipEvent_t ev_tab[kTabRing] = {};
+    HipEvent ev_tab[kTabRing];
     bool tab_pending[kTabRing] = {};
     uint64_t tab_seq = 0, ring_seq = 0;
     uint32_t vt_rounds = 1;  // new-particle tile size of the current frame (rounds of 256)
@@ -611,8 +709,8 @@ struct fw_ctx {
 
     // survivor forecast sums (update kernels)
     uint32_t fc_sums_prev = 0;    // format of the forecast the last forecast frame produced
-    uint4 *d_fce = nullptr;       // [2][tiles_cap] forecast entries of small segments (double-buffered)
-    unsigned long long *d_fc = nullptr;   // three rotating buffers of forecast sums: S[tiles_cap] | S2[tiles_cap / 64 + 1] | tag
+    HipBuf<uint4> d_fce;          // [2][tiles_cap] forecast entries of small segments (double-buffered)
+    HipBuf<unsigned long long> d_fc;      // three rotating buffers of forecast sums: S[tiles_cap] | S2[tiles_cap / 64 + 1] | tag
     size_t fc_len = 0;          // elements per buffer
     uint64_t fc_seq = 0;        // forecast-producing frames so far (buffer rotation)
     bool fc_dirty = false;      // the tile table changed: clear all three buffers before the next forecast frame
@@ -629,8 +727,8 @@ struct fw_ctx {
     // FW_TF=0 switches it off, FW_TF_MIN_TILES=n (the tests: 0).
     bool use_tf = true;
     uint32_t tf_min_tiles = 768;  // (tools/r06_tf_min_tiles.py: 977 tiles 30.1 -> 22.2 us per frame, 256 tiles 17.0 -> 18.2)
-    uint4 *d_fct = nullptr;     // [2][tiles_cap] headers, double-buffered like d_fce
-    float2 *d_fcl = nullptr;    // [2][tiles_cap][FW_TF_K] (age, lifetime) of the risky survivors
+    HipBuf<uint4> d_fct;        // [2][tiles_cap] headers, double-buffered like d_fce
+    HipBuf<float2> d_fcl;       // [2][tiles_cap][FW_TF_K] (age, lifetime) of the risky survivors
     size_t tf_cap = 0;          // tiles_cap the two arrays were allocated for (0: not yet)
     uint32_t tf_armed = 0;      // frames left in which producers write lists (re-armed whenever dt differs from the last frame's)
     float tf_prev_theta = 0.0f; // theta the PREVIOUS forecast frame's lists were made for (0: it made none)
@@ -731,9 +829,9 @@ struct fw_ctx {
     bool big_dirty = true;
     std::vector<uint32_t> small_list;   // the segments, ascending (rebuilt when small_dirty)
     bool small_dirty = true;
-    uint32_t *d_small = nullptr, *h_small = nullptr;  // device list / pinned staging
-    size_t small_cap = 0;
-    hipEvent_t ev_small = nullptr;
+    HipBuf<uint32_t> d_small, h_small;  // device list / pinned staging
+    size_t small_cap = 0;               // (of both)
+    HipEvent ev_small;
     bool small_pending = false;
     std::vector<FwOp> fifo_ops;  // this frame's Global ops that feed FIFO segments (spawned inside fw_k_update_fifo)
     std::vector<std::pair<uint32_t, FwOp>> range_mat_ops;  // the same for range rings other particles' entries emit from
@@ -779,15 +877,15 @@ struct fw_ctx {
     std::deque<BirthAge> birth_age;  // oldest first; only frames some range ring may still hold young particles of
     float range_life_max = 0.f;      // largest SegHost::range_life_lo in the context
     float range_age_keep = 0.f;      // largest lifetime.max of a range ring that receives Nested children (plus a margin)
-    FwRangeDesc *d_rdesc = nullptr;  // device table: one descriptor per workgroup of the range launch
-    FwRangeDesc *h_rdesc = nullptr;  // pinned staging of it
-    size_t rdesc_cap = 0;
+    HipBuf<FwRangeDesc> d_rdesc;     // device table: one descriptor per workgroup of the range launch
+    HipBuf<FwRangeDesc> h_rdesc;     // pinned staging of it
+    size_t rdesc_cap = 0;            // (of both and d_rstatus)
     uint32_t r_total = 0;            // workgroups of the range launch
     bool r_force = true;             // a range segment was (re)built: re-send the table
-    hipEvent_t ev_rtab = nullptr;
+    HipEvent ev_rtab;
     bool rtab_pending = false;
-    unsigned long long *d_rstatus = nullptr;  // look-back words of the OLD workgroups
-    char *h_rparam[kParamRing] = {};          // per-frame records + ops, written by the host, read by the kernel in place
+    HipBuf<unsigned long long> d_rstatus;     // look-back words of the OLD workgroups
+    HipBuf<char> h_rparam[kParamRing];        // per-frame records + ops, written by the host, read by the kernel in place
     // ... in DEVICE memory the host writes through the large BAR (fine-grained, hipExtMallocWithFlags) when the platform maps it, in
     // pinned host memory otherwise: a workgroup's record is the first thing its loads depend on, and read over the bus it costs
     // every launch ~3 us of dead time (tools/barwrite.hip, profiles/r05/rparam_ab.txt: one sparks.rs emitter 8.9 -> 5.7 us per frame,
@@ -797,7 +895,7 @@ struct fw_ctx {
     // ... and so do op TABLES of at most kBarParamBytes (a few hundred emitters on the compacting / wave-per-type launches: their
     // workgroups read a header and an op each before they can spawn); larger tables stay in pinned memory, written in place
     // (OpList): with thousands of emitters the frame is bound by the host, and write-combining stores cost it more than cached ones
-    char *b_param[kParamRing] = {};
+    HipBuf<char> b_param[kParamRing];
     bool range_spread_new = true;   // FW_RANGE_SPREAD_NEW=0: a segment's NEW workgroups all in front of its YOUNG ones (A/B)
     // An in-place ring launch (FIFO / range) that streams more than nt_bytes uses the fully non-temporal form of its kernel:
     // several times the 256 MiB Infinity Cache, where allocating lines that cannot survive until the next frame only costs.
@@ -809,7 +907,7 @@ struct fw_ctx {
     // (-1..4 % below 250 MB, -10..16 % at 320-425 MB); the FIFO kernel's non-temporal forms carry the generic write mask, which
     // costs 1-2 % where everything fits the cache, and gain from ~300 MB on (-10..16 % at 480-650 MB))
     uint64_t nt_wo_bytes = 280ull << 20, nt_wo_bytes_range = 64ull << 20;
-    unsigned long long *d_rts = nullptr;  // FW_DEBUG & 8: per-workgroup timestamps of the last range launch
+    HipBuf<unsigned long long> d_rts;     // FW_DEBUG & 8: per-workgroup timestamps of the last range launch
     std::vector<uint32_t> range_scratch;
     size_t rparam_bytes = 0;
     uint64_t rslot_frame[kParamRing] = {};    // frame that last used the slot (+1; 0 = free)
@@ -835,7 +933,7 @@ struct fw_ctx {
 
     // kernel timing
     bool timing = false;
-    std::vector<hipEvent_t> tev;
+    std::vector<HipEvent> tev;
     size_t tev_used = 0;
     uint64_t timing_particles_start = 0;
     double tev_overhead_ms = 0;  // duration of an empty hipEvent pair on this stream
@@ -844,20 +942,27 @@ struct fw_ctx {
     uint32_t live_ring_n = 0;
     uint64_t live_ring_frames = 0;            // frames written since the ring was registered
 
-    FwCollider *d_colliders = nullptr;  // device-resident analytic colliders (fw_ctx_set_colliders)
+    HipBuf<FwCollider> d_colliders;     // device-resident analytic colliders (fw_ctx_set_colliders)
     uint32_t n_colliders = 0;
-    size_t coll_cap = 0;                // records the device table holds
     // a new set travels as ONE copy in the context's stream (ordered behind the frames that read the old set, in front of the
     // frames that will read the new one: no synchronisation); the pinned staging is double-buffered
-    FwCollider *h_coll[2] = {nullptr, nullptr};
-    size_t h_coll_cap[2] = {0, 0};
-    hipEvent_t ev_coll[2] = {nullptr, nullptr};
+    HipBuf<FwCollider> h_coll[2];
+    HipEvent ev_coll[2];
     bool coll_pending[2] = {false, false};
     uint64_t coll_seq = 0;
-    float *d_aabb = nullptr;   // 256 partial boxes of the AABB query
-    float *h_aabb = nullptr;   // pinned result {min.xyz, any, max.xyz, -}
-    unsigned long long *d_total = nullptr;
-    uint32_t *d_segids = nullptr;
+    HipBuf<float> d_aabb;      // 256 partial boxes of the AABB query
+    HipBuf<float> h_aabb;      // pinned result {min.xyz, any, max.xyz, -}
+    HipBuf<unsigned long long> d_total;
+    HipBuf<uint32_t> d_segids;
+
+    // `ab` build, FW_FAIL_ALLOC=k: the k-th allocation of the context fails (hipErrorOutOfMemory, no HIP call) -- the failure paths
+    // under test
+    uint64_t fail_alloc = 0, n_alloc = 0;
+
+    fw_ctx() = default;
+    fw_ctx(const fw_ctx &) = delete;
+    fw_ctx &operator=(const fw_ctx &) = delete;
+    ~fw_ctx();  // waits for the context's streams; the members then release themselves
 };
 
 namespace fwh {
@@ -879,17 +984,51 @@ inline fw_status fail(fw_ctx *ctx, fw_status s, const std::string &msg) {
 
 inline uint32_t round_up(uint32_t x, uint32_t m) { return (x + m - 1) / m * m; }
 
-template <typename T>
-fw_status dev_reserve(fw_ctx *ctx, DevArray<T> &a, size_t need, size_t used) {
-    if (need <= a.cap) return FW_OK;
-    size_t ncap = std::max<size_t>(need, a.cap * 2 + 64);
-    T *nd = nullptr;
-    FW_HIP(ctx, hipMalloc((void **)&nd, ncap * sizeof(T)));
-    FW_HIP(ctx, fw_memset_done(nd, 0, ncap * sizeof(T)));
-    if (a.d && used) FW_HIP(ctx, hipMemcpy(nd, a.d, used * sizeof(T), hipMemcpyDeviceToDevice));
-    if (a.d) FW_HIP(ctx, hipFree(a.d));
-    a.d = nd;
-    a.cap = ncap;
+// The one allocation call of the engine: `bytes` of `kind` memory (fw_ctx::fail_alloc: the `ab` build's simulated failure).
+inline hipError_t hip_alloc(fw_ctx *ctx, void **p, size_t bytes, Mem kind, const char **call) {
+    *p = nullptr;
+    *call = kind == Mem::device ? "hipMalloc" : kind == Mem::fine ? "hipExtMallocWithFlags" : "hipHostMalloc";
+    if (ctx->fail_alloc && ++ctx->n_alloc == ctx->fail_alloc) {
+        fprintf(stderr, "[fw] FW_FAIL_ALLOC: allocation %llu fails\n", (unsigned long long)ctx->n_alloc);
+        return hipErrorOutOfMemory;
+    }
+    return kind == Mem::device ? hipMalloc(p, bytes)
+           : kind == Mem::fine ? hipExtMallocWithFlags(p, bytes, hipDeviceMallocFinegrained)
+                               : hipHostMalloc(p, bytes, hipHostMallocDefault);
+}
+
+// `b` gets a fresh buffer of n elements of `kind` memory, zeroed on request; what it held is released first.  A failure leaves
+// it empty and returns FW_EHIP with the failing call's text.  `view` (a FwGlobals pointer) follows the buffer either way.
+template <typename T, typename V = T>
+fw_status alloc_buf(fw_ctx *ctx, HipBuf<T> &b, size_t n, Mem kind = Mem::device, bool zero = false, V **view = nullptr) {
+    b.reset();
+    if (view) *view = nullptr;
+    void *p = nullptr;
+    const char *call = "";
+    hipError_t e = hip_alloc(ctx, &p, n * sizeof(T), kind, &call);
+    if (e == hipSuccess) {
+        b.adopt(p, n, kind);
+        if (zero && kind == Mem::device) e = fw_memset_done(p, 0, n * sizeof(T)), call = "hipMemset";
+        if (zero && kind != Mem::device) memset(p, 0, n * sizeof(T));  // (the host writes pinned and BAR memory itself)
+    }
+    if (e != hipSuccess) {
+        b.reset();
+        return fail(ctx, FW_EHIP, std::string(call) + "(" + std::to_string(n * sizeof(T)) + " bytes): " + hipGetErrorString(e));
+    }
+    if (view) *view = b.get();
+    return FW_OK;
+}
+
+// `b` (device memory) moves to a new buffer of n elements, zeroed on request, that starts with its first `used` elements.  A
+// failure leaves it as it was (FW_EHIP with the failing call's text).
+template <typename T, typename V = T>
+fw_status grow_buf(fw_ctx *ctx, HipBuf<T> &b, size_t n, bool zero, size_t used, V **view = nullptr) {
+    HipBuf<T> nb;
+    fw_status st = alloc_buf(ctx, nb, n, Mem::device, zero);
+    if (st) return st;
+    if (used) FW_HIP(ctx, hipMemcpy(nb.get(), b.get(), used * sizeof(T), hipMemcpyDeviceToDevice));
+    b = std::move(nb);
+    if (view) *view = b.get();
     return FW_OK;
 }
 
@@ -993,7 +1132,7 @@ fw_status acquire_slot(fw_ctx *ctx, int *out);
 fw_status ensure_ring(fw_ctx *ctx, FwFrame &fr, size_t bytes);
 fw_status enqueue_frame(fw_ctx *ctx, FwFrame &fr);
 fw_status upload_seg(fw_ctx *ctx, uint32_t si);
-fw_status alloc_seg_buffers(fw_ctx *ctx, SegHost &s, uint32_t capacity, bool want_destroyed);
+fw_status alloc_seg_buffers(fw_ctx *ctx, const SegHost &s, uint32_t capacity, bool ring, bool want_destroyed, SegBufs &out);
 fw_status refresh_rold(fw_ctx *ctx);
 fw_status refresh_counts_exact(fw_ctx *ctx);
 fw_status check_device_errors(fw_ctx *ctx);

@@ -26,6 +26,38 @@ static bool host_maps_writable(const void *p) {
     return ok;
 }
 
+// the streams, events and buffers of a new context (fw_ctx_create: knobs read); a failure leaves them to ~fw_ctx
+static fw_status create_resources(fw_ctx *ctx, hipStream_t stream) {
+    if (stream)
+        ctx->stream.borrow(stream);
+    else
+        FW_HIP(ctx, ctx->stream.create());
+    FW_HIP(ctx, ctx->copy_stream.create());
+    FW_HIP(ctx, ctx->fifo_stream.create());
+    for (HipEvent *ev : {&ctx->ev_side, &ctx->ev_rtab, &ctx->ev_small, &ctx->ev_main}) FW_HIP(ctx, ev->create());
+    for (int i = 0; i < kParamRing; i++) {
+        FW_HIP(ctx, ctx->ev_copied[i].create());
+        FW_HIP(ctx, ctx->ev_consumed[i].create());
+    }
+    for (int i = 0; i < kTabRing; i++) FW_HIP(ctx, ctx->ev_tab[i].create());
+    fw_status st;
+    if ((st = alloc_buf(ctx, ctx->h_done, 8, Mem::pinned, true))) return st;
+    ctx->h_err = ctx->h_done + 4, ctx->g.err_host = ctx->h_err;
+    if ((st = alloc_buf(ctx, ctx->gm.err, 16, Mem::device, true, &ctx->g.err)) ||
+        (st = alloc_buf(ctx, ctx->gm.stats, FW_STAT_SLOTS, Mem::device, true, &ctx->g.stats)) ||
+        (st = alloc_buf(ctx, ctx->d_aabb, 256 * 8)) || (st = alloc_buf(ctx, ctx->d_total, 8)))
+        return st;
+    for (int i = 0; i < kParamRing && ctx->param_bar; i++)
+        if ((st = alloc_buf(ctx, ctx->b_param[i], kBarParamBytes, Mem::fine))) return st;
+    return ensure_max_seg(ctx, 1024);
+}
+
+fw_ctx::~fw_ctx() {
+    // (work in flight may still use what the members release)
+    for (hipStream_t s : {(hipStream_t)stream, (hipStream_t)copy_stream, (hipStream_t)fifo_stream})
+        if (s) (void)hipStreamSynchronize(s);
+}
+
 extern "C" {
 
 
@@ -67,61 +99,25 @@ fw_status fw_ctx_create(int device, uint32_t seed, void *stream, fw_ctx **out) {
     fw_ctx *ctx = new fw_ctx();
     ctx->device = device;
     ctx->seed = seed;
-    {  // fw_ctx::param_bar: device memory the host can write (large BAR) -- asked of the runtime, then tried once
-        int large_bar = 0;
-        void *probe = nullptr;
-        if (hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, device) == hipSuccess && large_bar != 0 &&
-            hipExtMallocWithFlags(&probe, 4096, hipDeviceMallocFinegrained) == hipSuccess) {
-            hipPointerAttribute_t at{};
-            ctx->param_bar = hipPointerGetAttributes(&at, probe) == hipSuccess && at.type == hipMemoryTypeDevice && host_maps_writable(probe);
-            hipFree(probe);
-        }
-        (void)hipGetLastError();
-    }
-    auto bail = [&](const char *what, hipError_t he) {
-        g_create_error = std::string(what) + ": " + hipGetErrorString(he);
-        delete ctx;
-        return FW_EHIP;
-    };
-    if (stream) {
-        ctx->stream = (hipStream_t)stream;
-    } else {
-        if ((e = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)) != hipSuccess)
-            return bail("hipStreamCreate", e);
-        ctx->own_stream = true;
-    }
-    if ((e = hipStreamCreateWithFlags(&ctx->copy_stream, hipStreamNonBlocking)) != hipSuccess)
-        return bail("hipStreamCreate(copy)", e);
-    if ((e = hipStreamCreateWithFlags(&ctx->fifo_stream, hipStreamNonBlocking)) != hipSuccess)
-        return bail("hipStreamCreate(rings)", e);
-    if ((e = hipEventCreateWithFlags(&ctx->ev_side, hipEventDisableTiming)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&ctx->ev_rtab, hipEventDisableTiming)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&ctx->ev_small, hipEventDisableTiming)) != hipSuccess ||
-        (e = hipEventCreateWithFlags(&ctx->ev_main, hipEventDisableTiming)) != hipSuccess)
-        return bail("hipEventCreate", e);
-    for (int i = 0; i < kParamRing; i++) {
-        if ((e = hipEventCreateWithFlags(&ctx->ev_copied[i], hipEventDisableTiming)) != hipSuccess)
-            return bail("hipEventCreate", e);
-        if ((e = hipEventCreateWithFlags(&ctx->ev_consumed[i], hipEventDisableTiming)) != hipSuccess)
-            return bail("hipEventCreate", e);
-    }
-    for (int i = 0; i < kTabRing; i++)
-        if ((e = hipEventCreateWithFlags(&ctx->ev_tab[i], hipEventDisableTiming)) != hipSuccess)
-            return bail("hipEventCreate", e);
-    if ((e = hipHostMalloc((void **)&ctx->h_done, 64, hipHostMallocDefault)) != hipSuccess) return bail("hipHostMalloc", e);
-    *ctx->h_done = 0ull;
-    ctx->h_err = ctx->h_done + 4, ctx->h_err[0] = ctx->h_err[1] = 0ull, ctx->g.err_host = ctx->h_err;
-    if ((e = hipMalloc((void **)&ctx->g.err, 64)) != hipSuccess) return bail("hipMalloc", e);
-    fw_memset_done(ctx->g.err, 0, 64);
-    if ((e = hipMalloc((void **)&ctx->g.stats, FW_STAT_SLOTS * sizeof(unsigned long long))) != hipSuccess) return bail("hipMalloc", e);
-    fw_memset_done(ctx->g.stats, 0, FW_STAT_SLOTS * sizeof(unsigned long long));
-    if ((e = hipMalloc((void **)&ctx->d_aabb, 256 * 8 * sizeof(float))) != hipSuccess) return bail("hipMalloc", e);
-    if ((e = hipMalloc((void **)&ctx->d_total, 64)) != hipSuccess) return bail("hipMalloc", e);
-    ctx->g.seed = seed;
     // A/B and debugging switches (firework_hip_debug.h): read only when FW_ENABLE_KNOBS=1 -- a product process does not change
     // behaviour because of a stray environment variable
     const char *knobs_on = getenv("FW_ENABLE_KNOBS");
     auto getenv = [&](const char *name) -> const char * { return (knobs_on && atoi(knobs_on) != 0) ? ::getenv(name) : nullptr; };
+#ifdef FW_AB
+    if (const char *m = getenv("FW_FAIL_ALLOC")) ctx->fail_alloc = strtoull(m, nullptr, 10);
+#endif
+    {  // fw_ctx::param_bar: device memory the host can write (large BAR) -- asked of the runtime, then tried once
+        int large_bar = 0;
+        HipBuf<char> probe;
+        if (hipDeviceGetAttribute(&large_bar, hipDeviceAttributeIsLargeBar, device) == hipSuccess && large_bar != 0 &&
+            alloc_buf(ctx, probe, 4096, Mem::fine) == FW_OK) {
+            hipPointerAttribute_t at{};
+            ctx->param_bar = hipPointerGetAttributes(&at, probe) == hipSuccess && at.type == hipMemoryTypeDevice && host_maps_writable(probe);
+        }
+        (void)hipGetLastError();
+        ctx->err.clear();  // (no BAR memory is no error)
+    }
+    ctx->g.seed = seed;
     // -- path selectors: every one of them names a path the product takes by itself under some workload; the tests force each
     if (const char *m = getenv("FW_UPDATE_MODE")) ctx->update_mode = !strcmp(m, "split") ? FW_MODE_SPLIT : FW_MODE_FUSED;
     if (const char *m = getenv("FW_FORECAST")) ctx->use_forecast = atoi(m) != 0;
@@ -152,9 +148,6 @@ fw_status fw_ctx_create(int device, uint32_t seed, void *stream, fw_ctx **out) {
     if (const char *m = getenv("FW_WAVE_ALL_MIN")) ctx->wave_all_min = (uint32_t)strtoul(m, nullptr, 10);
     if (const char *m = getenv("FW_HOST_FAST")) ctx->host_fast = atoi(m) != 0;
     if (const char *m = getenv("FW_PARAM_BAR")) ctx->param_bar = ctx->param_bar && atoi(m) != 0;
-    for (int i = 0; i < kParamRing && ctx->param_bar; i++)
-        if ((e = hipExtMallocWithFlags((void **)&ctx->b_param[i], kBarParamBytes, hipDeviceMallocFinegrained)) != hipSuccess)
-            return bail("hipExtMallocWithFlags(op tables)", e);
     if (const char *m = getenv("FW_NT_MB")) ctx->nt_bytes = (uint64_t)atoll(m) << 20;
     if (const char *m = getenv("FW_NT_WO_MB")) ctx->nt_wo_bytes = ctx->nt_wo_bytes_range = (uint64_t)atoll(m) << 20;
 #ifdef FW_AB
@@ -166,7 +159,7 @@ fw_status fw_ctx_create(int device, uint32_t seed, void *stream, fw_ctx **out) {
     ctx->trace = getenv("FW_TRACE") != nullptr;
     if (const char *m = getenv("FW_HOST_PROF")) ctx->host_prof = atoi(m) != 0, ctx->host_prof_skip = atoi(m) > 1 ? (uint64_t)atoi(m) : 0;
 #endif
-    if (ensure_max_seg(ctx, 1024) != FW_OK) {
+    if (create_resources(ctx, (hipStream_t)stream) != FW_OK) {
         g_create_error = ctx->err;
         delete ctx;
         return FW_EHIP;
@@ -177,6 +170,7 @@ fw_status fw_ctx_create(int device, uint32_t seed, void *stream, fw_ctx **out) {
 
 fw_status fw_ctx_destroy(fw_ctx *ctx) {
     if (!ctx) return FW_EINVAL;
+    hipSetDevice(ctx->device);
     if (ctx->host_prof && ctx->prof_frames) {
         static const char *names[10] = {"windows+reset", "spawner loop", "tile table", "commit", "args", "op tables", "launch", "post", "", ""};
         fprintf(stderr, "[fw] host half of fw_step over %llu frames (ns per frame):", (unsigned long long)ctx->prof_frames);
@@ -187,68 +181,6 @@ fw_status fw_ctx_destroy(fw_ctx *ctx) {
                 sizeof(SpawnerHost), (size_t)((const char *)&ctx->spawners.data()->em.one_ - (const char *)ctx->spawners.data()),
                 sizeof(EmissionHost), sizeof(FwOp));
     }
-    hipSetDevice(ctx->device);
-    hipStreamSynchronize(ctx->stream);
-    hipStreamSynchronize(ctx->copy_stream);
-    if (ctx->fifo_stream) hipStreamSynchronize(ctx->fifo_stream);
-    for (auto &S : ctx->segs) {
-        if (S.buf[0]) hipFree(S.buf[0]);
-        if (S.destroyed) hipFree(S.destroyed);
-        if (S.h_report) hipHostFree(S.h_report);
-    }
-    void *frees[] = {ctx->d_type_coll.d, ctx->d_segs.d,       ctx->d_types.d,       ctx->d_keys.d,        ctx->d_emits.d,
-                     ctx->d_emit_serial.d, ctx->d_nest_start.d, ctx->g.range_ticket, ctx->g.count,        ctx->g.spawned,       ctx->g.appended,     ctx->g.rold,
-                     ctx->g.ndestroyed,   ctx->g.tile_cnt,      ctx->g.tile_off,      ctx->g.tile_status,
-                     ctx->g.err,          ctx->g.stats,         ctx->g.nest_status,   ctx->g.nest_ticket,
-                     ctx->d_aabb,         ctx->d_total,         ctx->d_segids,        ctx->g.dbg_ts,
-                     ctx->d_colliders,   ctx->g.tile_box,      ctx->d_stage};
-    for (void *p : frees)
-        if (p) hipFree(p);
-    for (int i = 0; i < kParamRing; i++) {
-        if (ctx->h_param[i]) hipHostFree(ctx->h_param[i]);
-        if (ctx->d_param[i]) hipFree(ctx->d_param[i]);
-        if (ctx->b_param[i]) hipFree(ctx->b_param[i]);
-        hipEventDestroy(ctx->ev_copied[i]);
-        hipEventDestroy(ctx->ev_consumed[i]);
-    }
-    for (int i = 0; i < kTabRing; i++) {
-        hipEventDestroy(ctx->ev_tab[i]);
-        if (ctx->h_tab[i]) hipHostFree(ctx->h_tab[i]);
-        if (ctx->h_desc[i]) hipHostFree(ctx->h_desc[i]);
-    }
-    if (ctx->d_tile_first) hipFree(ctx->d_tile_first);
-    if (ctx->d_tile_desc) hipFree(ctx->d_tile_desc);
-    if (ctx->d_tile_keys) hipFree(ctx->d_tile_keys);
-    for (int i = 0; i < kTabRing; i++)
-        if (ctx->h_keys[i]) hipHostFree(ctx->h_keys[i]);
-    if (ctx->d_fc) hipFree(ctx->d_fc);
-    if (ctx->d_fce) hipFree(ctx->d_fce);
-    if (ctx->d_fct) hipFree(ctx->d_fct);
-    if (ctx->d_fcl) hipFree(ctx->d_fcl);
-    if (ctx->h_snap) hipHostFree(ctx->h_snap);
-    if (ctx->h_aabb) hipHostFree(ctx->h_aabb);
-    if (ctx->h_done) hipHostFree(ctx->h_done);
-    for (hipEvent_t ev : ctx->tev) hipEventDestroy(ev);
-    hipStreamDestroy(ctx->copy_stream);
-    if (ctx->fifo_stream) hipStreamDestroy(ctx->fifo_stream);
-    if (ctx->ev_side) hipEventDestroy(ctx->ev_side);
-    if (ctx->ev_rtab) hipEventDestroy(ctx->ev_rtab);
-    if (ctx->ev_small) hipEventDestroy(ctx->ev_small);
-    if (ctx->d_small) hipFree(ctx->d_small);
-    if (ctx->h_small) hipHostFree(ctx->h_small);
-    for (int i = 0; i < 2; i++) {
-        if (ctx->ev_coll[i]) hipEventDestroy(ctx->ev_coll[i]);
-        if (ctx->h_coll[i]) hipHostFree(ctx->h_coll[i]);
-    }
-    if (ctx->d_rdesc) hipFree(ctx->d_rdesc);
-    if (ctx->h_rdesc) hipHostFree(ctx->h_rdesc);
-    if (ctx->d_rstatus) hipFree(ctx->d_rstatus);
-    if (ctx->d_rts) hipFree(ctx->d_rts);
-    for (int i = 0; i < kParamRing; i++) {
-        if (ctx->h_rparam[i]) ctx->param_bar ? hipFree(ctx->h_rparam[i]) : hipHostFree(ctx->h_rparam[i]);
-    }
-    if (ctx->ev_main) hipEventDestroy(ctx->ev_main);
-    if (ctx->own_stream) hipStreamDestroy(ctx->stream);
     delete ctx;
     return FW_OK;
 }
@@ -275,22 +207,12 @@ fw_status fw_ctx_set_colliders(fw_ctx *ctx, const fw_collider *colliders, uint32
         FW_HIP(ctx, hipEventSynchronize(ctx->ev_coll[slot]));
         ctx->coll_pending[slot] = false;
     }
-    if (!ctx->ev_coll[slot]) FW_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_coll[slot], hipEventDisableTiming));
-    if (n > ctx->h_coll_cap[slot]) {
-        const size_t ncap = std::max<size_t>(64, (size_t)n * 2);
-        if (ctx->h_coll[slot]) FW_HIP(ctx, hipHostFree(ctx->h_coll[slot]));
-        ctx->h_coll[slot] = nullptr, ctx->h_coll_cap[slot] = 0;
-        FW_HIP(ctx, hipHostMalloc((void **)&ctx->h_coll[slot], ncap * sizeof(FwCollider), hipHostMallocDefault));
-        ctx->h_coll_cap[slot] = ncap;
-    }
-    if (n > ctx->coll_cap) {  // a larger world than ever before: the one case that waits (kernels in flight read the old table)
-        fw_status st = sync(ctx);
-        if (st) return st;
-        const size_t ncap = std::max<size_t>(64, (size_t)n * 2);
-        if (ctx->d_colliders) FW_HIP(ctx, hipFree(ctx->d_colliders));
-        ctx->d_colliders = nullptr, ctx->coll_cap = 0;
-        FW_HIP(ctx, hipMalloc((void **)&ctx->d_colliders, ncap * sizeof(FwCollider)));
-        ctx->coll_cap = ncap;
+    if (!ctx->ev_coll[slot]) FW_HIP(ctx, ctx->ev_coll[slot].create());
+    const size_t ncap = std::max<size_t>(64, (size_t)n * 2);
+    fw_status st;
+    if (n > ctx->h_coll[slot].cap() && (st = alloc_buf(ctx, ctx->h_coll[slot], ncap, Mem::pinned))) return st;
+    if (n > ctx->d_colliders.cap()) {  // a larger world than ever before: the one case that waits (kernels in flight read the old table)
+        if ((st = sync(ctx)) || (st = alloc_buf(ctx, ctx->d_colliders, ncap, Mem::device, false, &ctx->g.colliders))) return st;
     }
     for (uint32_t i = 0; i < n; i++) {
         const fw_collider &c = colliders[i];
@@ -314,7 +236,7 @@ fw_status fw_ctx_set_colliders(fw_ctx *ctx, const fw_collider *colliders, uint32
         ctx->coll_pending[slot] = true;
     }
     ctx->n_colliders = n;
-    ctx->g.colliders = ctx->d_colliders, ctx->g.n_colliders = n;
+    ctx->g.n_colliders = n;
     ctx->fc_ok = false, ctx->boxes_epoch = 0;
     return FW_OK;
 }
@@ -369,7 +291,7 @@ fw_status fw_spawner_update_settings(fw_ctx *ctx, fw_spawner h, const fw_spawner
     for (const EmissionHost &e : sp->em) {
         unsigned long long s = e.serial;
         if (e.es.mode == FW_MODE_NESTED)
-            hipMemcpy(&s, ctx->d_emit_serial.d + e.emit_slot, sizeof s, hipMemcpyDeviceToHost);
+            hipMemcpy(&s, ctx->d_emit_serial + e.emit_slot, sizeof s, hipMemcpyDeviceToHost);
         serials.push_back(s);
     }
     if ((st = release_spawner_segments(ctx, *sp))) return st;
@@ -531,14 +453,10 @@ fw_status fw_spawner_poll_finished(fw_ctx *ctx, fw_spawner h, int32_t *out) {
 }
 
 static fw_status stage_buffer(fw_ctx *ctx, size_t bytes, void **out) {
-    if (bytes > ctx->stage_bytes) {
-        fw_status st = sync(ctx);
-        if (st) return st;
-        if (ctx->d_stage) FW_HIP(ctx, hipFree(ctx->d_stage));
-        ctx->d_stage = nullptr, ctx->stage_bytes = 0;
+    if (bytes > ctx->d_stage.cap()) {
         const size_t nb = (std::max<size_t>(bytes + bytes / 4, (size_t)1 << 20) + 65535u) & ~(size_t)65535u;
-        FW_HIP(ctx, hipMalloc(&ctx->d_stage, nb));
-        ctx->stage_bytes = nb;
+        fw_status st;
+        if ((st = sync(ctx)) || (st = alloc_buf(ctx, ctx->d_stage, nb))) return st;
     }
     *out = ctx->d_stage;
     return FW_OK;
@@ -557,7 +475,7 @@ static fw_status read_records(fw_ctx *ctx, const char *buf, uint32_t cap_seg, ui
     fw_status st = stage_buffer(ctx, m * sizeof(fw_particle), &tmp);
     if (st) return st;
     hipError_t e = fw_launch_gather(ctx->stream, buf, cap_seg, head, (uint32_t)m, pbr, tmp, const_rot, life_plane, life_const,
-                                    derived, ctx->d_keys.d, cpl);
+                                    derived, ctx->d_keys, cpl);
     // (the copy goes through the stream the kernel ran on, then one wait for both)
     if (e == hipSuccess) e = hipMemcpyAsync(out, tmp, m * sizeof(fw_particle), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -580,7 +498,7 @@ fw_status fw_spawner_read_particles(fw_ctx *ctx, fw_spawner h, uint32_t type, fw
     fw_status st2 = read_records(ctx, S.buf[ctx->parity], S.capacity, n, sp->types[type].ps.pbr, false, out, cap,
                                  ring_head_exact(S, n), S.nospin ? S.const_rot : nullptr,
                                  (S.nospin && !S.fifo) ? S.n_lplanes : 0xFFFFFFFFu, S.fifo_life,
-                                 S.derived ? ctx->d_types.d + S.type_idx : nullptr, S.ring());
+                                 S.derived ? ctx->d_types + S.type_idx : nullptr, S.ring());
     return st2 ? st2 : st;
 }
 
@@ -709,7 +627,7 @@ fw_status fw_spawner_pack_instances_device(fw_ctx *ctx, fw_spawner h, uint32_t t
     FW_HIP(ctx, fw_launch_pack_instances(ctx->stream, S.buf[ctx->parity], S.capacity, S.range ? S.young_lo : (S.fifo ? S.head : 0u),
                                          ctx->g.count + (size_t)ctx->parity * ctx->max_seg + si, ub, d_out,
                                          S.nospin ? S.const_rot : nullptr, S.range ? ctx->g.rold + (size_t)ctx->parity * ctx->max_seg + si : nullptr,
-                                         S.derived ? ctx->d_types.d + S.type_idx : nullptr, ctx->d_keys.d, S.life_plane(), S.fifo_life, S.ring()));
+                                         S.derived ? ctx->d_types + S.type_idx : nullptr, ctx->d_keys, S.life_plane(), S.fifo_life, S.ring()));
     return FW_OK;
 }
 
@@ -798,7 +716,10 @@ fw_status fw_spawner_aabb(fw_ctx *ctx, fw_spawner h, float out_min[3], float out
     if (!sp || !out_min || !out_max) return FW_EINVAL;
     if (poll_device_error(ctx), sp->poisoned) return poisoned_status(ctx);
     hipSetDevice(ctx->device);
-    if (!ctx->h_aabb) FW_HIP(ctx, hipHostMalloc((void **)&ctx->h_aabb, 8 * sizeof(float), hipHostMallocDefault));
+    if (!ctx->h_aabb) {
+        fw_status st = alloc_buf(ctx, ctx->h_aabb, 8, Mem::pinned);
+        if (st) return st;
+    }
     {
         fw_status jst = join_side(ctx);  // (the query kernels run on the main stream and may read rings)
         if (jst) return jst;
@@ -913,8 +834,9 @@ fw_status fw_ctx_kernel_timing(fw_ctx *ctx, int32_t enable) {
     fw_status st = sync(ctx);
     if (st) return st;
     if (enable && ctx->tev.empty()) {
-        ctx->tev.resize(kTimingEvents);
-        for (auto &ev : ctx->tev) FW_HIP(ctx, hipEventCreate(&ev));
+        std::vector<HipEvent> tev(kTimingEvents);
+        for (HipEvent &ev : tev) FW_HIP(ctx, ev.create(hipEventDefault));
+        ctx->tev = std::move(tev);
     }
     if (enable) {
         // for reference only: what an empty hipEventRecord pair on the stream costs (the timed launches do not use
@@ -1095,16 +1017,14 @@ fw_status fw_ctx_measure_copy_bandwidth(fw_ctx *ctx, uint64_t bytes, int32_t ite
     if (!ctx || !bytes_per_s || bytes < 4096 || iters < 1) return FW_EINVAL;
     hipSetDevice(ctx->device);
     bytes &= ~(uint64_t)0xFFF;
-    void *a = nullptr, *b = nullptr;
-    FW_HIP(ctx, hipMalloc(&a, bytes));
-    if (hipMalloc(&b, bytes) != hipSuccess) {
-        hipFree(a);
-        return fail(ctx, FW_ENOMEM, "copy probe allocation");
-    }
+    HipBuf<char> a, b;
+    fw_status st = alloc_buf(ctx, a, bytes);
+    if (st) return st;
+    if (alloc_buf(ctx, b, bytes)) return fail(ctx, FW_ENOMEM, "copy probe allocation: " + ctx->err);
     fw_memset_done(a, 1, bytes);
     fw_memset_done(b, 0, bytes);
-    hipEvent_t e0, e1;
-    hipEventCreate(&e0), hipEventCreate(&e1);
+    HipEvent e0, e1;
+    e0.create(hipEventDefault), e1.create(hipEventDefault);
     for (int i = 0; i < 3; i++) fw_launch_copy_probe(ctx->stream, a, b, bytes);
     hipEventRecord(e0, ctx->stream);
     for (int i = 0; i < iters; i++) fw_launch_copy_probe(ctx->stream, (i & 1) ? b : a, (i & 1) ? a : b, bytes);
@@ -1112,8 +1032,6 @@ fw_status fw_ctx_measure_copy_bandwidth(fw_ctx *ctx, uint64_t bytes, int32_t ite
     hipError_t e = hipEventSynchronize(e1);
     float ms = 0;
     if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
-    hipEventDestroy(e0), hipEventDestroy(e1);
-    hipFree(a), hipFree(b);
     FW_HIP(ctx, e);
     *bytes_per_s = 2.0 * (double)bytes * iters / (ms * 1e-3);
     return FW_OK;

@@ -124,18 +124,19 @@ fw_status build_spawner(fw_ctx *ctx, int h, const fw_spawner_desc *d, const std:
     sp.em.assign(ne, EmissionHost{});
     sp.seg.assign(nt, kNoSeg);
 
+    // a device table with room for `need` entries, the first `used` kept (amortised growth, zero-filled) and its FwGlobals view
+    auto reserve = [ctx](auto &b, size_t need, size_t used, auto **view) -> fw_status {
+        return need <= b.cap() ? FW_OK : grow_buf(ctx, b, std::max<size_t>(need, b.cap() * 2 + 64), true, used, view);
+    };
     fw_status st;
-    if ((st = dev_reserve(ctx, ctx->d_types, ctx->n_types + nt, ctx->n_types))) return st;
-    if ((st = dev_reserve(ctx, ctx->d_type_coll, ctx->n_types + nt, ctx->n_types))) return st;
-    if ((st = dev_reserve(ctx, ctx->d_emits, ctx->n_emits + ne, ctx->n_emits))) return st;
-    if ((st = dev_reserve(ctx, ctx->d_emit_serial, ctx->n_emit_slots + ne, ctx->n_emit_slots))) return st;
-    if ((st = dev_reserve(ctx, ctx->d_nest_start, ctx->n_emit_slots + ne, ctx->n_emit_slots))) return st;
+    if ((st = reserve(ctx->d_types, ctx->n_types + nt, ctx->n_types, &ctx->g.types))) return st;
+    if ((st = reserve(ctx->d_type_coll, ctx->n_types + nt, ctx->n_types, &ctx->g.type_coll))) return st;
+    if ((st = reserve(ctx->d_emits, ctx->n_emits + ne, ctx->n_emits, &ctx->g.emits))) return st;
+    if ((st = reserve(ctx->d_emit_serial, ctx->n_emit_slots + ne, ctx->n_emit_slots, &ctx->g.emit_serial))) return st;
+    if ((st = reserve(ctx->d_nest_start, ctx->n_emit_slots + ne, ctx->n_emit_slots, &ctx->g.nest_start))) return st;
     if (ctx->nest_ticket_base.size() < ctx->n_emit_slots + ne) ctx->nest_ticket_base.resize(ctx->n_emit_slots + ne, 0u);
-    if ((st = dev_reserve(ctx, ctx->d_segs, ctx->segs.size() + nt, ctx->segs.size()))) return st;
+    if ((st = reserve(ctx->d_segs, ctx->segs.size() + nt, ctx->segs.size(), &ctx->g.segs))) return st;
     if ((st = ensure_max_seg(ctx, (uint32_t)ctx->segs.size() + nt))) return st;
-    ctx->g.type_coll = ctx->d_type_coll.d;
-    ctx->g.types = ctx->d_types.d, ctx->g.emits = ctx->d_emits.d, ctx->g.keys = ctx->d_keys.d;
-    ctx->g.segs = ctx->d_segs.d, ctx->g.emit_serial = ctx->d_emit_serial.d, ctx->g.nest_start = ctx->d_nest_start.d;
 
     std::vector<uint32_t> caps(nt, 0);
     for (int pass = 0; pass < 2; pass++)
@@ -220,8 +221,7 @@ fw_status build_spawner(fw_ctx *ctx, int h, const fw_spawner_desc *d, const std:
             }
         if (!kwin_cap) {
             kwin_cap = std::max<uint32_t>(64u, pad4((uint32_t)keys.size()));
-            if ((st = dev_reserve(ctx, ctx->d_keys, ctx->keys_end + kwin_cap, ctx->keys_end))) return st;
-            ctx->g.keys = ctx->d_keys.d;
+            if ((st = reserve(ctx->d_keys, ctx->keys_end + kwin_cap, ctx->keys_end, &ctx->g.keys))) return st;
             kwin_off = (uint32_t)ctx->keys_end;
             ctx->keys_end += kwin_cap;
         }
@@ -248,10 +248,10 @@ fw_status build_spawner(fw_ctx *ctx, int h, const fw_spawner_desc *d, const std:
         if (S.derived) dt.flags |= FW_TYPE_DERIVED;
         memcpy(S.const_rot, dt.const_rot, sizeof S.const_rot);
         sp.seg[t] = si;
-        FW_HIP(ctx, hipMemcpy(ctx->d_keys.d + dt.keys_off, keys.data(), keys.size() * sizeof(float),
+        FW_HIP(ctx, hipMemcpy(ctx->d_keys + dt.keys_off, keys.data(), keys.size() * sizeof(float),
                               hipMemcpyHostToDevice));
-        FW_HIP(ctx, hipMemcpy(ctx->d_types.d + type_idx, &dt, sizeof dt, hipMemcpyHostToDevice));
-        FW_HIP(ctx, hipMemcpy(ctx->d_type_coll.d + type_idx, &dc, sizeof dc, hipMemcpyHostToDevice));
+        FW_HIP(ctx, hipMemcpy(ctx->d_types + type_idx, &dt, sizeof dt, hipMemcpyHostToDevice));
+        FW_HIP(ctx, hipMemcpy(ctx->d_type_coll + type_idx, &dc, sizeof dc, hipMemcpyHostToDevice));
         S.lplane_emission.clear();
         for (uint32_t i = 0; i < ne; i++) {
             const fw_emission_settings &e = d->emission_settings[i];
@@ -304,8 +304,7 @@ fw_status build_spawner(fw_ctx *ctx, int h, const fw_spawner_desc *d, const std:
                 S.fifo_mat = any_nested;
                 S.fifo_dev = S.nested_fed;
                 if (S.fifo_dev) {
-                    FW_HIP(ctx, hipHostMalloc((void **)&S.h_report, (size_t)kReportRing * sizeof(unsigned long long), hipHostMallocDefault));
-                    memset(S.h_report, 0, (size_t)kReportRing * sizeof(unsigned long long));
+                    if ((st = alloc_buf(ctx, S.h_report, kReportRing, Mem::pinned, true))) return st;
                 }
                 S.fifo_life = 0.0f * (p.lifetime.max - p.lifetime.min) + p.lifetime.min;  // u * (max - min) + min, any u
                 S.fifo_wm = (T.base.kind != 0 ? 1 : 0) | (T.emis.kind != 0 ? 2 : 0) | (T.scale.kind != 0 ? 4 : 0);
@@ -335,8 +334,7 @@ fw_status build_spawner(fw_ctx *ctx, int h, const fw_spawner_desc *d, const std:
                 if (S.range_dev) {
                     S.win_ok = false;
                     ctx->range_age_keep = std::max(ctx->range_age_keep, (float)(S.life_bound * 1.01 + 1e-3));
-                    FW_HIP(ctx, hipHostMalloc((void **)&S.h_report, (size_t)kReportRing * sizeof(unsigned long long), hipHostMallocDefault));
-                    memset(S.h_report, 0, (size_t)kReportRing * sizeof(unsigned long long));
+                    if ((st = alloc_buf(ctx, S.h_report, kReportRing, Mem::pinned, true))) return st;
                 }
             }
         }
@@ -354,7 +352,11 @@ fw_status build_spawner(fw_ctx *ctx, int h, const fw_spawner_desc *d, const std:
                 if ((uint32_t)d->emission_settings[i].particle_index == t) feeders++, global_feeders += d->emission_settings[i].mode == FW_MODE_GLOBAL ? 1u : 0u;
             S.one_feeder = feeders == 1 && global_feeders == 1;
         }
-        if ((st = alloc_seg_buffers(ctx, S, caps[t], p.report_destroyed != 0))) return st;
+        {
+            SegBufs nb;
+            if ((st = alloc_seg_buffers(ctx, S, caps[t], S.ring(), p.report_destroyed != 0, nb))) return st;
+            S.take(std::move(nb));
+        }
         if (small_eligible(ctx, S)) enter_small(ctx, S);  // (fw_ctx::n_small: the wave-per-type kernel)
         if ((st = upload_seg(ctx, si))) return st;
         const uint32_t zero2[2] = {0, 0};
@@ -414,11 +416,11 @@ fw_status build_spawner(fw_ctx *ctx, int h, const fw_spawner_desc *d, const std:
             E.emit_slot = ctx->n_emit_slots++;
         }
         E.assigned = true;
-        FW_HIP(ctx, hipMemcpy(ctx->d_emits.d + E.emit_idx, &de, sizeof de, hipMemcpyHostToDevice));
+        FW_HIP(ctx, hipMemcpy(ctx->d_emits + E.emit_idx, &de, sizeof de, hipMemcpyHostToDevice));
         const unsigned long long s0 = E.serial;
-        FW_HIP(ctx, hipMemcpy(ctx->d_emit_serial.d + E.emit_slot, &s0, sizeof s0, hipMemcpyHostToDevice));
+        FW_HIP(ctx, hipMemcpy(ctx->d_emit_serial + E.emit_slot, &s0, sizeof s0, hipMemcpyHostToDevice));
         const uint32_t t0 = 0u;
-        FW_HIP(ctx, hipMemcpy(ctx->d_nest_start.d + E.emit_slot, &t0, sizeof t0, hipMemcpyHostToDevice));
+        FW_HIP(ctx, hipMemcpy(ctx->d_nest_start + E.emit_slot, &t0, sizeof t0, hipMemcpyHostToDevice));
         ctx->nest_ticket_base[E.emit_slot] = 0u;
     }
     // ring types other particles' entries emit from that need no materialisation (SegHost::virt_parent)
@@ -445,11 +447,8 @@ fw_status build_spawner(fw_ctx *ctx, int h, const fw_spawner_desc *d, const std:
     if (ctx->segs.size() > ctx->small_cap) {  // the small-type list (fw_ctx::d_small): room for every segment slot; fw_step never allocates
         if ((st = sync(ctx))) return st;
         const size_t ncap = ctx->segs.size() * 2 + 256;
-        if (ctx->d_small) hipFree(ctx->d_small);
-        if (ctx->h_small) hipHostFree(ctx->h_small);
-        ctx->d_small = nullptr, ctx->h_small = nullptr, ctx->small_cap = 0, ctx->small_pending = false;
-        FW_HIP(ctx, hipMalloc((void **)&ctx->d_small, ncap * sizeof(uint32_t)));
-        FW_HIP(ctx, hipHostMalloc((void **)&ctx->h_small, ncap * sizeof(uint32_t), hipHostMallocDefault));
+        ctx->small_cap = 0, ctx->small_pending = false;
+        if ((st = alloc_buf(ctx, ctx->d_small, ncap)) || (st = alloc_buf(ctx, ctx->h_small, ncap, Mem::pinned))) return st;
         ctx->small_cap = ncap, ctx->small_dirty = true;
     }
     // the context is no longer one of few segments without a FIFO ring: its small range rings continue on the compacting path
@@ -476,6 +475,7 @@ fw_status release_spawner_segments(fw_ctx *ctx, SpawnerHost &sp) {
         ctx->free_emit_slots.push_back(e.emit_slot);
     }
     sp.em.clear();
+    hipError_t e = hipSuccess;  // (the release goes on: the first failure is reported at the end)
     for (uint32_t si : sp.seg) {
         if (si == kNoSeg) continue;
         SegHost &S = ctx->segs[si];
@@ -492,16 +492,13 @@ fw_status release_spawner_segments(fw_ctx *ctx, SpawnerHost &sp) {
         if (S.solo) ctx->n_solo--;
         ctx->n_in_use--, ctx->big_dirty = true;
         if (ctx->n_in_use <= ctx->range_few / 2) ctx->few_blocked = false;
-        if (S.h_report) hipHostFree(S.h_report);
-        if (S.buf[0]) FW_HIP(ctx, hipFree(S.buf[0]));
-        if (S.destroyed) FW_HIP(ctx, hipFree(S.destroyed));
-        S = SegHost{};
+        S = SegHost{};  // (releases its buffers)
         const uint32_t zero = 0;
-        for (int r = 0; r < 2; r++)
-            FW_HIP(ctx, hipMemcpy(ctx->g.count + (size_t)r * ctx->max_seg + si, &zero, 4, hipMemcpyHostToDevice));
+        for (int r = 0; r < 2 && e == hipSuccess; r++) e = hipMemcpy(ctx->g.count + (size_t)r * ctx->max_seg + si, &zero, 4, hipMemcpyHostToDevice);
     }
     sp.seg.clear();
     update_small_mode(ctx);
+    if (e != hipSuccess) return fail(ctx, FW_EHIP, std::string("hipMemcpy(live count of a released segment): ") + hipGetErrorString(e));
     return FW_OK;
 }
 

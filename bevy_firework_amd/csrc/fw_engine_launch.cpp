@@ -169,7 +169,7 @@ fw_status set_forecast(fw_ctx *ctx, FwFrame &fr) {
             ra.fce = ctx->d_fce + (size_t)((ctx->fc_seq + 1u) & 1u) * ctx->tiles_cap;
             ra.fct = ctx->d_fct + (size_t)((ctx->fc_seq + 1u) & 1u) * ctx->tiles_cap;
             ra.fcl = ctx->d_fcl + (size_t)((ctx->fc_seq + 1u) & 1u) * ctx->tiles_cap * FW_TF_K;
-            ra.tile_desc = n_seg == 1 ? nullptr : ctx->d_tile_desc;
+            ra.tile_desc = n_seg == 1 ? nullptr : ctx->d_tile_desc.get();
             ra.total_tiles = total_tiles, ra.parity = fr.p, ra.epoch = a.epoch, ra.dt = dt;
             FW_HIP(ctx, fw_launch_fc_resolve(ctx->stream, ctx->g, ra));
             a.fc_in = ctx->d_fc + (size_t)((ctx->fc_seq + 2u) % 3u) * ctx->fc_len;  // (per-tile entries: only its non-nullness matters)
@@ -181,11 +181,8 @@ fw_status set_forecast(fw_ctx *ctx, FwFrame &fr) {
         if (tf_size && ctx->tf_armed) {
             ctx->tf_armed--;
             if (ctx->tf_cap != ctx->tiles_cap) {  // (first use, or the tile scratch grew: ensure_tile_arrays)
-                if (ctx->d_fct) (void)hipFree(ctx->d_fct), ctx->d_fct = nullptr;
-                if (ctx->d_fcl) (void)hipFree(ctx->d_fcl), ctx->d_fcl = nullptr;
                 ctx->tf_cap = 0;
-                if (hipMalloc((void **)&ctx->d_fct, 2 * ctx->tiles_cap * sizeof(uint4)) == hipSuccess &&
-                    hipMalloc((void **)&ctx->d_fcl, 2 * ctx->tiles_cap * FW_TF_K * sizeof(float2)) == hipSuccess)
+                if (alloc_buf(ctx, ctx->d_fct, 2 * ctx->tiles_cap) == FW_OK && alloc_buf(ctx, ctx->d_fcl, 2 * ctx->tiles_cap * FW_TF_K) == FW_OK)
                     ctx->tf_cap = ctx->tiles_cap;
                 else
                     (void)hipGetLastError();  // (no memory for the lists: the look-back schedule stays)
@@ -426,7 +423,7 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
     // (never on a caller-supplied stream: work the caller orders behind fw_step on ITS stream must cover the whole
     // frame, as it did before the side stream existed)
     // (the wave-per-type launch of small types counts as "a general launch" here: it touches none of the rings either)
-    bool side = ctx->use_fifo_stream && ctx->own_stream && (fr.total_tiles != 0 || ctx->n_small != 0) && ctx->live_ring == nullptr;
+    bool side = ctx->use_fifo_stream && ctx->stream.owned() && (fr.total_tiles != 0 || ctx->n_small != 0) && ctx->live_ring == nullptr;
     // (... nor with a colliding ring: a new collider set travels in the MAIN stream, fw_ctx_set_colliders)
     for (const SegHost &S : ctx->segs) side &= !(S.in_use && S.fifo && (S.fifo_mat || S.inst != nullptr || S.collides));
     fw_status st = order_side(ctx, side, ctx->fifo_last_side);
@@ -595,7 +592,7 @@ fw_status launch_range(fw_ctx *ctx, FwFrame &fr) {
     const int rslot = (int)(ctx->rring_seq++ % kParamRing);
     fw_status st = wait_slot_free(ctx, ctx->rslot_frame[rslot]);  // (the kernel reads the slot in place)
     if (st) return st;
-    FwRangeRec *recs = (FwRangeRec *)ctx->h_rparam[rslot];
+    FwRangeRec *recs = (FwRangeRec *)ctx->h_rparam[rslot].get();
     FwOp *rops = (FwOp *)(ctx->h_rparam[rslot] + round_up((uint32_t)(ctx->max_seg * sizeof(FwRangeRec)), 64));
     std::vector<FwOp> &ops = ctx->range_ops;
     sort_by_segment(ops.data(), ops.data() + ops.size());
@@ -770,7 +767,7 @@ fw_status launch_small(fw_ctx *ctx, FwFrame &fr) {
     sa.done_tag = a.done_tag, sa.done_value = a.done_value;
     sa.host_counts = a.host_counts, sa.live_out = a.live_out, sa.live_next = a.live_next;
     // next to the collision passes of the frame, on the ring stream (fw_ctx::small_last_side)
-    const bool small_side = fr.legacy && fr.frame_mode != FW_MODE_FUSED && sa.n != 0 && ctx->host_fast && ctx->use_fifo_stream && ctx->own_stream &&
+    const bool small_side = fr.legacy && fr.frame_mode != FW_MODE_FUSED && sa.n != 0 && ctx->host_fast && ctx->use_fifo_stream && ctx->stream.owned() &&
                             ctx->live_ring == nullptr && ctx->n_small_coll == 0 && !list_resent;
     if (!sa.n) return FW_OK;
     if ((st = order_side(ctx, small_side, ctx->small_last_side))) return st;

@@ -26,59 +26,30 @@ fw_status join_side(fw_ctx *ctx) {
     return FW_OK;
 }
 
-// grows the [2][max_seg] bookkeeping arrays and the snapshot ring
+// grows the [2][max_seg] bookkeeping arrays and the snapshot ring: every new array is made (and filled) before any is installed --
+// the rows of the [2][max_seg] ones sit max_seg apart
 fw_status ensure_max_seg(fw_ctx *ctx, uint32_t need) {
     if (need <= ctx->max_seg) return FW_OK;
     fw_status st = sync(ctx);
     if (st) return st;
-    uint32_t nmax = std::max<uint32_t>(need, ctx->max_seg ? ctx->max_seg * 2 : 1024);
-    auto regrow2 = [&](uint32_t *&p) -> fw_status {
-        uint32_t *np = nullptr;
-        FW_HIP(ctx, hipMalloc((void **)&np, 2ull * nmax * sizeof(uint32_t)));
-        FW_HIP(ctx, fw_memset_done(np, 0, 2ull * nmax * sizeof(uint32_t)));
-        if (p) {
-            for (int r = 0; r < 2; r++)
-                FW_HIP(ctx, hipMemcpy(np + (size_t)r * nmax, p + (size_t)r * ctx->max_seg,
-                                      ctx->max_seg * sizeof(uint32_t), hipMemcpyDeviceToDevice));
-            FW_HIP(ctx, hipFree(p));
-        }
-        p = np;
-        return FW_OK;
-    };
-    if ((st = regrow2(ctx->g.count))) return st;
-    if ((st = regrow2(ctx->g.spawned))) return st;
-    if ((st = regrow2(ctx->g.appended))) return st;
-    if ((st = regrow2(ctx->g.rold))) return st;
-    {
-        uint32_t *np = nullptr;
-        FW_HIP(ctx, hipMalloc((void **)&np, (size_t)nmax * sizeof(uint32_t)));
-        FW_HIP(ctx, fw_memset_done(np, 0, (size_t)nmax * sizeof(uint32_t)));
-        if (ctx->g.ndestroyed) {
-            FW_HIP(ctx, hipMemcpy(np, ctx->g.ndestroyed, ctx->max_seg * sizeof(uint32_t), hipMemcpyDeviceToDevice));
-            FW_HIP(ctx, hipFree(ctx->g.ndestroyed));
-        }
-        ctx->g.ndestroyed = np;
+    const uint32_t omax = ctx->max_seg, nmax = std::max<uint32_t>(need, omax ? omax * 2 : 1024);
+    HipBuf<uint32_t> *const cur[6] = {&ctx->gm.count, &ctx->gm.spawned, &ctx->gm.appended, &ctx->gm.rold, &ctx->gm.ndestroyed, &ctx->gm.range_ticket};
+    HipBuf<uint32_t> nb[6], segids;
+    HipBuf<unsigned long long> snap;
+    for (int i = 0; i < 6; i++) {
+        const int rows = i < 4 ? 2 : 1;
+        if ((st = alloc_buf(ctx, nb[i], (size_t)rows * nmax, Mem::device, true))) return st;
+        for (int r = 0; r < rows && omax; r++)
+            FW_HIP(ctx, hipMemcpy(nb[i] + (size_t)r * nmax, *cur[i] + (size_t)r * omax, omax * sizeof(uint32_t), hipMemcpyDeviceToDevice));
     }
-    {
-        unsigned long long *nh = nullptr;
-        FW_HIP(ctx, hipHostMalloc((void **)&nh, (size_t)kSnapRing * nmax * sizeof(unsigned long long), hipHostMallocDefault));
-        memset(nh, 0, (size_t)kSnapRing * nmax * sizeof(unsigned long long));
-        if (ctx->h_snap) FW_HIP(ctx, hipHostFree(ctx->h_snap));
-        ctx->h_snap = nh;
-        for (int i = 0; i < kSnapRing; i++) ctx->snap_pending[i] = false;
-    }
-    {
-        uint32_t *np = nullptr;
-        FW_HIP(ctx, hipMalloc((void **)&np, (size_t)nmax * sizeof(uint32_t)));
-        FW_HIP(ctx, fw_memset_done(np, 0, (size_t)nmax * sizeof(uint32_t)));
-        if (ctx->g.range_ticket) {
-            FW_HIP(ctx, hipMemcpy(np, ctx->g.range_ticket, ctx->max_seg * sizeof(uint32_t), hipMemcpyDeviceToDevice));
-            FW_HIP(ctx, hipFree(ctx->g.range_ticket));
-        }
-        ctx->g.range_ticket = np;
-    }
-    if (ctx->d_segids) FW_HIP(ctx, hipFree(ctx->d_segids));
-    FW_HIP(ctx, hipMalloc((void **)&ctx->d_segids, (size_t)nmax * sizeof(uint32_t)));
+    if ((st = alloc_buf(ctx, snap, (size_t)kSnapRing * nmax, Mem::pinned, true))) return st;
+    if ((st = alloc_buf(ctx, segids, nmax))) return st;
+    for (int i = 0; i < 6; i++) *cur[i] = std::move(nb[i]);
+    ctx->g.count = ctx->gm.count, ctx->g.spawned = ctx->gm.spawned, ctx->g.appended = ctx->gm.appended, ctx->g.rold = ctx->gm.rold;
+    ctx->g.ndestroyed = ctx->gm.ndestroyed, ctx->g.range_ticket = ctx->gm.range_ticket;
+    ctx->h_snap = std::move(snap);
+    for (int i = 0; i < kSnapRing; i++) ctx->snap_pending[i] = false;
+    ctx->d_segids = std::move(segids);
     ctx->max_seg = nmax;
     ctx->g.max_seg = nmax;
     return FW_OK;
@@ -128,50 +99,28 @@ fw_status ensure_tile_arrays(fw_ctx *ctx) {
                 nest_ops++;
             }
     }
+    fw_status st;
     if (tiles > ctx->tiles_cap) {
-        fw_status st = sync(ctx);
-        if (st) return st;
+        if ((st = sync(ctx))) return st;
         size_t ncap = tiles * 2;
-        if (ctx->g.tile_cnt) hipFree(ctx->g.tile_cnt), hipFree(ctx->g.tile_off), hipFree(ctx->g.tile_status);
-        FW_HIP(ctx, hipMalloc((void **)&ctx->g.tile_cnt, ncap * sizeof(uint32_t)));
-        FW_HIP(ctx, hipMalloc((void **)&ctx->g.tile_off, ncap * sizeof(uint32_t)));
-        FW_HIP(ctx, hipMalloc((void **)&ctx->g.tile_status, ncap * sizeof(unsigned long long)));
-        FW_HIP(ctx, fw_memset_done(ctx->g.tile_status, 0, ncap * sizeof(unsigned long long)));
-        if (ctx->g.tile_box) hipFree(ctx->g.tile_box);
-        FW_HIP(ctx, hipMalloc((void **)&ctx->g.tile_box, ncap * 8 * sizeof(float)));
-        FW_HIP(ctx, fw_memset_done(ctx->g.tile_box, 0, ncap * 8 * sizeof(float)));
-        ctx->boxes_epoch = 0;
-        if (ctx->g.dbg_ts) hipFree(ctx->g.dbg_ts);
-        FW_HIP(ctx, hipMalloc((void **)&ctx->g.dbg_ts, (32768 + 8 * ncap) * sizeof(unsigned long long)));
-        FW_HIP(ctx, fw_memset_done(ctx->g.dbg_ts, 0, (32768 + 8 * ncap) * sizeof(unsigned long long)));
-        if (ctx->d_fce) hipFree(ctx->d_fce);
-        FW_HIP(ctx, hipMalloc((void **)&ctx->d_fce, 2 * ncap * sizeof(uint4)));
-        FW_HIP(ctx, fw_memset_done(ctx->d_fce, 0, 2 * ncap * sizeof(uint4)));
-        if (ctx->d_fc) hipFree(ctx->d_fc);
+        auto &m = ctx->gm;
+        ctx->tiles_cap = 0, ctx->fc_ok = false, ctx->boxes_epoch = 0;
         ctx->fc_len = ncap + (ncap / 64 + 2) * FW_FC_S2_STRIDE + 8;  // P | P2 | tag (64-bit words)
-        FW_HIP(ctx, hipMalloc((void **)&ctx->d_fc, 3 * ctx->fc_len * sizeof(unsigned long long)));
-        FW_HIP(ctx, fw_memset_done(ctx->d_fc, 0, 3 * ctx->fc_len * sizeof(unsigned long long)));
-        ctx->fc_ok = false, ctx->boxes_epoch = 0;
+        if ((st = alloc_buf(ctx, m.tile_cnt, ncap, Mem::device, false, &ctx->g.tile_cnt)) ||
+            (st = alloc_buf(ctx, m.tile_off, ncap, Mem::device, false, &ctx->g.tile_off)) ||
+            (st = alloc_buf(ctx, m.tile_status, ncap, Mem::device, true, &ctx->g.tile_status)) ||
+            (st = alloc_buf(ctx, m.tile_box, ncap * 8, Mem::device, true, &ctx->g.tile_box)) ||
+            (st = alloc_buf(ctx, m.dbg_ts, 32768 + 8 * ncap, Mem::device, true, &ctx->g.dbg_ts)) ||
+            (st = alloc_buf(ctx, ctx->d_fce, 2 * ncap, Mem::device, true)) || (st = alloc_buf(ctx, ctx->d_fc, 3 * ctx->fc_len, Mem::device, true)))
+            return st;
         ctx->fc_dirty = false;
         ctx->tiles_cap = ncap;
     }
-    if (nest_tiles > ctx->nest_tiles_cap) {
-        fw_status st = sync(ctx);
-        if (st) return st;
-        size_t ncap = nest_tiles * 2;
-        if (ctx->g.nest_status) hipFree(ctx->g.nest_status);
-        FW_HIP(ctx, hipMalloc((void **)&ctx->g.nest_status, ncap * sizeof(unsigned long long)));
-        FW_HIP(ctx, fw_memset_done(ctx->g.nest_status, 0, ncap * sizeof(unsigned long long)));
-        ctx->nest_tiles_cap = ncap;
+    if (nest_tiles > ctx->gm.nest_status.cap()) {
+        if ((st = sync(ctx)) || (st = alloc_buf(ctx, ctx->gm.nest_status, nest_tiles * 2, Mem::device, true, &ctx->g.nest_status))) return st;
     }
-    if (nest_ops > ctx->nest_ops_cap) {
-        fw_status st = sync(ctx);
-        if (st) return st;
-        size_t ncap = nest_ops * 2 + 16;
-        if (ctx->g.nest_ticket) hipFree(ctx->g.nest_ticket);
-        FW_HIP(ctx, hipMalloc((void **)&ctx->g.nest_ticket, ncap * sizeof(unsigned long long)));
-        FW_HIP(ctx, fw_memset_done(ctx->g.nest_ticket, 0, ncap * sizeof(unsigned long long)));
-        ctx->nest_ops_cap = ncap;
+    if (nest_ops > ctx->gm.nest_ticket.cap()) {
+        if ((st = sync(ctx)) || (st = alloc_buf(ctx, ctx->gm.nest_ticket, nest_ops * 2 + 16, Mem::device, true, &ctx->g.nest_ticket))) return st;
     }
     return FW_OK;
 }
@@ -185,39 +134,27 @@ fw_status ensure_range_arrays(fw_ctx *ctx) {
         if (s.in_use && s.range)  // OLD tiles of FW_TILE, YOUNG tiles of the build's size, NEW workgroups of FW_BLOCK
             // (... or, a launch on one-round tiles -- fw_ctx::range_small -- OLD and YOUNG tiles of FW_BLOCK)
             tiles += 2 * ((size_t)s.capacity / FW_BLOCK + 4) + (size_t)s.capacity / FW_BLOCK + 2;
+    fw_status st;
     if (tiles > ctx->rdesc_cap) {
-        fw_status st = sync(ctx);
-        if (st) return st;
+        if ((st = sync(ctx))) return st;
         const size_t ncap = tiles + tiles / 2 + 64;
-        if (ctx->d_rdesc) hipFree(ctx->d_rdesc);
-        if (ctx->h_rdesc) hipHostFree(ctx->h_rdesc);
-        if (ctx->d_rstatus) hipFree(ctx->d_rstatus);
-        ctx->d_rdesc = nullptr, ctx->h_rdesc = nullptr, ctx->d_rstatus = nullptr, ctx->rdesc_cap = 0;
-        FW_HIP(ctx, hipMalloc((void **)&ctx->d_rdesc, ncap * sizeof(FwRangeDesc)));
-        FW_HIP(ctx, hipHostMalloc((void **)&ctx->h_rdesc, ncap * sizeof(FwRangeDesc), hipHostMallocDefault));
-        FW_HIP(ctx, hipMalloc((void **)&ctx->d_rstatus, ncap * sizeof(unsigned long long)));
-        FW_HIP(ctx, fw_memset_done(ctx->d_rstatus, 0, ncap * sizeof(unsigned long long)));
-        if (ctx->dbg & 8u) {  // per-workgroup timestamps of the last range launch (tools/range_timeline.py)
-            if (ctx->d_rts) hipFree(ctx->d_rts);
-            ctx->d_rts = nullptr;
-            FW_HIP(ctx, hipMalloc((void **)&ctx->d_rts, ncap * 8 * sizeof(unsigned long long)));
-            FW_HIP(ctx, fw_memset_done(ctx->d_rts, 0, ncap * 8 * sizeof(unsigned long long)));
-        }
+        ctx->rdesc_cap = 0;
+        if ((st = alloc_buf(ctx, ctx->d_rdesc, ncap)) || (st = alloc_buf(ctx, ctx->h_rdesc, ncap, Mem::pinned)) ||
+            (st = alloc_buf(ctx, ctx->d_rstatus, ncap, Mem::device, true)))
+            return st;
+        // per-workgroup timestamps of the last range launch (tools/range_timeline.py)
+        if ((ctx->dbg & 8u) && (st = alloc_buf(ctx, ctx->d_rts, ncap * 8, Mem::device, true))) return st;
         ctx->rdesc_cap = ncap;
         ctx->r_force = true, ctx->rtab_pending = false;
     }
     // one record per segment slot + one op per emission entry of the context
     const size_t need = round_up((uint32_t)(ctx->max_seg * sizeof(FwRangeRec)), 64) + (size_t)(ctx->n_emits + 8) * sizeof(FwOp) + 64;
     if (ctx->n_range && need > ctx->rparam_bytes) {
-        fw_status st = sync(ctx);
-        if (st) return st;
+        if ((st = sync(ctx))) return st;
         const size_t nb = need * 2;
+        ctx->rparam_bytes = 0;
         for (int i = 0; i < kParamRing; i++) {
-            if (ctx->h_rparam[i]) FW_HIP(ctx, ctx->param_bar ? hipFree(ctx->h_rparam[i]) : hipHostFree(ctx->h_rparam[i]));
-            ctx->h_rparam[i] = nullptr;
-            FW_HIP(ctx, ctx->param_bar ? hipExtMallocWithFlags((void **)&ctx->h_rparam[i], nb, hipDeviceMallocFinegrained)
-                                       : hipHostMalloc((void **)&ctx->h_rparam[i], nb, hipHostMallocDefault));
-            memset(ctx->h_rparam[i], 0, nb);
+            if ((st = alloc_buf(ctx, ctx->h_rparam[i], nb, ctx->param_bar ? Mem::fine : Mem::pinned, true))) return st;
             ctx->rslot_frame[i] = 0;
         }
         ctx->rparam_bytes = nb;
@@ -241,10 +178,9 @@ fw_status ensure_param_ring(fw_ctx *ctx, size_t bytes) {
     if (st) return st;
     FW_HIP(ctx, hipStreamSynchronize(ctx->copy_stream));
     size_t nb = std::max<size_t>(bytes * 2, 1 << 16);
+    ctx->param_bytes = 0;
     for (int i = 0; i < kParamRing; i++) {
-        if (ctx->h_param[i]) hipHostFree(ctx->h_param[i]), hipFree(ctx->d_param[i]);
-        FW_HIP(ctx, hipHostMalloc((void **)&ctx->h_param[i], nb, hipHostMallocDefault));
-        FW_HIP(ctx, hipMalloc((void **)&ctx->d_param[i], nb));
+        if ((st = alloc_buf(ctx, ctx->h_param[i], nb, Mem::pinned)) || (st = alloc_buf(ctx, ctx->d_param[i], nb))) return st;
         ctx->consumed_pending[i] = false;
     }
     ctx->param_bytes = nb;
@@ -293,24 +229,20 @@ fw_status upload_seg(fw_ctx *ctx, uint32_t si) {
             const int32_t ei = s.lplane_emission[k];
             if (ei >= 0 && (size_t)ei < em.size() && em[ei].assigned) d.lplane_emit[k] = em[ei].emit_idx;
         }
-    FW_HIP(ctx, hipMemcpy(ctx->d_segs.d + si, &d, sizeof d, hipMemcpyHostToDevice));
+    FW_HIP(ctx, hipMemcpy(ctx->d_segs + si, &d, sizeof d, hipMemcpyHostToDevice));
     return FW_OK;
 }
 
-fw_status alloc_seg_buffers(fw_ctx *ctx, SegHost &s, uint32_t capacity, bool want_destroyed) {
+fw_status alloc_seg_buffers(fw_ctx *ctx, const SegHost &s, uint32_t capacity, bool ring, bool want_destroyed, SegBufs &out) {
     const size_t bytes = FW_BUF_BYTES((size_t)capacity, s.n_lplanes + s.n_xplanes);
-    char *b = nullptr;
-    hipError_t e = hipMalloc((void **)&b, bytes * (s.ring() ? 1 : 2));  // a ring is updated in place: one buffer
-    if (e != hipSuccess) return fail(ctx, FW_ENOMEM, std::string("hipMalloc particle buffers: ") + hipGetErrorString(e));
-    s.buf[0] = b;
-    s.buf[1] = s.ring() ? b : b + bytes;
-    s.capacity = capacity;
-    s.destroyed = nullptr;
-    if (want_destroyed) {
-        e = hipMalloc((void **)&s.destroyed, (size_t)capacity * sizeof(fw_particle));
-        if (e != hipSuccess) return fail(ctx, FW_ENOMEM, "hipMalloc destroyed buffer");
-    }
-    FW_HIP(ctx, fw_launch_fill_colors(ctx->stream, s.buf[0], s.ring() ? nullptr : s.buf[1], capacity, s.fill_bc, s.fill_em));
+    if (alloc_buf(ctx, out.mem, bytes * (ring ? 1 : 2)))  // a ring is updated in place: one buffer
+        return fail(ctx, FW_ENOMEM, "particle buffers: " + ctx->err);
+    if (want_destroyed && alloc_buf(ctx, out.destroyed, (size_t)capacity * sizeof(fw_particle)))
+        return fail(ctx, FW_ENOMEM, "destroyed buffer: " + ctx->err);
+    out.buf[0] = out.mem;
+    out.buf[1] = ring ? out.mem.get() : out.mem + bytes;
+    out.capacity = capacity;
+    FW_HIP(ctx, fw_launch_fill_colors(ctx->stream, out.buf[0], ring ? nullptr : out.buf[1], capacity, s.fill_bc, s.fill_em));
     FW_HIP(ctx, hipStreamSynchronize(ctx->stream));  // callers go on with blocking copies on the null stream
     return FW_OK;
 }

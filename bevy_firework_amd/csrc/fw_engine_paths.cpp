@@ -11,11 +11,65 @@ fw_status realloc_segment(fw_ctx *ctx, uint32_t si, uint32_t ncap, bool make_gen
     ctx->fc_ok = false, ctx->boxes_epoch = 0;
     fw_status st = refresh_counts_exact(ctx);
     if (st) return st;
-    SegHost old = s;
     if (s.fifo && ncap >= 0x40000000u) make_general = true;  // ring slots are computed in 32 bits: head + index < 2^32
     if (s.range && ncap > FW_RANGE_MAX_CAPACITY) make_general = true;  // (32-bit byte offsets into a plane)
-    if (make_general && s.fifo) {
+    const bool was_cpl = s.ring(), is_cpl = s.ring() && !make_general;  // (one buffer, component planes: below)
+    // the new buffers receive the particles before anything of the segment or the context changes: a failure leaves both as they were
+    SegBufs nb;
+    if ((st = alloc_seg_buffers(ctx, s, ncap, is_cpl, s.destroyed != nullptr, nb))) return st;
+    const uint32_t p = ctx->parity;
+    const uint32_t n = s.ub;  // exact after the refresh
+    const uint32_t h = ring_head_exact(s, n);
+    const uint32_t n1 = std::min<uint32_t>(n, s.capacity - h);  // up to the end of the old buffer, then from its slot 0
+    auto cp = [&](size_t noff, size_t ooff, size_t elem) -> hipError_t {
+        hipError_t e = hipSuccess;
+        if (n1) e = hipMemcpy(nb.buf[p] + noff, s.buf[p] + ooff + (size_t)h * elem, (size_t)n1 * elem, hipMemcpyDeviceToDevice);
+        if (e == hipSuccess && n > n1)
+            e = hipMemcpy(nb.buf[p] + noff + (size_t)n1 * elem, s.buf[p] + ooff, (size_t)(n - n1) * elem, hipMemcpyDeviceToDevice);
+        return e;
+    };
+    const size_t OC = s.capacity, NC = ncap;
+    FW_HIP(ctx, cp(FW_OFF_Q0(NC), FW_OFF_Q0(OC), 16));
+    // Q1 / Q3 of a RING are four component planes of 4-byte elements each (fw_device.h; their distance follows the capacity), of a segment
+    // of the compacting path float4 planes: a ring that grows keeps its layout, one that leaves for that path is transposed as it is
+    // unwrapped (hipMemcpy2D: rows of 4 bytes, 4 apart in the source, 16 apart in the destination)
+    auto cpq = [&](size_t noff, size_t ooff) -> hipError_t {
+        if (!was_cpl) return cp(noff, ooff, 16);  // (float4 -> float4; nothing becomes a ring here)
+        hipError_t e = hipSuccess;
+        for (size_t c = 0; c < 4 && e == hipSuccess; c++) {
+            if (is_cpl) {
+                e = cp(noff + c * 4 * NC, ooff + c * 4 * OC, 4);
+            } else {
+                if (n1) e = hipMemcpy2D(nb.buf[p] + noff + c * 4, 16, s.buf[p] + ooff + c * 4 * OC + (size_t)h * 4, 4, 4, n1, hipMemcpyDeviceToDevice);
+                if (e == hipSuccess && n > n1)
+                    e = hipMemcpy2D(nb.buf[p] + noff + (size_t)n1 * 16 + c * 4, 16, s.buf[p] + ooff + c * 4 * OC, 4, 4, n - n1, hipMemcpyDeviceToDevice);
+            }
+        }
+        return e;
+    };
+    FW_HIP(ctx, cpq(FW_OFF_Q1(NC), FW_OFF_Q1(OC)));
+    FW_HIP(ctx, cp(FW_OFF_Q2(NC), FW_OFF_Q2(OC), 16));
+    FW_HIP(ctx, cpq(FW_OFF_Q3(NC), FW_OFF_Q3(OC)));
+    FW_HIP(ctx, cp(FW_OFF_Q5(NC), FW_OFF_Q5(OC), 16));
+    FW_HIP(ctx, cp(FW_OFF_Q6(NC), FW_OFF_Q6(OC), 16));
+    FW_HIP(ctx, cp(FW_OFF_S4(NC), FW_OFF_S4(OC), 4));
+    for (uint32_t k = 0; k < s.n_lplanes + s.n_xplanes; k++) FW_HIP(ctx, cp(FW_OFF_L(NC, k), FW_OFF_L(OC, k), 4));
+    if (s.destroyed) {  // the records of the last update stay readable (fw_spawner_read_destroyed)
+        const size_t m = std::min<size_t>(s.capacity, ncap);  // (from the start of the buffer, or -- a range ring's -- up to its end)
+        const size_t so = s.dead_at_end ? (size_t)s.capacity - m : 0, dof = s.dead_at_end ? (size_t)ncap - m : 0;
+        FW_HIP(ctx, hipMemcpy(nb.destroyed + dof * sizeof(fw_particle), s.destroyed + so * sizeof(fw_particle), m * sizeof(fw_particle),
+                              hipMemcpyDeviceToDevice));
+    }
+    const bool leaves_fifo = s.fifo && make_general;
+    if (leaves_fifo && s.nospin) {  // a ring keeps no lifetime plane (one value); the compacting kernels read it
+        FW_HIP(ctx, fw_launch_fill_plane1(ctx->stream, nb.buf[0], nb.buf[1], FW_OFF_L((size_t)ncap, s.n_lplanes), ncap, s.fifo_life));
+        FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    // ---- commit: the list now starts in slot 0 (a range ring's old part first, the young part right behind it)
+    const uint32_t young_lo = s.range_dev ? std::min(s.rold_seen, n) : (n > s.young_n ? n - s.young_n : 0u);
+    if (leaves_fifo) {
         s.fifo = false, s.fifo_mat = s.fifo_dev = false, s.coh.clear();
+        s.win_ok = false;  // no lifetime window was kept: the bound follows the snapshots from here on
         ctx->n_fifo--;
         ctx->tab_force = true;
         ctx->seg_kind_changed = true;
@@ -29,75 +83,10 @@ fw_status realloc_segment(fw_ctx *ctx, uint32_t si, uint32_t ncap, bool make_gen
         ctx->tab_force = true, ctx->r_force = true;
         ctx->seg_kind_changed = true;
     }
-    st = alloc_seg_buffers(ctx, s, ncap, old.destroyed != nullptr);
-    if (st) {
-        if (old.fifo && !s.fifo) ctx->n_fifo++;
-        if (old.range && !s.range) ctx->n_range++;
-        if (old.few_ring && !s.few_ring) ctx->n_few++;
-        if (old.spilled && !s.spilled) ctx->n_spilled++;
-        s = old;
-        return st;
-    }
-    if (((old.fifo && !s.fifo) || (old.range && !s.range)) && s.h_report) hipHostFree(s.h_report), s.h_report = nullptr;
+    if (was_cpl && !is_cpl) s.h_report.reset();
     s.head = 0;
-    const uint32_t p = ctx->parity;
-    const uint32_t n = old.ub;  // exact after the refresh
-    const uint32_t h = ring_head_exact(old, n);
-    if (s.range) {  // the list now starts in slot 0: old part first, the young part right behind it
-        s.young_lo = old.range_dev ? std::min(old.rold_seen, n) : (n > old.young_n ? n - old.young_n : 0u);
-        ctx->r_force = true;
-    }
-    const uint32_t n1 = std::min<uint32_t>(n, old.capacity - h);  // up to the end of the old buffer, then from its slot 0
-    auto cp = [&](size_t noff, size_t ooff, size_t elem) -> hipError_t {
-        hipError_t e = hipSuccess;
-        if (n1) e = hipMemcpy(s.buf[p] + noff, old.buf[p] + ooff + (size_t)h * elem, (size_t)n1 * elem, hipMemcpyDeviceToDevice);
-        if (e == hipSuccess && n > n1)
-            e = hipMemcpy(s.buf[p] + noff + (size_t)n1 * elem, old.buf[p] + ooff, (size_t)(n - n1) * elem, hipMemcpyDeviceToDevice);
-        return e;
-    };
-    const size_t OC = old.capacity, NC = ncap;
-    FW_HIP(ctx, cp(FW_OFF_Q0(NC), FW_OFF_Q0(OC), 16));
-    // Q1 / Q3 of a RING are four component planes of 4-byte elements each (fw_device.h; their distance follows the capacity), of a segment
-    // of the compacting path float4 planes: a ring that grows keeps its layout, one that leaves for that path is transposed as it is
-    // unwrapped (hipMemcpy2D: rows of 4 bytes, 4 apart in the source, 16 apart in the destination)
-    const bool was_cpl = old.ring(), is_cpl = s.ring();
-    auto cpq = [&](size_t noff, size_t ooff) -> hipError_t {
-        if (!was_cpl) return cp(noff, ooff, 16);  // (float4 -> float4; nothing becomes a ring here)
-        hipError_t e = hipSuccess;
-        for (size_t c = 0; c < 4 && e == hipSuccess; c++) {
-            if (is_cpl) {
-                e = cp(noff + c * 4 * NC, ooff + c * 4 * OC, 4);
-            } else {
-                if (n1) e = hipMemcpy2D(s.buf[p] + noff + c * 4, 16, old.buf[p] + ooff + c * 4 * OC + (size_t)h * 4, 4, 4, n1, hipMemcpyDeviceToDevice);
-                if (e == hipSuccess && n > n1)
-                    e = hipMemcpy2D(s.buf[p] + noff + (size_t)n1 * 16 + c * 4, 16, old.buf[p] + ooff + c * 4 * OC, 4, 4, n - n1, hipMemcpyDeviceToDevice);
-            }
-        }
-        return e;
-    };
-    FW_HIP(ctx, cpq(FW_OFF_Q1(NC), FW_OFF_Q1(OC)));
-    FW_HIP(ctx, cp(FW_OFF_Q2(NC), FW_OFF_Q2(OC), 16));
-    FW_HIP(ctx, cpq(FW_OFF_Q3(NC), FW_OFF_Q3(OC)));
-    FW_HIP(ctx, cp(FW_OFF_Q5(NC), FW_OFF_Q5(OC), 16));
-    FW_HIP(ctx, cp(FW_OFF_Q6(NC), FW_OFF_Q6(OC), 16));
-    FW_HIP(ctx, cp(FW_OFF_S4(NC), FW_OFF_S4(OC), 4));
-    for (uint32_t k = 0; k < s.n_lplanes + s.n_xplanes; k++) FW_HIP(ctx, cp(FW_OFF_L(NC, k), FW_OFF_L(OC, k), 4));
-    if (old.destroyed) {  // the records of the last update stay readable (fw_spawner_read_destroyed)
-        const size_t m = std::min(old.capacity, ncap);  // (from the start of the buffer, or -- a range ring's -- up to its end)
-        const size_t so = old.dead_at_end ? (size_t)old.capacity - m : 0, dof = old.dead_at_end ? (size_t)ncap - m : 0;
-        FW_HIP(ctx, hipMemcpy(s.destroyed + dof * sizeof(fw_particle), old.destroyed + so * sizeof(fw_particle), m * sizeof(fw_particle),
-                              hipMemcpyDeviceToDevice));
-    }
-    FW_HIP(ctx, hipFree(old.buf[0]));
-    if (old.destroyed) FW_HIP(ctx, hipFree(old.destroyed));
-    if (old.fifo && !s.fifo) {
-        s.win_ok = false;  // no lifetime window was kept: the bound follows the snapshots from here on
-        if (s.nospin) {  // a ring keeps no lifetime plane (one value); the compacting kernels read it
-            FW_HIP(ctx, fw_launch_fill_plane1(ctx->stream, s.buf[0], s.buf[1], FW_OFF_L((size_t)s.capacity, s.n_lplanes), s.capacity,
-                                              s.fifo_life));
-            FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        }
-    }
+    if (s.range) s.young_lo = young_lo, ctx->r_force = true;
+    s.take(std::move(nb));  // (releases the old buffers)
     if ((st = upload_seg(ctx, si))) return st;
     if ((st = ensure_range_arrays(ctx))) return st;
     return ensure_tile_arrays(ctx);
@@ -269,7 +258,7 @@ fw_status fifo_to_range(fw_ctx *ctx, uint32_t si) {
         }
         S.young_n = (uint32_t)sum;  // (= the exact live count: everybody is young)
         S.win_sum = sum, S.win_ok = std::isfinite(S.life_bound);
-        if (S.h_report) hipHostFree(S.h_report), S.h_report = nullptr;
+        S.h_report.reset();
     }
     S.coh.clear();
     S.fifo_mat = S.fifo_dev = false;
@@ -306,7 +295,7 @@ fw_status leave_nospin(fw_ctx *ctx, uint32_t si) {
                                      s.fifo ? 0xFFFFFFFFu : s.n_lplanes, s.fifo_life, s.ring()));
     FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const uint32_t flags = s.derived ? FW_TYPE_DERIVED : 0u;
-    FW_HIP(ctx, hipMemcpy((char *)(ctx->d_types.d + s.type_idx) + offsetof(FwType, flags), &flags, sizeof flags, hipMemcpyHostToDevice));
+    FW_HIP(ctx, hipMemcpy((char *)(ctx->d_types + s.type_idx) + offsetof(FwType, flags), &flags, sizeof flags, hipMemcpyHostToDevice));
     s.nospin = false;
     ctx->tab_force = true, ctx->r_force = true;  // (the tile descriptors carry the flag)
     ctx->fc_ok = false, ctx->boxes_epoch = 0;
@@ -321,12 +310,12 @@ fw_status set_derived(fw_ctx *ctx, uint32_t si, bool on, bool refill) {
     fw_status st = sync(ctx);
     if (st) return st;
     if (!on && refill) {
-        FW_HIP(ctx, fw_launch_rederive(ctx->stream, s.buf[ctx->parity], s.capacity, ctx->d_types.d + s.type_idx, ctx->d_keys.d, s.nospin,
+        FW_HIP(ctx, fw_launch_rederive(ctx->stream, s.buf[ctx->parity], s.capacity, ctx->d_types + s.type_idx, ctx->d_keys, s.nospin,
                                        s.life_plane(), s.fifo_life, s.ring()));
         FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     uint32_t flags = (s.nospin ? FW_TYPE_NOSPIN : 0u) | (on ? FW_TYPE_DERIVED : 0u);
-    FW_HIP(ctx, hipMemcpy((char *)(ctx->d_types.d + s.type_idx) + offsetof(FwType, flags), &flags, sizeof flags, hipMemcpyHostToDevice));
+    FW_HIP(ctx, hipMemcpy((char *)(ctx->d_types + s.type_idx) + offsetof(FwType, flags), &flags, sizeof flags, hipMemcpyHostToDevice));
     s.derived = on;
     ctx->fc_ok = false, ctx->boxes_epoch = 0;
     if (s.range) ctx->r_force = true;  // (the range descriptors carry FW_TYPE_IDX_NOLIFE)
@@ -412,19 +401,14 @@ fw_status update_tile_table(fw_ctx *ctx) {
                 n_seg ? ctx->segs[0].ub : 0u);
     if (!dirty && ctx->d_tile_first) return FW_OK;
     ctx->fc_dirty = true;  // forecast sums are indexed by global tile: a new table invalidates whatever they hold
+    fw_status st;
     if (n_seg + 1 > ctx->tile_first_cap) {
-        fw_status st = sync(ctx);
-        if (st) return st;
+        if ((st = sync(ctx))) return st;
         const size_t ncap = (size_t)(n_seg + 1) * 2 + 64;
-        if (ctx->d_tile_first) hipFree(ctx->d_tile_first);
-        FW_HIP(ctx, hipMalloc((void **)&ctx->d_tile_first, ncap * sizeof(uint32_t)));
-        if (ctx->d_tile_keys) hipFree(ctx->d_tile_keys);
-        FW_HIP(ctx, hipMalloc((void **)&ctx->d_tile_keys, ncap * sizeof(uint2)));
+        ctx->tile_first_cap = 0;
+        if ((st = alloc_buf(ctx, ctx->d_tile_first, ncap)) || (st = alloc_buf(ctx, ctx->d_tile_keys, ncap))) return st;
         for (int i = 0; i < kTabRing; i++) {
-            if (ctx->h_tab[i]) hipHostFree(ctx->h_tab[i]);
-            FW_HIP(ctx, hipHostMalloc((void **)&ctx->h_tab[i], ncap * sizeof(uint32_t), hipHostMallocDefault));
-            if (ctx->h_keys[i]) hipHostFree(ctx->h_keys[i]);
-            FW_HIP(ctx, hipHostMalloc((void **)&ctx->h_keys[i], ncap * sizeof(uint2), hipHostMallocDefault));
+            if ((st = alloc_buf(ctx, ctx->h_tab[i], ncap, Mem::pinned)) || (st = alloc_buf(ctx, ctx->h_keys[i], ncap, Mem::pinned))) return st;
             ctx->tab_pending[i] = false;
         }
         ctx->tile_first_cap = ncap;
@@ -432,14 +416,12 @@ fw_status update_tile_table(fw_ctx *ctx) {
     uint32_t total_new = 0;
     for (uint32_t i = 0; i < n_seg; i++) total_new += ctx->tiles_dev[i];
     if (total_new > ctx->tile_desc_cap) {
-        fw_status st = sync(ctx);
-        if (st) return st;
+        if ((st = sync(ctx))) return st;
         const size_t ncap = (size_t)total_new * 2 + 256;
-        if (ctx->d_tile_desc) hipFree(ctx->d_tile_desc);
-        FW_HIP(ctx, hipMalloc((void **)&ctx->d_tile_desc, ncap * sizeof(uint4)));
+        ctx->tile_desc_cap = 0;
+        if ((st = alloc_buf(ctx, ctx->d_tile_desc, ncap))) return st;
         for (int i = 0; i < kTabRing; i++) {
-            if (ctx->h_desc[i]) hipHostFree(ctx->h_desc[i]);
-            FW_HIP(ctx, hipHostMalloc((void **)&ctx->h_desc[i], ncap * sizeof(uint4), hipHostMallocDefault));
+            if ((st = alloc_buf(ctx, ctx->h_desc[i], ncap, Mem::pinned))) return st;
             ctx->tab_pending[i] = false;
         }
         ctx->tile_desc_cap = ncap;

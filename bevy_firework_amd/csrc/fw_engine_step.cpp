@@ -201,7 +201,7 @@ fw_status take_op_slot(fw_ctx *ctx, FwFrame &fr) {
     if (ctx->param_bytes < off_ops0 + want_ops * sizeof(FwOp)) pst = ensure_param_ring(ctx, off_ops0 + (want_ops * 2 + 64) * sizeof(FwOp));
     if (!pst) pst = acquire_slot(ctx, &fr.pre_slot);
     if (pst) return pst;
-    fr.pre_hdr = (OpHdr *)ctx->h_param[fr.pre_slot];
+    fr.pre_hdr = (OpHdr *)ctx->h_param[fr.pre_slot].get();
     memset(fr.pre_hdr, 0, off_ops0);
     levels[0].g.borrow((FwOp *)(ctx->h_param[fr.pre_slot] + off_ops0), (ctx->param_bytes - off_ops0) / sizeof(FwOp));
     fr.pre_hdr_ok = true;
