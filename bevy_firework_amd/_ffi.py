@@ -65,6 +65,19 @@ def make_colliders(colliders):
     return arr
 
 
+class MeshCollider(C.Structure):
+    _fields_ = [("mesh", C.c_int32), ("layers", C.c_uint32), ("position", C.c_float * 3), ("rotation", C.c_float * 4)]
+
+
+def make_mesh_colliders(instances):
+    arr = (MeshCollider * max(len(instances), 1))()
+    for d, m in zip(arr, instances):
+        d.mesh, d.layers = int(m.mesh), int(m.layers) & 0xFFFFFFFF
+        d.position[:] = [float(x) for x in m.position]
+        d.rotation[:] = [float(x) for x in m.rotation]
+    return arr
+
+
 class ParticleSettings(C.Structure):
     _fields_ = [
         ("lifetime", RandF32),
@@ -221,6 +234,9 @@ SYMBOLS = [
     ("fw_ctx_stream", _P, [_P]),
     ("fw_ctx_synchronize", C.c_int, [_P]),
     ("fw_ctx_set_colliders", C.c_int, [_P, C.POINTER(Collider), C.c_uint32]),
+    ("fw_ctx_create_mesh", C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_int32)]),
+    ("fw_ctx_destroy_mesh", C.c_int, [_P, C.c_int32]),
+    ("fw_ctx_set_mesh_colliders", C.c_int, [_P, C.POINTER(MeshCollider), C.c_uint32]),
     ("fw_spawner_create", C.c_int, [_P, C.POINTER(SpawnerDesc), C.POINTER(C.c_int32)]),
     ("fw_spawner_update_settings", C.c_int, [_P, C.c_int32, C.POINTER(SpawnerDesc)]),
     ("fw_spawner_destroy", C.c_int, [_P, C.c_int32]),

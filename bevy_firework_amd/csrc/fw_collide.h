@@ -20,6 +20,18 @@ struct alignas(16) FwCollider {
     float half_extents[4]; // BOX; [1] = half the height of a CYLINDER / CONE (their axis is the local Y axis)
 };
 
+// one placed instance of a collider mesh (fw_ctx_set_mesh_colliders); the mesh's hierarchy and triangles in the layout of fw_bvh.h
+struct alignas(16) FwMeshInst {
+    float position[4];    // w: radius of a sphere around center[] that contains the placed mesh (set by the host: the wave skip)
+    float rotation[4];    // xyzw
+    float center[4];      // world-space centre of that sphere
+    const float4 *nodes;  // 2 per node, preorder
+    const float4 *tris;   // 3 per triangle, leaf order
+    uint32_t n_nodes;
+    uint32_t layers;
+    uint32_t pad_[2];
+};
+
 struct FwRayHit {
     float distance;
     fw_v3 normal;
@@ -210,9 +222,10 @@ FW_HD bool fw_ray_collider(const FwCollider &c, fw_v3 origin, fw_v3 dir, float m
     return true;
 }
 
-// SpatialQuery::cast_ray(origin, dir, max_distance, solid = true, filter): nearest hit, lowest index on ties
-FW_HD bool fw_cast_ray(const FwCollider *colliders, uint32_t n, uint32_t mask, fw_v3 origin, fw_v3 dir, float max_distance,
-                       FwRayHit *best) {
+// SpatialQuery::cast_ray(origin, dir, max_distance, solid = true, filter): nearest hit, lowest index on ties; the analytic
+// colliders first, then the mesh instances (include/firework_hip.h: fw_mesh_collider has the semantics and the tie rule)
+FW_HD bool fw_cast_ray(const FwCollider *colliders, uint32_t n, const FwMeshInst *meshes, uint32_t n_mesh, uint32_t mask,
+                       fw_v3 origin, fw_v3 dir, float max_distance, FwRayHit *best) {
     bool any = false;
     // (the best hit so far in scalars, written to *best once at the end: a struct updated through a pointer inside the loop
     // lived in scratch memory on the device)
@@ -238,13 +251,89 @@ FW_HD bool fw_cast_ray(const FwCollider *colliders, uint32_t n, uint32_t mask, f
             any = true;
         }
     }
+    for (uint32_t m = 0; m < n_mesh; m++) {
+        const FwMeshInst &M = meshes[m];
+        if (!(M.layers & mask)) continue;
+#ifdef __HIP_DEVICE_COMPILE__
+        {  // the wave skip of the analytic loop, against the sphere that contains the placed mesh
+            const fw_v3 dc = fw_sub3(origin, fw_v3{M.center[0], M.center[1], M.center[2]});
+            const float reach = M.position[3] + max_distance;
+            const bool far = fw_dot3(dc, dc) > reach * reach * 1.0001f + 1e-12f;
+            if (__ballot(!far) == 0ull) continue;
+        }
+#endif
+        const fw_v3 mpos{M.position[0], M.position[1], M.position[2]};
+        const fw_q4 q{M.rotation[0], M.rotation[1], M.rotation[2], M.rotation[3]};
+        const bool aligned = q.x == 0.0f && q.y == 0.0f && q.z == 0.0f && q.w == 1.0f;
+        const fw_v3 ol = aligned ? fw_sub3(origin, mpos) : fw_quat_mul_vec3(fw_q4{-q.x, -q.y, -q.z, q.w}, fw_sub3(origin, mpos));
+        const fw_v3 dl = aligned ? dir : fw_quat_mul_vec3(fw_q4{-q.x, -q.y, -q.z, q.w}, dir);
+        const float ix = 1.0f / dl.x, iy = 1.0f / dl.y, iz = 1.0f / dl.z;  // (a zero component takes the `== 0` arm below)
+        uint32_t bslot = 0xFFFFFFFFu, borig = 0xFFFFFFFFu;  // this instance's best triangle so far: slot, original index
+        // Stackless walk of the preorder hierarchy (fw_bvh.h): a box hit goes to i + 1 (a leaf: its triangles, then its escape),
+        // a miss to the escape.  Every step moves i forward (the max below holds even for a corrupt table), so the walk ends
+        // after at most n_nodes steps whatever the ray -- NaN included.  No per-lane stack: it would live in scratch memory.
+        for (uint32_t i = 0; i < M.n_nodes;) {
+            const float4 lo = M.nodes[2 * i], hi = M.nodes[2 * i + 1];
+            const uint32_t esc = __builtin_bit_cast(uint32_t, lo.w), leaf = __builtin_bit_cast(uint32_t, hi.w);
+            // slab test against the padded box, pruned by the best hit so far: only a box that starts beyond it is culled
+            // (the factor is slack for rounding; equal distances survive -- the tie rule needs them)
+            const float cut = (any ? bd : max_distance) * 1.0001f;
+            float tn = -INFINITY, tf = INFINITY;
+            bool hit = true;
+#define FW_NODE_SLAB(o, d, inv, l, h)                                          \
+    if ((d) == 0.0f) {                                                         \
+        if ((o) < (l) || (o) > (h)) hit = false;                               \
+    } else {                                                                   \
+        const float t1 = ((l) - (o)) * (inv), t2 = ((h) - (o)) * (inv);        \
+        tn = fmaxf(tn, fminf(t1, t2));                                         \
+        tf = fminf(tf, fmaxf(t1, t2));                                         \
+    }
+            FW_NODE_SLAB(ol.x, dl.x, ix, lo.x, hi.x)
+            FW_NODE_SLAB(ol.y, dl.y, iy, lo.y, hi.y)
+            FW_NODE_SLAB(ol.z, dl.z, iz, lo.z, hi.z)
+#undef FW_NODE_SLAB
+            hit = hit && tn <= tf && tf >= 0.0f && !(tn > cut);
+            uint32_t next = esc;
+            if (hit && leaf == 0u) next = i + 1u;
+            if (hit && leaf != 0u) {
+                const uint32_t first = leaf >> 4, last = first + (leaf & 15u);
+                for (uint32_t k = first; k < last; k++) {
+                    const float4 a = M.tris[3 * k], b = M.tris[3 * k + 1], c = M.tris[3 * k + 2];
+                    const fw_v3 e1{b.x, b.y, b.z}, e2{c.x, c.y, c.z};
+                    const fw_v3 p = fw_cross(dl, e2);
+                    const float det = fw_dot3(e1, p);
+                    if (det == 0.0f) continue;
+                    const float inv = 1.0f / det;
+                    const fw_v3 s = fw_sub3(ol, fw_v3{a.x, a.y, a.z});
+                    const float u = fw_dot3(s, p) * inv;
+                    const fw_v3 qv = fw_cross(s, e1);
+                    const float v = fw_dot3(dl, qv) * inv;
+                    const float t = fw_dot3(e2, qv) * inv;
+                    if (!(u >= 0.0f && v >= 0.0f && u + v <= 1.0f && t >= 0.0f && t <= max_distance)) continue;
+                    const uint32_t orig = __builtin_bit_cast(uint32_t, a.w);
+                    if (!any || t < bd || (t == bd && borig != 0xFFFFFFFFu && orig < borig)) {
+                        bd = t, any = true, bslot = k, borig = orig;
+                    }
+                }
+            }
+            i = next > i + 1u ? next : i + 1u;
+        }
+        if (bslot != 0xFFFFFFFFu) {  // the normal of this instance's best triangle, once
+            const float4 b = M.tris[3 * bslot + 1], c = M.tris[3 * bslot + 2];
+            fw_v3 nrm = fw_normalize3(fw_cross(fw_v3{b.x, b.y, b.z}, fw_v3{c.x, c.y, c.z}));
+            if (!aligned) nrm = fw_quat_mul_vec3(q, nrm);
+            if (fw_dot3(nrm, dir) > 0.0f) nrm = fw_v3{-nrm.x, -nrm.y, -nrm.z};
+            bnx = nrm.x, bny = nrm.y, bnz = nrm.z;
+        }
+    }
     *best = FwRayHit{bd, fw_v3{bnx, bny, bnz}};
     return any;
 }
 
 // particle_collision (src/core.rs:744-800).  Returns should_destroy; *pos / *vel are updated in place.
 FW_HD bool fw_particle_collision(fw_v3 *pos_io, fw_v3 *vel_io, float delta, float restitution, float friction,
-                                 bool destroy_on_collision, uint32_t mask, const FwCollider *colliders, uint32_t n) {
+                                 bool destroy_on_collision, uint32_t mask, const FwCollider *colliders, uint32_t n,
+                                 const FwMeshInst *meshes, uint32_t n_mesh) {
     fw_v3 pos = *pos_io, vel = *vel_io;
     const float orig_delta = delta;
     int n_steps = 0;
@@ -254,7 +343,7 @@ FW_HD bool fw_particle_collision(fw_v3 *pos_io, fw_v3 *vel_io, float delta, floa
         const float len = fw_len3(vel);
         const fw_v3 dir = (len < INFINITY && len > 0.0f) ? fw_v3{vel.x / len, vel.y / len, vel.z / len} : fw_v3{0.0f, 1.0f, 0.0f};
         FwRayHit hit;
-        if (fw_cast_ray(colliders, n, mask, pos, dir, fw_len3(vel) * delta, &hit)) {
+        if (fw_cast_ray(colliders, n, meshes, n_mesh, mask, pos, dir, fw_len3(vel) * delta, &hit)) {
             if (hit.distance == 0.0f) {  // core.rs:766-776
                 fw_v3 normal = hit.normal;
                 if (normal.x == 0.0f && normal.y == 0.0f && normal.z == 0.0f) {

@@ -23,6 +23,8 @@
 //                        tile table -- everything that can still be rolled back
 //   fw_engine_launch.cpp the enqueue of a planned frame (FwFrame): op tables, cohort replay, every launch, the frame's bookkeeping
 //   fw_engine_api.cpp    every other entry point of include/firework_hip.h (+ the debug hooks)
+//   fw_engine_mesh.cpp   the collider meshes: fw_ctx_create_mesh / fw_ctx_destroy_mesh / fw_ctx_set_mesh_colliders (the
+//                        hierarchy itself is built by fw_bvh.cpp, plain C++)
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -950,6 +952,21 @@ struct fw_ctx {
     HipEvent ev_coll[2];
     bool coll_pending[2] = {false, false};
     uint64_t coll_seq = 0;
+    // collider meshes (fw_engine_mesh.cpp): the meshes behind fw_mesh handles, and the instance set, staged and copied like the
+    // analytic set
+    struct MeshHost {
+        bool alive = false;
+        HipBuf<float4> nodes, tris;  // fw_bvh.h layout
+        uint32_t n_nodes = 0, n_tris = 0;
+        float center[3] = {0.0f, 0.0f, 0.0f}, radius = 0.0f;  // a sphere that contains the mesh, in its own frame
+    };
+    std::vector<MeshHost> meshes;
+    std::vector<fw_mesh> mesh_set;  // the meshes the current instance set places (fw_ctx_destroy_mesh refuses them)
+    HipBuf<FwMeshInst> d_mesh_inst;
+    HipBuf<FwMeshInst> h_mesh_inst[2];
+    HipEvent ev_mesh[2];
+    bool mesh_pending[2] = {false, false};
+    uint64_t mesh_seq = 0;
     HipBuf<float> d_aabb;      // 256 partial boxes of the AABB query
     HipBuf<float> h_aabb;      // pinned result {min.xyz, any, max.xyz, -}
     HipBuf<unsigned long long> d_total;

@@ -967,6 +967,8 @@ __global__ __launch_bounds__(FW_BLOCK) __attribute__((amdgpu_waves_per_eu(4))) v
 }
 
 // split mode, pass 1: survivors per tile
+// (MESH: the context has mesh instances -- the hierarchy walk costs registers, so the analytic-only form keeps its own)
+template <bool MESH>
 __global__ __launch_bounds__(FW_BLOCK) void fw_k_count(FwGlobals g, FwUpdateArgs a) {
     __shared__ uint32_t s_c[4];
     const uint32_t tile = blockIdx.x, tid = threadIdx.x;
@@ -992,7 +994,7 @@ __global__ __launch_bounds__(FW_BLOCK) void fw_k_count(FwGlobals g, FwUpdateArgs
                     const float4 q1 = fw_ld4(ib + FW_OFF_Q1(S.capacity), idx);
                     fw_v3 pos{q0.x, q0.y, q0.z}, vel{q1.x, q1.y, q1.z};
                     al = !fw_particle_collision(&pos, &vel, a.dt, T.coll_restitution, T.coll_friction, true, T.coll_mask,
-                                                g.colliders, g.n_colliders);
+                                                g.colliders, g.n_colliders, g.mesh_inst, MESH ? g.n_mesh_inst : 0u);
                 }
                 c += al ? 1u : 0u;
             }
@@ -1009,6 +1011,7 @@ __global__ __launch_bounds__(FW_BLOCK) void fw_k_count(FwGlobals g, FwUpdateArgs
 // [0, count + spawned + appended), everything materialised), output offset from fw_k_scan; per round: load, age test,
 // particle_collision for types that have collision settings, rank, integrate, store.  This is the feature path, not
 // the tuned one: no forecast, no fused spawn (the streaming kernels never run collisions and keep their registers).
+template <bool MESH>
 __global__ __launch_bounds__(FW_BLOCK) void fw_k_update_coll(FwGlobals g, FwUpdateArgs a) {
     constexpr int NW = FW_BLOCK / 64;
     __shared__ __attribute__((aligned(16))) float s_keys_lds[FW_KEYS_MAX];
@@ -1066,7 +1069,7 @@ __global__ __launch_bounds__(FW_BLOCK) void fw_k_update_coll(FwGlobals g, FwUpda
         bool killed = false;
         if (young && coll)
             killed = fw_particle_collision(&cpos, &cvel, a.dt, TC.coll_restitution, TC.coll_friction, coll_kill, TC.coll_mask,
-                                           g.colliders, g.n_colliders);
+                                           g.colliders, g.n_colliders, g.mesh_inst, MESH ? g.n_mesh_inst : 0u);
         const bool alive = young && !killed;
         const unsigned long long m = __ballot(alive);
         if (lane == 0) s_c[r & 1][wave] = (uint32_t)__popcll(m);
@@ -1160,11 +1163,17 @@ static void fw_launch_update_r(hipStream_t s, const FwGlobals &g, const FwUpdate
                                int spawn_form, int mode, hipEvent_t e0, hipEvent_t e1) {
     const dim3 grid(a.total_tiles), block(FW_TILE / R);
     if (mode == FW_MODE_SPLIT_COLL) {  // frames with colliding particle types: count (with collisions), scan, update
-        FW_LAUNCH_T(fw_k_count, grid, dim3(FW_BLOCK), s, e0, (hipEvent_t) nullptr, g, a);
-        hipLaunchKernelGGL(fw_k_scan, dim3(a.n_seg), dim3(FW_BLOCK), 0, s, g, a);
-        FW_LAUNCH_T(fw_k_update_coll, grid, dim3(FW_BLOCK), s, (hipEvent_t) nullptr, e1, g, a);
+        if (g.n_mesh_inst) {
+            FW_LAUNCH_T(fw_k_count<true>, grid, dim3(FW_BLOCK), s, e0, (hipEvent_t) nullptr, g, a);
+            hipLaunchKernelGGL(fw_k_scan, dim3(a.n_seg), dim3(FW_BLOCK), 0, s, g, a);
+            FW_LAUNCH_T(fw_k_update_coll<true>, grid, dim3(FW_BLOCK), s, (hipEvent_t) nullptr, e1, g, a);
+        } else {
+            FW_LAUNCH_T(fw_k_count<false>, grid, dim3(FW_BLOCK), s, e0, (hipEvent_t) nullptr, g, a);
+            hipLaunchKernelGGL(fw_k_scan, dim3(a.n_seg), dim3(FW_BLOCK), 0, s, g, a);
+            FW_LAUNCH_T(fw_k_update_coll<false>, grid, dim3(FW_BLOCK), s, (hipEvent_t) nullptr, e1, g, a);
+        }
     } else if (mode == FW_MODE_SPLIT) {  // debugging / A-B mode: three launches, no inter-workgroup traffic
-        FW_LAUNCH_T(fw_k_count, grid, dim3(FW_BLOCK), s, e0, (hipEvent_t) nullptr, g, a);
+        FW_LAUNCH_T(fw_k_count<false>, grid, dim3(FW_BLOCK), s, e0, (hipEvent_t) nullptr, g, a);
         hipLaunchKernelGGL(fw_k_scan, dim3(a.n_seg), dim3(FW_BLOCK), 0, s, g, a);
         FW_LAUNCH_T((fw_k_update<false, FW_SPAWN_NONE, R, INST, SUMS>), grid, block, s, (hipEvent_t) nullptr, e1, g, a, io);
     } else if (a.use_stream && a.fc_in && a.fc_out) {  // forecast frame: streaming schedule

@@ -45,7 +45,7 @@ struct FwCollArm {
     float restitution, friction;
     uint32_t mask;
 };
-template <bool COLL>
+template <int COLL>
 __device__ __forceinline__ FwCollArm fw_coll_arm(const FwGlobals &g, uint32_t type_idx) {
     if constexpr (COLL) {
         const FwTypeColl TC = g.type_coll[type_idx];
@@ -55,12 +55,13 @@ __device__ __forceinline__ FwCollArm fw_coll_arm(const FwGlobals &g, uint32_t ty
     }
 }
 // position / velocity after particle_collision (a particle that meets nothing comes out as position + velocity * dt, velocity)
-template <bool COLL>
+template <int COLL>
 __device__ __forceinline__ void fw_coll_step(const FwGlobals &g, const FwCollArm &A, bool active, float dt, float4 q0, float4 q1,
                                              fw_v3 *cpos, fw_v3 *cvel) {
     *cpos = fw_v3{q0.x, q0.y, q0.z}, *cvel = fw_v3{q1.x, q1.y, q1.z};
     if constexpr (COLL) {
-        if (A.on && active) fw_particle_collision(cpos, cvel, dt, A.restitution, A.friction, false, A.mask, g.colliders, g.n_colliders);
+        if (A.on && active) fw_particle_collision(cpos, cvel, dt, A.restitution, A.friction, false, A.mask, g.colliders, g.n_colliders, g.mesh_inst,
+                                                  COLL == 2 ? g.n_mesh_inst : 0u);
     }
 }
 
@@ -219,7 +220,7 @@ __device__ __forceinline__ void fw_fifo_nest_parents(const FwGlobals &g, const F
 // many waves work at once, not by memory -- the reference's own stress_test_collision (157k particles) is 154 workgroups of
 // four rounds, fewer than the chip has CUs, or 615 of one.
 // NEST: some Nested entry runs inside this launch (FwFifoArgs::nest): the parents' ring tiles run fw_fifo_nest_parents first
-template <bool INST, int WM, int NT, bool COLL, int TR, bool NEST>
+template <bool INST, int WM, int NT, int COLL, int TR, bool NEST>
 __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl) {
     constexpr int BLK = FW_BLOCK;
     constexpr int NW = BLK / 64;
@@ -491,7 +492,7 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
 #ifndef FW_FIFO_WAVES
 #define FW_FIFO_WAVES 1
 #endif
-template <bool INST, int WM, int NT = 0, bool COLL = false, int TR = FW_ROUNDS>
+template <bool INST, int WM, int NT = 0, int COLL = 0, int TR = FW_ROUNDS>
 __global__ __launch_bounds__(FW_BLOCK) __attribute__((amdgpu_waves_per_eu((!INST && !COLL && TR == FW_ROUNDS) ? FW_FIFO_WAVES : 1)))
 void fw_k_update_fifo(FwGlobals g, FwFifoArgs a, FwInlineOps inl) {
     fw_update_fifo_body<INST, WM, NT, COLL, TR, false>(g, a, inl);
@@ -585,7 +586,7 @@ uint32_t fw_range_young_tile(void) { return FW_RANGE_YR * FW_BLOCK; }
 // YRP: rounds of a YOUNG workgroup of a four-round launch (FwRangeArgs::young_rounds): FW_RANGE_YR, or 2 -- young tiles of 512
 // slots -- for launches of large segments (round 3 measured the fixed choices: +4 % at 16M particles in 64 Ki-particle segments,
 // -18 % on 8192-particle segments; the host now chooses per launch from the mean segment size)
-template <bool ALLNOSPIN, bool INST, int NT, bool COLL = false, int TR = FW_ROUNDS, int YRP = FW_RANGE_YR>
+template <bool ALLNOSPIN, bool INST, int NT, int COLL = 0, int TR = FW_ROUNDS, int YRP = FW_RANGE_YR>
 // (launches with a type that can turn, four-round tiles: pinned at 4 waves per SIMD -- with the OLD tiles' rotation planes parked in
 // LDS the kernel is 6 registers past the step and fits when asked to; not the forms that also write instance records: their 50 KB of
 // LDS allow three workgroups per CU anyway)
@@ -1066,14 +1067,26 @@ hipError_t fw_launch_update_fifo(hipStream_t s, const FwGlobals &g, const FwFifo
     }
     if (a.any_coll) {  // some ring of the launch collides (FwCollArm): generic write mask, plain or fully non-temporal
         // (one round per workgroup -- ring tiles of FW_FIFO_COLL_TILE slots: the host laid the launch out on that grid)
+        // (COLL = 2: the context has mesh instances -- the hierarchy walk costs registers, so the analytic-only form keeps its own)
+        if (g.n_mesh_inst) {
+            if (a.any_inst && nt == 2)
+                FW_LAUNCH_T((fw_k_update_fifo<true, -1, 2, 2, 1>), grid, block, s, e0, e1, g, a, inl);
+            else if (a.any_inst)
+                FW_LAUNCH_T((fw_k_update_fifo<true, -1, 0, 2, 1>), grid, block, s, e0, e1, g, a, inl);
+            else if (nt == 2)
+                FW_LAUNCH_T((fw_k_update_fifo<false, -1, 2, 2, 1>), grid, block, s, e0, e1, g, a, inl);
+            else
+                FW_LAUNCH_T((fw_k_update_fifo<false, -1, 0, 2, 1>), grid, block, s, e0, e1, g, a, inl);
+            return hipGetLastError();
+        }
         if (a.any_inst && nt == 2)
-            FW_LAUNCH_T((fw_k_update_fifo<true, -1, 2, true, 1>), grid, block, s, e0, e1, g, a, inl);
+            FW_LAUNCH_T((fw_k_update_fifo<true, -1, 2, 1, 1>), grid, block, s, e0, e1, g, a, inl);
         else if (a.any_inst)
-            FW_LAUNCH_T((fw_k_update_fifo<true, -1, 0, true, 1>), grid, block, s, e0, e1, g, a, inl);
+            FW_LAUNCH_T((fw_k_update_fifo<true, -1, 0, 1, 1>), grid, block, s, e0, e1, g, a, inl);
         else if (nt == 2)
-            FW_LAUNCH_T((fw_k_update_fifo<false, -1, 2, true, 1>), grid, block, s, e0, e1, g, a, inl);
+            FW_LAUNCH_T((fw_k_update_fifo<false, -1, 2, 1, 1>), grid, block, s, e0, e1, g, a, inl);
         else
-            FW_LAUNCH_T((fw_k_update_fifo<false, -1, 0, true, 1>), grid, block, s, e0, e1, g, a, inl);
+            FW_LAUNCH_T((fw_k_update_fifo<false, -1, 0, 1, 1>), grid, block, s, e0, e1, g, a, inl);
         return hipGetLastError();
     }
     if (a.small_tiles) {  // a launch of a few hundred four-round workgroups at most: one round each instead (generic write mask)
@@ -1121,14 +1134,25 @@ static void fw_launch_update_range_t(hipStream_t s, const FwGlobals &g, const Fw
                                      hipEvent_t e1) {
     const dim3 grid(a.total_tiles), block(FW_BLOCK);
     if constexpr (NT != 1) {
+        if (a.any_coll && g.n_mesh_inst) {  // ... against a world with mesh instances (COLL = 2, as in fw_launch_update_fifo)
+            if (a.any_inst) {
+                if (all_nospin) FW_LAUNCH_T((fw_k_update_range<true, true, NT, 2, 1>), grid, block, s, e0, e1, g, a);
+                else FW_LAUNCH_T((fw_k_update_range<false, true, NT, 2, 1>), grid, block, s, e0, e1, g, a);
+            } else if (all_nospin) {
+                FW_LAUNCH_T((fw_k_update_range<true, false, NT, 2, 1>), grid, block, s, e0, e1, g, a);
+            } else {
+                FW_LAUNCH_T((fw_k_update_range<false, false, NT, 2, 1>), grid, block, s, e0, e1, g, a);
+            }
+            return;
+        }
         if (a.any_coll) {  // some range ring of the launch collides (FwCollArm): one-round tiles, the host laid the launch out on them
             if (a.any_inst) {
-                if (all_nospin) FW_LAUNCH_T((fw_k_update_range<true, true, NT, true, 1>), grid, block, s, e0, e1, g, a);
-                else FW_LAUNCH_T((fw_k_update_range<false, true, NT, true, 1>), grid, block, s, e0, e1, g, a);
+                if (all_nospin) FW_LAUNCH_T((fw_k_update_range<true, true, NT, 1, 1>), grid, block, s, e0, e1, g, a);
+                else FW_LAUNCH_T((fw_k_update_range<false, true, NT, 1, 1>), grid, block, s, e0, e1, g, a);
             } else if (all_nospin) {
-                FW_LAUNCH_T((fw_k_update_range<true, false, NT, true, 1>), grid, block, s, e0, e1, g, a);
+                FW_LAUNCH_T((fw_k_update_range<true, false, NT, 1, 1>), grid, block, s, e0, e1, g, a);
             } else {
-                FW_LAUNCH_T((fw_k_update_range<false, false, NT, true, 1>), grid, block, s, e0, e1, g, a);
+                FW_LAUNCH_T((fw_k_update_range<false, false, NT, 1, 1>), grid, block, s, e0, e1, g, a);
             }
             return;
         }

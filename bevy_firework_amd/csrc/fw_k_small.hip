@@ -39,7 +39,7 @@
 // (COLL: some type of the launch has collision settings -- core.rs:607-643: a particle that survives the age test is moved by
 // particle_collision instead of the plain Euler step, and destroyed by it when the type says destroy_on_collision; the stable
 // compaction takes a destroyed particle out like one that died of age, so ANY colliding type can live here)
-template <bool WIDE, bool INST, bool COLL>
+template <bool WIDE, bool INST, int COLL>
 __device__ __forceinline__ void fw_small_type(const FwGlobals &g, const FwSmallArgs &a, uint32_t seg, float *s_keys, uint32_t (*s_cnt)[FW_BLOCK / 64],
                                               unsigned long long &entered, unsigned long long &live) {
     constexpr int NW = FW_BLOCK / 64;
@@ -168,7 +168,8 @@ __device__ __forceinline__ void fw_small_type(const FwGlobals &g, const FwSmallA
         fw_v3 cpos{q0.x, q0.y, q0.z}, cvel{q1.x, q1.y, q1.z};
         bool killed = false;
         if (COLL && young && coll)
-            killed = fw_particle_collision(&cpos, &cvel, a.dt, TC.coll_restitution, TC.coll_friction, coll_kill, TC.coll_mask, g.colliders, g.n_colliders);
+            killed = fw_particle_collision(&cpos, &cvel, a.dt, TC.coll_restitution, TC.coll_friction, coll_kill, TC.coll_mask, g.colliders, g.n_colliders, g.mesh_inst,
+                                           COLL == 2 ? g.n_mesh_inst : 0u);
         const bool alive = young && !killed;
         uint32_t o;
         place(alive, &o);
@@ -204,7 +205,8 @@ __device__ __forceinline__ void fw_small_type(const FwGlobals &g, const FwSmallA
             fw_v3 cpos{so.q0.x, so.q0.y, so.q0.z}, cvel{so.q1.x, so.q1.y, so.q1.z};
             bool killed = false;
             if (COLL && young && coll)
-                killed = fw_particle_collision(&cpos, &cvel, a.dt, TC.coll_restitution, TC.coll_friction, coll_kill, TC.coll_mask, g.colliders, g.n_colliders);
+                killed = fw_particle_collision(&cpos, &cvel, a.dt, TC.coll_restitution, TC.coll_friction, coll_kill, TC.coll_mask, g.colliders, g.n_colliders, g.mesh_inst,
+                                           COLL == 2 ? g.n_mesh_inst : 0u);
             const bool alive = young && !killed;
             uint32_t o;
             place(alive, &o);
@@ -226,7 +228,7 @@ __device__ __forceinline__ void fw_small_type(const FwGlobals &g, const FwSmallA
     entered = n_tot, live = run;
 }
 
-template <bool INST, bool COLL>
+template <bool INST, int COLL>
 __global__ __launch_bounds__(FW_BLOCK) void fw_k_update_small(FwGlobals g, FwSmallArgs a) {
     constexpr int NW = FW_BLOCK / 64;
     __shared__ __attribute__((aligned(16))) float s_keys_all[NW][FW_KEYS_MAX];
@@ -266,8 +268,11 @@ hipError_t fw_launch_update_small(hipStream_t s, const FwGlobals &g, const FwSma
     if (!a.n) return hipSuccess;
     const uint32_t nw = FW_BLOCK / 64;
     const dim3 grid((a.n_narrow + nw - 1) / nw + (a.n - a.n_narrow)), block(FW_BLOCK);
-    if (a.any_coll && a.any_inst) FW_LAUNCH_T((fw_k_update_small<true, true>), grid, block, s, e0, e1, g, a);
-    else if (a.any_coll) FW_LAUNCH_T((fw_k_update_small<false, true>), grid, block, s, e0, e1, g, a);
+    // (COLL = 2: the context has mesh instances -- the hierarchy walk costs registers, so the analytic-only form keeps its own)
+    if (a.any_coll && g.n_mesh_inst && a.any_inst) FW_LAUNCH_T((fw_k_update_small<true, 2>), grid, block, s, e0, e1, g, a);
+    else if (a.any_coll && g.n_mesh_inst) FW_LAUNCH_T((fw_k_update_small<false, 2>), grid, block, s, e0, e1, g, a);
+    else if (a.any_coll && a.any_inst) FW_LAUNCH_T((fw_k_update_small<true, 1>), grid, block, s, e0, e1, g, a);
+    else if (a.any_coll) FW_LAUNCH_T((fw_k_update_small<false, 1>), grid, block, s, e0, e1, g, a);
     else if (a.any_inst) FW_LAUNCH_T((fw_k_update_small<true, false>), grid, block, s, e0, e1, g, a);
     else FW_LAUNCH_T((fw_k_update_small<false, false>), grid, block, s, e0, e1, g, a);
     return hipGetLastError();

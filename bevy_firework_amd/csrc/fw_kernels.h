@@ -69,6 +69,8 @@ struct FwGlobals {
 #endif
     const FwCollider *colliders;         // the world particle_collision casts its rays into (fw_ctx_set_colliders)
     uint32_t n_colliders;
+    const FwMeshInst *mesh_inst;         // ... and its mesh instances (fw_ctx_set_mesh_colliders)
+    uint32_t n_mesh_inst;
 };
 
 struct FwUpdateArgs {

@@ -271,6 +271,18 @@ class Collider:
                         half_extents=(0.0, float(height) * 0.5, 0.0), layers=layers)
 
 
+@dataclass(frozen=True)
+class MeshCollider:
+    """One placed instance of a triangle mesh of the collider world (avian's Collider::trimesh and the shapes that become
+    triangles): ``mesh`` is a handle from ParticleSystem.create_mesh; the mesh's scale is baked into its vertices
+    (include/firework_hip.h: fw_mesh_collider has the ray-cast semantics -- a two-sided surface, no inside)."""
+
+    mesh: int
+    position: Vec3 = (0.0, 0.0, 0.0)
+    rotation: Quat = QUAT_IDENTITY
+    layers: int = 1
+
+
 @dataclass
 class ParticleSettings:
     """ParticleSettings (core.rs:99-142); defaults core.rs:187-211.

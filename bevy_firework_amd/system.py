@@ -221,6 +221,24 @@ class ParticleSystem:
         colliders (settings.Collider) standing in for avian's SpatialQuery."""
         self._check(self._lib.fw_ctx_set_colliders(self._ctx, _ffi.make_colliders(colliders), len(colliders)))
 
+    def create_mesh(self, vertices, indices) -> int:
+        """Uploads a triangle mesh of the collider world (vertices [n, 3] float32, indices [m, 3] uint32) and returns its
+        handle; place it with set_mesh_colliders.  Zero-area triangles are dropped; bad input raises FW_EINVAL."""
+        xyz = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+        idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1, 3)
+        h = C.c_int32(-1)
+        self._check(self._lib.fw_ctx_create_mesh(self._ctx, xyz.ctypes.data_as(C.c_void_p), len(xyz),
+                                                 idx.ctypes.data_as(C.c_void_p), len(idx), C.byref(h)))
+        return int(h.value)
+
+    def destroy_mesh(self, mesh: int) -> None:
+        """Frees a mesh the current instance set does not place (waits for the frames in flight)."""
+        self._check(self._lib.fw_ctx_destroy_mesh(self._ctx, int(mesh)))
+
+    def set_mesh_colliders(self, instances) -> None:
+        """Replaces the placed meshes (settings.MeshCollider) of the collider world; all-or-nothing, no synchronisation."""
+        self._check(self._lib.fw_ctx_set_mesh_colliders(self._ctx, _ffi.make_mesh_colliders(instances), len(instances)))
+
     # -- ECS-like surface ------------------------------------------------------------------------
     def spawn(self, spawner: S.ParticleSpawner, transform: Optional[S.Transform] = None,
               global_transform: Optional[S.Transform] = None, modifier: Optional[S.EffectModifier] = None,

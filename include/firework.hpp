@@ -15,7 +15,7 @@
 //   ParticleSpawnerData        src/core.rs:269-303  firework::ParticleSpawnerData (queue_particles, active, particles)
 //   ParticleData               src/core.rs:305-321  fw_particle
 //   EffectModifier             src/core.rs:323-336  firework::EffectModifier
-//   ParticleCollisionSettings  src/core.rs:240-248  firework::ParticleCollisionSettings (+ firework::Collider, set_colliders)
+//   ParticleCollisionSettings  src/core.rs:240-248  firework::ParticleCollisionSettings (+ firework::Collider, set_colliders, MeshCollider, create_mesh)
 //
 // Header-only; link with -lfirework_hip.  No simulation arithmetic lives here.
 #pragma once
@@ -177,6 +177,15 @@ struct Collider {
         Collider c; c.kind = FW_COLLIDER_CONE, c.position = center, c.radius = radius, c.half_extents = Vec3{0, height * 0.5f, 0};
         c.rotation = rotation, c.layers = layers; return c;
     }
+};
+
+// One placed instance of a triangle mesh of the collider world (fw_mesh_collider): `mesh` comes from
+// ParticleSystemPlugin::create_mesh, the mesh's scale is baked into its vertices.
+struct MeshCollider {
+    fw_mesh mesh = -1;
+    Vec3 position{};
+    Quat rotation{};
+    uint32_t layers = 1;
 };
 
 struct ParticleSettings {  // core.rs:99-142, defaults core.rs:187-211
@@ -360,6 +369,26 @@ class ParticleSystemPlugin {
             d.half_extents[0] = c.half_extents.x, d.half_extents[1] = c.half_extents.y, d.half_extents[2] = c.half_extents.z;
         }
         check(fw_ctx_set_colliders(ctx_, v.data(), (uint32_t)v.size()));
+    }
+
+    // triangle meshes of the collider world (fw_ctx_create_mesh): xyz = 3 floats per vertex, indices = 3 per triangle
+    fw_mesh create_mesh(const std::vector<float> &xyz, const std::vector<uint32_t> &indices) {
+        fw_mesh m = -1;
+        check(fw_ctx_create_mesh(ctx_, xyz.data(), (uint32_t)(xyz.size() / 3), indices.data(), (uint32_t)(indices.size() / 3), &m));
+        return m;
+    }
+    void destroy_mesh(fw_mesh m) { check(fw_ctx_destroy_mesh(ctx_, m)); }
+    void set_mesh_colliders(const std::vector<MeshCollider> &ms) {
+        std::vector<fw_mesh_collider> v(ms.size());
+        for (size_t i = 0; i < ms.size(); i++) {
+            const MeshCollider &m = ms[i];
+            v[i] = fw_mesh_collider{};
+            v[i].mesh = m.mesh, v[i].layers = m.layers;
+            v[i].position[0] = m.position.x, v[i].position[1] = m.position.y, v[i].position[2] = m.position.z;
+            v[i].rotation[0] = m.rotation.x, v[i].rotation[1] = m.rotation.y, v[i].rotation[2] = m.rotation.z;
+            v[i].rotation[3] = m.rotation.w;
+        }
+        check(fw_ctx_set_mesh_colliders(ctx_, v.data(), (uint32_t)v.size()));
     }
 
     // update_aabbs (render.rs:677-703) fused into the update: every frame leaves per-tile boxes, ParticleSpawnerData::aabb

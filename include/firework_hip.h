@@ -137,6 +137,29 @@ typedef struct fw_collider {
     float half_extents[3];  /* BOX; [1] = half the height of a CYLINDER / CONE */
 } fw_collider;
 
+/* Triangle meshes (avian's Collider::trimesh / heightfield / convex hulls, as triangles): a mesh is uploaded once and placed
+ * any number of times by instances.  Ray-cast semantics (ours, like those of the analytic kinds; all fp32, no fused a*b+c):
+ *   SURFACE   a mesh is a two-sided surface with no interior: no distance-0 "inside" hit, no push-out.
+ *   FRAME     the ray is taken into the instance's frame once: o = R^-1 (origin - position), d = R^-1 dir (R = rotation, xyzw;
+ *             the identity rotation skips both products).  The mesh is not scaled, so the distance t needs no conversion.
+ *   TRIANGLE  v0 as given, e1 = v1 - v0, e2 = v2 - v0 (fp32, at creation); Moeller-Trumbore in this order:
+ *               p = cross(d, e2); det = dot(e1, p); det == 0 is a miss; inv = 1 / det; s = o - v0; u = dot(s, p) * inv;
+ *               q = cross(s, e1); v = dot(d, q) * inv; t = dot(e2, q) * inv
+ *             (dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z; cross(a, b) = (a.y b.z - b.y a.z, a.z b.x - b.z a.x, a.x b.y - b.x a.y));
+ *             a hit needs u >= 0, v >= 0, u + v <= 1 and 0 <= t <= max_distance.
+ *   NORMAL    c = cross(e1, e2); n = c * (1 / sqrt(dot(c, c))), rotated by R, and negated when dot(n, dir) > 0.
+ *   TIES      the nearest hit wins; at equal distance analytic colliders come before mesh instances, lower instance indices
+ *             before higher ones, and within an instance the lower ORIGINAL triangle index (position in `indices`) wins.
+ *   FILTER    an instance takes part when (filter_mask & layers) != 0, as a collider does.
+ * Triangles whose c has dot(c, c) == 0 (or not finite) -- zero area -- are dropped at creation; no other triangle is. */
+typedef int32_t fw_mesh; /* handle >= 0, per context */
+typedef struct fw_mesh_collider { /* one placed instance of a mesh */
+    fw_mesh mesh;
+    uint32_t layers;   /* membership bits, as fw_collider.layers */
+    float position[3];
+    float rotation[4]; /* xyzw, a unit quaternion; scale is baked into the mesh's vertices */
+} fw_mesh_collider;
+
 enum { FW_PACING_ONESHOT = 0, FW_PACING_ONDEMAND = 1, FW_PACING_COUNT_OVER_DURATION = 2 }; /* core.rs:12-29 */
 enum { FW_MODE_GLOBAL = 0, FW_MODE_NESTED = 1 };                                           /* core.rs:47-54 */
 enum { FW_SHAPE_POINT = 0, FW_SHAPE_SPHERE = 1, FW_SHAPE_CIRCLE = 2 };                     /* emission_shape.rs:7-15 */
@@ -207,6 +230,18 @@ fw_status fw_ctx_synchronize(fw_ctx *ctx);
  * reference queries the live physics world every frame, core.rs:756-765 -- moving colliders cost one small copy per
  * frame).  Only a set larger than any before reallocates the device table, which waits for the frames in flight. */
 fw_status fw_ctx_set_colliders(fw_ctx *ctx, const fw_collider *colliders, uint32_t n);
+
+/* Meshes of the collider world (semantics next to fw_mesh_collider).  Creating one validates it -- FW_EINVAL for no vertices,
+ * no triangles, an index >= n_vertices, a non-finite vertex, or no triangle left once the zero-area ones are dropped -- builds
+ * its bounding-volume hierarchy on the host and uploads it once (synchronises).  xyz[n_vertices][3], indices[n_triangles][3]. */
+fw_status fw_ctx_create_mesh(fw_ctx *ctx, const float *xyz, uint32_t n_vertices, const uint32_t *indices, uint32_t n_triangles,
+                             fw_mesh *out);
+/* FW_EINVAL while the current instance set places the mesh; otherwise waits for the frames in flight and frees it */
+fw_status fw_ctx_destroy_mesh(fw_ctx *ctx, fw_mesh mesh);
+/* replaces the context's mesh instances (copied; n = 0 clears them); all-or-nothing: an unknown mesh handle -> FW_EINVAL and
+ * the previous set stays.  Like the analytic set it takes effect at the next fw_step and does not synchronise: the set travels
+ * as one copy in the context's stream, and only a set larger than any before waits for the frames in flight. */
+fw_status fw_ctx_set_mesh_colliders(fw_ctx *ctx, const fw_mesh_collider *instances, uint32_t n);
 
 /* ---- spawners ----------------------------------------------------------------- */
 /* ParticleSpawner insertion + first sync_spawner_data (core.rs:343-365) */

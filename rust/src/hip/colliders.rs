@@ -1,16 +1,19 @@
 //! The world `particle_collision` casts its rays into (core.rs:744-800), mirrored into the backend's device-resident set of
-//! analytic colliders (UNVERIFIED SOURCE: no Rust toolchain in the build image).
+//! analytic colliders and triangle meshes (UNVERIFIED SOURCE: no Rust toolchain in the build image).
 //!
 //! The reference asks avian's `SpatialQuery` (arbitrary parry shapes behind a CPU broadphase, core.rs:756-765).  The backend
-//! keeps planes, spheres, oriented boxes, cylinders and cones on the GPU (`fw_collider`; ray-cast semantics in
-//! `include/firework_hip.h`).  Entities opt in with the `ParticleCollider` marker; the set is replaced EVERY frame -- the call
-//! does not wait for the frames in flight, the new set travels as one small copy in the context's stream -- so moving bodies
-//! cost what the reference's per-frame query costs.  Shapes without an analytic counterpart (meshes, compounds, capsules) are
-//! skipped: particles do not collide with them on this path.
+//! keeps planes, spheres, oriented boxes, cylinders and cones on the GPU (`fw_collider`), and triangle meshes placed by
+//! instances (`fw_mesh_collider`; ray-cast semantics of both in `include/firework_hip.h`).  Entities opt in with the
+//! `ParticleCollider` marker; both sets are replaced EVERY frame -- the calls do not wait for the frames in flight, a new set
+//! travels as one small copy in the context's stream -- so moving bodies cost what the reference's per-frame query costs.
+//! `Collider::trimesh*`, heightfields and convex polyhedra become meshes: their triangles, scaled by the collider's scale, are
+//! uploaded once per (entity, scale) and freed when the entity (or its collider) goes away.  Capsules and compound shapes have
+//! no counterpart and are still skipped: particles do not collide with them on this path.
 use super::ffi::*;
 use super::HipBackend;
 use avian3d::prelude::*;
 use bevy::prelude::*;
+use std::collections::HashMap;
 
 /// "particles bounce off this collider"
 #[derive(Component, Default)]
@@ -23,18 +26,64 @@ pub struct ParticleCollider;
 #[derive(Resource, Default)]
 pub struct ParticleColliderExclusions(pub bevy::platform::collections::HashSet<Entity>);
 
+/// The device meshes of the mesh-shaped colliders, by entity: the scale they were baked with and the handle
+/// (`fw_ctx_create_mesh`).  A system-local: the cache lives and dies with `hip_sync_colliders`.
+#[derive(Default)]
+pub struct MeshCache(HashMap<Entity, ([u32; 3], fw_mesh)>);
+
+/// The triangles of a mesh-shaped collider in its own frame (unscaled), or None for every other shape.
+fn mesh_triangles(shape: &SharedShape) -> Option<(Vec<[f32; 3]>, Vec<[u32; 3]>)> {
+    let pts = |v: &[avian3d::parry::math::Point<f32>]| v.iter().map(|p| [p.x, p.y, p.z]).collect::<Vec<_>>();
+    if let Some(m) = shape.as_trimesh() {
+        Some((pts(m.vertices()), m.indices().to_vec()))                                  // Collider::trimesh*
+    } else if let Some(h) = shape.as_heightfield() {
+        let (v, i) = h.to_trimesh();                                                     // Collider::heightfield
+        Some((pts(&v), i))
+    } else if let Some(c) = shape.as_convex_polyhedron() {
+        let (v, i) = c.to_trimesh();                                                     // Collider::convex_hull / convex_decomposition pieces
+        Some((pts(&v), i))
+    } else {
+        None
+    }
+}
+
 pub fn hip_sync_colliders(
-    backend: NonSend<HipBackend>, excluded: Option<Res<ParticleColliderExclusions>>,
-    q: Query<(Entity, &Collider, &GlobalTransform, Option<&CollisionLayers>), With<ParticleCollider>>,
+    backend: NonSend<HipBackend>, excluded: Option<Res<ParticleColliderExclusions>>, mut meshes: Local<MeshCache>,
+    q: Query<(Entity, Ref<Collider>, &GlobalTransform, Option<&CollisionLayers>), With<ParticleCollider>>,
 ) {
     let mut set = Vec::<fw_collider>::new();
+    let mut insts = Vec::<fw_mesh_collider>::new();
+    let mut stale = Vec::<fw_mesh>::new(); // meshes the new instance set no longer places: freed once it is in
+    let mut seen = Vec::<Entity>::new();
     for (entity, collider, gt, layers) in &q {
         let t = gt.compute_transform();
         let out = excluded.as_ref().is_some_and(|x| x.0.contains(&entity));
+        let layers = if out { 0 } else { layers.map_or(1, |l| l.memberships.0) };
         let base = fw_collider {
-            kind: 0, layers: if out { 0 } else { layers.map_or(1, |l| l.memberships.0) }, position: t.translation.to_array(), rotation: t.rotation.to_array(),
+            kind: 0, layers, position: t.translation.to_array(), rotation: t.rotation.to_array(),
             normal: [0., 1., 0.], radius: 0., half_extents: [0.; 3],
         };
+        // a mesh-shaped collider: its triangles with the collider's scale baked in (instances carry no scale), cached
+        let scale = collider.scale();
+        let key = [scale.x.to_bits(), scale.y.to_bits(), scale.z.to_bits()];
+        let cached = meshes.0.get(&entity).copied().filter(|(k, _)| *k == key && !collider.is_changed());
+        let mesh = match cached {
+            Some((_, m)) => Some(m),
+            None => mesh_triangles(collider.shape()).and_then(|(v, i)| {
+                let xyz: Vec<f32> = v.iter().flat_map(|p| [p[0] * scale.x, p[1] * scale.y, p[2] * scale.z]).collect();
+                let idx: Vec<u32> = i.iter().flatten().copied().collect();
+                let mut m: fw_mesh = -1;
+                let st = unsafe { fw_ctx_create_mesh(backend.ctx, xyz.as_ptr(), v.len() as u32, idx.as_ptr(), i.len() as u32, &mut m) };
+                if backend.check(st).is_err() { return None; } // (FW_EINVAL: no triangle of non-zero area -- nothing to collide with)
+                if let Some((_, old)) = meshes.0.insert(entity, (key, m)) { stale.push(old); }
+                Some(m)
+            }),
+        };
+        if let Some(m) = mesh {
+            seen.push(entity);
+            insts.push(fw_mesh_collider { mesh: m, layers, position: base.position, rotation: base.rotation });
+            continue;
+        }
         let shape = collider.shape_scaled();
         if let Some(b) = shape.as_ball() {
             set.push(fw_collider { kind: 1, radius: b.radius, ..base });                                          // Collider::sphere
@@ -49,5 +98,13 @@ pub fn hip_sync_colliders(
             set.push(fw_collider { kind: 0, normal: n.to_array(), ..base });                                       // ::half_space
         }
     }
-    unsafe { let _ = backend.check(fw_ctx_set_colliders(backend.ctx, set.as_ptr(), set.len() as u32)); }
+    // entities that left the query (despawned, marker or collider removed, or no longer mesh-shaped): their meshes go too
+    meshes.0.retain(|e, (_, m)| { let keep = seen.contains(e); if !keep { stale.push(*m); } keep });
+    unsafe {
+        let _ = backend.check(fw_ctx_set_colliders(backend.ctx, set.as_ptr(), set.len() as u32));
+        let _ = backend.check(fw_ctx_set_mesh_colliders(backend.ctx, insts.as_ptr(), insts.len() as u32));
+        // (fw_ctx_destroy_mesh refuses a mesh the current set places and waits for the frames in flight: only after the new
+        // set, and only when a mesh-shaped collider went away or changed)
+        for m in stale { let _ = backend.check(fw_ctx_destroy_mesh(backend.ctx, m)); }
+    }
 }

@@ -29,6 +29,10 @@ pub type fw_spawner = i32;
     pub kind: i32, pub layers: u32, pub position: [f32; 3], pub rotation: [f32; 4], pub normal: [f32; 3],
     pub radius: f32, pub half_extents: [f32; 3],
 }
+pub type fw_mesh = i32;
+#[repr(C)] #[derive(Clone, Copy)] pub struct fw_mesh_collider {   // one placed instance of a collider mesh
+    pub mesh: fw_mesh, pub layers: u32, pub position: [f32; 3], pub rotation: [f32; 4],
+}
 #[repr(C)] pub struct fw_emission_settings {          // EmissionSettings, core.rs:144-162
     pub particle_index: i32, pub pacing_kind: i32, pub oneshot_count: u64,
     pub count: f32, pub duration: f32, pub offset_start: f32, pub offset_end: f32,
@@ -60,6 +64,9 @@ extern "C" {
     pub fn fw_ctx_stream(ctx: *const fw_ctx) -> *mut c_void;
     pub fn fw_ctx_synchronize(ctx: *mut fw_ctx) -> c_int;
     pub fn fw_ctx_set_colliders(ctx: *mut fw_ctx, colliders: *const fw_collider, n: u32) -> c_int;
+    pub fn fw_ctx_create_mesh(ctx: *mut fw_ctx, xyz: *const f32, n_vertices: u32, indices: *const u32, n_triangles: u32, out: *mut fw_mesh) -> c_int;
+    pub fn fw_ctx_destroy_mesh(ctx: *mut fw_ctx, mesh: fw_mesh) -> c_int;
+    pub fn fw_ctx_set_mesh_colliders(ctx: *mut fw_ctx, instances: *const fw_mesh_collider, n: u32) -> c_int;
     pub fn fw_spawner_create(ctx: *mut fw_ctx, desc: *const fw_spawner_desc, out: *mut fw_spawner) -> c_int;
     pub fn fw_spawner_update_settings(ctx: *mut fw_ctx, h: fw_spawner, desc: *const fw_spawner_desc) -> c_int;
     pub fn fw_spawner_destroy(ctx: *mut fw_ctx, h: fw_spawner) -> c_int;
