@@ -81,6 +81,52 @@ def make_colliders(colliders):
     return arr
 
 
+class _MeshCollider(C.Structure):
+    _fields_ = [("mesh", C.c_void_p), ("layers", C.c_uint32), ("position", C.c_float * 3), ("rotation", C.c_float * 4)]
+
+
+class OracleMesh:
+    """A triangle mesh of the oracle's collider world (vertices [n, 3] float32, indices [m, 3] uint32): validated and stripped
+    of its zero-area triangles like fw_ctx_create_mesh; ValueError for what that call answers with FW_EINVAL.  One mesh may be
+    placed by several instances of several OracleSpawners; keep it alive while a set places it."""
+
+    def __init__(self, vertices, indices):
+        xyz = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+        idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1, 3)
+        self.n_triangles = len(idx)
+        self._h = lib().fwo_mesh_create(xyz.ctypes.data_as(_VP), len(xyz), idx.ctypes.data_as(_VP), len(idx))
+        if not self._h:
+            raise ValueError("invalid mesh (fw_ctx_create_mesh would return FW_EINVAL)")
+
+    def kept(self) -> np.ndarray:
+        """the original indices of the triangles that were kept"""
+        out = np.zeros(self.n_triangles, dtype=np.uint32)
+        n = lib().fwo_mesh_kept(self._h, out.ctypes.data_as(_VP), len(out))
+        return out[:n]
+
+    def close(self):
+        if self._h:
+            lib().fwo_mesh_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def make_mesh_colliders(instances):
+    """instances: objects with .mesh (an OracleMesh), .position, .rotation (xyzw), .layers"""
+    arr = (_MeshCollider * max(len(instances), 1))()
+    for d, m in zip(arr, instances):
+        assert isinstance(m.mesh, OracleMesh) and m.mesh._h, "a mesh instance of the oracle places an open OracleMesh"
+        d.mesh, d.layers = m.mesh._h, int(m.layers) & 0xFFFFFFFF
+        d.position[:] = [float(x) for x in m.position]
+        d.rotation[:] = [float(x) for x in m.rotation]
+    return arr
+
+
 class _EmissionSettings(C.Structure):
     _fields_ = [
         ("particle_index", C.c_int32),
@@ -143,6 +189,20 @@ def lib() -> C.CDLL:
     L.fwo_particle_collision.restype = C.c_int32
     L.fwo_particle_collision.argtypes = [_FP, _FP, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_uint32,
                                          C.POINTER(_Collider), C.c_int32]
+    L.fwo_mesh_create.restype = _VP
+    L.fwo_mesh_create.argtypes = [_VP, C.c_uint32, _VP, C.c_uint32]
+    L.fwo_mesh_destroy.restype = None
+    L.fwo_mesh_destroy.argtypes = [_VP]
+    L.fwo_mesh_kept.restype = C.c_uint32
+    L.fwo_mesh_kept.argtypes = [_VP, _VP, C.c_uint32]
+    L.fwo_cast_rays.restype = None
+    L.fwo_cast_rays.argtypes = [C.POINTER(_Collider), C.c_int32, C.POINTER(_MeshCollider), C.c_int32, C.c_uint32, C.c_uint64,
+                                _VP, _VP, _VP, _VP, _VP, _VP]
+    L.fwo_particle_collision_world.restype = C.c_int32
+    L.fwo_particle_collision_world.argtypes = [_FP, _FP, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_uint32,
+                                               C.POINTER(_Collider), C.c_int32, C.POINTER(_MeshCollider), C.c_int32]
+    L.fwo_spawner_set_mesh_colliders.restype = None
+    L.fwo_spawner_set_mesh_colliders.argtypes = [_VP, C.POINTER(_MeshCollider), C.c_int32]
     L.fwo_spawner_set_colliders.restype = None
     L.fwo_spawner_set_colliders.argtypes = [_VP, C.POINTER(_Collider), C.c_int32]
     L.fwo_spawner_create.restype = _VP
@@ -333,6 +393,31 @@ def particle_collision(pos, vel, delta, settings: S.ParticleCollisionSettings, c
     return np.array(p[:], dtype=np.float32), np.array(v[:], dtype=np.float32), bool(d)
 
 
+def cast_rays(colliders, mesh_instances, mask, origin, direction, max_distance):
+    """the merged ray cast (analytic colliders + every triangle of every mesh instance) for arrays of rays
+    -> (found [n] bool, distance [n] float32, normal [n, 3] float32); distance and normal are zero where nothing was found"""
+    o = np.ascontiguousarray(origin, dtype=np.float32).reshape(-1, 3)
+    d = np.ascontiguousarray(direction, dtype=np.float32).reshape(-1, 3)
+    md = np.ascontiguousarray(np.broadcast_to(np.asarray(max_distance, dtype=np.float32), (len(o),)))
+    found = np.zeros(len(o), dtype=np.int32)
+    dist = np.zeros(len(o), dtype=np.float32)
+    nrm = np.zeros((len(o), 3), dtype=np.float32)
+    P = lambda a: a.ctypes.data_as(_VP)
+    lib().fwo_cast_rays(make_colliders(colliders), len(colliders), make_mesh_colliders(mesh_instances), len(mesh_instances),
+                        int(mask) & 0xFFFFFFFF, len(o), P(o), P(d), P(md), P(found), P(dist), P(nrm))
+    return found.astype(bool), dist, nrm
+
+
+def particle_collision_world(pos, vel, delta, settings: S.ParticleCollisionSettings, colliders, mesh_instances):
+    """particle_collision over the merged cast -> (pos, vel, should_destroy)"""
+    p, v = _farr(pos), _farr(vel)
+    d = lib().fwo_particle_collision_world(p, v, float(delta), float(settings.restitution), float(settings.friction),
+                                           1 if settings.destroy_on_collision else 0, int(settings.filter_mask) & 0xFFFFFFFF,
+                                           make_colliders(colliders), len(colliders), make_mesh_colliders(mesh_instances),
+                                           len(mesh_instances))
+    return np.array(p[:], dtype=np.float32), np.array(v[:], dtype=np.float32), bool(d)
+
+
 # ---- spawner ------------------------------------------------------------------------
 
 class OracleSpawner:
@@ -394,6 +479,11 @@ class OracleSpawner:
 
     def set_colliders(self, colliders):
         lib().fwo_spawner_set_colliders(self._h, make_colliders(colliders), len(colliders))
+
+    def set_mesh_colliders(self, instances):
+        """instances place OracleMesh objects (.mesh, .position, .rotation, .layers); the spawner keeps them alive"""
+        self._meshes = [m.mesh for m in instances]
+        lib().fwo_spawner_set_mesh_colliders(self._h, make_mesh_colliders(instances), len(instances))
 
     def queue_particles(self, n: int):
         lib().fwo_spawner_queue(self._h, int(n))

@@ -341,7 +341,7 @@ void fwo_shape_generate(const fwo_emission_settings *e, const float u[3], float 
 }
 
 /* ------------------------------------------------------------------------- */
-/* particle_collision (core.rs:744-800) with an analytic ray cast               */
+/* particle_collision (core.rs:744-800) with an analytic + mesh ray cast        */
 /* ------------------------------------------------------------------------- */
 
 static float v3_length(const float a[3]) { return sqrtf(v3_dot(a, a)); }
@@ -524,9 +524,115 @@ static int ray_collider(const fwo_collider *c, const float o[3], const float d[3
     return 1;
 }
 
-/* SpatialQuery::cast_ray(origin, dir, max_distance, true, filter): the nearest hit */
-static int cast_ray(const fwo_collider *cs, int n, uint32_t mask, const float o[3], const float d[3], float max_distance,
-                    float *dist, float normal[3]) {
+/* ------------------------------------------------------------------------- */
+/* Triangle meshes: the semantics in the comment above fw_mesh_collider         */
+/* (include/firework_hip.h) and DESIGN.md 4.3, restated by BRUTE FORCE: every    */
+/* kept triangle of every instance that passes the filter is tested, in input  */
+/* order; there is no hierarchy and nothing is culled.  Shares no source with   */
+/* the shipped library.                                                        */
+/* ------------------------------------------------------------------------- */
+
+struct fwo_mesh {
+    uint32_t n;     /* kept triangles, in input order */
+    float *v0;      /* [n][3] first vertex as given */
+    float *e1, *e2; /* [n][3] v1 - v0, v2 - v0 (fp32, computed once here) */
+    uint32_t *orig; /* [n] position of the triangle in the caller's `indices` (the tie rule) */
+};
+
+fwo_mesh *fwo_mesh_create(const float *xyz, uint32_t n_vertices, const uint32_t *indices, uint32_t n_triangles) {
+    if (!xyz || !indices || n_vertices == 0 || n_triangles == 0) return NULL;
+    for (size_t i = 0; i < (size_t)n_vertices * 3; i++)
+        if (!isfinite(xyz[i])) return NULL;
+    for (size_t i = 0; i < (size_t)n_triangles * 3; i++)
+        if (indices[i] >= n_vertices) return NULL;
+    fwo_mesh *m = (fwo_mesh *)calloc(1, sizeof *m);
+    m->v0 = (float *)malloc(sizeof(float) * 3 * (size_t)n_triangles);
+    m->e1 = (float *)malloc(sizeof(float) * 3 * (size_t)n_triangles);
+    m->e2 = (float *)malloc(sizeof(float) * 3 * (size_t)n_triangles);
+    m->orig = (uint32_t *)malloc(sizeof(uint32_t) * (size_t)n_triangles);
+    for (uint32_t t = 0; t < n_triangles; t++) {
+        const float *a = xyz + 3 * (size_t)indices[3 * (size_t)t];
+        const float *b = xyz + 3 * (size_t)indices[3 * (size_t)t + 1];
+        const float *c = xyz + 3 * (size_t)indices[3 * (size_t)t + 2];
+        float e1[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]};
+        float e2[3] = {c[0] - a[0], c[1] - a[1], c[2] - a[2]};
+        float cr[3];
+        v3_cross(e1, e2, cr);
+        float cc = v3_dot(cr, cr);
+        if (!(isfinite(cc) && cc > 0.0f)) continue; /* zero area (or an overflow): dropped */
+        uint32_t k = m->n++;
+        memcpy(m->v0 + 3 * (size_t)k, a, sizeof e1);
+        memcpy(m->e1 + 3 * (size_t)k, e1, sizeof e1);
+        memcpy(m->e2 + 3 * (size_t)k, e2, sizeof e2);
+        m->orig[k] = t;
+    }
+    if (m->n == 0) {
+        fwo_mesh_destroy(m);
+        return NULL;
+    }
+    return m;
+}
+
+void fwo_mesh_destroy(fwo_mesh *m) {
+    if (!m) return;
+    free(m->v0), free(m->e1), free(m->e2), free(m->orig), free(m);
+}
+
+uint32_t fwo_mesh_kept(const fwo_mesh *m, uint32_t *orig_out, uint32_t cap) {
+    for (uint32_t i = 0; i < m->n && i < cap; i++) orig_out[i] = m->orig[i];
+    return m->n;
+}
+
+/* one placed instance: the nearest triangle, the lower original index at equal distance */
+static int ray_mesh_instance(const fwo_mesh_collider *in, const float o[3], const float d[3], float max_distance, float *dist,
+                             float normal[3]) {
+    const fwo_mesh *m = in->mesh;
+    const float *r = in->rotation;
+    const int aligned = r[0] == 0.0f && r[1] == 0.0f && r[2] == 0.0f && r[3] == 1.0f;
+    float rel[3] = {o[0] - in->position[0], o[1] - in->position[1], o[2] - in->position[2]}, ol[3], dl[3];
+    if (aligned) { /* FRAME: the identity rotation skips both products */
+        memcpy(ol, rel, sizeof ol);
+        memcpy(dl, d, sizeof dl);
+    } else {
+        float qi[4] = {-r[0], -r[1], -r[2], r[3]};
+        fwo_quat_mul_vec3(qi, rel, ol);
+        fwo_quat_mul_vec3(qi, d, dl);
+    }
+    int any = 0;
+    uint32_t best = 0;
+    float best_t = 0.0f;
+    for (uint32_t k = 0; k < m->n; k++) { /* TRIANGLE: Moeller-Trumbore in the header's order */
+        const float *v0 = m->v0 + 3 * (size_t)k, *e1 = m->e1 + 3 * (size_t)k, *e2 = m->e2 + 3 * (size_t)k;
+        float p[3], q[3];
+        v3_cross(dl, e2, p);
+        float det = v3_dot(e1, p);
+        if (det == 0.0f) continue;
+        float inv = 1.0f / det;
+        float s[3] = {ol[0] - v0[0], ol[1] - v0[1], ol[2] - v0[2]};
+        float u = v3_dot(s, p) * inv;
+        v3_cross(s, e1, q);
+        float v = v3_dot(dl, q) * inv;
+        float t = v3_dot(e2, q) * inv;
+        if (!(u >= 0.0f && v >= 0.0f && u + v <= 1.0f && t >= 0.0f && t <= max_distance)) continue;
+        if (!any || t < best_t) best_t = t, best = k, any = 1; /* kept triangles are in input order: `<` keeps the lower index */
+    }
+    if (!any) return 0;
+    *dist = best_t;
+    float c[3], nl[3], n[3]; /* NORMAL */
+    v3_cross(m->e1 + 3 * (size_t)best, m->e2 + 3 * (size_t)best, c);
+    float rcp = 1.0f / sqrtf(v3_dot(c, c));
+    nl[0] = c[0] * rcp, nl[1] = c[1] * rcp, nl[2] = c[2] * rcp;
+    if (aligned) memcpy(n, nl, sizeof n);
+    else fwo_quat_mul_vec3(r, nl, n);
+    if (v3_dot(n, d) > 0.0f) n[0] = -n[0], n[1] = -n[1], n[2] = -n[2];
+    memcpy(normal, n, sizeof n);
+    return 1;
+}
+
+/* SpatialQuery::cast_ray(origin, dir, max_distance, true, filter): the nearest hit.  TIES: analytic colliders (lowest index)
+ * before mesh instances, lower instances before higher ones -- every later candidate must be strictly nearer. */
+int32_t fwo_cast_ray(const fwo_collider *cs, int32_t n, const fwo_mesh_collider *ms, int32_t n_mesh, uint32_t mask,
+                     const float o[3], const float d[3], float max_distance, float *dist, float normal[3]) {
     int any = 0;
     for (int i = 0; i < n; i++) {
         if (!(cs[i].layers & mask)) continue;
@@ -537,13 +643,30 @@ static int cast_ray(const fwo_collider *cs, int n, uint32_t mask, const float o[
             any = 1;
         }
     }
+    for (int i = 0; i < n_mesh; i++) {
+        if (!(ms[i].layers & mask)) continue;
+        float t, nn[3];
+        if (ray_mesh_instance(&ms[i], o, d, max_distance, &t, nn) && (!any || t < *dist)) {
+            *dist = t;
+            memcpy(normal, nn, sizeof nn);
+            any = 1;
+        }
+    }
     return any;
 }
 
+/* fwo_cast_ray for `n_rays` rays (origins / dirs / normals [n_rays][3]); rays that find nothing leave dist / normal untouched */
+void fwo_cast_rays(const fwo_collider *cs, int32_t n, const fwo_mesh_collider *ms, int32_t n_mesh, uint32_t mask, uint64_t n_rays,
+                   const float *origins, const float *dirs, const float *max_distances, int32_t *found, float *dists,
+                   float *normals) {
+    for (uint64_t i = 0; i < n_rays; i++)
+        found[i] = fwo_cast_ray(cs, n, ms, n_mesh, mask, origins + 3 * i, dirs + 3 * i, max_distances[i], dists + i, normals + 3 * i);
+}
+
 /* core.rs:744-800 */
-int32_t fwo_particle_collision(float pos[3], float vel[3], float delta, float restitution, float friction,
-                               int32_t destroy_on_collision, uint32_t filter_mask, const fwo_collider *colliders,
-                               int32_t n) {
+int32_t fwo_particle_collision_world(float pos[3], float vel[3], float delta, float restitution, float friction,
+                                     int32_t destroy_on_collision, uint32_t filter_mask, const fwo_collider *colliders,
+                                     int32_t n, const fwo_mesh_collider *meshes, int32_t n_mesh) {
     const float orig_delta = delta;
     int n_steps = 0, should_destroy = 0;
     while (delta > 0.0f && n_steps < 4) {
@@ -551,7 +674,7 @@ int32_t fwo_particle_collision(float pos[3], float vel[3], float delta, float re
         if (isfinite(len) && len > 0.0f)
             for (int i = 0; i < 3; i++) dir[i] = vel[i] / len;
         float dist, normal[3];
-        if (cast_ray(colliders, n, filter_mask, pos, dir, v3_length(vel) * delta, &dist, normal)) {
+        if (fwo_cast_ray(colliders, n, meshes, n_mesh, filter_mask, pos, dir, v3_length(vel) * delta, &dist, normal)) {
             if (dist == 0.0f) {
                 if (normal[0] == 0.0f && normal[1] == 0.0f && normal[2] == 0.0f) {
                     if (vel[0] != 0.0f || vel[1] != 0.0f || vel[2] != 0.0f) {
@@ -583,6 +706,13 @@ int32_t fwo_particle_collision(float pos[3], float vel[3], float delta, float re
         n_steps++;
     }
     return should_destroy;
+}
+
+int32_t fwo_particle_collision(float pos[3], float vel[3], float delta, float restitution, float friction,
+                               int32_t destroy_on_collision, uint32_t filter_mask, const fwo_collider *colliders,
+                               int32_t n) {
+    return fwo_particle_collision_world(pos, vel, delta, restitution, friction, destroy_on_collision, filter_mask, colliders,
+                                        n, NULL, 0);
 }
 
 /* ------------------------------------------------------------------------- */
@@ -626,6 +756,8 @@ struct fwo_spawner {
     float modifier_scale, modifier_speed;
     fwo_collider *colliders; /* the SpatialQuery world (analytic stand-in) */
     int32_t n_colliders;
+    fwo_mesh_collider *meshes; /* placed meshes of that world (the meshes themselves belong to the caller) */
+    int32_t n_meshes;
 };
 
 static void pvec_push(pvec *v, const particle *p) {
@@ -753,6 +885,7 @@ void fwo_spawner_destroy(fwo_spawner *s) {
         free((void *)s->ps[i].emissive_color.rgba);
     }
     free(s->colliders);
+    free(s->meshes);
     free(s->particles), free(s->destroyed), free(s->emission), free(s->ps), free(s->es), free(s);
 }
 
@@ -786,6 +919,15 @@ void fwo_spawner_set_colliders(fwo_spawner *s, const fwo_collider *colliders, in
         s->colliders = (fwo_collider *)malloc(sizeof(fwo_collider) * (size_t)n);
         memcpy(s->colliders, colliders, sizeof(fwo_collider) * (size_t)n);
         s->n_colliders = n;
+    }
+}
+void fwo_spawner_set_mesh_colliders(fwo_spawner *s, const fwo_mesh_collider *instances, int32_t n) {
+    free(s->meshes);
+    s->meshes = NULL, s->n_meshes = 0;
+    if (n > 0) {
+        s->meshes = (fwo_mesh_collider *)malloc(sizeof(fwo_mesh_collider) * (size_t)n);
+        memcpy(s->meshes, instances, sizeof(fwo_mesh_collider) * (size_t)n);
+        s->n_meshes = n;
     }
 }
 
@@ -918,9 +1060,9 @@ void fwo_spawner_update(fwo_spawner *s, float dt) {
 
             float sa[3];
             if (ps->coll_enabled) { /* core.rs:607-624 (feature physics_avian) */
-                int destroy = fwo_particle_collision(p.position, p.velocity, dt, ps->coll_restitution, ps->coll_friction,
-                                                     ps->coll_destroy_on_collision, ps->coll_filter_mask, s->colliders,
-                                                     s->n_colliders);
+                int destroy = fwo_particle_collision_world(p.position, p.velocity, dt, ps->coll_restitution, ps->coll_friction,
+                                                           ps->coll_destroy_on_collision, ps->coll_filter_mask, s->colliders,
+                                                           s->n_colliders, s->meshes, s->n_meshes);
                 if (destroy) { /* core.rs:636-639: the record carries the new position / velocity / scale */
                     pvec_push(&destroyed, &p);
                     continue;

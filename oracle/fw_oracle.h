@@ -39,6 +39,11 @@
  *     (tests/golden/np_sim.py) whose multi-frame trajectories this oracle
  *     reproduces (tests/test_oracle_golden.py) and which the HIP path is
  *     compared with directly (tests/test_gpu_golden.py).
+ *   - triangle-mesh colliders (fwo_mesh, fwo_cast_ray): the reference casts into avian's world, there is nothing of it to
+ *     restate -> "parity unpinned"; anchored on the semantics written above fw_mesh_collider (include/firework_hip.h), restated
+ *     here by brute force over every triangle, and on the independent numpy brute force tests/mesh_ref.py, with which this
+ *     cast agrees bit for bit on rays, ties and whole trajectories (tests/test_oracle_mesh_cpu.py, tests/test_fuzz_cpu.py,
+ *     tests/test_oracle_golden.py).
  *   - spawn ATTRIBUTES (RandF32/RandVec3/PitchYaw/shapes): the reference uses
  *     an unseeded thread-local RNG (rand::random), so they are unpinnable in
  *     principle; this oracle defines a Philox4x32-10 counter stream with the
@@ -95,6 +100,16 @@ typedef struct {
     float radius;
     float half_extents[3];
 } fwo_collider;
+
+/* triangle meshes of that world (semantics: the comment above fw_mesh_collider in include/firework_hip.h).  A mesh is created
+ * once and placed by any number of instances of any number of oracle spawners; it must outlive every set that places it. */
+typedef struct fwo_mesh fwo_mesh;
+typedef struct {
+    const fwo_mesh *mesh;
+    uint32_t layers;
+    float position[3];
+    float rotation[4]; /* xyzw */
+} fwo_mesh_collider;
 
 enum { FWO_PACING_ONESHOT = 0, FWO_PACING_ONDEMAND = 1, FWO_PACING_COUNT_OVER_DURATION = 2 };
 enum { FWO_MODE_GLOBAL = 0, FWO_MODE_NESTED = 1 };
@@ -157,6 +172,24 @@ int32_t fwo_particle_collision(float pos[3], float vel[3], float delta, float re
                                int32_t destroy_on_collision, uint32_t filter_mask, const fwo_collider *colliders,
                                int32_t n);
 
+/* xyz[n_vertices][3], indices[n_triangles][3].  NULL for no vertices, no triangles, an index >= n_vertices, a non-finite vertex, or
+ * no triangle left once those of zero area (c = cross(e1, e2), cc = (c0*c0 + c1*c1) + c2*c2 not finite or not > 0) are dropped. */
+fwo_mesh *fwo_mesh_create(const float *xyz, uint32_t n_vertices, const uint32_t *indices, uint32_t n_triangles);
+void fwo_mesh_destroy(fwo_mesh *m);
+/* the original indices of the kept triangles, ascending; returns their number */
+uint32_t fwo_mesh_kept(const fwo_mesh *m, uint32_t *orig_out, uint32_t cap);
+/* the merged ray cast: analytic colliders, then every triangle of every mesh instance (brute force, nothing culled); the
+ * nearest hit, at equal distance analytic before mesh, lower instance, lower original triangle.  Returns found. */
+int32_t fwo_cast_ray(const fwo_collider *colliders, int32_t n, const fwo_mesh_collider *meshes, int32_t n_mesh, uint32_t filter_mask,
+                     const float origin[3], const float dir[3], float max_distance, float *dist, float normal[3]);
+void fwo_cast_rays(const fwo_collider *colliders, int32_t n, const fwo_mesh_collider *meshes, int32_t n_mesh, uint32_t filter_mask,
+                   uint64_t n_rays, const float *origins, const float *dirs, const float *max_distances, int32_t *found,
+                   float *dists, float *normals);
+/* particle_collision over the merged cast */
+int32_t fwo_particle_collision_world(float pos[3], float vel[3], float delta, float restitution, float friction,
+                                     int32_t destroy_on_collision, uint32_t filter_mask, const fwo_collider *colliders,
+                                     int32_t n, const fwo_mesh_collider *meshes, int32_t n_mesh);
+
 /* ---- spawner lifecycle ----------------------------------------------------- */
 fwo_spawner *fwo_spawner_create(const fwo_particle_settings *ps, int32_t n_ps, const fwo_emission_settings *es,
                                 int32_t n_es, int32_t starts_enabled, uint32_t seed, uint32_t uid);
@@ -169,6 +202,8 @@ void fwo_spawner_set_modifier(fwo_spawner *s, float scale, float speed);
 void fwo_spawner_queue(fwo_spawner *s, uint64_t n);
 /* the world the spawner's particles collide with (copied) */
 void fwo_spawner_set_colliders(fwo_spawner *s, const fwo_collider *colliders, int32_t n);
+/* the placed meshes of that world (the instance records are copied, the meshes are not; n = 0 clears the set) */
+void fwo_spawner_set_mesh_colliders(fwo_spawner *s, const fwo_mesh_collider *instances, int32_t n);
 int32_t fwo_spawner_active(const fwo_spawner *s);
 /* returns 1 exactly once, like notify_finished_particle_spawners (core.rs:674-688) */
 int32_t fwo_spawner_poll_finished(fwo_spawner *s);

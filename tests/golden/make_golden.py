@@ -229,7 +229,48 @@ def trajectories():
     return {"source": "tests/golden/np_sim.py over tests/golden/scenarios.py", "counts_at_checkpoints": summary}
 
 
+def mesh_trajectories():
+    """scenarios.MESH (a terrain mesh + a ball; bouncing and destroying) stepped by np_sim.py with the brute-force mesh cast of
+    tests/mesh_ref.py in place of np_sim.cast_ray -> mesh_trajectories.npz, in the scheme of trajectories.npz"""
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    sys.path.insert(0, os.path.dirname(HERE))
+    import mesh_ref
+    import np_sim
+    import scenarios
+
+    out, summary = {}, {}
+    analytic, np_sim.cast_ray = np_sim.cast_ray, mesh_ref.cast_ray
+    try:
+        for name, make in scenarios.MESH.items():
+            sc = make()
+            sim = np_sim.Spawner(sc["spawner"], scenarios.SEED, sc["uid"], sc["transform"], sc["modifier"])
+            sim.parent_velocity = np.asarray(sc["parent_velocity"], dtype=f32)
+            ms = {k: mesh_ref.Mesh(*vt) for k, vt in sc["meshes"].items()}
+            sim.colliders = mesh_ref.World(list(sc["colliders"]), [mesh_ref.Instance(ms[k], p, q, layers) for k, p, q, layers in sc["mesh_instances"]])
+            counts = []
+            for fr in range(sc["frames"]):
+                sim.step(f32(sc["dts"][fr % len(sc["dts"])]))
+                if fr in sc["checkpoints"]:
+                    for t, p in enumerate(sim.particles):
+                        for k, v in p.items():
+                            out[f"{name}/f{fr}/t{t}/{k}"] = np.ascontiguousarray(v, dtype=f32)
+                        for k in ("age", "position", "velocity", "scale"):
+                            out[f"{name}/f{fr}/t{t}/destroyed_{k}"] = np.ascontiguousarray(sim.destroyed[t][k], dtype=f32)
+                    counts.append([fr] + [sim.count(t) for t in range(len(sim.particles))] + [len(d["age"]) for d in sim.destroyed])
+            summary[name] = counts
+    finally:
+        np_sim.cast_ray = analytic
+    np.savez_compressed(os.path.join(HERE, "mesh_trajectories.npz"), **out)
+    print("wrote mesh_trajectories.npz", summary)
+    return {"source": "tests/golden/np_sim.py + tests/mesh_ref.py over tests/golden/scenarios.py: MESH",
+            "counts_and_destroyed_at_checkpoints": summary}
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["mesh"]:  # (only the mesh file: trajectories.npz stays byte for byte what it is)
+        dump("mesh_trajectories.json", mesh_trajectories())
+        sys.exit(0)
+    dump("mesh_trajectories.json", mesh_trajectories())
     dump("trajectories.json", trajectories())
     dump("emission_kat.json", emission_kat())
     dump("emission_wrap.json", emission_wrap())

@@ -134,3 +134,45 @@ def bouncing_colliders():
 
 ALL = {f.__name__: f for f in (rotation_cone_sphere, two_types_circle_oneshot, nested_sparks_smoke, deaths_everywhere,
                                bouncing_colliders)}
+
+
+# ---- triangle-mesh colliders (tests/golden/mesh_trajectories.npz) ---------------------------------------------------------
+def _terrain(cells=10, extent=5.0):
+    """a height field of cells x cells quads over [-extent, extent]^2, two triangles each -> (vertices float32, indices uint32)"""
+    import numpy as np
+
+    xs = np.linspace(-extent, extent, cells + 1)
+    X, Z = np.meshgrid(xs, xs, indexing="ij")
+    Y = 0.4 * np.sin(0.8 * X) * np.cos(0.6 * Z) - 0.2
+    v = np.stack([X, Y, Z], axis=-1).reshape(-1, 3).astype(np.float32)
+    i = np.arange((cells + 1) ** 2).reshape(cells + 1, cells + 1)
+    a, b, c, e = i[:-1, :-1].ravel(), i[1:, :-1].ravel(), i[1:, 1:].ravel(), i[:-1, 1:].ravel()
+    return v, np.concatenate([np.stack([a, e, c], 1), np.stack([a, c, b], 1)]).astype(np.uint32)
+
+
+def _mesh_terrain(destroy):
+    ps = S.ParticleSettings(lifetime=S.RandF32(0.8, 1.6), initial_scale=S.RandF32.constant(0.05), linear_drag=0.1,
+                            collision_settings=S.ParticleCollisionSettings(0.6, 0.2, destroy, 0xFFFFFFFF))
+    es = S.EmissionSettings(emission_pacing=S.EmissionPacing.rate(800.0 if destroy else 240.0), emission_shape=S.EmissionShape.Point(),
+                            initial_velocity=S.RandVec3(S.RandF32(1.0, 7.0), (0.28, -0.93, 0.19), 0.0), inherit_parent_velocity=True)
+    q = (0.0, math.sin(0.15), 0.0, math.cos(0.15))
+    return dict(spawner=S.ParticleSpawner([ps], [es]), transform=S.Transform((0.5, 1.5, -0.3)), modifier=None,
+                parent_velocity=(0.4, 0.0, -0.3), uid=31, dts=[1 / 60] * 25 + [1 / 30, 1 / 120, 0.04], frames=110,
+                checkpoints=[12, 60, 109], exact=True, colliders=[S.Collider.Sphere((1.2, -0.4, 0.3), 0.6)],
+                meshes={"terrain": _terrain()},
+                # (the terrain twice: as it is, and turned about Y a little lower on layer 2 -- every mask of these types sees both)
+                mesh_instances=[("terrain", (0.0, 0.0, 0.0), (0.0, 0.0, 0.0, 1.0), 1), ("terrain", (0.25, -0.5, 0.0), q, 2)])
+
+
+def mesh_terrain_bouncing():
+    """a trig-free emitter above a height-field MESH and an analytic ball: particles bounce off both (include/firework_hip.h:
+    fw_mesh_collider has the semantics; tests/mesh_ref.py casts the rays for np_sim.py)"""
+    return _mesh_terrain(False)
+
+
+def mesh_terrain_destroying():
+    """... and destroy_on_collision: the records of the destroyed carry the position / velocity of the contact"""
+    return _mesh_terrain(True)
+
+
+MESH = {f.__name__: f for f in (mesh_terrain_bouncing, mesh_terrain_destroying)}

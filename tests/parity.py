@@ -72,6 +72,34 @@ def assert_particles_match(gpu: np.ndarray, cpu: np.ndarray, exact_all: bool = F
                               f"(worst {worst:.2f}x the allowance)")
 
 
+class MeshPair:
+    """One triangle mesh of the collider world on the device (a handle of `system`) and in the oracle (an OracleMesh)."""
+
+    def __init__(self, system, vertices, indices):
+        import oracle
+
+        self.system = system
+        self.gpu = system.create_mesh(vertices, indices)
+        self.cpu = oracle.OracleMesh(vertices, indices)
+
+    def destroy(self):
+        """(the device refuses while the current instance set places the mesh)"""
+        self.system.destroy_mesh(self.gpu)
+        self.cpu.close()
+        self.gpu = None
+
+
+def set_world(system, pairs, colliders, instances=()):
+    """The same collider world -- analytic colliders and placed meshes, `instances` = [(MeshPair, position, rotation xyzw,
+    layers)] -- in the context of `system` and in the oracle spawner of every Pair of `pairs`."""
+    system.set_colliders(list(colliders))
+    system.set_mesh_colliders([S.MeshCollider(m.gpu, p, q, layers) for m, p, q, layers in instances])
+    cpu = [S.MeshCollider(m.cpu, p, q, layers) for m, p, q, layers in instances]
+    for pair in pairs:
+        pair.cpu.set_colliders(list(colliders))
+        pair.cpu.set_mesh_colliders(cpu)
+
+
 class Pair:
     """The same spawner on the HIP backend and on the oracle, stepped in lockstep."""
 
@@ -79,6 +107,7 @@ class Pair:
         import oracle
 
         transform = transform or S.Transform()
+        self.system = system
         self.gpu = system.spawn(spawner, transform, uid=uid, modifier=modifier)
         self.cpu = oracle.OracleSpawner(spawner, seed=seed, uid=uid, transform=transform)
         if modifier is not None:
@@ -90,6 +119,11 @@ class Pair:
     def queue(self, n):
         self.gpu.queue_particles(n)
         self.cpu.queue_particles(n)
+
+    def set_world(self, colliders, instances=()):
+        """analytic colliders + placed meshes ([(MeshPair, position, rotation, layers)]) on both sides (the device's world
+        belongs to the whole context)"""
+        set_world(self.system, [self], colliders, instances)
 
     def step_cpu(self, dt):
         self.cpu.step(np.float32(dt))
@@ -129,9 +163,9 @@ def golden():
     return _GOLDEN
 
 
-def golden_particles(name: str, frame: int, t: int) -> np.ndarray:
+def golden_particles(name: str, frame: int, t: int, g=None) -> np.ndarray:
     """the stored state of particle type `t` at checkpoint `frame`, as a PARTICLE_DTYPE-like record array (no pbr)"""
-    g = golden()
+    g = golden() if g is None else g
     pre = f"{name}/f{frame}/t{t}/"
     n = len(g[pre + "age"])
     dt = np.dtype([(k, np.float32, s) if s else (k, np.float32) for k, s in

@@ -66,6 +66,34 @@ def test_struct_sizes_match_header(tmp_path):
     assert S.PARTICLE_DTYPE.itemsize == 104 and S.INSTANCE_DTYPE.itemsize == 64
 
 
+def test_mesh_collider_layout_matches_header(tmp_path):
+    """fw_mesh_collider: size and the offset of every field, the C compiler's against the ctypes mirror's -- and the oracle's own
+    instance record places its fields (behind a pointer instead of a handle) in the same order"""
+    import subprocess
+
+    import oracle
+
+    fields = ("mesh", "layers", "position", "rotation")
+    src = tmp_path / "mesh.c"
+    src.write_text('#include <stddef.h>\n#include <stdio.h>\n#include "firework_hip.h"\nint main(void){printf("%zu %zu %zu %zu %zu %zu\\n",'
+                   "sizeof(fw_mesh_collider),sizeof(fw_mesh)," + ",".join(f"offsetof(fw_mesh_collider,{k})" for k in fields)
+                   + ");return 0;}\n")
+    exe = tmp_path / "mesh"
+    subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    got = [int(x) for x in subprocess.check_output([str(exe)]).split()]
+    M = _ffi.MeshCollider
+    assert [name for name, _ in M._fields_] == list(fields)
+    assert got == [C.sizeof(M), C.sizeof(C.c_int32)] + [getattr(M, k).offset for k in fields], got
+    assert got[0] == 36
+    assert [name for name, _ in oracle._MeshCollider._fields_] == list(fields)
+    # the C++ mirror marshals field by field (include/firework.hpp: set_mesh_colliders): every field of the C struct is assigned
+    hpp = open(os.path.join(ROOT, "include", "firework.hpp")).read()
+    body = hpp[hpp.index("void set_mesh_colliders("):hpp.index("check(fw_ctx_set_mesh_colliders(")]
+    for want in ("v[i].mesh = m.mesh", "v[i].layers = m.layers") + tuple(f"v[i].position[{k}] = m.position.{c}" for k, c in enumerate("xyz")) \
+            + tuple(f"v[i].rotation[{k}] = m.rotation.{c}" for k, c in enumerate("xyzw")):
+        assert want in body, want
+
+
 def test_host_emission_count_is_bit_exact_with_golden():
     """fw_compute_emission_count is the arithmetic fw_step's host side uses for Global entries."""
     d = json.load(open(os.path.join(G, "emission_kat.json")))

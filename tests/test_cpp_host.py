@@ -42,19 +42,16 @@ def _fnv(b: bytes) -> int:
     return h
 
 
-@pytest.mark.gpu
-def test_cpp_mirror_and_python_mirror_drive_the_library_identically():
-    """examples/mirror_check.cpp (three particle types, Global / OnDemand / OneShot / Nested entries, all curve kinds,
-    modifier, transforms, parent velocity, destroyed handler, colliders, fused AABB) through include/firework.hpp, and
-    the same scenario through bevy_firework_amd/: the same library, so every digest must be identical -- a field either
-    mirror marshals differently (or forgets) shows up here"""
+def _run_both_mirrors(meshes):
+    """examples/mirror_check (with the argument `mesh`: triangle meshes in its collider world) and the same scenario through the
+    Python mirror; asserts that the lines are identical and returns them"""
     import numpy as np
 
     from bevy_firework_amd import settings as S
     from bevy_firework_amd.system import ParticleSystem
 
     build()
-    out = subprocess.run([os.path.join(ROOT, "examples", "mirror_check")], capture_output=True, text=True, timeout=120)
+    out = subprocess.run([os.path.join(ROOT, "examples", "mirror_check")] + (["mesh"] if meshes else []), capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stderr
     cpp_lines = out.stdout.strip().splitlines()
 
@@ -86,6 +83,11 @@ def test_cpp_mirror_and_python_mirror_drive_the_library_identically():
         ps.track_aabbs(True)
         ps.set_colliders([S.Collider.Plane((0.0, -1.0, 0.0), (0.0, 1.0, 0.0)), S.Collider.Sphere((1.0, 0.5, 0.0), 0.75, 2),
                           S.Collider.Box((-2.0, 0.0, 0.0), (0.5, 1.0, 0.5), (0.0, 0.38268343, 0.0, 0.92387953))])
+        if meshes:
+            ramp = ps.create_mesh(np.array([[-2.0, -0.25, -2.0], [2.0, -0.25, -2.0], [2.0, 0.25, 2.0], [-2.0, 0.25, 2.0]], dtype=np.float32),
+                                  np.array([[0, 2, 1], [0, 3, 2]], dtype=np.uint32))
+            ps.set_mesh_colliders([S.MeshCollider(ramp, (0.0, -0.25, 0.0), (0.0, 0.0, 0.0, 1.0), 1),
+                                   S.MeshCollider(ramp, (0.5, 0.25, 0.0), (0.0, 0.38268343, 0.0, 0.92387953), 2)])
         d = ps.spawn(S.ParticleSpawner([p0, p1, p2], [e0, e1, e2, e3]), S.Transform((0.0, 1.0, 0.0)), uid=42,
                      modifier=S.EffectModifier(2.0, 0.5))
         d.set_parent_velocity((0.5, 0.0, -0.25))
@@ -93,6 +95,11 @@ def test_cpp_mirror_and_python_mirror_drive_the_library_identically():
         for fr in range(60):
             if fr in (0, 7, 8, 31):
                 d.queue_particles(500 + 10 * fr)
+            if meshes and fr == 30:
+                sheet = ps.create_mesh(np.array([[-3.0, 0.0, -3.0], [3.0, 0.0, -3.0], [0.0, 0.5, 3.0]], dtype=np.float32),
+                                       np.array([[0, 2, 1]], dtype=np.uint32))
+                ps.set_mesh_colliders([S.MeshCollider(sheet, (1.0, 1.5, 3.0), (0.0, 0.0, 0.19509032, 0.98078528), 3)])
+                ps.destroy_mesh(ramp)
             if fr == 20:
                 d.set_transform(S.Transform((1.0, 2.0, 3.0), (0.0, 0.0, 0.38268343, 0.92387953)))
             ps.update(dt)
@@ -107,6 +114,29 @@ def test_cpp_mirror_and_python_mirror_drive_the_library_identically():
     lines.append(f"destroyed reported {seen[0]}")
     assert cpp_lines == lines, "\n".join(["C++:"] + cpp_lines + ["Python:"] + lines)
     assert int(cpp_lines[-2].split()[3]) > 1000 and seen[0] > 2000
+    return cpp_lines
+
+
+@pytest.mark.gpu
+def test_cpp_mirror_and_python_mirror_drive_the_library_identically():
+    """examples/mirror_check.cpp (three particle types, Global / OnDemand / OneShot / Nested entries, all curve kinds,
+    modifier, transforms, parent velocity, destroyed handler, colliders, fused AABB) through include/firework.hpp, and
+    the same scenario through bevy_firework_amd/: the same library, so every digest must be identical -- a field either
+    mirror marshals differently (or forgets) shows up here"""
+    _run_both_mirrors(False)
+
+
+@pytest.mark.gpu
+def test_cpp_mirror_and_python_mirror_place_meshes_identically():
+    """the same scenario with the mesh entry points of both mirrors (`mirror_check mesh`): one small mesh of literal vertices placed
+    twice -- one instance rotated, one on layer 2 -- then the set replaced by another mesh and the first one destroyed.  A slip in
+    either mirror's marshalling of fw_mesh_collider (mesh, layers, position, rotation) changes where the pebbles bounce and so the
+    digests; and the meshes do change them: the lines differ from those of the scenario without meshes"""
+    with_meshes = _run_both_mirrors(True)
+    without = _run_both_mirrors(False)
+    assert [ln.split()[:6] for ln in with_meshes] == [ln.split()[:6] for ln in without]  # (a bounce destroys nothing: the same counts)
+    for k in (2, 5):  # frames 29 and 59: the pebbles' digest under the first and under the second instance set
+        assert with_meshes[k].split()[8] != without[k].split()[8], (with_meshes[k], without[k])
 
 
 @pytest.mark.gpu

@@ -168,3 +168,72 @@ def test_the_colliding_cases_destroyed_particles_on_contact():
     if not hits:
         pytest.skip("the colliding cases did not run in this session")
     assert sum(hits.values()) > 50, hits
+
+
+@pytest.mark.parametrize("case", range(16))
+def test_oracle_and_numpy_restatement_agree_on_random_colliding_spawners_with_meshes(case, monkeypatch):
+    """the scenes of tests/test_gpu_fuzz.py::test_random_colliding_spawner_with_meshes_matches_the_oracle_bit_for_bit (the same
+    generator, the same seeds): the C oracle's brute-force mesh cast inside whole simulations against the numpy restatement with
+    tests/mesh_ref.py's cast patched in -- every field of the live particles and the destroyed records, bit for bit, every frame"""
+    np_sim, fz = _mods()
+    import mesh_ref
+
+    monkeypatch.setattr(np_sim, "cast_ray", mesh_ref.cast_ray)
+    sc = fz._mesh_scene(case)
+    spawner, tf, uid = sc["spawner"], sc["transform"], sc["uid"]
+    n_types = len(spawner.particle_settings)
+    o = oracle.OracleSpawner(spawner, seed=SEED, uid=uid, transform=tf)
+    free = oracle.OracleSpawner(spawner, seed=SEED, uid=uid, transform=tf) if case < 8 else None
+    n = np_sim.Spawner(spawner, SEED, uid, tf)
+    live, kills = {}, 0
+    for i, (dt, pv) in enumerate(zip(sc["dts"], sc["pvs"])):
+        ev = sc["events"].get(i)
+        if ev is not None:
+            for name, _, _, _ in ev["placements"]:
+                if name not in live:
+                    live[name] = (oracle.OracleMesh(*sc["meshes"][name]), mesh_ref.Mesh(*sc["meshes"][name]))
+            o.set_colliders(ev["analytic"])
+            o.set_mesh_colliders([S.MeshCollider(live[name][0], p, q, layers) for name, p, q, layers in ev["placements"]])
+            n.colliders = mesh_ref.World(list(ev["analytic"]), [mesh_ref.Instance(live[name][1], p, q, layers)
+                                                                for name, p, q, layers in ev["placements"]])
+            for name in ev["destroy"]:
+                live.pop(name)[0].close()
+            if free is not None:
+                free.set_colliders(ev["analytic"])
+        o.set_parent_velocity(pv)
+        n.parent_velocity = np.asarray(pv, dtype=np.float32)
+        o.step(dt), n.step(dt)
+        if free is not None:
+            free.set_parent_velocity(pv)
+            free.step(dt)
+        assert o.counts() == [n.count(t) for t in range(n_types)], (case, i)
+        for t in range(n_types):
+            got, dead = o.particles(t), o.destroyed(t)
+            for f in ("position", "velocity", "rotation", "angular_velocity", "age", "lifetime", "initial_scale", "scale", "base_color", "emissive_color"):
+                assert np.array_equal(got[f], n.particles[t][f]), (case, i, t, f)
+            assert len(dead) == len(n.destroyed[t]["age"]), (case, i, t)
+            for f in ("position", "velocity", "rotation", "angular_velocity", "age", "lifetime", "initial_scale", "scale", "base_color", "emissive_color"):
+                assert np.array_equal(dead[f], n.destroyed[t][f]), (case, i, t, "destroyed", f)
+            kills += int(np.count_nonzero(dead["age"] < dead["lifetime"]))
+    moved = None
+    if free is not None:
+        moved = any(len(a) != len(b) or bool((a["position"] != b["position"]).any())
+                    for a, b in ((o.particles(t), free.particles(t)) for t in range(n_types)))
+    test_oracle_and_numpy_restatement_agree_on_random_colliding_spawners_with_meshes.stats[case] = dict(
+        total=sum(o.counts()), kills=kills, moved=moved, nested=sc["nested"], twice=sc["twice"], empty_and_back=sc["empty_and_back"],
+        analytic_free=sc["analytic_free"])
+    assert 90 <= max(sc["triangles"]) <= 2500, sc["triangles"]
+
+
+test_oracle_and_numpy_restatement_agree_on_random_colliding_spawners_with_meshes.stats = {}
+
+
+def test_the_colliding_cases_with_meshes_were_not_trivial():
+    """the conditions tests/test_gpu_fuzz.py::test_colliding_cases_with_meshes_were_not_trivial puts on these scenes hold for the
+    reference alone: the meshes change the outcome, particles die of mesh hits, a Nested entry, a mesh placed twice and the
+    empty-and-back switch each occur"""
+    _, fz = _mods()
+    stats = test_oracle_and_numpy_restatement_agree_on_random_colliding_spawners_with_meshes.stats
+    assert len(stats) == 16, "run together with the 16 cases above: this is their bookkeeping"
+    fz._assert_mesh_cases_were_not_trivial(stats, 8)
+    print({k: (v["total"], v["kills"], v["moved"]) for k, v in stats.items()})

@@ -405,3 +405,46 @@ def test_stress_test_collision_without_trigonometry_is_bit_exact(monkeypatch, ge
     g, c = _run_collision_example(monkeypatch, general, spawner, tf, world, 150, 30, True)
     assert len(g) > 150000
     assert np.count_nonzero((g["age"] > 1.2) & (g["velocity"][:, 1] > 0.0)) > 1000  # they do bounce
+
+
+@pytest.mark.parametrize("general", [False, True])
+def test_stress_test_collision_with_the_boxes_as_meshes_is_bit_exact(monkeypatch, general):
+    """the trig-free variant above with the example's two cuboids as 12-triangle meshes (tests/mesh_ref.py: box_mesh) at the boxes'
+    positions and rotations: the whole state bit for bit against the oracle's brute force through two seconds of bounces, on the
+    ring path (fw_k_update_fifo's mesh form) and on count -> scan -> fw_k_update_coll<MESH>; and a particle that has touched
+    nothing in the analytic world -- it equals the same particle of a world without colliders -- is the same in all three runs"""
+    import os
+    import sys
+
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import mesh_ref
+    import oracle
+    from bevy_firework_amd.system import ParticleSystem
+    from parity import MeshPair
+
+    spawner, tf, world = workloads.stress_test_collision(rate=20000.0)
+    es = spawner.emission_settings[0]
+    es = S.EmissionSettings(emission_pacing=es.emission_pacing, emission_shape=S.EmissionShape.Point(),
+                            initial_velocity=S.RandVec3(S.RandF32(3.0, 9.0), (0.0, 1.0, 0.0), 0.0), inherit_parent_velocity=True)
+    spawner = S.ParticleSpawner(spawner.particle_settings, [es])
+    frames = 150
+    analytic, _ = _run_collision_example(monkeypatch, general, spawner, tf, world, frames, 30, True)
+    free = oracle.OracleSpawner(spawner, seed=SEED, uid=0, transform=tf)
+    with ParticleSystem(device=0, seed=SEED) as system:  # (the knobs _run_collision_example set are still in place)
+        pair = Pair(system, spawner, tf, seed=SEED, uid=0)
+        boxes = [(MeshPair(system, *mesh_ref.box_mesh(c.half_extents)), c.position, c.rotation, c.layers) for c in world]
+        pair.set_world([], boxes)
+        assert pair.gpu.update_path(0)[0] == ("general" if general else "fifo")
+        for fr in range(frames):
+            system.update(DT)
+            pair.step_cpu(DT)
+            free.step(DT)
+            if fr % 30 == 29:
+                pair.check(exact_all=True, what=f"frame {fr}")
+        g, f = pair.gpu.particles(0), free.particles(0)
+    assert len(g) == len(analytic) == len(f) > 35000
+    untouched = (analytic["position"] == f["position"]).all(axis=1) & (analytic["velocity"] == f["velocity"]).all(axis=1)
+    assert 3000 < untouched.sum() < len(g) - 3000, int(untouched.sum())
+    for k in g.dtype.names:
+        assert np.array_equal(g[k][untouched], analytic[k][untouched]), k
+    assert np.count_nonzero((g["age"] > 1.2) & (g["velocity"][:, 1] > 0.0)) > 250  # they do bounce off the triangles

@@ -211,24 +211,48 @@ def test_random_scenario_with_api_calls_on_single_lifetime_types(case):
     _api_scenario(case, 23000, 0.9)
 
 
-def _api_scenario(case, seed_base, const_p):
+@pytest.mark.parametrize("case", range(OFF, OFF + 12 + EXTRA // 4))
+def test_random_scenario_with_api_calls_over_a_mesh_world(case):
+    """... on a trig-free COLLIDING spawner over mesh terrain (replaced half way): the same calls, the same checks, everything bit
+    for bit -- the attached type is the colliding type 0, so its instance records (plain and windowed attach) come out of the mesh
+    forms of the update kernels, and the bounds hold particles that bounced off triangles"""
+    _api_scenario(case, 65000, 0.0, mesh_world=True)
+
+
+def _api_scenario(case, seed_base, const_p, mesh_world=False):
     import torch
     from bevy_firework_amd.system import ParticleSystem
 
     rng = np.random.default_rng(seed_base + case)
-    spawner = _spawner(rng, scale=1.0 if case % 3 else 4.0, const_p=const_p)
+    if mesh_world:
+        types, entries = _colliding_types_and_entries(rng, rates=(300.0, 2500.0))
+        entries.append(S.EmissionSettings(particle_index=0, emission_pacing=S.EmissionPacing.OnDemand(),  # (what queue() feeds)
+                                          initial_velocity=S.RandVec3(S.RandF32(1.0, 5.0), (0.0, -1.0, 0.0), 0.0)))
+        spawner = S.ParticleSpawner(types, entries)
+        meshes = {}
+        terrains = [[(name, pos, q, 1 if k == 0 else layers) for k, (name, pos, q, layers) in enumerate(_mesh_placements(rng, meshes, tag)[0])]
+                    for tag in "ab"]  # (the first instance of each world on layer 1: every mask of the generator sees it)
+    else:
+        spawner = _spawner(rng, scale=1.0 if case % 3 else 4.0, const_p=const_p)
     for p in spawner.particle_settings:  # the destroyed stream only exists for types that register a handler
         p.particles_destroyed = (lambda dead: None) if rng.random() < 0.6 else None
     with ParticleSystem(device=0, seed=SEED) as system:
-        pair = Pair(system, spawner, S.Transform(), seed=SEED, uid=(seed_base // 30) + case)
+        pair = Pair(system, spawner, S.Transform((0.0, 2.0, 0.0)) if mesh_world else S.Transform(), seed=SEED, uid=(seed_base // 30) + case)
+        if mesh_world:
+            from parity import MeshPair
+
+            live = {name: MeshPair(system, *vt) for name, vt in meshes.items()}
+            pair.set_world([], [(live[name], p, q, layers) for name, p, q, layers in terrains[0]])
         buf = None
         # every other case attaches the WINDOWED buffer (records at [first, first + count): a range ring keeps its path)
         attach = pair.gpu.attach_instances_window if case % 2 else pair.gpu.attach_instances
         for i, dt in enumerate(_steps(rng, 30)):
             dt = np.float32(dt)
+            if mesh_world and i == 15:
+                pair.set_world([_collider(rng)], [(live[name], p, q, layers) for name, p, q, layers in terrains[1]])
             a = int(rng.integers(0, 8))
             if a == 0:
-                tf = S.Transform(tuple(float(c) for c in rng.uniform(-3.0, 3.0, size=3)),
+                tf = S.Transform(tuple(float(c) for c in rng.uniform(-3.0, 3.0, size=3) + (np.array([0.0, 2.0, 0.0]) if mesh_world else 0.0)),
                                  tuple(float(c) for c in (lambda q: q / np.linalg.norm(q))(rng.normal(size=4))))
                 pair.gpu.set_transform(tf)
                 pair.cpu.set_origin(tf.translation, tf.rotation)
@@ -258,11 +282,11 @@ def _api_scenario(case, seed_base, const_p):
             system.update(dt)
             pair.step_cpu(dt)
             if i % 3 == 2:
-                pair.check(what=f"case {case} frame {i}")
+                pair.check(exact_all=mesh_world, what=f"case {case} frame {i}")
                 for t in range(pair.n_types):
                     if spawner.particle_settings[t].particles_destroyed is not None:
                         from parity import assert_particles_match
-                        assert_particles_match(pair.gpu.destroyed(t), pair.cpu.destroyed(t), False, f"destroyed type {t} frame {i}")
+                        assert_particles_match(pair.gpu.destroyed(t), pair.cpu.destroyed(t), mesh_world, f"destroyed type {t} frame {i}")
                 any_g, mn_g, mx_g = pair.gpu.aabb()
                 any_c, mn_c, mx_c = pair.cpu.aabb()
                 assert any_g == any_c
@@ -279,6 +303,20 @@ def _api_scenario(case, seed_base, const_p):
                         raise AssertionError(f"case {case} frame {i}: instance records: {len(rows)} of {n} differ, rows "
                                              f"{rows[0]}..{rows[-1]}, first got {got[rows[0]].view(np.float32)} want "
                                              f"{want[rows[0]].view(np.float32)}")
+                    if mesh_world:
+                        _api_scenario.attached_records += n
+        if mesh_world:
+            _api_scenario.mesh_cases += 1
+
+
+_api_scenario.attached_records = _api_scenario.mesh_cases = 0  # (of the mesh-world variant: its bookkeeping below)
+
+
+def test_api_scenarios_over_a_mesh_world_compared_instance_records():
+    """bookkeeping: over the mesh-world scenarios a buffer was attached to the colliding type and records were compared"""
+    if _api_scenario.mesh_cases < 12:
+        pytest.skip("the API scenarios over a mesh world did not run in this session")
+    assert _api_scenario.attached_records > 1000, _api_scenario.attached_records
 
 
 @pytest.mark.parametrize("case", range(OFF, OFF + 16 + EXTRA // 32))
@@ -358,16 +396,9 @@ def _collider(rng):
     return S.Collider.Box(centre(), tuple(float(c) for c in rng.uniform(0.2, 1.0, size=3)), tuple(float(c) for c in q / np.linalg.norm(q)), layers)
 
 
-@pytest.mark.parametrize("case", range(OFF, OFF + 16 + EXTRA // 4))
-def test_random_colliding_spawner_matches_the_oracle_bit_for_bit(case):
-    """particle_collision (core.rs:744-800) under random settings: one to four random colliders (planes, spheres, rotated
-    boxes, tilted cylinders and cones, on different layers), random restitution / friction / destroy_on_collision / filter mask, one or two colliding
-    types next to a plain one, a Nested entry now and then, colliders replaced half way.  A bounce amplifies any
-    difference, so the scene is built without a single libm call (Point emission, zero spread: directions vary through the
-    entries and a parent velocity that changes every frame) and EVERY field is compared bit for bit."""
-    from bevy_firework_amd.system import ParticleSystem
-
-    rng = np.random.default_rng(41000 + case)
+def _colliding_types_and_entries(rng, rates=(500.0, 6000.0)):
+    """the trig-free colliding spawner of the random colliding scenes: one to three types (type 0 collides, the others may), one or
+    two Point entries with zero spread per type, a Nested entry now and then -> (types, emissions)"""
     n_types = int(rng.integers(1, 4))
     types = []
     for t in range(n_types):
@@ -386,7 +417,7 @@ def test_random_colliding_spawner_matches_the_oracle_bit_for_bit(case):
         for _ in range(int(rng.integers(1, 3))):
             d = rng.normal(size=3) + np.array([0.0, -1.0, 0.0])
             emissions.append(S.EmissionSettings(
-                particle_index=t, emission_pacing=S.EmissionPacing.rate(float(rng.uniform(500.0, 6000.0))),
+                particle_index=t, emission_pacing=S.EmissionPacing.rate(float(rng.uniform(*rates))),
                 initial_velocity=S.RandVec3(S.RandF32(0.5, float(rng.uniform(1.0, 9.0))), tuple(float(c) for c in d / np.linalg.norm(d)), 0.0),
                 inherit_parent_velocity=bool(rng.random() < 0.7)))
     if n_types >= 2 and rng.random() < 0.5:
@@ -394,6 +425,21 @@ def test_random_colliding_spawner_matches_the_oracle_bit_for_bit(case):
             particle_index=1, emission_mode=S.EmissionMode.Nested(0),
             emission_pacing=S.EmissionPacing.CountOverDuration(float(rng.uniform(2.0, 10.0)), 1.0, 0.0, float(rng.uniform(0.3, 1.0))),
             initial_velocity=S.RandVec3(S.RandF32(0.0, 2.0), (0.0, -1.0, 0.0), 0.0), inherit_parent_velocity=bool(rng.random() < 0.5)))
+    return types, emissions
+
+
+@pytest.mark.parametrize("case", range(OFF, OFF + 16 + EXTRA // 4))
+def test_random_colliding_spawner_matches_the_oracle_bit_for_bit(case):
+    """particle_collision (core.rs:744-800) under random settings: one to four random colliders (planes, spheres, rotated
+    boxes, tilted cylinders and cones, on different layers), random restitution / friction / destroy_on_collision / filter mask, one or two colliding
+    types next to a plain one, a Nested entry now and then, colliders replaced half way.  A bounce amplifies any
+    difference, so the scene is built without a single libm call (Point emission, zero spread: directions vary through the
+    entries and a parent velocity that changes every frame) and EVERY field is compared bit for bit."""
+    from bevy_firework_amd.system import ParticleSystem
+
+    rng = np.random.default_rng(41000 + case)
+    types, emissions = _colliding_types_and_entries(rng)
+    n_types = len(types)
     worlds = [[_collider(rng) for _ in range(int(rng.integers(1, 5)))] for _ in range(2)]
     with ParticleSystem(device=0, seed=SEED) as system:
         pair = Pair(system, S.ParticleSpawner(types, emissions), S.Transform(tuple(float(c) for c in rng.uniform(-0.5, 0.5, size=3) + np.array([0.0, 2.0, 0.0]))),
@@ -445,6 +491,234 @@ def test_colliding_cases_were_not_trivial():
         pytest.skip("the colliding cases did not run in this session")
     assert sum(bool(v[2]) for v in checked) >= len(checked) // 2, sizes
     assert sum(v[0] for v in sizes.values()) > 20000 and sum(v[1] for v in sizes.values()) > 0, sizes
+
+
+# ---- the colliding scenes again, in a world of triangle meshes ---------------------------------------------------------------
+MESH_SEED_BASE = 61000
+_DESTROYED_FIELDS = ("age", "position", "velocity", "scale", "rotation", "angular_velocity", "lifetime", "initial_scale", "base_color",
+                     "emissive_color")
+
+
+def _mesh_ref():
+    import sys
+
+    here = os.path.dirname(os.path.abspath(__file__))
+    if here not in sys.path:
+        sys.path.insert(0, here)
+    import mesh_ref
+
+    return mesh_ref
+
+
+def _quat(rng, p_identity=0.4):
+    """a random unit quaternion; now and then EXACTLY the identity (the `aligned` arm of the cast skips both rotations)"""
+    if rng.random() < p_identity:
+        return (0.0, 0.0, 0.0, 1.0)
+    q = rng.normal(size=4)
+    return tuple(float(c) for c in q / np.linalg.norm(q))
+
+
+def _mesh(rng, kind):
+    """one mesh where the particles pass (emitters around (0, 2, 0), mostly pointing down) -> ((vertices, indices), a position)"""
+    mr = _mesh_ref()
+    centre = (float(rng.uniform(-1.3, 1.3)), float(rng.uniform(-1.5, 1.8)), float(rng.uniform(-1.3, 1.3)))
+    if kind == "grid":  # a height field under the emitters: 128 .. 392 triangles, shared edges and vertices
+        n = int(rng.integers(8, 15))
+        a, fx, fz = float(rng.uniform(0.1, 0.5)), float(rng.uniform(0.5, 2.0)), float(rng.uniform(0.5, 2.0))
+        vt = mr.grid_mesh(n, n, extent=float(rng.uniform(2.0, 3.5)), height=lambda x, z: a * np.sin(fx * x) * np.cos(fz * z))
+        return vt, (float(rng.uniform(-0.5, 0.5)), float(rng.uniform(0.0, 1.4)), float(rng.uniform(-0.5, 0.5)))
+    if kind == "ico":  # closed: 80 or 320 triangles
+        return mr.icosphere(int(rng.integers(1, 3)), float(rng.uniform(0.4, 1.2))), centre
+    if kind == "soup":  # 40 .. 150 unrelated triangles of every size and direction
+        n = int(rng.integers(40, 151))
+        v = (rng.uniform(-1.0, 1.0, size=(n, 1, 3)) * 1.6 + rng.normal(size=(n, 3, 3)) * rng.uniform(0.05, 0.6, size=(n, 1, 1)))
+        return (v.reshape(-1, 3).astype(np.float32), np.arange(3 * n, dtype=np.uint32).reshape(-1, 3)), (0.0, float(rng.uniform(0.3, 1.2)), 0.0)
+    return mr.box_mesh(tuple(float(c) for c in rng.uniform(0.2, 1.0, size=3))), centre
+
+
+def _mesh_placements(rng, meshes, tag):
+    """one to three instances of freshly drawn meshes (added to `meshes` under new names); in some draws the first mesh is placed twice"""
+    out = []
+    for k in range(int(rng.integers(1, 4))):
+        kind = str(rng.choice(["grid", "grid", "ico", "soup", "box"] if k else ["grid", "grid", "ico", "soup"]))
+        name = f"{tag}{k}-{kind}"
+        meshes[name], pos = _mesh(rng, kind)
+        out.append((name, pos, _quat(rng), int(rng.choice([1, 1, 2, 3]))))
+    twice = bool(rng.random() < 0.35)
+    if twice:
+        name, pos, _, _ = out[0]
+        out.append((name, tuple(float(c + d) for c, d in zip(pos, rng.uniform(-0.6, 0.6, size=3))), _quat(rng), int(rng.choice([1, 1, 2, 3]))))
+    return out, twice
+
+
+def _mesh_scene(case, seed_base=MESH_SEED_BASE):
+    """The random colliding scene (`_colliding_types_and_entries`: types, entries, Nested entry, destroy flags, masks) in a world of
+    one to three mesh instances (height field, icosphere, soup, box; random rotations, some exactly identity; layers; one mesh placed
+    twice now and then) with zero to two analytic colliders on top.  Half way the world changes, in one of four ways by case number:
+    0 / 3 everything is replaced (the old meshes are destroyed), 1 the instance set is emptied and the new world arrives two frames
+    later, 2 the first mesh stays placed while the others are destroyed and a new one is created next to it.  Pure data: the GPU test
+    and its CPU twin (tests/test_fuzz_cpu.py) build their worlds from it.  About 100 .. 1500 triangles and a few thousand particles:
+    the numpy brute force of the twin is rays x triangles."""
+    rng = np.random.default_rng(seed_base + case)
+    types, emissions = _colliding_types_and_entries(rng, rates=(150.0, 900.0))
+    n_an = int(rng.integers(0, 3))
+    meshes = {}
+    first, twice0 = _mesh_placements(rng, meshes, "a")
+    second, twice1 = _mesh_placements(rng, meshes, "b")
+    analytic = [[_collider(rng) for _ in range(n_an)] for _ in range(2)]
+    how = case % 4
+    events = {0: dict(analytic=analytic[0], placements=first, destroy=[])}
+    old = sorted({p[0] for p in first})
+    if how == 1:
+        events[20] = dict(analytic=analytic[0], placements=[], destroy=old)
+        events[22] = dict(analytic=analytic[1], placements=second, destroy=[])
+    elif how == 2:
+        stays = first[0]
+        events[20] = dict(analytic=analytic[1], placements=[stays] + second[:1], destroy=[n for n in old if n != stays[0]])
+    else:
+        events[20] = dict(analytic=analytic[1], placements=second, destroy=old)
+    tf = S.Transform(tuple(float(c) for c in rng.uniform(-0.5, 0.5, size=3) + np.array([0.0, 2.0, 0.0])))
+    dts = [np.float32(dt) for dt in _steps(rng, 40)]
+    pvs = [tuple(float(np.float32(c)) for c in rng.uniform(-1.0, 1.0, size=3)) for _ in dts]
+    return dict(spawner=S.ParticleSpawner(types, emissions), transform=tf, uid=7100 + case, meshes=meshes, events=events, dts=dts, pvs=pvs,
+                nested=any(e.emission_mode.kind == S.MODE_NESTED for e in emissions), twice=twice0 or (twice1 and how != 2),
+                empty_and_back=how == 1, analytic_free=n_an == 0,
+                triangles=[sum(len(meshes[p[0]][1]) for p in ev["placements"]) for ev in events.values()])
+
+
+def _assert_mesh_cases_were_not_trivial(stats, n_free):
+    """the conditions both the GPU test and its CPU twin put on the scenes (stats: case -> dict)"""
+    free = [v for v in stats.values() if v["moved"] is not None]
+    assert len(free) >= n_free, sorted(stats)
+    assert sum(bool(v["moved"]) for v in free) >= (len(free) + 1) // 2, stats   # the meshes change the outcome
+    # destroyed by a hit (age < lifetime) in worlds that never held an analytic collider: by a MESH hit
+    assert sum(v["kills"] for v in stats.values() if v["analytic_free"]) > 0, stats
+    for flag in ("nested", "twice", "empty_and_back"):
+        assert any(v[flag] for v in stats.values()), (flag, stats)
+    assert sum(v["total"] for v in stats.values()) > 5000, stats
+
+
+@pytest.mark.parametrize("case", range(OFF, OFF + 16 + EXTRA // 4))
+def test_random_colliding_spawner_with_meshes_matches_the_oracle_bit_for_bit(case):
+    """`_mesh_scene`: the random colliding spawners in a world of triangle meshes, against the oracle's brute force over every
+    triangle (which the device's hierarchy and its wave-level instance skip must therefore cull conservatively) -- EVERY field of
+    the live particles and of the destroyed records of every type bit for bit, every 8 frames"""
+    from bevy_firework_amd.system import ParticleSystem
+    from parity import MeshPair
+    import oracle
+
+    sc = _mesh_scene(case)
+    n_types = len(sc["spawner"].particle_settings)
+    with ParticleSystem(device=0, seed=SEED) as system:
+        pair = Pair(system, sc["spawner"], sc["transform"], seed=SEED, uid=sc["uid"])
+        # the same spawner with the analytic colliders only: how much do the meshes matter?
+        free = oracle.OracleSpawner(pair.spawner, seed=SEED, uid=sc["uid"], transform=pair.cpu_transform) if case - OFF < 8 else None
+        live, kills = {}, 0
+        for i, (dt, pv) in enumerate(zip(sc["dts"], sc["pvs"])):
+            ev = sc["events"].get(i)
+            if ev is not None:
+                for name, _, _, _ in ev["placements"]:
+                    if name not in live:
+                        live[name] = MeshPair(system, *sc["meshes"][name])
+                pair.set_world(ev["analytic"], [(live[name], p, q, layers) for name, p, q, layers in ev["placements"]])
+                for name in ev["destroy"]:
+                    live.pop(name).destroy()
+                if free is not None:
+                    free.set_colliders(ev["analytic"])
+            pair.gpu.set_parent_velocity(pv)
+            pair.cpu.set_parent_velocity(pv)
+            system.update(dt)
+            pair.step_cpu(dt)
+            if free is not None:
+                free.set_parent_velocity(pv)
+                free.step(dt)
+            for t in range(n_types):
+                cd = pair.cpu.destroyed(t)
+                kills += int(np.count_nonzero(cd["age"] < cd["lifetime"]))
+                if i % 8 == 7:
+                    gd = pair.gpu.destroyed(t)
+                    assert len(gd) == len(cd), f"case {case} frame {i} type {t}: destroyed {len(gd)} != {len(cd)}"
+                    for f in _DESTROYED_FIELDS:
+                        assert np.array_equal(gd[f], cd[f]), f"case {case} frame {i} type {t}: destroyed.{f}"
+            if i % 8 == 7:
+                pair.check(exact_all=True, what=f"case {case} frame {i}")
+        moved = None
+        if free is not None:
+            moved = any(len(a) != len(b) or bool((a["position"] != b["position"]).any())
+                        for a, b in ((pair.cpu.particles(t), free.particles(t)) for t in range(n_types)))
+            free.close()
+        test_random_colliding_spawner_with_meshes_matches_the_oracle_bit_for_bit.stats[case] = dict(
+            total=sum(pair.gpu.counts()), kills=kills, moved=moved, nested=sc["nested"], twice=sc["twice"],
+            empty_and_back=sc["empty_and_back"], analytic_free=sc["analytic_free"])
+
+
+test_random_colliding_spawner_with_meshes_matches_the_oracle_bit_for_bit.stats = {}
+
+
+def test_colliding_cases_with_meshes_were_not_trivial():
+    """bookkeeping for the cases above (tests/test_fuzz_cpu.py asserts the same of the oracle alone, where there is no GPU)"""
+    stats = test_random_colliding_spawner_with_meshes_matches_the_oracle_bit_for_bit.stats
+    if len(stats) < 16:
+        pytest.skip("the colliding cases with meshes did not run in this session")
+    _assert_mesh_cases_were_not_trivial(stats, 8)
+
+
+@pytest.mark.parametrize("case", range(OFF, OFF + 4 + EXTRA // 16))
+def test_random_multi_spawner_system_in_a_mesh_world(case):
+    """test_random_multi_spawner_system with a collider world of meshes in the context: a dozen random spawners that do not collide
+    (trigonometry allowed: the tolerance of parity.py, as without a world -- the world must not change them) next to four trig-free
+    colliding ones (bit for bit; small types among many: the wave-per-type kernel's colliding form on the `small` path); spawners
+    are despawned and replaced, the world is replaced half way and its old meshes destroyed"""
+    from bevy_firework_amd.system import ParticleSystem
+    from parity import MeshPair, set_world
+
+    rng = np.random.default_rng(63000 + case)
+    meshes = {}
+    worlds = [(_mesh_placements(rng, meshes, tag)[0], [_collider(rng) for _ in range(int(rng.integers(0, 3)))]) for tag in "ab"]
+
+    def make(k):
+        if k < 12:
+            return _spawner(rng, scale=0.5), S.Transform(tuple(float(c) for c in rng.uniform(-3.0, 3.0, size=3)))
+        types, entries = _colliding_types_and_entries(rng, rates=(150.0, 900.0))
+        return S.ParticleSpawner(types, entries), S.Transform(tuple(float(c) for c in rng.uniform(-0.5, 0.5, size=3) + np.array([0.0, 2.0, 0.0])))
+
+    with ParticleSystem(device=0, seed=SEED) as system:
+        pairs = []
+        for k in range(16):
+            spawner, tf = make(k)
+            pairs.append(Pair(system, spawner, tf, seed=SEED, uid=300 + 32 * case + k))
+        next_uid = 300 + 32 * case + 16
+        live = {}
+
+        def place(world):
+            placements, analytic = world
+            for name, _, _, _ in placements:
+                if name not in live:
+                    live[name] = MeshPair(system, *meshes[name])
+            set_world(system, pairs, analytic, [(live[name], p, q, layers) for name, p, q, layers in placements])
+            for name in [n for n in live if n not in {p[0] for p in placements}]:
+                live.pop(name).destroy()
+
+        place(worlds[0])
+        for i, dt in enumerate(_steps(rng, 30)):
+            dt = np.float32(dt)
+            if i in (7, 13, 21):
+                k = int(rng.integers(0, len(pairs))) if i != 13 else 12 + int(rng.integers(0, 4))  # (13: a colliding one for certain)
+                system.despawn(pairs[k].gpu)
+                pairs[k].cpu.close()
+                spawner, tf = make(k)
+                pairs[k] = Pair(system, spawner, tf, seed=SEED, uid=2000 * (case + 1) + next_uid)
+                next_uid += 1
+                place(worlds[0] if i < 15 else worlds[1])  # (the new oracle spawner gets the world the context holds)
+            if i == 15:
+                place(worlds[1])
+            system.update(dt)
+            for p in pairs:
+                p.step_cpu(dt)
+            if i % 10 == 9 or i in (8, 14, 16, 22):
+                for k, p in enumerate(pairs):
+                    p.check(exact_all=k >= 12, what=f"case {case} spawner {k} frame {i}")
+        assert sum(sum(p.gpu.counts()) for p in pairs[:12]) > 3000 and sum(sum(p.gpu.counts()) for p in pairs[12:]) > 300
 
 
 @pytest.mark.parametrize("case", range(OFF, OFF + 24 + EXTRA // 2))

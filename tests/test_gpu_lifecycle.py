@@ -290,3 +290,150 @@ def test_lifecycle_cases_were_not_trivial():
     assert all(set(v[1]) >= {"range", "general", "small"} for v in SEEN.values() if v[0] == "scenario_small_mode"), SEEN
     assert all("fifo" in v[1] for v in SEEN.values() if v[0] not in ("scenario_many", "scenario_small_mode")), SEEN
     assert sum(v[3] for v in SEEN.values()) > 20000 * len(SEEN) // 10, SEEN
+
+
+# ---- the same thresholds with a world of triangle meshes in the context ---------------------------------------------------------
+MESH_SEEN = {}
+
+
+def _colliding(rng, rate_lo, rate_hi, lo, hi):
+    """one trig-free colliding type (Point emission, zero spread, no spin: compared bit for bit), bouncing"""
+    lo = float(rng.uniform(lo, hi))
+    p = S.ParticleSettings(lifetime=S.RandF32(lo, lo + 0.1) if rng.random() < 0.6 else S.RandF32.constant(lo), scale_curve=_curve(rng),
+                           initial_scale=S.RandF32(0.01, 0.05), acceleration=tuple(float(c) for c in rng.uniform(-10.0, 3.0, size=3)),
+                           linear_drag=float(rng.uniform(0.0, 0.5)), base_color=_gradient(rng),
+                           collision_settings=S.ParticleCollisionSettings(float(rng.uniform(0.0, 1.0)), float(rng.uniform(0.0, 1.0)), False,
+                                                                          int(rng.choice([0xFFFFFFFF, 1, 3]))))
+    d = rng.normal(size=3) + np.array([0.0, -1.5, 0.0])
+    e = S.EmissionSettings(particle_index=0, emission_pacing=S.EmissionPacing.rate(float(rng.uniform(rate_lo, rate_hi))),
+                           initial_velocity=S.RandVec3(S.RandF32(0.5, float(rng.uniform(2.0, 12.0))), tuple(float(c) for c in d / np.linalg.norm(d)), 0.0),
+                           inherit_parent_velocity=False)
+    return S.ParticleSpawner([p], [e])
+
+
+class MeshWorld(World):
+    """World whose spawners are trig-free colliding ones ("ctiny": a few hundred particles, "cdust": 50 - 250) in a context that holds
+    mesh instances part of the time; every oracle spawner is given the world the context holds"""
+
+    def __init__(self, system, rng, case):
+        import test_gpu_fuzz as fz
+        from parity import MeshPair
+
+        super().__init__(system, rng, case)
+        self.fz, self.MeshPair = fz, MeshPair
+        self.live, self.placed, self.analytic = {}, [], []
+        self.generation = 0
+        self.with_meshes, self.switched_on = set(), set()  # paths checked with n_mesh_inst > 0 / on which the instance set toggled
+
+    def add(self, kind):
+        tf = S.Transform(tuple(float(c) for c in self.rng.uniform(-1.0, 1.0, size=3) + np.array([0.0, 2.0, 0.0])))
+        sp = _colliding(self.rng, 300.0, 1500.0, 0.15, 0.4) if kind == "ctiny" else _colliding(self.rng, 200.0, 600.0, 0.12, 0.2)
+        pair = Pair(self.system, sp, tf, seed=SEED, uid=self.uid)
+        pair.cpu.set_colliders(self.analytic)
+        pair.cpu.set_mesh_colliders([S.MeshCollider(m.cpu, p, q, layers) for m, p, q, layers in self.placed])
+        self.pairs.append(pair)
+        self.kinds.append(kind)
+        self.uid += 1
+
+    def new_world(self):
+        """freshly created meshes are placed; the ones of the previous world are destroyed once nothing places them"""
+        from parity import set_world
+
+        meshes = {}
+        placements, _ = self.fz._mesh_placements(self.rng, meshes, f"g{self.generation}-")
+        self.generation += 1
+        old, self.live = self.live, {name: self.MeshPair(self.system, *vt) for name, vt in meshes.items()}
+        # (layer 1 for the first instance: every mask of _colliding sees it)
+        self.placed = [(self.live[name], p, q, 1 if k == 0 else layers) for k, (name, p, q, layers) in enumerate(placements)]
+        self.analytic = [self.fz._collider(self.rng)] if self.rng.random() < 0.5 else []
+        set_world(self.system, self.pairs, self.analytic, self.placed)
+        for m in old.values():
+            m.destroy()
+
+    def toggle(self, what):
+        """instance set -> empty -> (a few frames) -> back, the state checked on both sides of each switch"""
+        from parity import set_world
+
+        self.switched_on.update(p for row in self.paths() for p in row)
+        keep, self.placed = self.placed, []
+        set_world(self.system, self.pairs, self.analytic, [])
+        self.step(int(self.rng.integers(1, 4)))
+        self.check(f"{what}: no mesh instances")
+        self.placed = keep
+        if self.rng.random() < 0.5:
+            self.new_world()
+        else:
+            set_world(self.system, self.pairs, self.analytic, self.placed)
+        self.step(int(self.rng.integers(2, 5)))
+        self.check(f"{what}: mesh instances again")
+
+    def check(self, what, limit=14):
+        rows = self.paths()
+        if self.placed:
+            self.with_meshes.update(p for row in rows for p in row)
+        order = [k for k, kind in enumerate(self.kinds) if kind == "ctiny"]
+        rest = [k for k in range(len(self.pairs)) if k not in order]
+        self.rng.shuffle(rest)
+        for k in (order[:6] + rest)[:limit]:
+            self.pairs[k].check(exact_all=True, what=f"case {self.case} frame {self.frames} ({what}) spawner {k} [{self.kinds[k]}] path {rows[k]}")
+
+
+@pytest.mark.parametrize("case", range(OFF, OFF + 8 + (CASES - 200) // 25))
+def test_lifecycle_with_a_mesh_world_at_product_defaults(case, monkeypatch):
+    """fw_ctx picks the mesh form of a kernel PER LAUNCH (FwGlobals::n_mesh_inst): histories at product defaults in which trig-free
+    colliding spawners come and go so that their types move range ring -> workgroups of the compacting kernels -> a wave each and back,
+    while the instance set toggles between empty and non-empty on every one of these paths and meshes are created and destroyed;
+    bit for bit against the oracle after every transition"""
+    from bevy_firework_amd.system import ParticleSystem
+
+    for k in KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    rng = np.random.default_rng(79000 + case)
+    with ParticleSystem(device=0, seed=SEED) as system:
+        w = MeshWorld(system, rng, case)
+        for _ in range(int(rng.integers(2, 5))):
+            w.add("ctiny")
+        w.new_world()
+        w.step(int(rng.integers(8, 20)))
+        w.check("few")
+        assert all(row == ("range",) for row in w.paths()), w.paths()
+        w.toggle("range rings")
+        while w.segments() <= RANGE_FEW:
+            w.add("cdust")
+            if rng.random() < 0.05:
+                w.step(1)
+        assert all(row == ("general",) for row in w.paths()), w.paths()
+        w.check("right after the context outgrew fw_ctx::range_few")
+        w.step(int(rng.integers(4, 10)))
+        w.toggle("compacting kernels")
+        while sum(kind == "cdust" for kind in w.kinds) < SMALL_MIN + int(rng.integers(0, 8)):
+            w.add("cdust")
+            if rng.random() < 0.03:
+                w.step(1)
+        assert all(row == ("small",) for row, kind in zip(w.paths(), w.kinds) if kind == "cdust"), [r for r in w.paths() if r != ("small",)]
+        w.check("right after the wave-per-type kernel took over")
+        w.step(int(rng.integers(4, 10)))
+        w.toggle("one wave per type")
+        while w.segments() >= SMALL_MIN * 3 // 4 - int(rng.integers(0, 10)):
+            w.remove(int(rng.integers(0, len(w.pairs))))
+            if rng.random() < 0.03:
+                w.step(1)
+        assert not any(row == ("small",) for row, kind in zip(w.paths(), w.kinds) if kind == "cdust"), w.paths()
+        w.check("right after the compacting kernels took over again")
+        w.step(int(rng.integers(3, 8)))
+        while w.segments() > int(rng.integers(8, 30)):
+            w.remove(int(rng.integers(0, len(w.pairs))))
+        w.add("ctiny")
+        assert w.paths()[-1] == ("range",), (w.segments(), w.paths()[-1])
+        w.step(int(rng.integers(6, 15)))
+        w.check("few again")
+        MESH_SEEN[case] = (sorted(w.with_meshes), sorted(w.switched_on), w.frames, sum(sum(p.gpu.counts()) for p in w.pairs), w.generation)
+
+
+def test_lifecycle_cases_with_a_mesh_world_were_not_trivial():
+    if len(MESH_SEEN) < 8:
+        pytest.skip("the lifecycle cases with a mesh world did not run in this session")
+    for v in MESH_SEEN.values():
+        assert set(v[0]) >= {"range", "general", "small"}, MESH_SEEN   # each path checked with mesh instances in the context
+        assert set(v[1]) >= {"range", "general", "small"}, MESH_SEEN   # ... and the instance set switched on each
+        assert v[4] >= 1 and v[3] > 500, MESH_SEEN

@@ -224,6 +224,73 @@ def test_oracle_follows_the_numpy_trajectories(name):
     assert sum(o.counts()) > 500
 
 
+@pytest.mark.parametrize("name", ["mesh_terrain_bouncing", "mesh_terrain_destroying"])
+def test_oracle_follows_the_numpy_mesh_trajectories(name):
+    """tests/golden/mesh_trajectories.npz: np_sim.py with the brute-force mesh cast of tests/mesh_ref.py over scenarios.MESH (a
+    terrain mesh placed twice + an analytic ball).  The oracle's own brute force reproduces every stored field of the live particles
+    and of the destroyed records bit for bit (no libm call in these scenes)."""
+    import parity
+
+    sc_mod = _scenarios()
+    sc = sc_mod.MESH[name]()
+    g = np.load(os.path.join(G, "mesh_trajectories.npz"))
+    o = oracle.OracleSpawner(sc["spawner"], seed=sc_mod.SEED, uid=sc["uid"], transform=sc["transform"])
+    o.set_parent_velocity(sc["parent_velocity"])
+    ms = {k: oracle.OracleMesh(*vt) for k, vt in sc["meshes"].items()}
+    o.set_colliders(sc["colliders"])
+    o.set_mesh_colliders([S.MeshCollider(ms[k], p, q, layers) for k, p, q, layers in sc["mesh_instances"]])
+    seen = {"live": 0, "bounced": 0, "dead on contact": 0}
+
+    def check(fr):
+        want = parity.golden_particles(name, fr, 0, g)
+        got = o.particles(0)
+        parity.assert_particles_match(got, want, exact_all=True, what=f"{name} frame {fr}")
+        assert np.array_equal(o.last_emitted(0, 0), g[f"{name}/f{fr}/t0/last_emitted_age"][:, 0])
+        dead = o.destroyed(0)
+        for k in ("age", "position", "velocity", "scale"):
+            assert np.array_equal(dead[k], g[f"{name}/f{fr}/t0/destroyed_{k}"]), (name, fr, k)
+        seen["live"] = len(got)
+        seen["bounced"] += int((got["velocity"][:, 1] > 0).sum())  # (emitted downwards, no acceleration: moving up means a bounce)
+        seen["dead on contact"] += int((dead["age"] < dead["lifetime"]).sum())
+
+    parity.run_scenario(sc, lambda: o.step, check)
+    # the scene is not empty and the surfaces matter.  Bouncing destroys nothing, and the last checkpoint lies past the longest
+    # lifetime, so at least rate x shortest lifetime = 240 x 0.8 = 192 particles live (one less for the emission's rounding);
+    # contact deaths leave no such floor, there the records themselves must exist
+    if name.endswith("destroying"):
+        assert seen["live"] > 0 and seen["dead on contact"] > 0, seen
+    else:
+        assert seen["live"] >= 191 and seen["bounced"] > 0, seen
+
+
+def test_mesh_fixture_is_reproducible():
+    """the committed mesh trajectories are what np_sim.py + mesh_ref.py produce today"""
+    import sys
+
+    sys.path.insert(0, G)
+    sys.path.insert(0, os.path.dirname(G))
+    import mesh_ref
+    import np_sim
+
+    sc_mod = _scenarios()
+    name = "mesh_terrain_bouncing"
+    sc = sc_mod.MESH[name]()
+    g = np.load(os.path.join(G, "mesh_trajectories.npz"))
+    sim = np_sim.Spawner(sc["spawner"], sc_mod.SEED, sc["uid"], sc["transform"], sc["modifier"])
+    sim.parent_velocity = np.asarray(sc["parent_velocity"], dtype=np.float32)
+    ms = {k: mesh_ref.Mesh(*vt) for k, vt in sc["meshes"].items()}
+    sim.colliders = mesh_ref.World(list(sc["colliders"]), [mesh_ref.Instance(ms[k], p, q, layers) for k, p, q, layers in sc["mesh_instances"]])
+    analytic, np_sim.cast_ray = np_sim.cast_ray, mesh_ref.cast_ray
+    try:
+        fr = sc["checkpoints"][1]
+        for k in range(fr + 1):
+            sim.step(np.float32(sc["dts"][k % len(sc["dts"])]))
+    finally:
+        np_sim.cast_ray = analytic
+    for k, v in sim.particles[0].items():
+        assert np.array_equal(v.view(np.uint32), g[f"{name}/f{fr}/t0/{k}"].view(np.uint32)), k
+
+
 def test_fixtures_are_reproducible():
     """the committed trajectories are what np_sim.py produces today (the generator is part of the repo)"""
     import sys
