@@ -37,10 +37,9 @@ struct Item {
     bool right;      // the parent's second child
 };
 
-}  // namespace
-
-int fw_bvh_build(const float *xyz, uint32_t n_vertices, const uint32_t *indices, uint32_t n_triangles, FwBvh *out,
-                 std::string *err) {
+// the one builder behind both entries; keep_all: a deformable mesh (every triangle gets a slot, the refit tables are filled)
+int build(const float *xyz, uint32_t n_vertices, const uint32_t *indices, uint32_t n_triangles, bool keep_all, FwBvh *out,
+          std::string *err) {
     *out = FwBvh{};
     if (!xyz || !indices || n_vertices == 0 || n_triangles == 0) return *err = "empty mesh", -1;
     if (n_triangles > (1u << 28)) return *err = "more than 2^28 triangles", -1;
@@ -54,6 +53,8 @@ int fw_bvh_build(const float *xyz, uint32_t n_vertices, const uint32_t *indices,
     std::vector<Prim> P;
     tri.reserve((size_t)n_triangles * 12);
     P.reserve(n_triangles);
+    std::vector<uint32_t> slot_src;  // keep_all: per kept triangle {its three vertex indices, its original index}
+    uint32_t n_live = 0;
     float maxabs = 0.0f;
     for (uint32_t t = 0; t < n_triangles; t++) {
         const float *v[3] = {xyz + 3 * (size_t)indices[3 * (size_t)t], xyz + 3 * (size_t)indices[3 * (size_t)t + 1],
@@ -63,7 +64,9 @@ int fw_bvh_build(const float *xyz, uint32_t n_vertices, const uint32_t *indices,
         // c = cross(e1, e2) in fw_cross's operation order
         const float c[3] = {e1[1] * e2[2] - e2[1] * e1[2], e1[2] * e2[0] - e2[2] * e1[0], e1[0] * e2[1] - e2[0] * e1[1]};
         const float cc = (c[0] * c[0] + c[1] * c[1]) + c[2] * c[2];
-        if (!(cc > 0.0f) || !std::isfinite(cc)) continue;
+        const bool live = cc > 0.0f && std::isfinite(cc);
+        if (!live && !keep_all) continue;
+        n_live += live;
         Prim p;
         for (int k = 0; k < 3; k++) {
             p.lo[k] = std::min(v[0][k], std::min(v[1][k], v[2][k]));
@@ -73,10 +76,16 @@ int fw_bvh_build(const float *xyz, uint32_t n_vertices, const uint32_t *indices,
         }
         p.tri = (uint32_t)P.size();
         P.push_back(p);
-        const float rec[12] = {v[0][0], v[0][1], v[0][2], bits_f(t), e1[0], e1[1], e1[2], 0.0f, e2[0], e2[1], e2[2], 0.0f};
+        // (a dropped triangle of a deformable mesh: e1 = e2 = 0, the record no ray hits -- fw_refit.h)
+        const float rec[12] = {v[0][0], v[0][1], v[0][2], bits_f(t), live ? e1[0] : 0.0f, live ? e1[1] : 0.0f, live ? e1[2] : 0.0f, 0.0f,
+                               live ? e2[0] : 0.0f, live ? e2[1] : 0.0f, live ? e2[2] : 0.0f, 0.0f};
         tri.insert(tri.end(), rec, rec + 12);
+        if (keep_all) {
+            const uint32_t si[4] = {indices[3 * (size_t)t], indices[3 * (size_t)t + 1], indices[3 * (size_t)t + 2], t};
+            slot_src.insert(slot_src.end(), si, si + 4);
+        }
     }
-    if (P.empty()) return *err = "no triangle of non-zero area", -1;
+    if (n_live == 0) return *err = "no triangle of non-zero area", -1;
     // Every box is grown by `pad` on each side.  The rounding of the slab test and of the triangle test is a few ulps of the
     // terms they subtract -- the ray origin in the mesh's frame against box faces and vertices -- and a ray can only hit the
     // mesh from within max_distance of it, so those terms stay below (largest vertex coordinate + max_distance).  The pad
@@ -88,6 +97,7 @@ int fw_bvh_build(const float *xyz, uint32_t n_vertices, const uint32_t *indices,
     const uint32_t n = (uint32_t)P.size();
     std::vector<float> &nodes = out->nodes;
     std::vector<int32_t> second;  // per node: index of its second child (-1: a leaf)
+    std::vector<int32_t> &parent = out->parent;
     nodes.reserve((size_t)2 * n * 8);
     second.reserve((size_t)2 * n);
     std::vector<uint32_t> leaf_order;
@@ -160,6 +170,7 @@ int fw_bvh_build(const float *xyz, uint32_t n_vertices, const uint32_t *indices,
                               box.hi[0] + pad, box.hi[1] + pad, box.hi[2] + pad, bits_f(leaf)};
         nodes.insert(nodes.end(), rec, rec + 8);
         second.push_back(-1);
+        parent.push_back(it.parent);
         if (!leaf) {  // the first child next (node idx + 1), the second after the first one's subtree
             stack.push_back({mid, it.e, (int32_t)idx, true});
             stack.push_back({it.b, mid, (int32_t)idx, false});
@@ -179,5 +190,57 @@ int fw_bvh_build(const float *xyz, uint32_t n_vertices, const uint32_t *indices,
     for (uint32_t i = 0; i < n; i++) memcpy(&out->tris[(size_t)i * 12], &tri[(size_t)leaf_order[i] * 12], 12 * sizeof(float));
     out->n_nodes = n_nodes, out->n_tris = n, out->pad = pad;
     for (int k = 0; k < 3; k++) out->lo[k] = nodes[k], out->hi[k] = nodes[4 + k];
+    if (!keep_all) return parent.clear(), 0;
+    out->slots.resize((size_t)n * 4);
+    for (uint32_t i = 0; i < n; i++) memcpy(&out->slots[(size_t)i * 4], &slot_src[(size_t)leaf_order[i] * 4], 4 * sizeof(uint32_t));
+    // the refit's schedule: nodes by height (a leaf: 0; an interior node: 1 + its higher child), so that every node of a level
+    // depends on lower levels only.  Children follow their parents in preorder: one pass backwards has the heights.
+    std::vector<uint32_t> height(n_nodes, 0u);
+    uint32_t top = 0;
+    for (uint32_t i = n_nodes; i-- > 1;) {
+        height[parent[i]] = std::max(height[parent[i]], height[i] + 1u);
+    }
+    top = height[0];
+    out->level_off.assign((size_t)top + 2, 0u);
+    for (uint32_t i = 0; i < n_nodes; i++) out->level_off[height[i] + 1]++;
+    for (uint32_t l = 0; l <= top; l++) out->level_off[l + 1] += out->level_off[l];
+    out->order.resize(n_nodes);
+    std::vector<uint32_t> at(out->level_off.begin(), out->level_off.end() - 1);
+    for (uint32_t i = 0; i < n_nodes; i++) out->order[at[height[i]]++] = i;
     return 0;
+}
+
+}  // namespace
+
+int fw_bvh_build(const float *xyz, uint32_t n_vertices, const uint32_t *indices, uint32_t n_triangles, FwBvh *out,
+                 std::string *err) {
+    return build(xyz, n_vertices, indices, n_triangles, false, out, err);
+}
+
+int fw_bvh_build_deformable(const float *xyz, uint32_t n_vertices, const uint32_t *indices, uint32_t n_triangles, FwBvh *out,
+                            std::string *err) {
+    return build(xyz, n_vertices, indices, n_triangles, true, out, err);
+}
+
+int64_t fw_bvh_stage_vertices(const float *xyz, const uint8_t *referenced, uint32_t n_vertices, float *dst, float lo[3], float hi[3],
+                              float *pad) {
+    float maxabs = 0.0f;
+    for (int k = 0; k < 3; k++) lo[k] = INFINITY, hi[k] = -INFINITY;
+    for (uint32_t v = 0; v < n_vertices; v++) {
+        const float x[3] = {xyz[3 * (size_t)v], xyz[3 * (size_t)v + 1], xyz[3 * (size_t)v + 2]};
+        if (!std::isfinite(x[0]) || !std::isfinite(x[1]) || !std::isfinite(x[2])) return (int64_t)v;
+        if (dst) dst[3 * (size_t)v] = x[0], dst[3 * (size_t)v + 1] = x[1], dst[3 * (size_t)v + 2] = x[2];
+        if (!referenced[v]) continue;
+        for (int k = 0; k < 3; k++) {
+            lo[k] = std::min(lo[k], x[k]), hi[k] = std::max(hi[k], x[k]);
+            maxabs = std::max(maxabs, std::fabs(x[k]));
+        }
+    }
+    *pad = std::max(1e-4f * maxabs, 1e-30f);
+    for (int k = 0; k < 3; k++) lo[k] = lo[k] - *pad, hi[k] = hi[k] + *pad;
+    return -1;
+}
+
+void fw_bvh_bounds(const float *xyz, const uint8_t *referenced, uint32_t n_vertices, float lo[3], float hi[3], float *pad) {
+    (void)fw_bvh_stage_vertices(xyz, referenced, n_vertices, nullptr, lo, hi, pad);
 }

@@ -24,6 +24,11 @@ struct FwBvh {
     uint32_t n_nodes = 0, n_tris = 0;
     float lo[3] = {0.0f, 0.0f, 0.0f}, hi[3] = {0.0f, 0.0f, 0.0f};  // the root's box (padded)
     float pad = 0.0f;                                                // what every box was grown by on each side
+    // fw_bvh_build_deformable only -- what a refit (fw_refit.h) needs next to the two tables:
+    std::vector<uint32_t> slots;      // per leaf-order triangle slot {vertex 0, 1, 2, original index}
+    std::vector<int32_t> parent;      // per node (-1: the root)
+    std::vector<uint32_t> order;      // every node, sorted by height (a leaf: 0; an interior node: 1 + its higher child)
+    std::vector<uint32_t> level_off;  // order[level_off[h] .. level_off[h + 1]) are the nodes of height h; sizes never grow with h
 };
 
 // Validates the mesh (xyz[n_vertices][3], indices[n_triangles][3]), drops its zero-area triangles (fp32 c = cross(e1, e2) with
@@ -31,3 +36,20 @@ struct FwBvh {
 // triangles, more than 2^28 triangles, an index >= n_vertices, a non-finite vertex, no triangle of non-zero area.
 int fw_bvh_build(const float *xyz, uint32_t n_vertices, const uint32_t *indices, uint32_t n_triangles, FwBvh *out,
                  std::string *err);
+
+// The same hierarchy over ALL triangles, for a mesh whose vertices will move (fw_ctx_create_deformable_mesh): a zero-area
+// triangle keeps its slot, its box still bounds its vertices, and its record is {v0, original index} {0} {0} -- e1 = e2 = 0 is
+// what no ray hits (fw_cast_ray: det == 0), so the walk needs no test of its own.  The pad is 1e-4 x the largest |coordinate|
+// of the vertices that triangles reference, dropped triangles included.  A mesh without zero-area triangles gets the tables
+// of fw_bvh_build, bit for bit.  Errors as there (no triangle of non-zero area included: creation still rejects it).
+int fw_bvh_build_deformable(const float *xyz, uint32_t n_vertices, const uint32_t *indices, uint32_t n_triangles, FwBvh *out,
+                            std::string *err);
+
+// What the host recomputes from new vertices of a deformable mesh: the pad by the rule above and the root's padded box
+// (referenced[v] != 0: some triangle uses vertex v).  Equal to FwBvh::pad / lo / hi of a deformable build over the same vertices.
+void fw_bvh_bounds(const float *xyz, const uint8_t *referenced, uint32_t n_vertices, float lo[3], float hi[3], float *pad);
+// The same in the ONE pass over the caller's array that fw_ctx_update_mesh_vertices makes: every vertex is checked (the index
+// of the first non-finite one is returned, dst then holds nothing of use), copied to dst (the pinned staging; may be null) and,
+// where referenced, taken into the bounds.  -1: all finite, lo / hi / pad are set.
+int64_t fw_bvh_stage_vertices(const float *xyz, const uint8_t *referenced, uint32_t n_vertices, float *dst, float lo[3], float hi[3],
+                              float *pad);

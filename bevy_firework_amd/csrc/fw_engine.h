@@ -23,7 +23,8 @@
 //                        tile table -- everything that can still be rolled back
 //   fw_engine_launch.cpp the enqueue of a planned frame (FwFrame): op tables, cohort replay, every launch, the frame's bookkeeping
 //   fw_engine_api.cpp    every other entry point of include/firework_hip.h (+ the debug hooks)
-//   fw_engine_mesh.cpp   the collider meshes: fw_ctx_create_mesh / fw_ctx_destroy_mesh / fw_ctx_set_mesh_colliders (the
+//   fw_engine_mesh.cpp   the collider meshes: fw_ctx_create_mesh / fw_ctx_create_deformable_mesh / fw_ctx_update_mesh_vertices /
+//                        fw_ctx_destroy_mesh / fw_ctx_set_mesh_colliders (the
 //                        hierarchy itself is built by fw_bvh.cpp, plain C++)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -959,9 +960,24 @@ struct fw_ctx {
         HipBuf<float4> nodes, tris;  // fw_bvh.h layout
         uint32_t n_nodes = 0, n_tris = 0;
         float center[3] = {0.0f, 0.0f, 0.0f}, radius = 0.0f;  // a sphere that contains the mesh, in its own frame
+        // a deformable mesh (fw_ctx_create_deformable_mesh) keeps what fw_ctx_update_mesh_vertices needs: the refit's tables
+        // (fw_refit.h) and the device vertices; the new vertices are staged in pinned memory, double-buffered, and travel as one
+        // copy in the context's stream like an instance set.  All of it is allocated at creation: an update allocates nothing.
+        bool deformable = false;
+        uint32_t n_vertices = 0;
+        HipBuf<FwSlotIdx> slots;
+        HipBuf<uint32_t> order, level_off;
+        HipBuf<float> xyz;
+        HipBuf<float> h_xyz[2];
+        HipEvent ev_xyz[2];
+        bool xyz_pending[2] = {false, false};
+        uint64_t xyz_seq = 0;
+        std::vector<uint32_t> h_level_off;  // the host's copy: which levels get a launch of their own (fw_launch_mesh_refit)
+        std::vector<uint8_t> referenced;    // per vertex: some triangle uses it (the pad and the bounding sphere go by these)
     };
     std::vector<MeshHost> meshes;
     std::vector<fw_mesh> mesh_set;  // the meshes the current instance set places (fw_ctx_destroy_mesh refuses them)
+    std::vector<fw_mesh_collider> mesh_insts;  // ... and the set itself as the caller gave it: restaged when a placed mesh deforms
     HipBuf<FwMeshInst> d_mesh_inst;
     HipBuf<FwMeshInst> h_mesh_inst[2];
     HipEvent ev_mesh[2];

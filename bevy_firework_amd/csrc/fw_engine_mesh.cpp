@@ -1,6 +1,7 @@
-// fw_engine_mesh.cpp -- the collider meshes of a context: fw_ctx_create_mesh / fw_ctx_destroy_mesh / fw_ctx_set_mesh_colliders
+// fw_engine_mesh.cpp -- the collider meshes of a context: fw_ctx_create_mesh / fw_ctx_create_deformable_mesh /
+// fw_ctx_update_mesh_vertices / fw_ctx_destroy_mesh / fw_ctx_set_mesh_colliders
 // (include/firework_hip.h: fw_mesh_collider has the ray-cast semantics; fw_collide.h walks what is uploaded here; fw_bvh.cpp
-// builds the hierarchy)
+// builds the hierarchy; fw_k_refit.hip redoes its boxes and triangles from new vertices)
 #include "fw_bvh.h"
 #include "fw_engine.h"
 
@@ -16,32 +17,52 @@ void quat_mul_vec3_d(const float *q, const double *v, double *out) {
     out[0] = v[0] * k0 + bx * k1 + cx * k2, out[1] = v[1] * k0 + by * k1 + cy * k2, out[2] = v[2] * k0 + bz * k1 + cz * k2;
 }
 
-}  // namespace
+// the sphere around the root's (padded) box, in the mesh's own frame
+void bounding_sphere(const float *lo, const float *hi, float *center, float *radius) {
+    double r2 = 0.0;
+    for (int k = 0; k < 3; k++) {
+        center[k] = (float)(((double)lo[k] + hi[k]) * 0.5);
+        const double h = std::max((double)hi[k] - center[k], (double)center[k] - lo[k]);
+        r2 += h * h;
+    }
+    *radius = (float)(std::sqrt(r2) * 1.0001);
+}
 
-extern "C" {
-
-fw_status fw_ctx_create_mesh(fw_ctx *ctx, const float *xyz, uint32_t n_vertices, const uint32_t *indices, uint32_t n_triangles,
-                             fw_mesh *out) {
+fw_status create_mesh(fw_ctx *ctx, const char *who, bool deformable, const float *xyz, uint32_t n_vertices, const uint32_t *indices,
+                      uint32_t n_triangles, fw_mesh *out) {
     if (out) *out = -1;
-    if (!ctx || !out) return fail(ctx, FW_EINVAL, "fw_ctx_create_mesh: bad arguments");
+    if (!ctx || !out) return fail(ctx, FW_EINVAL, std::string(who) + ": bad arguments");
     hipSetDevice(ctx->device);
     try {
         FwBvh bvh;
         std::string why;
-        if (fw_bvh_build(xyz, n_vertices, indices, n_triangles, &bvh, &why)) return fail(ctx, FW_EINVAL, "fw_ctx_create_mesh: " + why);
-        fw_ctx::MeshHost m;
+        if (deformable ? fw_bvh_build_deformable(xyz, n_vertices, indices, n_triangles, &bvh, &why)
+                       : fw_bvh_build(xyz, n_vertices, indices, n_triangles, &bvh, &why))
+            return fail(ctx, FW_EINVAL, std::string(who) + ": " + why);
+        fw_ctx::MeshHost m;  // (a failure below releases what it holds so far: the context stays as it was)
         fw_status st;
         if ((st = alloc_buf(ctx, m.nodes, (size_t)bvh.n_nodes * 2)) || (st = alloc_buf(ctx, m.tris, (size_t)bvh.n_tris * 3))) return st;
         FW_HIP(ctx, hipMemcpy(m.nodes, bvh.nodes.data(), bvh.nodes.size() * sizeof(float), hipMemcpyHostToDevice));
         FW_HIP(ctx, hipMemcpy(m.tris, bvh.tris.data(), bvh.tris.size() * sizeof(float), hipMemcpyHostToDevice));
         m.n_nodes = bvh.n_nodes, m.n_tris = bvh.n_tris;
-        double r2 = 0.0;
-        for (int k = 0; k < 3; k++) {
-            m.center[k] = (float)(((double)bvh.lo[k] + bvh.hi[k]) * 0.5);
-            const double h = std::max((double)bvh.hi[k] - m.center[k], (double)m.center[k] - bvh.lo[k]);
-            r2 += h * h;
+        bounding_sphere(bvh.lo, bvh.hi, m.center, &m.radius);
+        if (deformable) {
+            const size_t nf = (size_t)n_vertices * 3;
+            if ((st = alloc_buf(ctx, m.slots, (size_t)bvh.n_tris)) || (st = alloc_buf(ctx, m.order, (size_t)bvh.n_nodes)) ||
+                (st = alloc_buf(ctx, m.level_off, bvh.level_off.size())) || (st = alloc_buf(ctx, m.xyz, nf)) ||
+                (st = alloc_buf(ctx, m.h_xyz[0], nf, Mem::pinned)) || (st = alloc_buf(ctx, m.h_xyz[1], nf, Mem::pinned)))
+                return st;
+            FW_HIP(ctx, m.ev_xyz[0].create());
+            FW_HIP(ctx, m.ev_xyz[1].create());
+            FW_HIP(ctx, hipMemcpy(m.slots, bvh.slots.data(), bvh.slots.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+            FW_HIP(ctx, hipMemcpy(m.order, bvh.order.data(), bvh.order.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+            FW_HIP(ctx, hipMemcpy(m.level_off, bvh.level_off.data(), bvh.level_off.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+            FW_HIP(ctx, hipMemcpy(m.xyz, xyz, nf * sizeof(float), hipMemcpyHostToDevice));
+            m.h_level_off = std::move(bvh.level_off);
+            m.referenced.assign(n_vertices, 0);
+            for (size_t i = 0; i < (size_t)n_triangles * 3; i++) m.referenced[indices[i]] = 1;
+            m.deformable = true, m.n_vertices = n_vertices;
         }
-        m.radius = (float)(std::sqrt(r2) * 1.0001);
         m.alive = true;
         fw_mesh h = -1;
         for (size_t i = 0; i < ctx->meshes.size() && h < 0; i++)
@@ -54,45 +75,29 @@ fw_status fw_ctx_create_mesh(fw_ctx *ctx, const float *xyz, uint32_t n_vertices,
         *out = h;
         return FW_OK;
     } catch (const std::bad_alloc &) {
-        return fail(ctx, FW_ENOMEM, "fw_ctx_create_mesh: out of host memory");
+        return fail(ctx, FW_ENOMEM, std::string(who) + ": out of host memory");
     }
 }
 
-fw_status fw_ctx_destroy_mesh(fw_ctx *ctx, fw_mesh mesh) {
-    if (!ctx) return FW_EINVAL;
-    if (!mesh_alive(ctx, mesh)) return fail(ctx, FW_EINVAL, "fw_ctx_destroy_mesh: unknown mesh handle");
-    if (std::find(ctx->mesh_set.begin(), ctx->mesh_set.end(), mesh) != ctx->mesh_set.end())
-        return fail(ctx, FW_EINVAL, "fw_ctx_destroy_mesh: the current instance set places this mesh");
-    hipSetDevice(ctx->device);
-    fw_status st = sync(ctx);  // (frames in flight may still walk it under an older instance set)
-    if (st) return st;
-    ctx->meshes[mesh] = fw_ctx::MeshHost{};
-    return FW_OK;
-}
-
-fw_status fw_ctx_set_mesh_colliders(fw_ctx *ctx, const fw_mesh_collider *inst, uint32_t n) {
-    if (!ctx || (n && !inst)) return fail(ctx, FW_EINVAL, "bad mesh instance set");
-    for (uint32_t i = 0; i < n; i++)
-        if (!mesh_alive(ctx, inst[i].mesh)) return fail(ctx, FW_EINVAL, "fw_ctx_set_mesh_colliders: unknown mesh handle");
-    hipSetDevice(ctx->device);
-    // staged in pinned memory and copied by the stream itself, like fw_ctx_set_colliders: moving instances every frame does not
-    // stall the frames in flight
-    const int slot = (int)(ctx->mesh_seq++ & 1u);
+// The instance set into the staging slot of its turn and, as one copy, into the context's stream: pinned memory, double-buffered,
+// like fw_ctx_set_colliders -- moving instances every frame does not stall the frames in flight.  The device table must hold n.
+// the staging slot of the next set, free and large enough for n instances (the one wait: the copy before the previous one)
+fw_status reserve_staging(fw_ctx *ctx, uint32_t n) {
+    const int slot = (int)(ctx->mesh_seq & 1u);
     if (ctx->mesh_pending[slot]) {
         FW_HIP(ctx, hipEventSynchronize(ctx->ev_mesh[slot]));
         ctx->mesh_pending[slot] = false;
     }
     if (!ctx->ev_mesh[slot]) FW_HIP(ctx, ctx->ev_mesh[slot].create());
-    const size_t ncap = std::max<size_t>(16, (size_t)n * 2);
-    fw_status st;
-    if (n > ctx->h_mesh_inst[slot].cap() && (st = alloc_buf(ctx, ctx->h_mesh_inst[slot], ncap, Mem::pinned))) return st;
-    if (n > ctx->d_mesh_inst.cap()) {  // a larger set than ever before: the one case that waits (kernels in flight read the old table)
-        HipBuf<FwMeshInst> nb;         // (made before the old table goes: a failure keeps the previous set)
-        if ((st = alloc_buf(ctx, nb, ncap)) || (st = sync(ctx))) return st;
-        ctx->d_mesh_inst = std::move(nb);
-        ctx->g.mesh_inst = ctx->d_mesh_inst;
-    }
-    std::vector<fw_mesh> set(n);
+    if (n > ctx->h_mesh_inst[slot].cap()) return alloc_buf(ctx, ctx->h_mesh_inst[slot], std::max<size_t>(16, (size_t)n * 2), Mem::pinned);
+    return FW_OK;
+}
+
+fw_status stage_instances(fw_ctx *ctx, const fw_mesh_collider *inst, uint32_t n) {
+    const int slot = (int)(ctx->mesh_seq & 1u);
+    fw_status st = reserve_staging(ctx, n);
+    if (st) return st;
+    ctx->mesh_seq++;
     for (uint32_t i = 0; i < n; i++) {
         const fw_mesh_collider &c = inst[i];
         const fw_ctx::MeshHost &m = ctx->meshes[c.mesh];
@@ -116,14 +121,111 @@ fw_status fw_ctx_set_mesh_colliders(fw_ctx *ctx, const fw_mesh_collider *inst, u
         d.position[3] = (float)(m.radius / s * 1.001 + 1e-5 * big);
         if (!(s > 0.0) || !std::isfinite(d.position[3]) || !std::isfinite(d.center[0] + d.center[1] + d.center[2]))
             d.position[3] = INFINITY, memcpy(d.center, c.position, sizeof c.position);  // (never skipped)
-        set[i] = c.mesh;
     }
     if (n) {
         FW_HIP(ctx, hipMemcpyAsync(ctx->d_mesh_inst, ctx->h_mesh_inst[slot], n * sizeof(FwMeshInst), hipMemcpyHostToDevice, ctx->stream));
         FW_HIP(ctx, hipEventRecord(ctx->ev_mesh[slot], ctx->stream));
         ctx->mesh_pending[slot] = true;
     }
-    ctx->mesh_set.swap(set);
+    return FW_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+fw_status fw_ctx_create_mesh(fw_ctx *ctx, const float *xyz, uint32_t n_vertices, const uint32_t *indices, uint32_t n_triangles,
+                             fw_mesh *out) {
+    return create_mesh(ctx, "fw_ctx_create_mesh", false, xyz, n_vertices, indices, n_triangles, out);
+}
+
+fw_status fw_ctx_create_deformable_mesh(fw_ctx *ctx, const float *xyz, uint32_t n_vertices, const uint32_t *indices,
+                                        uint32_t n_triangles, fw_mesh *out) {
+    return create_mesh(ctx, "fw_ctx_create_deformable_mesh", true, xyz, n_vertices, indices, n_triangles, out);
+}
+
+fw_status fw_ctx_update_mesh_vertices(fw_ctx *ctx, fw_mesh mesh, const float *xyz, uint32_t n_vertices) {
+    if (!ctx) return FW_EINVAL;
+    if (!mesh_alive(ctx, mesh)) return fail(ctx, FW_EINVAL, "fw_ctx_update_mesh_vertices: unknown mesh handle");
+    fw_ctx::MeshHost &m = ctx->meshes[mesh];
+    if (!m.deformable) return fail(ctx, FW_EINVAL, "fw_ctx_update_mesh_vertices: the mesh was not created as deformable");
+    if (!xyz || n_vertices != m.n_vertices) return fail(ctx, FW_EINVAL, "fw_ctx_update_mesh_vertices: the vertex count differs from the creation's");
+    const size_t nf = (size_t)n_vertices * 3;
+    hipSetDevice(ctx->device);
+    const bool placed = std::find(ctx->mesh_set.begin(), ctx->mesh_set.end(), mesh) != ctx->mesh_set.end();
+    fw_status st;  // (the one allocation an update can need comes first: a failure leaves the mesh as it was)
+    if (placed && (st = reserve_staging(ctx, (uint32_t)ctx->mesh_insts.size()))) return st;
+    // the staging slot of this call's turn: the one wait of the call, and only when the copy before the previous one is still in
+    // flight.  Then ONE pass over the caller's array: finite check, copy into the slot, bounds and pad (a refused call leaves the
+    // slot unused: its turn comes again)
+    const int slot = (int)(m.xyz_seq & 1u);
+    if (m.xyz_pending[slot]) {
+        FW_HIP(ctx, hipEventSynchronize(m.ev_xyz[slot]));
+        m.xyz_pending[slot] = false;
+    }
+    float lo[3], hi[3], pad;
+    const int64_t bad = fw_bvh_stage_vertices(xyz, m.referenced.data(), n_vertices, m.h_xyz[slot], lo, hi, &pad);
+    if (bad >= 0) return fail(ctx, FW_EINVAL, "fw_ctx_update_mesh_vertices: non-finite vertex " + std::to_string(bad));
+    m.xyz_seq++;
+    FW_HIP(ctx, hipMemcpyAsync(m.xyz, m.h_xyz[slot], nf * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    FW_HIP(ctx, hipEventRecord(m.ev_xyz[slot], ctx->stream));
+    m.xyz_pending[slot] = true;
+    // The refit behind the copy, IN PLACE: nodes and triangles are rewritten where the frames walk them.  That is safe because
+    // every launch that casts rays runs on this same stream (a colliding ring or small type never goes to the side stream:
+    // launch_fifo, fw_ctx::small_last_side), so the frames enqueued before this call have read the old shape before the refit
+    // starts, and the frames after it start when it is done.
+    FwRefit R{};
+    R.nodes = reinterpret_cast<FwR4 *>(m.nodes.get()), R.tris = reinterpret_cast<FwR4 *>(m.tris.get());
+    R.slots = m.slots, R.xyz = m.xyz, R.order = m.order, R.pad = pad;
+    FW_HIP(ctx, fw_launch_mesh_refit(ctx->stream, R, m.level_off, m.h_level_off.data(), (uint32_t)m.h_level_off.size() - 1));
+    // the instances of the current set that place this mesh carry its bounding sphere: restaged, in the same stream order
+    // (the host's sphere changes for good only once they are on their way)
+    const float center0[3] = {m.center[0], m.center[1], m.center[2]}, radius0 = m.radius;
+    bounding_sphere(lo, hi, m.center, &m.radius);
+    if (placed && (st = stage_instances(ctx, ctx->mesh_insts.data(), (uint32_t)ctx->mesh_insts.size()))) {
+        memcpy(m.center, center0, sizeof center0), m.radius = radius0;
+        return st;
+    }
+    ctx->fc_ok = false, ctx->boxes_epoch = 0;
+    return FW_OK;
+}
+
+fw_status fw_ctx_destroy_mesh(fw_ctx *ctx, fw_mesh mesh) {
+    if (!ctx) return FW_EINVAL;
+    if (!mesh_alive(ctx, mesh)) return fail(ctx, FW_EINVAL, "fw_ctx_destroy_mesh: unknown mesh handle");
+    if (std::find(ctx->mesh_set.begin(), ctx->mesh_set.end(), mesh) != ctx->mesh_set.end())
+        return fail(ctx, FW_EINVAL, "fw_ctx_destroy_mesh: the current instance set places this mesh");
+    hipSetDevice(ctx->device);
+    fw_status st = sync(ctx);  // (frames in flight may still walk it under an older instance set)
+    if (st) return st;
+    ctx->meshes[mesh] = fw_ctx::MeshHost{};
+    return FW_OK;
+}
+
+fw_status fw_ctx_set_mesh_colliders(fw_ctx *ctx, const fw_mesh_collider *inst, uint32_t n) {
+    if (!ctx || (n && !inst)) return fail(ctx, FW_EINVAL, "bad mesh instance set");
+    for (uint32_t i = 0; i < n; i++)
+        if (!mesh_alive(ctx, inst[i].mesh)) return fail(ctx, FW_EINVAL, "fw_ctx_set_mesh_colliders: unknown mesh handle");
+    hipSetDevice(ctx->device);
+    const size_t ncap = std::max<size_t>(16, (size_t)n * 2);
+    fw_status st;
+    try {
+        std::vector<fw_mesh> set(n);
+        std::vector<fw_mesh_collider> insts(inst, inst + n);
+        for (uint32_t i = 0; i < n; i++) set[i] = inst[i].mesh;
+        if ((st = reserve_staging(ctx, n))) return st;
+        if (n > ctx->d_mesh_inst.cap()) {  // a larger set than ever before: the one case that waits (kernels in flight read the old table)
+            HipBuf<FwMeshInst> nb;         // (made before the old table goes: a failure keeps the previous set)
+            if ((st = alloc_buf(ctx, nb, ncap)) || (st = sync(ctx))) return st;
+            ctx->d_mesh_inst = std::move(nb);
+            ctx->g.mesh_inst = ctx->d_mesh_inst;
+        }
+        if ((st = stage_instances(ctx, inst, n))) return st;
+        ctx->mesh_set.swap(set);
+        ctx->mesh_insts.swap(insts);
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, FW_ENOMEM, "fw_ctx_set_mesh_colliders: out of host memory");
+    }
     ctx->g.n_mesh_inst = n;
     ctx->fc_ok = false, ctx->boxes_epoch = 0;
     return FW_OK;

@@ -5,6 +5,7 @@
 
 #include "fw_device.h"
 #include "fw_collide.h"
+#include "fw_refit.h"
 
 // The product build (the default `make`) carries no experiment surface: the FW_DEBUG profiling modes (kernel ablations, in-kernel
 // timestamps) and the A/B switches of measured-and-rejected variants exist only in the `make ab` build (-DFW_AB,
@@ -395,3 +396,9 @@ hipError_t fw_launch_aabb_from_tiles(hipStream_t s, const FwGlobals &g, const ui
                                      uint32_t parity, uint32_t epoch, const uint32_t *d_seg_tile_first, float *h_out8);
 hipError_t fw_launch_total(hipStream_t s, const uint32_t *counts, uint32_t n_seg, unsigned long long *d_out);
 hipError_t fw_launch_copy_probe(hipStream_t s, const void *src, void *dst, size_t bytes);
+// Refit of a deformable mesh (fw_k_refit.hip): the levels of R.order, lowest first -- one launch per level of more than
+// FW_REFIT_TAIL nodes, then one launch of one workgroup for all the others.  level_off: n_levels + 1 words, on the device
+// and (the same) on the host.  No workgroup waits for another; everything goes to stream s.
+#define FW_REFIT_TAIL 4096u
+hipError_t fw_launch_mesh_refit(hipStream_t s, const FwRefit &R, const uint32_t *d_level_off, const uint32_t *h_level_off,
+                                uint32_t n_levels);

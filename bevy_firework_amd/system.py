@@ -231,6 +231,23 @@ class ParticleSystem:
                                                  idx.ctypes.data_as(C.c_void_p), len(idx), C.byref(h)))
         return int(h.value)
 
+    def create_deformable_mesh(self, vertices, indices) -> int:
+        """create_mesh for a mesh whose vertices will move: it takes new positions through update_mesh_vertices.  Every
+        triangle keeps its place; zero-area ones are hit by nothing until an update opens them up."""
+        xyz = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+        idx = np.ascontiguousarray(indices, dtype=np.uint32).reshape(-1, 3)
+        h = C.c_int32(-1)
+        self._check(self._lib.fw_ctx_create_deformable_mesh(self._ctx, xyz.ctypes.data_as(C.c_void_p), len(xyz),
+                                                            idx.ctypes.data_as(C.c_void_p), len(idx), C.byref(h)))
+        return int(h.value)
+
+    def update_mesh_vertices(self, mesh: int, vertices) -> None:
+        """Replaces the vertex positions of a deformable mesh ([n, 3] float32, n as at creation): later frames cast against the
+        mesh as if it had been created from them.  All-or-nothing, no synchronisation (the array is copied before the call
+        returns); placed instances follow."""
+        xyz = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+        self._check(self._lib.fw_ctx_update_mesh_vertices(self._ctx, int(mesh), xyz.ctypes.data_as(C.c_void_p), len(xyz)))
+
     def destroy_mesh(self, mesh: int) -> None:
         """Frees a mesh the current instance set does not place (waits for the frames in flight)."""
         self._check(self._lib.fw_ctx_destroy_mesh(self._ctx, int(mesh)))

@@ -1,7 +1,8 @@
 // mirror_check.cpp -- a scenario that touches most of the C++ host mirror (include/firework.hpp): three particle types,
 // Global / OnDemand / Nested entries, every curve kind, modifier, transforms, parent velocity, destroyed-particle
 // handler, collisions against an analytic world, fused AABB tracking; with the argument `mesh` also against triangle meshes (one
-// mesh placed twice, the set replaced and a mesh destroyed half way).  Prints, every tenth frame, the live counts and an
+// mesh placed twice, the set replaced and a mesh destroyed half way), and with `deform` against the same meshes created deformable,
+// their vertices moved every fifth frame (create_deformable_mesh / update_mesh_vertices).  Prints, every tenth frame, the live counts and an
 // FNV-1a digest of every particle record; tests/test_cpp_host.py runs the same scenario through the Python mirror and
 // expects the same lines: both mirrors marshal the reference's settings into the C ABI the same way.
 //
@@ -21,16 +22,19 @@ static uint64_t fnv(const void *p, size_t n, uint64_t h = 1469598103934665603ull
 
 int main(int argc, char **argv) {
     // `mirror_check mesh`: the same scenario with triangle meshes in the collider world (create, place twice, replace, destroy)
-    const bool with_meshes = argc > 1 && std::strcmp(argv[1], "mesh") == 0;
+    // `mirror_check deform`: ... with both meshes deformable: the ramp's far edge rises every fifth frame, then the sheet's apex
+    const bool deform = argc > 1 && std::strcmp(argv[1], "deform") == 0;
+    const bool with_meshes = deform || (argc > 1 && std::strcmp(argv[1], "mesh") == 0);
     try {
         ParticleSystemPlugin app(0, /*seed*/ 0x00C0FFEE);
         app.track_aabbs(true);
         app.set_colliders({Collider::Plane({0.0f, -1.0f, 0.0f}, {0.0f, 1.0f, 0.0f}), Collider::Sphere({1.0f, 0.5f, 0.0f}, 0.75f, 2u),
                            Collider::Box({-2.0f, 0.0f, 0.0f}, {0.5f, 1.0f, 0.5f}, Quat{0.0f, 0.38268343f, 0.0f, 0.92387953f})});
         // a ramp of two triangles under the pebbles: as it is on layer 1, and turned about Y a little higher on layer 2
-        fw_mesh ramp = -1;
+        fw_mesh ramp = -1, sheet = -1;
+        if (deform) ramp = app.create_deformable_mesh({-2.0f, -0.25f, -2.0f, 2.0f, -0.25f, -2.0f, 2.0f, 0.25f, 2.0f, -2.0f, 0.25f, 2.0f}, {0, 2, 1, 0, 3, 2});
         if (with_meshes) {
-            ramp = app.create_mesh({-2.0f, -0.25f, -2.0f, 2.0f, -0.25f, -2.0f, 2.0f, 0.25f, 2.0f, -2.0f, 0.25f, 2.0f}, {0, 2, 1, 0, 3, 2});
+            if (!deform) ramp = app.create_mesh({-2.0f, -0.25f, -2.0f, 2.0f, -0.25f, -2.0f, 2.0f, 0.25f, 2.0f, -2.0f, 0.25f, 2.0f}, {0, 2, 1, 0, 3, 2});
             app.set_mesh_colliders({MeshCollider{ramp, {0.0f, -0.25f, 0.0f}, {}, 1u},
                                     MeshCollider{ramp, {0.5f, 0.25f, 0.0f}, Quat{0.0f, 0.38268343f, 0.0f, 0.92387953f}, 2u}});
         }
@@ -97,8 +101,15 @@ int main(int argc, char **argv) {
         const float dt = 1.0f / 60.0f;
         for (int fr = 0; fr < 60; fr++) {
             if (fr == 0 || fr == 7 || fr == 8 || fr == 31) d->queue_particles(500 + 10 * fr);
+            if (deform && fr % 5 == 0 && fr < 30) {  // the ramp's far edge at 0.25 + fr / 40 (exact in fp32), in both places it is placed
+                const float y = 0.25f + 0.125f * (float)(fr / 5);
+                app.update_mesh_vertices(ramp, {-2.0f, -0.25f, -2.0f, 2.0f, -0.25f, -2.0f, 2.0f, y, 2.0f, -2.0f, y, 2.0f});
+            }
+            if (deform && fr % 5 == 0 && fr > 30)  // the sheet's apex rises
+                app.update_mesh_vertices(sheet, {-3.0f, 0.0f, -3.0f, 3.0f, 0.0f, -3.0f, 0.0f, 0.5f + 0.25f * (float)(fr / 5 - 6), 3.0f});
             if (with_meshes && fr == 30) {  // another mesh takes the ramp's place (layers 1 | 2, tilted about Z); the ramp is destroyed
-                const fw_mesh sheet = app.create_mesh({-3.0f, 0.0f, -3.0f, 3.0f, 0.0f, -3.0f, 0.0f, 0.5f, 3.0f}, {0, 2, 1});
+                sheet = deform ? app.create_deformable_mesh({-3.0f, 0.0f, -3.0f, 3.0f, 0.0f, -3.0f, 0.0f, 0.5f, 3.0f}, {0, 2, 1})
+                               : app.create_mesh({-3.0f, 0.0f, -3.0f, 3.0f, 0.0f, -3.0f, 0.0f, 0.5f, 3.0f}, {0, 2, 1});
                 app.set_mesh_colliders({MeshCollider{sheet, {1.0f, 1.5f, 3.0f}, Quat{0.0f, 0.0f, 0.19509032f, 0.98078528f}, 3u}});
                 app.destroy_mesh(ramp);
             }

@@ -377,6 +377,16 @@ class ParticleSystemPlugin {
         check(fw_ctx_create_mesh(ctx_, xyz.data(), (uint32_t)(xyz.size() / 3), indices.data(), (uint32_t)(indices.size() / 3), &m));
         return m;
     }
+    // ... one whose vertices will move (fw_ctx_create_deformable_mesh), and its new vertex positions: as many as at creation,
+    // no synchronisation, placed instances follow (fw_ctx_update_mesh_vertices)
+    fw_mesh create_deformable_mesh(const std::vector<float> &xyz, const std::vector<uint32_t> &indices) {
+        fw_mesh m = -1;
+        check(fw_ctx_create_deformable_mesh(ctx_, xyz.data(), (uint32_t)(xyz.size() / 3), indices.data(), (uint32_t)(indices.size() / 3), &m));
+        return m;
+    }
+    void update_mesh_vertices(fw_mesh m, const std::vector<float> &xyz) {
+        check(fw_ctx_update_mesh_vertices(ctx_, m, xyz.data(), (uint32_t)(xyz.size() / 3)));
+    }
     void destroy_mesh(fw_mesh m) { check(fw_ctx_destroy_mesh(ctx_, m)); }
     void set_mesh_colliders(const std::vector<MeshCollider> &ms) {
         std::vector<fw_mesh_collider> v(ms.size());

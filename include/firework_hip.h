@@ -151,7 +151,25 @@ typedef struct fw_collider {
  *   TIES      the nearest hit wins; at equal distance analytic colliders come before mesh instances, lower instance indices
  *             before higher ones, and within an instance the lower ORIGINAL triangle index (position in `indices`) wins.
  *   FILTER    an instance takes part when (filter_mask & layers) != 0, as a collider does.
- * Triangles whose c has dot(c, c) == 0 (or not finite) -- zero area -- are dropped at creation; no other triangle is. */
+ * Triangles whose c has dot(c, c) == 0 (or not finite) -- zero area -- are dropped at creation; no other triangle is.
+ *
+ * DEFORMABLE MESHES.  A mesh made by fw_ctx_create_deformable_mesh takes new vertex positions through
+ * fw_ctx_update_mesh_vertices: same topology, same hierarchy shape, its boxes and triangles recomputed on the device.
+ *   AS IF CREATED ANEW   after an update with xyz', every ray cast of every later fw_step gives, bit for bit -- hit or miss,
+ *             distance, normal, ties -- what a mesh from fw_ctx_create_mesh(xyz', indices) would give in the same places.  The
+ *             zero-area rule is evaluated again per update with the same fp32 operations: a triangle that collapses stops
+ *             being hit, one that was degenerate (at creation too) and opens up starts being hit, and original triangle
+ *             indices never change.
+ *   ORDER     the call does not synchronise: the vertices are copied to pinned staging (double-buffered; the call waits only for
+ *             the copy before the previous one), travel as one copy in the context's stream, and the refit runs behind it in
+ *             the same stream -- frames enqueued before the call see the old shape, frames after it the new one.  Instances
+ *             of the current set that place the mesh follow (their bounding spheres are restaged in the same order).
+ *   ERRORS    all-or-nothing: FW_EINVAL and nothing changes for an unknown handle, a mesh not created as deformable, an
+ *             n_vertices other than the creation's, a non-finite vertex.  Vertices that leave NO triangle of non-zero area are
+ *             accepted: the mesh is hit by nothing until the next update (creation still rejects such a mesh).
+ *   QUALITY   a refit keeps the tree the creation vertices gave: after large deformations boxes overlap more and casts get
+ *             slower, never wrong.  A caller whose mesh has changed beyond recognition creates a new one.
+ * fw_ctx_destroy_mesh and fw_ctx_set_mesh_colliders treat a deformable mesh like any other. */
 typedef int32_t fw_mesh; /* handle >= 0, per context */
 typedef struct fw_mesh_collider { /* one placed instance of a mesh */
     fw_mesh mesh;
@@ -236,6 +254,13 @@ fw_status fw_ctx_set_colliders(fw_ctx *ctx, const fw_collider *colliders, uint32
  * its bounding-volume hierarchy on the host and uploads it once (synchronises).  xyz[n_vertices][3], indices[n_triangles][3]. */
 fw_status fw_ctx_create_mesh(fw_ctx *ctx, const float *xyz, uint32_t n_vertices, const uint32_t *indices, uint32_t n_triangles,
                              fw_mesh *out);
+/* like fw_ctx_create_mesh, but the mesh keeps what fw_ctx_update_mesh_vertices needs (its vertices and per-triangle vertex
+ * indices on the device, pinned staging for new vertices); every triangle keeps a place in the hierarchy, zero-area ones marked */
+fw_status fw_ctx_create_deformable_mesh(fw_ctx *ctx, const float *xyz, uint32_t n_vertices, const uint32_t *indices,
+                                        uint32_t n_triangles, fw_mesh *out);
+/* replaces the vertex positions of a deformable mesh (DEFORMABLE MESHES above); xyz[n_vertices][3] in host memory, n_vertices
+ * as at creation.  Does not synchronise. */
+fw_status fw_ctx_update_mesh_vertices(fw_ctx *ctx, fw_mesh mesh, const float *xyz, uint32_t n_vertices);
 /* FW_EINVAL while the current instance set places the mesh; otherwise waits for the frames in flight and frees it */
 fw_status fw_ctx_destroy_mesh(fw_ctx *ctx, fw_mesh mesh);
 /* replaces the context's mesh instances (copied; n = 0 clears them); all-or-nothing: an unknown mesh handle -> FW_EINVAL and

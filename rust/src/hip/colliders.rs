@@ -66,6 +66,8 @@ pub fn hip_sync_colliders(
         // a mesh-shaped collider: its triangles with the collider's scale baked in (instances carry no scale), cached
         let scale = collider.scale();
         let key = [scale.x.to_bits(), scale.y.to_bits(), scale.z.to_bits()];
+        // (a trimesh whose vertices change every frame -- `collider.is_changed()` with the same topology -- would be forwarded to
+        // `fw_ctx_update_mesh_vertices` of a mesh made by `fw_ctx_create_deformable_mesh` here instead of being created anew)
         let cached = meshes.0.get(&entity).copied().filter(|(k, _)| *k == key && !collider.is_changed());
         let mesh = match cached {
             Some((_, m)) => Some(m),

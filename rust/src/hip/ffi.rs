@@ -65,6 +65,8 @@ extern "C" {
     pub fn fw_ctx_synchronize(ctx: *mut fw_ctx) -> c_int;
     pub fn fw_ctx_set_colliders(ctx: *mut fw_ctx, colliders: *const fw_collider, n: u32) -> c_int;
     pub fn fw_ctx_create_mesh(ctx: *mut fw_ctx, xyz: *const f32, n_vertices: u32, indices: *const u32, n_triangles: u32, out: *mut fw_mesh) -> c_int;
+    pub fn fw_ctx_create_deformable_mesh(ctx: *mut fw_ctx, xyz: *const f32, n_vertices: u32, indices: *const u32, n_triangles: u32, out: *mut fw_mesh) -> c_int;
+    pub fn fw_ctx_update_mesh_vertices(ctx: *mut fw_ctx, mesh: fw_mesh, xyz: *const f32, n_vertices: u32) -> c_int;
     pub fn fw_ctx_destroy_mesh(ctx: *mut fw_ctx, mesh: fw_mesh) -> c_int;
     pub fn fw_ctx_set_mesh_colliders(ctx: *mut fw_ctx, instances: *const fw_mesh_collider, n: u32) -> c_int;
     pub fn fw_spawner_create(ctx: *mut fw_ctx, desc: *const fw_spawner_desc, out: *mut fw_spawner) -> c_int;

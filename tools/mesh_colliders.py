@@ -9,6 +9,11 @@
                                                            same extent, at 157k and 1.26M particles
   python tools/mesh_colliders.py build                     fw_ctx_create_mesh time (host build + upload) and device bytes for
                                                            131k and 1M triangles
+  python tools/mesh_colliders.py deform                    a terrain of 2 048 and of 131 072 triangles whose heights change EVERY frame:
+                                                           fw_ctx_update_mesh_vertices + fw_step, pipelined (deformN), against the only way
+                                                           before deformable meshes, destroy + create + set per frame (rebuildN: the set is
+                                                           emptied first, a placed mesh cannot be destroyed); and the
+                                                           cast cost over a refitted tree against a fresh build of the same vertices
   python tools/mesh_colliders.py one WORLD RATE [FRAMES]   one measurement (what the modes above run; also the rocprofv3 target)
 
 Frame time: 150 warm-up frames (the 2 s lifetime fills), then the best of 3 windows of 300 frames, each ending in a
@@ -34,11 +39,11 @@ def _box_mesh(h):
     return v, np.array([t for a, b, c, e in quads for t in ((a, b, c), (a, c, e))], dtype=np.uint32)
 
 
-def _terrain(cells, extent=4.0):
+def _terrain(cells, extent=4.0, phase=0.0, amp=0.15):
     """cells x cells quads (2 triangles each) over [-extent, extent]^2, a gentle height field around y = 0"""
     xs = np.linspace(-extent, extent, cells + 1)
     X, Z = np.meshgrid(xs, xs, indexing="ij")
-    Y = 0.15 * np.sin(1.7 * X) * np.cos(1.3 * Z)
+    Y = amp * np.sin(1.7 * X + phase) * np.cos(1.3 * Z - 0.5 * phase)
     v = np.stack([X, Y, Z], -1).reshape(-1, 3).astype(f32)
     i = np.arange((cells + 1) ** 2).reshape(cells + 1, cells + 1)
     a, b, c, e = i[:-1, :-1].ravel(), i[1:, :-1].ravel(), i[1:, 1:].ravel(), i[:-1, 1:].ravel()
@@ -73,10 +78,49 @@ def one(world, rate, frames=300):
         info["triangles"] = len(t)
         ps.set_mesh_colliders([S.MeshCollider(m)])
         ps.set_colliders(colliders[1:])
+    elif world.startswith(("deform", "rebuild", "refitted", "fresh")):
+        # a terrain that moves: deformN updates a deformable mesh every frame, rebuildN destroys and creates a static one;
+        # refittedN:A / freshN:A cast (no per-frame change) over a tree refitted to phase A against one built there
+        kind = next(k for k in ("deform", "rebuild", "refitted", "fresh") if world.startswith(k))
+        spec = world[len(kind):].split(":")
+        cells, far = int(spec[0]), float(spec[1]) if len(spec) > 1 else 0.0
+        t = _terrain(cells)[1]
+        phases = [_terrain(cells, phase=0.05 * k)[0] for k in range(16)]
+        ps.set_colliders(colliders[1:])
+        info["triangles"] = len(t)
+        if kind == "refitted":
+            m = ps.create_deformable_mesh(phases[0], t)
+            ps.update_mesh_vertices(m, _terrain(cells, phase=far, amp=0.15 + 0.2 * far)[0])
+        elif kind == "fresh":
+            m = ps.create_mesh(_terrain(cells, phase=far, amp=0.15 + 0.2 * far)[0], t)
+        else:
+            m = ps.create_deformable_mesh(phases[0], t) if kind == "deform" else ps.create_mesh(phases[0], t)
+        ps.set_mesh_colliders([S.MeshCollider(m)])
+        state = {"m": m, "k": 0, "host": 0.0, "calls": 0}
+
+        def per_frame():
+            state["k"] += 1
+            v = phases[state["k"] % len(phases)]
+            t0 = time.perf_counter()
+            if kind == "deform":
+                ps.update_mesh_vertices(state["m"], v)
+            elif kind == "rebuild":
+                ps.set_mesh_colliders([])
+                ps.destroy_mesh(state["m"])
+                state["m"] = ps.create_mesh(v, t)
+                ps.set_mesh_colliders([S.MeshCollider(state["m"])])
+            state["host"] += time.perf_counter() - t0
+            state["calls"] += 1
     else:
         raise SystemExit(f"unknown world {world}")
+    if not world.startswith(("deform", "rebuild")):
+        per_frame = None
+    if world.startswith("rebuild"):
+        frames = min(frames, 30)  # (tens of milliseconds each at 131k triangles)
     ps.update(dt)
-    for _ in range(150):
+    for _ in range(150):  # (every world alike: the rows compare the same particle state)
+        if per_frame:
+            per_frame()
         ps.step(dt)
     ps.synchronize()
     best = math.inf
@@ -84,9 +128,13 @@ def one(world, rate, frames=300):
         ps.synchronize()
         t0 = time.perf_counter()
         for _ in range(frames):
+            if per_frame:
+                per_frame()
             ps.step(dt)
         ps.synchronize()
         best = min(best, (time.perf_counter() - t0) / frames * 1e6)
+    if per_frame:
+        info["host_us_per_call"] = round(state["host"] / state["calls"] * 1e6, 2)
     info.update(us_per_frame=round(best, 2), live=h.count(0), path=h.update_path(0)[0])
     ps.close()
     return info
@@ -128,6 +176,16 @@ def main():
                 r = _run(world, rate)
                 print(f"{world:10s} ({r['triangles']:6d} triangles) rate {rate:8.0f}: {r['us_per_frame']:.2f} us per frame "
                       f"({r['live']} live, {r['path']} path)", flush=True)
+    elif mode == "deform":
+        for rate in (80000.0, 640000.0):
+            for world in ("terrain32", "deform32", "rebuild32", "terrain256", "deform256", "rebuild256"):
+                r = _run(world, rate)
+                print(f"{world:11s} ({r['triangles']:6d} triangles) rate {rate:8.0f}: {r['us_per_frame']:.2f} us per frame, "
+                      f"{r.get('host_us_per_call', 0.0):.2f} us of host time per change ({r['live']} live, {r['path']} path)", flush=True)
+        for far in (0.3, 3.0):  # a small and a large deformation: the tree quality a refit gives up
+            for world in (f"refitted256:{far}", f"fresh256:{far}"):
+                r = _run(world, 640000.0)
+                print(f"{world:16s} rate   640000: {r['us_per_frame']:.2f} us per frame ({r['live']} live)", flush=True)
     elif mode == "build":
         import torch
 
