@@ -237,6 +237,8 @@ SYMBOLS = [
     ("fw_ctx_create_mesh", C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_int32)]),
     ("fw_ctx_create_deformable_mesh", C.c_int, [_P, _P, C.c_uint32, _P, C.c_uint32, C.POINTER(C.c_int32)]),
     ("fw_ctx_update_mesh_vertices", C.c_int, [_P, C.c_int32, _P, C.c_uint32]),
+    ("fw_ctx_update_mesh_vertices_device", C.c_int, [_P, C.c_int32, _P, C.c_uint32]),
+    ("fw_ctx_mesh_update_status", C.c_int, [_P, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]),
     ("fw_ctx_destroy_mesh", C.c_int, [_P, C.c_int32]),
     ("fw_ctx_set_mesh_colliders", C.c_int, [_P, C.POINTER(MeshCollider), C.c_uint32]),
     ("fw_spawner_create", C.c_int, [_P, C.POINTER(SpawnerDesc), C.POINTER(C.c_int32)]),

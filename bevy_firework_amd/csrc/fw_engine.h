@@ -974,7 +974,20 @@ struct fw_ctx {
         uint64_t xyz_seq = 0;
         std::vector<uint32_t> h_level_off;  // the host's copy: which levels get a launch of their own (fw_launch_mesh_refit)
         std::vector<uint8_t> referenced;    // per vertex: some triangle uses it (the pad and the bounding sphere go by these)
+        float lo[3] = {0.0f, 0.0f, 0.0f}, hi[3] = {0.0f, 0.0f, 0.0f}, pad = 0.0f;  // the root's padded box and the pad, as the host last knew them
+        // vertices from device memory (fw_ctx_update_mesh_vertices_device): what the device then has to find out itself.  Allocated
+        // and uploaded by the mesh's FIRST such call (kMeshDeviceAllocs allocations), not at creation; later calls allocate nothing.
+        HipBuf<FwMeshRecord> d_rec;        // bounds, pad, rejected flag, counts (fw_mesh_bounds.h)
+        HipBuf<FwVtxAcc> d_partials;       // one per workgroup of fw_k_mesh_bounds
+        HipBuf<uint8_t> d_referenced;      // `referenced` on the device
+        HipBuf<FwMeshReport> h_report;     // pinned: the counts as the device last stored them (fw_ctx_mesh_update_status)
+        // the bounds are the device's (d_rec) since a device-form update; center / radius / lo / hi above are stale until a
+        // host-form update takes them back.  stage_instances then stages the mesh's instances as never skipped and has
+        // fw_k_mesh_spheres fix them behind the copy.
+        bool dev_bounds = false;
+        uint64_t sphere_stamp = 0;  // stage_instances: the instance set (fw_ctx::mesh_seq) this mesh's sphere launch was last enqueued for
     };
+    static constexpr int kMeshDeviceAllocs = 4;  // d_rec, d_partials, d_referenced, h_report
     std::vector<MeshHost> meshes;
     std::vector<fw_mesh> mesh_set;  // the meshes the current instance set places (fw_ctx_destroy_mesh refuses them)
     std::vector<fw_mesh_collider> mesh_insts;  // ... and the set itself as the caller gave it: restaged when a placed mesh deforms

@@ -1,5 +1,6 @@
 // fw_engine_mesh.cpp -- the collider meshes of a context: fw_ctx_create_mesh / fw_ctx_create_deformable_mesh /
-// fw_ctx_update_mesh_vertices / fw_ctx_destroy_mesh / fw_ctx_set_mesh_colliders
+// fw_ctx_update_mesh_vertices / fw_ctx_update_mesh_vertices_device / fw_ctx_mesh_update_status / fw_ctx_destroy_mesh /
+// fw_ctx_set_mesh_colliders
 // (include/firework_hip.h: fw_mesh_collider has the ray-cast semantics; fw_collide.h walks what is uploaded here; fw_bvh.cpp
 // builds the hierarchy; fw_k_refit.hip redoes its boxes and triangles from new vertices)
 #include "fw_bvh.h"
@@ -46,6 +47,7 @@ fw_status create_mesh(fw_ctx *ctx, const char *who, bool deformable, const float
         FW_HIP(ctx, hipMemcpy(m.tris, bvh.tris.data(), bvh.tris.size() * sizeof(float), hipMemcpyHostToDevice));
         m.n_nodes = bvh.n_nodes, m.n_tris = bvh.n_tris;
         bounding_sphere(bvh.lo, bvh.hi, m.center, &m.radius);
+        memcpy(m.lo, bvh.lo, sizeof m.lo), memcpy(m.hi, bvh.hi, sizeof m.hi), m.pad = bvh.pad;
         if (deformable) {
             const size_t nf = (size_t)n_vertices * 3;
             if ((st = alloc_buf(ctx, m.slots, (size_t)bvh.n_tris)) || (st = alloc_buf(ctx, m.order, (size_t)bvh.n_nodes)) ||
@@ -106,6 +108,10 @@ fw_status stage_instances(fw_ctx *ctx, const fw_mesh_collider *inst, uint32_t n)
         memcpy(d.position, c.position, sizeof c.position);
         memcpy(d.rotation, c.rotation, sizeof c.rotation);
         d.nodes = m.nodes, d.tris = m.tris, d.n_nodes = m.n_nodes, d.layers = c.layers;
+        if (m.dev_bounds) {  // only the device knows this mesh's box: never skipped until fw_k_mesh_spheres (below) has been there
+            d.position[3] = INFINITY, memcpy(d.center, c.position, sizeof c.position);
+            continue;
+        }
         // the sphere that contains the placed mesh (the wave skip of fw_cast_ray): a ray meets the instance where
         // R^-1 (x - position) lies in the mesh, R^-1 scaling lengths by s = |rotation|^2 -- centre position + R c / s, radius r / s
         const double s = (double)c.rotation[0] * c.rotation[0] + (double)c.rotation[1] * c.rotation[1] +
@@ -126,7 +132,35 @@ fw_status stage_instances(fw_ctx *ctx, const fw_mesh_collider *inst, uint32_t n)
         FW_HIP(ctx, hipMemcpyAsync(ctx->d_mesh_inst, ctx->h_mesh_inst[slot], n * sizeof(FwMeshInst), hipMemcpyHostToDevice, ctx->stream));
         FW_HIP(ctx, hipEventRecord(ctx->ev_mesh[slot], ctx->stream));
         ctx->mesh_pending[slot] = true;
+        // behind the copy, in the same stream: the spheres of the meshes whose bounds are the device's, one launch per such mesh
+        for (uint32_t i = 0; i < n; i++) {
+            fw_ctx::MeshHost &m = ctx->meshes[inst[i].mesh];
+            if (!m.dev_bounds || m.sphere_stamp == ctx->mesh_seq) continue;
+            m.sphere_stamp = ctx->mesh_seq;
+            FW_HIP(ctx, fw_launch_mesh_spheres(ctx->stream, ctx->d_mesh_inst, n, m.nodes, m.d_rec, false));
+        }
     }
+    return FW_OK;
+}
+
+// what only a mesh whose vertices come from device memory needs, made by its first fw_ctx_update_mesh_vertices_device:
+// fw_ctx::kMeshDeviceAllocs allocations, all or none (a failure releases what it got and leaves the mesh as it was)
+fw_status reserve_device_form(fw_ctx *ctx, fw_ctx::MeshHost &m) {
+    if (m.d_rec) return FW_OK;
+    HipBuf<FwMeshRecord> rec;
+    HipBuf<FwVtxAcc> partials;
+    HipBuf<uint8_t> referenced;
+    HipBuf<FwMeshReport> report;
+    fw_status st;
+    if ((st = alloc_buf(ctx, rec, 1)) || (st = alloc_buf(ctx, partials, fw_mesh_bounds_partials(m.n_vertices))) ||
+        (st = alloc_buf(ctx, referenced, m.n_vertices)) || (st = alloc_buf(ctx, report, 1, Mem::pinned)))
+        return st;
+    FwMeshRecord r{};
+    r.first_bad = -1;
+    *report.get() = FwMeshReport{0ull, 0ull, -1ll};
+    FW_HIP(ctx, hipMemcpy(rec, &r, sizeof r, hipMemcpyHostToDevice));
+    FW_HIP(ctx, hipMemcpy(referenced, m.referenced.data(), m.n_vertices, hipMemcpyHostToDevice));
+    m.d_rec = std::move(rec), m.d_partials = std::move(partials), m.d_referenced = std::move(referenced), m.h_report = std::move(report);
     return FW_OK;
 }
 
@@ -180,13 +214,61 @@ fw_status fw_ctx_update_mesh_vertices(fw_ctx *ctx, fw_mesh mesh, const float *xy
     FW_HIP(ctx, fw_launch_mesh_refit(ctx->stream, R, m.level_off, m.h_level_off.data(), (uint32_t)m.h_level_off.size() - 1));
     // the instances of the current set that place this mesh carry its bounding sphere: restaged, in the same stream order
     // (the host's sphere changes for good only once they are on their way)
+    // (the bounds are the host's again, whatever device-form updates came before)
     const float center0[3] = {m.center[0], m.center[1], m.center[2]}, radius0 = m.radius;
+    const bool dev0 = m.dev_bounds;
     bounding_sphere(lo, hi, m.center, &m.radius);
+    m.dev_bounds = false;
     if (placed && (st = stage_instances(ctx, ctx->mesh_insts.data(), (uint32_t)ctx->mesh_insts.size()))) {
-        memcpy(m.center, center0, sizeof center0), m.radius = radius0;
+        memcpy(m.center, center0, sizeof center0), m.radius = radius0, m.dev_bounds = dev0;
         return st;
     }
+    memcpy(m.lo, lo, sizeof lo), memcpy(m.hi, hi, sizeof hi), m.pad = pad;
     ctx->fc_ok = false, ctx->boxes_epoch = 0;
+    return FW_OK;
+}
+
+fw_status fw_ctx_update_mesh_vertices_device(fw_ctx *ctx, fw_mesh mesh, const void *d_xyz, uint32_t n_vertices) {
+    if (!ctx) return FW_EINVAL;
+    if (!mesh_alive(ctx, mesh)) return fail(ctx, FW_EINVAL, "fw_ctx_update_mesh_vertices_device: unknown mesh handle");
+    fw_ctx::MeshHost &m = ctx->meshes[mesh];
+    if (!m.deformable) return fail(ctx, FW_EINVAL, "fw_ctx_update_mesh_vertices_device: the mesh was not created as deformable");
+    if (!d_xyz || n_vertices != m.n_vertices)
+        return fail(ctx, FW_EINVAL, "fw_ctx_update_mesh_vertices_device: the vertex count differs from the creation's");
+    hipSetDevice(ctx->device);
+    fw_status st;  // (the allocations of a mesh's first call come first: a failure leaves the mesh as it was, for both forms)
+    if ((st = reserve_device_form(ctx, m))) return st;
+    // Everything below is launches into the context's stream: no wait, no pass over the vertices, no copy of them.
+    //   1. bounds: every vertex checked, the referenced ones reduced; one workgroup folds the partials into the record and the
+    //      report.  A record that has held the host's box until now takes it when this update is rejected (the seed), so that it
+    //      always describes the last accepted shape.
+    //   2. the refit, gathering straight from d_xyz, with the record's pad -- nothing when the record says rejected.
+    //   3. the spheres of the instances that place the mesh, in place in the device table -- nothing when rejected.
+    // In-place is safe for the reason the host form gives: every launch that casts rays runs on this stream.
+    FwMeshSeed seed;
+    memcpy(seed.lo, m.lo, sizeof m.lo), memcpy(seed.hi, m.hi, sizeof m.hi), seed.pad = m.pad;
+    FW_HIP(ctx, fw_launch_mesh_bounds(ctx->stream, static_cast<const float *>(d_xyz), m.d_referenced, n_vertices, m.d_partials, m.d_rec,
+                                      m.h_report, m.dev_bounds ? nullptr : &seed));
+    FwRefit R{};
+    R.nodes = reinterpret_cast<FwR4 *>(m.nodes.get()), R.tris = reinterpret_cast<FwR4 *>(m.tris.get());
+    R.slots = m.slots, R.xyz = static_cast<const float *>(d_xyz), R.order = m.order, R.rec = m.d_rec;
+    FW_HIP(ctx, fw_launch_mesh_refit(ctx->stream, R, m.level_off, m.h_level_off.data(), (uint32_t)m.h_level_off.size() - 1));
+    m.dev_bounds = true;
+    if (std::find(ctx->mesh_set.begin(), ctx->mesh_set.end(), mesh) != ctx->mesh_set.end())
+        FW_HIP(ctx, fw_launch_mesh_spheres(ctx->stream, ctx->d_mesh_inst, ctx->g.n_mesh_inst, m.nodes, m.d_rec, true));
+    ctx->fc_ok = false, ctx->boxes_epoch = 0;
+    return FW_OK;
+}
+
+fw_status fw_ctx_mesh_update_status(fw_ctx *ctx, fw_mesh mesh, uint64_t *n_applied, uint64_t *n_rejected, int64_t *first_bad_vertex) {
+    if (!ctx) return FW_EINVAL;
+    if (!mesh_alive(ctx, mesh)) return fail(ctx, FW_EINVAL, "fw_ctx_mesh_update_status: unknown mesh handle");
+    const fw_ctx::MeshHost &m = ctx->meshes[mesh];
+    if (!m.deformable) return fail(ctx, FW_EINVAL, "fw_ctx_mesh_update_status: the mesh was not created as deformable");
+    const volatile FwMeshReport *r = m.h_report.get();  // (null: no device-form update yet)
+    if (n_applied) *n_applied = r ? r->n_applied : 0;
+    if (n_rejected) *n_rejected = r ? r->n_rejected : 0;
+    if (first_bad_vertex) *first_bad_vertex = r ? r->first_bad : -1;
     return FW_OK;
 }
 

@@ -6,6 +6,7 @@
 #include "fw_device.h"
 #include "fw_collide.h"
 #include "fw_refit.h"
+#include "fw_mesh_bounds.h"
 
 // The product build (the default `make`) carries no experiment surface: the FW_DEBUG profiling modes (kernel ablations, in-kernel
 // timestamps) and the A/B switches of measured-and-rejected variants exist only in the `make ab` build (-DFW_AB,
@@ -402,3 +403,19 @@ hipError_t fw_launch_copy_probe(hipStream_t s, const void *src, void *dst, size_
 #define FW_REFIT_TAIL 4096u
 hipError_t fw_launch_mesh_refit(hipStream_t s, const FwRefit &R, const uint32_t *d_level_off, const uint32_t *h_level_off,
                                 uint32_t n_levels);
+// Vertices that are already in device memory (fw_ctx_update_mesh_vertices_device; fw_mesh_bounds.h has the arithmetic).
+// fw_launch_mesh_bounds: one launch of fw_mesh_bounds_partials(n_vertices) workgroups (capped: this is latency, not bandwidth)
+// leaves a partial each in d_partials, a second launch of ONE workgroup folds them into the mesh's record and the pinned
+// report.  seed (may be null): the box the record takes when this update is rejected (the host's, which held until now).
+#define FW_BOUNDS_BLOCK 256
+#define FW_BOUNDS_MAX_GRID 256u
+struct FwMeshSeed {
+    float lo[3], hi[3], pad;
+};
+uint32_t fw_mesh_bounds_partials(uint32_t n_vertices);
+hipError_t fw_launch_mesh_bounds(hipStream_t s, const float *d_xyz, const uint8_t *d_referenced, uint32_t n_vertices, FwVtxAcc *d_partials,
+                                 FwMeshRecord *d_rec, FwMeshReport *h_report, const FwMeshSeed *seed);
+// the bounding spheres of the instances in d_inst[0 .. n_inst) whose tables start at `nodes`, rewritten from the record's box;
+// after_update: nothing when the record says the latest update was rejected
+hipError_t fw_launch_mesh_spheres(hipStream_t s, FwMeshInst *d_inst, uint32_t n_inst, const float4 *nodes, const FwMeshRecord *d_rec,
+                                  bool after_update);

@@ -30,6 +30,9 @@ struct FwRefit {
     const float *xyz;        // the new vertices, 3 floats each
     const uint32_t *order;   // every node, by height: the leaves first, every interior node behind both its children (FwBvh::order)
     float pad;               // what every leaf box is grown by: the builder's rule over the new vertices (fw_bvh_bounds)
+    // vertices from device memory (fw_mesh_bounds.h): the launch takes the pad from this record of the device instead, and does
+    // nothing when the record says the update was rejected.  Null: `pad` above holds (the host form, the CPU test)
+    const struct FwMeshRecord *rec;
 };
 
 // std::min / std::max as the builder calls them

@@ -248,6 +248,22 @@ class ParticleSystem:
         xyz = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
         self._check(self._lib.fw_ctx_update_mesh_vertices(self._ctx, int(mesh), xyz.ctypes.data_as(C.c_void_p), len(xyz)))
 
+    def update_mesh_vertices_device(self, mesh: int, data_ptr: int, n_vertices: int) -> None:
+        """update_mesh_vertices for positions that are already in device memory: data_ptr is the device address of n_vertices
+        packed float32 triples (a torch tensor's data_ptr(), as attach_instances takes one), written on this context's stream
+        or ordered in front of it by the caller.  Never synchronises and copies nothing: the buffer is read by work enqueued
+        inside the call only, so it may be overwritten by work ordered behind the call.  A non-finite vertex is found on the
+        device: that update is rejected there and the mesh keeps its shape (mesh_update_status)."""
+        self._check(self._lib.fw_ctx_update_mesh_vertices_device(self._ctx, int(mesh), C.c_void_p(int(data_ptr)), int(n_vertices)))
+
+    def mesh_update_status(self, mesh: int):
+        """-> (applied, rejected, first_bad_vertex) of the mesh's device-form updates as the device has reported them so far
+        (first_bad_vertex: the lowest non-finite index of the latest rejected update, -1 for none).  Does not synchronise; exact
+        after synchronize()."""
+        a, r, b = C.c_uint64(0), C.c_uint64(0), C.c_int64(-1)
+        self._check(self._lib.fw_ctx_mesh_update_status(self._ctx, int(mesh), C.byref(a), C.byref(r), C.byref(b)))
+        return int(a.value), int(r.value), int(b.value)
+
     def destroy_mesh(self, mesh: int) -> None:
         """Frees a mesh the current instance set does not place (waits for the frames in flight)."""
         self._check(self._lib.fw_ctx_destroy_mesh(self._ctx, int(mesh)))

@@ -2,13 +2,18 @@
 // Global / OnDemand / Nested entries, every curve kind, modifier, transforms, parent velocity, destroyed-particle
 // handler, collisions against an analytic world, fused AABB tracking; with the argument `mesh` also against triangle meshes (one
 // mesh placed twice, the set replaced and a mesh destroyed half way), and with `deform` against the same meshes created deformable,
-// their vertices moved every fifth frame (create_deformable_mesh / update_mesh_vertices).  Prints, every tenth frame, the live counts and an
+// their vertices moved every fifth frame (create_deformable_mesh / update_mesh_vertices); `deform_device` is `deform` with the new
+// vertices handed over in DEVICE memory (update_mesh_vertices_device: copied there on the context's stream, no wait) and one more
+// line, the device's verdict on the sheet's updates (mesh_update_status).  Prints, every tenth frame, the live counts and an
 // FNV-1a digest of every particle record; tests/test_cpp_host.py runs the same scenario through the Python mirror and
 // expects the same lines: both mirrors marshal the reference's settings into the C ABI the same way.
 //
 //   make -C examples && ./examples/mirror_check
 #include <cstdio>
 #include <cstring>
+#include <vector>
+
+#include <hip/hip_runtime_api.h>
 
 #include "firework.hpp"
 
@@ -23,10 +28,25 @@ static uint64_t fnv(const void *p, size_t n, uint64_t h = 1469598103934665603ull
 int main(int argc, char **argv) {
     // `mirror_check mesh`: the same scenario with triangle meshes in the collider world (create, place twice, replace, destroy)
     // `mirror_check deform`: ... with both meshes deformable: the ramp's far edge rises every fifth frame, then the sheet's apex
-    const bool deform = argc > 1 && std::strcmp(argv[1], "deform") == 0;
+    // `mirror_check deform_device`: ... with those vertices taken from device memory
+    const bool deform_device = argc > 1 && std::strcmp(argv[1], "deform_device") == 0;
+    const bool deform = deform_device || (argc > 1 && std::strcmp(argv[1], "deform") == 0);
     const bool with_meshes = deform || (argc > 1 && std::strcmp(argv[1], "mesh") == 0);
     try {
         ParticleSystemPlugin app(0, /*seed*/ 0x00C0FFEE);
+        // new vertices of a deformable mesh, in host memory or (deform_device) through a device buffer of their own per update --
+        // a stand-in for the output of a GPU pass -- filled on the context's stream; freed at the end
+        std::vector<void *> device_buffers;
+        auto move_vertices = [&](fw_mesh m, const std::vector<float> &xyz) {
+            if (!deform_device) return app.update_mesh_vertices(m, xyz);
+            void *d = nullptr;
+            if (hipMalloc(&d, xyz.size() * sizeof(float)) != hipSuccess) throw Error(FW_EHIP, "hipMalloc");
+            device_buffers.push_back(d);
+            // (pageable source: the runtime has taken the values when the call returns)
+            if (hipMemcpyAsync(d, xyz.data(), xyz.size() * sizeof(float), hipMemcpyHostToDevice, (hipStream_t)app.stream()) != hipSuccess)
+                throw Error(FW_EHIP, "hipMemcpyAsync");
+            app.update_mesh_vertices_device(m, d, (uint32_t)(xyz.size() / 3));
+        };
         app.track_aabbs(true);
         app.set_colliders({Collider::Plane({0.0f, -1.0f, 0.0f}, {0.0f, 1.0f, 0.0f}), Collider::Sphere({1.0f, 0.5f, 0.0f}, 0.75f, 2u),
                            Collider::Box({-2.0f, 0.0f, 0.0f}, {0.5f, 1.0f, 0.5f}, Quat{0.0f, 0.38268343f, 0.0f, 0.92387953f})});
@@ -103,10 +123,10 @@ int main(int argc, char **argv) {
             if (fr == 0 || fr == 7 || fr == 8 || fr == 31) d->queue_particles(500 + 10 * fr);
             if (deform && fr % 5 == 0 && fr < 30) {  // the ramp's far edge at 0.25 + fr / 40 (exact in fp32), in both places it is placed
                 const float y = 0.25f + 0.125f * (float)(fr / 5);
-                app.update_mesh_vertices(ramp, {-2.0f, -0.25f, -2.0f, 2.0f, -0.25f, -2.0f, 2.0f, y, 2.0f, -2.0f, y, 2.0f});
+                move_vertices(ramp, {-2.0f, -0.25f, -2.0f, 2.0f, -0.25f, -2.0f, 2.0f, y, 2.0f, -2.0f, y, 2.0f});
             }
             if (deform && fr % 5 == 0 && fr > 30)  // the sheet's apex rises
-                app.update_mesh_vertices(sheet, {-3.0f, 0.0f, -3.0f, 3.0f, 0.0f, -3.0f, 0.0f, 0.5f + 0.25f * (float)(fr / 5 - 6), 3.0f});
+                move_vertices(sheet, {-3.0f, 0.0f, -3.0f, 3.0f, 0.0f, -3.0f, 0.0f, 0.5f + 0.25f * (float)(fr / 5 - 6), 3.0f});
             if (with_meshes && fr == 30) {  // another mesh takes the ramp's place (layers 1 | 2, tilted about Z); the ramp is destroyed
                 sheet = deform ? app.create_deformable_mesh({-3.0f, 0.0f, -3.0f, 3.0f, 0.0f, -3.0f, 0.0f, 0.5f, 3.0f}, {0, 2, 1})
                                : app.create_mesh({-3.0f, 0.0f, -3.0f, 3.0f, 0.0f, -3.0f, 0.0f, 0.5f, 3.0f}, {0, 2, 1});
@@ -128,6 +148,12 @@ int main(int argc, char **argv) {
             std::printf(" aabb %d %016llx active %d\n", any ? 1 : 0, (unsigned long long)fnv(box, sizeof box), d->active() ? 1 : 0);
         }
         std::printf("destroyed reported %llu\n", (unsigned long long)destroyed_seen);
+        if (deform_device) {
+            app.synchronize();
+            const auto s = app.mesh_update_status(sheet);
+            std::printf("sheet device updates %llu %llu %lld\n", (unsigned long long)s.applied, (unsigned long long)s.rejected, (long long)s.first_bad_vertex);
+            for (void *d : device_buffers) (void)hipFree(d);
+        }
     } catch (const Error &e) {
         std::fprintf(stderr, "firework error %d: %s\n", (int)e.status, e.what());
         return 1;

@@ -387,6 +387,21 @@ class ParticleSystemPlugin {
     void update_mesh_vertices(fw_mesh m, const std::vector<float> &xyz) {
         check(fw_ctx_update_mesh_vertices(ctx_, m, xyz.data(), (uint32_t)(xyz.size() / 3)));
     }
+    // ... positions that are already in device memory (d_xyz: n_vertices packed float triples written on stream(), read only by
+    // what the call enqueues): never synchronises; a non-finite vertex rejects the update ON THE DEVICE, which
+    // mesh_update_status reports (exact after synchronize())
+    void update_mesh_vertices_device(fw_mesh m, const void *d_xyz, uint32_t n_vertices) {
+        check(fw_ctx_update_mesh_vertices_device(ctx_, m, d_xyz, n_vertices));
+    }
+    struct MeshUpdateStatus {
+        uint64_t applied = 0, rejected = 0;
+        int64_t first_bad_vertex = -1;
+    };
+    MeshUpdateStatus mesh_update_status(fw_mesh m) {
+        MeshUpdateStatus s;
+        check(fw_ctx_mesh_update_status(ctx_, m, &s.applied, &s.rejected, &s.first_bad_vertex));
+        return s;
+    }
     void destroy_mesh(fw_mesh m) { check(fw_ctx_destroy_mesh(ctx_, m)); }
     void set_mesh_colliders(const std::vector<MeshCollider> &ms) {
         std::vector<fw_mesh_collider> v(ms.size());
@@ -452,6 +467,7 @@ class ParticleSystemPlugin {
         check(fw_ctx_queue(ctx_, (uint32_t)h.size(), h.data(), counts.data()));
     }
     void synchronize() { check(fw_ctx_synchronize(ctx_)); }
+    void *stream() const { return fw_ctx_stream(ctx_); }  // the hipStream_t the context enqueues on
     uint64_t live_count() {
         uint64_t n = 0;
         check(fw_ctx_live_count(ctx_, &n));

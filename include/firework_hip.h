@@ -169,6 +169,24 @@ typedef struct fw_collider {
  *             accepted: the mesh is hit by nothing until the next update (creation still rejects such a mesh).
  *   QUALITY   a refit keeps the tree the creation vertices gave: after large deformations boxes overlap more and casts get
  *             slower, never wrong.  A caller whose mesh has changed beyond recognition creates a new one.
+ *   FROM DEVICE MEMORY   fw_ctx_update_mesh_vertices_device is the same update for vertices a GPU pass has just produced
+ *             (skinning, cloth, a terrain that is dug into).  AS IF CREATED ANEW holds unchanged, and the result equals what
+ *             fw_ctx_update_mesh_vertices gives for the same values, bit for bit.  The call never waits for the device and does
+ *             no host work that grows with the vertex count; everything it enqueues goes to the context's stream
+ *             (fw_ctx_stream).  The caller writes d_xyz on that stream, or orders its producer in front of the call itself.  The
+ *             buffer is read ONLY by work enqueued inside the call -- no copy is made, the refit gathers straight from it -- so
+ *             work the caller orders behind the call on that stream may overwrite it.  Frames enqueued before the call see the
+ *             old shape, frames after it the new one.  A mesh's first such call allocates what the device side needs (a
+ *             failure: FW_EHIP, everything released, the mesh usable by both forms) and uploads a byte per vertex, which may
+ *             wait for that copy; later calls allocate nothing.
+ *             Host-side errors are those of the host form, at once and with nothing changed (null pointer, unknown handle,
+ *             not deformable, another vertex count).  A NON-FINITE vertex is something only the device can see: the update is
+ *             then REJECTED ON THE DEVICE -- hierarchy, triangles and the bounding spheres of placed instances stay exactly
+ *             what they were, frames go on casting against the previous shape, fw_step does not fail, and the next good
+ *             update of either form applies normally.  fw_ctx_mesh_update_status reports, without waiting, how many device-form
+ *             updates of the mesh the device has applied and rejected so far and the lowest non-finite vertex index of the
+ *             latest rejected one (-1: none yet); the words are written by the device into pinned memory, so they lag the
+ *             calls until fw_ctx_synchronize, after which they are exact.  The two forms may alternate freely on one mesh.
  * fw_ctx_destroy_mesh and fw_ctx_set_mesh_colliders treat a deformable mesh like any other. */
 typedef int32_t fw_mesh; /* handle >= 0, per context */
 typedef struct fw_mesh_collider { /* one placed instance of a mesh */
@@ -261,6 +279,14 @@ fw_status fw_ctx_create_deformable_mesh(fw_ctx *ctx, const float *xyz, uint32_t 
 /* replaces the vertex positions of a deformable mesh (DEFORMABLE MESHES above); xyz[n_vertices][3] in host memory, n_vertices
  * as at creation.  Does not synchronise. */
 fw_status fw_ctx_update_mesh_vertices(fw_ctx *ctx, fw_mesh mesh, const float *xyz, uint32_t n_vertices);
+/* as fw_ctx_update_mesh_vertices, but d_xyz[n_vertices][3] (packed float) is DEVICE memory, read in the order of the context's
+ * stream by the launches this call enqueues and by nothing later (DEFORMABLE MESHES: FROM DEVICE MEMORY).  Never synchronises;
+ * a non-finite vertex is found by the device and reported through fw_ctx_mesh_update_status. */
+fw_status fw_ctx_update_mesh_vertices_device(fw_ctx *ctx, fw_mesh mesh, const void *d_xyz, uint32_t n_vertices);
+/* what the device has decided about the device-form updates of a deformable mesh so far: updates applied, updates rejected,
+ * lowest non-finite vertex index of the latest rejected one (-1: none).  Any out pointer may be NULL.  Does not synchronise:
+ * exact after fw_ctx_synchronize.  FW_EINVAL: unknown handle, mesh not deformable. */
+fw_status fw_ctx_mesh_update_status(fw_ctx *ctx, fw_mesh mesh, uint64_t *n_applied, uint64_t *n_rejected, int64_t *first_bad_vertex);
 /* FW_EINVAL while the current instance set places the mesh; otherwise waits for the frames in flight and frees it */
 fw_status fw_ctx_destroy_mesh(fw_ctx *ctx, fw_mesh mesh);
 /* replaces the context's mesh instances (copied; n = 0 clears them); all-or-nothing: an unknown mesh handle -> FW_EINVAL and

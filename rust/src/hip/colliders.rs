@@ -67,7 +67,10 @@ pub fn hip_sync_colliders(
         let scale = collider.scale();
         let key = [scale.x.to_bits(), scale.y.to_bits(), scale.z.to_bits()];
         // (a trimesh whose vertices change every frame -- `collider.is_changed()` with the same topology -- would be forwarded to
-        // `fw_ctx_update_mesh_vertices` of a mesh made by `fw_ctx_create_deformable_mesh` here instead of being created anew)
+        // `fw_ctx_update_mesh_vertices` of a mesh made by `fw_ctx_create_deformable_mesh` here instead of being created anew;
+        // vertices that a GPU pass of the host has written, e.g. skinning output in a wgpu buffer shared with HIP, go through
+        // `fw_ctx_update_mesh_vertices_device` once that pass is ordered in front of `fw_ctx_stream`, and what the device decided
+        // about them -- a non-finite vertex rejects the update there -- is read back with `fw_ctx_mesh_update_status`)
         let cached = meshes.0.get(&entity).copied().filter(|(k, _)| *k == key && !collider.is_changed());
         let mesh = match cached {
             Some((_, m)) => Some(m),

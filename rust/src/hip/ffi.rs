@@ -67,6 +67,8 @@ extern "C" {
     pub fn fw_ctx_create_mesh(ctx: *mut fw_ctx, xyz: *const f32, n_vertices: u32, indices: *const u32, n_triangles: u32, out: *mut fw_mesh) -> c_int;
     pub fn fw_ctx_create_deformable_mesh(ctx: *mut fw_ctx, xyz: *const f32, n_vertices: u32, indices: *const u32, n_triangles: u32, out: *mut fw_mesh) -> c_int;
     pub fn fw_ctx_update_mesh_vertices(ctx: *mut fw_ctx, mesh: fw_mesh, xyz: *const f32, n_vertices: u32) -> c_int;
+    pub fn fw_ctx_update_mesh_vertices_device(ctx: *mut fw_ctx, mesh: fw_mesh, d_xyz: *const c_void, n_vertices: u32) -> c_int;
+    pub fn fw_ctx_mesh_update_status(ctx: *mut fw_ctx, mesh: fw_mesh, n_applied: *mut u64, n_rejected: *mut u64, first_bad_vertex: *mut i64) -> c_int;
     pub fn fw_ctx_destroy_mesh(ctx: *mut fw_ctx, mesh: fw_mesh) -> c_int;
     pub fn fw_ctx_set_mesh_colliders(ctx: *mut fw_ctx, instances: *const fw_mesh_collider, n: u32) -> c_int;
     pub fn fw_spawner_create(ctx: *mut fw_ctx, desc: *const fw_spawner_desc, out: *mut fw_spawner) -> c_int;

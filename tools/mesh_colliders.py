@@ -14,6 +14,10 @@
                                                            before deformable meshes, destroy + create + set per frame (rebuildN: the set is
                                                            emptied first, a placed mesh cannot be destroyed); and the
                                                            cast cost over a refitted tree against a fresh build of the same vertices
+  python tools/mesh_colliders.py device_vertices           the deformN rows next to devdeformN -- the same 16 vertex sets resident in device
+                                                           memory, handed over by fw_ctx_update_mesh_vertices_device (no copy back, no
+                                                           host pass, no upload) -- and to the static terrain: alternated, 3 rounds, one
+                                                           subprocess per run; us per frame and the host time inside the call
   python tools/mesh_colliders.py one WORLD RATE [FRAMES]   one measurement (what the modes above run; also the rocprofv3 target)
 
 Frame time: 150 warm-up frames (the 2 s lifetime fills), then the best of 3 windows of 300 frames, each ending in a
@@ -78,10 +82,11 @@ def one(world, rate, frames=300):
         info["triangles"] = len(t)
         ps.set_mesh_colliders([S.MeshCollider(m)])
         ps.set_colliders(colliders[1:])
-    elif world.startswith(("deform", "rebuild", "refitted", "fresh")):
+    elif world.startswith(("devdeform", "deform", "rebuild", "refitted", "fresh")):
         # a terrain that moves: deformN updates a deformable mesh every frame, rebuildN destroys and creates a static one;
         # refittedN:A / freshN:A cast (no per-frame change) over a tree refitted to phase A against one built there
-        kind = next(k for k in ("deform", "rebuild", "refitted", "fresh") if world.startswith(k))
+        # devdeformN is deformN with the vertex sets in device tensors (fw_ctx_update_mesh_vertices_device)
+        kind = next(k for k in ("devdeform", "deform", "rebuild", "refitted", "fresh") if world.startswith(k))
         spec = world[len(kind):].split(":")
         cells, far = int(spec[0]), float(spec[1]) if len(spec) > 1 else 0.0
         t = _terrain(cells)[1]
@@ -94,7 +99,13 @@ def one(world, rate, frames=300):
         elif kind == "fresh":
             m = ps.create_mesh(_terrain(cells, phase=far, amp=0.15 + 0.2 * far)[0], t)
         else:
-            m = ps.create_deformable_mesh(phases[0], t) if kind == "deform" else ps.create_mesh(phases[0], t)
+            m = ps.create_deformable_mesh(phases[0], t) if kind in ("deform", "devdeform") else ps.create_mesh(phases[0], t)
+        if kind == "devdeform":
+            import torch
+
+            with torch.cuda.stream(torch.cuda.ExternalStream(ps.stream)):
+                d_phases = [torch.from_numpy(v.copy()).to("cuda") for v in phases]
+            ptrs = [d.data_ptr() for d in d_phases]
         ps.set_mesh_colliders([S.MeshCollider(m)])
         state = {"m": m, "k": 0, "host": 0.0, "calls": 0}
 
@@ -104,6 +115,8 @@ def one(world, rate, frames=300):
             t0 = time.perf_counter()
             if kind == "deform":
                 ps.update_mesh_vertices(state["m"], v)
+            elif kind == "devdeform":
+                ps.update_mesh_vertices_device(state["m"], ptrs[state["k"] % len(phases)], len(v))
             elif kind == "rebuild":
                 ps.set_mesh_colliders([])
                 ps.destroy_mesh(state["m"])
@@ -113,7 +126,7 @@ def one(world, rate, frames=300):
             state["calls"] += 1
     else:
         raise SystemExit(f"unknown world {world}")
-    if not world.startswith(("deform", "rebuild")):
+    if not world.startswith(("devdeform", "deform", "rebuild")):
         per_frame = None
     if world.startswith("rebuild"):
         frames = min(frames, 30)  # (tens of milliseconds each at 131k triangles)
@@ -135,6 +148,8 @@ def one(world, rate, frames=300):
         best = min(best, (time.perf_counter() - t0) / frames * 1e6)
     if per_frame:
         info["host_us_per_call"] = round(state["host"] / state["calls"] * 1e6, 2)
+    if world.startswith("devdeform"):
+        info["status"] = ps.mesh_update_status(state["m"])
     info.update(us_per_frame=round(best, 2), live=h.count(0), path=h.update_path(0)[0])
     ps.close()
     return info
@@ -186,6 +201,20 @@ def main():
             for world in (f"refitted256:{far}", f"fresh256:{far}"):
                 r = _run(world, 640000.0)
                 print(f"{world:16s} rate   640000: {r['us_per_frame']:.2f} us per frame ({r['live']} live)", flush=True)
+    elif mode == "device_vertices":
+        rows = {}
+        for rnd in range(3):
+            for rate in (80000.0, 640000.0):
+                for cells in (32, 256):
+                    for world in (f"deform{cells}", f"devdeform{cells}", f"terrain{cells}"):
+                        r = _run(world, rate)
+                        rows.setdefault((rate, cells, world), []).append((r["us_per_frame"], r.get("host_us_per_call", 0.0)))
+                        print(f"round {rnd + 1} {world:13s} ({r['triangles']:6d} triangles) rate {rate:8.0f}: {r['us_per_frame']:.2f} us per frame, "
+                              f"{r.get('host_us_per_call', 0.0):.2f} us of host time per change ({r['live']} live, {r['path']} path"
+                              f"{', status ' + str(r['status']) if 'status' in r else ''})", flush=True)
+        for (rate, cells, world), v in rows.items():
+            print(f"{world:13s} rate {rate:8.0f}: us per frame {[a for a, _ in v]} (best {min(a for a, _ in v):.2f}); host us per change "
+                  f"{[b for _, b in v]}", flush=True)
     elif mode == "build":
         import torch
 
