@@ -423,7 +423,8 @@ __device__ __forceinline__ fw_q4 fw_quat_step(fw_v3 v) {
 
 // INPLACE (FIFO segments, fw_k_update_fifo): the output slot is the input slot, so a plane whose new value is
 // bit-identical to the loaded one for every lane of the wave is not written (rotation and angular velocity of particles
-// that do not spin, the scale under a constant curve); `full` marks a lane whose slot holds nothing yet (a particle
+// that do not spin, the scale under a constant curve); the angular velocity, whose components are planes of their own, is
+// tested and skipped component by component (round 11); `full` marks a lane whose slot holds nothing yet (a particle
 // spawned this frame): it writes everything.
 // WM >= 0: which of the optional planes the launch writes is a compile-time fact (bit 0 base colour, 1 emissive, 2 scale)
 // wmode (INPLACE only): where the particle's two constants -- initial_scale in q1.w, lifetime in q3.w -- are.  FW_W_REGS: in the
@@ -493,10 +494,15 @@ __device__ __forceinline__ void fw_integrate_store(const FwType &T, const float 
         }
         const uint32_t d2 = (__float_as_uint(nr.x) ^ __float_as_uint(q2.x)) | (__float_as_uint(nr.y) ^ __float_as_uint(q2.y)) |
                             (__float_as_uint(nr.z) ^ __float_as_uint(q2.z)) | (__float_as_uint(nr.w) ^ __float_as_uint(q2.w));
-        const uint32_t d3 = (__float_as_uint(wx) ^ __float_as_uint(q3.x)) | (__float_as_uint(wy) ^ __float_as_uint(q3.y)) |
-                            (__float_as_uint(wz) ^ __float_as_uint(q3.z));
         if (W.wr2 && __any(full || d2 != 0u)) fw_st4w<NT == 2>(W.q2, b16, make_float4(nr.x, nr.y, nr.z, nr.w));  // wave-uniform branches
-        if (W.wr3 && __any(full || d3 != 0u)) fw_stc3w<NT == 2>(W.q3, W.cp, b4, wx, wy, wz);
+        // (round 11: the angular velocity's components live in planes of their own, so each one is tested -- and skipped -- by itself:
+        // particles that spin about a fixed axis, RandVec3 with spread 0 and no angular acceleration across it, keep a +0 in the other
+        // two for ever.  The same exact test, the same store per plane as fw_stc3w.)
+        if (W.wr3) {
+            if (__any(full || __float_as_uint(wx) != __float_as_uint(q3.x))) fw_st1w<NT == 2>(W.q3, b4, wx);
+            if (__any(full || __float_as_uint(wy) != __float_as_uint(q3.y))) fw_st1w<NT == 2>(W.q3 + W.cp, b4, wy);
+            if (__any(full || __float_as_uint(wz) != __float_as_uint(q3.z))) fw_st1w<NT == 2>(W.q3 + 2 * W.cp, b4, wz);
+        }
         // (`full` lanes -- slots that hold nothing yet -- write every plane the type MAINTAINS: W.wr4 is false exactly for FW_TYPE_DERIVED)
         const bool fullk = full && W.wr4;
         if ((WM >= 0 ? (WM & 1) != 0 : W.wr5) || fullk) fw_st4w<NT != 0>(W.q5, b16, make_float4(bc[0], bc[1], bc[2], bc[3]));

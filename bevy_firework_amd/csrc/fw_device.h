@@ -16,7 +16,8 @@
 //   Q2  float4 {rot.x, rot.y, rot.z, rot.w}          offset  32*C   read+write
 //   Q3  float4 {angvel.x, .y, .z, lifetime}          offset  48*C   read+write
 //       (round 6, RING segments -- FwSeg::cpl: the Q1 and Q3 regions hold their four components as four planes of C floats each,
-//       4*C bytes apart: initial_scale and lifetime never change, an in-place update moves three dwords per lane, not a dwordx4)
+//       4*C bytes apart: initial_scale and lifetime never change, an in-place update moves three dwords per lane, not a dwordx4;
+//       round 11: each component plane of Q3 is stored only in waves where that component's bits changed -- fw_integrate_store)
 //   Q5  float4 base_color rgba                       offset  64*C   write only
 //   Q6  float4 emissive_color rgba                   offset  80*C   write only
 //   S4  float  scale                                 offset  96*C   write only

@@ -11,6 +11,8 @@
 // Per live particle the kernel reads the four state planes (64 B) and writes position+age and velocity (32 B), the
 // colour planes whose gradient is not constant, the scale unless its curve is constant, and rotation / angular
 // velocity only in waves where they changed: 132 B for the linear 2-key curves of configs[1] instead of 164.
+// (round 11: the angular velocity -- three component planes -- is tested and written per COMPONENT: about a fixed axis, two of its
+// three dwords are never stored after the particle's first update.  The rotation is a float4 and still moves whole.)
 // ---------------------------------------------------------------------------------
 // the ParticleInstance records of a wave's survivors: consecutive in the output unless the wave straddles the ring's head
 template <bool INST, bool NT = false>

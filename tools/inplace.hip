@@ -146,6 +146,84 @@ __global__ __launch_bounds__(256) void k_upd_s3(char* __restrict__ buf, uint32_t
     }
 }
 
+// round 11 question: an in-place update must LOAD a component to know that it did not change, but need not store it.  With a fixed spin
+// axis (0,1,0) four of the 14 maintained words keep their bits: Q2 x/z and Q3 x/z.  Does a cut of the WRITES alone shorten the kernel?
+// Q2P: Q2 as four scalar planes (else a float4, written whole when any component moved); M2 / M3: bit c = component c of Q2 / Q3 moves
+// (a mover adds a constant, so its bits change every launch; the others keep theirs).  Every store of Q2 / Q3 sits under the product's
+// test -- __any(new bits != loaded bits) -- so the rows carry its cost too.  All 14 words are read in every row.
+template <int Q2P, int M2, int M3, int NT>
+__global__ __launch_bounds__(256) void k_upd_cw(char* __restrict__ buf, uint32_t n, uint32_t C, int K, float z) {  // z: 0 at run time, unknown to the compiler
+    constexpr int R = 4;
+    const uint32_t base = blockIdx.x * 256 * R;
+    f4v q0[R];
+    float q1[R][3], q2[R][4], q3[R][3];
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        const uint32_t i = min(base + r * 256 + threadIdx.x, n - 1);
+        const f4v* a0 = (const f4v*)(buf) + i;
+        q0[r] = NT ? __builtin_nontemporal_load(a0) : *a0;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const float* a1 = (const float*)(buf + (size_t)(16 + 4 * c) * C) + i;
+            q1[r][c] = NT ? __builtin_nontemporal_load(a1) : *a1;
+        }
+        if (Q2P) {
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                const float* a2 = (const float*)(buf + (size_t)(32 + 4 * c) * C) + i;
+                q2[r][c] = NT ? __builtin_nontemporal_load(a2) : *a2;
+            }
+        } else {
+            const f4v* a2 = (const f4v*)(buf + (size_t)32 * C) + i;
+            const f4v v = NT ? __builtin_nontemporal_load(a2) : *a2;
+            q2[r][0] = v.x, q2[r][1] = v.y, q2[r][2] = v.z, q2[r][3] = v.w;
+        }
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const float* a3 = (const float*)(buf + (size_t)(48 + 4 * c) * C) + i;
+            q3[r][c] = NT ? __builtin_nontemporal_load(a3) : *a3;
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < R; r++) {
+        const uint32_t i = base + r * 256 + threadIdx.x;
+        if (i < n) {
+            f4v a = q0[r];
+            a.x = work(a.x + q1[r][0], K); q1[r][1] += a.y; q1[r][2] += a.z; q1[r][0] += a.w;
+            f4v* o0 = (f4v*)(buf) + i;
+            if (NT) __builtin_nontemporal_store(a, o0); else *o0 = a;
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                float* o1 = (float*)(buf + (size_t)(16 + 4 * c) * C) + i;
+                if (NT) __builtin_nontemporal_store(q1[r][c], o1); else *o1 = q1[r][c];
+            }
+            float n2[4], n3[3];
+#pragma unroll
+            for (int c = 0; c < 4; c++) n2[c] = q2[r][c] + ((M2 >> c & 1) ? 1.0f : z);
+#pragma unroll
+            for (int c = 0; c < 3; c++) n3[c] = q3[r][c] + ((M3 >> c & 1) ? 1.0f : z);
+            if (Q2P) {
+#pragma unroll
+                for (int c = 0; c < 4; c++) {
+                    float* o2 = (float*)(buf + (size_t)(32 + 4 * c) * C) + i;
+                    if (__any(__float_as_uint(n2[c]) != __float_as_uint(q2[r][c]))) { if (NT) __builtin_nontemporal_store(n2[c], o2); else *o2 = n2[c]; }
+                }
+            } else {
+                const uint32_t d2 = (__float_as_uint(n2[0]) ^ __float_as_uint(q2[r][0])) | (__float_as_uint(n2[1]) ^ __float_as_uint(q2[r][1])) |
+                                    (__float_as_uint(n2[2]) ^ __float_as_uint(q2[r][2])) | (__float_as_uint(n2[3]) ^ __float_as_uint(q2[r][3]));
+                f4v* o2 = (f4v*)(buf + (size_t)32 * C) + i;
+                const f4v v = {n2[0], n2[1], n2[2], n2[3]};
+                if (__any(d2 != 0u)) { if (NT) __builtin_nontemporal_store(v, o2); else *o2 = v; }
+            }
+#pragma unroll
+            for (int c = 0; c < 3; c++) {
+                float* o3 = (float*)(buf + (size_t)(48 + 4 * c) * C) + i;
+                if (__any(__float_as_uint(n3[c]) != __float_as_uint(q3[r][c]))) { if (NT) __builtin_nontemporal_store(n3[c], o3); else *o3 = n3[c]; }
+            }
+        }
+    }
+}
+
 template <int R, int RD, int WR, bool STSHIFT = false>
 __global__ __launch_bounds__(256) void k_upd(const char* __restrict__ in, char* __restrict__ out, uint32_t n, uint32_t C, uint32_t shift, int K) {
     const uint32_t base = blockIdx.x * 256 * R;
@@ -225,7 +303,33 @@ double timeit(F f, int iters) {
     return ms * 1e-3 / iters;
 }
 
-int main() {
+// round 11: `tools/inplace cw` -- the component-write rows next to the 112-B row, interleaved, REPS rounds in one process
+static void component_writes() {
+    constexpr int REPS = 9, ITERS = 200;
+    for (uint32_t n : {1000000u, 16000000u}) {
+        const uint32_t C = (n + 1023) / 1024 * 1024 + 262144;
+        const size_t pb = (size_t)100 * C;
+        char *p0; CK(hipMalloc(&p0, pb)); CK(hipMemset(p0, 0, pb));
+        const dim3 g((n + 1023) / 1024), b(256);
+        for (int K : {0, 150}) {
+            for (int rep = 0; rep < REPS; rep++) {
+                double t;
+#define RUN_CW(KERNEL, wr, tag, ...) \
+                t = timeit([&](int i) { hipLaunchKernelGGL(KERNEL, g, b, 0, 0, p0, n, C, K, ##__VA_ARGS__); }, ITERS); \
+                printf("n=%8u K=%3d rep %d %-58s: %8.2f us  (r 56 B + w %2d B)\n", n, K, rep, tag, t * 1e6, wr);
+                RUN_CW((k_upd_s3<1, 0>), 56, "r6 row: Q2 float4, no test, 14 words written")
+                RUN_CW((k_upd_cw<0, 15, 7, 0>), 56, "Q2 float4, tests, all move: 14 words written", 0.0f)
+                RUN_CW((k_upd_cw<0, 10, 2, 0>), 48, "Q2 float4 written whole, Q3 x/z skipped: 12 words", 0.0f)
+                RUN_CW((k_upd_cw<1, 15, 7, 0>), 56, "Q2 four planes, tests, all move: 14 words written", 0.0f)
+                RUN_CW((k_upd_cw<1, 10, 2, 0>), 40, "Q2 four planes, Q2 x/z + Q3 x/z skipped: 10 words", 0.0f)
+            }
+        }
+        CK(hipFree(p0));
+    }
+}
+
+int main(int argc, char** argv) {
+    if (argc > 1 && argv[1][0] == 'c') { component_writes(); return 0; }
     for (uint32_t n : {1000000u, 4000000u, 16000000u}) {
         const uint32_t C = (n + 1023) / 1024 * 1024 + 262144;
         const size_t pb = (size_t)100 * C;
