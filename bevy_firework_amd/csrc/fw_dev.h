@@ -139,8 +139,10 @@ __device__ __forceinline__ uint4 fw_ld4u(const char *win, uint32_t byte_off) {
 __device__ __forceinline__ uint32_t fw_ld1u(const uint32_t *base, uint32_t idx) {
     return reinterpret_cast<const FW_GLOBAL uint32_t *>(reinterpret_cast<uintptr_t>(base))[idx];
 }
-// ---- component planes (round 6, fw_device.h; RING segments only -- FwSeg::cpl): the Q1 and Q3 regions of a ring's buffer hold their
-// four components as four 4-byte planes of C slots each -- x at +0, y at +4C, z at +8C, w at +12C bytes -- because `.w` of both (initial_scale, lifetime) never changes:
+// ---- component planes (round 6, fw_device.h; RING segments only -- FwSeg::cpl): the Q1 and Q3 regions of a ring's buffer -- and Q2 of a FIFO ring's -- hold their
+// four components as four 4-byte planes of C slots each -- x at +0, y at +4C, z at +8C, w at +12C bytes -- because `.w` of Q1 and Q3
+// (initial_scale, lifetime) never changes, and (round 12) because two components of the rotation of a particle that spins about a
+// coordinate axis never do either (FW_TYPE_IDX_AXIS, fw_device.h):
 // an in-place update loads and stores three dwords per lane and plane instead of a dwordx4 (tools/inplace.hip: the shapes follow the
 // bytes with scalar planes, 1M particles 16.6 -> 14.7 us, 16M 167.5 -> 147.5; packed float3 planes -- dwordx3 -- get SLOWER).
 // Segments on the compacting paths keep float4 planes: out of place everything moves anyway, and four dword accesses where one dwordx4
@@ -160,7 +162,7 @@ __device__ __forceinline__ void fw_stc4(char *reg, uint32_t C, uint32_t i, float
     const size_t cp = FW_CP(C);
     fw_st1(reg, i, v.x), fw_st1(reg + cp, i, v.y), fw_st1(reg + 2 * cp, i, v.z), fw_st1(reg + 3 * cp, i, v.w);
 }
-// element i of a Q1 / Q3 region in either layout (cpl: component planes) -- the readers
+// element i of a Q1 / Q2 / Q3 region in either layout (cpl: component planes) -- the readers
 __device__ __forceinline__ float4 fw_ldq(const char *reg, uint32_t C, uint32_t i, bool cpl) {
     return cpl ? fw_ldc4(reg, C, i) : fw_ld4(reg, i);
 }
@@ -214,7 +216,7 @@ __device__ __forceinline__ float fw_ldb1(fw_rsrc r, uint32_t byte_off) {
 }
 
 struct FwOutWin {  // output planes advanced to slot `first` (workgroup-uniform)
-    char *q0, *q1, *q2, *q3, *q5, *q6, *s4;  // (q1 / q3 of a ring -- component planes: the x plane advanced by 4 * first, `cp` bytes apart)
+    char *q0, *q1, *q2, *q3, *q5, *q6, *s4;  // (q1 / q2 / q3 of a ring -- component planes: the x plane advanced by 4 * first, `cp` bytes apart)
     size_t cp;
     uint32_t first;
     // A gradient with a single key (the reference's default emissive colour, core.rs:205) gives every particle of the
@@ -230,9 +232,9 @@ struct FwOutWin {  // output planes advanced to slot `first` (workgroup-uniform)
     bool wr4;  // scale plane (false, like wr5 / wr6, for a type whose instance records carry it: FW_TYPE_DERIVED)
 };
 __device__ __forceinline__ FwOutWin fw_out_window(char *ob, uint32_t C, uint32_t first, const FwType &T, uint32_t force_colors,
-                                                  uint32_t n_lplanes = 0u, bool cpl = false) {
+                                                  uint32_t n_lplanes = 0u, bool cpl = false, bool q2pl = false) {
     const size_t f16 = (size_t)first * 16u, f4 = (size_t)first * 4u, fq = cpl ? f4 : f16;
-    return FwOutWin{ob + FW_OFF_Q0(C) + f16, ob + FW_OFF_Q1(C) + fq, ob + FW_OFF_Q2(C) + f16, ob + FW_OFF_Q3(C) + fq,
+    return FwOutWin{ob + FW_OFF_Q0(C) + f16, ob + FW_OFF_Q1(C) + fq, ob + FW_OFF_Q2(C) + (q2pl ? f4 : f16), ob + FW_OFF_Q3(C) + fq,
                     ob + FW_OFF_Q5(C) + f16, ob + FW_OFF_Q6(C) + f16, ob + FW_OFF_S4(C) + f4, FW_CP(C), first,
                     (T.bc_kind != 0 || force_colors != 0u) && !(T.flags & FW_TYPE_DERIVED),
                     (T.em_kind != 0 || force_colors != 0u) && !(T.flags & FW_TYPE_DERIVED), !(T.flags & FW_TYPE_NOSPIN),
@@ -360,8 +362,8 @@ __device__ __forceinline__ void fw_store_new(const FwGlobals &g, const FwSeg &S,
     fw_gradient_sample(T.bc_kind, T.bc_n, keys + T.o_bc_t, keys + T.o_bc_v, 0.0f, bc);
     fw_gradient_sample(T.em_kind, T.em_n, keys + T.o_em_t, keys + T.o_em_v, 0.0f, em);
     fw_st4(buf + FW_OFF_Q0(C), slot, o.q0);
-    fw_stq(buf + FW_OFF_Q1(C), C, slot, o.q1, S.cpl != 0u);  // (a ring's Q1 / Q3: component planes)
-    fw_st4(buf + FW_OFF_Q2(C), slot, o.q2);
+    fw_stq(buf + FW_OFF_Q1(C), C, slot, o.q1, S.cpl != 0u);  // (a ring's Q1 / Q2 / Q3: component planes)
+    fw_stq(buf + FW_OFF_Q2(C), C, slot, o.q2, (S.cpl & 2u) != 0u);  // (bit 1: a FIFO ring -- the rotation in planes as well)
     fw_stq(buf + FW_OFF_Q3(C), C, slot, o.q3, S.cpl != 0u);
     if (T.flags & FW_TYPE_NOSPIN) fw_st1(buf + FW_OFF_L(C, S.n_lplanes), slot, o.q3.w);  // the lifetime plane (FwOutWin::lf)
     fw_st4(buf + FW_OFF_Q5(C), slot, make_float4(bc[0], bc[1], bc[2], bc[3]));
@@ -423,8 +425,8 @@ __device__ __forceinline__ fw_q4 fw_quat_step(fw_v3 v) {
 
 // INPLACE (FIFO segments, fw_k_update_fifo): the output slot is the input slot, so a plane whose new value is
 // bit-identical to the loaded one for every lane of the wave is not written (rotation and angular velocity of particles
-// that do not spin, the scale under a constant curve); the angular velocity, whose components are planes of their own, is
-// tested and skipped component by component (round 11); `full` marks a lane whose slot holds nothing yet (a particle
+// that do not spin, the scale under a constant curve); rotation and angular velocity, whose components are planes of their own, are
+// tested and skipped component by component (round 11, round 12); `full` marks a lane whose slot holds nothing yet (a particle
 // spawned this frame): it writes everything.
 // WM >= 0: which of the optional planes the launch writes is a compile-time fact (bit 0 base colour, 1 emissive, 2 scale)
 // wmode (INPLACE only): where the particle's two constants -- initial_scale in q1.w, lifetime in q3.w -- are.  FW_W_REGS: in the
@@ -433,7 +435,8 @@ __device__ __forceinline__ fw_q4 fw_quat_step(fw_v3 v) {
 // unless somebody needs the scale (a type whose planes are stored, an instance record, the boxes): then it is read here.
 enum { FW_W_REGS = 0, FW_W_MEM = 1, FW_W_MEM_LAZY = 2 };
 // CPL: the output segment is a ring -- Q1 / Q3 are component planes (the ring kernels; everybody else writes float4 planes)
-template <bool INPLACE = false, int WM = -1, int NT = 0, bool CPL = false>
+// Q2PL: ... and so is Q2 (a FIFO ring; a range ring keeps the rotation as a float4 plane: FwSeg::cpl bit 1)
+template <bool INPLACE = false, int WM = -1, int NT = 0, bool CPL = false, bool Q2PL = CPL>
 __device__ __forceinline__ void fw_integrate_store(const FwType &T, const float *s_keys, float dt, float4 q0, float4 q1,
                                                    float4 q2, float4 q3, float age_new, const FwOutWin &W, uint32_t o,
                                                    float4 *rec = nullptr, const fw_v3 *cpos = nullptr,
@@ -492,12 +495,20 @@ __device__ __forceinline__ void fw_integrate_store(const FwType &T, const float 
             if (full) fw_st1w<NT == 2>(W.q1 + 3 * W.cp, b4, q1.w);
             if (full && W.wr3) fw_st1w<NT == 2>(W.q3 + 3 * W.cp, b4, lifetime);
         }
-        const uint32_t d2 = (__float_as_uint(nr.x) ^ __float_as_uint(q2.x)) | (__float_as_uint(nr.y) ^ __float_as_uint(q2.y)) |
-                            (__float_as_uint(nr.z) ^ __float_as_uint(q2.z)) | (__float_as_uint(nr.w) ^ __float_as_uint(q2.w));
-        if (W.wr2 && __any(full || d2 != 0u)) fw_st4w<NT == 2>(W.q2, b16, make_float4(nr.x, nr.y, nr.z, nr.w));  // wave-uniform branches
-        // (round 11: the angular velocity's components live in planes of their own, so each one is tested -- and skipped -- by itself:
-        // particles that spin about a fixed axis, RandVec3 with spread 0 and no angular acceleration across it, keep a +0 in the other
-        // two for ever.  The same exact test, the same store per plane as fw_stc3w.)
+        // (rounds 11 / 12: the components of rotation and angular velocity live in planes of their own, so each one is tested -- and
+        // skipped -- by itself: particles that spin about a fixed axis, RandVec3 with spread 0 and no angular acceleration across it,
+        // keep a +0 in the other two of both for ever.  The same exact test, the same store per plane as fw_stc3w.  A segment under
+        // the axis rule -- FW_TYPE_IDX_AXIS -- did not even load those planes: its caller passed the +0 the host proved they hold.)
+        if constexpr (!Q2PL) {  // (the young part of a range ring: a float4 plane, written whole where any bit of it changed)
+            const uint32_t d2 = (__float_as_uint(nr.x) ^ __float_as_uint(q2.x)) | (__float_as_uint(nr.y) ^ __float_as_uint(q2.y)) |
+                                (__float_as_uint(nr.z) ^ __float_as_uint(q2.z)) | (__float_as_uint(nr.w) ^ __float_as_uint(q2.w));
+            if (W.wr2 && __any(full || d2 != 0u)) fw_st4w<NT == 2>(W.q2, b16, make_float4(nr.x, nr.y, nr.z, nr.w));
+        } else if (W.wr2) {  // wave-uniform branches
+            if (__any(full || __float_as_uint(nr.x) != __float_as_uint(q2.x))) fw_st1w<NT == 2>(W.q2, b4, nr.x);
+            if (__any(full || __float_as_uint(nr.y) != __float_as_uint(q2.y))) fw_st1w<NT == 2>(W.q2 + W.cp, b4, nr.y);
+            if (__any(full || __float_as_uint(nr.z) != __float_as_uint(q2.z))) fw_st1w<NT == 2>(W.q2 + 2 * W.cp, b4, nr.z);
+            if (__any(full || __float_as_uint(nr.w) != __float_as_uint(q2.w))) fw_st1w<NT == 2>(W.q2 + 3 * W.cp, b4, nr.w);
+        }
         if (W.wr3) {
             if (__any(full || __float_as_uint(wx) != __float_as_uint(q3.x))) fw_st1w<NT == 2>(W.q3, b4, wx);
             if (__any(full || __float_as_uint(wy) != __float_as_uint(q3.y))) fw_st1w<NT == 2>(W.q3 + W.cp, b4, wy);
@@ -509,7 +520,11 @@ __device__ __forceinline__ void fw_integrate_store(const FwType &T, const float 
         if ((WM >= 0 ? (WM & 2) != 0 : W.wr6) || fullk) fw_st4w<NT != 0>(W.q6, b16, make_float4(em[0], em[1], em[2], em[3]));
         if ((WM >= 0 ? (WM & 4) != 0 : (T.sc_kind != 0 && W.wr4)) || fullk) fw_st1w<NT != 0>(W.s4, (o - W.first) * 4u, scale);
     } else {
-        if (W.wr2) fw_st4w<NT == 2>(W.q2, b16, make_float4(nr.x, nr.y, nr.z, nr.w));
+        if constexpr (Q2PL) {
+            if (W.wr2) fw_stc4w<NT == 2>(W.q2, W.cp, b4, make_float4(nr.x, nr.y, nr.z, nr.w));
+        } else {
+            if (W.wr2) fw_st4w<NT == 2>(W.q2, b16, make_float4(nr.x, nr.y, nr.z, nr.w));
+        }
         if constexpr (CPL) {
             fw_st1w<NT == 2>(W.q1 + 3 * W.cp, b4, q1.w);  // (the old part of a range ring, its new particles: the constants are stored too)
             if (W.wr3) fw_stc4w<NT == 2>(W.q3, W.cp, b4, make_float4(wx, wy, wz, lifetime));

@@ -17,7 +17,9 @@
 //   Q3  float4 {angvel.x, .y, .z, lifetime}          offset  48*C   read+write
 //       (round 6, RING segments -- FwSeg::cpl: the Q1 and Q3 regions hold their four components as four planes of C floats each,
 //       4*C bytes apart: initial_scale and lifetime never change, an in-place update moves three dwords per lane, not a dwordx4;
-//       round 11: each component plane of Q3 is stored only in waves where that component's bits changed -- fw_integrate_store)
+//       round 11: each component plane of Q3 is stored only in waves where that component's bits changed -- fw_integrate_store;
+//       round 12: so is Q2 of a FIFO ring -- x | y | z | w planes, FwSeg::cpl bit 1, stored component by component -- and a ring whose particles
+//       all spin about one coordinate axis neither loads nor stores the two zero planes of Q2 and of Q3: FW_TYPE_IDX_AXIS)
 //   Q5  float4 base_color rgba                       offset  64*C   write only
 //   Q6  float4 emissive_color rgba                   offset  80*C   write only
 //   S4  float  scale                                 offset  96*C   write only
@@ -65,7 +67,8 @@ struct alignas(16) FwSeg {
     // nothing (offsets >= 0) and left `next` in the plane (core.rs:488-500): the spawning lane computes that value itself
     // (fw_init_last_emitted) and fw_k_spawn has nothing to materialise.
     uint32_t lplane_emit[2];
-    // 1: a RING segment (FIFO / range ring) -- its Q1 and Q3 regions are component planes (fw_dev.h: FW_CP); 0: float4 planes
+    // bit 0: a RING segment (FIFO / range ring) -- its Q1 and Q3 regions are component planes (fw_dev.h: FW_CP); bit 1: a FIFO ring -- Q2
+    // as well (a range ring keeps the rotation as a float4 plane: its kernel moves it whole); 0: float4 planes
     uint32_t cpl;
     uint32_t pad_[3];
 };
@@ -109,7 +112,13 @@ struct alignas(16) FwType {
 // lifetime except the consistency check, which the tile at the boundary to the old part runs for everybody: ages never increase along
 // the list, so if the oldest young particles cannot die nobody behind them can.  The other young tiles do not load it: 60 -> 56 B)
 #define FW_TYPE_IDX_NOLIFE 0x40000000u
-#define FW_TYPE_IDX_MASK 0x3FFFFFFFu
+// (FwFifoSeg::type_idx, round 12: bits 28-29 = k + 1 when every particle of the ring spins about coordinate axis k -- 1 x, 2 y, 3 z --
+// and this frame's dt is one the proof in fw_engine_build.cpp (axis_spin_rule) covers: the other two components of rotation and
+// angular velocity are +0 bit for bit before and after the update, so the ring's tiles neither load nor store those four planes.
+// Set per LAUNCH by the host, never stored: the planes hold the true values at all times and no reader looks at the bits.)
+#define FW_TYPE_IDX_AXIS_SHIFT 28
+#define FW_TYPE_IDX_AXIS 0x30000000u
+#define FW_TYPE_IDX_MASK 0x0FFFFFFFu
 // collision_settings of a particle type (core.rs:137-138, 240-248), in a table of its own next to FwType: only the
 // collision kernels read it, the streaming kernels' per-type record (and their scalar-register budget) stays as it was
 struct alignas(16) FwTypeColl {
@@ -180,7 +189,7 @@ struct alignas(16) FwNestOp {
     uint32_t parent_head;    // ring heads of the two segments (FIFO rings; 0 otherwise): particle i sits in slot
     uint32_t child_head;     // (head + i) mod capacity
     uint32_t parent_nospin;  // bit 0: the parent type cannot turn (FW_TYPE_NOSPIN): its rotation is parent_rot, not in the plane,
-                             // (bit 1: the parent segment is a ring -- its Q1 / Q3 are component planes, FwSeg::cpl)
+                             // (bit 1: the parent segment is a ring -- its Q1 / Q3 are component planes, FwSeg::cpl; bit 2: a FIFO ring -- Q2 too)
     uint32_t parent_life_plane;  // ... and its lifetimes sit in this 4-byte plane (FW_OFF_L index), not in Q3;
     float parent_life_const;     // 0xFFFFFFFF: the parent is a ring, all its particles have this lifetime
     float parent_rot[4];

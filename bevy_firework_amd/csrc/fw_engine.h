@@ -423,6 +423,13 @@ struct alignas(64) SegHost {
     // FW_TYPE_NOSPIN (fw_device.h): no particle of the type can turn; the rotation plane is neither read nor written
     bool nospin = false;
     float const_rot[4] = {0.f, 0.f, 0.f, 1.f};
+    // The axis-spin rule (fw_engine_build.cpp: axis_spin_rule; FW_TYPE_IDX_AXIS): 0, or k + 1 when every particle of the type spins
+    // about coordinate axis k.  launch_fifo sets the bits of a frame whose dt the proof covers (axis_dt_ok); the first frame that
+    // voids the proof, the caller rewriting the particles, or the ring leaving the FIFO kernel (fifo_to_general, fifo_to_range)
+    // clears the property for good: it is never set again after build_spawner.
+    uint32_t axis = 0;
+    float axis_wmax = 0.f;  // |angular velocity| of every particle of the type is at most this, for ever
+    float axis_drag = 0.f;  // the type's angular_drag (finite, >= +0)
     // ... and keeps its lifetimes in one more 4-byte plane behind the n_lplanes last_emitted_age planes instead of in Q3
     // (allocated with the type, kept when the type leaves the mode)
     uint32_t n_xplanes = 0;
@@ -492,7 +499,10 @@ struct alignas(64) SegHost {
     uint64_t gcoh_sum = 0;
     uint32_t rold_seen = 0;     // the old part's size as of the last exact read (refresh_counts_exact): FwGlobals::rold
     uint32_t r_young_main = 0;  // range_dev: young tiles the current table keeps in front (the rest: probably idle, at its end)
-    bool ring() const { return fifo || range; }  // one buffer, particle 0 not in slot 0
+    bool ring() const { return fifo || range; }
+    // FwSeg::cpl: bit 0 -- a ring, Q1 / Q3 in component planes; bit 1 -- a FIFO ring, the rotation (Q2) as well.  A range ring keeps Q2 as a
+    // float4 plane (fifo_to_range transposes it where it stands).
+    uint32_t cpl_bits() const { return ring() ? (fifo ? 3u : 1u) : 0u; }  // one buffer, particle 0 not in slot 0
     // FW_TYPE_DERIVED (fw_device.h): the planes S4 / Q5 / Q6 are not stored by the update; every reader evaluates scale and
     // colours from age / lifetime / initial_scale (an attached instance buffer receives them in its records).  Every type but
     // colliding ones and those whose curve keys exceed the LDS staging (fw_ctx::derive_all, wants_derived)
@@ -746,6 +756,7 @@ struct fw_ctx {
     bool use_fifo = true;      // FW_FIFO=0: constant-lifetime types take the general (compacting) path too (A/B, tests)
     bool fifo_nested = true;   // FW_FIFO_NESTED=0: ... those of spawners with Nested entries do (A/B)
     bool use_nospin = true;    // FW_NOSPIN=0: every type keeps its rotation plane (A/B)
+    bool use_axis = true;      // FW_AXIS_SPIN=0: no ring runs under the axis-spin rule (A/B in one build)
     bool use_derived = true;   // FW_DERIVED=0: every type stores its scale / colour planes, attached instance buffer or not (A/B)
     // Round 6: scale, base colour and emissive colour are pure functions of (age, lifetime, initial_scale) (core.rs:601-605,
     // 652-655) -- the update of EVERY type whose curves fit the LDS staging stops storing them (36 of the 100 B a configs[2]
@@ -1196,6 +1207,7 @@ bool fifo_may_become_range(const fw_ctx *ctx, const SegHost &S);
 fw_status fifo_to_range(fw_ctx *ctx, uint32_t si);
 fw_status spill_fifo_rings(fw_ctx *ctx);
 fw_status leave_nospin(fw_ctx *ctx, uint32_t si);
+bool axis_dt_ok(const SegHost &S, float dt);
 fw_status set_derived(fw_ctx *ctx, uint32_t si, bool on, bool refill = true);
 // does the type's update leave scale and colours to its readers?  (colliding types -- and `bigkeys` ones, which run on their
 // kernels -- stay as they are: the feature path reads the stored planes)

@@ -136,6 +136,7 @@ fw_status fw_ctx_create(int device, uint32_t seed, void *stream, fw_ctx **out) {
     if (const char *m = getenv("FW_RANGE_SMALL")) ctx->range_small_tiles = (uint32_t)strtoul(m, nullptr, 10);
     if (const char *m = getenv("FW_RANGE_YOUNG_BIG")) ctx->range_young_big = (uint32_t)strtoul(m, nullptr, 10);
     if (const char *m = getenv("FW_NOSPIN")) ctx->use_nospin = atoi(m) != 0;
+    if (const char *m = getenv("FW_AXIS_SPIN")) ctx->use_axis = atoi(m) != 0;
     // 0: scale / colour planes always stored; 1: not stored for types with an attached instance buffer; 2 (default): for no type
     if (const char *m = getenv("FW_DERIVED")) ctx->use_derived = atoi(m) != 0, ctx->derive_all = atoi(m) >= 2;
     if (const char *m = getenv("FW_NEST_FUSE")) ctx->nest_fuse = atoi(m) != 0;
@@ -464,7 +465,7 @@ static fw_status stage_buffer(fw_ctx *ctx, size_t bytes, void **out) {
 
 static fw_status read_records(fw_ctx *ctx, const char *buf, uint32_t cap_seg, uint32_t n, int32_t pbr, bool aos,
                               fw_particle *out, uint64_t cap, uint32_t head = 0, const float *const_rot = nullptr,
-                              uint32_t life_plane = 0xFFFFFFFFu, float life_const = 0.f, const FwType *derived = nullptr, bool cpl = false) {
+                              uint32_t life_plane = 0xFFFFFFFFu, float life_const = 0.f, const FwType *derived = nullptr, uint32_t cpl = 0u) {
     const uint64_t m = std::min<uint64_t>(n, cap);
     if (!m || !out) return FW_OK;
     if (aos) {
@@ -498,7 +499,7 @@ fw_status fw_spawner_read_particles(fw_ctx *ctx, fw_spawner h, uint32_t type, fw
     fw_status st2 = read_records(ctx, S.buf[ctx->parity], S.capacity, n, sp->types[type].ps.pbr, false, out, cap,
                                  ring_head_exact(S, n), S.nospin ? S.const_rot : nullptr,
                                  (S.nospin && !S.fifo) ? S.n_lplanes : 0xFFFFFFFFu, S.fifo_life,
-                                 S.derived ? ctx->d_types + S.type_idx : nullptr, S.ring());
+                                 S.derived ? ctx->d_types + S.type_idx : nullptr, S.cpl_bits());
     return st2 ? st2 : st;
 }
 
@@ -543,6 +544,7 @@ fw_status fw_spawner_write_particles(fw_ctx *ctx, fw_spawner h, uint32_t type, c
     if ((st = fifo_to_general(ctx, si))) return st;  // ages and lifetimes will be whatever the caller writes
     leave_small(ctx, ctx->segs[si]);                  // (any number of particles, any colours: the compacting kernels take it from here)
     if ((st = leave_nospin(ctx, si))) return st;      // ... and so will rotations and angular velocities
+    ctx->segs[si].axis = 0;                           // (... about any axis: the axis-spin rule is void for good)
     // ... and scales and colours: the planes are stored and read again until every particle has been through an update
     // (an attached buffer keeps receiving records; the mode comes back after the next step)
     if ((st = set_derived(ctx, si, false, false))) return st;
@@ -627,7 +629,7 @@ fw_status fw_spawner_pack_instances_device(fw_ctx *ctx, fw_spawner h, uint32_t t
     FW_HIP(ctx, fw_launch_pack_instances(ctx->stream, S.buf[ctx->parity], S.capacity, S.range ? S.young_lo : (S.fifo ? S.head : 0u),
                                          ctx->g.count + (size_t)ctx->parity * ctx->max_seg + si, ub, d_out,
                                          S.nospin ? S.const_rot : nullptr, S.range ? ctx->g.rold + (size_t)ctx->parity * ctx->max_seg + si : nullptr,
-                                         S.derived ? ctx->d_types + S.type_idx : nullptr, ctx->d_keys, S.life_plane(), S.fifo_life, S.ring()));
+                                         S.derived ? ctx->d_types + S.type_idx : nullptr, ctx->d_keys, S.life_plane(), S.fifo_life, S.cpl_bits()));
     return FW_OK;
 }
 
@@ -950,6 +952,10 @@ fw_status fw_debug_update_path(fw_ctx *ctx, fw_spawner h, uint32_t type, int32_t
         // (round 6: Q1 / Q3 are component planes -- velocity and angular velocity move as 12 bytes each way, the constants that
         // shared their float4, initial_scale and lifetime, stay where they are: every byte moved is algorithmic)
         moved = (S.nospin ? 28u : 56u) + 28u + q2 + (q3 ? 12u : 0u) + (T.scale.kind != 0 ? 4u : 0u) + colours;
+        // (round 12, a FIFO ring under the axis-spin rule -- SegHost::axis: of rotation and angular velocity only the axis' component
+        // and the rotation's w move: 8 + 4 bytes in, 8 out, 4 more where the drag changes the angular velocity.  The figure of a
+        // frame whose dt the rule covers; the range kernel loads every plane.)
+        if (S.fifo && S.axis != 0u) moved = 28u + 12u + 28u + (spins ? 8u : 0u) + (q3 ? 4u : 0u) + (T.scale.kind != 0 ? 4u : 0u) + colours;
         algo = moved;
         // (a range ring: the part of the list that may lose particles, a fifth of configs[2], is compacted in place and reads and
         // rewrites every plane it keeps, the 4-byte lifetime included: the figure is the young part's)

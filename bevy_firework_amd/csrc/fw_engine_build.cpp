@@ -109,6 +109,85 @@ void fill_randvec3(const fw_rand_vec3 &r, float &mn, float &mx, float &spread, f
     arc[0] = q.x, arc[1] = q.y, arc[2] = q.z, arc[3] = q.w;
 }
 
+// ---- The axis-spin rule (round 12; SegHost::axis, FW_TYPE_IDX_AXIS in fw_device.h) -------------------------------------------------
+// Decides, when a spawner is built, whether every particle of type t turns about ONE coordinate axis k for ever.  Then the other two
+// components -- call them a and b -- of its angular velocity and of its rotation are +0 (bits 0x00000000) after every update, and a
+// FIFO ring of the type neither loads nor stores those four planes (fw_update_fifo_body): it puts +0 in the registers and runs the
+// same fw_integrate_store, whose per-plane bit test then finds nothing to store.
+// Conditions (all tested below; "+0" always means the bit pattern, -0 fails):
+//   (C1) every entry that feeds the type: angular-velocity spread not > 0 (the `dir` arm of fw_randvec3), direction a and b +0,
+//        direction k finite, magnitude min and max finite with the sign bit clear;
+//   (C2) every such entry: initial_rotation a and b +0, k and w finite;
+//   (C3) the type: angular_acceleration a and b +0, k == 0; angular_drag finite with the sign bit clear;
+//   (C4) wmax = max over the entries of |dir k| * max(mag.min, mag.max) is finite;
+//   per frame (axis_dt_ok): dt finite with the sign bit clear, 0.25f * (wmax * dt)^2 < 0.6f in fp32, drag * dt <= 1.
+// Proof, for the arithmetic as compiled (fp32, round to nearest, no fast-math; -ffp-contract may fuse a product into the sum that
+// follows it, it never reorders sums).  Two facts about zeros are all it needs: (Z1) (+0) * p = +0 for finite p with the sign bit
+// clear, and (+0) * p is a zero of some sign for any finite p; (Z2) a sum -- fused or not -- of zeros, one of which is +0, is +0:
+// round to nearest gives -0 only when EVERY addend is -0, and x - y adds -y.
+//   Spawn (fw_spawn_one): m = u * (max - min) + min with u in [0, 1).  max - min is finite, the exact value lies between min and max,
+//   both >= +0, rounding is monotonic and an exact 0 from a non-trivial sum is +0; fused or not, m is finite with the sign bit clear
+//   (u = 0 and max < min give -0 + min with min > 0).  angular velocity = dir * m: components a, b are (+0) * m = +0 by Z1;
+//   |component k| <= |dir k| * max(min, max) <= wmax (monotonic rounding).  rotation = initial_rotation: a, b +0, k, w finite.
+//   Update, induction step (fw_integrate_store): assume w_a = w_b = +0, |w_k| <= wmax, q_a = q_b = +0, q_k and q_w finite.
+//   - v = w * dt: v_a = v_b = (+0) * dt = +0 (Z1: dt finite, sign clear -- a negative dt or -0 would give -0, hence the test).
+//   - fw_quat_step: h2 = 0.25 * (v_x^2 + v_y^2 + v_z^2); the two zero squares are +0 and add nothing, however the sum is fused, so
+//     h2 = 0.25 * fl(v_k^2) <= 0.25 * fl(fl(wmax * dt)^2) < 0.6 by monotonic rounding: EVERY lane of every wave of the ring takes the
+//     polynomial arm (the ballot is over lanes of this type only: every caller reaches fw_integrate_store under `if (alive)` /
+//     `if (mine)`, so the ballot sees the ring's own live lanes and nothing else -- a caller that ran it on unmasked lanes would void
+//     this step), the libm arm -- cos(h) < 0 there could make every addend of a sum
+//     below -0 -- is never entered.  On [0, 0.6) the polynomial values are sh in [0.45, 0.5] and c in [0.7, 1]: finite, positive.
+//     dq_a = dq_b = (+0) * sh = +0 (Z1), dq_k = v_k * sh finite, dq_w = c > 0.
+//   - fw_quat_mul(dq, q) (fw_math.h): the x, y and z sums each START with dq.w * q.<same component>.  For component a that is
+//     c * (+0) = +0 (Z1); the other three products each contain dq_a, dq_b, q_a or q_b -- a +0 times a finite number -- so they are
+//     zeros of some sign.  Sums are evaluated left to right, every partial sum contains that first +0: by Z2 each is +0, whichever
+//     products the compiler fuses.  The same for b.  So q'_a = q'_b = +0.  q'_k, q'_w stay finite: |q'| <= |q| (1 + 8 eps) per update,
+//     finite for more than 10^8 updates of one particle at worst-case rounding.
+//   - angular velocity, component a: w_a + (acc_a - drag * w_a) * dt.  drag * (+0) = +0 (Z1), (+0) - (+0) = +0, or fused
+//     fma(-drag, +0, +0) = (-0) + (+0) = +0 (Z2); (+0) * dt = +0; (+0) + (+0) = +0, or fma(+0, dt, +0) = +0.  The same for b.
+//     Component k: acc_k is a zero, t = drag * w_k * dt has the sign of w_k and |t| <= |w_k| (1 + 3 eps) since drag * dt <= 1,
+//     so |w_k - t| <= |w_k| <= wmax: the bound on h2 holds in every later frame.
+// `full` lanes (a particle's first update) and every spawn path store all planes, so the planes hold the true values -- the zeros
+// included -- at all times; readers never look at the rule, and a frame that runs without it loads what is there.  After such a
+// frame (libm arm, or a drag that overshoots) a plane may hold -0: the rule does not come back (launch_fifo).
+static uint32_t f32_bits(float x) {
+    uint32_t u;
+    memcpy(&u, &x, sizeof u);
+    return u;
+}
+static uint32_t axis_spin_rule(const fw_spawner_desc *d, uint32_t t, float *wmax_out) {
+    const fw_particle_settings &p = d->particle_settings[t];
+    if (!std::isfinite(p.angular_drag) || std::signbit(p.angular_drag)) return 0u;  // (C3)
+    for (uint32_t k = 0; k < 3; k++) {
+        const uint32_t a = (k + 1) % 3, b = (k + 2) % 3;
+        if (f32_bits(p.angular_acceleration[a]) != 0u || f32_bits(p.angular_acceleration[b]) != 0u || p.angular_acceleration[k] != 0.f) continue;
+        bool ok = true, fed = false;
+        float wmax = 0.f;
+        for (uint32_t i = 0; i < d->n_emission_settings && ok; i++) {
+            const fw_emission_settings &e = d->emission_settings[i];
+            if ((uint32_t)e.particle_index != t) continue;
+            fed = true;
+            const fw_rand_vec3 &w = e.initial_angular_velocity;
+            ok = !(w.spread > 0.f) && f32_bits(w.direction[a]) == 0u && f32_bits(w.direction[b]) == 0u && std::isfinite(w.direction[k]) &&
+                 std::isfinite(w.magnitude.min) && std::isfinite(w.magnitude.max) && !std::signbit(w.magnitude.min) && !std::signbit(w.magnitude.max) &&  // (C1)
+                 f32_bits(e.initial_rotation[a]) == 0u && f32_bits(e.initial_rotation[b]) == 0u && std::isfinite(e.initial_rotation[k]) &&
+                 std::isfinite(e.initial_rotation[3]);  // (C2)
+            if (ok) wmax = std::max(wmax, std::fabs(w.direction[k]) * std::max(w.magnitude.min, w.magnitude.max));
+        }
+        if (ok && fed && std::isfinite(wmax)) {  // (C4)
+            *wmax_out = wmax;
+            return k + 1u;
+        }
+    }
+    return 0u;
+}
+// the per-frame half of the rule: this dt keeps every particle of the ring inside the proof
+bool axis_dt_ok(const SegHost &S, float dt) {
+    if (!std::isfinite(dt) || std::signbit(dt)) return false;
+    const float v = S.axis_wmax * dt, h2 = 0.25f * (v * v);
+    return h2 < 0.6f && S.axis_drag * dt <= 1.0f;
+}
+
 uint32_t pad4(uint32_t n) { return (n + 3u) & ~3u; }
 
 // builds the device tables (types, keys, emits, segments) of one spawner
@@ -242,6 +321,8 @@ fw_status build_spawner(fw_ctx *ctx, int h, const fw_spawner_desc *d, const std:
         ctx->n_in_use++, ctx->big_dirty = true;
         S.keys_off = dt.keys_off, S.keys_len = dt.keys_len, S.keys_cap = kwin_cap, S.bigkeys = bigkeys;
         S.nospin = nospin, S.n_xplanes = nospin ? 1u : 0u;
+        if (ctx->use_axis && !nospin) S.axis = axis_spin_rule(d, t, &S.axis_wmax), S.axis_drag = p.angular_drag;
+        if (type_idx > FW_TYPE_IDX_MASK) return fail(ctx, FW_EINVAL, "more particle types than a type index holds");
         // scale and colours are left to the readers from the first frame on (fw_ctx::derive_all; wants_derived: not for a type that
         // runs on the collision kernels)
         S.derived = ctx->use_derived && ctx->derive_all && !(p.collision.enabled != 0 || bigkeys);

@@ -281,7 +281,7 @@ fw_status spawn_passes(fw_ctx *ctx, FwFrame &fr) {
                 op.parent_head = PS.fifo ? PS.head : (PS.range ? PS.young_lo : 0u);
                 op.child_head = CS.fifo ? CS.head : (CS.range ? CS.young_lo : 0u);
                 op.parent_range = PS.range ? 1u : 0u, op.child_range = CS.range ? 1u : 0u;
-                op.parent_nospin = (ctx->segs[op.parent_seg].nospin ? 1u : 0u) | (ctx->segs[op.parent_seg].ring() ? 2u : 0u);
+                op.parent_nospin = (ctx->segs[op.parent_seg].nospin ? 1u : 0u) | (ctx->segs[op.parent_seg].ring() ? 2u : 0u) | (ctx->segs[op.parent_seg].fifo ? 4u : 0u);
                 memcpy(op.parent_rot, ctx->segs[op.parent_seg].const_rot, sizeof op.parent_rot);
                 // (its lifetimes: the lifetime plane of a compacting segment, one value for a ring)
                 op.parent_life_plane = ctx->segs[op.parent_seg].fifo ? 0xFFFFFFFFu : ctx->segs[op.parent_seg].n_lplanes;
@@ -500,7 +500,9 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
         FwFifoSeg &F = fa.s[fa.n_segs++];
         F.buf = S.buf[0], F.destroyed = S.destroyed, F.inst = S.inst;
         F.inst_cap = S.inst_cap, F.capacity = S.capacity, F.seg = si;
-        F.type_idx = S.type_idx | (S.nospin ? FW_TYPE_IDX_NOSPIN : 0u), F.life = S.fifo_life;
+        // (the axis-spin rule travels per launch: a frame whose dt voids its proof runs without it, and so does every frame after it)
+        if (S.axis != 0u && !axis_dt_ok(S, dt)) S.axis = 0u;
+        F.type_idx = S.type_idx | (S.nospin ? FW_TYPE_IDX_NOSPIN : 0u) | (S.axis << FW_TYPE_IDX_AXIS_SHIFT), F.life = S.fifo_life;
         F.keys_off = S.keys_off, F.keys_len = S.keys_len;
         F.head = S.head, F.n_in = n_in, F.n_spawn = n_spawn, F.dead = dead;
         F.mat = mat ? 1u : 0u;

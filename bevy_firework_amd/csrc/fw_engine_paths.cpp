@@ -30,7 +30,7 @@ fw_status realloc_segment(fw_ctx *ctx, uint32_t si, uint32_t ncap, bool make_gen
     };
     const size_t OC = s.capacity, NC = ncap;
     FW_HIP(ctx, cp(FW_OFF_Q0(NC), FW_OFF_Q0(OC), 16));
-    // Q1 / Q3 of a RING are four component planes of 4-byte elements each (fw_device.h; their distance follows the capacity), of a segment
+    // Q1 / Q3 of a RING, and Q2 of a FIFO ring, are four component planes of 4-byte elements each (fw_device.h; their distance follows the capacity), of a segment
     // of the compacting path float4 planes: a ring that grows keeps its layout, one that leaves for that path is transposed as it is
     // unwrapped (hipMemcpy2D: rows of 4 bytes, 4 apart in the source, 16 apart in the destination)
     auto cpq = [&](size_t noff, size_t ooff) -> hipError_t {
@@ -48,7 +48,8 @@ fw_status realloc_segment(fw_ctx *ctx, uint32_t si, uint32_t ncap, bool make_gen
         return e;
     };
     FW_HIP(ctx, cpq(FW_OFF_Q1(NC), FW_OFF_Q1(OC)));
-    FW_HIP(ctx, cp(FW_OFF_Q2(NC), FW_OFF_Q2(OC), 16));
+    if (s.fifo) FW_HIP(ctx, cpq(FW_OFF_Q2(NC), FW_OFF_Q2(OC)));  // (a FIFO ring's rotation: planes; everybody else's: a float4 plane)
+    else FW_HIP(ctx, cp(FW_OFF_Q2(NC), FW_OFF_Q2(OC), 16));
     FW_HIP(ctx, cpq(FW_OFF_Q3(NC), FW_OFF_Q3(OC)));
     FW_HIP(ctx, cp(FW_OFF_Q5(NC), FW_OFF_Q5(OC), 16));
     FW_HIP(ctx, cp(FW_OFF_Q6(NC), FW_OFF_Q6(OC), 16));
@@ -119,6 +120,7 @@ bool nested_fed_wants_growth(const SegHost &S) {
 // continues as an ordinary segment
 fw_status fifo_to_general(fw_ctx *ctx, uint32_t si) {
     if (!ctx->segs[si].ring()) return FW_OK;
+    ctx->segs[si].axis = 0u;  // (the axis-spin rule is the FIFO kernel's: void for good once the ring leaves it)
     return realloc_segment(ctx, si, ctx->segs[si].capacity, true);
 }
 
@@ -207,6 +209,7 @@ fw_status fifo_to_range(fw_ctx *ctx, uint32_t si) {
     fw_status st = refresh_counts_exact(ctx);  // (a ring that receives Nested children: only the device knows its count)
     if (st) return st;
     SegHost &S = ctx->segs[si];
+    S.axis = 0u;  // (the axis-spin rule is the FIFO kernel's: the range kernel loads every plane)
     const TypeHost &T = ctx->spawners[S.spawner].types[S.type];
     ctx->fc_ok = false, ctx->boxes_epoch = 0;
     // ---- the ages of the frames its cohorts were born in: fw_ctx::birth_age holds one entry per frame, contiguous up to the
@@ -229,6 +232,17 @@ fw_status fifo_to_range(fw_ctx *ctx, uint32_t si) {
         }
         for (const SegHost::Cohort &c : S.coh)
             if (!B.empty() && c.frame >= B.front().frame && c.frame - B.front().frame < B.size()) B[(size_t)(c.frame - B.front().frame)].age = c.age;
+    }
+    // ---- the rotation: planes in a FIFO ring, a float4 plane in a range ring (whose kernel moves it whole: four dword accesses where
+    // one dwordx4 did cost it 1.3 %, profiles/r12).  Transposed where it stands, through a copy of the region: once per conversion.
+    {
+        const size_t C = S.capacity, q2 = FW_OFF_Q2(C);
+        HipBuf<char> tmp;
+        if ((st = sync(ctx)) || (st = alloc_buf(ctx, tmp, 16 * C))) return st;
+        FW_HIP(ctx, hipMemcpy(tmp, S.buf[0] + q2, 16 * C, hipMemcpyDeviceToDevice));
+        for (size_t c = 0; c < 4; c++)
+            FW_HIP(ctx, hipMemcpy2D(S.buf[0] + q2 + c * 4, 16, (const char *)tmp + c * 4 * C, 4, 4, C, hipMemcpyDeviceToDevice));
+        FW_HIP(ctx, hipDeviceSynchronize());
     }
     // ---- the ring's own bookkeeping
     S.fifo = false, ctx->n_fifo--;
@@ -271,6 +285,7 @@ fw_status fifo_to_range(fw_ctx *ctx, uint32_t si) {
         FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     ctx->tab_force = true, ctx->r_force = true;
+    if ((st = upload_seg(ctx, si))) return st;  // (FwSeg::cpl: the rotation is a float4 plane now)
     return ensure_range_arrays(ctx);
 }
 
@@ -290,7 +305,7 @@ fw_status leave_nospin(fw_ctx *ctx, uint32_t si) {
     if (!s.nospin) return FW_OK;
     fw_status st = sync(ctx);
     if (st) return st;
-    FW_HIP(ctx, fw_launch_fill_rotation(ctx->stream, s.buf[0], s.ring() ? nullptr : s.buf[1], s.capacity, s.const_rot));
+    FW_HIP(ctx, fw_launch_fill_rotation(ctx->stream, s.buf[0], s.ring() ? nullptr : s.buf[1], s.capacity, s.const_rot, s.fifo));
     FW_HIP(ctx, fw_launch_restore_q3(ctx->stream, s.buf[0], s.ring() ? nullptr : s.buf[1], s.capacity,
                                      s.fifo ? 0xFFFFFFFFu : s.n_lplanes, s.fifo_life, s.ring()));
     FW_HIP(ctx, hipStreamSynchronize(ctx->stream));

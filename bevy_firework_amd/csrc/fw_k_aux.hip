@@ -9,12 +9,12 @@
 // SoA planes -> fw_particle records (26 x 4 B)
 // (rot: the rotation of every particle of a type that cannot turn -- FW_TYPE_NOSPIN, its plane is not maintained -- or null)
 __global__ void fw_k_gather(const char *buf, uint32_t C, uint32_t head, uint32_t n, int32_t pbr, float *out, bool nospin, float4 rot,
-                            uint32_t life_plane, float life_const, const FwType *derived, const float *keys, bool cpl) {
+                            uint32_t life_plane, float life_const, const FwType *derived, const float *keys, uint32_t cpl) {  // (cpl: FwSeg::cpl -- bit 0 Q1 / Q3 in planes, bit 1 Q2 too)
     const uint32_t li = blockIdx.x * blockDim.x + threadIdx.x;
     if (li >= n) return;
     const uint32_t i = fw_ring_slot(head, li, C);
     const float4 q0 = fw_ld4(buf + FW_OFF_Q0(C), i), q1 = fw_ldq(buf + FW_OFF_Q1(C), C, i, cpl),
-                 q2 = nospin ? rot : fw_ld4(buf + FW_OFF_Q2(C), i),
+                 q2 = nospin ? rot : fw_ldq(buf + FW_OFF_Q2(C), C, i, (cpl & 2u) != 0u),
                  // (cannot turn: angular velocity 0; the lifetime from its plane, or -- a ring -- the type's one value)
                  q3 = !nospin ? fw_ldq(buf + FW_OFF_Q3(C), C, i, cpl)
                               : make_float4(0.0f, 0.0f, 0.0f, life_plane != 0xFFFFFFFFu ? fw_ld1(buf + FW_OFF_L(C, life_plane), i) : life_const),
@@ -77,11 +77,12 @@ hipError_t fw_launch_rederive(hipStream_t s, char *buf, uint32_t capacity, const
 }
 
 // a type leaves FW_TYPE_NOSPIN: its rotation plane, which nobody maintained, gets the constant rotation in every slot
-__global__ void fw_k_fill_rotation(char *buf0, char *buf1, uint32_t C, float4 rot) {
+// (cpl: a FIFO ring -- the rotation in component planes, fw_dev.h)
+__global__ void fw_k_fill_rotation(char *buf0, char *buf1, uint32_t C, float4 rot, bool cpl) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= C) return;
-    fw_st4(buf0 + FW_OFF_Q2(C), i, rot);
-    if (buf1) fw_st4(buf1 + FW_OFF_Q2(C), i, rot);
+    fw_stq(buf0 + FW_OFF_Q2(C), C, i, rot, cpl);
+    if (buf1) fw_stq(buf1 + FW_OFF_Q2(C), C, i, rot, cpl);
 }
 
 // a 4-byte plane filled with one value (the lifetime plane of a ring that becomes a compacting segment)
@@ -106,7 +107,7 @@ __global__ void fw_k_restore_q3(char *buf0, char *buf1, uint32_t C, uint32_t lif
 // its own record with four float4 stores would touch 64 lines a quarter at a time).
 __global__ __launch_bounds__(256) void fw_k_pack(const char *buf, uint32_t C, uint32_t head, const uint32_t *d_count,
                                                  uint32_t n_upper, float4 *out, bool nospin, float4 rot, const uint32_t *d_rold,
-                                                 const FwType *derived, const float *keys, uint32_t life_plane, float life_const, bool cpl) {
+                                                 const FwType *derived, const float *keys, uint32_t life_plane, float life_const, uint32_t cpl) {
     __shared__ float4 s_rec[256 * 4];
     // a range ring (d_rold: the size of its old part, FwGlobals::rold): `head` is the slot of the first young particle
     if (d_rold) head = fw_range_head(head, *d_rold, C);
@@ -116,7 +117,7 @@ __global__ __launch_bounds__(256) void fw_k_pack(const char *buf, uint32_t C, ui
         const uint32_t i = fw_ring_slot(head, min(b + tid, n - 1u), C);
         const float4 q0 = fw_ld4(buf + FW_OFF_Q0(C), i);
         float sc = fw_ld1(buf + FW_OFF_S4(C), i);
-        const float4 q2 = nospin ? rot : fw_ld4(buf + FW_OFF_Q2(C), i);
+        const float4 q2 = nospin ? rot : fw_ldq(buf + FW_OFF_Q2(C), C, i, (cpl & 2u) != 0u);
         float4 q5 = fw_ld4(buf + FW_OFF_Q5(C), i);
         float4 q6 = fw_ld4(buf + FW_OFF_Q6(C), i);
         if (derived) {  // FW_TYPE_DERIVED: the three planes are not maintained -- what the last update computed, again
@@ -326,7 +327,7 @@ __global__ __launch_bounds__(FW_BLOCK) void fw_k_copy(const float4 *src, float4 
 // ---- launch wrappers
 
 hipError_t fw_launch_gather(hipStream_t s, const char *buf, uint32_t capacity, uint32_t head, uint32_t n, int32_t pbr, void *d_out,
-                            const float *const_rot, uint32_t life_plane, float life_const, const FwType *derived, const float *keys, bool cpl) {
+                            const float *const_rot, uint32_t life_plane, float life_const, const FwType *derived, const float *keys, uint32_t cpl) {
     if (!n) return hipSuccess;
     const float4 rot = const_rot ? make_float4(const_rot[0], const_rot[1], const_rot[2], const_rot[3]) : make_float4(0.f, 0.f, 0.f, 1.f);
     hipLaunchKernelGGL(fw_k_gather, dim3((n + 255) / 256), dim3(256), 0, s, buf, capacity, head, n, pbr, (float *)d_out,
@@ -360,16 +361,16 @@ hipError_t fw_launch_restore_q3(hipStream_t s, char *buf0, char *buf1, uint32_t 
     return hipGetLastError();
 }
 
-hipError_t fw_launch_fill_rotation(hipStream_t s, char *buf0, char *buf1, uint32_t capacity, const float rot[4]) {
+hipError_t fw_launch_fill_rotation(hipStream_t s, char *buf0, char *buf1, uint32_t capacity, const float rot[4], bool cpl) {
     if (!capacity) return hipSuccess;
     hipLaunchKernelGGL(fw_k_fill_rotation, dim3((capacity + 255) / 256), dim3(256), 0, s, buf0, buf1, capacity,
-                       make_float4(rot[0], rot[1], rot[2], rot[3]));
+                       make_float4(rot[0], rot[1], rot[2], rot[3]), cpl);
     return hipGetLastError();
 }
 
 hipError_t fw_launch_pack_instances(hipStream_t s, const char *buf, uint32_t capacity, uint32_t head, const uint32_t *d_count,
                                     uint32_t n_upper, void *d_out, const float *const_rot, const uint32_t *d_rold, const FwType *derived,
-                                    const float *keys, uint32_t life_plane, float life_const, bool cpl) {
+                                    const float *keys, uint32_t life_plane, float life_const, uint32_t cpl) {
     if (!n_upper) return hipSuccess;
     uint32_t blocks = (n_upper + 255) / 256;
     if (blocks > 8192) blocks = 8192;

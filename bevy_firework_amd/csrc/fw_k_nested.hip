@@ -216,7 +216,7 @@ __global__ __launch_bounds__(FW_BLOCK) void fw_k_nest(FwGlobals g, FwNestInline 
                 s_par[wave][0][lane] = fw_ld4(pb + FW_OFF_Q0(PC), ps);
                 s_par[wave][1][lane] = fw_ldq(pb + FW_OFF_Q1(PC), PC, ps, (op.parent_nospin & 2u) != 0u);  // (the parent's velocity; a ring's Q1: component planes)
                 s_par[wave][2][lane] = (op.parent_nospin & 1u) ? make_float4(op.parent_rot[0], op.parent_rot[1], op.parent_rot[2], op.parent_rot[3])
-                                                        : fw_ld4(pb + FW_OFF_Q2(PC), ps);
+                                                        : fw_ldq(pb + FW_OFF_Q2(PC), PC, ps, (op.parent_nospin & 4u) != 0u);
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();

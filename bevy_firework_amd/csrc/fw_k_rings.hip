@@ -93,7 +93,7 @@ __device__ __forceinline__ void fw_fifo_nest_parents(const FwGlobals &g, const F
     char *pb = F.buf;
     // (window addressing as everywhere in this kernel: the tile's first slot on the scalar unit, 32-bit offsets per lane)
     const char *w0 = pb + FW_OFF_Q0(C) + (size_t)sbase * 16u, *w1 = pb + FW_OFF_Q1(C) + (size_t)sbase * 4u;  // (w1: component planes)
-    const char *w2 = pb + FW_OFF_Q2(C) + (size_t)sbase * 16u;
+    const char *w2 = pb + FW_OFF_Q2(C) + (size_t)sbase * 4u;  // (w2: component planes too)
     char *wl = pb + FW_OFF_L(C, N.parent_lplane) + (size_t)sbase * 4u;
     const bool pnospin = (F.type_idx & FW_TYPE_IDX_NOSPIN) != 0u;
     float p_age[R], p_lea[R];
@@ -107,7 +107,7 @@ __device__ __forceinline__ void fw_fifo_nest_parents(const FwGlobals &g, const F
     const uint32_t cbase = g.count[cidx] + g.spawned[cidx] + g.appended[cidx];  // first child slot of the entry (list index)
     const unsigned long long serial0 = g.emit_serial[N.emit_slot];
     const FwEmit &e = g.emits[N.emit];
-    const FwType Tc = g.types[Fc.type_idx & ~FW_TYPE_IDX_NOSPIN];
+    const FwType Tc = g.types[Fc.type_idx & FW_TYPE_IDX_MASK];
     for (uint32_t i = tid; i < Fc.keys_len; i += BLK) s_ckeys[i] = g.keys[Fc.keys_off + i];
 #pragma unroll
     for (int r = 0; r < R; r++) {
@@ -160,10 +160,10 @@ __device__ __forceinline__ void fw_fifo_nest_parents(const FwGlobals &g, const F
         __hip_atomic_store(&g.nest_status[tile], fw_pack_status(N.tag, FW_ST_INCL, incl64 > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)incl64), RLX, AGENT);
     if (tile_total == 0u) return;  // (workgroup-uniform: most tiles of a ring hold parents past their emission window)
     // ---- children, wave-cooperatively (parent-major order), spawned and given their first update
-    const FwOutWin Wc = fw_out_window(Fc.buf, Cc, 0u, Tc, 0u, 0u, true);  // (child capacity <= FW_RANGE_MAX_CAPACITY: 32-bit byte offsets, the host checks)
+    const FwOutWin Wc = fw_out_window(Fc.buf, Cc, 0u, Tc, 0u, 0u, true, true);  // (child capacity <= FW_RANGE_MAX_CAPACITY: 32-bit byte offsets, the host checks)
     float4 prot = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
     if (pnospin) {
-        const FwType &Tp = g.types[F.type_idx & ~FW_TYPE_IDX_NOSPIN];
+        const FwType &Tp = g.types[F.type_idx & FW_TYPE_IDX_MASK];
         prot = make_float4(Tp.const_rot[0], Tp.const_rot[1], Tp.const_rot[2], Tp.const_rot[3]);
     }
     uint32_t run = excl;  // children of the entry before (round r, wave 0)
@@ -181,7 +181,7 @@ __device__ __forceinline__ void fw_fifo_nest_parents(const FwGlobals &g, const F
             const uint32_t o16 = ((uint32_t)(r * BLK) + tid) * 16u;
             s_par[wave][0][lane] = fw_ld4w(w0, o16);
             s_par[wave][1][lane] = fw_ldc3w(w1, FW_CP(C), o16 / 4u, 0.0f);  // (the parent's velocity: core.rs:706-736)
-            s_par[wave][2][lane] = pnospin ? prot : fw_ld4w(w2, o16);
+            s_par[wave][2][lane] = pnospin ? prot : fw_ldc4w(w2, FW_CP(C), o16 / 4u);
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -268,7 +268,11 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
     // value -- neither the Q2 nor the Q3 plane is read (every lane asks for the tile's first slot instead: one line per
     // wave, loads stay unconditional)
     const bool nospin = (F.type_idx & FW_TYPE_IDX_NOSPIN) != 0u;
-    const uint32_t m2 = nospin ? 0u : 0xFFFFFFFFu;
+    // a ring under the axis rule (FW_TYPE_IDX_AXIS, fw_device.h: host-proved, per launch): of rotation and angular velocity only the
+    // axis' own component -- and the rotation's w -- is loaded; the other registers get the +0 their planes hold.  Workgroup-uniform
+    // branches, like nospin: no template parameter, one code for every axis.
+    const uint32_t axis = (F.type_idx & FW_TYPE_IDX_AXIS) >> FW_TYPE_IDX_AXIS_SHIFT;
+    const bool ldx = !nospin && (axis == 0u || axis == 1u), ldy = !nospin && (axis == 0u || axis == 2u), ldz = !nospin && (axis == 0u || axis == 3u);
     const float4 q3s = make_float4(0.0f, 0.0f, 0.0f, F.life);
     const bool defer = F.mat != 0u && F.n_in == 0xFFFFFFFFu;
     const uint32_t i1 = (uint32_t)(min(1, R - 1) * BLK + (int)tid) * 16u;
@@ -291,10 +295,10 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
         }
     }
     const size_t sfirst = (size_t)sbase * 16u, cp = FW_CP(C);
-    // (Q1 / Q3: component planes, fw_dev.h -- windows of the x plane, offsets of 4 bytes per slot.  A ring type has ONE lifetime value
+    // (Q1 / Q2 / Q3 of a FIFO ring: component planes, fw_dev.h -- windows of the x plane, offsets of 4 bytes per slot.  A ring type has ONE lifetime value
     // (F.life) and its initial_scale matters to instance records and destroyed records only: neither `.w` is loaded by the streaming loop)
     const char *iw0 = buf + FW_OFF_Q0(C) + sfirst, *iw1 = buf + FW_OFF_Q1(C) + sfirst / 4u;
-    const char *iw2 = buf + FW_OFF_Q2(C) + sfirst, *iw3 = buf + FW_OFF_Q3(C) + sfirst / 4u;
+    const char *iw2 = buf + FW_OFF_Q2(C) + sfirst / 4u, *iw3 = buf + FW_OFF_Q3(C) + sfirst / 4u;
     auto ld1 = [&](uint32_t o16) -> float4 {  // velocity (+ initial_scale when this launch writes instance records)
         if constexpr (INST) return fw_ldc4w<NT == 2>(iw1, cp, o16 / 4u);
         else return fw_ldc3w<NT == 2>(iw1, cp, o16 / 4u, 0.0f);
@@ -302,12 +306,17 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
     // (rotation and angular velocity of a type that cannot turn: not even dummy loads -- a workgroup-uniform branch)
     auto ld3 = [&](uint32_t o16) -> float4 {
         float4 v = q3s;
-        if (!nospin) v = fw_ldc3w<NT == 2>(iw3, cp, o16 / 4u, F.life);
+        if (ldx) v.x = fw_ld1w<NT == 2>(iw3, o16 / 4u);
+        if (ldy) v.y = fw_ld1w<NT == 2>(iw3 + cp, o16 / 4u);
+        if (ldz) v.z = fw_ld1w<NT == 2>(iw3 + 2 * cp, o16 / 4u);
         return v;
     };
     auto ld2 = [&](uint32_t o16) -> float4 {
         float4 v = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
-        if (!nospin) v = fw_ld4w<NT == 2>(iw2, o16);
+        if (ldx) v.x = fw_ld1w<NT == 2>(iw2, o16 / 4u);
+        if (ldy) v.y = fw_ld1w<NT == 2>(iw2 + cp, o16 / 4u);
+        if (ldz) v.z = fw_ld1w<NT == 2>(iw2 + 2 * cp, o16 / 4u);
+        if (!nospin) v.w = fw_ld1w<NT == 2>(iw2 + 3 * cp, o16 / 4u);
         return v;
     };
     if (!spawner && !defer) {
@@ -333,8 +342,8 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
         if (a.live_next) *a.live_next = 0ull;
         if (a.done_tag) *a.done_tag = a.done_value;
     }
-    const FwType T = g.types[F.type_idx & ~FW_TYPE_IDX_NOSPIN];
-    const FwCollArm CA = fw_coll_arm<COLL>(g, F.type_idx & ~FW_TYPE_IDX_NOSPIN);
+    const FwType T = g.types[F.type_idx & FW_TYPE_IDX_MASK];
+    const FwCollArm CA = fw_coll_arm<COLL>(g, F.type_idx & FW_TYPE_IDX_MASK);
     if (tid < F.keys_len) s_keys[tid] = key0;
     for (uint32_t i = tid + BLK; i < F.keys_len; i += BLK) s_keys[i] = g.keys[F.keys_off + i];
     __syncthreads();
@@ -347,7 +356,7 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
     }
     char *inst = INST ? F.inst : nullptr;
     float4 *s_inst_wave = s_inst + (INST ? wave * 256u : 0u);
-    const FwOutWin W = fw_out_window(buf, C, sbase, T, 0u, 0u, true);
+    const FwOutWin W = fw_out_window(buf, C, sbase, T, 0u, 0u, true, true);
     bool bad = false;
     if (spawner) {
         // ---- this frame's new particles: spawn_particles (core.rs:437-469) right before update_particles, each in the
@@ -398,7 +407,9 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
                 if (s < head) i += C;
                 if (i < n_dead && i < n_in) {
                     const uint32_t b16 = (uint32_t)(r * BLK + (int)tid) * 16u;
-                    const float4 q0 = fw_ld4w<NT == 2>(iw0, b16), q1 = fw_ldc4w<NT == 2>(iw1, cp, b16 / 4u), q2 = fw_ld4w<NT == 2>(iw2, b16 & m2);
+                    const float4 q0 = fw_ld4w<NT == 2>(iw0, b16), q1 = fw_ldc4w<NT == 2>(iw1, cp, b16 / 4u);
+                    // (the destroyed records read every plane: they hold the true values, axis rule or not)
+                    const float4 q2 = nospin ? make_float4(0.0f, 0.0f, 0.0f, 1.0f) : fw_ldc4w<NT == 2>(iw2, cp, b16 / 4u);
                     const float4 q3 = nospin ? q3s : fw_ldc4w<NT == 2>(iw3, cp, b16 / 4u);
                     // (a materialised particle that dies in its first update carries the spawn-time colours and scale, like any
                     // particle born and destroyed in one frame: evaluated, not read -- the planes of a FW_TYPE_DERIVED type
@@ -495,7 +506,7 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
 #define FW_FIFO_WAVES 1
 #endif
 template <bool INST, int WM, int NT = 0, int COLL = 0, int TR = FW_ROUNDS>
-__global__ __launch_bounds__(FW_BLOCK) __attribute__((amdgpu_waves_per_eu((!INST && !COLL && TR == FW_ROUNDS) ? FW_FIFO_WAVES : 1)))
+__global__ __launch_bounds__(FW_BLOCK) __attribute__((amdgpu_waves_per_eu((!INST && !COLL && TR == FW_ROUNDS) ? FW_FIFO_WAVES : (!INST && COLL == 1 && TR == 1) ? 4 : 1)))
 void fw_k_update_fifo(FwGlobals g, FwFifoArgs a, FwInlineOps inl) {
     fw_update_fifo_body<INST, WM, NT, COLL, TR, false>(g, a, inl);
 }
@@ -656,7 +667,7 @@ void fw_k_update_range(FwGlobals g, FwRangeArgs a) {
         if (a.done_tag) *a.done_tag = a.done_value;
     }
     const char *p0 = buf + FW_OFF_Q0(C), *p1 = buf + FW_OFF_Q1(C), *p2 = buf + FW_OFF_Q2(C), *p3 = buf + FW_OFF_Q3(C);
-    const size_t cp = FW_CP(C);  // (Q1 / Q3: component planes, fw_dev.h)
+    const size_t cp = FW_CP(C);  // (Q1 / Q3: component planes, fw_dev.h; Q2 of a range ring is a float4 plane -- FwSeg::cpl bit 1)
     // lifetimes: a plane of their own for a type that cannot turn (FwOutWin::lf), the w plane of Q3 otherwise
     const char *pl = nospin ? buf + FW_OFF_L(C, Sp->n_lplanes) : p3 + 3 * cp;
     char *inst = INST ? Sp->inst : nullptr;
@@ -728,7 +739,7 @@ void fw_k_update_range(FwGlobals g, FwRangeArgs a) {
             if (tid < keys_len) s_keys[tid] = key0;
             for (uint32_t i = tid + BLK; i < keys_len; i += BLK) s_keys[i] = g.keys[keys_off + i];
             __syncthreads();
-            const FwOutWin W = fw_out_window(buf, C, 0u, T, 0u, Sp->n_lplanes, true);
+            const FwOutWin W = fw_out_window(buf, C, 0u, T, 0u, Sp->n_lplanes, true, false);
             bool bad = false;
 #pragma unroll
             for (int r = 0; r < YR; r++) {
@@ -750,7 +761,7 @@ void fw_k_update_range(FwGlobals g, FwRangeArgs a) {
                 fw_v3 cpos, cvel;
                 fw_coll_step<COLL>(g, CA, mine, a.dt, q0v, q1v, &cpos, &cvel);
                 if (mine)
-                    fw_integrate_store<true, -1, NT, true>(T, s_keys, a.dt, q0v, q1v, q3v, q3v, age_new, W, s, rec, COLL ? &cpos : nullptr,
+                    fw_integrate_store<true, -1, NT, true, false>(T, s_keys, a.dt, q0v, q1v, q3v, q3v, age_new, W, s, rec, COLL ? &cpos : nullptr,
                                                      COLL ? &cvel : nullptr, nullptr, false, yi >= y_full, CA.on, WMODE);
                 if (INST) fw_range_inst_out<NT == 2>(inst, inst_cap, s_inst_wave, rec, lane, mi, rec0 + yi, false);
             }
@@ -781,7 +792,7 @@ void fw_k_update_range(FwGlobals g, FwRangeArgs a) {
         for (uint32_t i = tid + BLK; i < keys_len; i += BLK) s_keys[i] = g.keys[keys_off + i];
         __syncthreads();
         FW_STAMP(2, T.flags);  // type record + keys in LDS
-        const FwOutWin W = fw_out_window(buf, C, 0u, T, 0u, Sp->n_lplanes, true);
+        const FwOutWin W = fw_out_window(buf, C, 0u, T, 0u, Sp->n_lplanes, true, false);
         bool bad = false;
         FW_STAMP(6, __float_as_uint(q0c.w) | __float_as_uint(q1c.w));  // the first round's particles have arrived
 #pragma unroll
@@ -803,7 +814,7 @@ void fw_k_update_range(FwGlobals g, FwRangeArgs a) {
             fw_v3 cpos, cvel;
             fw_coll_step<COLL>(g, CA, mine, a.dt, q0c, q1c, &cpos, &cvel);
             if (mine)
-                fw_integrate_store<true, -1, NT, true>(T, s_keys, a.dt, q0c, q1c, q2c, q3c, age_new, W, s, rec, COLL ? &cpos : nullptr,
+                fw_integrate_store<true, -1, NT, true, false>(T, s_keys, a.dt, q0c, q1c, q2c, q3c, age_new, W, s, rec, COLL ? &cpos : nullptr,
                                                  COLL ? &cvel : nullptr, nullptr, false, yi >= y_full, CA.on, WMODE);
             if (INST) fw_range_inst_out<NT == 2>(inst, inst_cap, s_inst_wave, rec, lane, mi, rec0 + yi, false);
             q0c = q0n, q1c = q1n, q2c = q2n, q3c = q3n, lfc = lfn;
@@ -850,10 +861,10 @@ void fw_k_update_range(FwGlobals g, FwRangeArgs a) {
             const bool surv = fw_survives(so.q0.w, a.dt, so.q3.w, &age_new);
             if (!surv) fw_raise(g, 8u, seg, kk);
             // (the colour plane of a constant gradient holds that colour in every slot since the buffer was allocated)
-            const FwOutWin W = fw_out_window(buf, C, 0u, T, 0u, Sp->n_lplanes, true);
+            const FwOutWin W = fw_out_window(buf, C, 0u, T, 0u, Sp->n_lplanes, true, false);
             fw_v3 cpos, cvel;
             fw_coll_step<COLL>(g, CA, true, a.dt, so.q0, so.q1, &cpos, &cvel);
-            fw_integrate_store<false, -1, NT, true>(T, s_keys, a.dt, so.q0, so.q1, so.q2, so.q3, age_new, W, s, rec, COLL ? &cpos : nullptr,
+            fw_integrate_store<false, -1, NT, true, false>(T, s_keys, a.dt, so.q0, so.q1, so.q2, so.q3, age_new, W, s, rec, COLL ? &cpos : nullptr,
                                               COLL ? &cvel : nullptr, nullptr, false, false, CA.on);
             if (Sp->n_lplanes) fw_init_last_emitted(g, *Sp, buf, s, g.emits[op.emit].emission_index, so.q3.w);  // (other particles' entries emit from it)
         }
@@ -992,7 +1003,7 @@ void fw_k_update_range(FwGlobals g, FwRangeArgs a) {
     }
     if (tid == 0 && !withhold) __hip_atomic_store(&a.status[tile], fw_pack_status(a.epoch, FW_ST_INCL, excl + tile_surv), RLX, AGENT);
     const bool want_destroyed = T.report_destroyed && want_destroyed_any;
-    const FwOutWin W = fw_out_window(buf, C, 0u, T, 0u, Sp->n_lplanes, true);
+    const FwOutWin W = fw_out_window(buf, C, 0u, T, 0u, Sp->n_lplanes, true, false);
     uint32_t run = excl;
 #pragma unroll
     for (int r = 0; r < R; r++) {
@@ -1014,7 +1025,7 @@ void fw_k_update_range(FwGlobals g, FwRangeArgs a) {
         if (alive) {
             uint32_t s = bm1 - od;
             if (s >= C) s -= C;
-            fw_integrate_store<false, -1, NT, true>(T, s_keys, a.dt, q0[r], q1[r], old_q2(r), old_q3(r), age_new[r], W, s, rec, COLL ? &cpos : nullptr,
+            fw_integrate_store<false, -1, NT, true, false>(T, s_keys, a.dt, q0[r], q1[r], old_q2(r), old_q3(r), age_new[r], W, s, rec, COLL ? &cpos : nullptr,
                                               COLL ? &cvel : nullptr, nullptr, false, false, CA.on);
             if (nlp) {
 #pragma unroll

@@ -6,7 +6,7 @@
  * the measured roofline, in-kernel timestamps, and which update path a particle type is on.  They may change between
  * builds without an ABI version bump.
  *
- * Environment knobs.  The library reads A/B and debugging switches from the environment (FW_FIFO, FW_RANGE, FW_NOSPIN,
+ * Environment knobs.  The library reads A/B and debugging switches from the environment (FW_FIFO, FW_RANGE, FW_NOSPIN, FW_AXIS_SPIN,
  * FW_FORECAST, FW_UPDATE_MODE, FW_DEBUG, ...; DESIGN.md section 7 lists them) ONLY when FW_ENABLE_KNOBS=1 is set: a
  * product process never changes behaviour because of a stray variable.  The tests and the tools set it.
  */

@@ -150,8 +150,9 @@ __global__ __launch_bounds__(256) void k_upd_s3(char* __restrict__ buf, uint32_t
 // axis (0,1,0) four of the 14 maintained words keep their bits: Q2 x/z and Q3 x/z.  Does a cut of the WRITES alone shorten the kernel?
 // Q2P: Q2 as four scalar planes (else a float4, written whole when any component moved); M2 / M3: bit c = component c of Q2 / Q3 moves
 // (a mover adds a constant, so its bits change every launch; the others keep theirs).  Every store of Q2 / Q3 sits under the product's
-// test -- __any(new bits != loaded bits) -- so the rows carry its cost too.  All 14 words are read in every row.
-template <int Q2P, int M2, int M3, int NT>
+// test -- __any(new bits != loaded bits) -- so the rows carry its cost too.  All 14 words are read in every row, except with SK (round 12,
+// the axis-spin rule's shape): a component that does not move is not loaded either, its register gets z.
+template <int Q2P, int M2, int M3, int NT, int SK = 0>
 __global__ __launch_bounds__(256) void k_upd_cw(char* __restrict__ buf, uint32_t n, uint32_t C, int K, float z) {  // z: 0 at run time, unknown to the compiler
     constexpr int R = 4;
     const uint32_t base = blockIdx.x * 256 * R;
@@ -171,7 +172,8 @@ __global__ __launch_bounds__(256) void k_upd_cw(char* __restrict__ buf, uint32_t
 #pragma unroll
             for (int c = 0; c < 4; c++) {
                 const float* a2 = (const float*)(buf + (size_t)(32 + 4 * c) * C) + i;
-                q2[r][c] = NT ? __builtin_nontemporal_load(a2) : *a2;
+                if (SK && !(M2 >> c & 1)) q2[r][c] = z;
+                else q2[r][c] = NT ? __builtin_nontemporal_load(a2) : *a2;
             }
         } else {
             const f4v* a2 = (const f4v*)(buf + (size_t)32 * C) + i;
@@ -181,7 +183,8 @@ __global__ __launch_bounds__(256) void k_upd_cw(char* __restrict__ buf, uint32_t
 #pragma unroll
         for (int c = 0; c < 3; c++) {
             const float* a3 = (const float*)(buf + (size_t)(48 + 4 * c) * C) + i;
-            q3[r][c] = NT ? __builtin_nontemporal_load(a3) : *a3;
+            if (SK && !(M3 >> c & 1)) q3[r][c] = z;
+            else q3[r][c] = NT ? __builtin_nontemporal_load(a3) : *a3;
         }
     }
 #pragma unroll
@@ -322,6 +325,7 @@ static void component_writes() {
                 RUN_CW((k_upd_cw<0, 10, 2, 0>), 48, "Q2 float4 written whole, Q3 x/z skipped: 12 words", 0.0f)
                 RUN_CW((k_upd_cw<1, 15, 7, 0>), 56, "Q2 four planes, tests, all move: 14 words written", 0.0f)
                 RUN_CW((k_upd_cw<1, 10, 2, 0>), 40, "Q2 four planes, Q2 x/z + Q3 x/z skipped: 10 words", 0.0f)
+                RUN_CW((k_upd_cw<1, 10, 2, 0, 1>), 40, "... and not loaded either: r 40 B, the axis rule's 80 B", 0.0f)
             }
         }
         CK(hipFree(p0));
