@@ -69,6 +69,15 @@ class MeshCollider(C.Structure):
     _fields_ = [("mesh", C.c_int32), ("layers", C.c_uint32), ("position", C.c_float * 3), ("rotation", C.c_float * 4)]
 
 
+class Ray(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("max_distance", C.c_float), ("dir", C.c_float * 3), ("filter_mask", C.c_uint32)]
+
+
+class RayHit(C.Structure):
+    _fields_ = [("distance", C.c_float), ("normal", C.c_float * 3), ("kind", C.c_int32), ("index", C.c_uint32),
+                ("triangle", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 def make_mesh_colliders(instances):
     arr = (MeshCollider * max(len(instances), 1))()
     for d, m in zip(arr, instances):
@@ -241,6 +250,8 @@ SYMBOLS = [
     ("fw_ctx_mesh_update_status", C.c_int, [_P, C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_int64)]),
     ("fw_ctx_destroy_mesh", C.c_int, [_P, C.c_int32]),
     ("fw_ctx_set_mesh_colliders", C.c_int, [_P, C.POINTER(MeshCollider), C.c_uint32]),
+    ("fw_ctx_cast_rays", C.c_int, [_P, _P, C.c_uint64, _P]),
+    ("fw_ctx_cast_rays_device", C.c_int, [_P, _P, C.c_uint64, _P]),
     ("fw_spawner_create", C.c_int, [_P, C.POINTER(SpawnerDesc), C.POINTER(C.c_int32)]),
     ("fw_spawner_update_settings", C.c_int, [_P, C.c_int32, C.POINTER(SpawnerDesc)]),
     ("fw_spawner_destroy", C.c_int, [_P, C.c_int32]),

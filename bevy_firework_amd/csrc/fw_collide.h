@@ -222,10 +222,26 @@ FW_HD bool fw_ray_collider(const FwCollider &c, fw_v3 origin, fw_v3 dir, float m
     return true;
 }
 
+// WHO was hit (fw_ctx_cast_rays: fw_ray_hit::kind / index / triangle) is a policy of the cast: it is told each time the best hit
+// so far changes, and only then -- so what it holds at the end follows the tie rule of the cast itself.  The particles do not
+// ask (FwNoHitId: empty, the calls fold away and the cast compiles to what it was without them); the query kernel does
+// (FwHitId, fw_k_query.hip).
+struct FwNoHitId {
+    FW_HD void analytic(uint32_t) {}
+    FW_HD void triangle(uint32_t, uint32_t) {}
+};
+struct FwHitId {
+    int32_t kind = 0;  // FW_HIT_NONE / FW_HIT_COLLIDER / FW_HIT_MESH
+    uint32_t index = 0xFFFFFFFFu, tri = 0xFFFFFFFFu;
+    FW_HD void analytic(uint32_t i) { kind = 1, index = i, tri = 0xFFFFFFFFu; }
+    FW_HD void triangle(uint32_t m, uint32_t orig) { kind = 2, index = m, tri = orig; }
+};
+
 // SpatialQuery::cast_ray(origin, dir, max_distance, solid = true, filter): nearest hit, lowest index on ties; the analytic
 // colliders first, then the mesh instances (include/firework_hip.h: fw_mesh_collider has the semantics and the tie rule)
+template <class Id>
 FW_HD bool fw_cast_ray(const FwCollider *colliders, uint32_t n, const FwMeshInst *meshes, uint32_t n_mesh, uint32_t mask,
-                       fw_v3 origin, fw_v3 dir, float max_distance, FwRayHit *best) {
+                       fw_v3 origin, fw_v3 dir, float max_distance, FwRayHit *best, Id &id) {
     bool any = false;
     // (the best hit so far in scalars, written to *best once at the end: a struct updated through a pointer inside the loop
     // lived in scratch memory on the device)
@@ -249,6 +265,7 @@ FW_HD bool fw_cast_ray(const FwCollider *colliders, uint32_t n, const FwMeshInst
         if (fw_ray_collider(colliders[i], origin, dir, max_distance, &h) && (!any || h.distance < bd)) {
             bd = h.distance, bnx = h.normal.x, bny = h.normal.y, bnz = h.normal.z;
             any = true;
+            id.analytic(i);
         }
     }
     for (uint32_t m = 0; m < n_mesh; m++) {
@@ -313,6 +330,7 @@ FW_HD bool fw_cast_ray(const FwCollider *colliders, uint32_t n, const FwMeshInst
                     const uint32_t orig = __builtin_bit_cast(uint32_t, a.w);
                     if (!any || t < bd || (t == bd && borig != 0xFFFFFFFFu && orig < borig)) {
                         bd = t, any = true, bslot = k, borig = orig;
+                        id.triangle(m, orig);
                     }
                 }
             }
@@ -328,6 +346,11 @@ FW_HD bool fw_cast_ray(const FwCollider *colliders, uint32_t n, const FwMeshInst
     }
     *best = FwRayHit{bd, fw_v3{bnx, bny, bnz}};
     return any;
+}
+FW_HD bool fw_cast_ray(const FwCollider *colliders, uint32_t n, const FwMeshInst *meshes, uint32_t n_mesh, uint32_t mask,
+                       fw_v3 origin, fw_v3 dir, float max_distance, FwRayHit *best) {
+    FwNoHitId id;
+    return fw_cast_ray(colliders, n, meshes, n_mesh, mask, origin, dir, max_distance, best, id);
 }
 
 // particle_collision (src/core.rs:744-800).  Returns should_destroy; *pos / *vel are updated in place.

@@ -26,6 +26,7 @@
 //   fw_engine_mesh.cpp   the collider meshes: fw_ctx_create_mesh / fw_ctx_create_deformable_mesh / fw_ctx_update_mesh_vertices /
 //                        fw_ctx_destroy_mesh / fw_ctx_set_mesh_colliders (the
 //                        hierarchy itself is built by fw_bvh.cpp, plain C++)
+//   fw_engine_query.cpp  the ray-cast query into the collider world: fw_ctx_cast_rays / fw_ctx_cast_rays_device
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -1007,6 +1008,9 @@ struct fw_ctx {
     HipEvent ev_mesh[2];
     bool mesh_pending[2] = {false, false};
     uint64_t mesh_seq = 0;
+    // the host form of the ray-cast query (fw_engine_query.cpp): pinned staging and device buffers for rays and hits, 32 bytes per
+    // record each, grown on demand and kept; the device form needs nothing of its own
+    HipBuf<float4> h_rays, h_hits, d_rays, d_hits;
     HipBuf<float> d_aabb;      // 256 partial boxes of the AABB query
     HipBuf<float> h_aabb;      // pinned result {min.xyz, any, max.xyz, -}
     HipBuf<unsigned long long> d_total;

@@ -1,0 +1,50 @@
+// fw_k_query.hip -- the public ray-cast query (fw_ctx_cast_rays / fw_ctx_cast_rays_device): a batch of rays in, nearest hits out,
+// against the context's device-resident collider world.  One ray per lane, workgroups of FW_QUERY_BLOCK; a ray is two 16-byte
+// loads (fw_ray), a hit two 16-byte stores (fw_ray_hit).
+//
+// The cast is fw_cast_ray of fw_collide.h itself -- the function the update kernels call -- instantiated with the identity
+// policy FwHitId, so distance and normal are what a particle gets for the same ray and kind / index / triangle follow the
+// cast's own tie rule (the policy is told when the best hit changes, and only then).
+//
+// What differs from the particle kernels: the filter mask is per LANE.  fw_cast_ray tests `layers & mask` in front of the wave
+// skip's __ballot, so here that branch diverges; the ballot then counts the lanes that passed it and no others -- __ballot
+// reports active lanes only -- which is exactly "no ray that takes part can reach this collider".  Lanes past n leave before the
+// first load: they are inactive for the whole cast, so they load nothing, store nothing and keep no collider alive for the rest
+// of their wave.  Nothing here waits for another workgroup and there is no barrier, so the early exit is safe.
+#include <hip/hip_runtime.h>
+
+#include "fw_kernels.h"
+
+#define FW_QUERY_BLOCK 256
+#define FW_QUERY_MAX_LAUNCH (1ull << 30)  // rays per launch: lane indices and the grid stay well inside 32 bits
+
+template <bool MESH>
+__global__ __launch_bounds__(FW_QUERY_BLOCK) void fw_k_cast_rays(const FwCollider *colliders, uint32_t n_colliders, const FwMeshInst *meshes,
+                                                                 uint32_t n_mesh, const float4 *rays, uint32_t n, float4 *hits) {
+    const uint32_t i = blockIdx.x * FW_QUERY_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const float4 a = rays[2 * (size_t)i], b = rays[2 * (size_t)i + 1];  // {origin, max_distance}, {dir, filter_mask}
+    FwRayHit h;
+    FwHitId id;
+    fw_cast_ray(colliders, n_colliders, MESH ? meshes : nullptr, MESH ? n_mesh : 0u, __builtin_bit_cast(uint32_t, b.w), fw_v3{a.x, a.y, a.z},
+                fw_v3{b.x, b.y, b.z}, a.w, &h, id);
+    // (a miss: the cast never touched its best slot or the policy -- distance 0, normal 0, kind FW_HIT_NONE, index = triangle = ~0)
+    hits[2 * (size_t)i] = float4{h.distance, h.normal.x, h.normal.y, h.normal.z};
+    hits[2 * (size_t)i + 1] = float4{__builtin_bit_cast(float, id.kind), __builtin_bit_cast(float, id.index), __builtin_bit_cast(float, id.tri),
+                                     __builtin_bit_cast(float, 0u)};
+}
+
+hipError_t fw_launch_cast_rays(hipStream_t s, const FwGlobals &g, const void *d_rays, uint64_t n, void *d_hits) {
+    const bool mesh = g.n_mesh_inst != 0u;  // (no instances: the form without the mesh loop, as the update kernels pick theirs)
+    for (uint64_t first = 0; first < n; first += FW_QUERY_MAX_LAUNCH) {
+        const uint32_t cnt = (uint32_t)(n - first < FW_QUERY_MAX_LAUNCH ? n - first : FW_QUERY_MAX_LAUNCH);
+        const float4 *rays = static_cast<const float4 *>(d_rays) + 2 * first;
+        float4 *hits = static_cast<float4 *>(d_hits) + 2 * first;
+        const dim3 grid((cnt + FW_QUERY_BLOCK - 1) / FW_QUERY_BLOCK), block(FW_QUERY_BLOCK);
+        if (mesh)
+            hipLaunchKernelGGL(fw_k_cast_rays<true>, grid, block, 0, s, g.colliders, g.n_colliders, g.mesh_inst, g.n_mesh_inst, rays, cnt, hits);
+        else
+            hipLaunchKernelGGL(fw_k_cast_rays<false>, grid, block, 0, s, g.colliders, g.n_colliders, g.mesh_inst, 0u, rays, cnt, hits);
+    }
+    return hipGetLastError();
+}

@@ -1,5 +1,6 @@
 // fw_kernels.h -- launch interface between the host engine (fw_engine.h, fw_engine_*.cpp) and the
-// gfx950 kernels (fw_k_general.hip, fw_k_rings.hip, fw_k_nested.hip, fw_k_aux.hip; shared device helpers: fw_dev.h).
+// gfx950 kernels (fw_k_general.hip, fw_k_rings.hip, fw_k_nested.hip, fw_k_aux.hip, fw_k_refit.hip, fw_k_query.hip; shared device
+// helpers: fw_dev.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -419,3 +420,6 @@ hipError_t fw_launch_mesh_bounds(hipStream_t s, const float *d_xyz, const uint8_
 // after_update: nothing when the record says the latest update was rejected
 hipError_t fw_launch_mesh_spheres(hipStream_t s, FwMeshInst *d_inst, uint32_t n_inst, const float4 *nodes, const FwMeshRecord *d_rec,
                                   bool after_update);
+// The ray-cast query (fw_k_query.hip; fw_ctx_cast_rays[_device]): n fw_ray records at d_rays -> n fw_ray_hit records at d_hits, both
+// device memory, against g's collider world as of the launch's place in stream s (launches of at most 2^30 rays each).
+hipError_t fw_launch_cast_rays(hipStream_t s, const FwGlobals &g, const void *d_rays, uint64_t n, void *d_hits);

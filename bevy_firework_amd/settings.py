@@ -382,3 +382,26 @@ INSTANCE_DTYPE = np.dtype(
     ]
 )
 assert INSTANCE_DTYPE.itemsize == 64
+
+# fw_ray / fw_ray_hit (include/firework_hip.h): the records of ParticleSystem.cast_rays
+RAY_DTYPE = np.dtype(
+    [
+        ("origin", np.float32, 3),
+        ("max_distance", np.float32),
+        ("dir", np.float32, 3),
+        ("filter_mask", np.uint32),
+    ]
+)
+assert RAY_DTYPE.itemsize == 32
+HIT_NONE, HIT_COLLIDER, HIT_MESH = 0, 1, 2
+RAY_HIT_DTYPE = np.dtype(
+    [
+        ("distance", np.float32),
+        ("normal", np.float32, 3),
+        ("kind", np.int32),
+        ("index", np.uint32),
+        ("triangle", np.uint32),
+        ("reserved", np.uint32),
+    ]
+)
+assert RAY_HIT_DTYPE.itemsize == 32

@@ -272,6 +272,35 @@ class ParticleSystem:
         """Replaces the placed meshes (settings.MeshCollider) of the collider world; all-or-nothing, no synchronisation."""
         self._check(self._lib.fw_ctx_set_mesh_colliders(self._ctx, _ffi.make_mesh_colliders(instances), len(instances)))
 
+    def cast_rays(self, origins, dirs, max_distances, masks) -> np.ndarray:
+        """SpatialQuery::cast_ray for a batch: origins [n, 3], dirs [n, 3] (used as given: pass unit vectors for distances in
+        world units), max_distances [n] or a scalar, masks [n] or a scalar (as ParticleCollisionSettings.filter_mask) -> a
+        structured array (settings.RAY_HIT_DTYPE) of the nearest hit of each ray in the collider world as it stands behind
+        every call made so far: distance and normal are bit for bit what a particle's own cast gives, kind / index / triangle
+        name what was hit (settings.HIT_*; index counts in the list given to set_colliders / set_mesh_colliders).
+        Synchronises."""
+        o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+        rays = np.zeros(len(o), dtype=S.RAY_DTYPE)
+        rays["origin"] = o
+        rays["dir"] = np.asarray(dirs, dtype=np.float32).reshape(-1, 3)
+        rays["max_distance"] = np.asarray(max_distances, dtype=np.float32)
+        rays["filter_mask"] = np.asarray(masks, dtype=np.uint32)
+        return self.cast_ray_records(rays)
+
+    def cast_ray_records(self, rays: np.ndarray) -> np.ndarray:
+        """cast_rays for rays that are already settings.RAY_DTYPE records"""
+        rays = np.ascontiguousarray(rays, dtype=S.RAY_DTYPE)
+        hits = np.zeros(len(rays), dtype=S.RAY_HIT_DTYPE)
+        self._check(self._lib.fw_ctx_cast_rays(self._ctx, rays.ctypes.data_as(C.c_void_p), len(rays), hits.ctypes.data_as(C.c_void_p)))
+        return hits
+
+    def cast_rays_device(self, rays_ptr: int, n: int, hits_ptr: int) -> None:
+        """cast_rays for n settings.RAY_DTYPE records at device address rays_ptr into n settings.RAY_HIT_DTYPE records at
+        hits_ptr (torch tensors' data_ptr()): enqueued on this context's stream, never synchronises; the buffers are read and
+        written only by work enqueued inside the call."""
+        self._check(self._lib.fw_ctx_cast_rays_device(self._ctx, C.c_void_p(int(rays_ptr)) if rays_ptr else None, int(n),
+                                                      C.c_void_p(int(hits_ptr)) if hits_ptr else None))
+
     # -- ECS-like surface ------------------------------------------------------------------------
     def spawn(self, spawner: S.ParticleSpawner, transform: Optional[S.Transform] = None,
               global_transform: Optional[S.Transform] = None, modifier: Optional[S.EffectModifier] = None,

@@ -4,7 +4,9 @@
 // mesh placed twice, the set replaced and a mesh destroyed half way), and with `deform` against the same meshes created deformable,
 // their vertices moved every fifth frame (create_deformable_mesh / update_mesh_vertices); `deform_device` is `deform` with the new
 // vertices handed over in DEVICE memory (update_mesh_vertices_device: copied there on the context's stream, no wait) and one more
-// line, the device's verdict on the sheet's updates (mesh_update_status).  Prints, every tenth frame, the live counts and an
+// line, the device's verdict on the sheet's updates (mesh_update_status); `query` is `mesh` with a batch of 512 rays cast into the
+// collider world behind every tenth frame (cast_rays, and cast_rays_device through device buffers of its own) and one more line
+// per such frame: the rays that hit something and the digest of the hit records of either form.  Prints, every tenth frame, the live counts and an
 // FNV-1a digest of every particle record; tests/test_cpp_host.py runs the same scenario through the Python mirror and
 // expects the same lines: both mirrors marshal the reference's settings into the C ABI the same way.
 //
@@ -31,7 +33,9 @@ int main(int argc, char **argv) {
     // `mirror_check deform_device`: ... with those vertices taken from device memory
     const bool deform_device = argc > 1 && std::strcmp(argv[1], "deform_device") == 0;
     const bool deform = deform_device || (argc > 1 && std::strcmp(argv[1], "deform") == 0);
-    const bool with_meshes = deform || (argc > 1 && std::strcmp(argv[1], "mesh") == 0);
+    // `mirror_check query`: the `mesh` scenario, and ray-cast queries into its collider world
+    const bool query = argc > 1 && std::strcmp(argv[1], "query") == 0;
+    const bool with_meshes = deform || query || (argc > 1 && std::strcmp(argv[1], "mesh") == 0);
     try {
         ParticleSystemPlugin app(0, /*seed*/ 0x00C0FFEE);
         // new vertices of a deformable mesh, in host memory or (deform_device) through a device buffer of their own per update --
@@ -47,6 +51,19 @@ int main(int argc, char **argv) {
                 throw Error(FW_EHIP, "hipMemcpyAsync");
             app.update_mesh_vertices_device(m, d, (uint32_t)(xyz.size() / 3));
         };
+        // the rays of `query`: a grid 3 above the scene, straight down and slanted by turns, the three filter masks by turns (every
+        // operand exact in fp32)
+        std::vector<fw_ray> rays(query ? 512 : 0);
+        for (size_t i = 0; i < rays.size(); i++) {
+            fw_ray &r = rays[i];
+            r.origin[0] = -3.0f + (float)(i % 32) * 0.1875f, r.origin[1] = 3.0f, r.origin[2] = -3.0f + (float)(i / 32) * 0.375f;
+            r.max_distance = 6.0f;
+            r.dir[0] = i % 2 ? 0.6f : 0.0f, r.dir[1] = i % 2 ? -0.8f : -1.0f, r.dir[2] = 0.0f;
+            r.filter_mask = 1u + (uint32_t)(i % 3);
+        }
+        void *d_rays = nullptr, *d_hits = nullptr;
+        if (query && (hipMalloc(&d_rays, rays.size() * sizeof(fw_ray)) != hipSuccess || hipMalloc(&d_hits, rays.size() * sizeof(fw_ray_hit)) != hipSuccess))
+            throw Error(FW_EHIP, "hipMalloc");
         app.track_aabbs(true);
         app.set_colliders({Collider::Plane({0.0f, -1.0f, 0.0f}, {0.0f, 1.0f, 0.0f}), Collider::Sphere({1.0f, 0.5f, 0.0f}, 0.75f, 2u),
                            Collider::Box({-2.0f, 0.0f, 0.0f}, {0.5f, 1.0f, 0.5f}, Quat{0.0f, 0.38268343f, 0.0f, 0.92387953f})});
@@ -146,6 +163,22 @@ int main(int argc, char **argv) {
             const bool any = d->aabb(mn, mx);
             const float box[6] = {mn.x, mn.y, mn.z, mx.x, mx.y, mx.z};
             std::printf(" aabb %d %016llx active %d\n", any ? 1 : 0, (unsigned long long)fnv(box, sizeof box), d->active() ? 1 : 0);
+            if (query) {
+                const std::vector<fw_ray_hit> hits = app.cast_rays(rays);
+                std::vector<fw_ray_hit> from_device(rays.size());
+                hipStream_t st = (hipStream_t)app.stream();
+                if (hipMemcpyAsync(d_rays, rays.data(), rays.size() * sizeof(fw_ray), hipMemcpyHostToDevice, st) != hipSuccess)
+                    throw Error(FW_EHIP, "hipMemcpyAsync");
+                app.cast_rays_device(d_rays, rays.size(), d_hits);
+                if (hipMemcpyAsync(from_device.data(), d_hits, rays.size() * sizeof(fw_ray_hit), hipMemcpyDeviceToHost, st) != hipSuccess)
+                    throw Error(FW_EHIP, "hipMemcpyAsync");
+                app.synchronize();
+                unsigned n_coll = 0, n_mesh = 0;
+                for (const fw_ray_hit &h : hits) n_coll += h.kind == FW_HIT_COLLIDER, n_mesh += h.kind == FW_HIT_MESH;
+                std::printf("query frame %d colliders %u meshes %u host %016llx device %016llx\n", fr, n_coll, n_mesh,
+                            (unsigned long long)fnv(hits.data(), hits.size() * sizeof(fw_ray_hit)),
+                            (unsigned long long)fnv(from_device.data(), from_device.size() * sizeof(fw_ray_hit)));
+            }
         }
         std::printf("destroyed reported %llu\n", (unsigned long long)destroyed_seen);
         if (deform_device) {
@@ -154,6 +187,7 @@ int main(int argc, char **argv) {
             std::printf("sheet device updates %llu %llu %lld\n", (unsigned long long)s.applied, (unsigned long long)s.rejected, (long long)s.first_bad_vertex);
             for (void *d : device_buffers) (void)hipFree(d);
         }
+        if (query) (void)hipFree(d_rays), (void)hipFree(d_hits);
     } catch (const Error &e) {
         std::fprintf(stderr, "firework error %d: %s\n", (int)e.status, e.what());
         return 1;

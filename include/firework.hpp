@@ -415,6 +415,16 @@ class ParticleSystemPlugin {
         }
         check(fw_ctx_set_mesh_colliders(ctx_, v.data(), (uint32_t)v.size()));
     }
+    // SpatialQuery::cast_ray for a batch (fw_ctx_cast_rays): the nearest hit of every ray in the collider world as it stands behind
+    // the calls made so far -- distance and normal are what a particle's own cast gives, kind / index / triangle name what was hit
+    // (index: position in the vector given to set_colliders / set_mesh_colliders).  Waits for the result.
+    std::vector<fw_ray_hit> cast_rays(const std::vector<fw_ray> &rays) {
+        std::vector<fw_ray_hit> hits(rays.size());
+        check(fw_ctx_cast_rays(ctx_, rays.data(), (uint64_t)rays.size(), hits.data()));
+        return hits;
+    }
+    // ... rays and hits in device memory (n fw_ray at d_rays, n fw_ray_hit at d_hits), enqueued on stream(): never waits
+    void cast_rays_device(const void *d_rays, uint64_t n, void *d_hits) { check(fw_ctx_cast_rays_device(ctx_, d_rays, n, d_hits)); }
 
     // update_aabbs (render.rs:677-703) fused into the update: every frame leaves per-tile boxes, ParticleSpawnerData::aabb
     // folds them instead of re-reading the particles

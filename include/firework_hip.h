@@ -85,7 +85,8 @@ typedef struct fw_gradient { int32_t kind; int32_t n; const float *times; const 
 /* ParticleCollisionSettings (core.rs:240-248, feature physics_avian): `enabled` = the Option is Some.
  * `filter_mask` stands in for SpatialQueryFilter (core.rs:247, passed to cast_ray at core.rs:764): a collider takes part when
  * (filter_mask & collider.layers) != 0 -- avian's `mask` against the collider's `memberships`.
- * NOT SUPPORTED: `SpatialQueryFilter::excluded_entities`.  The device-resident set has no entity identity: a host that needs
+ * NOT SUPPORTED: `SpatialQueryFilter::excluded_entities`.  The device-resident set has no entity identity (the ray-cast query
+ * names what it hit by its position in the set: fw_ray_hit.index, below): a host that needs
  * an exclusion keeps the excluded colliders out of the set it sends (fw_ctx_set_colliders; the set is per context, so this
  * excludes them for every particle type of the context) or gives them a membership bit no particle type's mask contains
  * (rust/src/hip/colliders.rs does the latter for entities listed in a `ParticleColliderExclusions` resource). */
@@ -196,6 +197,44 @@ typedef struct fw_mesh_collider { /* one placed instance of a mesh */
     float rotation[4]; /* xyzw, a unit quaternion; scale is baked into the mesh's vertices */
 } fw_mesh_collider;
 
+/* RAY-CAST QUERIES (avian's SpatialQuery::cast_ray for everybody else: decals, impact sounds, "where will this spark land").  The
+ * collider world lives on the device; fw_ctx_cast_rays[_device] casts a batch of rays into it, one nearest hit per ray.
+ *   SAME CAST the cast is the one particle_collision runs (the same device function): hit or miss, `distance` and `normal` are, bit
+ *             for bit, what a particle gets for the same origin, dir, max_distance and mask, in the world as of the call's place in
+ *             the context's stream, with the same tie rule -- the nearest hit wins; at equal distance analytic colliders come
+ *             before mesh instances, then the lower index, then the lower ORIGINAL triangle.  `dir` is used as given: the update
+ *             passes a unit vector, the query does not normalise (`distance` is in units of |dir|).  A ray that starts inside a
+ *             solid reports distance 0 with a zero normal and names that solid (the lowest index on ties there too).
+ *   MISS      kind = FW_HIT_NONE, distance = 0, normal = 0, index = triangle = 0xFFFFFFFF.
+ *   IDENTITY  `kind` says which set `index` counts in: the one last given to fw_ctx_set_colliders (FW_HIT_COLLIDER) or to
+ *             fw_ctx_set_mesh_colliders (FW_HIT_MESH) before the query; `triangle` is the position in `indices` at the mesh's
+ *             creation, whatever was dropped or reordered since.  The host built both sets, so it keeps the parallel vector
+ *             of entities.
+ *   ORDER     both forms enqueue on the context's main stream (fw_ctx_stream), where collider sets, instance sets, refits and every
+ *             launch that casts rays already travel: a query sees every fw_ctx_set_colliders, fw_ctx_set_mesh_colliders and
+ *             fw_ctx_update_mesh_vertices[_device] called before it and none called after it.  The device form never waits,
+ *             allocates nothing, does no host work that grows with n, and reads d_rays / writes d_hits ONLY in work it enqueues
+ *             itself (as fw_ctx_update_mesh_vertices_device does): the caller writes d_rays on that stream or orders its producer
+ *             in front of the call, and reads d_hits behind it.  The host form stages through pinned memory (grown on demand,
+ *             kept by the context) and waits for its result.
+ *   ERRORS    a null pointer with n > 0: FW_EINVAL, nothing enqueued.  n == 0: FW_OK, nothing touched.  An empty world: every ray
+ *             misses.  NaN or infinite rays give whatever the operations give, deterministically; the walk ends for any ray. */
+typedef struct fw_ray { /* 32 bytes */
+    float origin[3];
+    float max_distance;
+    float dir[3];
+    uint32_t filter_mask; /* as fw_collision_settings.filter_mask */
+} fw_ray;
+enum { FW_HIT_NONE = 0, FW_HIT_COLLIDER = 1, FW_HIT_MESH = 2 };
+typedef struct fw_ray_hit { /* 32 bytes */
+    float distance;
+    float normal[3];
+    int32_t kind;      /* FW_HIT_* */
+    uint32_t index;    /* position in the set given to fw_ctx_set_colliders / fw_ctx_set_mesh_colliders */
+    uint32_t triangle; /* FW_HIT_MESH: ORIGINAL triangle index (position in `indices` at creation); else 0xFFFFFFFF */
+    uint32_t reserved; /* 0 */
+} fw_ray_hit;
+
 enum { FW_PACING_ONESHOT = 0, FW_PACING_ONDEMAND = 1, FW_PACING_COUNT_OVER_DURATION = 2 }; /* core.rs:12-29 */
 enum { FW_MODE_GLOBAL = 0, FW_MODE_NESTED = 1 };                                           /* core.rs:47-54 */
 enum { FW_SHAPE_POINT = 0, FW_SHAPE_SPHERE = 1, FW_SHAPE_CIRCLE = 2 };                     /* emission_shape.rs:7-15 */
@@ -293,6 +332,11 @@ fw_status fw_ctx_destroy_mesh(fw_ctx *ctx, fw_mesh mesh);
  * the previous set stays.  Like the analytic set it takes effect at the next fw_step and does not synchronise: the set travels
  * as one copy in the context's stream, and only a set larger than any before waits for the frames in flight. */
 fw_status fw_ctx_set_mesh_colliders(fw_ctx *ctx, const fw_mesh_collider *instances, uint32_t n);
+/* casts rays[n] into the collider world and writes hits[n] (RAY-CAST QUERIES above); host memory, synchronises */
+fw_status fw_ctx_cast_rays(fw_ctx *ctx, const fw_ray *rays, uint64_t n, fw_ray_hit *hits);
+/* the same for n fw_ray records at d_rays and n fw_ray_hit records at d_hits in DEVICE memory (16-byte aligned), read and written in
+ * the order of the context's stream by the launches this call enqueues and by nothing else.  Never synchronises. */
+fw_status fw_ctx_cast_rays_device(fw_ctx *ctx, const void *d_rays, uint64_t n, void *d_hits);
 
 /* ---- spawners ----------------------------------------------------------------- */
 /* ParticleSpawner insertion + first sync_spawner_data (core.rs:343-365) */
