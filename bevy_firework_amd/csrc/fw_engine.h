@@ -504,6 +504,9 @@ struct alignas(64) SegHost {
     // FwSeg::cpl: bit 0 -- a ring, Q1 / Q3 in component planes; bit 1 -- a FIFO ring, the rotation (Q2) as well.  A range ring keeps Q2 as a
     // float4 plane (fifo_to_range transposes it where it stands).
     uint32_t cpl_bits() const { return ring() ? (fifo ? 3u : 1u) : 0u; }  // one buffer, particle 0 not in slot 0
+    // ... but in this slot, as a launch that is ENQUEUED now has to be told (behind updates that may still be in flight): a FIFO ring's
+    // head; a range ring's first YOUNG slot -- the device subtracts the old part, whose size only it knows (FwGlobals::rold)
+    uint32_t enqueue_head() const { return fifo ? head : (range ? young_lo : 0u); }
     // FW_TYPE_DERIVED (fw_device.h): the planes S4 / Q5 / Q6 are not stored by the update; every reader evaluates scale and
     // colours from age / lifetime / initial_scale (an attached instance buffer receives them in its records).  Every type but
     // colliding ones and those whose curve keys exceed the LDS staging (fw_ctx::derive_all, wants_derived)
@@ -1187,6 +1190,8 @@ uint32_t seg_tiles(const SegHost &s, uint32_t vt_rounds = 1);
 fw_status ensure_tile_arrays(fw_ctx *ctx);
 fw_status ensure_range_arrays(fw_ctx *ctx);
 uint32_t ring_head_exact(const SegHost &S, uint32_t count);
+FwSegView seg_view(const fw_ctx *ctx, uint32_t si, uint32_t parity);
+FwSegView seg_view_exact(const fw_ctx *ctx, uint32_t si, uint32_t parity, uint32_t count);
 fw_status ensure_param_ring(fw_ctx *ctx, size_t bytes);
 fw_status wait_slot_free(fw_ctx *ctx, uint64_t &tag);
 fw_status acquire_slot(fw_ctx *ctx, int *out);

@@ -58,6 +58,25 @@ fw_ctx::~fw_ctx() {
         if (s) (void)hipStreamSynchronize(s);
 }
 
+// What the entry points that read a spawner's particles open with: the spawner, the sticky status of a poisoned one, the device,
+// the exact live counts.  begin_read returns false when the call ends there, with r.st; otherwise r.st is FW_OK or FW_ECAPACITY
+// (a type overflowed: the call goes on and reports it at its end, unless a later error takes precedence).
+// args_ok: the call's own argument check, which may look at the spawner
+struct SpawnerRead {
+    SpawnerHost *sp = nullptr;
+    std::vector<uint32_t> c;  // per segment
+    fw_status st = FW_OK;
+};
+template <typename ArgsOk>
+static bool begin_read(fw_ctx *ctx, fw_spawner h, SpawnerRead &r, ArgsOk args_ok) {
+    r.sp = get_spawner(ctx, h);
+    if (!r.sp || !args_ok(*r.sp)) return r.st = FW_EINVAL, false;
+    if (poll_device_error(ctx), r.sp->poisoned) return r.st = poisoned_status(ctx), false;
+    hipSetDevice(ctx->device);
+    r.st = read_counts(ctx, r.c);
+    return !r.st || r.st == FW_ECAPACITY;
+}
+
 extern "C" {
 
 
@@ -412,45 +431,30 @@ fw_status fw_ctx_queue(fw_ctx *ctx, uint32_t n, const fw_spawner *handles, const
 
 // ---- outputs -----------------------------------------------------------------------------
 fw_status fw_spawner_counts(fw_ctx *ctx, fw_spawner h, uint32_t *per_type, uint32_t n_types) {
-    SpawnerHost *sp = get_spawner(ctx, h);
-    if (!sp || !per_type) return FW_EINVAL;
-    if (poll_device_error(ctx), sp->poisoned) return poisoned_status(ctx);
-    hipSetDevice(ctx->device);
-    std::vector<uint32_t> c;
-    fw_status st = read_counts(ctx, c);
-    if (st && st != FW_ECAPACITY) return st;
-    for (uint32_t t = 0; t < n_types && t < sp->seg.size(); t++) per_type[t] = c[sp->seg[t]];
-    return st;
+    SpawnerRead r;
+    if (!begin_read(ctx, h, r, [&](const SpawnerHost &) { return per_type != nullptr; })) return r.st;
+    for (uint32_t t = 0; t < n_types && t < r.sp->seg.size(); t++) per_type[t] = r.c[r.sp->seg[t]];
+    return r.st;
 }
 
 fw_status fw_spawner_active(fw_ctx *ctx, fw_spawner h, int32_t *out) {
-    SpawnerHost *sp = get_spawner(ctx, h);
-    if (!sp || !out) return FW_EINVAL;
-    if (poll_device_error(ctx), sp->poisoned) return poisoned_status(ctx);
-    hipSetDevice(ctx->device);
-    std::vector<uint32_t> c;
-    fw_status st = read_counts(ctx, c);
-    if (st && st != FW_ECAPACITY) return st;
-    *out = spawner_active(ctx, *sp, c) ? 1 : 0;
-    return st;
+    SpawnerRead r;
+    if (!begin_read(ctx, h, r, [&](const SpawnerHost &) { return out != nullptr; })) return r.st;
+    *out = spawner_active(ctx, *r.sp, r.c) ? 1 : 0;
+    return r.st;
 }
 
 fw_status fw_spawner_poll_finished(fw_ctx *ctx, fw_spawner h, int32_t *out) {
-    SpawnerHost *sp = get_spawner(ctx, h);
-    if (!sp || !out) return FW_EINVAL;
-    if (poll_device_error(ctx), sp->poisoned) return poisoned_status(ctx);
-    hipSetDevice(ctx->device);
-    std::vector<uint32_t> c;
-    fw_status st = read_counts(ctx, c);
-    if (st && st != FW_ECAPACITY) return st;
+    SpawnerRead r;
+    if (!begin_read(ctx, h, r, [&](const SpawnerHost &) { return out != nullptr; })) return r.st;
     bool all_empty = true;
-    for (uint32_t si : sp->seg) all_empty &= c[si] == 0;
+    for (uint32_t si : r.sp->seg) all_empty &= r.c[si] == 0;
     *out = 0;
-    if (all_empty && !spawner_active(ctx, *sp, c) && sp->initialized && !sp->finished_notified) {  // core.rs:679-686
-        sp->finished_notified = true;
+    if (all_empty && !spawner_active(ctx, *r.sp, r.c) && r.sp->initialized && !r.sp->finished_notified) {  // core.rs:679-686
+        r.sp->finished_notified = true;
         *out = 1;
     }
-    return st;
+    return r.st;
 }
 
 static fw_status stage_buffer(fw_ctx *ctx, size_t bytes, void **out) {
@@ -463,20 +467,14 @@ static fw_status stage_buffer(fw_ctx *ctx, size_t bytes, void **out) {
     return FW_OK;
 }
 
-static fw_status read_records(fw_ctx *ctx, const char *buf, uint32_t cap_seg, uint32_t n, int32_t pbr, bool aos,
-                              fw_particle *out, uint64_t cap, uint32_t head = 0, const float *const_rot = nullptr,
-                              uint32_t life_plane = 0xFFFFFFFFu, float life_const = 0.f, const FwType *derived = nullptr, uint32_t cpl = 0u) {
+// the first min(n, cap) particles of a segment as fw_particle records, through the staging buffer
+static fw_status read_records(fw_ctx *ctx, const FwSegView &v, uint32_t n, int32_t pbr, fw_particle *out, uint64_t cap) {
     const uint64_t m = std::min<uint64_t>(n, cap);
     if (!m || !out) return FW_OK;
-    if (aos) {
-        FW_HIP(ctx, hipMemcpy(out, buf, m * sizeof(fw_particle), hipMemcpyDeviceToHost));
-        return FW_OK;
-    }
     void *tmp = nullptr;
     fw_status st = stage_buffer(ctx, m * sizeof(fw_particle), &tmp);
     if (st) return st;
-    hipError_t e = fw_launch_gather(ctx->stream, buf, cap_seg, head, (uint32_t)m, pbr, tmp, const_rot, life_plane, life_const,
-                                    derived, ctx->d_keys, cpl);
+    hipError_t e = fw_launch_gather(ctx->stream, v, (uint32_t)m, pbr, tmp);
     // (the copy goes through the stream the kernel ran on, then one wait for both)
     if (e == hipSuccess) e = hipMemcpyAsync(out, tmp, m * sizeof(fw_particle), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -486,50 +484,37 @@ static fw_status read_records(fw_ctx *ctx, const char *buf, uint32_t cap_seg, ui
 
 fw_status fw_spawner_read_particles(fw_ctx *ctx, fw_spawner h, uint32_t type, fw_particle *out, uint64_t cap,
                                     uint64_t *n_out) {
-    SpawnerHost *sp = get_spawner(ctx, h);
-    if (!sp || type >= sp->seg.size()) return FW_EINVAL;
-    if (poll_device_error(ctx), sp->poisoned) return poisoned_status(ctx);
-    hipSetDevice(ctx->device);
-    std::vector<uint32_t> c;
-    fw_status st = read_counts(ctx, c);
-    if (st && st != FW_ECAPACITY) return st;
-    const SegHost &S = ctx->segs[sp->seg[type]];
-    const uint32_t n = c[sp->seg[type]];
+    SpawnerRead r;
+    if (!begin_read(ctx, h, r, [&](const SpawnerHost &sp) { return type < sp.seg.size(); })) return r.st;
+    const uint32_t n = r.c[r.sp->seg[type]];
     if (n_out) *n_out = n;
-    fw_status st2 = read_records(ctx, S.buf[ctx->parity], S.capacity, n, sp->types[type].ps.pbr, false, out, cap,
-                                 ring_head_exact(S, n), S.nospin ? S.const_rot : nullptr,
-                                 (S.nospin && !S.fifo) ? S.n_lplanes : 0xFFFFFFFFu, S.fifo_life,
-                                 S.derived ? ctx->d_types + S.type_idx : nullptr, S.cpl_bits());
-    return st2 ? st2 : st;
+    // (the counts are exact and the stream has been waited for: the host places particle 0 itself)
+    fw_status st2 = read_records(ctx, seg_view_exact(ctx, r.sp->seg[type], ctx->parity, n), n, r.sp->types[type].ps.pbr, out, cap);
+    return st2 ? st2 : r.st;
 }
 
 fw_status fw_spawner_read_last_emitted(fw_ctx *ctx, fw_spawner h, uint32_t type, uint32_t emission_index, float *out,
                                        uint64_t cap, uint64_t *n_out) {
-    SpawnerHost *sp = get_spawner(ctx, h);
-    if (!sp || type >= sp->seg.size() || emission_index >= sp->em.size()) return FW_EINVAL;
-    if (poll_device_error(ctx), sp->poisoned) return poisoned_status(ctx);
-    hipSetDevice(ctx->device);
-    std::vector<uint32_t> c;
-    fw_status st = read_counts(ctx, c);
-    if (st && st != FW_ECAPACITY) return st;
-    const SegHost &S = ctx->segs[sp->seg[type]];
-    const uint32_t n = c[sp->seg[type]];
+    SpawnerRead r;
+    if (!begin_read(ctx, h, r, [&](const SpawnerHost &sp) { return type < sp.seg.size() && emission_index < sp.em.size(); })) return r.st;
+    const SegHost &S = ctx->segs[r.sp->seg[type]];
+    const uint32_t n = r.c[r.sp->seg[type]];
     if (n_out) *n_out = n;
     const uint64_t m = std::min<uint64_t>(n, cap);
-    if (!m || !out) return st;
+    if (!m || !out) return r.st;
     int plane = -1;
     for (uint32_t k = 0; k < S.n_lplanes; k++)
         if (S.lplane_emission[k] == (int32_t)emission_index) plane = (int)k;
     if (plane < 0) {
         for (uint64_t i = 0; i < m; i++) out[i] = FW_F32_MIN;  // never touched: still vec![f32::MIN; n] (core.rs:467)
-        return st;
+        return r.st;
     }
     const char *pl = S.buf[ctx->parity] + FW_OFF_L((size_t)S.capacity, plane);
     const uint32_t h0 = ring_head_exact(S, n);  // a ring: from the head to the end of the buffer, then from slot 0
     const uint64_t m1 = std::min<uint64_t>(m, S.capacity - h0);
     FW_HIP(ctx, hipMemcpy(out, pl + (size_t)h0 * sizeof(float), m1 * sizeof(float), hipMemcpyDeviceToHost));
     if (m > m1) FW_HIP(ctx, hipMemcpy(out + m1, pl, (m - m1) * sizeof(float), hipMemcpyDeviceToHost));
-    return st;
+    return r.st;
 }
 
 fw_status fw_spawner_write_particles(fw_ctx *ctx, fw_spawner h, uint32_t type, const fw_particle *in, uint64_t n) {
@@ -608,7 +593,10 @@ fw_status fw_spawner_read_destroyed(fw_ctx *ctx, fw_spawner h, uint32_t type, fw
     if (n_out) *n_out = n;
     // (a range ring fills its records from the END of the buffer, the youngest dead first: the last n are in list order)
     const char *first = S.destroyed + (S.dead_at_end && n <= S.capacity ? (size_t)(S.capacity - n) * sizeof(fw_particle) : (size_t)0);
-    return read_records(ctx, first, S.capacity, n, 0, true, out, cap);
+    // (the update wrote them as fw_particle records: a plain copy)
+    const uint64_t m = std::min<uint64_t>(n, cap);
+    if (m && out) FW_HIP(ctx, hipMemcpy(out, first, m * sizeof(fw_particle), hipMemcpyDeviceToHost));
+    return FW_OK;
 }
 
 fw_status fw_spawner_pack_instances_device(fw_ctx *ctx, fw_spawner h, uint32_t type, void *d_out, uint64_t cap,
@@ -625,11 +613,9 @@ fw_status fw_spawner_pack_instances_device(fw_ctx *ctx, fw_spawner h, uint32_t t
         fw_status jst = join_side(ctx);
         if (jst) return jst;
     }
-    // (a range ring: particle 0 sits `count - young_n` slots before the first young particle -- the kernel reads the count)
-    FW_HIP(ctx, fw_launch_pack_instances(ctx->stream, S.buf[ctx->parity], S.capacity, S.range ? S.young_lo : (S.fifo ? S.head : 0u),
-                                         ctx->g.count + (size_t)ctx->parity * ctx->max_seg + si, ub, d_out,
-                                         S.nospin ? S.const_rot : nullptr, S.range ? ctx->g.rold + (size_t)ctx->parity * ctx->max_seg + si : nullptr,
-                                         S.derived ? ctx->d_types + S.type_idx : nullptr, ctx->d_keys, S.life_plane(), S.fifo_life, S.cpl_bits()));
+    // (no synchronisation: the kernel reads the count -- and a range ring's old part -- from the device)
+    FW_HIP(ctx, fw_launch_pack_instances(ctx->stream, seg_view(ctx, si, ctx->parity), ctx->g.count + (size_t)ctx->parity * ctx->max_seg + si, ub,
+                                         d_out));
     return FW_OK;
 }
 
@@ -673,35 +659,25 @@ fw_status fw_spawner_attach_instances_window(fw_ctx *ctx, fw_spawner h, uint32_t
 }
 
 fw_status fw_spawner_instance_window(fw_ctx *ctx, fw_spawner h, uint32_t type, uint64_t *first, uint64_t *count) {
-    SpawnerHost *sp = get_spawner(ctx, h);
-    if (!sp || type >= sp->seg.size() || !first || !count) return FW_EINVAL;
-    if (poll_device_error(ctx), sp->poisoned) return poisoned_status(ctx);
-    hipSetDevice(ctx->device);
-    std::vector<uint32_t> c;
-    fw_status st = read_counts(ctx, c);
-    if (st && st != FW_ECAPACITY) return st;
-    const uint32_t si = sp->seg[type];
+    SpawnerRead r;
+    if (!begin_read(ctx, h, r, [&](const SpawnerHost &sp) { return type < sp.seg.size() && first && count; })) return r.st;
+    const uint32_t si = r.sp->seg[type];
     const SegHost &S = ctx->segs[si];
     uint32_t dead = 0;
     // a range ring's update numbers its records from the particles it destroys (fw_k_update_range): they sit behind them
     if (S.dead_at_end && S.inst_window) FW_HIP(ctx, hipMemcpy(&dead, ctx->g.ndestroyed + si, 4, hipMemcpyDeviceToHost));
-    *first = dead, *count = c[si];
-    return st;
+    *first = dead, *count = r.c[si];
+    return r.st;
 }
 
 fw_status fw_spawner_pack_instances(fw_ctx *ctx, fw_spawner h, uint32_t type, fw_particle_instance *out, uint64_t cap,
                                     uint64_t *n_out) {
-    SpawnerHost *sp = get_spawner(ctx, h);
-    if (!sp || type >= sp->seg.size()) return FW_EINVAL;
-    if (poll_device_error(ctx), sp->poisoned) return poisoned_status(ctx);
-    hipSetDevice(ctx->device);
-    std::vector<uint32_t> c;
-    fw_status st = read_counts(ctx, c);
-    if (st && st != FW_ECAPACITY) return st;
-    const uint32_t n = c[sp->seg[type]];
+    SpawnerRead r;
+    if (!begin_read(ctx, h, r, [&](const SpawnerHost &sp) { return type < sp.seg.size(); })) return r.st;
+    const uint32_t n = r.c[r.sp->seg[type]];
     if (n_out) *n_out = n;
     const uint64_t m = std::min<uint64_t>(n, cap);
-    if (!m || !out) return st;
+    if (!m || !out) return r.st;
     void *tmp = nullptr;
     fw_status sst = stage_buffer(ctx, m * sizeof(fw_particle_instance), &tmp);
     if (sst) return sst;
@@ -710,7 +686,7 @@ fw_status fw_spawner_pack_instances(fw_ctx *ctx, fw_spawner h, uint32_t type, fw
     hipError_t e = hipMemcpyAsync(out, tmp, m * sizeof(fw_particle_instance), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     FW_HIP(ctx, e);
-    return st2 ? st2 : st;
+    return st2 ? st2 : r.st;
 }
 
 fw_status fw_spawner_aabb(fw_ctx *ctx, fw_spawner h, float out_min[3], float out_max[3], int32_t *any) {
@@ -736,14 +712,11 @@ fw_status fw_spawner_aabb(fw_ctx *ctx, fw_spawner h, float out_min[3], float out
         const uint32_t n = (uint32_t)std::min<size_t>(8, nt - std::min(nt, t0));
         if (!n) break;
         bool any_ring = false;  // rings (and types a wave / workgroup of fw_k_update_small updates) leave no per-tile boxes: the two-pass query reads them
-        uint32_t heads[8] = {}, range_y[8], life_plane[8];
-        float life_const[8];
+        FwSegView views[8];
         for (uint32_t t = 0; t < n; t++) {
             const SegHost &S = ctx->segs[sp->seg[t0 + t]];
             any_ring |= S.ring() || S.small;
-            heads[t] = S.range ? S.young_lo : (S.fifo ? S.head : 0u);
-            range_y[t] = S.range ? 1u : 0xFFFFFFFFu;  // (a range ring: the kernel takes the old part's size from FwGlobals::rold)
-            life_plane[t] = S.life_plane(), life_const[t] = S.fifo_life;
+            views[t] = seg_view(ctx, sp->seg[t0 + t], ctx->parity);
         }
         if (ctx->boxes_epoch && ctx->d_tile_first && !any_ring) {
             // the last update left the box of every tile's survivors (fw_ctx_track_aabbs): fold those -- one small launch
@@ -751,8 +724,7 @@ fw_status fw_spawner_aabb(fw_ctx *ctx, fw_spawner h, float out_min[3], float out
                                                   ctx->d_tile_first, ctx->h_aabb));
         } else {
             // two launches over the particles, the result lands in pinned memory: one synchronisation, no copies
-            FW_HIP(ctx, fw_launch_aabb(ctx->stream, ctx->g, sp->seg.data() + t0, heads, n, ctx->parity, ctx->d_aabb, ctx->h_aabb,
-                                       range_y, life_plane, life_const));
+            FW_HIP(ctx, fw_launch_aabb(ctx->stream, ctx->g, sp->seg.data() + t0, views, n, ctx->parity, ctx->d_aabb, ctx->h_aabb));
         }
         fw_status st = sync(ctx);
         if (!st) st = check_device_errors(ctx);

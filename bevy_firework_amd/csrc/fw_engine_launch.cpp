@@ -273,19 +273,15 @@ fw_status spawn_passes(fw_ctx *ctx, FwFrame &fr) {
             for (FwNestOp op : L.n) {
                 op.first_tile = tiles;
                 tiles += op.n_tiles;
-                op.parent_buf = ctx->segs[op.parent_seg].buf[p];
-                op.parent_cap = ctx->segs[op.parent_seg].capacity;
                 // (a range ring: the slot of its first YOUNG particle as of the last update -- this frame's cohorts join the
                 // old part in launch_range, after these launches have been enqueued -- and the device subtracts the old part)
                 const SegHost &PS = ctx->segs[op.parent_seg], &CS = ctx->segs[op.child_seg];
-                op.parent_head = PS.fifo ? PS.head : (PS.range ? PS.young_lo : 0u);
-                op.child_head = CS.fifo ? CS.head : (CS.range ? CS.young_lo : 0u);
+                op.parent_buf = PS.buf[p], op.parent_cap = PS.capacity;
+                op.parent_head = PS.enqueue_head(), op.child_head = CS.enqueue_head();
                 op.parent_range = PS.range ? 1u : 0u, op.child_range = CS.range ? 1u : 0u;
-                op.parent_nospin = (ctx->segs[op.parent_seg].nospin ? 1u : 0u) | (ctx->segs[op.parent_seg].ring() ? 2u : 0u) | (ctx->segs[op.parent_seg].fifo ? 4u : 0u);
-                memcpy(op.parent_rot, ctx->segs[op.parent_seg].const_rot, sizeof op.parent_rot);
-                // (its lifetimes: the lifetime plane of a compacting segment, one value for a ring)
-                op.parent_life_plane = ctx->segs[op.parent_seg].fifo ? 0xFFFFFFFFu : ctx->segs[op.parent_seg].n_lplanes;
-                op.parent_life_const = ctx->segs[op.parent_seg].fifo_life;
+                op.parent_nospin = (PS.nospin ? 1u : 0u) | (PS.cpl_bits() << 1);  // (bit 1: Q1 / Q3 in component planes, bit 2: Q2 too)
+                memcpy(op.parent_rot, PS.const_rot, sizeof op.parent_rot);
+                op.parent_life_plane = PS.life_plane(), op.parent_life_const = PS.fifo_life;  // (read under bit 0 of parent_nospin only)
                 // (START tickets, fw_kernels.h: every workgroup of the op takes one)
                 op.ticket_base = ctx->nest_ticket_base[op.emit_slot], ctx->nest_ticket_base[op.emit_slot] += op.n_tiles;
                 h_nops[ni++] = op;

@@ -172,6 +172,30 @@ uint32_t ring_head_exact(const SegHost &S, uint32_t count) {
     return (uint32_t)(((uint64_t)S.young_lo + S.capacity - (n_old % S.capacity)) % S.capacity);
 }
 
+// How the readers outside the update kernels find the particles of segment si in buffer `parity` (FwSegView, fw_kernels.h): the one
+// place a view is made, every field from SegHost.  There are two heads.  A launch that is enqueued behind updates still in
+// flight cannot know a range ring's old part: it gets the first young slot and the device's word of FwGlobals::rold ...
+FwSegView seg_view(const fw_ctx *ctx, uint32_t si, uint32_t parity) {
+    const SegHost &S = ctx->segs[si];
+    FwSegView v{};
+    v.buf = S.buf[parity], v.capacity = S.capacity;
+    v.head = S.enqueue_head();
+    v.d_rold = S.range ? ctx->g.rold + (size_t)parity * ctx->max_seg + si : nullptr;
+    v.cpl = S.cpl_bits();
+    v.nospin = S.nospin ? 1u : 0u;
+    v.rot = S.nospin ? make_float4(S.const_rot[0], S.const_rot[1], S.const_rot[2], S.const_rot[3]) : make_float4(0.f, 0.f, 0.f, 1.f);
+    v.life_plane = S.life_plane(), v.life_const = S.fifo_life;
+    v.derived = S.derived ? ctx->d_types + S.type_idx : nullptr, v.keys = ctx->d_keys;
+    return v;
+}
+// ... a caller that has waited for the stream and holds the segment's exact `count` (read_counts) places particle 0 itself
+// (ring_head_exact): the form of the synchronous readers
+FwSegView seg_view_exact(const fw_ctx *ctx, uint32_t si, uint32_t parity, uint32_t count) {
+    FwSegView v = seg_view(ctx, si, parity);
+    v.head = ring_head_exact(ctx->segs[si], count), v.d_rold = nullptr;
+    return v;
+}
+
 fw_status ensure_param_ring(fw_ctx *ctx, size_t bytes) {
     if (bytes <= ctx->param_bytes) return FW_OK;
     fw_status st = sync(ctx);

@@ -305,9 +305,9 @@ fw_status leave_nospin(fw_ctx *ctx, uint32_t si) {
     if (!s.nospin) return FW_OK;
     fw_status st = sync(ctx);
     if (st) return st;
-    FW_HIP(ctx, fw_launch_fill_rotation(ctx->stream, s.buf[0], s.ring() ? nullptr : s.buf[1], s.capacity, s.const_rot, s.fifo));
-    FW_HIP(ctx, fw_launch_restore_q3(ctx->stream, s.buf[0], s.ring() ? nullptr : s.buf[1], s.capacity,
-                                     s.fifo ? 0xFFFFFFFFu : s.n_lplanes, s.fifo_life, s.ring()));
+    FW_HIP(ctx, fw_launch_fill_rotation(ctx->stream, s.buf[0], s.ring() ? nullptr : s.buf[1], s.capacity, s.const_rot, s.cpl_bits()));
+    FW_HIP(ctx, fw_launch_restore_q3(ctx->stream, s.buf[0], s.ring() ? nullptr : s.buf[1], s.capacity, s.life_plane(), s.fifo_life,
+                                     s.cpl_bits()));
     FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
     const uint32_t flags = s.derived ? FW_TYPE_DERIVED : 0u;
     FW_HIP(ctx, hipMemcpy((char *)(ctx->d_types + s.type_idx) + offsetof(FwType, flags), &flags, sizeof flags, hipMemcpyHostToDevice));
@@ -325,8 +325,7 @@ fw_status set_derived(fw_ctx *ctx, uint32_t si, bool on, bool refill) {
     fw_status st = sync(ctx);
     if (st) return st;
     if (!on && refill) {
-        FW_HIP(ctx, fw_launch_rederive(ctx->stream, s.buf[ctx->parity], s.capacity, ctx->d_types + s.type_idx, ctx->d_keys, s.nospin,
-                                       s.life_plane(), s.fifo_life, s.ring()));
+        FW_HIP(ctx, fw_launch_rederive(ctx->stream, seg_view(ctx, si, ctx->parity)));  // (s.derived is still set)
         FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     uint32_t flags = (s.nospin ? FW_TYPE_NOSPIN : 0u) | (on ? FW_TYPE_DERIVED : 0u);

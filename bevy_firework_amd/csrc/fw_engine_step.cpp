@@ -450,7 +450,7 @@ void route_ring_ops(fw_ctx *ctx, FwFrame &fr) {
     for (auto &L : levels) fr.nested_frame |= !L.n.empty();
     for (auto &io : ctx->fifo_mat_ops) {
         if (fr.nested_frame) {
-            io.second.head = ctx->segs[io.second.seg].head;
+            io.second.head = ctx->segs[io.second.seg].enqueue_head();
             levels[io.first].g.push_back(io.second);
         } else {
             ctx->fifo_ops.push_back(io.second);
@@ -460,7 +460,7 @@ void route_ring_ops(fw_ctx *ctx, FwFrame &fr) {
     // the list's first particle follows from the old part's size, which the device keeps: FwOp::range_ring)
     for (auto &io : ctx->range_mat_ops) {
         if (fr.nested_frame) {
-            io.second.head = ctx->segs[io.second.seg].young_lo, io.second.range_ring = 1u;
+            io.second.head = ctx->segs[io.second.seg].enqueue_head(), io.second.range_ring = 1u;
             levels[io.first].g.push_back(io.second);
         } else {
             ctx->range_ops.push_back(io.second);

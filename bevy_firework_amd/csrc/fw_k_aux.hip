@@ -6,22 +6,51 @@
 // readback / upload / render hand-off helpers
 // ---------------------------------------------------------------------------------
 
+// ---- a segment through its view (FwSegView, fw_kernels.h): the ONE place the readers below decode a segment's storage
+// slot of particle 0 (a range ring -- d_rold -- keeps the size of its old part on the device: FwGlobals::rold) ...
+__device__ __forceinline__ uint32_t fw_view_head(const FwSegView &v) {
+    return v.d_rold ? fw_range_head(v.head, *v.d_rold, v.capacity) : v.head;
+}
+// ... and of particle li, given that one
+__device__ __forceinline__ uint32_t fw_view_slot(const FwSegView &v, uint32_t head, uint32_t li) { return fw_ring_slot(head, li, v.capacity); }
+// lifetime of slot i: Q3.w, or -- a type that cannot turn -- its plane, or -- a FIFO ring of such a type -- the type's one value
+__device__ __forceinline__ float fw_view_life(const FwSegView &v, uint32_t i) {
+    if (v.nospin && v.life_plane == 0xFFFFFFFFu) return v.life_const;
+    return fw_load_lifetime(v.buf, v.capacity, v.life_plane, i, v.nospin != 0u, v.cpl != 0u);
+}
+// velocity + initial_scale, angular velocity + lifetime (cannot turn: 0), rotation (cannot turn: the type's one)
+__device__ __forceinline__ float4 fw_view_q1(const FwSegView &v, uint32_t i) { return fw_ldq(v.buf + FW_OFF_Q1(v.capacity), v.capacity, i, v.cpl != 0u); }
+__device__ __forceinline__ float fw_view_q1w(const FwSegView &v, uint32_t i) { return fw_ldq_w(v.buf + FW_OFF_Q1(v.capacity), v.capacity, i, v.cpl != 0u); }
+__device__ __forceinline__ float4 fw_view_q3(const FwSegView &v, uint32_t i) {
+    return !v.nospin ? fw_ldq(v.buf + FW_OFF_Q3(v.capacity), v.capacity, i, v.cpl != 0u) : make_float4(0.0f, 0.0f, 0.0f, fw_view_life(v, i));
+}
+__device__ __forceinline__ float4 fw_view_rot(const FwSegView &v, uint32_t i) {
+    return v.nospin ? v.rot : fw_ldq(v.buf + FW_OFF_Q2(v.capacity), v.capacity, i, (v.cpl & 2u) != 0u);
+}
+// scale and colours of slot i (age: its Q0.w): what the planes hold, or -- FW_TYPE_DERIVED: the planes are not maintained --
+// what the last update computed, again
+__device__ __forceinline__ void fw_view_look(const FwSegView &v, uint32_t i, float age, float4 *bc, float4 *em, float *sc) {
+    *sc = fw_ld1(v.buf + FW_OFF_S4(v.capacity), i), *bc = fw_ld4(v.buf + FW_OFF_Q5(v.capacity), i), *em = fw_ld4(v.buf + FW_OFF_Q6(v.capacity), i);
+    if (v.derived) fw_derived_values(*v.derived, v.keys + v.derived->keys_off, age, fw_view_life(v, i), fw_view_q1w(v, i), bc, em, sc);
+}
+// ... and the scale alone
+__device__ __forceinline__ float fw_view_scale(const FwSegView &v, uint32_t i, float age) {
+    const float sc = fw_ld1(v.buf + FW_OFF_S4(v.capacity), i);
+    if (!v.derived) return sc;
+    const FwType &T = *v.derived;
+    const float *keys = v.keys + T.keys_off;
+    return fw_view_q1w(v, i) * fw_curve_sample(T.sc_kind, T.sc_n, keys, keys + T.o_sc_v, age / fw_view_life(v, i));
+}
+
 // SoA planes -> fw_particle records (26 x 4 B)
-// (rot: the rotation of every particle of a type that cannot turn -- FW_TYPE_NOSPIN, its plane is not maintained -- or null)
-__global__ void fw_k_gather(const char *buf, uint32_t C, uint32_t head, uint32_t n, int32_t pbr, float *out, bool nospin, float4 rot,
-                            uint32_t life_plane, float life_const, const FwType *derived, const float *keys, uint32_t cpl) {  // (cpl: FwSeg::cpl -- bit 0 Q1 / Q3 in planes, bit 1 Q2 too)
+__global__ void fw_k_gather(FwSegView v, uint32_t n, int32_t pbr, float *out) {
     const uint32_t li = blockIdx.x * blockDim.x + threadIdx.x;
     if (li >= n) return;
-    const uint32_t i = fw_ring_slot(head, li, C);
-    const float4 q0 = fw_ld4(buf + FW_OFF_Q0(C), i), q1 = fw_ldq(buf + FW_OFF_Q1(C), C, i, cpl),
-                 q2 = nospin ? rot : fw_ldq(buf + FW_OFF_Q2(C), C, i, (cpl & 2u) != 0u),
-                 // (cannot turn: angular velocity 0; the lifetime from its plane, or -- a ring -- the type's one value)
-                 q3 = !nospin ? fw_ldq(buf + FW_OFF_Q3(C), C, i, cpl)
-                              : make_float4(0.0f, 0.0f, 0.0f, life_plane != 0xFFFFFFFFu ? fw_ld1(buf + FW_OFF_L(C, life_plane), i) : life_const),
-                 bc0 = fw_ld4(buf + FW_OFF_Q5(C), i), em0 = fw_ld4(buf + FW_OFF_Q6(C), i);
-    float4 bc = bc0, em = em0;
-    float sc = reinterpret_cast<const float *>(buf + FW_OFF_S4(C))[i];
-    if (derived) fw_derived_values(*derived, keys + derived->keys_off, q0.w, q3.w, q1.w, &bc, &em, &sc);  // FW_TYPE_DERIVED
+    const uint32_t i = fw_view_slot(v, fw_view_head(v), li);
+    const float4 q0 = fw_ld4(v.buf + FW_OFF_Q0(v.capacity), i), q1 = fw_view_q1(v, i), q2 = fw_view_rot(v, i), q3 = fw_view_q3(v, i);
+    float4 bc, em;
+    float sc;
+    fw_view_look(v, i, q0.w, &bc, &em, &sc);
     float *r = out + (size_t)li * 26;
     r[0] = q0.x, r[1] = q0.y, r[2] = q0.z;
     r[3] = q1.x, r[4] = q1.y, r[5] = q1.z;
@@ -58,31 +87,29 @@ __global__ void fw_k_fill_colors(char *buf0, char *buf1, uint32_t C, float4 bc, 
 
 // a type leaves FW_TYPE_DERIVED (its instance buffer is detached): scale and colour planes of every slot, evaluated from
 // the slot's age / lifetime / initial_scale -- what the updates would have stored
-__global__ void fw_k_rederive(char *buf, uint32_t C, const FwType *T, const float *keys, bool nospin, uint32_t life_plane, float life_const, bool cpl) {
+__global__ void fw_k_rederive(FwSegView v) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= C) return;
-    const float4 q0 = fw_ld4(buf + FW_OFF_Q0(C), i);
-    const float life = !nospin ? fw_ldq_w(buf + FW_OFF_Q3(C), C, i, cpl)
-                               : (life_plane != 0xFFFFFFFFu ? fw_ld1(buf + FW_OFF_L(C, life_plane), i) : life_const);
+    if (i >= v.capacity) return;
+    const float4 q0 = fw_ld4(v.buf + FW_OFF_Q0(v.capacity), i);
     float4 bc, em;
     float sc;
-    fw_derived_values(*T, keys + T->keys_off, q0.w, life, fw_ldq_w(buf + FW_OFF_Q1(C), C, i, cpl), &bc, &em, &sc);
-    fw_st4(buf + FW_OFF_Q5(C), i, bc), fw_st4(buf + FW_OFF_Q6(C), i, em), fw_st1(buf + FW_OFF_S4(C), i, sc);
+    fw_derived_values(*v.derived, v.keys + v.derived->keys_off, q0.w, fw_view_life(v, i), fw_view_q1w(v, i), &bc, &em, &sc);
+    fw_st4(v.buf + FW_OFF_Q5(v.capacity), i, bc), fw_st4(v.buf + FW_OFF_Q6(v.capacity), i, em), fw_st1(v.buf + FW_OFF_S4(v.capacity), i, sc);
 }
-hipError_t fw_launch_rederive(hipStream_t s, char *buf, uint32_t capacity, const FwType *d_type, const float *d_keys, bool nospin,
-                              uint32_t life_plane, float life_const, bool cpl) {
-    if (!capacity) return hipSuccess;
-    hipLaunchKernelGGL(fw_k_rederive, dim3((capacity + 255) / 256), dim3(256), 0, s, buf, capacity, d_type, d_keys, nospin, life_plane, life_const, cpl);
+hipError_t fw_launch_rederive(hipStream_t s, const FwSegView &v) {
+    if (!v.derived) return hipErrorInvalidValue;
+    if (!v.capacity) return hipSuccess;
+    hipLaunchKernelGGL(fw_k_rederive, dim3((v.capacity + 255) / 256), dim3(256), 0, s, v);
     return hipGetLastError();
 }
 
 // a type leaves FW_TYPE_NOSPIN: its rotation plane, which nobody maintained, gets the constant rotation in every slot
-// (cpl: a FIFO ring -- the rotation in component planes, fw_dev.h)
-__global__ void fw_k_fill_rotation(char *buf0, char *buf1, uint32_t C, float4 rot, bool cpl) {
+// (cpl: FwSegView::cpl -- bit 1: a FIFO ring, the rotation in component planes, fw_dev.h)
+__global__ void fw_k_fill_rotation(char *buf0, char *buf1, uint32_t C, float4 rot, uint32_t cpl) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= C) return;
-    fw_stq(buf0 + FW_OFF_Q2(C), C, i, rot, cpl);
-    if (buf1) fw_stq(buf1 + FW_OFF_Q2(C), C, i, rot, cpl);
+    fw_stq(buf0 + FW_OFF_Q2(C), C, i, rot, (cpl & 2u) != 0u);
+    if (buf1) fw_stq(buf1 + FW_OFF_Q2(C), C, i, rot, (cpl & 2u) != 0u);
 }
 
 // a 4-byte plane filled with one value (the lifetime plane of a ring that becomes a compacting segment)
@@ -92,39 +119,33 @@ __global__ void fw_k_fill_plane1(char *buf0, char *buf1, size_t plane_off, uint3
     fw_st1(buf0 + plane_off, i, v);
     if (buf1) fw_st1(buf1 + plane_off, i, v);
 }
-// a type leaves FW_TYPE_NOSPIN: Q3 = {0, 0, 0, lifetime} again, the lifetime from its plane (or one value: a ring)
-__global__ void fw_k_restore_q3(char *buf0, char *buf1, uint32_t C, uint32_t life_plane, float life_const, bool cpl) {
+// a type leaves FW_TYPE_NOSPIN: Q3 = {0, 0, 0, lifetime} again -- what a reader of the no-spin view sees, stored; buf1 (or null):
+// the same for the segment's other buffer
+__global__ void fw_k_restore_q3(FwSegView v, char *buf1) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= C) return;
-    const bool pl = life_plane != 0xFFFFFFFFu;
-    fw_stq(buf0 + FW_OFF_Q3(C), C, i, make_float4(0.f, 0.f, 0.f, pl ? fw_ld1(buf0 + FW_OFF_L(C, life_plane), i) : life_const), cpl);
-    if (buf1) fw_stq(buf1 + FW_OFF_Q3(C), C, i, make_float4(0.f, 0.f, 0.f, pl ? fw_ld1(buf1 + FW_OFF_L(C, life_plane), i) : life_const), cpl);
+    if (i >= v.capacity) return;
+    fw_stq(v.buf + FW_OFF_Q3(v.capacity), v.capacity, i, fw_view_q3(v, i), v.cpl != 0u);
+    if (!buf1) return;
+    FwSegView w = v;
+    w.buf = buf1;
+    fw_stq(w.buf + FW_OFF_Q3(w.capacity), w.capacity, i, fw_view_q3(w, i), w.cpl != 0u);
 }
 
 // ParticleInstance packing (reference src/render.rs:95-115): {pos, scale, rot, base, emissive}
 // SoA planes -> ParticleInstance records (render.rs:95-115).  Loads are plane-wise coalesced; the 64-byte records are
 // transposed through LDS so that every store instruction of a wave writes 1 KiB of consecutive bytes (a lane writing
 // its own record with four float4 stores would touch 64 lines a quarter at a time).
-__global__ __launch_bounds__(256) void fw_k_pack(const char *buf, uint32_t C, uint32_t head, const uint32_t *d_count,
-                                                 uint32_t n_upper, float4 *out, bool nospin, float4 rot, const uint32_t *d_rold,
-                                                 const FwType *derived, const float *keys, uint32_t life_plane, float life_const, uint32_t cpl) {
+__global__ __launch_bounds__(256) void fw_k_pack(FwSegView v, const uint32_t *d_count, uint32_t n_upper, float4 *out) {
     __shared__ float4 s_rec[256 * 4];
-    // a range ring (d_rold: the size of its old part, FwGlobals::rold): `head` is the slot of the first young particle
-    if (d_rold) head = fw_range_head(head, *d_rold, C);
+    const uint32_t head = fw_view_head(v);
     const uint32_t n = min(*d_count, n_upper);
     const uint32_t tid = threadIdx.x;
     for (uint32_t b = blockIdx.x * 256u; b < n; b += gridDim.x * 256u) {
-        const uint32_t i = fw_ring_slot(head, min(b + tid, n - 1u), C);
-        const float4 q0 = fw_ld4(buf + FW_OFF_Q0(C), i);
-        float sc = fw_ld1(buf + FW_OFF_S4(C), i);
-        const float4 q2 = nospin ? rot : fw_ldq(buf + FW_OFF_Q2(C), C, i, (cpl & 2u) != 0u);
-        float4 q5 = fw_ld4(buf + FW_OFF_Q5(C), i);
-        float4 q6 = fw_ld4(buf + FW_OFF_Q6(C), i);
-        if (derived) {  // FW_TYPE_DERIVED: the three planes are not maintained -- what the last update computed, again
-            const float life = !nospin ? fw_ldq_w(buf + FW_OFF_Q3(C), C, i, cpl)
-                                       : (life_plane != 0xFFFFFFFFu ? fw_ld1(buf + FW_OFF_L(C, life_plane), i) : life_const);
-            fw_derived_values(*derived, keys + derived->keys_off, q0.w, life, fw_ldq_w(buf + FW_OFF_Q1(C), C, i, cpl), &q5, &q6, &sc);
-        }
+        const uint32_t i = fw_view_slot(v, head, min(b + tid, n - 1u));
+        const float4 q0 = fw_ld4(v.buf + FW_OFF_Q0(v.capacity), i), q2 = fw_view_rot(v, i);
+        float4 q5, q6;
+        float sc;
+        fw_view_look(v, i, q0.w, &q5, &q6, &sc);
         s_rec[tid * 4 + 0] = make_float4(q0.x, q0.y, q0.z, sc);
         s_rec[tid * 4 + 1] = q2;
         s_rec[tid * 4 + 2] = q5;
@@ -166,65 +187,16 @@ __device__ __forceinline__ void fw_atomic_maxf(float *addr, float v) {
 // {min.xyz, any, max.xyz, -} in PINNED host memory, so the query costs one stream synchronisation and no copies.
 struct FwSegList {
     uint32_t n;
-    uint32_t id[8];    // FW_MAX_TYPES
-    uint32_t head[8];  // slot of each segment's particle 0 (FIFO rings; 0 otherwise)
-    uint32_t range_y[8];  // 0xFFFFFFFF, or -- a range ring -- its young count: head[] is the slot of its first young particle
-    uint32_t life_plane[8];  // FW_TYPE_DERIVED types (scale evaluated from age / lifetime): where a type that cannot turn keeps
-    float life_const[8];     // its lifetimes -- a plane behind the last_emitted_age planes, or (0xFFFFFFFF) one value
+    uint32_t id[8];  // FW_MAX_TYPES
+    FwSegView v[8];  // (fw_k_aabb only: the other two fold what somebody else read)
 };
-#define FW_AABB_BLOCKS 256u
-__global__ __launch_bounds__(FW_BLOCK) void fw_k_aabb(FwGlobals g, FwSegList L, uint32_t parity, float *part8) {
-    __shared__ float s_m[4][6];
-    float mn[3] = {3.40282347e+38f, 3.40282347e+38f, 3.40282347e+38f};
-    float mx[3] = {FW_F32_MIN, FW_F32_MIN, FW_F32_MIN};
-    for (uint32_t k = 0; k < L.n; k++) {
-        const uint32_t seg = L.id[k];
-        const FwSeg &S = g.segs[seg];
-        const uint32_t n = g.count[parity * g.max_seg + seg];
-        const char *buf = S.buf[parity];
-        const FwType &TT = g.types[S.type_idx];
-        uint32_t head = L.head[k];
-        if (L.range_y[k] != 0xFFFFFFFFu) head = fw_range_head(head, g.rold[parity * g.max_seg + seg], S.capacity);  // (a range ring)
-        for (uint32_t li = blockIdx.x * FW_BLOCK + threadIdx.x; li < n; li += gridDim.x * FW_BLOCK) {
-            const uint32_t i = fw_ring_slot(head, li, S.capacity);
-            const float4 q0 = fw_ld4(buf + FW_OFF_Q0(S.capacity), i);
-            float sc = fw_ld1(buf + FW_OFF_S4(S.capacity), i);
-            if (TT.flags & FW_TYPE_DERIVED) {  // the scale plane is not maintained: what the last update computed, again
-                const float life = !(TT.flags & FW_TYPE_NOSPIN) ? fw_ldq_w(buf + FW_OFF_Q3(S.capacity), S.capacity, i, S.cpl != 0u)
-                                   : (L.life_plane[k] != 0xFFFFFFFFu ? fw_ld1(buf + FW_OFF_L(S.capacity, L.life_plane[k]), i) : L.life_const[k]);
-                const float *keys = g.keys + TT.keys_off;
-                sc = fw_ldq_w(buf + FW_OFF_Q1(S.capacity), S.capacity, i, S.cpl != 0u) * fw_curve_sample(TT.sc_kind, TT.sc_n, keys, keys + TT.o_sc_v, q0.w / life);
-            }
-            mn[0] = fminf(mn[0], q0.x - sc), mn[1] = fminf(mn[1], q0.y - sc), mn[2] = fminf(mn[2], q0.z - sc);
-            mx[0] = fmaxf(mx[0], q0.x + sc), mx[1] = fmaxf(mx[1], q0.y + sc), mx[2] = fmaxf(mx[2], q0.z + sc);
-        }
-    }
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            mn[c] = fminf(mn[c], __shfl_xor(mn[c], o, 64));
-            mx[c] = fmaxf(mx[c], __shfl_xor(mx[c], o, 64));
-        }
-    }
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    if (lane == 0)
-        for (int c = 0; c < 3; c++) s_m[wave][c] = mn[c], s_m[wave][3 + c] = mx[c];
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const uint32_t c = threadIdx.x;
-        float v = s_m[0][c];
-        for (int w = 1; w < 4; w++) v = c < 3 ? fminf(v, s_m[w][c]) : fmaxf(v, s_m[w][c]);
-        part8[blockIdx.x * 8u + c] = v;
-    }
-}
-__global__ __launch_bounds__(FW_AABB_BLOCKS) void fw_k_aabb_fold(FwGlobals g, FwSegList L, uint32_t parity,
-                                                                 const float *part8, float *host8) {
-    __shared__ float s_m[FW_AABB_BLOCKS / 64][6];
-    float v[6];
+// What the three kernels end in: every lane's {min.xyz, max.xyz} folded over the workgroup (WG lanes) -- over the wave, then across
+// the waves through LDS; lane c < 6 returns component c of the result
+template <uint32_t WG>
+__device__ __forceinline__ float fw_box_fold(float v[6]) {
+    __shared__ float s_m[WG / 64][6];
 #pragma unroll
     for (int c = 0; c < 6; c++) {
-        v[c] = part8[threadIdx.x * 8u + c];
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             const float other = __shfl_xor(v[c], o, 64);
@@ -235,24 +207,55 @@ __global__ __launch_bounds__(FW_AABB_BLOCKS) void fw_k_aabb_fold(FwGlobals g, Fw
     if (lane == 0)
         for (int c = 0; c < 6; c++) s_m[wave][c] = v[c];
     __syncthreads();
+    float r = 0.0f;
     if (threadIdx.x < 6) {
         const uint32_t c = threadIdx.x;
-        float r = s_m[0][c];
-        for (uint32_t w = 1; w < FW_AABB_BLOCKS / 64; w++) r = c < 3 ? fminf(r, s_m[w][c]) : fmaxf(r, s_m[w][c]);
-        host8[c < 3 ? c : c + 1u] = r;
+        r = s_m[0][c];
+        for (uint32_t w = 1; w < WG / 64; w++) r = c < 3 ? fminf(r, s_m[w][c]) : fmaxf(r, s_m[w][c]);
     }
+    return r;
+}
+// ... and the answer in pinned host memory: {min.xyz, any, max.xyz, -}
+template <uint32_t WG>
+__device__ __forceinline__ void fw_box_answer(const FwGlobals &g, const FwSegList &L, uint32_t parity, float v[6], float *host8) {
+    const float r = fw_box_fold<WG>(v);
+    if (threadIdx.x < 6) host8[threadIdx.x < 3 ? threadIdx.x : threadIdx.x + 1u] = r;
     if (threadIdx.x == 0) {
         uint32_t any = 0;
         for (uint32_t k = 0; k < L.n; k++) any |= g.count[parity * g.max_seg + L.id[k]];
         host8[3] = any ? 1.0f : 0.0f;
     }
 }
+#define FW_AABB_BLOCKS 256u
+__global__ __launch_bounds__(FW_BLOCK) void fw_k_aabb(FwGlobals g, FwSegList L, uint32_t parity, float *part8) {
+    float m[6] = {3.40282347e+38f, 3.40282347e+38f, 3.40282347e+38f, FW_F32_MIN, FW_F32_MIN, FW_F32_MIN};
+    for (uint32_t k = 0; k < L.n; k++) {
+        const FwSegView &v = L.v[k];
+        const uint32_t n = g.count[parity * g.max_seg + L.id[k]];
+        const uint32_t head = fw_view_head(v);
+        for (uint32_t li = blockIdx.x * FW_BLOCK + threadIdx.x; li < n; li += gridDim.x * FW_BLOCK) {
+            const uint32_t i = fw_view_slot(v, head, li);
+            const float4 q0 = fw_ld4(v.buf + FW_OFF_Q0(v.capacity), i);
+            const float sc = fw_view_scale(v, i, q0.w);
+            m[0] = fminf(m[0], q0.x - sc), m[1] = fminf(m[1], q0.y - sc), m[2] = fminf(m[2], q0.z - sc);
+            m[3] = fmaxf(m[3], q0.x + sc), m[4] = fmaxf(m[4], q0.y + sc), m[5] = fmaxf(m[5], q0.z + sc);
+        }
+    }
+    const float r = fw_box_fold<FW_BLOCK>(m);
+    if (threadIdx.x < 6) part8[blockIdx.x * 8u + threadIdx.x] = r;
+}
+__global__ __launch_bounds__(FW_AABB_BLOCKS) void fw_k_aabb_fold(FwGlobals g, FwSegList L, uint32_t parity,
+                                                                 const float *part8, float *host8) {
+    float v[6];
+#pragma unroll
+    for (int c = 0; c < 6; c++) v[c] = part8[threadIdx.x * 8u + c];
+    fw_box_answer<FW_AABB_BLOCKS>(g, L, parity, v, host8);
+}
 
 // fw_spawner_aabb from the per-tile boxes the last update left (fw_tile_box_flush): one workgroup folds the boxes of the
 // spawner's segments -- a few hundred 32-byte records -- and leaves {min.xyz, any, max.xyz, -} in pinned host memory.
 __global__ __launch_bounds__(FW_BLOCK) void fw_k_aabb_from_tiles(FwGlobals g, FwSegList L, uint32_t parity, uint32_t epoch,
                                                                  const uint32_t *seg_tile_first, float *host8) {
-    __shared__ float s_m[FW_BLOCK / 64][6];
     float v[6] = {3.40282347e+38f, 3.40282347e+38f, 3.40282347e+38f, FW_F32_MIN, FW_F32_MIN, FW_F32_MIN};
     const float4 *boxes = reinterpret_cast<const float4 *>(g.tile_box);
     for (uint32_t k = 0; k < L.n; k++) {
@@ -265,29 +268,7 @@ __global__ __launch_bounds__(FW_BLOCK) void fw_k_aabb_from_tiles(FwGlobals g, Fw
             v[3] = fmaxf(v[3], hi.x), v[4] = fmaxf(v[4], hi.y), v[5] = fmaxf(v[5], hi.z);
         }
     }
-#pragma unroll
-    for (int c = 0; c < 6; c++) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const float other = __shfl_xor(v[c], o, 64);
-            v[c] = c < 3 ? fminf(v[c], other) : fmaxf(v[c], other);
-        }
-    }
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    if (lane == 0)
-        for (int c = 0; c < 6; c++) s_m[wave][c] = v[c];
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const uint32_t c = threadIdx.x;
-        float r = s_m[0][c];
-        for (uint32_t w = 1; w < FW_BLOCK / 64; w++) r = c < 3 ? fminf(r, s_m[w][c]) : fmaxf(r, s_m[w][c]);
-        host8[c < 3 ? c : c + 1u] = r;
-    }
-    if (threadIdx.x == 0) {
-        uint32_t any = 0;
-        for (uint32_t k = 0; k < L.n; k++) any |= g.count[parity * g.max_seg + L.id[k]];
-        host8[3] = any ? 1.0f : 0.0f;
-    }
+fw_box_answer<FW_BLOCK>(g, L, parity, v, host8);
 }
 
 __global__ void fw_k_total(const uint32_t *counts, uint32_t n_seg, unsigned long long *out) {
@@ -326,12 +307,9 @@ __global__ __launch_bounds__(FW_BLOCK) void fw_k_copy(const float4 *src, float4 
 
 // ---- launch wrappers
 
-hipError_t fw_launch_gather(hipStream_t s, const char *buf, uint32_t capacity, uint32_t head, uint32_t n, int32_t pbr, void *d_out,
-                            const float *const_rot, uint32_t life_plane, float life_const, const FwType *derived, const float *keys, uint32_t cpl) {
+hipError_t fw_launch_gather(hipStream_t s, const FwSegView &v, uint32_t n, int32_t pbr, void *d_out) {
     if (!n) return hipSuccess;
-    const float4 rot = const_rot ? make_float4(const_rot[0], const_rot[1], const_rot[2], const_rot[3]) : make_float4(0.f, 0.f, 0.f, 1.f);
-    hipLaunchKernelGGL(fw_k_gather, dim3((n + 255) / 256), dim3(256), 0, s, buf, capacity, head, n, pbr, (float *)d_out,
-                       const_rot != nullptr, rot, life_plane, life_const, derived, keys, cpl);
+    hipLaunchKernelGGL(fw_k_gather, dim3((n + 255) / 256), dim3(256), 0, s, v, n, pbr, (float *)d_out);
     return hipGetLastError();
 }
 
@@ -355,40 +333,35 @@ hipError_t fw_launch_fill_plane1(hipStream_t s, char *buf0, char *buf1, size_t p
     hipLaunchKernelGGL(fw_k_fill_plane1, dim3((capacity + 255) / 256), dim3(256), 0, s, buf0, buf1, plane_off, capacity, v);
     return hipGetLastError();
 }
-hipError_t fw_launch_restore_q3(hipStream_t s, char *buf0, char *buf1, uint32_t capacity, uint32_t life_plane, float life_const, bool cpl) {
+hipError_t fw_launch_restore_q3(hipStream_t s, char *buf0, char *buf1, uint32_t capacity, uint32_t life_plane, float life_const, uint32_t cpl) {
     if (!capacity) return hipSuccess;
-    hipLaunchKernelGGL(fw_k_restore_q3, dim3((capacity + 255) / 256), dim3(256), 0, s, buf0, buf1, capacity, life_plane, life_const, cpl);
+    FwSegView v{};  // (the segment as its readers see it until the flag goes: no spin)
+    v.buf = buf0, v.capacity = capacity, v.cpl = cpl, v.nospin = 1u, v.life_plane = life_plane, v.life_const = life_const;
+    hipLaunchKernelGGL(fw_k_restore_q3, dim3((capacity + 255) / 256), dim3(256), 0, s, v, buf1);
     return hipGetLastError();
 }
 
-hipError_t fw_launch_fill_rotation(hipStream_t s, char *buf0, char *buf1, uint32_t capacity, const float rot[4], bool cpl) {
+hipError_t fw_launch_fill_rotation(hipStream_t s, char *buf0, char *buf1, uint32_t capacity, const float rot[4], uint32_t cpl) {
     if (!capacity) return hipSuccess;
     hipLaunchKernelGGL(fw_k_fill_rotation, dim3((capacity + 255) / 256), dim3(256), 0, s, buf0, buf1, capacity,
                        make_float4(rot[0], rot[1], rot[2], rot[3]), cpl);
     return hipGetLastError();
 }
 
-hipError_t fw_launch_pack_instances(hipStream_t s, const char *buf, uint32_t capacity, uint32_t head, const uint32_t *d_count,
-                                    uint32_t n_upper, void *d_out, const float *const_rot, const uint32_t *d_rold, const FwType *derived,
-                                    const float *keys, uint32_t life_plane, float life_const, uint32_t cpl) {
+hipError_t fw_launch_pack_instances(hipStream_t s, const FwSegView &v, const uint32_t *d_count, uint32_t n_upper, void *d_out) {
     if (!n_upper) return hipSuccess;
     uint32_t blocks = (n_upper + 255) / 256;
     if (blocks > 8192) blocks = 8192;
-    const float4 rot = const_rot ? make_float4(const_rot[0], const_rot[1], const_rot[2], const_rot[3]) : make_float4(0.f, 0.f, 0.f, 1.f);
-    hipLaunchKernelGGL(fw_k_pack, dim3(blocks), dim3(256), 0, s, buf, capacity, head, d_count, n_upper, (float4 *)d_out,
-                       const_rot != nullptr, rot, d_rold, derived, keys, life_plane, life_const, cpl);
+    hipLaunchKernelGGL(fw_k_pack, dim3(blocks), dim3(256), 0, s, v, d_count, n_upper, (float4 *)d_out);
     return hipGetLastError();
 }
 
-hipError_t fw_launch_aabb(hipStream_t s, const FwGlobals &g, const uint32_t *seg_ids, const uint32_t *seg_heads, uint32_t n_segs,
-                          uint32_t parity, float *d_part, float *h_out8, const uint32_t *seg_range_y, const uint32_t *seg_life_plane,
-                          const float *seg_life_const) {
+hipError_t fw_launch_aabb(hipStream_t s, const FwGlobals &g, const uint32_t *seg_ids, const FwSegView *views, uint32_t n_segs,
+                          uint32_t parity, float *d_part, float *h_out8) {
     if (!n_segs || n_segs > 8u) return hipErrorInvalidValue;  // FW_MAX_TYPES
     FwSegList L{};
     L.n = n_segs;
-    for (uint32_t i = 0; i < n_segs; i++)
-        L.id[i] = seg_ids[i], L.head[i] = seg_heads ? seg_heads[i] : 0u, L.range_y[i] = seg_range_y ? seg_range_y[i] : 0xFFFFFFFFu,
-        L.life_plane[i] = seg_life_plane ? seg_life_plane[i] : 0xFFFFFFFFu, L.life_const[i] = seg_life_const ? seg_life_const[i] : 0.0f;
+    for (uint32_t i = 0; i < n_segs; i++) L.id[i] = seg_ids[i], L.v[i] = views[i];
     hipLaunchKernelGGL(fw_k_aabb, dim3(FW_AABB_BLOCKS), dim3(FW_BLOCK), 0, s, g, L, parity, d_part);
     hipLaunchKernelGGL(fw_k_aabb_fold, dim3(1), dim3(FW_AABB_BLOCKS), 0, s, g, L, parity, (const float *)d_part, h_out8);
     return hipGetLastError();

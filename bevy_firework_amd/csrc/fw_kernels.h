@@ -360,39 +360,48 @@ hipError_t fw_launch_update_range(hipStream_t s, const FwGlobals &g, const FwRan
                                   hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 hipError_t fw_launch_nested(hipStream_t s, const FwGlobals &g, const FwNestOp *d_ops, const FwNestOp *h_ops, uint32_t n_ops,
                             uint32_t total_tiles, uint32_t parity, uint32_t tag, uint32_t spin_limit, uint32_t dbg = 0);
-// SoA -> AoS gather of `n` particles of one segment buffer into fw_particle records (device)
-// (head: slot of particle 0 -- 0 for every segment but a FIFO ring)
-// (const_rot: the rotation of a type that cannot turn -- FW_TYPE_NOSPIN, its plane is not maintained -- or null)
-// (... and then its lifetimes sit in plane `life_plane` behind the last_emitted_age planes, or -- a ring: 0xFFFFFFFF -- all
-// equal life_const)
-// (derived: the type's device record when it is FW_TYPE_DERIVED -- scale and colours are then evaluated, not read -- + the key pool)
-hipError_t fw_launch_gather(hipStream_t s, const char *buf, uint32_t capacity, uint32_t head, uint32_t n, int32_t pbr, void *d_out,
-                            const float *const_rot = nullptr, uint32_t life_plane = 0xFFFFFFFFu, float life_const = 0.0f,
-                            const FwType *derived = nullptr, const float *keys = nullptr, uint32_t cpl = 0u);
-// (cpl: FwSeg::cpl -- bit 0: a ring, its Q1 / Q3 regions are component planes; bit 1: a FIFO ring, Q2 as well; fw_dev.h)
-// fills the scale / colour planes of one buffer from age, lifetime and initial_scale (a type leaves FW_TYPE_DERIVED)
-hipError_t fw_launch_rederive(hipStream_t s, char *buf, uint32_t capacity, const FwType *d_type, const float *d_keys, bool nospin,
-                              uint32_t life_plane, float life_const, bool cpl);
+// ---- the readers of a segment's particles outside the update kernels (fw_k_aux.hip) --------------------------------
+// fw_k_gather (fw_particle records), fw_k_pack (ParticleInstance records), fw_k_aabb, fw_k_rederive and fw_k_restore_q3 all
+// have to know how a segment stores its particles.  FwSegView says it once; the host fills it in ONE place (seg_view,
+// fw_engine_mem.cpp: every field from SegHost) and the device reads it through ONE set of functions (fw_view_*, fw_k_aux.hip):
+//   in which slot is particle 0?            head / d_rold       SegHost::enqueue_head(), or ring_head_exact (seg_view_exact)
+//   Q1 / Q3 in component planes?  Q2?       cpl                 SegHost::cpl_bits()
+//   a rotation plane, or one rotation?      nospin / rot        SegHost::nospin, const_rot
+//   where is the lifetime?                  life_plane / const  SegHost::life_plane(), fifo_life -- read under `nospin` only
+//   scale and colours stored, or evaluated? derived / keys      SegHost::derived
+//   which buffer, how many slots?           buf / capacity      SegHost::buf[parity], capacity
+struct FwSegView {
+    char *buf;
+    uint32_t capacity;
+    uint32_t head;           // slot of particle 0 -- or, d_rold set, of the ring's first YOUNG particle
+    const uint32_t *d_rold;  // null, or -- a range ring -- the segment's word of FwGlobals::rold: particle 0 sits so many slots before `head`
+    uint32_t cpl;            // FwSeg::cpl -- bit 0: a ring, its Q1 / Q3 regions are component planes; bit 1: a FIFO ring, Q2 as well (fw_dev.h)
+    uint32_t nospin;         // FW_TYPE_NOSPIN: the rotation plane is not maintained and Q3 is not read -- every particle has
+    float4 rot;              //   this rotation, angular velocity 0,
+    uint32_t life_plane;     //   and its lifetime in this plane behind the last_emitted_age planes, or -- 0xFFFFFFFF: a FIFO ring --
+    float life_const;        //   this one value
+    const FwType *derived;   // null, or the type's device record when it is FW_TYPE_DERIVED: scale and colours are evaluated, not read,
+    const float *keys;       //   from the key pool
+};
+// SoA -> AoS gather of the first `n` particles of a segment into fw_particle records (device)
+hipError_t fw_launch_gather(hipStream_t s, const FwSegView &v, uint32_t n, int32_t pbr, void *d_out);
+// fills the scale / colour planes of every slot from age, lifetime and initial_scale (a type leaves FW_TYPE_DERIVED: v.derived is still set)
+hipError_t fw_launch_rederive(hipStream_t s, const FwSegView &v);
 hipError_t fw_launch_fill_plane1(hipStream_t s, char *buf0, char *buf1, size_t plane_off, uint32_t capacity, float v);
-hipError_t fw_launch_restore_q3(hipStream_t s, char *buf0, char *buf1, uint32_t capacity, uint32_t life_plane, float life_const, bool cpl);
+// A type leaves FW_TYPE_NOSPIN, in one (buf1 == nullptr) or both buffers of its segment: Q3 = {0, 0, 0, lifetime} again, and the
+// rotation plane, which nobody maintained, filled with the type's one rotation.  cpl, life_plane, life_const: as in FwSegView
+hipError_t fw_launch_restore_q3(hipStream_t s, char *buf0, char *buf1, uint32_t capacity, uint32_t life_plane, float life_const, uint32_t cpl);
+hipError_t fw_launch_fill_rotation(hipStream_t s, char *buf0, char *buf1, uint32_t capacity, const float rot[4], uint32_t cpl);
 hipError_t fw_launch_scatter(hipStream_t s, char *buf, uint32_t capacity, uint32_t n, uint32_t n_lplanes,
                              const void *d_in);
 // fills the base / emissive colour planes of one (buf1 == nullptr) or both buffers of a segment (capacity slots each)
 hipError_t fw_launch_fill_colors(hipStream_t s, char *buf0, char *buf1, uint32_t capacity, const float bc[4], const float em[4]);
-// (d_rold != null: a range ring -- `head` is the slot of its first YOUNG particle and particle 0 sits *d_rold slots before it:
-// the segment's word of FwGlobals::rold)
-hipError_t fw_launch_pack_instances(hipStream_t s, const char *buf, uint32_t capacity, uint32_t head, const uint32_t *d_count,
-                                    uint32_t n_upper, void *d_out, const float *const_rot = nullptr,
-                                    const uint32_t *d_rold = nullptr, const FwType *derived = nullptr, const float *keys = nullptr,
-                                    uint32_t life_plane = 0xFFFFFFFFu, float life_const = 0.0f, uint32_t cpl = 0u);
-// fills the rotation plane of both buffers of a segment (a type leaves FW_TYPE_NOSPIN)
-hipError_t fw_launch_fill_rotation(hipStream_t s, char *buf0, char *buf1, uint32_t capacity, const float rot[4], bool cpl);
-// seg_ids: host array; d_part: device scratch of 256 * 8 floats; h_out8: PINNED host {min.xyz, any, max.xyz, -}
-// seg_heads: ring heads of the segments (host array, or null = all 0); seg_range_y (or null): per segment 0xFFFFFFFF, or --
-// a range ring -- anything else: seg_heads[i] is then the slot of its first young particle (see fw_launch_pack_instances)
-hipError_t fw_launch_aabb(hipStream_t s, const FwGlobals &g, const uint32_t *seg_ids, const uint32_t *seg_heads, uint32_t n_segs,
-                          uint32_t parity, float *d_part, float *h_out8, const uint32_t *seg_range_y = nullptr,
-                          const uint32_t *seg_life_plane = nullptr, const float *seg_life_const = nullptr);
+// ParticleInstance records of the first min(*d_count, n_upper) particles of a segment (the count is the device's: no synchronisation)
+hipError_t fw_launch_pack_instances(hipStream_t s, const FwSegView &v, const uint32_t *d_count, uint32_t n_upper, void *d_out);
+// box of position -/+ scale over up to eight segments: seg_ids, views: host arrays of n_segs (views[i] for buffer `parity` of
+// seg_ids[i]); d_part: device scratch of 256 * 8 floats; h_out8: PINNED host {min.xyz, any, max.xyz, -}
+hipError_t fw_launch_aabb(hipStream_t s, const FwGlobals &g, const uint32_t *seg_ids, const FwSegView *views, uint32_t n_segs,
+                          uint32_t parity, float *d_part, float *h_out8);
 // the same query answered from the per-tile boxes of the last update (epoch = that update's)
 hipError_t fw_launch_aabb_from_tiles(hipStream_t s, const FwGlobals &g, const uint32_t *seg_ids, uint32_t n_segs,
                                      uint32_t parity, uint32_t epoch, const uint32_t *d_seg_tile_first, float *h_out8);
