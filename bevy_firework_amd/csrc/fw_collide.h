@@ -15,9 +15,9 @@ struct alignas(16) FwCollider {
     float bound;           // radius of a sphere around `position` that contains the collider (INFINITY for a plane): set by the host
                            // (fw_ctx_set_colliders); lets a wave skip a collider none of its rays can reach (fw_cast_ray)
     float position[4];
-    float rotation[4];     // xyzw (BOX, CYLINDER, CONE)
+    float rotation[4];     // xyzw (BOX, CYLINDER, CONE, CAPSULE)
     float normal[4];       // PLANE
-    float half_extents[4]; // BOX; [1] = half the height of a CYLINDER / CONE (their axis is the local Y axis)
+    float half_extents[4]; // BOX; [1] = half the height of a CYLINDER / CONE, half the segment of a CAPSULE (their axis is the local Y axis)
 };
 
 // one placed instance of a collider mesh (fw_ctx_set_mesh_colliders); the mesh's hierarchy and triangles in the layout of fw_bvh.h
@@ -84,7 +84,7 @@ FW_HD bool fw_ray_collider(const FwCollider &c, fw_v3 origin, fw_v3 dir, float m
         *hit = FwRayHit{t, fw_normalize3(p)};
         return true;
     }
-    // BOX, CYLINDER, CONE: solids with a frame of their own.  The ray is taken into that frame ONCE, each kind finds where the ray
+    // BOX, CYLINDER, CONE, CAPSULE: solids with a frame of their own.  The ray is taken into that frame ONCE, each kind finds where the ray
     // enters (distance + the surface normal there, in the frame), and the normal is taken back ONCE: three inlined copies of the
     // rotations took the colliding ring kernels from 113 to 141 VGPRs (4 -> 3 waves per SIMD).
     const fw_q4 q{c.rotation[0], c.rotation[1], c.rotation[2], c.rotation[3]};
@@ -182,6 +182,49 @@ FW_HD bool fw_ray_collider(const FwCollider &c, fw_v3 origin, fw_v3 dir, float m
             const fw_v3 g{w.x, -(k2 * w.y), w.z};  // gradient of x^2 + z^2 - k^2 y^2: outward on the lower nappe
             nl = (g.x == 0.0f && g.y == 0.0f && g.z == 0.0f) ? fw_v3{0.0f, 1.0f, 0.0f} : fw_normalize3(g);
         }
+    } else if (c.kind == 5) {
+        // CAPSULE (avian Collider::capsule(radius, length), parry's Capsule): every point within `radius` of the segment from
+        // (0, -hl, 0) to (0, +hl, 0); hl = half the SEGMENT.  The header's INSIDE / ENTRY / NORMAL, operation by operation.
+        const float hl = c.half_extents[1], rr = c.radius * c.radius;
+        const float xz = ol.x * ol.x + ol.z * ol.z;
+        {
+            const float yc = ol.y < -hl ? -hl : (ol.y > hl ? hl : ol.y);  // the nearest point of the segment
+            const float dy = ol.y - yc;
+            if ((xz + dy * dy) - rr <= 0.0f) {  // inside (or on) the solid
+                *hit = FwRayHit{0.0f, fw_v3{0.0f, 0.0f, 0.0f}};
+                return true;
+            }
+        }
+        // the boundary of the convex solid is the lateral surface and the outer hemispheres of the two caps: the smallest valid near
+        // root, in that order (a later piece only when strictly nearer).  Kept as one distance and which piece holds it: the normal
+        // is formed once, below, for whichever piece won.
+        float best = INFINITY;
+        int piece = -1;  // 0 the lateral surface, 1 the bottom cap, 2 the top cap
+        {
+            const float a = dl.x * dl.x + dl.z * dl.z, b = ol.x * dl.x + ol.z * dl.z;
+            const float disc = b * b - a * (xz - rr);
+            if (a != 0.0f && disc >= 0.0f) {
+                const float t = (-b - sqrtf(disc)) / a;
+                if (t >= 0.0f && fabsf(ol.y + dl.y * t) <= hl) best = t, piece = 0;
+            }
+        }
+        // (the two caps run the same instructions on cy = -hl, +hl: the sphere kind's quadratic about the cap's centre)
+#pragma unroll
+        for (int k = 1; k <= 2; k++) {
+            const float cy = k == 1 ? -hl : hl;
+            const fw_v3 w{ol.x, ol.y - cy, ol.z};
+            const float bs = fw_dot3(w, dl);
+            if (bs > 0.0f) continue;  // outside and moving away
+            const float as = fw_dot3(dl, dl);
+            const float delta = bs * bs - as * (fw_dot3(w, w) - rr);
+            if (!(delta >= 0.0f)) continue;
+            const float t = (-bs - sqrtf(delta)) / as;
+            const float y = ol.y + dl.y * t;
+            if (t >= 0.0f && (k == 1 ? y <= -hl : y >= hl) && t < best) best = t, piece = k;
+        }
+        if (piece < 0 || !(best <= max_distance)) return false;
+        t_hit = best;
+        nl = fw_normalize3(fw_v3{ol.x + dl.x * best, piece == 0 ? 0.0f : (ol.y + dl.y * best) - (piece == 1 ? -hl : hl), ol.z + dl.z * best});
     } else {
         // BOX: slabs in the box's own frame
         // (the three slabs written out one by one, in axis order: indexed arrays of three would live in scratch memory on the device)

@@ -505,8 +505,10 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
 #ifndef FW_FIFO_WAVES
 #define FW_FIFO_WAVES 1
 #endif
+// (the colliding one-round instantiations sit at the 128-register step: with the capsule arm in the cast the instance-writing ones took
+// 130 registers, 4 -> 3 waves per SIMD, until they were asked for four waves like the plain ones -- 128 again, no scratch)
 template <bool INST, int WM, int NT = 0, int COLL = 0, int TR = FW_ROUNDS>
-__global__ __launch_bounds__(FW_BLOCK) __attribute__((amdgpu_waves_per_eu((!INST && !COLL && TR == FW_ROUNDS) ? FW_FIFO_WAVES : (!INST && COLL == 1 && TR == 1) ? 4 : 1)))
+__global__ __launch_bounds__(FW_BLOCK) __attribute__((amdgpu_waves_per_eu((!INST && !COLL && TR == FW_ROUNDS) ? FW_FIFO_WAVES : (COLL == 1 && TR == 1) ? 4 : 1)))
 void fw_k_update_fifo(FwGlobals g, FwFifoArgs a, FwInlineOps inl) {
     fw_update_fifo_body<INST, WM, NT, COLL, TR, false>(g, a, inl);
 }

@@ -225,13 +225,14 @@ class ParticleCollisionSettings:
     filter_mask: int = 0xFFFFFFFF
 
 
-COLLIDER_PLANE, COLLIDER_SPHERE, COLLIDER_BOX, COLLIDER_CYLINDER, COLLIDER_CONE = 0, 1, 2, 3, 4
+COLLIDER_PLANE, COLLIDER_SPHERE, COLLIDER_BOX, COLLIDER_CYLINDER, COLLIDER_CONE, COLLIDER_CAPSULE = 0, 1, 2, 3, 4, 5
 
 
 @dataclass(frozen=True)
 class Collider:
     """One analytic collider of the world particle_collision casts its rays into (core.rs:744-800).  The reference
-    asks avian's SpatialQuery; this backend keeps a device-resident set of planes / spheres / boxes instead
+    asks avian's SpatialQuery; this backend keeps a device-resident set of planes / spheres / boxes / cylinders / cones /
+    capsules instead
     (include/firework_hip.h: fw_collider has the ray-cast semantics)."""
 
     kind: int
@@ -269,6 +270,41 @@ class Collider:
         """avian's Collider::cone(radius, height) (examples/textures.rs:211): base disc at local y = -height / 2, apex at +height / 2"""
         return Collider(COLLIDER_CONE, tuple(float(c) for c in center), tuple(float(c) for c in rotation), radius=float(radius),
                         half_extents=(0.0, float(height) * 0.5, 0.0), layers=layers)
+
+    @staticmethod
+    def Capsule(center: Vec3, radius: float, length: float, rotation: Quat = QUAT_IDENTITY, layers: int = 1) -> "Collider":
+        """avian's Collider::capsule(radius, length): every point within ``radius`` of a segment of ``length`` along the collider's
+        local Y (half_extents[1] = length / 2: half the SEGMENT, parry's half_height -- not half the total height)"""
+        return Collider(COLLIDER_CAPSULE, tuple(float(c) for c in center), tuple(float(c) for c in rotation), radius=float(radius),
+                        half_extents=(0.0, float(length) * 0.5, 0.0), layers=layers)
+
+    @staticmethod
+    def CapsuleEndpoints(a: Vec3, b: Vec3, radius: float, layers: int = 1) -> "Collider":
+        """avian's Collider::capsule_endpoints(radius, a, b): the segment from ``a`` to ``b``.  position = the midpoint, rotation = the
+        arc from +Y to b - a (the identity when a == b, half a turn about X when b - a points straight down), in float32 operation by operation as firework::Collider::capsule_endpoints
+        does it, so that both mirrors hand the library the same bits"""
+        f = np.float32
+        a, b = np.asarray(a, dtype=f), np.asarray(b, dtype=f)
+        mid = ((a + b).astype(f) * f(0.5)).astype(f)
+        d = (b - a).astype(f)
+        ln = np.sqrt(f(f(f(d[0] * d[0]) + f(d[1] * d[1])) + f(d[2] * d[2]))).astype(f)
+        rot = (0.0, 0.0, 0.0, 1.0)
+        if ln > 0:
+            u = (d / ln).astype(f)
+            # (cross(+Y, u), 1 + dot(+Y, u)), normalised; below the equator 1 + u.y cancels, and (u.x^2 + u.z^2) / (1 - u.y) is
+            # the same number without the cancellation; nothing left of it -- b - a along -Y -- is half a turn about X
+            s2 = f(f(u[2] * u[2]) + f(u[0] * u[0]))
+            w = f(f(1.0) + u[1]) if u[1] >= 0 else f(s2 / f(f(1.0) - u[1]))
+            n2 = f(s2 + f(w * w))
+            if n2 > 0:
+                inv = f(f(1.0) / np.sqrt(n2).astype(f))
+                rot = (float(f(u[2] * inv)), 0.0, float(f(f(-u[0]) * inv)), float(f(w * inv)))
+            else:
+                rot = (1.0, 0.0, 0.0, 0.0)
+        else:
+            ln = f(0.0)
+        return Collider(COLLIDER_CAPSULE, tuple(float(c) for c in mid), rot, radius=float(radius),
+                        half_extents=(0.0, float(f(ln * f(0.5))), 0.0), layers=layers)
 
 
 @dataclass(frozen=True)

@@ -139,6 +139,27 @@ def stress_test_collision(rate: float = 80000.0):
     return ParticleSpawner([ps], [es]), tf, colliders
 
 
+def stress_test_collision_capsules(rate: float = 80000.0):
+    """stress_test_collision's spawner over the example's ground slab and, in the angled cube's place, a handful of capsules -- what a
+    character and the limbs of a ragdoll put into an avian world: two standing, two lying (one by its endpoints), two rotated off
+    every axis, all within the fountain's reach.  Returns (spawner, transform, colliders)."""
+    spawner, tf, boxes = stress_test_collision(rate)
+    h = math.pi / 8.0
+    tilt = _quat_mul((math.sin(h), 0.0, 0.0, math.cos(h)), (0.0, math.sin(h), 0.0, math.cos(h)))  # the angled cube's rotation
+    lean = _quat_mul((0.0, 0.0, math.sin(0.3), math.cos(0.3)), (math.sin(-0.2), 0.0, 0.0, math.cos(-0.2)))
+    lying = (0.0, 0.0, math.sin(math.pi / 4.0), math.cos(math.pi / 4.0))  # Quat::from_rotation_z(PI / 2.): the axis along X
+    colliders = [
+        boxes[0],                                                          # the ground slab
+        Collider.Capsule((0.0, 0.9, 0.0), 0.4, 1.0),                       # standing where the cube stood
+        Collider.Capsule((-1.5, 0.75, 1.0), 0.25, 1.0),                    # standing, thinner
+        Collider.Capsule((1.5, 0.3, -1.5), 0.3, 1.5, lying),               # lying on the slab
+        Collider.CapsuleEndpoints((-2.5, 0.2, -2.0), (-0.5, 0.2, -2.5), 0.2),  # lying, by its endpoints
+        Collider.Capsule((2.5, 1.2, 1.0), 0.3, 1.6, tilt),                 # rotated off every axis
+        Collider.Capsule((-0.5, 1.6, -0.8), 0.15, 1.2, lean),              # a thin limb, leaning
+    ]
+    return spawner, tf, colliders
+
+
 # ---- the reference's remaining examples (examples/*.rs), settings only: what a user of the crate actually runs ---------------
 SPARKS_GRADIENT = [  # examples/sparks.rs:58-64, examples/on_demand.rs:62-68
     (0.0, (150.0, 100.0, 15.0, 1.0)), (0.7, (3.0, 1.0, 1.0, 1.0)), (0.8, (1.0, 0.3, 0.3, 1.0)),

@@ -6,7 +6,9 @@
 // vertices handed over in DEVICE memory (update_mesh_vertices_device: copied there on the context's stream, no wait) and one more
 // line, the device's verdict on the sheet's updates (mesh_update_status); `query` is `mesh` with a batch of 512 rays cast into the
 // collider world behind every tenth frame (cast_rays, and cast_rays_device through device buffers of its own) and one more line
-// per such frame: the rays that hit something and the digest of the hit records of either form.  Prints, every tenth frame, the live counts and an
+// per such frame: the rays that hit something and the digest of the hit records of either form; `capsule` is a scenario of its own -- a
+// small fixed world of capsules (both constructors, identity and rotated, one on another layer) over a ground slab, one colliding
+// spawner, a batch of rays every tenth frame (tests/test_cpp_host_capsule.py runs the same through the Python mirror).  Prints, every tenth frame, the live counts and an
 // FNV-1a digest of every particle record; tests/test_cpp_host.py runs the same scenario through the Python mirror and
 // expects the same lines: both mirrors marshal the reference's settings into the C ABI the same way.
 //
@@ -27,7 +29,67 @@ static uint64_t fnv(const void *p, size_t n, uint64_t h = 1469598103934665603ull
     return h;
 }
 
+// `mirror_check capsule`: Collider::capsule / Collider::capsule_endpoints through set_colliders, particles that bounce off them, rays
+// that name them
+static int capsule_scenario() {
+    try {
+        ParticleSystemPlugin app(0, /*seed*/ 0x00C0FFEE);
+        const std::vector<Collider> world = {
+            Collider::Box({0.0f, -0.5f, 0.0f}, {4.0f, 0.5f, 4.0f}),
+            Collider::capsule({0.25f, 0.875f, 0.125f}, 0.375f, 1.0f),
+            Collider::capsule({-0.75f, 1.0f, 0.5f}, 0.25f, 1.5f, Quat{0.30151135f, 0.0f, 0.30151135f, 0.90453404f}, 3u),
+            Collider::capsule_endpoints({-1.0f, 0.25f, -1.0f}, {1.5f, 0.5f, -0.375f}, 0.1875f),
+            Collider::capsule_endpoints({1.0f, 2.0f, 1.0f}, {1.125f, 0.75f, 1.0f}, 0.125f, 2u),
+            Collider::capsule_endpoints({2.0f, 0.5f, 0.0f}, {2.0f, 0.5f, 0.0f}, 0.5f)};
+        app.set_colliders(world);
+        ParticleSpawner sp;
+        sp.particle_settings.resize(1);
+        {
+            ParticleSettings &p = sp.particle_settings[0];
+            p.lifetime = RandF32::constant(0.75f);
+            p.linear_drag = 0.125f;
+            p.has_collision_settings = true;
+            p.collision_settings = ParticleCollisionSettings{0.5f, 0.25f, false, 1u};
+        }
+        sp.emission_settings.resize(1);
+        {
+            EmissionSettings &e = sp.emission_settings[0];
+            e.particle_index = 0;
+            e.emission_pacing = EmissionPacing::rate(2000.0f);
+            e.emission_shape = EmissionShape::Sphere(0.75f);
+            e.initial_velocity = {{1.0f, 6.0f}, {0.0f, -1.0f, 0.0f}, 0.0f};
+        }
+        ParticleSpawnerData *d = app.spawn(sp, Transform{{0.25f, 3.0f, 0.125f}, {}}, 7u);
+        std::vector<fw_ray> rays(256);
+        for (size_t i = 0; i < rays.size(); i++) {
+            fw_ray &r = rays[i];
+            r.origin[0] = -2.0f + (float)(i % 16) * 0.25f, r.origin[1] = 3.0f, r.origin[2] = -1.5f + (float)(i / 16) * 0.1875f;
+            r.max_distance = 6.0f;
+            r.dir[0] = i % 2 ? 0.6f : 0.0f, r.dir[1] = i % 2 ? -0.8f : -1.0f, r.dir[2] = 0.0f;
+            r.filter_mask = 1u + (uint32_t)(i % 3);
+        }
+        const float dt = 1.0f / 60.0f;
+        for (int fr = 0; fr < 40; fr++) {
+            app.update(dt);
+            if (fr % 10 != 9) continue;
+            const auto ps = d->particles(0);
+            const std::vector<fw_ray_hit> hits = app.cast_rays(rays);
+            unsigned per[6] = {0, 0, 0, 0, 0, 0};
+            for (const fw_ray_hit &h : hits)
+                if (h.kind == FW_HIT_COLLIDER && h.index < 6) per[h.index]++;
+            std::printf("frame %d count %u %016llx hits %u %u %u %u %u %u %016llx\n", fr, d->counts()[0],
+                        (unsigned long long)fnv(ps.data(), ps.size() * sizeof(fw_particle)), per[0], per[1], per[2], per[3], per[4], per[5],
+                        (unsigned long long)fnv(hits.data(), hits.size() * sizeof(fw_ray_hit)));
+        }
+    } catch (const Error &e) {
+        std::fprintf(stderr, "firework error %d: %s\n", (int)e.status, e.what());
+        return 1;
+    }
+    return 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc > 1 && std::strcmp(argv[1], "capsule") == 0) return capsule_scenario();
     // `mirror_check mesh`: the same scenario with triangle meshes in the collider world (create, place twice, replace, destroy)
     // `mirror_check deform`: ... with both meshes deformable: the ramp's far edge rises every fifth frame, then the sheet's apex
     // `mirror_check deform_device`: ... with those vertices taken from device memory

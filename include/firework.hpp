@@ -177,6 +177,36 @@ struct Collider {
         Collider c; c.kind = FW_COLLIDER_CONE, c.position = center, c.radius = radius, c.half_extents = Vec3{0, height * 0.5f, 0};
         c.rotation = rotation, c.layers = layers; return c;
     }
+    // avian's Collider::capsule(radius, length): every point within `radius` of a segment of `length` along the local Y axis
+    // (half_extents.y = length / 2: half the SEGMENT, parry's half_height -- not half the total height)
+    static Collider capsule(Vec3 center, float radius, float length, Quat rotation = {}, uint32_t layers = 1) {
+        Collider c; c.kind = FW_COLLIDER_CAPSULE, c.position = center, c.radius = radius, c.half_extents = Vec3{0, length * 0.5f, 0};
+        c.rotation = rotation, c.layers = layers; return c;
+    }
+    // avian's Collider::capsule_endpoints(radius, a, b): position = the midpoint, rotation = the arc from +Y to b - a (the identity
+    // when a == b; half a turn about X when b - a points along -Y)
+    static Collider capsule_endpoints(Vec3 a, Vec3 b, float radius, uint32_t layers = 1) {
+        Collider c; c.kind = FW_COLLIDER_CAPSULE, c.radius = radius, c.layers = layers;
+        c.position = Vec3{(a.x + b.x) * 0.5f, (a.y + b.y) * 0.5f, (a.z + b.z) * 0.5f};
+        const float dx = b.x - a.x, dy = b.y - a.y, dz = b.z - a.z;
+        const float len = std::sqrt((dx * dx + dy * dy) + dz * dz);
+        if (len > 0.0f) {
+            const float ux = dx / len, uy = dy / len, uz = dz / len;
+            // (cross(+Y, u), 1 + dot(+Y, u)), normalised; below the equator 1 + u.y cancels, and (u.x^2 + u.z^2) / (1 - u.y) is the
+            // same number without the cancellation
+            const float s2 = uz * uz + ux * ux;
+            const float w = uy >= 0.0f ? 1.0f + uy : s2 / (1.0f - uy);
+            const float n2 = s2 + w * w;
+            if (n2 > 0.0f) {
+                const float inv = 1.0f / std::sqrt(n2);
+                c.rotation = Quat{uz * inv, 0.0f, -ux * inv, w * inv};
+            } else {
+                c.rotation = Quat{1.0f, 0.0f, 0.0f, 0.0f};
+            }
+            c.half_extents = Vec3{0, len * 0.5f, 0};
+        }
+        return c;
+    }
 };
 
 // One placed instance of a triangle mesh of the collider world (fw_mesh_collider): `mesh` comes from

@@ -124,18 +124,44 @@ typedef struct fw_particle_settings {
  *           on the lateral surface the radial direction (both rotated by R)
  *   CONE    avian's Collider::cone(radius, height) (examples/textures.rs:211): base disc of `radius` at y = -half_extents[1], apex
  *           at y = +half_extents[1]; solid between them; the base reports -Y, the lateral surface its outward normal
+ *   CAPSULE avian's Collider::capsule(radius, length) (parry's Capsule): in the collider's frame (R, position) the axis is Y; every
+ *           point within `radius` of the segment from (0, -hl, 0) to (0, +hl, 0) is solid.  hl = half_extents[1] is half the length of
+ *           the SEGMENT (parry's half_height), NOT half the total height; hl == 0 is a ball.  The cast, all fp32 with no fused a*b+c
+ *           (dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z), with o = R^-1 (origin - position), d = R^-1 dir (the identity rotation skips
+ *           both products, as for the other framed kinds) and rr = radius * radius:
+ *     INSIDE  yc = min(max(o.y, -hl), hl), evaluated as o.y < -hl ? -hl : (o.y > hl ? hl : o.y); dy = o.y - yc;
+ *             xz = (o.x * o.x) + (o.z * o.z); the origin is inside or on the solid when ((xz + (dy * dy)) - rr) <= 0: distance 0, zero
+ *             normal, like every solid.
+ *     ENTRY   otherwise the solid is convex and its boundary three pieces; the hit is the smallest valid t over them, taken in the
+ *             order lateral surface, bottom cap (cy = -hl), top cap (cy = +hl): a later piece replaces an earlier one only when its t
+ *             is strictly smaller (<), so the earlier piece wins a tie.  Near roots suffice: each cap's whole ball lies inside the
+ *             solid, so a ray from outside meets a cap's sphere first at its near root, and the far root of the lateral surface is an
+ *             exit.
+ *       lateral  the cylinder's quadratic: a = (d.x * d.x) + (d.z * d.z); b = (o.x * d.x) + (o.z * d.z); c2 = xz - rr; no root when
+ *                a == 0 or disc = (b * b) - (a * c2) is not >= 0; t = (-b - sqrt(disc)) / a; valid when t >= 0 and
+ *                |o.y + (d.y * t)| <= hl.
+ *       cap      the sphere's quadratic about the cap's centre (0, cy, 0), operation by operation: w = (o.x, o.y - cy, o.z);
+ *                A = dot(d, d); B = dot(w, d); C = dot(w, w) - rr; no root when B > 0 ("outside and moving away") or
+ *                delta = (B * B) - (A * C) is not >= 0; t = (-B - sqrt(delta)) / A; valid when t >= 0 and the hit point lies on the
+ *                outer hemisphere: y = o.y + (d.y * t) with y <= -hl for the bottom cap, y >= hl for the top cap.  (The sphere's own
+ *                "inside" test is not repeated: INSIDE above has answered it for the whole solid.)
+ *       a hit needs t <= max_distance.
+ *     NORMAL  p = (o.x + (d.x * t), o.y + (d.y * t), o.z + (d.z * t)); v = (p.x, 0, p.z) on the lateral surface, (p.x, p.y - cy, p.z) on
+ *             a cap; n = v * (1 / sqrt(dot(v, v))), rotated by R (not at all under the identity rotation).
+ *     REACH   the sphere around `position` a wave may skip the collider by (fw_ctx_set_colliders computes it) has the radius
+ *             (hl + radius) * 1.0001f; NaN or negative gives INFINITY (never skipped), as for every kind.
  *   a ray that starts inside a solid hits it at distance 0 with a ZERO normal (core.rs:762-771 handles that case);
  *   otherwise the hit is the entry point, its normal the outward surface normal; the nearest hit over all colliders
  *   that pass the filter wins (lowest index on ties). */
-enum { FW_COLLIDER_PLANE = 0, FW_COLLIDER_SPHERE = 1, FW_COLLIDER_BOX = 2, FW_COLLIDER_CYLINDER = 3, FW_COLLIDER_CONE = 4 };
+enum { FW_COLLIDER_PLANE = 0, FW_COLLIDER_SPHERE = 1, FW_COLLIDER_BOX = 2, FW_COLLIDER_CYLINDER = 3, FW_COLLIDER_CONE = 4, FW_COLLIDER_CAPSULE = 5 };
 typedef struct fw_collider {
     int32_t kind;
     uint32_t layers;        /* collision layers (membership bits) */
     float position[3];
-    float rotation[4];      /* xyzw; BOX, CYLINDER, CONE */
+    float rotation[4];      /* xyzw; BOX, CYLINDER, CONE, CAPSULE */
     float normal[3];        /* PLANE only */
-    float radius;           /* SPHERE, CYLINDER, CONE */
-    float half_extents[3];  /* BOX; [1] = half the height of a CYLINDER / CONE */
+    float radius;           /* SPHERE, CYLINDER, CONE, CAPSULE */
+    float half_extents[3];  /* BOX; [1] = half the height of a CYLINDER / CONE, half the SEGMENT of a CAPSULE */
 } fw_collider;
 
 /* Triangle meshes (avian's Collider::trimesh / heightfield / convex hulls, as triangles): a mesh is uploaded once and placed

@@ -2,13 +2,15 @@
 //! analytic colliders and triangle meshes (UNVERIFIED SOURCE: no Rust toolchain in the build image).
 //!
 //! The reference asks avian's `SpatialQuery` (arbitrary parry shapes behind a CPU broadphase, core.rs:756-765).  The backend
-//! keeps planes, spheres, oriented boxes, cylinders and cones on the GPU (`fw_collider`), and triangle meshes placed by
+//! keeps planes, spheres, oriented boxes, cylinders, cones and capsules on the GPU (`fw_collider`), and triangle meshes placed by
 //! instances (`fw_mesh_collider`; ray-cast semantics of both in `include/firework_hip.h`).  Entities opt in with the
 //! `ParticleCollider` marker; both sets are replaced EVERY frame -- the calls do not wait for the frames in flight, a new set
 //! travels as one small copy in the context's stream -- so moving bodies cost what the reference's per-frame query costs.
 //! `Collider::trimesh*`, heightfields and convex polyhedra become meshes: their triangles, scaled by the collider's scale, are
-//! uploaded once per (entity, scale) and freed when the entity (or its collider) goes away.  Capsules and compound shapes have
-//! no counterpart and are still skipped: particles do not collide with them on this path.
+//! uploaded once per (entity, scale) and freed when the entity (or its collider) goes away.  A capsule is the sixth analytic kind
+//! (`FW_COLLIDER_CAPSULE`, mapped from the segment's endpoints and radius); a compound shape is flattened -- each child's isometry
+//! composed with the body's, each child pushed as its own `fw_collider` or mesh instance, and the entity repeated in the parallel
+//! `Vec<Entity>`s (`ColliderEntities`) so that `fw_ray_hit.index` still finds it.
 use super::ffi::*;
 use super::HipBackend;
 use avian3d::prelude::*;
@@ -47,22 +49,63 @@ fn mesh_triangles(shape: &SharedShape) -> Option<(Vec<[f32; 3]>, Vec<[u32; 3]>)>
     }
 }
 
+/// The entities behind the two sets as last sent, in the sets' order: `fw_ray_hit.index` counts in `analytic` (FW_HIT_COLLIDER)
+/// or in `meshes` (FW_HIT_MESH).  A compound's entity appears once per child.
+#[derive(Resource, Default)]
+pub struct ColliderEntities { pub analytic: Vec<Entity>, pub meshes: Vec<Entity> }
+
+/// One analytic primitive placed by `iso` (parry isometry, in the body's frame) under the body's transform `t`; None for a shape
+/// with no analytic counterpart.
+fn analytic_collider(shape: &dyn avian3d::parry::shape::Shape, t: &Transform, iso: Option<&avian3d::parry::math::Isometry<f32>>, layers: u32) -> Option<fw_collider> {
+    // the child's isometry composed with the body's: position = T + R * child.translation, rotation = R * child.rotation
+    let (cp, cr) = iso.map_or((Vec3::ZERO, Quat::IDENTITY), |i| {
+        (Vec3::new(i.translation.x, i.translation.y, i.translation.z), Quat::from_xyzw(i.rotation.i, i.rotation.j, i.rotation.k, i.rotation.w))
+    });
+    let (pos, rot) = (t.translation + t.rotation * cp, t.rotation * cr);
+    let base = fw_collider {
+        kind: 0, layers, position: pos.to_array(), rotation: rot.to_array(), normal: [0., 1., 0.], radius: 0., half_extents: [0.; 3],
+    };
+    if let Some(b) = shape.as_ball() {
+        Some(fw_collider { kind: FW_COLLIDER_SPHERE, radius: b.radius, ..base })                                    // Collider::sphere
+    } else if let Some(c) = shape.as_cuboid() {
+        Some(fw_collider { kind: FW_COLLIDER_BOX, half_extents: [c.half_extents.x, c.half_extents.y, c.half_extents.z], ..base }) // ::cuboid
+    } else if let Some(c) = shape.as_cylinder() {
+        Some(fw_collider { kind: FW_COLLIDER_CYLINDER, radius: c.radius, half_extents: [0., c.half_height, 0.], ..base })   // ::cylinder (textures.rs:195)
+    } else if let Some(c) = shape.as_cone() {
+        Some(fw_collider { kind: FW_COLLIDER_CONE, radius: c.radius, half_extents: [0., c.half_height, 0.], ..base })       // ::cone (textures.rs:211)
+    } else if let Some(c) = shape.as_capsule() {
+        // ::capsule / ::capsule_endpoints: parry keeps the SEGMENT (a, b) and the radius, in any direction of the shape's frame:
+        // position = the midpoint, rotation = the arc from +Y to b - a (the identity for a ball-like capsule, a == b), each under (pos, rot)
+        let (a, b) = (Vec3::new(c.segment.a.x, c.segment.a.y, c.segment.a.z), Vec3::new(c.segment.b.x, c.segment.b.y, c.segment.b.z));
+        let d = b - a;
+        let arc = if d.length() > 0. { Quat::from_rotation_arc(Vec3::Y, d / d.length()) } else { Quat::IDENTITY };
+        Some(fw_collider {
+            kind: FW_COLLIDER_CAPSULE, radius: c.radius, half_extents: [0., 0.5 * d.length(), 0.],
+            position: (pos + rot * ((a + b) * 0.5)).to_array(), rotation: (rot * arc).to_array(), ..base
+        })
+    } else if let Some(h) = shape.as_halfspace() {
+        let n = rot * Vec3::new(h.normal.x, h.normal.y, h.normal.z);
+        Some(fw_collider { kind: FW_COLLIDER_PLANE, normal: n.to_array(), ..base })                                  // ::half_space
+    } else {
+        None
+    }
+}
+
 pub fn hip_sync_colliders(
     backend: NonSend<HipBackend>, excluded: Option<Res<ParticleColliderExclusions>>, mut meshes: Local<MeshCache>,
+    mut entities: ResMut<ColliderEntities>,
     q: Query<(Entity, Ref<Collider>, &GlobalTransform, Option<&CollisionLayers>), With<ParticleCollider>>,
 ) {
     let mut set = Vec::<fw_collider>::new();
     let mut insts = Vec::<fw_mesh_collider>::new();
     let mut stale = Vec::<fw_mesh>::new(); // meshes the new instance set no longer places: freed once it is in
     let mut seen = Vec::<Entity>::new();
+    entities.analytic.clear();
+    entities.meshes.clear();
     for (entity, collider, gt, layers) in &q {
         let t = gt.compute_transform();
         let out = excluded.as_ref().is_some_and(|x| x.0.contains(&entity));
         let layers = if out { 0 } else { layers.map_or(1, |l| l.memberships.0) };
-        let base = fw_collider {
-            kind: 0, layers, position: t.translation.to_array(), rotation: t.rotation.to_array(),
-            normal: [0., 1., 0.], radius: 0., half_extents: [0.; 3],
-        };
         // a mesh-shaped collider: its triangles with the collider's scale baked in (instances carry no scale), cached
         let scale = collider.scale();
         let key = [scale.x.to_bits(), scale.y.to_bits(), scale.z.to_bits()];
@@ -86,21 +129,24 @@ pub fn hip_sync_colliders(
         };
         if let Some(m) = mesh {
             seen.push(entity);
-            insts.push(fw_mesh_collider { mesh: m, layers, position: base.position, rotation: base.rotation });
+            insts.push(fw_mesh_collider { mesh: m, layers, position: t.translation.to_array(), rotation: t.rotation.to_array() });
+            entities.meshes.push(entity);
             continue;
         }
         let shape = collider.shape_scaled();
-        if let Some(b) = shape.as_ball() {
-            set.push(fw_collider { kind: 1, radius: b.radius, ..base });                                          // Collider::sphere
-        } else if let Some(c) = shape.as_cuboid() {
-            set.push(fw_collider { kind: 2, half_extents: [c.half_extents.x, c.half_extents.y, c.half_extents.z], ..base }); // ::cuboid
-        } else if let Some(c) = shape.as_cylinder() {
-            set.push(fw_collider { kind: 3, radius: c.radius, half_extents: [0., c.half_height, 0.], ..base });   // ::cylinder (textures.rs:195)
-        } else if let Some(c) = shape.as_cone() {
-            set.push(fw_collider { kind: 4, radius: c.radius, half_extents: [0., c.half_height, 0.], ..base });   // ::cone (textures.rs:211)
-        } else if let Some(h) = shape.as_halfspace() {
-            let n = t.rotation * Vec3::new(h.normal.x, h.normal.y, h.normal.z);
-            set.push(fw_collider { kind: 0, normal: n.to_array(), ..base });                                       // ::half_space
+        if let Some(compound) = shape.as_compound() {
+            // Collider::compound: a list of placed primitives -- flattened, the entity once per child.  (A mesh-shaped child would be
+            // created and cached like a mesh-shaped collider, keyed by (entity, child index), and pushed to `insts` under the composed
+            // isometry; children with no counterpart are left out like such colliders.)
+            for (iso, child) in compound.shapes() {
+                if let Some(c) = analytic_collider(child.as_ref(), &t, Some(iso), layers) {
+                    set.push(c);
+                    entities.analytic.push(entity);
+                }
+            }
+        } else if let Some(c) = analytic_collider(shape.as_ref(), &t, None, layers) {
+            set.push(c);
+            entities.analytic.push(entity);
         }
     }
     // entities that left the query (despawned, marker or collider removed, or no longer mesh-shaped): their meshes go too

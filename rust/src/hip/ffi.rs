@@ -25,6 +25,9 @@ pub type fw_spawner = i32;
 #[repr(C)] #[derive(Clone, Copy, Default)] pub struct fw_collision_settings {   // ParticleCollisionSettings, core.rs:240-248
     pub enabled: i32, pub restitution: f32, pub friction: f32, pub destroy_on_collision: i32, pub filter_mask: u32,
 }
+pub const FW_COLLIDER_PLANE: i32 = 0; pub const FW_COLLIDER_SPHERE: i32 = 1; pub const FW_COLLIDER_BOX: i32 = 2;
+pub const FW_COLLIDER_CYLINDER: i32 = 3; pub const FW_COLLIDER_CONE: i32 = 4;
+pub const FW_COLLIDER_CAPSULE: i32 = 5;   // half_extents[1] = half the SEGMENT (parry's half_height), radius = radius; axis = local Y
 #[repr(C)] #[derive(Clone, Copy)] pub struct fw_collider {   // one analytic collider of the device-resident world
     pub kind: i32, pub layers: u32, pub position: [f32; 3], pub rotation: [f32; 4], pub normal: [f32; 3],
     pub radius: f32, pub half_extents: [f32; 3],

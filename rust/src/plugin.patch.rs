@@ -6,6 +6,7 @@
 {
     use crate::hip::{hip_frame, hip_notify_finished, hip_sync_spawner_data, HipBackend};
     app.insert_non_send_resource(HipBackend::new(/* device */ 0, /* seed */ rand::random()).expect("libfirework_hip: no usable gfx950 device"))
+        .init_resource::<crate::hip::colliders::ColliderEntities>() // the entities behind fw_ray_hit.index, as last sent
         .add_systems(
             self.update_schedule,
             (

@@ -87,6 +87,11 @@ if "cc" in which:  # examples/stress_test_collision.rs: bouncing particles (at t
     run("stress_test_collision rate 80000 (~157k live)", [(sp, tf)], 130, 600, colliders=world)
     sp, tf, world = workloads.stress_test_collision(640000.0)
     run("stress_test_collision rate 640000 (~1.26M live)", [(sp, tf)], 130, 300, colliders=world)
+if "ccap" in which:  # the same spawner over the slab and six capsules (workloads.stress_test_collision_capsules), the same two rates
+    sp, tf, world = workloads.stress_test_collision_capsules(80000.0)
+    run("stress_test_collision_capsules rate 80000 (~157k live)", [(sp, tf)], 130, 600, colliders=world)
+    sp, tf, world = workloads.stress_test_collision_capsules(640000.0)
+    run("stress_test_collision_capsules rate 640000 (~1.26M live)", [(sp, tf)], 130, 300, colliders=world)
 if "r1" in which:  # the reference's stress_test with a lifetime RANGE (0.8-1.2 s): one mid-size range ring
     from bevy_firework_amd import settings as _S
     for rate in (160000.0, 500000.0):

@@ -3,7 +3,8 @@
   python tools/ray_queries.py all                 every world below: the device form at 1M rays, the host form at 1k / 64k / 1M
   python tools/ray_queries.py one WORLD [N]       the device form alone, 30 calls (the rocprofv3 --kernel-trace --stats target)
 
-Worlds are those of tools/mesh_colliders.py: `analytic` (the two boxes of stress_test_collision), `terrain32` (2 048 triangles)
+Worlds are those of tools/mesh_colliders.py: `analytic` (the two boxes of stress_test_collision), `capsules` (the slab and six capsules of
+stress_test_collision_capsules), `terrain32` (2 048 triangles)
 and `terrain256` (131 072 triangles; the cube stays analytic).  Rays: origins uniform over the scene, unit directions, two
 lengths -- `short` like a particle's step (max_distance in [0.02, 0.3], what the colliding update casts) and `long` (8: across
 the scene).  Device form: 5 warm-up calls, then the best of 5 windows of 20 calls, each ending in a synchronise.  Host form: the
@@ -29,6 +30,9 @@ def _world(ps, world):
     _, _, colliders = workloads.stress_test_collision(rate=80000.0)
     if world == "analytic":
         ps.set_colliders(colliders)
+        return 0
+    if world == "capsules":  # the slab and the six capsules of workloads.stress_test_collision_capsules
+        ps.set_colliders(workloads.stress_test_collision_capsules(rate=80000.0)[2])
         return 0
     v, t = _terrain(int(world[len("terrain"):]))
     ps.set_mesh_colliders([S.MeshCollider(ps.create_mesh(v, t))])
@@ -94,7 +98,7 @@ def main():
     if mode == "one":
         print(json.dumps(measure(sys.argv[2], int(sys.argv[3]) if len(sys.argv) > 3 else 1000000, host_sizes=(), windows=1, calls=30)), flush=True)
     elif mode == "all":
-        for world in ("analytic", "terrain32", "terrain256"):
+        for world in ("analytic", "capsules", "terrain32", "terrain256"):
             r = measure(world)
             for length in ("short", "long"):
                 x = r[length]
