@@ -78,6 +78,15 @@ class RayHit(C.Structure):
                 ("triangle", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class Point(C.Structure):
+    _fields_ = [("position", C.c_float * 3), ("filter_mask", C.c_uint32)]
+
+
+class PointProjection(C.Structure):
+    _fields_ = [("point", C.c_float * 3), ("distance", C.c_float), ("kind", C.c_int32), ("index", C.c_uint32),
+                ("triangle", C.c_uint32), ("is_inside", C.c_uint32)]
+
+
 def make_mesh_colliders(instances):
     arr = (MeshCollider * max(len(instances), 1))()
     for d, m in zip(arr, instances):
@@ -252,6 +261,8 @@ SYMBOLS = [
     ("fw_ctx_set_mesh_colliders", C.c_int, [_P, C.POINTER(MeshCollider), C.c_uint32]),
     ("fw_ctx_cast_rays", C.c_int, [_P, _P, C.c_uint64, _P]),
     ("fw_ctx_cast_rays_device", C.c_int, [_P, _P, C.c_uint64, _P]),
+    ("fw_ctx_project_points", C.c_int, [_P, _P, C.c_uint64, _P]),
+    ("fw_ctx_project_points_device", C.c_int, [_P, _P, C.c_uint64, _P]),
     ("fw_spawner_create", C.c_int, [_P, C.POINTER(SpawnerDesc), C.POINTER(C.c_int32)]),
     ("fw_spawner_update_settings", C.c_int, [_P, C.c_int32, C.POINTER(SpawnerDesc)]),
     ("fw_spawner_destroy", C.c_int, [_P, C.c_int32]),

@@ -26,7 +26,7 @@
 //   fw_engine_mesh.cpp   the collider meshes: fw_ctx_create_mesh / fw_ctx_create_deformable_mesh / fw_ctx_update_mesh_vertices /
 //                        fw_ctx_destroy_mesh / fw_ctx_set_mesh_colliders (the
 //                        hierarchy itself is built by fw_bvh.cpp, plain C++)
-//   fw_engine_query.cpp  the ray-cast query into the collider world: fw_ctx_cast_rays / fw_ctx_cast_rays_device
+//   fw_engine_query.cpp  the queries into the collider world: fw_ctx_cast_rays[_device], fw_ctx_project_points[_device]
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -1011,8 +1011,9 @@ struct fw_ctx {
     HipEvent ev_mesh[2];
     bool mesh_pending[2] = {false, false};
     uint64_t mesh_seq = 0;
-    // the host form of the ray-cast query (fw_engine_query.cpp): pinned staging and device buffers for rays and hits, 32 bytes per
-    // record each, grown on demand and kept; the device form needs nothing of its own
+    // the host forms of the queries (fw_engine_query.cpp): pinned staging and device buffers for rays and hits, 32 bytes per
+    // record each (points in, 16 bytes each, and projections out share them), grown on demand and kept; the device forms need
+    // nothing of their own
     HipBuf<float4> h_rays, h_hits, d_rays, d_hits;
     HipBuf<float> d_aabb;      // 256 partial boxes of the AABB query
     HipBuf<float> h_aabb;      // pinned result {min.xyz, any, max.xyz, -}

@@ -11,9 +11,14 @@
 // reports active lanes only -- which is exactly "no ray that takes part can reach this collider".  Lanes past n leave before the
 // first load: they are inactive for the whole cast, so they load nothing, store nothing and keep no collider alive for the rest
 // of their wave.  Nothing here waits for another workgroup and there is no barrier, so the early exit is safe.
+//
+// The point query (fw_ctx_project_points / fw_ctx_project_points_device) has the same shape: one point per lane, a point one 16-byte
+// load (fw_point), a projection two 16-byte stores (fw_point_projection), the arithmetic fw_project_point of fw_project.h and none
+// here; its wave skips count active lanes in the same way.
 #include <hip/hip_runtime.h>
 
 #include "fw_kernels.h"
+#include "fw_project.h"
 
 #define FW_QUERY_BLOCK 256
 #define FW_QUERY_MAX_LAUNCH (1ull << 30)  // rays per launch: lane indices and the grid stay well inside 32 bits
@@ -45,6 +50,36 @@ hipError_t fw_launch_cast_rays(hipStream_t s, const FwGlobals &g, const void *d_
             hipLaunchKernelGGL(fw_k_cast_rays<true>, grid, block, 0, s, g.colliders, g.n_colliders, g.mesh_inst, g.n_mesh_inst, rays, cnt, hits);
         else
             hipLaunchKernelGGL(fw_k_cast_rays<false>, grid, block, 0, s, g.colliders, g.n_colliders, g.mesh_inst, 0u, rays, cnt, hits);
+    }
+    return hipGetLastError();
+}
+
+template <bool MESH>
+__global__ __launch_bounds__(FW_QUERY_BLOCK) void fw_k_project_points(const FwCollider *colliders, uint32_t n_colliders, const FwMeshInst *meshes,
+                                                                      uint32_t n_mesh, const float4 *points, uint32_t n, float4 *out) {
+    const uint32_t i = blockIdx.x * FW_QUERY_BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const float4 a = points[i];  // {position, filter_mask}
+    FwProjection p;
+    FwHitId id;
+    fw_project_point(colliders, n_colliders, MESH ? meshes : nullptr, MESH ? n_mesh : 0u, __builtin_bit_cast(uint32_t, a.w), fw_v3{a.x, a.y, a.z}, &p, id);
+    // (nobody answered: the projection left its result and the policy as they start -- point 0, distance 0, FW_HIT_NONE, index = triangle = ~0)
+    out[2 * (size_t)i] = float4{p.point.x, p.point.y, p.point.z, p.distance};
+    out[2 * (size_t)i + 1] = float4{__builtin_bit_cast(float, id.kind), __builtin_bit_cast(float, id.index), __builtin_bit_cast(float, id.tri),
+                                    __builtin_bit_cast(float, p.is_inside)};
+}
+
+hipError_t fw_launch_project_points(hipStream_t s, const FwGlobals &g, const void *d_points, uint64_t n, void *d_out) {
+    const bool mesh = g.n_mesh_inst != 0u;
+    for (uint64_t first = 0; first < n; first += FW_QUERY_MAX_LAUNCH) {
+        const uint32_t cnt = (uint32_t)(n - first < FW_QUERY_MAX_LAUNCH ? n - first : FW_QUERY_MAX_LAUNCH);
+        const float4 *points = static_cast<const float4 *>(d_points) + first;
+        float4 *out = static_cast<float4 *>(d_out) + 2 * first;
+        const dim3 grid((cnt + FW_QUERY_BLOCK - 1) / FW_QUERY_BLOCK), block(FW_QUERY_BLOCK);
+        if (mesh)
+            hipLaunchKernelGGL(fw_k_project_points<true>, grid, block, 0, s, g.colliders, g.n_colliders, g.mesh_inst, g.n_mesh_inst, points, cnt, out);
+        else
+            hipLaunchKernelGGL(fw_k_project_points<false>, grid, block, 0, s, g.colliders, g.n_colliders, g.mesh_inst, 0u, points, cnt, out);
     }
     return hipGetLastError();
 }

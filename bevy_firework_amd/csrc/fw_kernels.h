@@ -432,3 +432,6 @@ hipError_t fw_launch_mesh_spheres(hipStream_t s, FwMeshInst *d_inst, uint32_t n_
 // The ray-cast query (fw_k_query.hip; fw_ctx_cast_rays[_device]): n fw_ray records at d_rays -> n fw_ray_hit records at d_hits, both
 // device memory, against g's collider world as of the launch's place in stream s (launches of at most 2^30 rays each).
 hipError_t fw_launch_cast_rays(hipStream_t s, const FwGlobals &g, const void *d_rays, uint64_t n, void *d_hits);
+// The point query (fw_k_query.hip; fw_ctx_project_points[_device]): n fw_point records (16 bytes) at d_points -> n fw_point_projection
+// records (32 bytes) at d_out, in the same way.
+hipError_t fw_launch_project_points(hipStream_t s, const FwGlobals &g, const void *d_points, uint64_t n, void *d_out);

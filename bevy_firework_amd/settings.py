@@ -441,3 +441,23 @@ RAY_HIT_DTYPE = np.dtype(
     ]
 )
 assert RAY_HIT_DTYPE.itemsize == 32
+
+# fw_point / fw_point_projection (include/firework_hip.h: POINT QUERIES): the records of ParticleSystem.project_points
+POINT_DTYPE = np.dtype(
+    [
+        ("position", np.float32, 3),
+        ("filter_mask", np.uint32),
+    ]
+)
+assert POINT_DTYPE.itemsize == 16
+POINT_PROJECTION_DTYPE = np.dtype(
+    [
+        ("point", np.float32, 3),
+        ("distance", np.float32),
+        ("kind", np.int32),
+        ("index", np.uint32),
+        ("triangle", np.uint32),
+        ("is_inside", np.uint32),
+    ]
+)
+assert POINT_PROJECTION_DTYPE.itemsize == 32

@@ -301,6 +301,31 @@ class ParticleSystem:
         self._check(self._lib.fw_ctx_cast_rays_device(self._ctx, C.c_void_p(int(rays_ptr)) if rays_ptr else None, int(n),
                                                       C.c_void_p(int(hits_ptr)) if hits_ptr else None))
 
+    def project_points(self, positions, masks) -> np.ndarray:
+        """SpatialQuery::project_point (solid = true) for a batch: positions [n, 3], masks [n] or a scalar -> a structured array
+        (settings.POINT_PROJECTION_DTYPE): the nearest point of the collider world as it stands behind every call made so far,
+        its distance, who owns it (kind / index / triangle as cast_rays reports them) and is_inside (1: the position lies inside
+        or on the analytic solid named -- point_intersections' question; point is then the position, distance 0).  Synchronises."""
+        p = np.asarray(positions, dtype=np.float32).reshape(-1, 3)
+        points = np.zeros(len(p), dtype=S.POINT_DTYPE)
+        points["position"] = p
+        points["filter_mask"] = np.asarray(masks, dtype=np.uint32)
+        return self.project_point_records(points)
+
+    def project_point_records(self, points: np.ndarray) -> np.ndarray:
+        """project_points for points that are already settings.POINT_DTYPE records"""
+        points = np.ascontiguousarray(points, dtype=S.POINT_DTYPE)
+        out = np.zeros(len(points), dtype=S.POINT_PROJECTION_DTYPE)
+        self._check(self._lib.fw_ctx_project_points(self._ctx, points.ctypes.data_as(C.c_void_p), len(points), out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def project_points_device(self, points_ptr: int, n: int, out_ptr: int) -> None:
+        """project_points for n settings.POINT_DTYPE records at device address points_ptr into n settings.POINT_PROJECTION_DTYPE
+        records at out_ptr: enqueued on this context's stream, never synchronises; the buffers are read and written only by work
+        enqueued inside the call."""
+        self._check(self._lib.fw_ctx_project_points_device(self._ctx, C.c_void_p(int(points_ptr)) if points_ptr else None, int(n),
+                                                           C.c_void_p(int(out_ptr)) if out_ptr else None))
+
     # -- ECS-like surface ------------------------------------------------------------------------
     def spawn(self, spawner: S.ParticleSpawner, transform: Optional[S.Transform] = None,
               global_transform: Optional[S.Transform] = None, modifier: Optional[S.EffectModifier] = None,

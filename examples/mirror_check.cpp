@@ -8,7 +8,10 @@
 // collider world behind every tenth frame (cast_rays, and cast_rays_device through device buffers of its own) and one more line
 // per such frame: the rays that hit something and the digest of the hit records of either form; `capsule` is a scenario of its own -- a
 // small fixed world of capsules (both constructors, identity and rotated, one on another layer) over a ground slab, one colliding
-// spawner, a batch of rays every tenth frame (tests/test_cpp_host_capsule.py runs the same through the Python mirror).  Prints, every tenth frame, the live counts and an
+// spawner, a batch of rays every tenth frame (tests/test_cpp_host_capsule.py runs the same through the Python mirror); `project` is
+// another -- a fixed small world (one collider of each kind plus one mesh instance), a fixed list of points projected onto it
+// (project_points, and project_points_device through device buffers of its own), every field's bits printed per point
+// (tests/test_cpp_host_project.py).  Prints, every tenth frame, the live counts and an
 // FNV-1a digest of every particle record; tests/test_cpp_host.py runs the same scenario through the Python mirror and
 // expects the same lines: both mirrors marshal the reference's settings into the C ABI the same way.
 //
@@ -88,7 +91,52 @@ static int capsule_scenario() {
     return 0;
 }
 
+// `mirror_check project`: one collider of each kind and one mesh instance, 96 points on a lattice through and around them (every
+// operand exact in fp32), the three filter masks by turns; one line per point with the bits of every field of its projection
+static int project_scenario() {
+    try {
+        ParticleSystemPlugin app(0, /*seed*/ 0x00C0FFEE);
+        app.set_colliders({Collider::Plane({0.0f, -1.0f, 0.0f}, {0.0f, 1.0f, 0.0f}), Collider::Sphere({1.0f, 0.5f, 0.0f}, 0.75f, 2u),
+                           Collider::Box({-2.0f, 0.0f, 0.0f}, {0.5f, 1.0f, 0.5f}, Quat{0.0f, 0.38268343f, 0.0f, 0.92387953f}),
+                           Collider::Cylinder({0.0f, 0.5f, -2.0f}, 0.5f, 1.5f, {}, 3u),
+                           Collider::Cone({2.0f, 0.0f, 2.0f}, 0.75f, 2.0f, Quat{0.0f, 0.0f, 0.19509032f, 0.98078528f}),
+                           Collider::capsule({-0.75f, 1.0f, 1.5f}, 0.25f, 1.5f, Quat{0.30151135f, 0.0f, 0.30151135f, 0.90453404f}, 2u)});
+        const fw_mesh ramp = app.create_mesh({-2.0f, -0.25f, -2.0f, 2.0f, -0.25f, -2.0f, 2.0f, 0.25f, 2.0f, -2.0f, 0.25f, 2.0f}, {0, 2, 1, 0, 3, 2});
+        app.set_mesh_colliders({MeshCollider{ramp, {0.5f, 1.75f, 0.0f}, Quat{0.0f, 0.38268343f, 0.0f, 0.92387953f}, 3u}});
+        std::vector<fw_point> points(96);
+        for (size_t i = 0; i < points.size(); i++) {
+            fw_point &p = points[i];
+            p.position[0] = -3.0f + (float)(i % 8) * 0.875f, p.position[1] = -1.5f + (float)((i / 8) % 4) * 1.125f, p.position[2] = -2.5f + (float)(i / 32) * 2.25f;
+            p.filter_mask = 1u + (uint32_t)(i % 3);
+        }
+        const std::vector<fw_point_projection> host = app.project_points(points);
+        std::vector<fw_point_projection> from_device(points.size());
+        void *d_points = nullptr, *d_out = nullptr;
+        if (hipMalloc(&d_points, points.size() * sizeof(fw_point)) != hipSuccess || hipMalloc(&d_out, points.size() * sizeof(fw_point_projection)) != hipSuccess)
+            throw Error(FW_EHIP, "hipMalloc");
+        hipStream_t st = (hipStream_t)app.stream();
+        if (hipMemcpyAsync(d_points, points.data(), points.size() * sizeof(fw_point), hipMemcpyHostToDevice, st) != hipSuccess) throw Error(FW_EHIP, "hipMemcpyAsync");
+        app.project_points_device(d_points, points.size(), d_out);
+        if (hipMemcpyAsync(from_device.data(), d_out, points.size() * sizeof(fw_point_projection), hipMemcpyDeviceToHost, st) != hipSuccess)
+            throw Error(FW_EHIP, "hipMemcpyAsync");
+        app.synchronize();
+        (void)hipFree(d_points), (void)hipFree(d_out);
+        for (size_t i = 0; i < host.size(); i++) {
+            uint32_t w[8];
+            std::memcpy(w, &host[i], sizeof w);
+            std::printf("point %zu %08x %08x %08x %08x %08x %08x %08x %08x\n", i, w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7]);
+        }
+        std::printf("host %016llx device %016llx\n", (unsigned long long)fnv(host.data(), host.size() * sizeof(fw_point_projection)),
+                    (unsigned long long)fnv(from_device.data(), from_device.size() * sizeof(fw_point_projection)));
+    } catch (const Error &e) {
+        std::fprintf(stderr, "firework error %d: %s\n", (int)e.status, e.what());
+        return 1;
+    }
+    return 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc > 1 && std::strcmp(argv[1], "project") == 0) return project_scenario();
     if (argc > 1 && std::strcmp(argv[1], "capsule") == 0) return capsule_scenario();
     // `mirror_check mesh`: the same scenario with triangle meshes in the collider world (create, place twice, replace, destroy)
     // `mirror_check deform`: ... with both meshes deformable: the ramp's far edge rises every fifth frame, then the sheet's apex

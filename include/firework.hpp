@@ -455,6 +455,16 @@ class ParticleSystemPlugin {
     }
     // ... rays and hits in device memory (n fw_ray at d_rays, n fw_ray_hit at d_hits), enqueued on stream(): never waits
     void cast_rays_device(const void *d_rays, uint64_t n, void *d_hits) { check(fw_ctx_cast_rays_device(ctx_, d_rays, n, d_hits)); }
+    // SpatialQuery::project_point / point_intersections for a batch (fw_ctx_project_points): per point the nearest point of the
+    // collider world, its distance, who owns it (kind / index / triangle as in fw_ray_hit) and whether the point lies inside or on an
+    // analytic solid (is_inside: point = the position, distance 0).  Waits for the result.
+    std::vector<fw_point_projection> project_points(const std::vector<fw_point> &points) {
+        std::vector<fw_point_projection> out(points.size());
+        check(fw_ctx_project_points(ctx_, points.data(), (uint64_t)points.size(), out.data()));
+        return out;
+    }
+    // ... points and projections in device memory (n fw_point at d_points, n fw_point_projection at d_out), enqueued on stream(): never waits
+    void project_points_device(const void *d_points, uint64_t n, void *d_out) { check(fw_ctx_project_points_device(ctx_, d_points, n, d_out)); }
 
     // update_aabbs (render.rs:677-703) fused into the update: every frame leaves per-tile boxes, ParticleSpawnerData::aabb
     // folds them instead of re-reading the particles

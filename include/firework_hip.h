@@ -261,6 +261,76 @@ typedef struct fw_ray_hit { /* 32 bytes */
     uint32_t reserved; /* 0 */
 } fw_ray_hit;
 
+/* POINT QUERIES (avian's SpatialQuery::project_point and point_intersections: an emitter snapped to the nearest surface, a decal
+ * placed from an explosion's centre, "is this spawn position buried?").  fw_ctx_project_points[_device] projects a batch of points
+ * onto the collider world: per point the nearest point of the world, its distance, who owns it, and whether the point lies inside
+ * a solid.  All fp32, no fused a*b+c; dot and cross as under TRIANGLE above; clamp(x, h) = x < -h ? -h : (x > h ? h : x).
+ *   FILTER    a collider or instance takes part when (filter_mask & layers) != 0.
+ *   SOLID     analytic kinds are solids (parry's `solid = true`).  "inside or on" is, kind by kind, the expression the ray cast
+ *             tests for its distance-0 case, so is_inside agrees bit for bit with "a ray from this point reports distance 0 with a
+ *             zero normal" for that collider.  With c = the collider, x = position, o as under FRAME below:
+ *               PLANE     dot(n, c.position - x) > 0
+ *               SPHERE    dot(v, v) - radius * radius <= 0, v = x - c.position
+ *               BOX       |o.x| <= hx and |o.y| <= hy and |o.z| <= hz
+ *               CYLINDER  |o.y| <= hh and (o.x o.x + o.z o.z) - radius * radius <= 0
+ *               CONE      o.y >= -hh and wy <= 0 and (o.x o.x + o.z o.z) - k2 * (wy * wy) <= 0, wy = o.y - hh, k = radius / (hh + hh), k2 = k * k
+ *               CAPSULE   ((o.x o.x + o.z o.z) + dy * dy) - radius * radius <= 0, yc = clamp(o.y, hl), dy = o.y - yc
+ *             The participating collider of the LOWEST index that contains the point answers, whatever else is near: point =
+ *             position (the caller's bits), distance = 0, is_inside = 1, kind = FW_HIT_COLLIDER, index = that collider.
+ *   FRAME     PLANE and SPHERE work in the world (o = x).  BOX, CYLINDER, CONE and CAPSULE work in the collider's frame:
+ *             o = R^-1 (x - c.position), the identity rotation skipping the product, as in the cast.
+ *   NEAREST   for a point outside the solid, q = the nearest point of the solid:
+ *               PLANE     s = dot(n, x - c.position); q = x - n * s
+ *               SPHERE    q = c.position + v * (radius / sqrt(dot(v, v)))
+ *               BOX       q = (clamp(o.x, hx), clamp(o.y, hy), clamp(o.z, hz))
+ *               CYLINDER  r = sqrt(o.x o.x + o.z o.z); profile point qr = r > radius ? radius : r, qy = clamp(o.y, hh)
+ *               CONE      r as above; first the base segment: qr = r > radius ? radius : r, qy = -hh, db = (r - qr)^2 + (o.y - qy)^2;
+ *                         then the slant segment from the rim (radius, -hh) to the apex (0, +hh): h = hh + hh,
+ *                         t = ((o.y + hh) * h - (r - radius) * radius) / (radius * radius + h * h), clamped to [0, 1] (t < 0 ? 0 : (t > 1 ? 1 : t)),
+ *                         sr = radius - radius * t, sy = h * t - hh, ds = (r - sr)^2 + (o.y - sy)^2; (qr, qy) = (sr, sy) only when ds < db
+ *               CYLINDER and CONE take the profile point back as q = (qr * o.x / r, qy, qr * o.z / r), or (qr, qy, 0) when r == 0
+ *               CAPSULE   v = (o.x, dy, o.z); s = radius / sqrt(dot(v, v)); q = (v.x * s, yc + v.y * s, v.z * s)
+ *             then w = o - q and d2 = dot(w, w): candidates compete on this squared distance.
+ *   MESHES    surfaces, as for rays: never inside.  The point is taken into the instance's frame once (o as under FRAME of the mesh
+ *             block).  A triangle takes part only when c = cross(e1, e2) of its STORED edges has dot(c, c) > 0 and finite -- the
+ *             zero-area rule of creation; a deformable mesh keeps its collapsed triangles as records with zero edges, and those do not
+ *             answer.  Per triangle the closest point by regions (Ericson, Real-Time Collision Detection, 5.1.5) from v0, e1, e2:
+ *               ap = o - v0; d1 = dot(e1, ap); d2 = dot(e2, ap); bp = ap - e1; d3 = dot(e1, bp); d4 = dot(e2, bp);
+ *               cp = ap - e2; d5 = dot(e1, cp); d6 = dot(e2, cp); vc = d1 d4 - d3 d2; vb = d5 d2 - d1 d6; va = d3 d6 - d5 d4;
+ *             the FIRST of these tests that holds gives the barycentric pair (v, w):
+ *               d1 <= 0 and d2 <= 0: (0, 0);   d3 >= 0 and d4 <= d3: (1, 0);   vc <= 0 and d1 >= 0 and d3 <= 0: (d1 / (d1 - d3), 0);
+ *               d6 >= 0 and d5 <= d6: (0, 1);   vb <= 0 and d2 >= 0 and d6 <= 0: (0, d2 / (d2 - d6));
+ *               va <= 0 and d4 - d3 >= 0 and d5 - d6 >= 0: w = (d4 - d3) / ((d4 - d3) + (d5 - d6)), v = 1 - w;
+ *               otherwise (the face): denom = 1 / ((va + vb) + vc); v = vb * denom; w = vc * denom;
+ *             q = (v0 + e1 * v) + e2 * w per component, w' = o - q, d2 = dot(w', w').
+ *   TIES      the smaller d2 wins; the best starts at +infinity and is replaced by strict <, so a candidate whose d2 is NaN or
+ *             infinite never wins.  The analytic colliders compete in index order, then the instances in index order: at bit-equal
+ *             d2 analytic colliders come before mesh instances and lower indices before higher ones.  Within an instance the lower
+ *             ORIGINAL triangle index wins a bit-equal d2 (neighbouring triangles do tie, on shared edges and vertices).
+ *   RESULT    only the winner's q goes back to the world (R q + position, the identity rotation skipping the product; PLANE and
+ *             SPHERE are there already), and only the winner takes the root: distance = sqrt(d2).  kind / index / triangle name the
+ *             winner as in fw_ray_hit.  Nobody took part, or nobody won: kind = FW_HIT_NONE, point = 0, distance = 0,
+ *             index = triangle = 0xFFFFFFFF, is_inside = 0.
+ *   ORDER     both forms enqueue on the context's main stream (fw_ctx_stream), where collider sets, instance sets, refits and every
+ *             launch that casts rays already travel: a query sees every fw_ctx_set_colliders, fw_ctx_set_mesh_colliders and
+ *             fw_ctx_update_mesh_vertices[_device] called before it and none called after it.  The device form never waits,
+ *             allocates nothing, does no host work that grows with n, and reads d_points / writes d_out ONLY in work it enqueues
+ *             itself.  The host form stages through pinned memory (grown on demand, kept by the context) and waits for its result.
+ *   ERRORS    a null pointer with n > 0: FW_EINVAL, nothing enqueued.  n == 0: FW_OK, nothing touched.  NaN or infinite points give
+ *             whatever the operations give, deterministically; the walk of a mesh ends for any point. */
+typedef struct fw_point { /* 16 bytes */
+    float position[3];
+    uint32_t filter_mask; /* as fw_ray.filter_mask */
+} fw_point;
+typedef struct fw_point_projection { /* 32 bytes */
+    float point[3];     /* nearest point of the world to `position` (position itself when is_inside) */
+    float distance;     /* sqrt of the winning squared distance; 0 when is_inside */
+    int32_t kind;       /* FW_HIT_NONE / FW_HIT_COLLIDER / FW_HIT_MESH */
+    uint32_t index;     /* as fw_ray_hit.index */
+    uint32_t triangle;  /* as fw_ray_hit.triangle */
+    uint32_t is_inside; /* 1: position lies inside or on the analytic solid named; meshes never */
+} fw_point_projection;
+
 enum { FW_PACING_ONESHOT = 0, FW_PACING_ONDEMAND = 1, FW_PACING_COUNT_OVER_DURATION = 2 }; /* core.rs:12-29 */
 enum { FW_MODE_GLOBAL = 0, FW_MODE_NESTED = 1 };                                           /* core.rs:47-54 */
 enum { FW_SHAPE_POINT = 0, FW_SHAPE_SPHERE = 1, FW_SHAPE_CIRCLE = 2 };                     /* emission_shape.rs:7-15 */
@@ -363,6 +433,11 @@ fw_status fw_ctx_cast_rays(fw_ctx *ctx, const fw_ray *rays, uint64_t n, fw_ray_h
 /* the same for n fw_ray records at d_rays and n fw_ray_hit records at d_hits in DEVICE memory (16-byte aligned), read and written in
  * the order of the context's stream by the launches this call enqueues and by nothing else.  Never synchronises. */
 fw_status fw_ctx_cast_rays_device(fw_ctx *ctx, const void *d_rays, uint64_t n, void *d_hits);
+/* projects points[n] onto the collider world and writes out[n] (POINT QUERIES above); host memory, synchronises */
+fw_status fw_ctx_project_points(fw_ctx *ctx, const fw_point *points, uint64_t n, fw_point_projection *out);
+/* the same for n fw_point records at d_points and n fw_point_projection records at d_out in DEVICE memory (16-byte aligned), read and
+ * written in the order of the context's stream by the launches this call enqueues and by nothing else.  Never synchronises. */
+fw_status fw_ctx_project_points_device(fw_ctx *ctx, const void *d_points, uint64_t n, void *d_out);
 
 /* ---- spawners ----------------------------------------------------------------- */
 /* ParticleSpawner insertion + first sync_spawner_data (core.rs:343-365) */

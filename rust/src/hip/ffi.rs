@@ -43,6 +43,12 @@ pub const FW_HIT_NONE: i32 = 0; pub const FW_HIT_COLLIDER: i32 = 1; pub const FW
 #[repr(C)] #[derive(Clone, Copy)] pub struct fw_ray_hit {         // its nearest hit (32 bytes); index: position in the set sent
     pub distance: f32, pub normal: [f32; 3], pub kind: i32, pub index: u32, pub triangle: u32, pub reserved: u32,
 }
+#[repr(C)] #[derive(Clone, Copy)] pub struct fw_point {           // one point of fw_ctx_project_points (16 bytes)
+    pub position: [f32; 3], pub filter_mask: u32,
+}
+#[repr(C)] #[derive(Clone, Copy)] pub struct fw_point_projection { // the nearest point of the world to it (32 bytes); kind / index / triangle as fw_ray_hit
+    pub point: [f32; 3], pub distance: f32, pub kind: i32, pub index: u32, pub triangle: u32, pub is_inside: u32,
+}
 #[repr(C)] pub struct fw_emission_settings {          // EmissionSettings, core.rs:144-162
     pub particle_index: i32, pub pacing_kind: i32, pub oneshot_count: u64,
     pub count: f32, pub duration: f32, pub offset_start: f32, pub offset_end: f32,
@@ -83,6 +89,8 @@ extern "C" {
     pub fn fw_ctx_set_mesh_colliders(ctx: *mut fw_ctx, instances: *const fw_mesh_collider, n: u32) -> c_int;
     pub fn fw_ctx_cast_rays(ctx: *mut fw_ctx, rays: *const fw_ray, n: u64, hits: *mut fw_ray_hit) -> c_int;
     pub fn fw_ctx_cast_rays_device(ctx: *mut fw_ctx, d_rays: *const c_void, n: u64, d_hits: *mut c_void) -> c_int;
+    pub fn fw_ctx_project_points(ctx: *mut fw_ctx, points: *const fw_point, n: u64, out: *mut fw_point_projection) -> c_int;
+    pub fn fw_ctx_project_points_device(ctx: *mut fw_ctx, d_points: *const c_void, n: u64, d_out: *mut c_void) -> c_int;
     pub fn fw_spawner_create(ctx: *mut fw_ctx, desc: *const fw_spawner_desc, out: *mut fw_spawner) -> c_int;
     pub fn fw_spawner_update_settings(ctx: *mut fw_ctx, h: fw_spawner, desc: *const fw_spawner_desc) -> c_int;
     pub fn fw_spawner_destroy(ctx: *mut fw_ctx, h: fw_spawner) -> c_int;
