@@ -1011,10 +1011,9 @@ struct fw_ctx {
     HipEvent ev_mesh[2];
     bool mesh_pending[2] = {false, false};
     uint64_t mesh_seq = 0;
-    // the host forms of the queries (fw_engine_query.cpp): pinned staging and device buffers for rays and hits, 32 bytes per
-    // record each (points in, 16 bytes each, and projections out share them), grown on demand and kept; the device forms need
-    // nothing of their own
-    HipBuf<float4> h_rays, h_hits, d_rays, d_hits;
+    // the host forms of the queries (fw_engine_query.cpp: query_staged): pinned staging and device buffers for the input and the
+    // output records, grown on demand and kept; the device forms need nothing of their own
+    HipBuf<float4> q_in_h, q_out_h, q_in_d, q_out_d;
     HipBuf<float> d_aabb;      // 256 partial boxes of the AABB query
     HipBuf<float> h_aabb;      // pinned result {min.xyz, any, max.xyz, -}
     HipBuf<unsigned long long> d_total;
@@ -1219,6 +1218,8 @@ fw_status spill_fifo_rings(fw_ctx *ctx);
 fw_status leave_nospin(fw_ctx *ctx, uint32_t si);
 bool axis_dt_ok(const SegHost &S, float dt);
 fw_status set_derived(fw_ctx *ctx, uint32_t si, bool on, bool refill = true);
+// the live count of segment si, as the kernels keep it, at the current parity (si = 0: the row of all segments)
+static inline uint32_t *count_slot(const fw_ctx *ctx, uint32_t si = 0) { return ctx->g.count + (size_t)ctx->parity * ctx->max_seg + si; }
 // does the type's update leave scale and colours to its readers?  (colliding types -- and `bigkeys` ones, which run on their
 // kernels -- stay as they are: the feature path reads the stored planes)
 static inline bool wants_derived(const fw_ctx *ctx, const SegHost &S) {

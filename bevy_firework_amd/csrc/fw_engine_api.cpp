@@ -58,23 +58,65 @@ fw_ctx::~fw_ctx() {
         if (s) (void)hipStreamSynchronize(s);
 }
 
-// What the entry points that read a spawner's particles open with: the spawner, the sticky status of a poisoned one, the device,
-// the exact live counts.  begin_read returns false when the call ends there, with r.st; otherwise r.st is FW_OK or FW_ECAPACITY
-// (a type overflowed: the call goes on and reports it at its end, unless a later error takes precedence).
-// args_ok: the call's own argument check, which may look at the spawner
-struct SpawnerRead {
+// What the entry points that read or write a spawner's particles open with: the spawner, the call's own argument check (args_ok,
+// which may look at the spawner), the sticky status of a poisoned one, the device -- and then what the call needs before it touches
+// particle state: nothing (it enqueues behind what is in flight), sync(ctx), join_side(ctx) or read_counts(ctx, r.c).  begin_call
+// returns false when the call ends there, with r.st; otherwise r.st is FW_OK or, after Then::counts alone, FW_ECAPACITY (a type
+// overflowed: the call goes on and reports it at its end, unless a later error takes precedence).
+enum class Then { nothing, sync, join, counts };
+struct SpawnerCall {
     SpawnerHost *sp = nullptr;
-    std::vector<uint32_t> c;  // per segment
+    std::vector<uint32_t> c;  // per segment (Then::counts)
     fw_status st = FW_OK;
 };
 template <typename ArgsOk>
-static bool begin_read(fw_ctx *ctx, fw_spawner h, SpawnerRead &r, ArgsOk args_ok) {
+static bool begin_call(fw_ctx *ctx, fw_spawner h, SpawnerCall &r, Then then, ArgsOk args_ok) {
     r.sp = get_spawner(ctx, h);
     if (!r.sp || !args_ok(*r.sp)) return r.st = FW_EINVAL, false;
     if (poll_device_error(ctx), r.sp->poisoned) return r.st = poisoned_status(ctx), false;
     hipSetDevice(ctx->device);
-    r.st = read_counts(ctx, r.c);
-    return !r.st || r.st == FW_ECAPACITY;
+    r.st = then == Then::sync ? sync(ctx) : then == Then::join ? join_side(ctx) : then == Then::counts ? read_counts(ctx, r.c) : FW_OK;
+    return !r.st || (then == Then::counts && r.st == FW_ECAPACITY);
+}
+
+// Everything enqueued on top of a poisoned spawner's invalid state has finished (the caller synchronised): what those frames
+// reported again is not news, and the segment slots the report names are about to be reused or released.  (But the word may by now
+// name ANOTHER spawner, healthy so far -- one word, the last writer wins: mark it before the report is dropped)
+static fw_status clear_poison_report(fw_ctx *ctx) {
+    poll_device_error(ctx);
+    ctx->h_err[0] = ctx->h_err[1] = 0ull;
+    const uint32_t zero = 0;
+    FW_HIP(ctx, hipMemcpy(ctx->g.err, &zero, sizeof zero, hipMemcpyHostToDevice));
+    return FW_OK;
+}
+
+static void recount_poisoned(fw_ctx *ctx) {  // (fw_step looks for invalid spawners only while some exist)
+    ctx->n_poisoned = 0;
+    for (const SpawnerHost &x : ctx->spawners) ctx->n_poisoned += (x.alive && x.poisoned) ? 1u : 0u;
+}
+
+// the batch setters' handle array: every handle names a live spawner, or nothing is set (msg: the setter's own text)
+static fw_status check_handles(fw_ctx *ctx, uint32_t n, const fw_spawner *handles, const char *msg) {
+    for (uint32_t i = 0; i < n; i++)
+        if (!get_spawner(ctx, handles[i])) return fail(ctx, FW_EINVAL, msg);
+    return FW_OK;
+}
+
+// the last_emitted_age plane a segment keeps for an emission entry; -1: none, the entry never reads it
+static int lplane_of(const SegHost &S, uint32_t emission_index) {
+    int plane = -1;
+    for (uint32_t k = 0; k < S.n_lplanes; k++)
+        if (S.lplane_emission[k] == (int32_t)emission_index) plane = (int)k;
+    return plane;
+}
+
+// the running total of particles that entered update_particles: the sum of the stat slots (the caller synchronised)
+static fw_status read_stat_total(fw_ctx *ctx, uint64_t *total) {
+    unsigned long long slots[FW_STAT_SLOTS];
+    FW_HIP(ctx, hipMemcpy(slots, ctx->g.stats, sizeof slots, hipMemcpyDeviceToHost));
+    *total = 0;
+    for (unsigned long long v : slots) *total += v;
+    return FW_OK;
 }
 
 extern "C" {
@@ -240,10 +282,10 @@ fw_status fw_ctx_set_colliders(fw_ctx *ctx, const fw_collider *colliders, uint32
         d = FwCollider{};
         d.kind = c.kind, d.layers = c.layers, d.radius = c.radius;
         // (the sphere around `position` that contains it: a wave skips a collider none of its rays can reach, fw_cast_ray)
-        d.bound = c.kind == 1 ? c.radius
-                  : c.kind == 2 ? std::sqrt(c.half_extents[0] * c.half_extents[0] + c.half_extents[1] * c.half_extents[1] + c.half_extents[2] * c.half_extents[2]) * 1.0001f
-                  : (c.kind == 3 || c.kind == 4) ? std::sqrt(c.radius * c.radius + c.half_extents[1] * c.half_extents[1]) * 1.0001f  // (the rim of a cap / of the base)
-                  : c.kind == 5 ? (c.half_extents[1] + c.radius) * 1.0001f  // (the poles of the caps)
+        d.bound = c.kind == FW_COLLIDER_SPHERE ? c.radius
+                  : c.kind == FW_COLLIDER_BOX ? std::sqrt(c.half_extents[0] * c.half_extents[0] + c.half_extents[1] * c.half_extents[1] + c.half_extents[2] * c.half_extents[2]) * 1.0001f
+                  : (c.kind == FW_COLLIDER_CYLINDER || c.kind == FW_COLLIDER_CONE) ? std::sqrt(c.radius * c.radius + c.half_extents[1] * c.half_extents[1]) * 1.0001f  // (the rim of a cap / of the base)
+                  : c.kind == FW_COLLIDER_CAPSULE ? (c.half_extents[1] + c.radius) * 1.0001f  // (the poles of the caps)
                                 : INFINITY;
         if (!(d.bound >= 0.0f)) d.bound = INFINITY;  // (NaN / negative extents: never skipped)
         memcpy(d.position, c.position, sizeof c.position);
@@ -297,16 +339,7 @@ fw_status fw_spawner_update_settings(fw_ctx *ctx, fw_spawner h, const fw_spawner
     fw_status st = validate_desc(ctx, desc);
     if (st) return st;
     if ((st = sync(ctx))) return st;
-    if (sp->poisoned) {
-        // everything enqueued on top of the invalid state has finished: what those frames reported again is not news, and the
-        // segment slots the report names are about to be reused by the rebuilt spawner
-        // (... but the word may by now name ANOTHER spawner, healthy so far -- one word, the last writer wins: mark it before the
-        // report is dropped)
-        poll_device_error(ctx);
-        ctx->h_err[0] = ctx->h_err[1] = 0ull;
-        const uint32_t zero = 0;
-        FW_HIP(ctx, hipMemcpy(ctx->g.err, &zero, sizeof zero, hipMemcpyHostToDevice));
-    }
+    if (sp->poisoned && (st = clear_poison_report(ctx))) return st;
     // RNG streams never replay: carry the serials of surviving emission indices
     std::vector<uint64_t> serials;
     for (const EmissionHost &e : sp->em) {
@@ -337,8 +370,7 @@ fw_status fw_spawner_update_settings(fw_ctx *ctx, fw_spawner h, const fw_spawner
         return st;
     }
     ctx->spawners[h].finished_notified = finished_notified;
-    ctx->n_poisoned = 0;  // (fw_step looks for invalid spawners only while some exist)
-    for (const SpawnerHost &x : ctx->spawners) ctx->n_poisoned += (x.alive && x.poisoned) ? 1u : 0u;
+    recount_poisoned(ctx);
     return st;
 }
 
@@ -348,16 +380,10 @@ fw_status fw_spawner_destroy(fw_ctx *ctx, fw_spawner h) {
     hipSetDevice(ctx->device);
     fw_status st = sync(ctx);
     if (st) return st;
-    if (sp->poisoned) {  // (as in fw_spawner_update_settings)
-        poll_device_error(ctx);
-        ctx->h_err[0] = ctx->h_err[1] = 0ull;
-        const uint32_t zero = 0;
-        FW_HIP(ctx, hipMemcpy(ctx->g.err, &zero, sizeof zero, hipMemcpyHostToDevice));
-    }
+    if (sp->poisoned && (st = clear_poison_report(ctx))) return st;
     if ((st = release_spawner_segments(ctx, *sp))) return st;
     *sp = SpawnerHost{};
-    ctx->n_poisoned = 0;
-    for (const SpawnerHost &x : ctx->spawners) ctx->n_poisoned += (x.alive && x.poisoned) ? 1u : 0u;
+    recount_poisoned(ctx);
     return FW_OK;
 }
 
@@ -372,8 +398,7 @@ fw_status fw_spawner_set_origin(fw_ctx *ctx, fw_spawner h, const float t[3], con
 fw_status fw_ctx_set_origins(fw_ctx *ctx, uint32_t n, const fw_spawner *handles, const float *translations,
                              const float *rotations_xyzw) {
     if (!ctx || (n && (!handles || !translations || !rotations_xyzw))) return FW_EINVAL;
-    for (uint32_t i = 0; i < n; i++)
-        if (!get_spawner(ctx, handles[i])) return fail(ctx, FW_EINVAL, "fw_ctx_set_origins: invalid spawner handle");
+    if (fw_status st = check_handles(ctx, n, handles, "fw_ctx_set_origins: invalid spawner handle")) return st;
     for (uint32_t i = 0; i < n; i++) {
         SpawnerHost &sp = ctx->spawners[(size_t)handles[i]];
         memcpy(sp.origin_pos, translations + (size_t)i * 3, sizeof sp.origin_pos);
@@ -405,16 +430,14 @@ fw_status fw_spawner_queue(fw_ctx *ctx, fw_spawner h, uint64_t count) {
 
 fw_status fw_ctx_set_parent_velocities(fw_ctx *ctx, uint32_t n, const fw_spawner *handles, const float *velocities) {
     if (!ctx || (n && (!handles || !velocities))) return FW_EINVAL;
-    for (uint32_t i = 0; i < n; i++)
-        if (!get_spawner(ctx, handles[i])) return fail(ctx, FW_EINVAL, "fw_ctx_set_parent_velocities: invalid spawner handle");
+    if (fw_status st = check_handles(ctx, n, handles, "fw_ctx_set_parent_velocities: invalid spawner handle")) return st;
     for (uint32_t i = 0; i < n; i++) memcpy(ctx->spawners[(size_t)handles[i]].parent_vel, velocities + (size_t)i * 3, 3 * sizeof(float));
     return FW_OK;
 }
 
 fw_status fw_ctx_set_modifiers(fw_ctx *ctx, uint32_t n, const fw_spawner *handles, const float *scales, const float *speeds) {
     if (!ctx || (n && (!handles || !scales || !speeds))) return FW_EINVAL;
-    for (uint32_t i = 0; i < n; i++)
-        if (!get_spawner(ctx, handles[i])) return fail(ctx, FW_EINVAL, "fw_ctx_set_modifiers: invalid spawner handle");
+    if (fw_status st = check_handles(ctx, n, handles, "fw_ctx_set_modifiers: invalid spawner handle")) return st;
     for (uint32_t i = 0; i < n; i++) {
         SpawnerHost &sp = ctx->spawners[(size_t)handles[i]];
         sp.mod_scale = scales[i], sp.mod_speed = speeds[i];
@@ -424,30 +447,29 @@ fw_status fw_ctx_set_modifiers(fw_ctx *ctx, uint32_t n, const fw_spawner *handle
 
 fw_status fw_ctx_queue(fw_ctx *ctx, uint32_t n, const fw_spawner *handles, const uint64_t *counts) {
     if (!ctx || (n && (!handles || !counts))) return FW_EINVAL;
-    for (uint32_t i = 0; i < n; i++)
-        if (!get_spawner(ctx, handles[i])) return fail(ctx, FW_EINVAL, "fw_ctx_queue: invalid spawner handle");
+    if (fw_status st = check_handles(ctx, n, handles, "fw_ctx_queue: invalid spawner handle")) return st;
     for (uint32_t i = 0; i < n; i++) ctx->spawners[(size_t)handles[i]].manual_queued_count += counts[i];  // core.rs:284-286
     return FW_OK;
 }
 
 // ---- outputs -----------------------------------------------------------------------------
 fw_status fw_spawner_counts(fw_ctx *ctx, fw_spawner h, uint32_t *per_type, uint32_t n_types) {
-    SpawnerRead r;
-    if (!begin_read(ctx, h, r, [&](const SpawnerHost &) { return per_type != nullptr; })) return r.st;
+    SpawnerCall r;
+    if (!begin_call(ctx, h, r, Then::counts, [&](const SpawnerHost &) { return per_type != nullptr; })) return r.st;
     for (uint32_t t = 0; t < n_types && t < r.sp->seg.size(); t++) per_type[t] = r.c[r.sp->seg[t]];
     return r.st;
 }
 
 fw_status fw_spawner_active(fw_ctx *ctx, fw_spawner h, int32_t *out) {
-    SpawnerRead r;
-    if (!begin_read(ctx, h, r, [&](const SpawnerHost &) { return out != nullptr; })) return r.st;
+    SpawnerCall r;
+    if (!begin_call(ctx, h, r, Then::counts, [&](const SpawnerHost &) { return out != nullptr; })) return r.st;
     *out = spawner_active(ctx, *r.sp, r.c) ? 1 : 0;
     return r.st;
 }
 
 fw_status fw_spawner_poll_finished(fw_ctx *ctx, fw_spawner h, int32_t *out) {
-    SpawnerRead r;
-    if (!begin_read(ctx, h, r, [&](const SpawnerHost &) { return out != nullptr; })) return r.st;
+    SpawnerCall r;
+    if (!begin_call(ctx, h, r, Then::counts, [&](const SpawnerHost &) { return out != nullptr; })) return r.st;
     bool all_empty = true;
     for (uint32_t si : r.sp->seg) all_empty &= r.c[si] == 0;
     *out = 0;
@@ -485,8 +507,8 @@ static fw_status read_records(fw_ctx *ctx, const FwSegView &v, uint32_t n, int32
 
 fw_status fw_spawner_read_particles(fw_ctx *ctx, fw_spawner h, uint32_t type, fw_particle *out, uint64_t cap,
                                     uint64_t *n_out) {
-    SpawnerRead r;
-    if (!begin_read(ctx, h, r, [&](const SpawnerHost &sp) { return type < sp.seg.size(); })) return r.st;
+    SpawnerCall r;
+    if (!begin_call(ctx, h, r, Then::counts, [&](const SpawnerHost &sp) { return type < sp.seg.size(); })) return r.st;
     const uint32_t n = r.c[r.sp->seg[type]];
     if (n_out) *n_out = n;
     // (the counts are exact and the stream has been waited for: the host places particle 0 itself)
@@ -496,16 +518,14 @@ fw_status fw_spawner_read_particles(fw_ctx *ctx, fw_spawner h, uint32_t type, fw
 
 fw_status fw_spawner_read_last_emitted(fw_ctx *ctx, fw_spawner h, uint32_t type, uint32_t emission_index, float *out,
                                        uint64_t cap, uint64_t *n_out) {
-    SpawnerRead r;
-    if (!begin_read(ctx, h, r, [&](const SpawnerHost &sp) { return type < sp.seg.size() && emission_index < sp.em.size(); })) return r.st;
+    SpawnerCall r;
+    if (!begin_call(ctx, h, r, Then::counts, [&](const SpawnerHost &sp) { return type < sp.seg.size() && emission_index < sp.em.size(); })) return r.st;
     const SegHost &S = ctx->segs[r.sp->seg[type]];
     const uint32_t n = r.c[r.sp->seg[type]];
     if (n_out) *n_out = n;
     const uint64_t m = std::min<uint64_t>(n, cap);
     if (!m || !out) return r.st;
-    int plane = -1;
-    for (uint32_t k = 0; k < S.n_lplanes; k++)
-        if (S.lplane_emission[k] == (int32_t)emission_index) plane = (int)k;
+    const int plane = lplane_of(S, emission_index);
     if (plane < 0) {
         for (uint64_t i = 0; i < m; i++) out[i] = FW_F32_MIN;  // never touched: still vec![f32::MIN; n] (core.rs:467)
         return r.st;
@@ -519,13 +539,11 @@ fw_status fw_spawner_read_last_emitted(fw_ctx *ctx, fw_spawner h, uint32_t type,
 }
 
 fw_status fw_spawner_write_particles(fw_ctx *ctx, fw_spawner h, uint32_t type, const fw_particle *in, uint64_t n) {
-    SpawnerHost *sp = get_spawner(ctx, h);
-    if (!sp || type >= sp->seg.size() || (n && !in) || n > 0xF0000000ull) return FW_EINVAL;
-    if (poll_device_error(ctx), sp->poisoned) return poisoned_status(ctx);
-    hipSetDevice(ctx->device);
-    fw_status st = sync(ctx);
-    if (st) return st;
-    const uint32_t si = sp->seg[type];
+    SpawnerCall r;
+    if (!begin_call(ctx, h, r, Then::sync, [&](const SpawnerHost &sp) { return type < sp.seg.size() && !(n && !in) && n <= 0xF0000000ull; }))
+        return r.st;
+    fw_status st;
+    const uint32_t si = r.sp->seg[type];
     ctx->fc_ok = false, ctx->boxes_epoch = 0;
     if ((st = fifo_to_general(ctx, si))) return st;  // ages and lifetimes will be whatever the caller writes
     leave_small(ctx, ctx->segs[si]);                  // (any number of particles, any colours: the compacting kernels take it from here)
@@ -538,7 +556,7 @@ fw_status fw_spawner_write_particles(fw_ctx *ctx, fw_spawner h, uint32_t type, c
     if (n > ctx->segs[si].capacity) {
         ctx->segs[si].ub = 0;
         const uint32_t zero = 0;
-        FW_HIP(ctx, hipMemcpy(ctx->g.count + (size_t)ctx->parity * ctx->max_seg + si, &zero, 4, hipMemcpyHostToDevice));
+        FW_HIP(ctx, hipMemcpy(count_slot(ctx, si), &zero, 4, hipMemcpyHostToDevice));
         if ((st = grow_segment(ctx, si, (uint32_t)n))) return st;
     }
     SegHost &S = ctx->segs[si];
@@ -551,7 +569,7 @@ fw_status fw_spawner_write_particles(fw_ctx *ctx, fw_spawner h, uint32_t type, c
         FW_HIP(ctx, e);
     }
     const uint32_t n32 = (uint32_t)n;
-    FW_HIP(ctx, hipMemcpy(ctx->g.count + (size_t)ctx->parity * ctx->max_seg + si, &n32, 4, hipMemcpyHostToDevice));
+    FW_HIP(ctx, hipMemcpy(count_slot(ctx, si), &n32, 4, hipMemcpyHostToDevice));
     S.ub = n32;
     S.win_ok = false;  // ages and lifetimes are now whatever the caller wrote
     S.colors_dirty = true, ctx->colors_dirty = true;  // and so are the colours: the next update writes them all
@@ -561,17 +579,12 @@ fw_status fw_spawner_write_particles(fw_ctx *ctx, fw_spawner h, uint32_t type, c
 
 fw_status fw_spawner_write_last_emitted(fw_ctx *ctx, fw_spawner h, uint32_t type, uint32_t emission_index,
                                         const float *in, uint64_t n) {
-    SpawnerHost *sp = get_spawner(ctx, h);
-    if (!sp || type >= sp->seg.size() || emission_index >= sp->em.size() || (n && !in)) return FW_EINVAL;
-    if (poll_device_error(ctx), sp->poisoned) return poisoned_status(ctx);
-    hipSetDevice(ctx->device);
-    fw_status st = sync(ctx);
-    if (st) return st;
-    if ((st = fifo_to_general(ctx, sp->seg[type]))) return st;  // (caller-written state: the general path takes over)
-    const SegHost &S = ctx->segs[sp->seg[type]];
-    int plane = -1;
-    for (uint32_t k = 0; k < S.n_lplanes; k++)
-        if (S.lplane_emission[k] == (int32_t)emission_index) plane = (int)k;
+    SpawnerCall r;
+    if (!begin_call(ctx, h, r, Then::sync, [&](const SpawnerHost &sp) { return type < sp.seg.size() && emission_index < sp.em.size() && !(n && !in); }))
+        return r.st;
+    if (fw_status st = fifo_to_general(ctx, r.sp->seg[type])) return st;  // (caller-written state: the general path takes over)
+    const SegHost &S = ctx->segs[r.sp->seg[type]];
+    const int plane = lplane_of(S, emission_index);
     if (plane < 0) return FW_OK;  // entry never reads it
     const uint64_t m = std::min<uint64_t>(n, S.capacity);
     if (m)
@@ -582,15 +595,11 @@ fw_status fw_spawner_write_last_emitted(fw_ctx *ctx, fw_spawner h, uint32_t type
 
 fw_status fw_spawner_read_destroyed(fw_ctx *ctx, fw_spawner h, uint32_t type, fw_particle *out, uint64_t cap,
                                     uint64_t *n_out) {
-    SpawnerHost *sp = get_spawner(ctx, h);
-    if (!sp || type >= sp->seg.size()) return FW_EINVAL;
-    if (poll_device_error(ctx), sp->poisoned) return poisoned_status(ctx);
-    hipSetDevice(ctx->device);
-    fw_status st = sync(ctx);
-    if (st) return st;
-    const SegHost &S = ctx->segs[sp->seg[type]];
+    SpawnerCall r;
+    if (!begin_call(ctx, h, r, Then::sync, [&](const SpawnerHost &sp) { return type < sp.seg.size(); })) return r.st;
+    const SegHost &S = ctx->segs[r.sp->seg[type]];
     uint32_t n = 0;
-    if (S.destroyed) FW_HIP(ctx, hipMemcpy(&n, ctx->g.ndestroyed + sp->seg[type], 4, hipMemcpyDeviceToHost));
+    if (S.destroyed) FW_HIP(ctx, hipMemcpy(&n, ctx->g.ndestroyed + r.sp->seg[type], 4, hipMemcpyDeviceToHost));
     if (n_out) *n_out = n;
     // (a range ring fills its records from the END of the buffer, the youngest dead first: the last n are in list order)
     const char *first = S.destroyed + (S.dead_at_end && n <= S.capacity ? (size_t)(S.capacity - n) * sizeof(fw_particle) : (size_t)0);
@@ -602,11 +611,9 @@ fw_status fw_spawner_read_destroyed(fw_ctx *ctx, fw_spawner h, uint32_t type, fw
 
 fw_status fw_spawner_pack_instances_device(fw_ctx *ctx, fw_spawner h, uint32_t type, void *d_out, uint64_t cap,
                                            uint64_t *n_upper_bound) {
-    SpawnerHost *sp = get_spawner(ctx, h);
-    if (!sp || type >= sp->seg.size() || !d_out) return FW_EINVAL;
-    if (poll_device_error(ctx), sp->poisoned) return poisoned_status(ctx);
-    hipSetDevice(ctx->device);
-    const uint32_t si = sp->seg[type];
+    SpawnerCall r;
+    if (!begin_call(ctx, h, r, Then::nothing, [&](const SpawnerHost &sp) { return type < sp.seg.size() && d_out; })) return r.st;
+    const uint32_t si = r.sp->seg[type];
     const SegHost &S = ctx->segs[si];
     const uint32_t ub = (uint32_t)std::min<uint64_t>(S.nested_fed ? S.capacity : std::min(S.ub, S.capacity), cap);
     if (n_upper_bound) *n_upper_bound = ub;
@@ -615,21 +622,18 @@ fw_status fw_spawner_pack_instances_device(fw_ctx *ctx, fw_spawner h, uint32_t t
         if (jst) return jst;
     }
     // (no synchronisation: the kernel reads the count -- and a range ring's old part -- from the device)
-    FW_HIP(ctx, fw_launch_pack_instances(ctx->stream, seg_view(ctx, si, ctx->parity), ctx->g.count + (size_t)ctx->parity * ctx->max_seg + si, ub,
-                                         d_out));
+    FW_HIP(ctx, fw_launch_pack_instances(ctx->stream, seg_view(ctx, si, ctx->parity), count_slot(ctx, si), ub, d_out));
     return FW_OK;
 }
 
 static fw_status attach_instances(fw_ctx *ctx, fw_spawner h, uint32_t type, void *d_out, uint64_t cap, bool window) {
-    SpawnerHost *sp = get_spawner(ctx, h);
-    if (!sp || type >= sp->seg.size() || (d_out && !cap)) return FW_EINVAL;
-    if (poll_device_error(ctx), sp->poisoned) return poisoned_status(ctx);
-    hipSetDevice(ctx->device);
-    fw_status st = sync(ctx);  // kernels in flight hold the old record
+    SpawnerCall r;  // (Then::sync: kernels in flight hold the old record)
+    if (!begin_call(ctx, h, r, Then::sync, [&](const SpawnerHost &sp) { return type < sp.seg.size() && !(d_out && !cap); })) return r.st;
+    SpawnerHost *const sp = r.sp;
     // ... and whatever the caller enqueued on ITS streams to initialise the buffer has happened before a frame writes to it
     // (the context's streams are non-blocking ones: nothing else orders them against, say, a fill on the null stream)
-    if (!st && d_out) FW_HIP(ctx, hipDeviceSynchronize());
-    if (st) return st;
+    if (d_out) FW_HIP(ctx, hipDeviceSynchronize());
+    fw_status st;
     if (d_out && !window && ctx->segs[sp->seg[type]].range) {
         // records at index `list position` counted from 0: a tile of a range ring only knows that once the whole old part
         // has been counted -- such a type continues on the compacting path (the windowed attach keeps it a ring)
@@ -660,8 +664,8 @@ fw_status fw_spawner_attach_instances_window(fw_ctx *ctx, fw_spawner h, uint32_t
 }
 
 fw_status fw_spawner_instance_window(fw_ctx *ctx, fw_spawner h, uint32_t type, uint64_t *first, uint64_t *count) {
-    SpawnerRead r;
-    if (!begin_read(ctx, h, r, [&](const SpawnerHost &sp) { return type < sp.seg.size() && first && count; })) return r.st;
+    SpawnerCall r;
+    if (!begin_call(ctx, h, r, Then::counts, [&](const SpawnerHost &sp) { return type < sp.seg.size() && first && count; })) return r.st;
     const uint32_t si = r.sp->seg[type];
     const SegHost &S = ctx->segs[si];
     uint32_t dead = 0;
@@ -673,8 +677,8 @@ fw_status fw_spawner_instance_window(fw_ctx *ctx, fw_spawner h, uint32_t type, u
 
 fw_status fw_spawner_pack_instances(fw_ctx *ctx, fw_spawner h, uint32_t type, fw_particle_instance *out, uint64_t cap,
                                     uint64_t *n_out) {
-    SpawnerRead r;
-    if (!begin_read(ctx, h, r, [&](const SpawnerHost &sp) { return type < sp.seg.size(); })) return r.st;
+    SpawnerCall r;
+    if (!begin_call(ctx, h, r, Then::counts, [&](const SpawnerHost &sp) { return type < sp.seg.size(); })) return r.st;
     const uint32_t n = r.c[r.sp->seg[type]];
     if (n_out) *n_out = n;
     const uint64_t m = std::min<uint64_t>(n, cap);
@@ -691,18 +695,11 @@ fw_status fw_spawner_pack_instances(fw_ctx *ctx, fw_spawner h, uint32_t type, fw
 }
 
 fw_status fw_spawner_aabb(fw_ctx *ctx, fw_spawner h, float out_min[3], float out_max[3], int32_t *any) {
-    SpawnerHost *sp = get_spawner(ctx, h);
-    if (!sp || !out_min || !out_max) return FW_EINVAL;
-    if (poll_device_error(ctx), sp->poisoned) return poisoned_status(ctx);
-    hipSetDevice(ctx->device);
-    if (!ctx->h_aabb) {
-        fw_status st = alloc_buf(ctx, ctx->h_aabb, 8, Mem::pinned);
-        if (st) return st;
-    }
-    {
-        fw_status jst = join_side(ctx);  // (the query kernels run on the main stream and may read rings)
-        if (jst) return jst;
-    }
+    SpawnerCall call;  // (Then::join: the query kernels run on the main stream and may read rings)
+    if (!begin_call(ctx, h, call, Then::join, [&](const SpawnerHost &) { return out_min && out_max; })) return call.st;
+    const SpawnerHost *const sp = call.sp;
+    if (!ctx->h_aabb)
+        if (fw_status st = alloc_buf(ctx, ctx->h_aabb, 8, Mem::pinned)) return st;
     // the query kernels take up to eight particle types at a time (their segment list rides in the kernel arguments): a
     // spawner with more is answered in chunks, folded here -- min / max are exact and order-independent
     const size_t nt = sp->seg.size();
@@ -773,8 +770,7 @@ fw_status fw_ctx_live_count_device(fw_ctx *ctx, void *d_out_u64) {
     hipSetDevice(ctx->device);
     fw_status jst = join_side(ctx);  // the counts of ring segments are written by the side stream's launches
     if (jst) return jst;
-    FW_HIP(ctx, fw_launch_total(ctx->stream, ctx->g.count + (size_t)ctx->parity * ctx->max_seg,
-                                (uint32_t)ctx->segs.size(), (unsigned long long *)d_out_u64));
+    FW_HIP(ctx, fw_launch_total(ctx->stream, count_slot(ctx), (uint32_t)ctx->segs.size(), (unsigned long long *)d_out_u64));
     return FW_OK;
 }
 
@@ -796,11 +792,7 @@ fw_status fw_ctx_last_step_updated(fw_ctx *ctx, uint64_t *out) {
     hipSetDevice(ctx->device);
     fw_status st = sync(ctx);
     if (st) return st;
-    unsigned long long now = 0, slots[FW_STAT_SLOTS];
-    FW_HIP(ctx, hipMemcpy(slots, ctx->g.stats, sizeof slots, hipMemcpyDeviceToHost));
-    for (unsigned long long v : slots) now += v;
-    *out = now;  // running total of particles that entered update_particles
-    return FW_OK;
+    return read_stat_total(ctx, out);
 }
 
 fw_status fw_ctx_kernel_timing(fw_ctx *ctx, int32_t enable) {
@@ -832,11 +824,7 @@ fw_status fw_ctx_kernel_timing(fw_ctx *ctx, int32_t enable) {
     }
     ctx->timing = enable != 0;
     ctx->tev_used = 0, ctx->tev_frames = 0;
-    unsigned long long now = 0, slots[FW_STAT_SLOTS];
-    FW_HIP(ctx, hipMemcpy(slots, ctx->g.stats, sizeof slots, hipMemcpyDeviceToHost));
-    for (unsigned long long v : slots) now += v;
-    ctx->timing_particles_start = now;
-    return FW_OK;
+    return read_stat_total(ctx, &ctx->timing_particles_start);
 }
 
 fw_status fw_ctx_kernel_timing_read(fw_ctx *ctx, double *ms_total, uint64_t *launches, uint64_t *particles) {
@@ -853,9 +841,8 @@ fw_status fw_ctx_kernel_timing_read(fw_ctx *ctx, double *ms_total, uint64_t *lau
     const uint64_t nl = ctx->tev_frames;  // frames: a frame's update may be several launches (FIFO + general), all summed
     if (ms_total) *ms_total = ms;
     if (launches) *launches = nl;
-    unsigned long long now = 0, slots[FW_STAT_SLOTS];
-    FW_HIP(ctx, hipMemcpy(slots, ctx->g.stats, sizeof slots, hipMemcpyDeviceToHost));
-    for (unsigned long long v : slots) now += v;
+    uint64_t now = 0;
+    if ((st = read_stat_total(ctx, &now))) return st;
     if (particles) *particles = now - ctx->timing_particles_start;
     return FW_OK;
 }

@@ -292,7 +292,7 @@ fw_status refresh_counts_exact(fw_ctx *ctx) {
     const uint32_t n = (uint32_t)ctx->segs.size();
     if (!n) return FW_OK;
     std::vector<uint32_t> c(n);
-    FW_HIP(ctx, hipMemcpy(c.data(), ctx->g.count + (size_t)ctx->parity * ctx->max_seg, n * sizeof(uint32_t),
+    FW_HIP(ctx, hipMemcpy(c.data(), count_slot(ctx), n * sizeof(uint32_t),
                           hipMemcpyDeviceToHost));
     for (uint32_t i = 0; i < n; i++)
         if (ctx->segs[i].in_use) ctx->segs[i].ub = c[i];
@@ -398,7 +398,7 @@ fw_status read_counts(fw_ctx *ctx, std::vector<uint32_t> &out) {
     if (st) return st;
     out.assign(ctx->segs.size(), 0);
     if (!out.empty())
-        FW_HIP(ctx, hipMemcpy(out.data(), ctx->g.count + (size_t)ctx->parity * ctx->max_seg,
+        FW_HIP(ctx, hipMemcpy(out.data(), count_slot(ctx),
                               out.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
     if ((st = refresh_rold(ctx))) return st;
     return check_device_errors(ctx);

@@ -39,21 +39,6 @@ __global__ __launch_bounds__(FW_QUERY_BLOCK) void fw_k_cast_rays(const FwCollide
                                      __builtin_bit_cast(float, 0u)};
 }
 
-hipError_t fw_launch_cast_rays(hipStream_t s, const FwGlobals &g, const void *d_rays, uint64_t n, void *d_hits) {
-    const bool mesh = g.n_mesh_inst != 0u;  // (no instances: the form without the mesh loop, as the update kernels pick theirs)
-    for (uint64_t first = 0; first < n; first += FW_QUERY_MAX_LAUNCH) {
-        const uint32_t cnt = (uint32_t)(n - first < FW_QUERY_MAX_LAUNCH ? n - first : FW_QUERY_MAX_LAUNCH);
-        const float4 *rays = static_cast<const float4 *>(d_rays) + 2 * first;
-        float4 *hits = static_cast<float4 *>(d_hits) + 2 * first;
-        const dim3 grid((cnt + FW_QUERY_BLOCK - 1) / FW_QUERY_BLOCK), block(FW_QUERY_BLOCK);
-        if (mesh)
-            hipLaunchKernelGGL(fw_k_cast_rays<true>, grid, block, 0, s, g.colliders, g.n_colliders, g.mesh_inst, g.n_mesh_inst, rays, cnt, hits);
-        else
-            hipLaunchKernelGGL(fw_k_cast_rays<false>, grid, block, 0, s, g.colliders, g.n_colliders, g.mesh_inst, 0u, rays, cnt, hits);
-    }
-    return hipGetLastError();
-}
-
 template <bool MESH>
 __global__ __launch_bounds__(FW_QUERY_BLOCK) void fw_k_project_points(const FwCollider *colliders, uint32_t n_colliders, const FwMeshInst *meshes,
                                                                       uint32_t n_mesh, const float4 *points, uint32_t n, float4 *out) {
@@ -69,17 +54,26 @@ __global__ __launch_bounds__(FW_QUERY_BLOCK) void fw_k_project_points(const FwCo
                                     __builtin_bit_cast(float, p.is_inside)};
 }
 
-hipError_t fw_launch_project_points(hipStream_t s, const FwGlobals &g, const void *d_points, uint64_t n, void *d_out) {
-    const bool mesh = g.n_mesh_inst != 0u;
+// The host half of both queries: launches of at most FW_QUERY_MAX_LAUNCH records, each the form without the mesh loop when the world
+// holds no instances (as the update kernels pick theirs).  in_quads / out_quads: float4 per input / output record.
+template <typename K>
+static hipError_t fw_launch_query(hipStream_t s, const FwGlobals &g, K with_mesh, K without_mesh, const void *d_in, uint32_t in_quads, uint64_t n,
+                                  void *d_out, uint32_t out_quads) {
+    const K kernel = g.n_mesh_inst != 0u ? with_mesh : without_mesh;
     for (uint64_t first = 0; first < n; first += FW_QUERY_MAX_LAUNCH) {
         const uint32_t cnt = (uint32_t)(n - first < FW_QUERY_MAX_LAUNCH ? n - first : FW_QUERY_MAX_LAUNCH);
-        const float4 *points = static_cast<const float4 *>(d_points) + first;
-        float4 *out = static_cast<float4 *>(d_out) + 2 * first;
+        const float4 *in = static_cast<const float4 *>(d_in) + in_quads * first;
+        float4 *out = static_cast<float4 *>(d_out) + out_quads * first;
         const dim3 grid((cnt + FW_QUERY_BLOCK - 1) / FW_QUERY_BLOCK), block(FW_QUERY_BLOCK);
-        if (mesh)
-            hipLaunchKernelGGL(fw_k_project_points<true>, grid, block, 0, s, g.colliders, g.n_colliders, g.mesh_inst, g.n_mesh_inst, points, cnt, out);
-        else
-            hipLaunchKernelGGL(fw_k_project_points<false>, grid, block, 0, s, g.colliders, g.n_colliders, g.mesh_inst, 0u, points, cnt, out);
+        hipLaunchKernelGGL(kernel, grid, block, 0, s, g.colliders, g.n_colliders, g.mesh_inst, g.n_mesh_inst, in, cnt, out);
     }
     return hipGetLastError();
+}
+
+hipError_t fw_launch_cast_rays(hipStream_t s, const FwGlobals &g, const void *d_rays, uint64_t n, void *d_hits) {
+    return fw_launch_query(s, g, fw_k_cast_rays<true>, fw_k_cast_rays<false>, d_rays, 2, n, d_hits, 2);
+}
+
+hipError_t fw_launch_project_points(hipStream_t s, const FwGlobals &g, const void *d_points, uint64_t n, void *d_out) {
+    return fw_launch_query(s, g, fw_k_project_points<true>, fw_k_project_points<false>, d_points, 1, n, d_out, 2);
 }
