@@ -87,6 +87,37 @@ class PointProjection(C.Structure):
                 ("triangle", C.c_uint32), ("is_inside", C.c_uint32)]
 
 
+class PathSettings(C.Structure):
+    _fields_ = [("dt", C.c_float), ("n_steps", C.c_uint32), ("acceleration", C.c_float * 3), ("linear_drag", C.c_float),
+                ("collision", CollisionSettings)]
+
+
+class Path(C.Structure):
+    _fields_ = [("position", C.c_float * 3), ("age", C.c_float), ("velocity", C.c_float * 3), ("lifetime", C.c_float)]
+
+
+class PathResult(C.Structure):
+    _fields_ = [("position", C.c_float * 3), ("age", C.c_float), ("velocity", C.c_float * 3), ("steps", C.c_uint32),
+                ("contact_point", C.c_float * 3), ("contact_step", C.c_uint32), ("contact_normal", C.c_float * 3), ("status", C.c_uint32),
+                ("kind", C.c_int32), ("index", C.c_uint32), ("triangle", C.c_uint32), ("n_contacts", C.c_uint32)]
+
+
+def fill_collision(d, cs):
+    d.enabled = 1 if cs is not None else 0
+    if cs is not None:
+        d.restitution, d.friction = float(cs.restitution), float(cs.friction)
+        d.destroy_on_collision = 1 if cs.destroy_on_collision else 0
+        d.filter_mask = int(cs.filter_mask) & 0xFFFFFFFF
+
+
+def make_path_settings(ps):
+    d = PathSettings()
+    d.dt, d.n_steps, d.linear_drag = float(ps.dt), int(ps.n_steps), float(ps.linear_drag)
+    d.acceleration[:] = [float(x) for x in ps.acceleration]
+    fill_collision(d.collision, ps.collision_settings)
+    return d
+
+
 def make_mesh_colliders(instances):
     arr = (MeshCollider * max(len(instances), 1))()
     for d, m in zip(arr, instances):
@@ -222,12 +253,7 @@ def make_desc(spawner: S.ParticleSpawner, uid: int):
         d.pbr = 1 if p.pbr else 0
         d.report_destroyed = 1 if p.particles_destroyed is not None else 0
         d.capacity = int(p.capacity)
-        cs = p.collision_settings
-        d.collision.enabled = 1 if cs is not None else 0
-        if cs is not None:
-            d.collision.restitution, d.collision.friction = float(cs.restitution), float(cs.friction)
-            d.collision.destroy_on_collision = 1 if cs.destroy_on_collision else 0
-            d.collision.filter_mask = int(cs.filter_mask) & 0xFFFFFFFF
+        fill_collision(d.collision, p.collision_settings)
     for i, e in enumerate(spawner.emission_settings):
         fill_emission(es[i], e)
     desc = SpawnerDesc()
@@ -263,6 +289,8 @@ SYMBOLS = [
     ("fw_ctx_cast_rays_device", C.c_int, [_P, _P, C.c_uint64, _P]),
     ("fw_ctx_project_points", C.c_int, [_P, _P, C.c_uint64, _P]),
     ("fw_ctx_project_points_device", C.c_int, [_P, _P, C.c_uint64, _P]),
+    ("fw_ctx_trace_paths", C.c_int, [_P, C.POINTER(PathSettings), _P, C.c_uint64, _P, _P]),
+    ("fw_ctx_trace_paths_device", C.c_int, [_P, C.POINTER(PathSettings), _P, C.c_uint64, _P, _P]),
     ("fw_spawner_create", C.c_int, [_P, C.POINTER(SpawnerDesc), C.POINTER(C.c_int32)]),
     ("fw_spawner_update_settings", C.c_int, [_P, C.c_int32, C.POINTER(SpawnerDesc)]),
     ("fw_spawner_destroy", C.c_int, [_P, C.c_int32]),

@@ -396,10 +396,22 @@ FW_HD bool fw_cast_ray(const FwCollider *colliders, uint32_t n, const FwMeshInst
     return fw_cast_ray(colliders, n, meshes, n_mesh, mask, origin, dir, max_distance, best, id);
 }
 
+// WHAT a particle met on its way (fw_ctx_trace_paths: fw_path_result::contact_* / n_contacts) is a policy of particle_collision, as
+// WHO was hit is one of the cast: the observer is told once per hit a sub-step's cast returns -- the position the hit happened at
+// (distance > 0: after the advance along the velocity, before the nudge off the surface; distance 0: before the push-out), the
+// cast's normal as reported (zero for an inside hit), the distance, and the identity its cast collected -- and it names the
+// identity policy that cast runs with.  The particles do not ask (FwNoContact: empty, its cast runs with FwNoHitId, everything
+// folds away and the update kernels compile to what they were); the path query does (FwPathContacts, fw_trace.h).
+struct FwNoContact {
+    using Id = FwNoHitId;
+    FW_HD void hit(fw_v3, fw_v3, float, const Id &) {}
+};
+
 // particle_collision (src/core.rs:744-800).  Returns should_destroy; *pos / *vel are updated in place.
+template <class Obs>
 FW_HD bool fw_particle_collision(fw_v3 *pos_io, fw_v3 *vel_io, float delta, float restitution, float friction,
                                  bool destroy_on_collision, uint32_t mask, const FwCollider *colliders, uint32_t n,
-                                 const FwMeshInst *meshes, uint32_t n_mesh) {
+                                 const FwMeshInst *meshes, uint32_t n_mesh, Obs &obs) {
     fw_v3 pos = *pos_io, vel = *vel_io;
     const float orig_delta = delta;
     int n_steps = 0;
@@ -409,8 +421,10 @@ FW_HD bool fw_particle_collision(fw_v3 *pos_io, fw_v3 *vel_io, float delta, floa
         const float len = fw_len3(vel);
         const fw_v3 dir = (len < INFINITY && len > 0.0f) ? fw_v3{vel.x / len, vel.y / len, vel.z / len} : fw_v3{0.0f, 1.0f, 0.0f};
         FwRayHit hit;
-        if (fw_cast_ray(colliders, n, meshes, n_mesh, mask, pos, dir, fw_len3(vel) * delta, &hit)) {
+        typename Obs::Id id;
+        if (fw_cast_ray(colliders, n, meshes, n_mesh, mask, pos, dir, fw_len3(vel) * delta, &hit, id)) {
             if (hit.distance == 0.0f) {  // core.rs:766-776
+                obs.hit(pos, hit.normal, hit.distance, id);
                 fw_v3 normal = hit.normal;
                 if (normal.x == 0.0f && normal.y == 0.0f && normal.z == 0.0f) {
                     if (vel.x != 0.0f || vel.y != 0.0f || vel.z != 0.0f)
@@ -422,6 +436,7 @@ FW_HD bool fw_particle_collision(fw_v3 *pos_io, fw_v3 *vel_io, float delta, floa
                 pos = fw_add3(pos, fw_scale3(fw_scale3(normal, k), delta));  // vel.length().max(1.) * normal * delta
             } else {  // core.rs:777-787
                 pos = fw_add3(pos, fw_scale3(fw_normalize_or_zero(vel), hit.distance));
+                obs.hit(pos, hit.normal, hit.distance, id);
                 const fw_v3 vel_project0 = fw_project_onto(vel, hit.normal);
                 const fw_v3 vel_reject = fw_sub3(vel, vel_project0);          // reject_from = self - project_onto
                 const fw_v3 vel_project = fw_project_onto(vel, hit.normal);
@@ -444,4 +459,10 @@ FW_HD bool fw_particle_collision(fw_v3 *pos_io, fw_v3 *vel_io, float delta, floa
     }
     *pos_io = pos, *vel_io = vel;
     return should_destroy;
+}
+FW_HD bool fw_particle_collision(fw_v3 *pos_io, fw_v3 *vel_io, float delta, float restitution, float friction,
+                                 bool destroy_on_collision, uint32_t mask, const FwCollider *colliders, uint32_t n,
+                                 const FwMeshInst *meshes, uint32_t n_mesh) {
+    FwNoContact obs;
+    return fw_particle_collision(pos_io, vel_io, delta, restitution, friction, destroy_on_collision, mask, colliders, n, meshes, n_mesh, obs);
 }

@@ -1014,6 +1014,7 @@ struct fw_ctx {
     // the host forms of the queries (fw_engine_query.cpp: query_staged): pinned staging and device buffers for the input and the
     // output records, grown on demand and kept; the device forms need nothing of their own
     HipBuf<float4> q_in_h, q_out_h, q_in_d, q_out_d;
+    HipBuf<float4> q_out2_h, q_out2_d;  // ... and for the optional second output (the path query's samples): untouched until one is asked for
     HipBuf<float> d_aabb;      // 256 partial boxes of the AABB query
     HipBuf<float> h_aabb;      // pinned result {min.xyz, any, max.xyz, -}
     HipBuf<unsigned long long> d_total;

@@ -435,3 +435,9 @@ hipError_t fw_launch_cast_rays(hipStream_t s, const FwGlobals &g, const void *d_
 // The point query (fw_k_query.hip; fw_ctx_project_points[_device]): n fw_point records (16 bytes) at d_points -> n fw_point_projection
 // records (32 bytes) at d_out, in the same way.
 hipError_t fw_launch_project_points(hipStream_t s, const FwGlobals &g, const void *d_points, uint64_t n, void *d_out);
+// The path query (fw_k_query.hip; fw_ctx_trace_paths[_device]): n fw_path records (32 bytes) at d_paths -> n fw_path_result records (80
+// bytes) at d_out and, d_samples not null, settings.n_steps * n float4 {position, age} at d_samples[step * n + path]; settings
+// (fw_trace.h) travel in the kernel arguments.
+struct FwPathSettings;
+hipError_t fw_launch_trace_paths(hipStream_t s, const FwGlobals &g, const FwPathSettings &settings, const void *d_paths, uint64_t n, void *d_out,
+                                 void *d_samples);

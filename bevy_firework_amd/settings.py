@@ -461,3 +461,47 @@ POINT_PROJECTION_DTYPE = np.dtype(
     ]
 )
 assert POINT_PROJECTION_DTYPE.itemsize == 32
+
+# fw_path_settings / fw_path / fw_path_result (include/firework_hip.h: PATH QUERIES): the records of ParticleSystem.trace_paths
+PATH_RUNNING, PATH_EXPIRED, PATH_DESTROYED = 0, 1, 2
+PATH_MAX_STEPS = 4096
+
+
+@dataclass
+class PathSettings:
+    """fw_path_settings: what a batch of traced paths shares -- the step, how many of them, and the three settings of a particle type
+    a step reads (ParticleSettings.acceleration / linear_drag / collision_settings; None: no casts, position += velocity * dt)."""
+
+    dt: float
+    n_steps: int
+    acceleration: Vec3 = (0.0, 0.0, 0.0)
+    linear_drag: float = 0.0
+    collision_settings: Optional[ParticleCollisionSettings] = None
+
+
+PATH_DTYPE = np.dtype(
+    [
+        ("position", np.float32, 3),
+        ("age", np.float32),
+        ("velocity", np.float32, 3),
+        ("lifetime", np.float32),
+    ]
+)
+assert PATH_DTYPE.itemsize == 32
+PATH_RESULT_DTYPE = np.dtype(
+    [
+        ("position", np.float32, 3),
+        ("age", np.float32),
+        ("velocity", np.float32, 3),
+        ("steps", np.uint32),
+        ("contact_point", np.float32, 3),
+        ("contact_step", np.uint32),
+        ("contact_normal", np.float32, 3),
+        ("status", np.uint32),
+        ("kind", np.int32),
+        ("index", np.uint32),
+        ("triangle", np.uint32),
+        ("n_contacts", np.uint32),
+    ]
+)
+assert PATH_RESULT_DTYPE.itemsize == 80

@@ -326,6 +326,37 @@ class ParticleSystem:
         self._check(self._lib.fw_ctx_project_points_device(self._ctx, C.c_void_p(int(points_ptr)) if points_ptr else None, int(n),
                                                            C.c_void_p(int(out_ptr)) if out_ptr else None))
 
+    def trace_paths(self, settings: S.PathSettings, positions, velocities, ages=0.0, lifetimes=np.inf, samples: bool = False):
+        """Where particles WOULD go: positions [n, 3], velocities [n, 3], ages and lifetimes [n] or scalars, stepped settings.n_steps
+        times by settings.dt with the arithmetic update_particles gives a particle of a type with these settings, in the collider
+        world as it stands behind every call made so far (frozen for the whole path) -> a structured array
+        (settings.PATH_RESULT_DTYPE): where each path ended and how (status: settings.PATH_*), its first contact and how many it had.
+        samples=True: -> (results, samples[n_steps, n, 4]), {position, age} after every step.  Nothing is spawned.  Synchronises."""
+        p = np.asarray(positions, dtype=np.float32).reshape(-1, 3)
+        paths = np.zeros(len(p), dtype=S.PATH_DTYPE)
+        paths["position"] = p
+        paths["velocity"] = np.asarray(velocities, dtype=np.float32).reshape(-1, 3)
+        paths["age"] = np.asarray(ages, dtype=np.float32)
+        paths["lifetime"] = np.asarray(lifetimes, dtype=np.float32)
+        return self.trace_path_records(settings, paths, samples)
+
+    def trace_path_records(self, settings: S.PathSettings, paths: np.ndarray, samples: bool = False):
+        """trace_paths for paths that are already settings.PATH_DTYPE records"""
+        paths = np.ascontiguousarray(paths, dtype=S.PATH_DTYPE)
+        out = np.zeros(len(paths), dtype=S.PATH_RESULT_DTYPE)
+        smp = np.zeros((int(settings.n_steps), len(paths), 4), dtype=np.float32) if samples else None
+        self._check(self._lib.fw_ctx_trace_paths(self._ctx, C.byref(_ffi.make_path_settings(settings)), paths.ctypes.data_as(C.c_void_p), len(paths),
+                                                 out.ctypes.data_as(C.c_void_p), smp.ctypes.data_as(C.c_void_p) if samples else None))
+        return (out, smp) if samples else out
+
+    def trace_paths_device(self, settings: S.PathSettings, paths_ptr: int, n: int, out_ptr: int, samples_ptr: int = 0) -> None:
+        """trace_paths for n settings.PATH_DTYPE records at device address paths_ptr into n settings.PATH_RESULT_DTYPE records at
+        out_ptr and, samples_ptr not 0, settings.n_steps * n float4 there ([step][path]): enqueued on this context's stream, never
+        synchronises; the buffers are read and written only by work enqueued inside the call."""
+        self._check(self._lib.fw_ctx_trace_paths_device(self._ctx, C.byref(_ffi.make_path_settings(settings)), C.c_void_p(int(paths_ptr)) if paths_ptr else None,
+                                                        int(n), C.c_void_p(int(out_ptr)) if out_ptr else None,
+                                                        C.c_void_p(int(samples_ptr)) if samples_ptr else None))
+
     # -- ECS-like surface ------------------------------------------------------------------------
     def spawn(self, spawner: S.ParticleSpawner, transform: Optional[S.Transform] = None,
               global_transform: Optional[S.Transform] = None, modifier: Optional[S.EffectModifier] = None,

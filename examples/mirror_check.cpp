@@ -11,7 +11,8 @@
 // spawner, a batch of rays every tenth frame (tests/test_cpp_host_capsule.py runs the same through the Python mirror); `project` is
 // another -- a fixed small world (one collider of each kind plus one mesh instance), a fixed list of points projected onto it
 // (project_points, and project_points_device through device buffers of its own), every field's bits printed per point
-// (tests/test_cpp_host_project.py).  Prints, every tenth frame, the live counts and an
+// (tests/test_cpp_host_project.py); `paths` another -- the same world, a fixed list of hypothetical particles traced through it
+// (trace_paths, trace_paths_device), every field's bits printed per path (tests/test_cpp_host_paths.py).  Prints, every tenth frame, the live counts and an
 // FNV-1a digest of every particle record; tests/test_cpp_host.py runs the same scenario through the Python mirror and
 // expects the same lines: both mirrors marshal the reference's settings into the C ABI the same way.
 //
@@ -135,8 +136,66 @@ static int project_scenario() {
     return 0;
 }
 
+// `mirror_check paths`: the world of `project`, 96 hypothetical particles on the same lattice thrown down and sideways (every operand
+// exact in fp32), traced for 24 steps under gravity, drag, restitution and friction (trace_paths with samples, and trace_paths_device
+// through device buffers of its own); one line per path with the bits of every field of its result
+static int paths_scenario() {
+    try {
+        ParticleSystemPlugin app(0, /*seed*/ 0x00C0FFEE);
+        app.set_colliders({Collider::Plane({0.0f, -1.0f, 0.0f}, {0.0f, 1.0f, 0.0f}), Collider::Sphere({1.0f, 0.5f, 0.0f}, 0.75f, 2u),
+                           Collider::Box({-2.0f, 0.0f, 0.0f}, {0.5f, 1.0f, 0.5f}, Quat{0.0f, 0.38268343f, 0.0f, 0.92387953f}),
+                           Collider::Cylinder({0.0f, 0.5f, -2.0f}, 0.5f, 1.5f, {}, 3u),
+                           Collider::Cone({2.0f, 0.0f, 2.0f}, 0.75f, 2.0f, Quat{0.0f, 0.0f, 0.19509032f, 0.98078528f}),
+                           Collider::capsule({-0.75f, 1.0f, 1.5f}, 0.25f, 1.5f, Quat{0.30151135f, 0.0f, 0.30151135f, 0.90453404f}, 2u)});
+        const fw_mesh ramp = app.create_mesh({-2.0f, -0.25f, -2.0f, 2.0f, -0.25f, -2.0f, 2.0f, 0.25f, 2.0f, -2.0f, 0.25f, 2.0f}, {0, 2, 1, 0, 3, 2});
+        app.set_mesh_colliders({MeshCollider{ramp, {0.5f, 1.75f, 0.0f}, Quat{0.0f, 0.38268343f, 0.0f, 0.92387953f}, 3u}});
+        fw_path_settings settings{};
+        settings.dt = 0.03125f, settings.n_steps = 24u, settings.acceleration[1] = -9.75f, settings.linear_drag = 0.125f;
+        settings.collision.enabled = 1, settings.collision.restitution = 0.5f, settings.collision.friction = 0.25f, settings.collision.filter_mask = 3u;
+        std::vector<fw_path> paths(96);
+        for (size_t i = 0; i < paths.size(); i++) {
+            fw_path &p = paths[i];
+            p.position[0] = -3.0f + (float)(i % 8) * 0.875f, p.position[1] = -1.5f + (float)((i / 8) % 4) * 1.125f, p.position[2] = -2.5f + (float)(i / 32) * 2.25f;
+            p.velocity[0] = 1.5f - (float)(i % 5) * 0.75f, p.velocity[1] = -0.5f * (float)(i % 4), p.velocity[2] = (float)(i % 3) - 1.0f;
+            p.age = 0.0625f * (float)(i % 2), p.lifetime = 0.25f + 0.125f * (float)(i % 7);
+        }
+        std::vector<float> samples;
+        const std::vector<fw_path_result> host = app.trace_paths(settings, paths, &samples);
+        std::vector<fw_path_result> from_device(paths.size());
+        std::vector<float> samples_from_device(samples.size());
+        void *d_paths = nullptr, *d_out = nullptr, *d_samples = nullptr;
+        if (hipMalloc(&d_paths, paths.size() * sizeof(fw_path)) != hipSuccess || hipMalloc(&d_out, paths.size() * sizeof(fw_path_result)) != hipSuccess ||
+            hipMalloc(&d_samples, samples.size() * sizeof(float)) != hipSuccess)
+            throw Error(FW_EHIP, "hipMalloc");
+        hipStream_t st = (hipStream_t)app.stream();
+        if (hipMemcpyAsync(d_paths, paths.data(), paths.size() * sizeof(fw_path), hipMemcpyHostToDevice, st) != hipSuccess) throw Error(FW_EHIP, "hipMemcpyAsync");
+        app.trace_paths_device(settings, d_paths, paths.size(), d_out, d_samples);
+        if (hipMemcpyAsync(from_device.data(), d_out, paths.size() * sizeof(fw_path_result), hipMemcpyDeviceToHost, st) != hipSuccess ||
+            hipMemcpyAsync(samples_from_device.data(), d_samples, samples.size() * sizeof(float), hipMemcpyDeviceToHost, st) != hipSuccess)
+            throw Error(FW_EHIP, "hipMemcpyAsync");
+        app.synchronize();
+        (void)hipFree(d_paths), (void)hipFree(d_out), (void)hipFree(d_samples);
+        for (size_t i = 0; i < host.size(); i++) {
+            uint32_t w[20];
+            std::memcpy(w, &host[i], sizeof w);
+            std::printf("path %zu", i);
+            for (uint32_t x : w) std::printf(" %08x", x);
+            std::printf("\n");
+        }
+        std::printf("host %016llx device %016llx samples %016llx device %016llx\n", (unsigned long long)fnv(host.data(), host.size() * sizeof(fw_path_result)),
+                    (unsigned long long)fnv(from_device.data(), from_device.size() * sizeof(fw_path_result)),
+                    (unsigned long long)fnv(samples.data(), samples.size() * sizeof(float)),
+                    (unsigned long long)fnv(samples_from_device.data(), samples_from_device.size() * sizeof(float)));
+    } catch (const Error &e) {
+        std::fprintf(stderr, "firework error %d: %s\n", (int)e.status, e.what());
+        return 1;
+    }
+    return 0;
+}
+
 int main(int argc, char **argv) {
     if (argc > 1 && std::strcmp(argv[1], "project") == 0) return project_scenario();
+    if (argc > 1 && std::strcmp(argv[1], "paths") == 0) return paths_scenario();
     if (argc > 1 && std::strcmp(argv[1], "capsule") == 0) return capsule_scenario();
     // `mirror_check mesh`: the same scenario with triangle meshes in the collider world (create, place twice, replace, destroy)
     // `mirror_check deform`: ... with both meshes deformable: the ramp's far edge rises every fifth frame, then the sheet's apex

@@ -465,6 +465,20 @@ class ParticleSystemPlugin {
     }
     // ... points and projections in device memory (n fw_point at d_points, n fw_point_projection at d_out), enqueued on stream(): never waits
     void project_points_device(const void *d_points, uint64_t n, void *d_out) { check(fw_ctx_project_points_device(ctx_, d_points, n, d_out)); }
+    // Where particles WOULD go (fw_ctx_trace_paths): every path stepped settings.n_steps times by settings.dt with the arithmetic a
+    // particle of a type with these settings gets, in the collider world as it stands (frozen for the whole path); per path where and
+    // how it ended (FW_PATH_*), its first contact and the number of contacts.  samples (may be null): resized to n_steps * n * 4
+    // floats, {position, age} of path i after step k at [(k * n + i) * 4].  Nothing is spawned.  Waits for the result.
+    std::vector<fw_path_result> trace_paths(const fw_path_settings &settings, const std::vector<fw_path> &paths, std::vector<float> *samples = nullptr) {
+        std::vector<fw_path_result> out(paths.size());
+        if (samples) samples->assign((size_t)settings.n_steps * paths.size() * 4, 0.0f);
+        check(fw_ctx_trace_paths(ctx_, &settings, paths.data(), (uint64_t)paths.size(), out.data(), samples && !samples->empty() ? samples->data() : nullptr));
+        return out;
+    }
+    // ... paths, results and samples (or null) in device memory, enqueued on stream(): never waits
+    void trace_paths_device(const fw_path_settings &settings, const void *d_paths, uint64_t n, void *d_out, void *d_samples = nullptr) {
+        check(fw_ctx_trace_paths_device(ctx_, &settings, d_paths, n, d_out, d_samples));
+    }
 
     // update_aabbs (render.rs:677-703) fused into the update: every frame leaves per-tile boxes, ParticleSpawnerData::aabb
     // folds them instead of re-reading the particles

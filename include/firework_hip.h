@@ -331,6 +331,80 @@ typedef struct fw_point_projection { /* 32 bytes */
     uint32_t is_inside; /* 1: position lies inside or on the analytic solid named; meshes never */
 } fw_point_projection;
 
+/* PATH QUERIES ("where will this spark land": an aim arc for a mortar shell, a decal or a light placed before the spark arrives, the
+ * emitter direction that clears a wall).  A ray cannot answer that: a particle falls, slows under drag, bounces with restitution and
+ * friction and lives for a limited time.  fw_ctx_trace_paths[_device] runs a batch of HYPOTHETICAL particles through n_steps frames of
+ * dt each, off the frame's path -- nothing is spawned, no spawner's state is read or written -- with the arithmetic a real particle
+ * gets.  All fp32, no fused a*b+c.  One fw_path_settings per call, shared by the batch.
+ *   SAME STEP one step is update_particles (core.rs:594-643) restricted to age, position and velocity, in this order:
+ *               1. age = age + dt;
+ *               2. age >= lifetime: the path ends FW_PATH_EXPIRED; position and velocity stay as they were, age is the advanced one
+ *                  (what a destroyed record carries);
+ *               3. otherwise particle_collision(position, velocity, dt) (core.rs:744-800: up to four sub-steps, each a cast along the
+ *                  velocity of length |velocity| * remaining time into the world under collision.filter_mask, the push-out of an
+ *                  inside hit, the bounce with restitution and friction) when collision.enabled, else position = position +
+ *                  velocity * dt per component;
+ *               4. the collision said destroy (destroy_on_collision and a hit): the path ends FW_PATH_DESTROYED with the
+ *                  position and velocity the collision left;
+ *               5. otherwise velocity = velocity + (acceleration - velocity * linear_drag) * dt per component, and the step is
+ *                  survived (`steps` counts these).
+ *             The promise: take a particle of a type with these settings (acceleration, linear_drag, collision), written with
+ *             fw_spawner_write_particles at the path's position, velocity, age and lifetime.  After k calls of fw_step(dt) in the same
+ *             world its position, velocity and age hold, bit for bit, what the path holds after k steps; it is removed in the step in
+ *             which the path ends, and its destroyed record holds the result's position, velocity and age.
+ *   CONTACTS  every hit a sub-step's cast returns is a contact, the distance-0 "inside" hit included; n_contacts counts them over the
+ *             path.  The FIRST fills contact_*: contact_step is the step it happened in, counted from 0; contact_normal is the cast's
+ *             normal as reported (zero for an inside hit, before core.rs:767-774 replaces it); contact_point is, for distance > 0, the
+ *             position after position += normalize_or_zero(velocity) * distance and before the + normal * 0.0001 nudge, for distance
+ *             == 0 the position before the push-out; kind / index / triangle name what was hit as in fw_ray_hit.  No contact:
+ *             contact_point = contact_normal = 0, kind = FW_HIT_NONE, index = triangle = contact_step = 0xFFFFFFFF, n_contacts = 0.
+ *   RESULT    position, velocity and age after the last step taken; steps = the steps survived; status = FW_PATH_RUNNING when all
+ *             n_steps were.  n_steps == 0 gives the inputs back: RUNNING, steps 0, no contact.
+ *   SAMPLES   optional (NULL: none, and nothing is reserved, written or copied for them): n_steps * n records of four floats,
+ *             samples[(step * n + i) * 4 ..] = {position, age} of path i after that step.  Steps after a path has ended repeat its
+ *             final values (those of the result).
+ *   FROZEN WORLD  the whole path runs in the world as of the call's place in the context's stream; colliders a host moves between
+ *             frames are not predicted.
+ *   ORDER     both forms enqueue on the context's main stream (fw_ctx_stream), where collider sets, instance sets, refits and every
+ *             launch that casts rays already travel: a query sees every fw_ctx_set_colliders, fw_ctx_set_mesh_colliders and
+ *             fw_ctx_update_mesh_vertices[_device] called before it and none called after it.  The device form never waits,
+ *             allocates nothing, does no host work that grows with n or n_steps, and reads d_paths / writes d_out and d_samples ONLY
+ *             in work it enqueues itself; the settings are read on the host inside the call and travel as kernel arguments.  The
+ *             host form stages through pinned memory (grown on demand, kept by the context) and waits for its result.
+ *   ERRORS    checked in this order, FW_EINVAL with nothing enqueued: a null settings pointer; a non-finite dt; n_steps >
+ *             FW_PATH_MAX_STEPS (the cap bounds one launch's running time).  Then n == 0: FW_OK, nothing touched.  Then a null
+ *             paths or out pointer: FW_EINVAL, nothing enqueued.  NaN or infinite paths give whatever the operations give,
+ *             deterministically, and every path ends after at most n_steps steps. */
+enum { FW_PATH_RUNNING = 0, FW_PATH_EXPIRED = 1, FW_PATH_DESTROYED = 2 };
+#define FW_PATH_MAX_STEPS 4096u
+typedef struct fw_path_settings { /* one per call, shared by the batch */
+    float dt;
+    uint32_t n_steps;
+    float acceleration[3];
+    float linear_drag;
+    fw_collision_settings collision; /* enabled = 0: no casts, position += velocity * dt */
+} fw_path_settings;
+typedef struct fw_path { /* 32 bytes */
+    float position[3];
+    float age;
+    float velocity[3];
+    float lifetime;
+} fw_path;
+typedef struct fw_path_result { /* 80 bytes */
+    float position[3];
+    float age;
+    float velocity[3];
+    uint32_t steps;          /* steps survived */
+    float contact_point[3];
+    uint32_t contact_step;   /* 0xFFFFFFFF: the path met nothing */
+    float contact_normal[3];
+    uint32_t status;         /* FW_PATH_* */
+    int32_t kind;            /* FW_HIT_* of the first contact */
+    uint32_t index;          /* as fw_ray_hit.index */
+    uint32_t triangle;       /* as fw_ray_hit.triangle */
+    uint32_t n_contacts;
+} fw_path_result;
+
 enum { FW_PACING_ONESHOT = 0, FW_PACING_ONDEMAND = 1, FW_PACING_COUNT_OVER_DURATION = 2 }; /* core.rs:12-29 */
 enum { FW_MODE_GLOBAL = 0, FW_MODE_NESTED = 1 };                                           /* core.rs:47-54 */
 enum { FW_SHAPE_POINT = 0, FW_SHAPE_SPHERE = 1, FW_SHAPE_CIRCLE = 2 };                     /* emission_shape.rs:7-15 */
@@ -438,6 +512,13 @@ fw_status fw_ctx_project_points(fw_ctx *ctx, const fw_point *points, uint64_t n,
 /* the same for n fw_point records at d_points and n fw_point_projection records at d_out in DEVICE memory (16-byte aligned), read and
  * written in the order of the context's stream by the launches this call enqueues and by nothing else.  Never synchronises. */
 fw_status fw_ctx_project_points_device(fw_ctx *ctx, const void *d_points, uint64_t n, void *d_out);
+/* traces paths[n] through settings->n_steps steps and writes out[n] and, samples not NULL, samples[n_steps * n * 4] (PATH QUERIES
+ * above); host memory, synchronises */
+fw_status fw_ctx_trace_paths(fw_ctx *ctx, const fw_path_settings *settings, const fw_path *paths, uint64_t n, fw_path_result *out, float *samples);
+/* the same for n fw_path records at d_paths, n fw_path_result records at d_out and (or NULL) n_steps * n float4 at d_samples in DEVICE
+ * memory (16-byte aligned), read and written in the order of the context's stream by the launches this call enqueues and by nothing
+ * else; settings is host memory, read inside the call.  Never synchronises. */
+fw_status fw_ctx_trace_paths_device(fw_ctx *ctx, const fw_path_settings *settings, const void *d_paths, uint64_t n, void *d_out, void *d_samples);
 
 /* ---- spawners ----------------------------------------------------------------- */
 /* ParticleSpawner insertion + first sync_spawner_data (core.rs:343-365) */

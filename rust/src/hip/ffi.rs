@@ -49,6 +49,19 @@ pub const FW_HIT_NONE: i32 = 0; pub const FW_HIT_COLLIDER: i32 = 1; pub const FW
 #[repr(C)] #[derive(Clone, Copy)] pub struct fw_point_projection { // the nearest point of the world to it (32 bytes); kind / index / triangle as fw_ray_hit
     pub point: [f32; 3], pub distance: f32, pub kind: i32, pub index: u32, pub triangle: u32, pub is_inside: u32,
 }
+pub const FW_PATH_RUNNING: u32 = 0; pub const FW_PATH_EXPIRED: u32 = 1; pub const FW_PATH_DESTROYED: u32 = 2;
+pub const FW_PATH_MAX_STEPS: u32 = 4096;
+#[repr(C)] #[derive(Clone, Copy)] pub struct fw_path_settings {   // what a batch of fw_ctx_trace_paths shares; collision.enabled = 0: no casts
+    pub dt: f32, pub n_steps: u32, pub acceleration: [f32; 3], pub linear_drag: f32, pub collision: fw_collision_settings,
+}
+#[repr(C)] #[derive(Clone, Copy)] pub struct fw_path {            // one hypothetical particle (32 bytes)
+    pub position: [f32; 3], pub age: f32, pub velocity: [f32; 3], pub lifetime: f32,
+}
+#[repr(C)] #[derive(Clone, Copy)] pub struct fw_path_result {     // where it ended, its first contact (80 bytes); kind / index / triangle as fw_ray_hit
+    pub position: [f32; 3], pub age: f32, pub velocity: [f32; 3], pub steps: u32,
+    pub contact_point: [f32; 3], pub contact_step: u32, pub contact_normal: [f32; 3], pub status: u32,
+    pub kind: i32, pub index: u32, pub triangle: u32, pub n_contacts: u32,
+}
 #[repr(C)] pub struct fw_emission_settings {          // EmissionSettings, core.rs:144-162
     pub particle_index: i32, pub pacing_kind: i32, pub oneshot_count: u64,
     pub count: f32, pub duration: f32, pub offset_start: f32, pub offset_end: f32,
@@ -91,6 +104,8 @@ extern "C" {
     pub fn fw_ctx_cast_rays_device(ctx: *mut fw_ctx, d_rays: *const c_void, n: u64, d_hits: *mut c_void) -> c_int;
     pub fn fw_ctx_project_points(ctx: *mut fw_ctx, points: *const fw_point, n: u64, out: *mut fw_point_projection) -> c_int;
     pub fn fw_ctx_project_points_device(ctx: *mut fw_ctx, d_points: *const c_void, n: u64, d_out: *mut c_void) -> c_int;
+    pub fn fw_ctx_trace_paths(ctx: *mut fw_ctx, settings: *const fw_path_settings, paths: *const fw_path, n: u64, out: *mut fw_path_result, samples: *mut f32) -> c_int;
+    pub fn fw_ctx_trace_paths_device(ctx: *mut fw_ctx, settings: *const fw_path_settings, d_paths: *const c_void, n: u64, d_out: *mut c_void, d_samples: *mut c_void) -> c_int;
     pub fn fw_spawner_create(ctx: *mut fw_ctx, desc: *const fw_spawner_desc, out: *mut fw_spawner) -> c_int;
     pub fn fw_spawner_update_settings(ctx: *mut fw_ctx, h: fw_spawner, desc: *const fw_spawner_desc) -> c_int;
     pub fn fw_spawner_destroy(ctx: *mut fw_ctx, h: fw_spawner) -> c_int;
