@@ -173,6 +173,15 @@ __device__ __forceinline__ void fw_stq(char *reg, uint32_t C, uint32_t i, float4
     if (cpl) fw_stc4(reg, C, i, v);
     else fw_st4(reg, i, v);
 }
+// Q0 (position, age) of slot i: four component planes in a FIFO ring that may run under the age rule (FwSeg::cpl bit 2, round 18), a float4
+// plane everywhere else
+#define FW_CPL_Q0 4u
+__device__ __forceinline__ float4 fw_ldq0(const char *buf, uint32_t C, uint32_t i, uint32_t cpl) {
+    return fw_ldq(buf + FW_OFF_Q0(C), C, i, (cpl & FW_CPL_Q0) != 0u);
+}
+__device__ __forceinline__ float fw_ldq0_age(const char *buf, uint32_t C, uint32_t i, uint32_t cpl) {
+    return fw_ldq_w(buf + FW_OFF_Q0(C), C, i, (cpl & FW_CPL_Q0) != 0u);
+}
 template <bool NT = false>
 __device__ __forceinline__ float4 fw_ldc4w(const char *win, size_t cp, uint32_t off4) {
     return make_float4(fw_ld1w<NT>(win, off4), fw_ld1w<NT>(win + cp, off4), fw_ld1w<NT>(win + 2 * cp, off4), fw_ld1w<NT>(win + 3 * cp, off4));
@@ -230,15 +239,19 @@ struct FwOutWin {  // output planes advanced to slot `first` (workgroup-uniform)
     bool wr3;
     char *lf;
     bool wr4;  // scale plane (false, like wr5 / wr6, for a type whose instance records carry it: FW_TYPE_DERIVED)
+    // the age plane of a FIFO ring (q0 + 3 * cp); false in a launch that carries FW_TYPE_IDX_AGELESS for the ring: nobody stores the age,
+    // the host's cohort ages stand for the plane until fw_k_fifo_ages writes it back (fw_device.h)
+    bool wr_age;
+    bool q0pl;  // Q0 of the output ring is four component planes (FwSeg::cpl bit 2: a FIFO ring that may run under the age rule)
 };
 __device__ __forceinline__ FwOutWin fw_out_window(char *ob, uint32_t C, uint32_t first, const FwType &T, uint32_t force_colors,
-                                                  uint32_t n_lplanes = 0u, bool cpl = false, bool q2pl = false) {
+                                                  uint32_t n_lplanes = 0u, bool cpl = false, bool q2pl = false, bool q0pl = false, bool ageless = false) {
     const size_t f16 = (size_t)first * 16u, f4 = (size_t)first * 4u, fq = cpl ? f4 : f16;
-    return FwOutWin{ob + FW_OFF_Q0(C) + f16, ob + FW_OFF_Q1(C) + fq, ob + FW_OFF_Q2(C) + (q2pl ? f4 : f16), ob + FW_OFF_Q3(C) + fq,
+    return FwOutWin{ob + FW_OFF_Q0(C) + (q0pl ? f4 : f16), ob + FW_OFF_Q1(C) + fq, ob + FW_OFF_Q2(C) + (q2pl ? f4 : f16), ob + FW_OFF_Q3(C) + fq,
                     ob + FW_OFF_Q5(C) + f16, ob + FW_OFF_Q6(C) + f16, ob + FW_OFF_S4(C) + f4, FW_CP(C), first,
                     (T.bc_kind != 0 || force_colors != 0u) && !(T.flags & FW_TYPE_DERIVED),
                     (T.em_kind != 0 || force_colors != 0u) && !(T.flags & FW_TYPE_DERIVED), !(T.flags & FW_TYPE_NOSPIN),
-                    !(T.flags & FW_TYPE_NOSPIN), ob + FW_OFF_L(C, n_lplanes) + (size_t)first * 4u, !(T.flags & FW_TYPE_DERIVED)};
+                    !(T.flags & FW_TYPE_NOSPIN), ob + FW_OFF_L(C, n_lplanes) + (size_t)first * 4u, !(T.flags & FW_TYPE_DERIVED), !ageless, q0pl};
 }
 
 // slot of logical particle i of a segment whose particle 0 sits in slot `head` (0 unless the segment is a FIFO ring)
@@ -361,7 +374,7 @@ __device__ __forceinline__ void fw_store_new(const FwGlobals &g, const FwSeg &S,
     float bc[4], em[4];  // gradient.sample_clamped(0.) (core.rs:460-461)
     fw_gradient_sample(T.bc_kind, T.bc_n, keys + T.o_bc_t, keys + T.o_bc_v, 0.0f, bc);
     fw_gradient_sample(T.em_kind, T.em_n, keys + T.o_em_t, keys + T.o_em_v, 0.0f, em);
-    fw_st4(buf + FW_OFF_Q0(C), slot, o.q0);
+    fw_stq(buf + FW_OFF_Q0(C), C, slot, o.q0, (S.cpl & FW_CPL_Q0) != 0u);  // (bit 2: position and age in planes)
     fw_stq(buf + FW_OFF_Q1(C), C, slot, o.q1, S.cpl != 0u);  // (a ring's Q1 / Q2 / Q3: component planes)
     fw_stq(buf + FW_OFF_Q2(C), C, slot, o.q2, (S.cpl & 2u) != 0u);  // (bit 1: a FIFO ring -- the rotation in planes as well)
     fw_stq(buf + FW_OFF_Q3(C), C, slot, o.q3, S.cpl != 0u);
@@ -435,7 +448,8 @@ __device__ __forceinline__ fw_q4 fw_quat_step(fw_v3 v) {
 // unless somebody needs the scale (a type whose planes are stored, an instance record, the boxes): then it is read here.
 enum { FW_W_REGS = 0, FW_W_MEM = 1, FW_W_MEM_LAZY = 2 };
 // CPL: the output segment is a ring -- Q1 / Q3 are component planes (the ring kernels; everybody else writes float4 planes)
-// Q2PL: ... and so is Q2 (a FIFO ring; a range ring keeps the rotation as a float4 plane: FwSeg::cpl bit 1)
+// Q2PL: ... and so is Q2 (a FIFO ring; a range ring keeps the rotation as a float4 plane: FwSeg::cpl bit 1) -- and, where the ring's window
+// says so (FwOutWin::q0pl, workgroup-uniform), Q0
 template <bool INPLACE = false, int WM = -1, int NT = 0, bool CPL = false, bool Q2PL = CPL>
 __device__ __forceinline__ void fw_integrate_store(const FwType &T, const float *s_keys, float dt, float4 q0, float4 q1,
                                                    float4 q2, float4 q3, float age_new, const FwOutWin &W, uint32_t o,
@@ -484,8 +498,13 @@ __device__ __forceinline__ void fw_integrate_store(const FwType &T, const float 
         wz = q3.z + (T.angacc[2] - T.ang_drag * q3.z) * dt;
     }
     const uint32_t b16 = (o - W.first) * 16u;  // < 16 KiB + a tile: the window starts at the tile's first output slot
-    fw_st4w<NT == 2>(W.q0, b16, make_float4(px, py, pz, age_new));
     const uint32_t b4 = (o - W.first) * 4u;
+    if (Q2PL && W.q0pl) {  // (a FIFO ring with x | y | z | age planes; the age only in a launch that keeps it -- workgroup-uniform)
+        fw_stc3w<NT == 2>(W.q0, W.cp, b4, px, py, pz);
+        if (W.wr_age) fw_st1w<NT == 2>(W.q0 + 3 * W.cp, b4, age_new);
+    } else {
+        fw_st4w<NT == 2>(W.q0, b16, make_float4(px, py, pz, age_new));
+    }
     if constexpr (CPL) fw_stc3w<NT == 2>(W.q1, W.cp, b4, vx, vy, vz);
     else fw_st4w<NT == 2>(W.q1, b16, make_float4(vx, vy, vz, q1.w));
     if (INPLACE) {

@@ -19,7 +19,9 @@
 //       4*C bytes apart: initial_scale and lifetime never change, an in-place update moves three dwords per lane, not a dwordx4;
 //       round 11: each component plane of Q3 is stored only in waves where that component's bits changed -- fw_integrate_store;
 //       round 12: so is Q2 of a FIFO ring -- x | y | z | w planes, FwSeg::cpl bit 1, stored component by component -- and a ring whose particles
-//       all spin about one coordinate axis neither loads nor stores the two zero planes of Q2 and of Q3: FW_TYPE_IDX_AXIS)
+//       all spin about one coordinate axis neither loads nor stores the two zero planes of Q2 and of Q3: FW_TYPE_IDX_AXIS;
+//       round 18: so is Q0 of a large FIFO ring fed by Global entries alone -- x | y | z | age planes, FwSeg::cpl bit 2 -- and such a ring
+//       neither loads nor stores the age plane in its streaming launches: FW_TYPE_IDX_AGELESS)
 //   Q5  float4 base_color rgba                       offset  64*C   write only
 //   Q6  float4 emissive_color rgba                   offset  80*C   write only
 //   S4  float  scale                                 offset  96*C   write only
@@ -68,7 +70,8 @@ struct alignas(16) FwSeg {
     // (fw_init_last_emitted) and fw_k_spawn has nothing to materialise.
     uint32_t lplane_emit[2];
     // bit 0: a RING segment (FIFO / range ring) -- its Q1 and Q3 regions are component planes (fw_dev.h: FW_CP); bit 1: a FIFO ring -- Q2
-    // as well (a range ring keeps the rotation as a float4 plane: its kernel moves it whole); 0: float4 planes
+    // as well (a range ring keeps the rotation as a float4 plane: its kernel moves it whole); bit 2: a FIFO ring that may run under the age rule -- Q0 (position, age) too;
+    // 0: float4 planes
     uint32_t cpl;
     uint32_t pad_[3];
 };
@@ -118,6 +121,16 @@ struct alignas(16) FwType {
 // Set per LAUNCH by the host, never stored: the planes hold the true values at all times and no reader looks at the bits.)
 #define FW_TYPE_IDX_AXIS_SHIFT 28
 #define FW_TYPE_IDX_AXIS 0x30000000u
+// (FwFifoSeg::type_idx, round 18: bit 30 -- the range descriptors' FW_TYPE_IDX_NOLIFE, which no FIFO record carries -- = the ring's tiles
+// neither load nor store the age plane in this launch.  In a FIFO ring the age is a property of the spawn cohort: every particle of a
+// cohort is born with age 0 and gets the same fp32 `age + dt` per frame, and the host keeps the identical running sum per cohort
+// (launch_fifo; SegHost::coh), from which it already decides who dies (FwFifoSeg::dead).  Set per LAUNCH by the host, for a ring that keeps
+// Q0 in planes (FwSeg::cpl bit 2: fed by Global entries alone, no Nested entry in its spawner, no collisions), when the launch streams
+// -- four-round tiles, no instance buffer, no collider --, the type is FW_TYPE_DERIVED, reports no destroyed particles and dt is +0
+// or a normal, finite, positive fp32.  The age plane is
+// then STALE (SegHost::ages_stale): fw_k_fifo_ages writes the cohort ages back -- the same bits the kernel would have stored -- before
+// anybody reads the plane or a launch without the bit runs: ensure_ages, fw_engine_mem.cpp.)
+#define FW_TYPE_IDX_AGELESS 0x40000000u
 #define FW_TYPE_IDX_MASK 0x0FFFFFFFu
 // collision_settings of a particle type (core.rs:137-138, 240-248), in a table of its own next to FwType: only the
 // collision kernels read it, the streaming kernels' per-type record (and their scalar-register budget) stays as it was
@@ -189,7 +202,7 @@ struct alignas(16) FwNestOp {
     uint32_t parent_head;    // ring heads of the two segments (FIFO rings; 0 otherwise): particle i sits in slot
     uint32_t child_head;     // (head + i) mod capacity
     uint32_t parent_nospin;  // bit 0: the parent type cannot turn (FW_TYPE_NOSPIN): its rotation is parent_rot, not in the plane,
-                             // (bit 1: the parent segment is a ring -- its Q1 / Q3 are component planes, FwSeg::cpl; bit 2: a FIFO ring -- Q2 too)
+                             // (bit 1: the parent segment is a ring -- its Q1 / Q3 are component planes, FwSeg::cpl; bit 2: a FIFO ring -- Q2 too; bit 3: ... and Q0)
     uint32_t parent_life_plane;  // ... and its lifetimes sit in this 4-byte plane (FW_OFF_L index), not in Q3;
     float parent_life_const;     // 0xFFFFFFFF: the parent is a ring, all its particles have this lifetime
     float parent_rot[4];

@@ -49,6 +49,7 @@
 #include "../../include/firework_hip_debug.h"
 #include "fw_kernels.h"
 #include "fw_math.h"
+#include "fw_ages.h"
 
 namespace fwh {
 
@@ -441,6 +442,11 @@ struct alignas(64) SegHost {
         bool known = true;   // false: a cohort of Nested children whose size the device has not been asked for yet
     };
     std::deque<Cohort> coh;  // oldest first
+    // The age rule (fw_device.h: FW_TYPE_IDX_AGELESS): the ring's latest launches neither loaded nor stored the age plane -- the cohort
+    // ages above stand for it.  ensure_ages writes them back (fw_k_fifo_ages) before anybody reads the plane, before a launch that
+    // does not carry the bit, and before the ring is copied or changes its kind.  ageless_last: the latest launch carried the bit.
+    bool ages_stale = false, ageless_last = false;
+    bool q0pl = false;  // the ring keeps Q0 (position, age) as four component planes (FwSeg::cpl bit 2): set where the ring is built
     // A ring in a spawner WITH Nested entries: in frames that run the Nested pass its new particles are materialised in
     // the ring before the update (fw_k_spawn / fw_k_nest address it through the head) and fw_k_update_fifo gives them
     // their first update (FwFifoSeg::mat).  fifo_dev: the type receives Nested children -- its live count is known to the
@@ -503,7 +509,8 @@ struct alignas(64) SegHost {
     bool ring() const { return fifo || range; }
     // FwSeg::cpl: bit 0 -- a ring, Q1 / Q3 in component planes; bit 1 -- a FIFO ring, the rotation (Q2) as well.  A range ring keeps Q2 as a
     // float4 plane (fifo_to_range transposes it where it stands).
-    uint32_t cpl_bits() const { return ring() ? (fifo ? 3u : 1u) : 0u; }  // one buffer, particle 0 not in slot 0
+    // (round 18: bit 2 -- a FIFO ring that may run under the age rule, SegHost::q0pl: Q0 as well; fifo_to_range transposes that one too)
+    uint32_t cpl_bits() const { return ring() ? (fifo ? (q0pl ? 7u : 3u) : 1u) : 0u; }  // one buffer, particle 0 not in slot 0
     // ... but in this slot, as a launch that is ENQUEUED now has to be told (behind updates that may still be in flight): a FIFO ring's
     // head; a range ring's first YOUNG slot -- the device subtracts the old part, whose size only it knows (FwGlobals::rold)
     uint32_t enqueue_head() const { return fifo ? head : (range ? young_lo : 0u); }
@@ -760,6 +767,14 @@ struct fw_ctx {
     bool use_fifo = true;      // FW_FIFO=0: constant-lifetime types take the general (compacting) path too (A/B, tests)
     bool fifo_nested = true;   // FW_FIFO_NESTED=0: ... those of spawners with Nested entries do (A/B)
     bool use_nospin = true;    // FW_NOSPIN=0: every type keeps its rotation plane (A/B)
+    bool use_ageless = true;   // FW_AGELESS=0: no ring runs under the age rule (A/B in one build)
+    // the cohort table of the latest ensure_ages: written in pinned memory, copied to the device in the stream of the kernel that reads
+    // it; ages_busy: that stream, until it has been waited for (the next table is written into the same pinned words)
+    HipBuf<char> h_ages, d_ages;
+    size_t ages_cap = 0;
+    hipStream_t ages_busy = nullptr;
+    bool ages_pending = false;
+    uint64_t age_launches = 0;  // fw_debug_age_launches
     bool use_axis = true;      // FW_AXIS_SPIN=0: no ring runs under the axis-spin rule (A/B in one build)
     bool use_derived = true;   // FW_DERIVED=0: every type stores its scale / colour planes, attached instance buffer or not (A/B)
     // Round 6: scale, base colour and emissive colour are pure functions of (age, lifetime, initial_scale) (core.rs:601-605,
@@ -1185,6 +1200,10 @@ struct FwFrame {
 // ---- shared functions (definitions: see the list of translation units above)
 fw_status sync(fw_ctx *ctx);
 fw_status join_side(fw_ctx *ctx);
+// a FIFO ring whose age plane is stale (SegHost::ages_stale) gets it written back; stream: where the kernel goes -- null: the main
+// stream, which first waits for the ring launches on the side stream (join_side)
+fw_status ensure_ages(fw_ctx *ctx, uint32_t si, hipStream_t stream = nullptr);
+bool ageless_dt_ok(float dt);
 fw_status ensure_max_seg(fw_ctx *ctx, uint32_t need);
 uint32_t seg_live_tiles(const SegHost &s);
 uint32_t seg_tiles(const SegHost &s, uint32_t vt_rounds = 1);

@@ -63,18 +63,24 @@ fw_ctx::~fw_ctx() {
 // particle state: nothing (it enqueues behind what is in flight), sync(ctx), join_side(ctx) or read_counts(ctx, r.c).  begin_call
 // returns false when the call ends there, with r.st; otherwise r.st is FW_OK or, after Then::counts alone, FW_ECAPACITY (a type
 // overflowed: the call goes on and reports it at its end, unless a later error takes precedence).
+// Ages: whether the call reads or copies particles.  Ages::write -- a ring under the age rule gets its ages written back first
+// (ensure_ages; nothing where none is stale).  Ages::leave -- the call looks at counts, records or last_emitted planes only: a stale
+// age plane stays stale, and a host that polls every frame keeps the rule.
 enum class Then { nothing, sync, join, counts };
+enum class Ages { leave, write };
 struct SpawnerCall {
     SpawnerHost *sp = nullptr;
     std::vector<uint32_t> c;  // per segment (Then::counts)
     fw_status st = FW_OK;
 };
 template <typename ArgsOk>
-static bool begin_call(fw_ctx *ctx, fw_spawner h, SpawnerCall &r, Then then, ArgsOk args_ok) {
+static bool begin_call(fw_ctx *ctx, fw_spawner h, SpawnerCall &r, Then then, Ages ages, ArgsOk args_ok) {
     r.sp = get_spawner(ctx, h);
     if (!r.sp || !args_ok(*r.sp)) return r.st = FW_EINVAL, false;
     if (poll_device_error(ctx), r.sp->poisoned) return r.st = poisoned_status(ctx), false;
     hipSetDevice(ctx->device);
+    for (size_t t = 0; ages == Ages::write && t < r.sp->seg.size(); t++)
+        if ((r.st = ensure_ages(ctx, r.sp->seg[t]))) return false;
     r.st = then == Then::sync ? sync(ctx) : then == Then::join ? join_side(ctx) : then == Then::counts ? read_counts(ctx, r.c) : FW_OK;
     return !r.st || (then == Then::counts && r.st == FW_ECAPACITY);
 }
@@ -198,6 +204,7 @@ fw_status fw_ctx_create(int device, uint32_t seed, void *stream, fw_ctx **out) {
     if (const char *m = getenv("FW_RANGE_YOUNG_BIG")) ctx->range_young_big = (uint32_t)strtoul(m, nullptr, 10);
     if (const char *m = getenv("FW_NOSPIN")) ctx->use_nospin = atoi(m) != 0;
     if (const char *m = getenv("FW_AXIS_SPIN")) ctx->use_axis = atoi(m) != 0;
+    if (const char *m = getenv("FW_AGELESS")) ctx->use_ageless = atoi(m) != 0;
     // 0: scale / colour planes always stored; 1: not stored for types with an attached instance buffer; 2 (default): for no type
     if (const char *m = getenv("FW_DERIVED")) ctx->use_derived = atoi(m) != 0, ctx->derive_all = atoi(m) >= 2;
     if (const char *m = getenv("FW_NEST_FUSE")) ctx->nest_fuse = atoi(m) != 0;
@@ -455,21 +462,21 @@ fw_status fw_ctx_queue(fw_ctx *ctx, uint32_t n, const fw_spawner *handles, const
 // ---- outputs -----------------------------------------------------------------------------
 fw_status fw_spawner_counts(fw_ctx *ctx, fw_spawner h, uint32_t *per_type, uint32_t n_types) {
     SpawnerCall r;
-    if (!begin_call(ctx, h, r, Then::counts, [&](const SpawnerHost &) { return per_type != nullptr; })) return r.st;
+    if (!begin_call(ctx, h, r, Then::counts, Ages::leave, [&](const SpawnerHost &) { return per_type != nullptr; })) return r.st;
     for (uint32_t t = 0; t < n_types && t < r.sp->seg.size(); t++) per_type[t] = r.c[r.sp->seg[t]];
     return r.st;
 }
 
 fw_status fw_spawner_active(fw_ctx *ctx, fw_spawner h, int32_t *out) {
     SpawnerCall r;
-    if (!begin_call(ctx, h, r, Then::counts, [&](const SpawnerHost &) { return out != nullptr; })) return r.st;
+    if (!begin_call(ctx, h, r, Then::counts, Ages::leave, [&](const SpawnerHost &) { return out != nullptr; })) return r.st;
     *out = spawner_active(ctx, *r.sp, r.c) ? 1 : 0;
     return r.st;
 }
 
 fw_status fw_spawner_poll_finished(fw_ctx *ctx, fw_spawner h, int32_t *out) {
     SpawnerCall r;
-    if (!begin_call(ctx, h, r, Then::counts, [&](const SpawnerHost &) { return out != nullptr; })) return r.st;
+    if (!begin_call(ctx, h, r, Then::counts, Ages::leave, [&](const SpawnerHost &) { return out != nullptr; })) return r.st;
     bool all_empty = true;
     for (uint32_t si : r.sp->seg) all_empty &= r.c[si] == 0;
     *out = 0;
@@ -508,7 +515,7 @@ static fw_status read_records(fw_ctx *ctx, const FwSegView &v, uint32_t n, int32
 fw_status fw_spawner_read_particles(fw_ctx *ctx, fw_spawner h, uint32_t type, fw_particle *out, uint64_t cap,
                                     uint64_t *n_out) {
     SpawnerCall r;
-    if (!begin_call(ctx, h, r, Then::counts, [&](const SpawnerHost &sp) { return type < sp.seg.size(); })) return r.st;
+    if (!begin_call(ctx, h, r, Then::counts, Ages::write, [&](const SpawnerHost &sp) { return type < sp.seg.size(); })) return r.st;
     const uint32_t n = r.c[r.sp->seg[type]];
     if (n_out) *n_out = n;
     // (the counts are exact and the stream has been waited for: the host places particle 0 itself)
@@ -519,7 +526,7 @@ fw_status fw_spawner_read_particles(fw_ctx *ctx, fw_spawner h, uint32_t type, fw
 fw_status fw_spawner_read_last_emitted(fw_ctx *ctx, fw_spawner h, uint32_t type, uint32_t emission_index, float *out,
                                        uint64_t cap, uint64_t *n_out) {
     SpawnerCall r;
-    if (!begin_call(ctx, h, r, Then::counts, [&](const SpawnerHost &sp) { return type < sp.seg.size() && emission_index < sp.em.size(); })) return r.st;
+    if (!begin_call(ctx, h, r, Then::counts, Ages::leave, [&](const SpawnerHost &sp) { return type < sp.seg.size() && emission_index < sp.em.size(); })) return r.st;
     const SegHost &S = ctx->segs[r.sp->seg[type]];
     const uint32_t n = r.c[r.sp->seg[type]];
     if (n_out) *n_out = n;
@@ -540,7 +547,7 @@ fw_status fw_spawner_read_last_emitted(fw_ctx *ctx, fw_spawner h, uint32_t type,
 
 fw_status fw_spawner_write_particles(fw_ctx *ctx, fw_spawner h, uint32_t type, const fw_particle *in, uint64_t n) {
     SpawnerCall r;
-    if (!begin_call(ctx, h, r, Then::sync, [&](const SpawnerHost &sp) { return type < sp.seg.size() && !(n && !in) && n <= 0xF0000000ull; }))
+    if (!begin_call(ctx, h, r, Then::sync, Ages::write, [&](const SpawnerHost &sp) { return type < sp.seg.size() && !(n && !in) && n <= 0xF0000000ull; }))
         return r.st;
     fw_status st;
     const uint32_t si = r.sp->seg[type];
@@ -580,7 +587,7 @@ fw_status fw_spawner_write_particles(fw_ctx *ctx, fw_spawner h, uint32_t type, c
 fw_status fw_spawner_write_last_emitted(fw_ctx *ctx, fw_spawner h, uint32_t type, uint32_t emission_index,
                                         const float *in, uint64_t n) {
     SpawnerCall r;
-    if (!begin_call(ctx, h, r, Then::sync, [&](const SpawnerHost &sp) { return type < sp.seg.size() && emission_index < sp.em.size() && !(n && !in); }))
+    if (!begin_call(ctx, h, r, Then::sync, Ages::leave, [&](const SpawnerHost &sp) { return type < sp.seg.size() && emission_index < sp.em.size() && !(n && !in); }))
         return r.st;
     if (fw_status st = fifo_to_general(ctx, r.sp->seg[type])) return st;  // (caller-written state: the general path takes over)
     const SegHost &S = ctx->segs[r.sp->seg[type]];
@@ -596,7 +603,7 @@ fw_status fw_spawner_write_last_emitted(fw_ctx *ctx, fw_spawner h, uint32_t type
 fw_status fw_spawner_read_destroyed(fw_ctx *ctx, fw_spawner h, uint32_t type, fw_particle *out, uint64_t cap,
                                     uint64_t *n_out) {
     SpawnerCall r;
-    if (!begin_call(ctx, h, r, Then::sync, [&](const SpawnerHost &sp) { return type < sp.seg.size(); })) return r.st;
+    if (!begin_call(ctx, h, r, Then::sync, Ages::leave, [&](const SpawnerHost &sp) { return type < sp.seg.size(); })) return r.st;
     const SegHost &S = ctx->segs[r.sp->seg[type]];
     uint32_t n = 0;
     if (S.destroyed) FW_HIP(ctx, hipMemcpy(&n, ctx->g.ndestroyed + r.sp->seg[type], 4, hipMemcpyDeviceToHost));
@@ -612,7 +619,7 @@ fw_status fw_spawner_read_destroyed(fw_ctx *ctx, fw_spawner h, uint32_t type, fw
 fw_status fw_spawner_pack_instances_device(fw_ctx *ctx, fw_spawner h, uint32_t type, void *d_out, uint64_t cap,
                                            uint64_t *n_upper_bound) {
     SpawnerCall r;
-    if (!begin_call(ctx, h, r, Then::nothing, [&](const SpawnerHost &sp) { return type < sp.seg.size() && d_out; })) return r.st;
+    if (!begin_call(ctx, h, r, Then::nothing, Ages::write, [&](const SpawnerHost &sp) { return type < sp.seg.size() && d_out; })) return r.st;
     const uint32_t si = r.sp->seg[type];
     const SegHost &S = ctx->segs[si];
     const uint32_t ub = (uint32_t)std::min<uint64_t>(S.nested_fed ? S.capacity : std::min(S.ub, S.capacity), cap);
@@ -628,7 +635,7 @@ fw_status fw_spawner_pack_instances_device(fw_ctx *ctx, fw_spawner h, uint32_t t
 
 static fw_status attach_instances(fw_ctx *ctx, fw_spawner h, uint32_t type, void *d_out, uint64_t cap, bool window) {
     SpawnerCall r;  // (Then::sync: kernels in flight hold the old record)
-    if (!begin_call(ctx, h, r, Then::sync, [&](const SpawnerHost &sp) { return type < sp.seg.size() && !(d_out && !cap); })) return r.st;
+    if (!begin_call(ctx, h, r, Then::sync, Ages::write, [&](const SpawnerHost &sp) { return type < sp.seg.size() && !(d_out && !cap); })) return r.st;
     SpawnerHost *const sp = r.sp;
     // ... and whatever the caller enqueued on ITS streams to initialise the buffer has happened before a frame writes to it
     // (the context's streams are non-blocking ones: nothing else orders them against, say, a fill on the null stream)
@@ -665,7 +672,7 @@ fw_status fw_spawner_attach_instances_window(fw_ctx *ctx, fw_spawner h, uint32_t
 
 fw_status fw_spawner_instance_window(fw_ctx *ctx, fw_spawner h, uint32_t type, uint64_t *first, uint64_t *count) {
     SpawnerCall r;
-    if (!begin_call(ctx, h, r, Then::counts, [&](const SpawnerHost &sp) { return type < sp.seg.size() && first && count; })) return r.st;
+    if (!begin_call(ctx, h, r, Then::counts, Ages::leave, [&](const SpawnerHost &sp) { return type < sp.seg.size() && first && count; })) return r.st;
     const uint32_t si = r.sp->seg[type];
     const SegHost &S = ctx->segs[si];
     uint32_t dead = 0;
@@ -678,7 +685,7 @@ fw_status fw_spawner_instance_window(fw_ctx *ctx, fw_spawner h, uint32_t type, u
 fw_status fw_spawner_pack_instances(fw_ctx *ctx, fw_spawner h, uint32_t type, fw_particle_instance *out, uint64_t cap,
                                     uint64_t *n_out) {
     SpawnerCall r;
-    if (!begin_call(ctx, h, r, Then::counts, [&](const SpawnerHost &sp) { return type < sp.seg.size(); })) return r.st;
+    if (!begin_call(ctx, h, r, Then::counts, Ages::write, [&](const SpawnerHost &sp) { return type < sp.seg.size(); })) return r.st;
     const uint32_t n = r.c[r.sp->seg[type]];
     if (n_out) *n_out = n;
     const uint64_t m = std::min<uint64_t>(n, cap);
@@ -696,7 +703,7 @@ fw_status fw_spawner_pack_instances(fw_ctx *ctx, fw_spawner h, uint32_t type, fw
 
 fw_status fw_spawner_aabb(fw_ctx *ctx, fw_spawner h, float out_min[3], float out_max[3], int32_t *any) {
     SpawnerCall call;  // (Then::join: the query kernels run on the main stream and may read rings)
-    if (!begin_call(ctx, h, call, Then::join, [&](const SpawnerHost &) { return out_min && out_max; })) return call.st;
+    if (!begin_call(ctx, h, call, Then::join, Ages::write, [&](const SpawnerHost &) { return out_min && out_max; })) return call.st;
     const SpawnerHost *const sp = call.sp;
     if (!ctx->h_aabb)
         if (fw_status st = alloc_buf(ctx, ctx->h_aabb, 8, Mem::pinned)) return st;
@@ -916,6 +923,8 @@ fw_status fw_debug_update_path(fw_ctx *ctx, fw_spawner h, uint32_t type, int32_t
         // and the rotation's w move: 8 + 4 bytes in, 8 out, 4 more where the drag changes the angular velocity.  The figure of a
         // frame whose dt the rule covers; the range kernel loads every plane.)
         if (S.fifo && S.axis != 0u) moved = 28u + 12u + 28u + (spins ? 8u : 0u) + (q3 ? 4u : 0u) + (T.scale.kind != 0 ? 4u : 0u) + colours;
+        // (round 18, a FIFO ring whose latest launch ran under the age rule -- SegHost::ageless_last: the age plane moved neither way)
+        if (S.fifo && S.ageless_last) moved -= 8u;
         algo = moved;
         // (a range ring: the part of the list that may lose particles, a fifth of configs[2], is compacted in place and reads and
         // rewrites every plane it keeps, the 4-byte lifetime included: the figure is the young part's)
@@ -957,6 +966,12 @@ fw_status fw_debug_tile_scratch(fw_ctx *ctx, uint64_t *table_tiles, uint64_t *sc
 fw_status fw_debug_recovered_rings(fw_ctx *ctx, uint64_t *n) {
     if (!ctx || !n) return FW_EINVAL;
     *n = ctx->recovered_rings;
+    return FW_OK;
+}
+// launches of fw_k_fifo_ages so far (ensure_ages: a ring under the age rule had its ages written back)
+fw_status fw_debug_age_launches(fw_ctx *ctx, uint64_t *n) {
+    if (!ctx || !n) return FW_EINVAL;
+    *n = ctx->age_launches;
     return FW_OK;
 }
 fw_status fw_debug_tf_frames(fw_ctx *ctx, uint64_t *n) {

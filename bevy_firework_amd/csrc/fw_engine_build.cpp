@@ -389,6 +389,12 @@ fw_status build_spawner(fw_ctx *ctx, int h, const fw_spawner_desc *d, const std:
                 }
                 S.fifo_life = 0.0f * (p.lifetime.max - p.lifetime.min) + p.lifetime.min;  // u * (max - min) + min, any u
                 S.fifo_wm = (T.base.kind != 0 ? 1 : 0) | (T.emis.kind != 0 ? 2 : 0) | (T.scale.kind != 0 ? 4 : 0);
+                // Position + age in four planes (SegHost::q0pl) -- the layout the age rule needs -- only for a ring that can ever run
+                // under it: fed by Global entries alone, no Nested entry on it, no collisions, and large enough by itself for a streaming
+                // launch (fw_ctx::fifo_small_tiles).  Everybody else keeps the float4: four dword accesses where one dwordx4 did cost
+                // the one-round and the Nested launches 1.5-1.8 % (profiles/r18/ageless_ab.txt).  Decided once, here.
+                S.q0pl = ctx->use_ageless && ctx->fifo_small_tiles != 0u && !any_nested && !S.nested_fed && S.n_lplanes == 0 && !S.collides &&
+                         (uint64_t)caps[t] >= (uint64_t)ctx->fifo_small_tiles * FW_TILE;
             }
             // Range ring (SegHost::range): any finite lifetime range -- a single value included, for the types the eight
             // FIFO records of a launch have no room for -- in a spawner without Nested entries; the young part of the

@@ -279,7 +279,7 @@ fw_status spawn_passes(fw_ctx *ctx, FwFrame &fr) {
                 op.parent_buf = PS.buf[p], op.parent_cap = PS.capacity;
                 op.parent_head = PS.enqueue_head(), op.child_head = CS.enqueue_head();
                 op.parent_range = PS.range ? 1u : 0u, op.child_range = CS.range ? 1u : 0u;
-                op.parent_nospin = (PS.nospin ? 1u : 0u) | (PS.cpl_bits() << 1);  // (bit 1: Q1 / Q3 in component planes, bit 2: Q2 too)
+                op.parent_nospin = (PS.nospin ? 1u : 0u) | (PS.cpl_bits() << 1);  // (bit 1: Q1 / Q3 in component planes, bit 2: Q2 too, bit 3: Q0 too)
                 memcpy(op.parent_rot, PS.const_rot, sizeof op.parent_rot);
                 op.parent_life_plane = PS.life_plane(), op.parent_life_const = PS.fifo_life;  // (read under bit 0 of parent_nospin only)
                 // (START tickets, fw_kernels.h: every workgroup of the op takes one)
@@ -458,106 +458,125 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
         fr.fifo_launched = true;
         return e;
     };
-    for (uint32_t si = 0; si < n_seg; si++) {
-        SegHost &S = ctx->segs[si];
-        if (!S.in_use || !S.fifo) continue;
-        uint32_t k_ops = 0;
-        for (const FwOp &op : ctx->fifo_ops) k_ops += op.seg == si ? 1u : 0u;
-        if (k_ops > FW_INLINE_OPS)  // (build_spawner never makes such a type a ring)
-            return poison_segment(ctx, si, "a FIFO ring with more spawn ops than its launch can carry");
-        if (fa.n_segs == FW_FIFO_PER_LAUNCH || f_ops + k_ops > FW_INLINE_OPS) FW_HIP(ctx, flush());
-        const int32_t wm = S.derived ? 0 : S.fifo_wm;  // (FW_TYPE_DERIVED: none of the optional planes is stored)
-        if (!fa.n_segs) fa.write_mask = wm;
-        else if (fa.write_mask != wm) fa.write_mask = -1;
-        // frames that materialise (Nested pass): the segment's Global particles of this frame already sit in the ring
-        const bool mat_frame = S.fifo_mat && fr.nested_frame && !S.virt_parent;
-        const bool mat = S.fifo_dev || mat_frame;
-        const uint32_t n_spawn = mat_frame ? 0u : S.frame_spawn;  // spawned by fw_k_update_fifo itself
-        // live particles before fw_k_update_fifo's own spawns (a type that receives children: only the device knows)
-        const uint32_t n_in = S.fifo_dev ? 0xFFFFFFFFu : S.ub - n_spawn;
-        // the cohorts age by this dt exactly as their particles do (fp32 additions, fw_survives); the oldest die first
-        if (S.fifo_dev) {
-            S.coh.push_back(SegHost::Cohort{0u, 0.0f, ctx->frame, false});  // size: whatever the device appends
-        } else if (S.frame_spawn) {
-            if (!S.coh.empty() && S.coh.back().age == 0.0f && !std::signbit(S.coh.back().age))
-                S.coh.back().n += S.frame_spawn;
-            else
-                S.coh.push_back(SegHost::Cohort{S.frame_spawn, 0.0f, ctx->frame, true});
+    // (two passes: the rings that keep Q0 in planes -- SegHost::q0pl, the ones that may run under the age rule -- get a launch of their own,
+    // behind everybody else's: the colliding and the Nested instantiations of the kernel never meet that layout)
+    for (int pass = 0; pass < 2; pass++) {
+        for (uint32_t si = 0; si < n_seg; si++) {
+            SegHost &S = ctx->segs[si];
+            if (!S.in_use || !S.fifo || S.q0pl != (pass == 1)) continue;
+            uint32_t k_ops = 0;
+            for (const FwOp &op : ctx->fifo_ops) k_ops += op.seg == si ? 1u : 0u;
+            if (k_ops > FW_INLINE_OPS)  // (build_spawner never makes such a type a ring)
+                return poison_segment(ctx, si, "a FIFO ring with more spawn ops than its launch can carry");
+            if (fa.n_segs == FW_FIFO_PER_LAUNCH || f_ops + k_ops > FW_INLINE_OPS) FW_HIP(ctx, flush());
+            const int32_t wm = S.derived ? 0 : S.fifo_wm;  // (FW_TYPE_DERIVED: none of the optional planes is stored)
+            if (!fa.n_segs) fa.write_mask = wm;
+            else if (fa.write_mask != wm) fa.write_mask = -1;
+            // frames that materialise (Nested pass): the segment's Global particles of this frame already sit in the ring
+            const bool mat_frame = S.fifo_mat && fr.nested_frame && !S.virt_parent;
+            const bool mat = S.fifo_dev || mat_frame;
+            const uint32_t n_spawn = mat_frame ? 0u : S.frame_spawn;  // spawned by fw_k_update_fifo itself
+            // live particles before fw_k_update_fifo's own spawns (a type that receives children: only the device knows)
+            const uint32_t n_in = S.fifo_dev ? 0xFFFFFFFFu : S.ub - n_spawn;
+            // the age rule (fw_device.h: FW_TYPE_IDX_AGELESS), per launch: a streaming launch -- four-round tiles, no collider, no instance
+            // records of this ring --, a ring fed by Global entries alone that no Nested entry touches, a FW_TYPE_DERIVED type that reports
+            // no destroyed particles, a dt both sides add alike.  Any other launch finds the true ages in the plane: written back first,
+            // from the cohorts as they stand BEFORE this frame's spawns and dt (what the ring holds).
+            bool nest_touches = false;
+            for (uint32_t k = 0; fr.fuse && k < fr.n_fuse; k++) nest_touches |= fr.fuse_plan[k].parent_seg == si || fr.fuse_plan[k].child_seg == si;
+            // ("streaming" is judged by the context's own threshold, fw_ctx::fifo_small_tiles: with FW_FIFO_SMALL=0 -- no threshold, four-round
+            // tiles at any size -- nothing says the launch is bound by bandwidth, and the rule stays off)
+            const bool ageless = ctx->use_ageless && S.q0pl && ctx->fifo_small_tiles != 0u && !fifo_small && !fifo_coll_real && S.inst == nullptr && !S.collides && !S.fifo_dev && !S.fifo_mat &&
+                                 !S.nested_fed && S.n_lplanes == 0 && !nest_touches && S.derived && S.destroyed == nullptr && ageless_dt_ok(dt);
+            if (!ageless && (st = ensure_ages(ctx, si, fstream))) return st;
+            if (ageless) S.ages_stale = true;
+            S.ageless_last = ageless;
+            // the cohorts age by this dt exactly as their particles do (fp32 additions, fw_survives); the oldest die first
+            if (S.fifo_dev) {
+                S.coh.push_back(SegHost::Cohort{0u, 0.0f, ctx->frame, false});  // size: whatever the device appends
+            } else if (S.frame_spawn) {
+                if (!S.coh.empty() && S.coh.back().age == 0.0f && !std::signbit(S.coh.back().age))
+                    S.coh.back().n += S.frame_spawn;
+                else
+                    S.coh.push_back(SegHost::Cohort{S.frame_spawn, 0.0f, ctx->frame, true});
+            }
+            for (auto &c : S.coh) c.age = c.age + dt;
+            uint32_t dead = 0;
+            while (!S.coh.empty() && S.coh.front().age >= S.fifo_life) {
+                SegHost::Cohort &c = S.coh.front();
+                // (children added `lifetime` ago)
+                if (!c.known && c.frame != ctx->frame && (st = take_report(ctx, si, c, "cohort report missing"))) return st;
+                dead += c.n;
+                S.coh.pop_front();
+            }
+            FwFifoSeg &F = fa.s[fa.n_segs++];
+            F.buf = S.buf[0], F.destroyed = S.destroyed, F.inst = S.inst;
+            F.inst_cap = S.inst_cap, F.capacity = S.capacity, F.seg = si;
+            // (the axis-spin rule travels per launch: a frame whose dt voids its proof runs without it, and so does every frame after it)
+            if (S.axis != 0u && !axis_dt_ok(S, dt)) S.axis = 0u;
+            F.type_idx = S.type_idx | (S.nospin ? FW_TYPE_IDX_NOSPIN : 0u) | (S.axis << FW_TYPE_IDX_AXIS_SHIFT) | (ageless ? FW_TYPE_IDX_AGELESS : 0u), F.life = S.fifo_life;
+            F.keys_off = S.keys_off, F.keys_len = S.keys_len;
+            F.head = S.head, F.n_in = n_in, F.n_spawn = n_spawn, F.dead = dead;
+            F.mat = mat ? 1u : 0u;
+            fa.q0pl = S.q0pl ? 1u : 0u;  // (the same for every ring of a launch: the two passes)
+            F.n_lplanes = S.n_lplanes;
+            F.report = S.fifo_dev ? S.h_report + (ctx->frame % kReportRing) : nullptr;
+            F.op0 = f_ops;
+            if (!mat_frame)
+                for (const FwOp &op : ctx->fifo_ops)
+                    if (op.seg == si) fio.ops[f_ops++] = op;
+            F.op1 = f_ops;
+            // workgroups: the new particles first, FW_BLOCK each, in two groups of consecutive slots (up to the end of the
+            // buffer / from slot 0); then the ring tiles from the first slot the update touches (the first destroyed particle
+            // when their records are wanted, the first survivor otherwise) to the last old particle (a type whose count
+            // only the device knows: the whole ring, empty tiles leave at once); at least one in all (it publishes the counts)
+            const uint32_t n_old = S.fifo_dev ? S.capacity : n_in;
+            // (... or a ring whose particles a Nested entry of this launch emits from: the ones about to die still emit, and the
+            // tiles' ranks count from the ring's head)
+            int nest_parent = -1, nest_child = -1;
+            for (uint32_t k = 0; fr.fuse && k < fr.n_fuse; k++) {
+                if (fr.fuse_plan[k].parent_seg == si) nest_parent = (int)k;
+                if (fr.fuse_plan[k].child_seg == si) nest_child = (int)k;
+            }
+            const uint32_t lo = std::min((S.destroyed || nest_parent >= 0) ? 0u : dead, n_old), cnt = n_old - lo;
+            const uint32_t ftile = fifo_coll ? FW_FIFO_COLL_TILE : FW_TILE;
+            const uint32_t ps = (uint32_t)(((uint64_t)S.head + lo) % S.capacity), ring_tiles = S.capacity / ftile;
+            const uint32_t ns0 = (uint32_t)(((uint64_t)S.head + (S.fifo_dev ? 0u : n_in)) % S.capacity);  // slot of the first new particle
+            F.spawn_a = std::min(n_spawn, S.capacity - ns0);
+            F.n_vt_a = (F.spawn_a + FW_BLOCK - 1) / FW_BLOCK, F.n_vt_b = (n_spawn - F.spawn_a + FW_BLOCK - 1) / FW_BLOCK;
+            F.tile0 = ps / ftile;
+            const uint32_t live_tiles = cnt ? std::min<uint32_t>(ring_tiles, (ps % ftile + cnt + ftile - 1) / ftile) : 0u;
+            F.n_tiles = std::max(1u, F.n_vt_a + F.n_vt_b + live_tiles);
+            F.tile_first = f_tiles;
+            f_tiles += F.n_tiles;
+            F.nest = 0u;
+            if (nest_parent >= 0) {
+                const FwNestOp &op = fr.fuse_plan[nest_parent];
+                FwFifoNest &N = fa.nest[nest_parent];
+                F.nest = (uint32_t)nest_parent + 1u;
+                N.parent = fa.n_segs - 1u;
+                N.emit = op.emit, N.emit_slot = op.emit_slot, N.parent_lplane = op.parent_lplane;
+                N.n_count = op.n_count, N.n_start = op.n_start, N.n_end = op.n_end, N.speed = op.speed, N.scale = op.scale;
+                N.status_first = nest_status_next, N.n_ptiles = F.n_tiles - (F.n_vt_a + F.n_vt_b);
+                nest_status_next += N.n_ptiles;
+                N.ticket_base = ctx->nest_ticket_base[op.emit_slot], ctx->nest_ticket_base[op.emit_slot] += N.n_ptiles;
+                N.tag = nest_tag, N.spin_limit = ctx->spin_limit;
+                fa.n_nest = fr.n_fuse;
+            }
+            if (nest_child >= 0) {
+                F.nest = ((uint32_t)nest_child + 1u) | FW_FIFO_NEST_CHILD;
+                fa.nest[nest_child].child = fa.n_segs - 1u;
+            }
+            f_bytes += (uint64_t)live_tiles * ftile * (S.nospin ? 104u : 164u);
+            fa.any_inst |= S.inst != nullptr ? 1u : 0u;
+            // (a launch of q0pl rings -- none of them collides -- in a context with a colliding ring: the plain one-round form on the same tile grid)
+            fa.any_coll |= (fifo_coll_real && !S.q0pl) ? 1u : 0u;
+            fa.small_tiles = (fifo_coll && !(fifo_coll_real && !S.q0pl)) ? 1u : 0u;
+            S.head = (uint32_t)(((uint64_t)S.head + dead) % S.capacity);
+            if (!S.fifo_dev) S.ub = n_in + n_spawn - std::min(dead, n_in + n_spawn);  // exact
         }
-        for (auto &c : S.coh) c.age = c.age + dt;
-        uint32_t dead = 0;
-        while (!S.coh.empty() && S.coh.front().age >= S.fifo_life) {
-            SegHost::Cohort &c = S.coh.front();
-            // (children added `lifetime` ago)
-            if (!c.known && c.frame != ctx->frame && (st = take_report(ctx, si, c, "cohort report missing"))) return st;
-            dead += c.n;
-            S.coh.pop_front();
-        }
-        FwFifoSeg &F = fa.s[fa.n_segs++];
-        F.buf = S.buf[0], F.destroyed = S.destroyed, F.inst = S.inst;
-        F.inst_cap = S.inst_cap, F.capacity = S.capacity, F.seg = si;
-        // (the axis-spin rule travels per launch: a frame whose dt voids its proof runs without it, and so does every frame after it)
-        if (S.axis != 0u && !axis_dt_ok(S, dt)) S.axis = 0u;
-        F.type_idx = S.type_idx | (S.nospin ? FW_TYPE_IDX_NOSPIN : 0u) | (S.axis << FW_TYPE_IDX_AXIS_SHIFT), F.life = S.fifo_life;
-        F.keys_off = S.keys_off, F.keys_len = S.keys_len;
-        F.head = S.head, F.n_in = n_in, F.n_spawn = n_spawn, F.dead = dead;
-        F.mat = mat ? 1u : 0u;
-        F.n_lplanes = S.n_lplanes;
-        F.report = S.fifo_dev ? S.h_report + (ctx->frame % kReportRing) : nullptr;
-        F.op0 = f_ops;
-        if (!mat_frame)
-            for (const FwOp &op : ctx->fifo_ops)
-                if (op.seg == si) fio.ops[f_ops++] = op;
-        F.op1 = f_ops;
-        // workgroups: the new particles first, FW_BLOCK each, in two groups of consecutive slots (up to the end of the
-        // buffer / from slot 0); then the ring tiles from the first slot the update touches (the first destroyed particle
-        // when their records are wanted, the first survivor otherwise) to the last old particle (a type whose count
-        // only the device knows: the whole ring, empty tiles leave at once); at least one in all (it publishes the counts)
-        const uint32_t n_old = S.fifo_dev ? S.capacity : n_in;
-        // (... or a ring whose particles a Nested entry of this launch emits from: the ones about to die still emit, and the
-        // tiles' ranks count from the ring's head)
-        int nest_parent = -1, nest_child = -1;
-        for (uint32_t k = 0; fr.fuse && k < fr.n_fuse; k++) {
-            if (fr.fuse_plan[k].parent_seg == si) nest_parent = (int)k;
-            if (fr.fuse_plan[k].child_seg == si) nest_child = (int)k;
-        }
-        const uint32_t lo = std::min((S.destroyed || nest_parent >= 0) ? 0u : dead, n_old), cnt = n_old - lo;
-        const uint32_t ftile = fifo_coll ? FW_FIFO_COLL_TILE : FW_TILE;
-        const uint32_t ps = (uint32_t)(((uint64_t)S.head + lo) % S.capacity), ring_tiles = S.capacity / ftile;
-        const uint32_t ns0 = (uint32_t)(((uint64_t)S.head + (S.fifo_dev ? 0u : n_in)) % S.capacity);  // slot of the first new particle
-        F.spawn_a = std::min(n_spawn, S.capacity - ns0);
-        F.n_vt_a = (F.spawn_a + FW_BLOCK - 1) / FW_BLOCK, F.n_vt_b = (n_spawn - F.spawn_a + FW_BLOCK - 1) / FW_BLOCK;
-        F.tile0 = ps / ftile;
-        const uint32_t live_tiles = cnt ? std::min<uint32_t>(ring_tiles, (ps % ftile + cnt + ftile - 1) / ftile) : 0u;
-        F.n_tiles = std::max(1u, F.n_vt_a + F.n_vt_b + live_tiles);
-        F.tile_first = f_tiles;
-        f_tiles += F.n_tiles;
-        F.nest = 0u;
-        if (nest_parent >= 0) {
-            const FwNestOp &op = fr.fuse_plan[nest_parent];
-            FwFifoNest &N = fa.nest[nest_parent];
-            F.nest = (uint32_t)nest_parent + 1u;
-            N.parent = fa.n_segs - 1u;
-            N.emit = op.emit, N.emit_slot = op.emit_slot, N.parent_lplane = op.parent_lplane;
-            N.n_count = op.n_count, N.n_start = op.n_start, N.n_end = op.n_end, N.speed = op.speed, N.scale = op.scale;
-            N.status_first = nest_status_next, N.n_ptiles = F.n_tiles - (F.n_vt_a + F.n_vt_b);
-            nest_status_next += N.n_ptiles;
-            N.ticket_base = ctx->nest_ticket_base[op.emit_slot], ctx->nest_ticket_base[op.emit_slot] += N.n_ptiles;
-            N.tag = nest_tag, N.spin_limit = ctx->spin_limit;
-            fa.n_nest = fr.n_fuse;
-        }
-        if (nest_child >= 0) {
-            F.nest = ((uint32_t)nest_child + 1u) | FW_FIFO_NEST_CHILD;
-            fa.nest[nest_child].child = fa.n_segs - 1u;
-        }
-        f_bytes += (uint64_t)live_tiles * ftile * (S.nospin ? 104u : 164u);
-        fa.any_inst |= S.inst != nullptr ? 1u : 0u;
-        fa.any_coll |= fifo_coll_real ? 1u : 0u;
-        fa.small_tiles = (fifo_coll && !fifo_coll_real) ? 1u : 0u;
-        S.head = (uint32_t)(((uint64_t)S.head + dead) % S.capacity);
-        if (!S.fifo_dev) S.ub = n_in + n_spawn - std::min(dead, n_in + n_spawn);  // exact
+        FW_HIP(ctx, flush());
     }
-    FW_HIP(ctx, flush());
     return FW_OK;
 }
 

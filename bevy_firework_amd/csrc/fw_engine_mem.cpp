@@ -26,6 +26,53 @@ fw_status join_side(fw_ctx *ctx) {
     return FW_OK;
 }
 
+// the age rule's per-frame condition on dt: the host's cohort sums and the device's `age + dt` are the same fp32 additions only where
+// neither side may treat dt differently -- +0, or a positive normal finite value (a denormal may be flushed on one side only)
+bool ageless_dt_ok(float dt) { return !std::signbit(dt) && (dt == 0.0f || std::isnormal(dt)); }
+
+fw_status ensure_ages(fw_ctx *ctx, uint32_t si, hipStream_t stream) {
+    SegHost &S = ctx->segs[si];
+    if (!S.ages_stale) return FW_OK;
+    fw_status st;
+    if (!stream) {
+        if ((st = join_side(ctx))) return st;
+        stream = ctx->stream;
+    }
+    // one entry per cohort that holds particles: the ring's live particles are its cohorts laid end to end, oldest first (fw_ages.h)
+    const size_t n_max = S.coh.size();
+    if (S.fifo && n_max) {
+        if (ctx->ages_pending) {  // (the previous table may still be on its way to the device)
+            FW_HIP(ctx, hipStreamSynchronize(ctx->ages_busy));
+            ctx->ages_pending = false;
+        }
+        if (n_max > ctx->ages_cap) {
+            const size_t cap = std::max<size_t>(n_max * 2, 1024);
+            ctx->ages_cap = 0;
+            if ((st = sync(ctx)) || (st = alloc_buf(ctx, ctx->h_ages, cap * sizeof(FwAgeEntry), Mem::pinned)) ||
+                (st = alloc_buf(ctx, ctx->d_ages, cap * sizeof(FwAgeEntry))))
+                return st;
+            ctx->ages_cap = cap;
+        }
+        FwAgeEntry *tab = (FwAgeEntry *)ctx->h_ages.get();
+        uint32_t n = 0;
+        uint64_t live = 0;
+        for (const SegHost::Cohort &c : S.coh) {
+            if (!c.n) continue;
+            tab[n++] = FwAgeEntry{(uint32_t)live, c.age};
+            live += c.n;
+        }
+        if (live > S.capacity) return poison_segment(ctx, si, "a FIFO ring's cohorts hold more particles than the ring");
+        if (n) {
+            FW_HIP(ctx, hipMemcpyAsync(ctx->d_ages, tab, n * sizeof(FwAgeEntry), hipMemcpyHostToDevice, stream));
+            FW_HIP(ctx, fw_launch_fifo_ages(stream, S.buf[0], S.capacity, S.head, (uint32_t)live, ctx->d_ages, n));
+            ctx->ages_pending = true, ctx->ages_busy = stream;
+            ctx->age_launches++;
+        }
+    }
+    S.ages_stale = false;
+    return FW_OK;
+}
+
 // grows the [2][max_seg] bookkeeping arrays and the snapshot ring: every new array is made (and filled) before any is installed --
 // the rows of the [2][max_seg] ones sit max_seg apart
 fw_status ensure_max_seg(fw_ctx *ctx, uint32_t need) {

@@ -9,7 +9,8 @@ namespace fwh {
 fw_status realloc_segment(fw_ctx *ctx, uint32_t si, uint32_t ncap, bool make_general) {
     SegHost &s = ctx->segs[si];
     ctx->fc_ok = false, ctx->boxes_epoch = 0;
-    fw_status st = refresh_counts_exact(ctx);
+    fw_status st = ensure_ages(ctx, si);  // (the copies below take the age plane as it is: the refresh waits for the kernel)
+    if (!st) st = refresh_counts_exact(ctx);
     if (st) return st;
     if (s.fifo && ncap >= 0x40000000u) make_general = true;  // ring slots are computed in 32 bits: head + index < 2^32
     if (s.range && ncap > FW_RANGE_MAX_CAPACITY) make_general = true;  // (32-bit byte offsets into a plane)
@@ -29,7 +30,6 @@ fw_status realloc_segment(fw_ctx *ctx, uint32_t si, uint32_t ncap, bool make_gen
         return e;
     };
     const size_t OC = s.capacity, NC = ncap;
-    FW_HIP(ctx, cp(FW_OFF_Q0(NC), FW_OFF_Q0(OC), 16));
     // Q1 / Q3 of a RING, and Q2 of a FIFO ring, are four component planes of 4-byte elements each (fw_device.h; their distance follows the capacity), of a segment
     // of the compacting path float4 planes: a ring that grows keeps its layout, one that leaves for that path is transposed as it is
     // unwrapped (hipMemcpy2D: rows of 4 bytes, 4 apart in the source, 16 apart in the destination)
@@ -48,7 +48,10 @@ fw_status realloc_segment(fw_ctx *ctx, uint32_t si, uint32_t ncap, bool make_gen
         return e;
     };
     FW_HIP(ctx, cpq(FW_OFF_Q1(NC), FW_OFF_Q1(OC)));
-    if (s.fifo) FW_HIP(ctx, cpq(FW_OFF_Q2(NC), FW_OFF_Q2(OC)));  // (a FIFO ring's rotation: planes; everybody else's: a float4 plane)
+    // (a FIFO ring's rotation -- and, SegHost::q0pl, its position + age --: planes; everybody else's: float4 planes)
+    if (s.fifo && s.q0pl) FW_HIP(ctx, cpq(FW_OFF_Q0(NC), FW_OFF_Q0(OC)));
+    else FW_HIP(ctx, cp(FW_OFF_Q0(NC), FW_OFF_Q0(OC), 16));
+    if (s.fifo) FW_HIP(ctx, cpq(FW_OFF_Q2(NC), FW_OFF_Q2(OC)));
     else FW_HIP(ctx, cp(FW_OFF_Q2(NC), FW_OFF_Q2(OC), 16));
     FW_HIP(ctx, cpq(FW_OFF_Q3(NC), FW_OFF_Q3(OC)));
     FW_HIP(ctx, cp(FW_OFF_Q5(NC), FW_OFF_Q5(OC), 16));
@@ -70,6 +73,7 @@ fw_status realloc_segment(fw_ctx *ctx, uint32_t si, uint32_t ncap, bool make_gen
     const uint32_t young_lo = s.range_dev ? std::min(s.rold_seen, n) : (n > s.young_n ? n - s.young_n : 0u);
     if (leaves_fifo) {
         s.fifo = false, s.fifo_mat = s.fifo_dev = false, s.coh.clear();
+        s.q0pl = false, s.ageless_last = false;
         s.win_ok = false;  // no lifetime window was kept: the bound follows the snapshots from here on
         ctx->n_fifo--;
         ctx->tab_force = true;
@@ -206,7 +210,10 @@ bool fifo_may_become_range(const fw_ctx *ctx, const SegHost &S) {
 // die in it to the old part as for any range ring.  The context is synchronised (build time).
 fw_status fifo_to_range(fw_ctx *ctx, uint32_t si) {
     if (!fifo_may_become_range(ctx, ctx->segs[si])) return FW_OK;
-    fw_status st = refresh_counts_exact(ctx);  // (a ring that receives Nested children: only the device knows its count)
+    fw_status st = ensure_ages(ctx, si);  // (the range kernel reads every particle's age: written back first)
+    if (st) return st;
+    ctx->segs[si].ageless_last = false;
+    st = refresh_counts_exact(ctx);  // (a ring that receives Nested children: only the device knows its count)
     if (st) return st;
     SegHost &S = ctx->segs[si];
     S.axis = 0u;  // (the axis-spin rule is the FIFO kernel's: the range kernel loads every plane)
@@ -233,19 +240,25 @@ fw_status fifo_to_range(fw_ctx *ctx, uint32_t si) {
         for (const SegHost::Cohort &c : S.coh)
             if (!B.empty() && c.frame >= B.front().frame && c.frame - B.front().frame < B.size()) B[(size_t)(c.frame - B.front().frame)].age = c.age;
     }
-    // ---- the rotation: planes in a FIFO ring, a float4 plane in a range ring (whose kernel moves it whole: four dword accesses where
+    // ---- the rotation -- and position + age --: planes in a FIFO ring, a float4 plane in a range ring (whose kernel moves it whole: four dword accesses where
     // one dwordx4 did cost it 1.3 %, profiles/r12).  Transposed where it stands, through a copy of the region: once per conversion.
     {
-        const size_t C = S.capacity, q2 = FW_OFF_Q2(C);
+        const size_t C = S.capacity;
         HipBuf<char> tmp;
         if ((st = sync(ctx)) || (st = alloc_buf(ctx, tmp, 16 * C))) return st;
-        FW_HIP(ctx, hipMemcpy(tmp, S.buf[0] + q2, 16 * C, hipMemcpyDeviceToDevice));
-        for (size_t c = 0; c < 4; c++)
-            FW_HIP(ctx, hipMemcpy2D(S.buf[0] + q2 + c * 4, 16, (const char *)tmp + c * 4 * C, 4, 4, C, hipMemcpyDeviceToDevice));
-        FW_HIP(ctx, hipDeviceSynchronize());
+        auto planes_to_float4 = [&](size_t q) -> fw_status {
+            FW_HIP(ctx, hipMemcpy(tmp, S.buf[0] + q, 16 * C, hipMemcpyDeviceToDevice));
+            for (size_t c = 0; c < 4; c++)
+                FW_HIP(ctx, hipMemcpy2D(S.buf[0] + q + c * 4, 16, (const char *)tmp + c * 4 * C, 4, 4, C, hipMemcpyDeviceToDevice));
+            FW_HIP(ctx, hipDeviceSynchronize());
+            return FW_OK;
+        };
+        if (S.q0pl && (st = planes_to_float4(FW_OFF_Q0(C)))) return st;  // (a ring that never qualified for the age rule: a float4 already)
+        if ((st = planes_to_float4(FW_OFF_Q2(C)))) return st;
     }
     // ---- the ring's own bookkeeping
     S.fifo = false, ctx->n_fifo--;
+    S.q0pl = false;
     S.range = true, ctx->n_range++;
     S.spilled = true, ctx->n_spilled++;
     S.young_lo = S.head, S.head = 0;
@@ -325,6 +338,7 @@ fw_status set_derived(fw_ctx *ctx, uint32_t si, bool on, bool refill) {
     fw_status st = sync(ctx);
     if (st) return st;
     if (!on && refill) {
+        if ((st = ensure_ages(ctx, si))) return st;  // (scale and colours are functions of the age)
         FW_HIP(ctx, fw_launch_rederive(ctx->stream, seg_view(ctx, si, ctx->parity)));  // (s.derived is still set)
         FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }

@@ -1,6 +1,7 @@
 // fw_k_aux.hip -- readback / upload (AoS <-> planes), plane fills, render hand-off (fw_k_pack), AABB queries, live totals, the copy-bandwidth probe
 // (gfx950 only; device helpers in fw_dev.h, launch interface in fw_kernels.h)
 #include "fw_dev.h"
+#include "fw_ages.h"
 
 // ---------------------------------------------------------------------------------
 // readback / upload / render hand-off helpers
@@ -18,6 +19,8 @@ __device__ __forceinline__ float fw_view_life(const FwSegView &v, uint32_t i) {
     if (v.nospin && v.life_plane == 0xFFFFFFFFu) return v.life_const;
     return fw_load_lifetime(v.buf, v.capacity, v.life_plane, i, v.nospin != 0u, v.cpl != 0u);
 }
+// position + age (a FIFO ring: component planes, FwSegView::cpl bit 2)
+__device__ __forceinline__ float4 fw_view_q0(const FwSegView &v, uint32_t i) { return fw_ldq0(v.buf, v.capacity, i, v.cpl); }
 // velocity + initial_scale, angular velocity + lifetime (cannot turn: 0), rotation (cannot turn: the type's one)
 __device__ __forceinline__ float4 fw_view_q1(const FwSegView &v, uint32_t i) { return fw_ldq(v.buf + FW_OFF_Q1(v.capacity), v.capacity, i, v.cpl != 0u); }
 __device__ __forceinline__ float fw_view_q1w(const FwSegView &v, uint32_t i) { return fw_ldq_w(v.buf + FW_OFF_Q1(v.capacity), v.capacity, i, v.cpl != 0u); }
@@ -47,7 +50,7 @@ __global__ void fw_k_gather(FwSegView v, uint32_t n, int32_t pbr, float *out) {
     const uint32_t li = blockIdx.x * blockDim.x + threadIdx.x;
     if (li >= n) return;
     const uint32_t i = fw_view_slot(v, fw_view_head(v), li);
-    const float4 q0 = fw_ld4(v.buf + FW_OFF_Q0(v.capacity), i), q1 = fw_view_q1(v, i), q2 = fw_view_rot(v, i), q3 = fw_view_q3(v, i);
+    const float4 q0 = fw_view_q0(v, i), q1 = fw_view_q1(v, i), q2 = fw_view_rot(v, i), q3 = fw_view_q3(v, i);
     float4 bc, em;
     float sc;
     fw_view_look(v, i, q0.w, &bc, &em, &sc);
@@ -90,7 +93,7 @@ __global__ void fw_k_fill_colors(char *buf0, char *buf1, uint32_t C, float4 bc, 
 __global__ void fw_k_rederive(FwSegView v) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= v.capacity) return;
-    const float4 q0 = fw_ld4(v.buf + FW_OFF_Q0(v.capacity), i);
+    const float4 q0 = fw_view_q0(v, i);
     float4 bc, em;
     float sc;
     fw_derived_values(*v.derived, v.keys + v.derived->keys_off, q0.w, fw_view_life(v, i), fw_view_q1w(v, i), &bc, &em, &sc);
@@ -100,6 +103,20 @@ hipError_t fw_launch_rederive(hipStream_t s, const FwSegView &v) {
     if (!v.derived) return hipErrorInvalidValue;
     if (!v.capacity) return hipSuccess;
     hipLaunchKernelGGL(fw_k_rederive, dim3((v.capacity + 255) / 256), dim3(256), 0, s, v);
+    return hipGetLastError();
+}
+
+// The age plane of a FIFO ring whose launches ran under the age rule (FW_TYPE_IDX_AGELESS, fw_device.h), written back from the host's
+// cohorts: logical particle li < live gets the age of its cohort (fw_ages.h) in slot (head + li) mod capacity of the plane.
+__global__ void fw_k_fifo_ages(char *buf, uint32_t C, uint32_t head, uint32_t live, const FwAgeEntry *tab, uint32_t n) {
+    const uint32_t li = blockIdx.x * blockDim.x + threadIdx.x;
+    float age;
+    if (!fw_age_of(tab, n, live, li, &age)) return;
+    fw_st1(buf + FW_OFF_Q0(C) + 3 * FW_CP(C), fw_ring_slot(head, li, C), age);
+}
+hipError_t fw_launch_fifo_ages(hipStream_t s, char *buf, uint32_t capacity, uint32_t head, uint32_t live, const void *d_table, uint32_t n) {
+    if (!live || !n || live > capacity || head >= capacity) return hipSuccess;
+    hipLaunchKernelGGL(fw_k_fifo_ages, dim3((live + 255) / 256), dim3(256), 0, s, buf, capacity, head, live, (const FwAgeEntry *)d_table, n);
     return hipGetLastError();
 }
 
@@ -142,7 +159,7 @@ __global__ __launch_bounds__(256) void fw_k_pack(FwSegView v, const uint32_t *d_
     const uint32_t tid = threadIdx.x;
     for (uint32_t b = blockIdx.x * 256u; b < n; b += gridDim.x * 256u) {
         const uint32_t i = fw_view_slot(v, head, min(b + tid, n - 1u));
-        const float4 q0 = fw_ld4(v.buf + FW_OFF_Q0(v.capacity), i), q2 = fw_view_rot(v, i);
+        const float4 q0 = fw_view_q0(v, i), q2 = fw_view_rot(v, i);
         float4 q5, q6;
         float sc;
         fw_view_look(v, i, q0.w, &q5, &q6, &sc);
@@ -235,7 +252,7 @@ __global__ __launch_bounds__(FW_BLOCK) void fw_k_aabb(FwGlobals g, FwSegList L, 
         const uint32_t head = fw_view_head(v);
         for (uint32_t li = blockIdx.x * FW_BLOCK + threadIdx.x; li < n; li += gridDim.x * FW_BLOCK) {
             const uint32_t i = fw_view_slot(v, head, li);
-            const float4 q0 = fw_ld4(v.buf + FW_OFF_Q0(v.capacity), i);
+            const float4 q0 = fw_view_q0(v, i);
             const float sc = fw_view_scale(v, i, q0.w);
             m[0] = fminf(m[0], q0.x - sc), m[1] = fminf(m[1], q0.y - sc), m[2] = fminf(m[2], q0.z - sc);
             m[3] = fmaxf(m[3], q0.x + sc), m[4] = fmaxf(m[4], q0.y + sc), m[5] = fmaxf(m[5], q0.z + sc);

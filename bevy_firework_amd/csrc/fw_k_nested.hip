@@ -125,7 +125,7 @@ __global__ __launch_bounds__(FW_BLOCK) void fw_k_nest(FwGlobals g, FwNestInline 
 #pragma unroll
     for (int r = 0; r < FW_NEST_TILE / FW_BLOCK; r++) {
         const uint32_t ci = fw_ring_slot(parent_head, min(pbase + r * FW_BLOCK + tid, op.parent_cap - 1u), op.parent_cap);
-        p_age[r] = fw_ld4(op.parent_buf + FW_OFF_Q0(op.parent_cap), ci).w;
+        p_age[r] = fw_ldq0_age(op.parent_buf, op.parent_cap, ci, op.parent_nospin >> 1);  // (bits 1-3: FwSeg::cpl of the parents' segment)
         p_life[r] = ((op.parent_nospin & 1u) != 0u && op.parent_life_plane == 0xFFFFFFFFu)
                         ? op.parent_life_const
                         : fw_load_lifetime(op.parent_buf, op.parent_cap, op.parent_life_plane, ci, (op.parent_nospin & 1u) != 0u, (op.parent_nospin & 2u) != 0u);
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(FW_BLOCK) void fw_k_nest(FwGlobals g, FwNestInline 
             s_inc[wave][lane] = inc[r];
             if (n[r] != 0) {
                 const uint32_t ps = fw_ring_slot(parent_head, idx, PC);
-                s_par[wave][0][lane] = fw_ld4(pb + FW_OFF_Q0(PC), ps);
+                s_par[wave][0][lane] = fw_ldq0(pb, PC, ps, op.parent_nospin >> 1);
                 s_par[wave][1][lane] = fw_ldq(pb + FW_OFF_Q1(PC), PC, ps, (op.parent_nospin & 2u) != 0u);  // (the parent's velocity; a ring's Q1: component planes)
                 s_par[wave][2][lane] = (op.parent_nospin & 1u) ? make_float4(op.parent_rot[0], op.parent_rot[1], op.parent_rot[2], op.parent_rot[3])
                                                         : fw_ldq(pb + FW_OFF_Q2(PC), PC, ps, (op.parent_nospin & 4u) != 0u);

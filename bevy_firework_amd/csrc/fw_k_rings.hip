@@ -92,6 +92,8 @@ __device__ __forceinline__ void fw_fifo_nest_parents(const FwGlobals &g, const F
     const uint32_t C = F.capacity, head = F.head, Cc = Fc.capacity;
     char *pb = F.buf;
     // (window addressing as everywhere in this kernel: the tile's first slot on the scalar unit, 32-bit offsets per lane)
+    // (Q0 is a float4 plane here: a ring a Nested entry touches never keeps it in planes -- SegHost::q0pl -- and the host launches the rings
+    // that do by themselves, launch_fifo)
     const char *w0 = pb + FW_OFF_Q0(C) + (size_t)sbase * 16u, *w1 = pb + FW_OFF_Q1(C) + (size_t)sbase * 4u;  // (w1: component planes)
     const char *w2 = pb + FW_OFF_Q2(C) + (size_t)sbase * 4u;  // (w2: component planes too)
     char *wl = pb + FW_OFF_L(C, N.parent_lplane) + (size_t)sbase * 4u;
@@ -222,7 +224,9 @@ __device__ __forceinline__ void fw_fifo_nest_parents(const FwGlobals &g, const F
 // many waves work at once, not by memory -- the reference's own stress_test_collision (157k particles) is 154 workgroups of
 // four rounds, fewer than the chip has CUs, or 615 of one.
 // NEST: some Nested entry runs inside this launch (FwFifoArgs::nest): the parents' ring tiles run fw_fifo_nest_parents first
-template <bool INST, int WM, int NT, int COLL, int TR, bool NEST>
+// Q0PL: every ring of the launch keeps Q0 (position, age) as four component planes (FwFifoArgs::q0pl) -- the rings that may run under the
+// age rule, which the host launches by themselves; never with COLL or NEST
+template <bool INST, int WM, int NT, int COLL, int TR, bool NEST, bool Q0PL = false>
 __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl) {
     constexpr int BLK = FW_BLOCK;
     constexpr int NW = BLK / 64;
@@ -297,8 +301,20 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
     const size_t sfirst = (size_t)sbase * 16u, cp = FW_CP(C);
     // (Q1 / Q2 / Q3 of a FIFO ring: component planes, fw_dev.h -- windows of the x plane, offsets of 4 bytes per slot.  A ring type has ONE lifetime value
     // (F.life) and its initial_scale matters to instance records and destroyed records only: neither `.w` is loaded by the streaming loop)
-    const char *iw0 = buf + FW_OFF_Q0(C) + sfirst, *iw1 = buf + FW_OFF_Q1(C) + sfirst / 4u;
+    // Q0: four planes in the rings that may run under the age rule, a float4 in every other -- a compile-time fact of the launch (Q0PL)
+    static_assert(!Q0PL || (!NEST && COLL == 0), "rings with Q0 in planes are launched by themselves");
+    constexpr bool q0pl = Q0PL;
+    const char *iw0 = buf + FW_OFF_Q0(C) + (q0pl ? sfirst / 4u : sfirst), *iw1 = buf + FW_OFF_Q1(C) + sfirst / 4u;
     const char *iw2 = buf + FW_OFF_Q2(C) + sfirst / 4u, *iw3 = buf + FW_OFF_Q3(C) + sfirst / 4u;
+    // (round 18: a ring under the age rule, FW_TYPE_IDX_AGELESS: host-proved, per launch, does not load the age plane; its register gets
+    // a +0 nobody looks at.  Workgroup-uniform branches, like the axis rule's.)
+    const bool ageless = q0pl && (F.type_idx & FW_TYPE_IDX_AGELESS) != 0u;
+    auto ld0 = [&](uint32_t o16) -> float4 {
+        if (!q0pl) return fw_ld4w<NT == 2>(iw0, o16);
+        float4 v = fw_ldc3w<NT == 2>(iw0, cp, o16 / 4u, 0.0f);
+        if (!ageless) v.w = fw_ld1w<NT == 2>(iw0 + 3 * cp, o16 / 4u);
+        return v;
+    };
     auto ld1 = [&](uint32_t o16) -> float4 {  // velocity (+ initial_scale when this launch writes instance records)
         if constexpr (INST) return fw_ldc4w<NT == 2>(iw1, cp, o16 / 4u);
         else return fw_ldc3w<NT == 2>(iw1, cp, o16 / 4u, 0.0f);
@@ -320,10 +336,10 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
         return v;
     };
     if (!spawner && !defer) {
-        q0c = fw_ld4w<NT == 2>(iw0, tid * 16u), q3c = ld3(tid * 16u);
+        q0c = ld0(tid * 16u), q3c = ld3(tid * 16u);
         q1c = ld1(tid * 16u), q2c = ld2(tid * 16u);
         if constexpr (R > 1) {
-            q0n = fw_ld4w<NT == 2>(iw0, i1), q3n = ld3(i1);
+            q0n = ld0(i1), q3n = ld3(i1);
             q1n = ld1(i1), q2n = ld2(i1);
         }
     }
@@ -331,10 +347,10 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
         uint32_t i0 = sbase - head;
         if (sbase < head) i0 += C;
         if (tis != 0u && !(i0 < n_tot || (i0 + TILE > C && n_tot != 0u))) return;
-        q0c = fw_ld4w<NT == 2>(iw0, tid * 16u), q3c = ld3(tid * 16u);
+        q0c = ld0(tid * 16u), q3c = ld3(tid * 16u);
         q1c = ld1(tid * 16u), q2c = ld2(tid * 16u);
         if constexpr (R > 1) {
-            q0n = fw_ld4w<NT == 2>(iw0, i1), q3n = ld3(i1);
+            q0n = ld0(i1), q3n = ld3(i1);
             q1n = ld1(i1), q2n = ld2(i1);
         }
     }
@@ -356,7 +372,7 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
     }
     char *inst = INST ? F.inst : nullptr;
     float4 *s_inst_wave = s_inst + (INST ? wave * 256u : 0u);
-    const FwOutWin W = fw_out_window(buf, C, sbase, T, 0u, 0u, true, true);
+    const FwOutWin W = fw_out_window(buf, C, sbase, T, 0u, 0u, true, true, q0pl, ageless);
     bool bad = false;
     if (spawner) {
         // ---- this frame's new particles: spawn_particles (core.rs:437-469) right before update_particles, each in the
@@ -407,7 +423,7 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
                 if (s < head) i += C;
                 if (i < n_dead && i < n_in) {
                     const uint32_t b16 = (uint32_t)(r * BLK + (int)tid) * 16u;
-                    const float4 q0 = fw_ld4w<NT == 2>(iw0, b16), q1 = fw_ldc4w<NT == 2>(iw1, cp, b16 / 4u);
+                    const float4 q0 = q0pl ? fw_ldc4w<NT == 2>(iw0, cp, b16 / 4u) : fw_ld4w<NT == 2>(iw0, b16), q1 = fw_ldc4w<NT == 2>(iw1, cp, b16 / 4u);
                     // (the destroyed records read every plane: they hold the true values, axis rule or not)
                     const float4 q2 = nospin ? make_float4(0.0f, 0.0f, 0.0f, 1.0f) : fw_ldc4w<NT == 2>(iw2, cp, b16 / 4u);
                     const float4 q3 = nospin ? q3s : fw_ldc4w<NT == 2>(iw3, cp, b16 / 4u);
@@ -426,7 +442,7 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
             const uint32_t in_ = (uint32_t)(min(r + 2, R - 1) * BLK + (int)tid) * 16u;  // two rounds ahead (the last re-read)
             float4 q0f = q0c, q3f = q3c, q1f = q1c, q2f = q2c;
             if constexpr (R > 1) {  // (a one-round workgroup has nothing to prefetch)
-                q0f = fw_ld4w<NT == 2>(iw0, in_), q3f = ld3(in_);
+                q0f = ld0(in_), q3f = ld3(in_);
                 q1f = ld1(in_), q2f = ld2(in_);
             }
             if (nospin) q3c = q3s;
@@ -435,7 +451,7 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
             float age_new;
             const bool surv = fw_survives(q0c.w, a.dt, q3c.w, &age_new);
             const bool mine = i < n_in, dead = i < n_dead;
-            bad |= mine && surv == dead;  // the host's cohort ages and the particle disagree
+            bad |= !ageless && mine && surv == dead;  // the host's cohort ages and the particle disagree (no age loaded: the cohorts decide)
             const bool alive = mine && !dead;
             const unsigned long long m = INST ? __ballot(alive) : 0ull;
             float4 *rec = (INST && inst != nullptr) ? s_inst_wave + fw_lane_prefix(m) * 4u : nullptr;
@@ -444,7 +460,13 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
             if (alive) {
                 if FW_DBG(a.dbg, 2u) {  // profiling only: stream without arithmetic
                     const uint32_t b16 = (s - W.first) * 16u;
-                    fw_st4w<NT == 2>(W.q0, b16, make_float4(q0c.x, q0c.y, q0c.z, age_new)), fw_stc3w<NT == 2>(W.q1, W.cp, b16 / 4u, q1c.x, q1c.y, q1c.z);
+                    if (W.q0pl) {
+                        fw_stc3w<NT == 2>(W.q0, W.cp, b16 / 4u, q0c.x, q0c.y, q0c.z);
+                        if (W.wr_age) fw_st1w<NT == 2>(W.q0 + 3 * W.cp, b16 / 4u, age_new);
+                    } else {
+                        fw_st4w<NT == 2>(W.q0, b16, make_float4(q0c.x, q0c.y, q0c.z, age_new));
+                    }
+                    fw_stc3w<NT == 2>(W.q1, W.cp, b16 / 4u, q1c.x, q1c.y, q1c.z);
                     if (WM >= 0 ? (WM & 1) != 0 : W.wr5) fw_st4w<NT != 0>(W.q5, b16, q0c);
                     if (WM >= 0 ? (WM & 2) != 0 : W.wr6) fw_st4w<NT != 0>(W.q6, b16, q1c);
                     if (WM >= 0 ? (WM & 4) != 0 : T.sc_kind != 0) fw_st1w<NT != 0>(W.s4, (s - W.first) * 4u, q1c.w);
@@ -507,10 +529,10 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
 #endif
 // (the colliding one-round instantiations sit at the 128-register step: with the capsule arm in the cast the instance-writing ones took
 // 130 registers, 4 -> 3 waves per SIMD, until they were asked for four waves like the plain ones -- 128 again, no scratch)
-template <bool INST, int WM, int NT = 0, int COLL = 0, int TR = FW_ROUNDS>
+template <bool INST, int WM, int NT = 0, int COLL = 0, int TR = FW_ROUNDS, bool Q0PL = false>
 __global__ __launch_bounds__(FW_BLOCK) __attribute__((amdgpu_waves_per_eu((!INST && !COLL && TR == FW_ROUNDS) ? FW_FIFO_WAVES : (COLL == 1 && TR == 1) ? 4 : 1)))
 void fw_k_update_fifo(FwGlobals g, FwFifoArgs a, FwInlineOps inl) {
-    fw_update_fifo_body<INST, WM, NT, COLL, TR, false>(g, a, inl);
+    fw_update_fifo_body<INST, WM, NT, COLL, TR, false, Q0PL>(g, a, inl);
 }
 // ... with Nested entries inside the launch (FwFifoNest).  A kernel of its own so that the plain instantiations keep their code
 // and their register budget; pinned at 4 waves per SIMD (the nest phase took the four-round form to 133 VGPRs: the bulk of such
@@ -1065,10 +1087,55 @@ void fw_k_update_range(FwGlobals g, FwRangeArgs a) {
 
 // ---- launch wrappers
 
+// the launches without a collider or a Nested entry; Q0PL: every ring of the launch keeps Q0 in component planes (FwFifoArgs::q0pl)
+template <bool Q0PL>
+static hipError_t fw_launch_update_fifo_plain(hipStream_t s, const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl, dim3 grid, dim3 block,
+                                              int nt, hipEvent_t e0, hipEvent_t e1) {
+    if (a.small_tiles) {  // a launch of a few hundred four-round workgroups at most: one round each instead (generic write mask)
+        if (a.any_inst)
+            FW_LAUNCH_T((fw_k_update_fifo<true, -1, 0, 0, 1, Q0PL>), grid, block, s, e0, e1, g, a, inl);
+        else
+            FW_LAUNCH_T((fw_k_update_fifo<false, -1, 0, 0, 1, Q0PL>), grid, block, s, e0, e1, g, a, inl);
+        return hipGetLastError();
+    }
+    if (nt) {  // non-temporal forms (fw_ld4w): the generic write mask only -- beyond the Infinity Cache the compile-time one buys nothing
+        if (a.any_inst && nt == 2)
+            FW_LAUNCH_T((fw_k_update_fifo<true, -1, 2, 0, FW_ROUNDS, Q0PL>), grid, block, s, e0, e1, g, a, inl);
+        else if (a.any_inst)
+            FW_LAUNCH_T((fw_k_update_fifo<true, -1, 1, 0, FW_ROUNDS, Q0PL>), grid, block, s, e0, e1, g, a, inl);
+        else if (nt == 2)
+            FW_LAUNCH_T((fw_k_update_fifo<false, -1, 2, 0, FW_ROUNDS, Q0PL>), grid, block, s, e0, e1, g, a, inl);
+        else
+            FW_LAUNCH_T((fw_k_update_fifo<false, -1, 1, 0, FW_ROUNDS, Q0PL>), grid, block, s, e0, e1, g, a, inl);
+        return hipGetLastError();
+    }
+#define FW_FIFO_CASE(wm)                                                                   \
+    case wm:                                                                               \
+        if (a.any_inst)                                                                    \
+            FW_LAUNCH_T((fw_k_update_fifo<true, wm, 0, 0, FW_ROUNDS, Q0PL>), grid, block, s, e0, e1, g, a, inl);  \
+        else                                                                               \
+            FW_LAUNCH_T((fw_k_update_fifo<false, wm, 0, 0, FW_ROUNDS, Q0PL>), grid, block, s, e0, e1, g, a, inl); \
+        break;
+    // (round 6: every type leaves scale and colours to its readers -- write mask 0 is what the product launches; the other seven
+    // compile-time masks of rounds 3-5 served types that stored those planes: FW_DERIVED=0 / 1 and colliding types now take the
+    // generic form -- 14 instantiations and a third of the library's build time less)
+    switch (a.write_mask) {
+        FW_FIFO_CASE(0)
+        default:
+            if (a.any_inst)
+                FW_LAUNCH_T((fw_k_update_fifo<true, -1, 0, 0, FW_ROUNDS, Q0PL>), grid, block, s, e0, e1, g, a, inl);
+            else
+                FW_LAUNCH_T((fw_k_update_fifo<false, -1, 0, 0, FW_ROUNDS, Q0PL>), grid, block, s, e0, e1, g, a, inl);
+    }
+#undef FW_FIFO_CASE
+    return hipGetLastError();
+}
+
 hipError_t fw_launch_update_fifo(hipStream_t s, const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl,
                                  uint32_t total_tiles, int nt, hipEvent_t e0, hipEvent_t e1) {
     if (!total_tiles || !a.n_segs) return hipErrorInvalidValue;
     const dim3 grid(total_tiles), block(FW_BLOCK);
+    if (a.q0pl && (a.n_nest || a.any_coll)) return hipErrorInvalidValue;  // (the host launches rings with Q0 in planes by themselves)
     if (a.n_nest) {  // Nested entries inside the launch (FwFifoNest): generic write mask; the host keeps instance buffers and colliders out
         // (... and such a launch holds a ring whose count only the device knows: never laid out on one-round tiles)
         if (a.any_inst || a.any_coll || a.small_tiles) return hipErrorInvalidValue;
@@ -1104,44 +1171,8 @@ hipError_t fw_launch_update_fifo(hipStream_t s, const FwGlobals &g, const FwFifo
             FW_LAUNCH_T((fw_k_update_fifo<false, -1, 0, 1, 1>), grid, block, s, e0, e1, g, a, inl);
         return hipGetLastError();
     }
-    if (a.small_tiles) {  // a launch of a few hundred four-round workgroups at most: one round each instead (generic write mask)
-        if (a.any_inst)
-            FW_LAUNCH_T((fw_k_update_fifo<true, -1, 0, false, 1>), grid, block, s, e0, e1, g, a, inl);
-        else
-            FW_LAUNCH_T((fw_k_update_fifo<false, -1, 0, false, 1>), grid, block, s, e0, e1, g, a, inl);
-        return hipGetLastError();
-    }
-    if (nt) {  // non-temporal forms (fw_ld4w): the generic write mask only -- beyond the Infinity Cache the compile-time one buys nothing
-        if (a.any_inst && nt == 2)
-            FW_LAUNCH_T((fw_k_update_fifo<true, -1, 2>), grid, block, s, e0, e1, g, a, inl);
-        else if (a.any_inst)
-            FW_LAUNCH_T((fw_k_update_fifo<true, -1, 1>), grid, block, s, e0, e1, g, a, inl);
-        else if (nt == 2)
-            FW_LAUNCH_T((fw_k_update_fifo<false, -1, 2>), grid, block, s, e0, e1, g, a, inl);
-        else
-            FW_LAUNCH_T((fw_k_update_fifo<false, -1, 1>), grid, block, s, e0, e1, g, a, inl);
-        return hipGetLastError();
-    }
-#define FW_FIFO_CASE(wm)                                                                   \
-    case wm:                                                                               \
-        if (a.any_inst)                                                                    \
-            FW_LAUNCH_T((fw_k_update_fifo<true, wm>), grid, block, s, e0, e1, g, a, inl);  \
-        else                                                                               \
-            FW_LAUNCH_T((fw_k_update_fifo<false, wm>), grid, block, s, e0, e1, g, a, inl); \
-        break;
-    // (round 6: every type leaves scale and colours to its readers -- write mask 0 is what the product launches; the other seven
-    // compile-time masks of rounds 3-5 served types that stored those planes: FW_DERIVED=0 / 1 and colliding types now take the
-    // generic form -- 14 instantiations and a third of the library's build time less)
-    switch (a.write_mask) {
-        FW_FIFO_CASE(0)
-        default:
-            if (a.any_inst)
-                FW_LAUNCH_T((fw_k_update_fifo<true, -1>), grid, block, s, e0, e1, g, a, inl);
-            else
-                FW_LAUNCH_T((fw_k_update_fifo<false, -1>), grid, block, s, e0, e1, g, a, inl);
-    }
-#undef FW_FIFO_CASE
-    return hipGetLastError();
+    if (a.q0pl) return fw_launch_update_fifo_plain<true>(s, g, a, inl, grid, block, nt, e0, e1);
+    return fw_launch_update_fifo_plain<false>(s, g, a, inl, grid, block, nt, e0, e1);
 }
 
 template <int NT>

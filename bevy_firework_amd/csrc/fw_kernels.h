@@ -245,7 +245,10 @@ struct FwFifoArgs {
     unsigned long long done_value;
     unsigned long long *host_counts;
     unsigned long long *live_out, *live_next;
-    uint32_t n_nest, pad_nest;         // Nested entries run inside this launch (the NEST instantiations of fw_k_update_fifo)
+    uint32_t n_nest;                   // Nested entries run inside this launch (the NEST instantiations of fw_k_update_fifo)
+    uint32_t q0pl;                     // 1: EVERY ring of the launch keeps Q0 (position, age) as four component planes (FwSeg::cpl bit 2,
+                                       // SegHost::q0pl: the rings that may run under the age rule -- the host launches them by themselves,
+                                       // never with a collider or a Nested entry: the Q0PL instantiations); 0: none does
     FwFifoNest nest[FW_FIFO_NEST_MAX];
 };
 
@@ -365,7 +368,7 @@ hipError_t fw_launch_nested(hipStream_t s, const FwGlobals &g, const FwNestOp *d
 // have to know how a segment stores its particles.  FwSegView says it once; the host fills it in ONE place (seg_view,
 // fw_engine_mem.cpp: every field from SegHost) and the device reads it through ONE set of functions (fw_view_*, fw_k_aux.hip):
 //   in which slot is particle 0?            head / d_rold       SegHost::enqueue_head(), or ring_head_exact (seg_view_exact)
-//   Q1 / Q3 in component planes?  Q2?       cpl                 SegHost::cpl_bits()
+//   Q1 / Q3 in component planes?  Q2?  Q0?  cpl                 SegHost::cpl_bits()
 //   a rotation plane, or one rotation?      nospin / rot        SegHost::nospin, const_rot
 //   where is the lifetime?                  life_plane / const  SegHost::life_plane(), fifo_life -- read under `nospin` only
 //   scale and colours stored, or evaluated? derived / keys      SegHost::derived
@@ -375,7 +378,7 @@ struct FwSegView {
     uint32_t capacity;
     uint32_t head;           // slot of particle 0 -- or, d_rold set, of the ring's first YOUNG particle
     const uint32_t *d_rold;  // null, or -- a range ring -- the segment's word of FwGlobals::rold: particle 0 sits so many slots before `head`
-    uint32_t cpl;            // FwSeg::cpl -- bit 0: a ring, its Q1 / Q3 regions are component planes; bit 1: a FIFO ring, Q2 as well (fw_dev.h)
+    uint32_t cpl;            // FwSeg::cpl -- bit 0: a ring, its Q1 / Q3 regions are component planes; bit 1: a FIFO ring, Q2 as well; bit 2: ... and Q0 (fw_dev.h)
     uint32_t nospin;         // FW_TYPE_NOSPIN: the rotation plane is not maintained and Q3 is not read -- every particle has
     float4 rot;              //   this rotation, angular velocity 0,
     uint32_t life_plane;     //   and its lifetime in this plane behind the last_emitted_age planes, or -- 0xFFFFFFFF: a FIFO ring --
@@ -387,6 +390,8 @@ struct FwSegView {
 hipError_t fw_launch_gather(hipStream_t s, const FwSegView &v, uint32_t n, int32_t pbr, void *d_out);
 // fills the scale / colour planes of every slot from age, lifetime and initial_scale (a type leaves FW_TYPE_DERIVED: v.derived is still set)
 hipError_t fw_launch_rederive(hipStream_t s, const FwSegView &v);
+// the age plane of a FIFO ring from its cohort table (fw_ages.h: n FwAgeEntry records in device memory), for logical particles [0, live)
+hipError_t fw_launch_fifo_ages(hipStream_t s, char *buf, uint32_t capacity, uint32_t head, uint32_t live, const void *d_table, uint32_t n);
 hipError_t fw_launch_fill_plane1(hipStream_t s, char *buf0, char *buf1, size_t plane_off, uint32_t capacity, float v);
 // A type leaves FW_TYPE_NOSPIN, in one (buf1 == nullptr) or both buffers of its segment: Q3 = {0, 0, 0, lifetime} again, and the
 // rotation plane, which nobody maintained, filled with the type's one rotation.  cpl, life_plane, life_const: as in FwSegView

@@ -495,6 +495,12 @@ class ParticleSystem:
         self._check(self._lib.fw_debug_tf_frames(self._ctx, C.byref(n)))
         return int(n.value)
 
+    def age_launches(self) -> int:
+        """launches of fw_k_fifo_ages so far: a FIFO ring under the age rule had its ages written back for a reader"""
+        n = C.c_uint64()
+        self._check(self._lib.fw_debug_age_launches(self._ctx, C.byref(n)))
+        return int(n.value)
+
     def recovered_rings(self) -> int:
         """rings moved to the compacting path (particles kept) because a cohort report was missing when it was due"""
         n = C.c_uint64()

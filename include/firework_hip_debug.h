@@ -6,7 +6,7 @@
  * the measured roofline, in-kernel timestamps, and which update path a particle type is on.  They may change between
  * builds without an ABI version bump.
  *
- * Environment knobs.  The library reads A/B and debugging switches from the environment (FW_FIFO, FW_RANGE, FW_NOSPIN, FW_AXIS_SPIN,
+ * Environment knobs.  The library reads A/B and debugging switches from the environment (FW_FIFO, FW_RANGE, FW_NOSPIN, FW_AXIS_SPIN, FW_AGELESS,
  * FW_FORECAST, FW_UPDATE_MODE, FW_DEBUG, ...; DESIGN.md section 7 lists them) ONLY when FW_ENABLE_KNOBS=1 is set: a
  * product process never changes behaviour because of a stray variable.  The tests and the tools set it.
  */
@@ -62,6 +62,11 @@ fw_status fw_debug_recovered_rings(fw_ctx *ctx, uint64_t *n);
 /* frames of the compacting launch that ran under a dt different from the previous frame's on the STREAMING schedule (threshold
  * forecast: fw_k_fc_resolve in front of fw_k_update_stream) instead of the decoupled look-back */
 fw_status fw_debug_tf_frames(fw_ctx *ctx, uint64_t *n);
+
+/* launches so far of the kernel that writes the ages of a FIFO ring under the age rule back from the host's spawn cohorts (DESIGN.md
+ * 4.0): one per read or copy of such a ring's particles after frames that did not move the age plane, none for a call that only
+ * asks for counts */
+fw_status fw_debug_age_launches(fw_ctx *ctx, uint64_t *n);
 
 /* *on = 1: the context keeps the per-frame records of its range launches and its small op tables in DEVICE memory that the host writes
  * through the large BAR; 0: in pinned host memory (the platform does not map device memory for the host, or

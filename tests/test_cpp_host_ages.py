@@ -1,0 +1,155 @@
+"""The age of a FIFO-ring particle from the host's spawn cohorts without a GPU (csrc/fw_ages.h, the lookup fw_k_fifo_ages runs per lane):
+a stand-alone C++ program, compiled here with g++ -- once plainly, once with -fsanitize=address,undefined --, replays the cohorts of a
+frame sequence the way launch_fifo does (`age = age + dt` per cohort, -ffp-contract=off), lays the table out the way ensure_ages does
+(one entry per cohort that holds particles) and answers queries through fw_age_of; a plain Python loop of np.float32 additions over
+every single particle says what each answer must be, bit for bit."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "bevy_firework_amd", "csrc")
+K_MAX_COHORTS = 16384  # fw_engine.h: kMaxCohorts
+
+PROGRAM = r"""
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+#include "fw_ages.h"
+struct Cohort { uint32_t n; float age; };
+int main(int argc, char **argv) {
+    if (argc != 2) return 2;
+    FILE *f = fopen(argv[1], "r");
+    if (!f) return 2;
+    unsigned frames = 0, queries = 0;
+    if (fscanf(f, "%u %u", &frames, &queries) != 2) return 2;
+    std::vector<Cohort> coh;
+    for (unsigned i = 0; i < frames; i++) {
+        unsigned n = 0, bits = 0;
+        if (fscanf(f, "%u %x", &n, &bits) != 2) return 2;
+        float dt;
+        memcpy(&dt, &bits, 4);
+        coh.push_back(Cohort{n, 0.0f});
+        for (Cohort &c : coh) c.age = c.age + dt;
+    }
+    std::vector<FwAgeEntry> tab;
+    unsigned long long live = 0;
+    for (const Cohort &c : coh) {
+        if (!c.n) continue;
+        tab.push_back(FwAgeEntry{(uint32_t)live, c.age});
+        live += c.n;
+    }
+    // (a table of exactly its size on the heap: the sanitizer build sees a lookup that leaves it)
+    FwAgeEntry *t = tab.empty() ? nullptr : (FwAgeEntry *)malloc(tab.size() * sizeof(FwAgeEntry));
+    if (t) memcpy(t, tab.data(), tab.size() * sizeof(FwAgeEntry));
+    printf("entries %zu live %llu\n", tab.size(), live);
+    for (unsigned q = 0; q < queries; q++) {
+        unsigned i = 0;
+        if (fscanf(f, "%u", &i) != 1) return 2;
+        float age = -1.0f;
+        if (fw_age_of(t, (uint32_t)tab.size(), (uint32_t)live, i, &age)) {
+            unsigned bits;
+            memcpy(&bits, &age, 4);
+            printf("%u %08x\n", i, bits);
+        } else {
+            printf("%u none\n", i);
+        }
+    }
+    free(t);
+    fclose(f);
+    return 0;
+}
+"""
+
+
+@pytest.fixture(scope="module", params=["plain", "address,undefined"])
+def program(request, tmp_path_factory):
+    d = tmp_path_factory.mktemp("ages")
+    (d / "ages.cpp").write_text(PROGRAM)
+    exe = d / "ages"
+    flags = ["-O2"] if request.param == "plain" else ["-O1", "-g", "-fsanitize=" + request.param, "-fno-sanitize-recover=all", "-fno-omit-frame-pointer"]
+    subprocess.check_call(["g++", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-Wall", "-Werror", "-I", CSRC] + flags + [str(d / "ages.cpp"), "-o", str(exe)])
+    return str(exe), d
+
+
+def _expected(frames):
+    """every particle by itself: born with age 0, `age + dt` in fp32 per frame -> (ages in list order, first index of every cohort that
+    holds particles, its last index)"""
+    ages = np.zeros(0, dtype=np.float32)
+    born = np.zeros(0, dtype=np.int64)
+    for k, (n, dt) in enumerate(frames):
+        ages = np.concatenate([ages, np.zeros(n, dtype=np.float32)])
+        born = np.concatenate([born, np.full(n, k)])
+        for i in range(len(ages)):  # (the plain loop: one np.float32 addition per particle and frame)
+            ages[i] = np.float32(ages[i]) + np.float32(dt)
+    firsts = [int(np.flatnonzero(born == k)[0]) for k in range(len(frames)) if (born == k).any()]
+    lasts = [int(np.flatnonzero(born == k)[-1]) for k in range(len(frames)) if (born == k).any()]
+    return ages, firsts, lasts
+
+
+def _run(program, frames, queries, name):
+    exe, d = program
+    path = d / (name + ".txt")
+    lines = [f"{len(frames)} {len(queries)}"] + [f"{n} {np.float32(dt).view(np.uint32):08x}" for n, dt in frames] + [str(q) for q in queries]
+    path.write_text("\n".join(lines) + "\n")
+    r = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stderr[-2000:]
+    out = r.stdout.strip().splitlines()
+    head = out[0].split()
+    return int(head[1]), int(head[3]), [ln.split() for ln in out[1:]]
+
+
+def _check(program, frames, name, extra=()):
+    ages, firsts, lasts = _expected(frames)
+    queries = sorted(set(firsts + lasts + list(extra))) + [len(ages), len(ages) + 1, 0xFFFFFFFF]
+    entries, live, answers = _run(program, frames, queries, name)
+    assert entries == len(firsts) and live == len(ages)
+    assert len(answers) == len(queries)
+    for q, (i, got) in zip(queries, answers):
+        assert int(i) == q
+        want = f"{ages[q].view(np.uint32):08x}" if q < len(ages) else "none"
+        assert got == want, (name, q, got, want)
+
+
+def test_first_and_last_index_of_every_cohort(program):
+    """a jittering dt, dt = 0 frames (two cohorts of one age), frames that spawn nothing (no entry), cohorts of one particle"""
+    rng = np.random.default_rng(18)
+    frames = [(int(n), np.float32(dt)) for n, dt in zip(rng.integers(0, 40, size=48), rng.uniform(0.001, 0.03, size=48))]
+    for k in (5, 6, 20):
+        frames[k] = (frames[k][0] + 3, np.float32(0.0))
+    for k in (9, 10, 30):
+        frames[k] = (0, frames[k][1])
+    frames[12] = (1, frames[12][1])
+    frames[0] = (0, frames[0][1])  # (the oldest cohort is an empty one: entry 0 still starts at index 0)
+    _check(program, frames, "jitter", extra=range(0, 64))
+
+
+def test_one_cohort(program):
+    _check(program, [(777, np.float32(1.0 / 60.0))], "one", extra=(1, 388, 775))
+    _check(program, [(1, np.float32(0.25))], "one_particle")
+
+
+def test_kmaxcohorts_cohorts_of_one_particle_each(program):
+    """the largest table a ring keeps (fw_engine.h: kMaxCohorts), every entry one particle: every index is a first and a last.  (The
+    per-particle loop of _expected is quadratic in the frames: the ages of this case are the running sums, newest first, added the
+    same way -- one np.float32 addition per frame.)"""
+    dt = np.float32(1.0 / 1024.0)
+    frames = [(1, dt)] * K_MAX_COHORTS
+    sums = np.zeros(K_MAX_COHORTS + 1, dtype=np.float32)
+    for k in range(K_MAX_COHORTS):
+        sums[k + 1] = np.float32(sums[k]) + dt
+    ages = sums[1:][::-1]  # particle i was born in frame i and has been through K - i additions
+    queries = list(range(K_MAX_COHORTS)) + [K_MAX_COHORTS]
+    entries, live, answers = _run(program, frames, queries, "kmax")
+    assert entries == K_MAX_COHORTS and live == K_MAX_COHORTS
+    assert [a[1] for a in answers[:-1]] == [f"{a.view(np.uint32):08x}" for a in ages] and answers[-1][1] == "none"
+
+
+def test_empty_table(program):
+    """no cohort at all, and cohorts without a particle: no entry, nobody has an age"""
+    for name, frames in (("none", []), ("hollow", [(0, np.float32(0.01))] * 5)):
+        entries, live, answers = _run(program, frames, [0, 1, 0xFFFFFFFF], "empty_" + name)
+        assert entries == 0 and live == 0 and [a[1] for a in answers] == ["none"] * 3

@@ -152,7 +152,9 @@ __global__ __launch_bounds__(256) void k_upd_s3(char* __restrict__ buf, uint32_t
 // (a mover adds a constant, so its bits change every launch; the others keep theirs).  Every store of Q2 / Q3 sits under the product's
 // test -- __any(new bits != loaded bits) -- so the rows carry its cost too.  All 14 words are read in every row, except with SK (round 12,
 // the axis-spin rule's shape): a component that does not move is not loaded either, its register gets z.
-template <int Q2P, int M2, int M3, int NT, int SK = 0>
+// Q0P (round 18): 1 = Q0 as four scalar planes, all read and written (the layout the age rule needs); 2 = the fourth of them -- the age --
+// neither read nor written, its register gets z (the age rule's 72 B shape).
+template <int Q2P, int M2, int M3, int NT, int SK = 0, int Q0P = 0>
 __global__ __launch_bounds__(256) void k_upd_cw(char* __restrict__ buf, uint32_t n, uint32_t C, int K, float z) {  // z: 0 at run time, unknown to the compiler
     constexpr int R = 4;
     const uint32_t base = blockIdx.x * 256 * R;
@@ -161,8 +163,19 @@ __global__ __launch_bounds__(256) void k_upd_cw(char* __restrict__ buf, uint32_t
 #pragma unroll
     for (int r = 0; r < R; r++) {
         const uint32_t i = min(base + r * 256 + threadIdx.x, n - 1);
-        const f4v* a0 = (const f4v*)(buf) + i;
-        q0[r] = NT ? __builtin_nontemporal_load(a0) : *a0;
+        if (Q0P) {
+            float v[4];
+#pragma unroll
+            for (int c = 0; c < 4; c++) {
+                const float* a0 = (const float*)(buf + (size_t)(4 * c) * C) + i;
+                if (Q0P == 2 && c == 3) v[c] = z;
+                else v[c] = NT ? __builtin_nontemporal_load(a0) : *a0;
+            }
+            q0[r] = f4v{v[0], v[1], v[2], v[3]};
+        } else {
+            const f4v* a0 = (const f4v*)(buf) + i;
+            q0[r] = NT ? __builtin_nontemporal_load(a0) : *a0;
+        }
 #pragma unroll
         for (int c = 0; c < 3; c++) {
             const float* a1 = (const float*)(buf + (size_t)(16 + 4 * c) * C) + i;
@@ -193,8 +206,17 @@ __global__ __launch_bounds__(256) void k_upd_cw(char* __restrict__ buf, uint32_t
         if (i < n) {
             f4v a = q0[r];
             a.x = work(a.x + q1[r][0], K); q1[r][1] += a.y; q1[r][2] += a.z; q1[r][0] += a.w;
-            f4v* o0 = (f4v*)(buf) + i;
-            if (NT) __builtin_nontemporal_store(a, o0); else *o0 = a;
+            if (Q0P) {
+                const float v[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+                for (int c = 0; c < (Q0P == 2 ? 3 : 4); c++) {
+                    float* o0 = (float*)(buf + (size_t)(4 * c) * C) + i;
+                    if (NT) __builtin_nontemporal_store(v[c], o0); else *o0 = v[c];
+                }
+            } else {
+                f4v* o0 = (f4v*)(buf) + i;
+                if (NT) __builtin_nontemporal_store(a, o0); else *o0 = a;
+            }
 #pragma unroll
             for (int c = 0; c < 3; c++) {
                 float* o1 = (float*)(buf + (size_t)(16 + 4 * c) * C) + i;
@@ -326,6 +348,8 @@ static void component_writes() {
                 RUN_CW((k_upd_cw<1, 15, 7, 0>), 56, "Q2 four planes, tests, all move: 14 words written", 0.0f)
                 RUN_CW((k_upd_cw<1, 10, 2, 0>), 40, "Q2 four planes, Q2 x/z + Q3 x/z skipped: 10 words", 0.0f)
                 RUN_CW((k_upd_cw<1, 10, 2, 0, 1>), 40, "... and not loaded either: r 40 B, the axis rule's 80 B", 0.0f)
+                RUN_CW((k_upd_cw<1, 10, 2, 0, 1, 1>), 40, "r18: those 80 B with Q0 as four planes: r 40 B", 0.0f)
+                RUN_CW((k_upd_cw<1, 10, 2, 0, 1, 2>), 36, "r18: ... the age plane untouched, the rule's 72 B: r 36 B", 0.0f)
             }
         }
         CK(hipFree(p0));
