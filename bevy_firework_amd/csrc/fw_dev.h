@@ -436,6 +436,23 @@ __device__ __forceinline__ fw_q4 fw_quat_step(fw_v3 v) {
     return fw_quat_from_scaled_axis(v);
 }
 
+// one frame of a particle's spin: rotation = from_scaled_axis(angvel * dt) * rotation, no renormalisation (core.rs:645-647), then the
+// angular velocity (core.rs:648-650).  The ONE definition: fw_integrate_store runs it per update, fw_k_fifo_spin (fw_k_aux.hip) once per
+// logged dt of a ring whose spin was deferred (fw_spin.h) -- the same statements in the same order, so the replay gives the update's bits.
+struct FwSpin {
+    fw_q4 rot;
+    float wx, wy, wz;
+};
+__device__ __forceinline__ FwSpin fw_spin_step(const FwType &T, float dt, float4 q2, float4 q3) {
+    const fw_q4 dq = fw_quat_step(fw_v3{q3.x * dt, q3.y * dt, q3.z * dt});
+    FwSpin o;
+    o.rot = fw_quat_mul(dq, fw_q4{q2.x, q2.y, q2.z, q2.w});
+    o.wx = q3.x + (T.angacc[0] - T.ang_drag * q3.x) * dt;  // core.rs:648-650
+    o.wy = q3.y + (T.angacc[1] - T.ang_drag * q3.y) * dt;
+    o.wz = q3.z + (T.angacc[2] - T.ang_drag * q3.z) * dt;
+    return o;
+}
+
 // INPLACE (FIFO segments, fw_k_update_fifo): the output slot is the input slot, so a plane whose new value is
 // bit-identical to the loaded one for every lane of the wave is not written (rotation and angular velocity of particles
 // that do not spin, the scale under a constant curve); rotation and angular velocity, whose components are planes of their own, are
@@ -491,11 +508,8 @@ __device__ __forceinline__ void fw_integrate_store(const FwType &T, const float 
     fw_q4 nr{q2.x, q2.y, q2.z, q2.w};
     float wx = 0.0f, wy = 0.0f, wz = 0.0f;
     if (!(T.flags & FW_TYPE_NOSPIN)) {
-        const fw_q4 dq = fw_quat_step(fw_v3{q3.x * dt, q3.y * dt, q3.z * dt});
-        nr = fw_quat_mul(dq, fw_q4{q2.x, q2.y, q2.z, q2.w});
-        wx = q3.x + (T.angacc[0] - T.ang_drag * q3.x) * dt;  // core.rs:648-650
-        wy = q3.y + (T.angacc[1] - T.ang_drag * q3.y) * dt;
-        wz = q3.z + (T.angacc[2] - T.ang_drag * q3.z) * dt;
+        const FwSpin sp = fw_spin_step(T, dt, q2, q3);
+        nr = sp.rot, wx = sp.wx, wy = sp.wy, wz = sp.wz;
     }
     const uint32_t b16 = (o - W.first) * 16u;  // < 16 KiB + a tile: the window starts at the tile's first output slot
     const uint32_t b4 = (o - W.first) * 4u;

@@ -131,6 +131,16 @@ struct alignas(16) FwType {
 // then STALE (SegHost::ages_stale): fw_k_fifo_ages writes the cohort ages back -- the same bits the kernel would have stored -- before
 // anybody reads the plane or a launch without the bit runs: ensure_ages, fw_engine_mem.cpp.)
 #define FW_TYPE_IDX_AGELESS 0x40000000u
+// (FwFifoSeg::type_idx, round 19: FW_TYPE_IDX_NOSPIN TOGETHER WITH a non-zero FW_TYPE_IDX_AXIS field -- a pair no launch carried before:
+// a type that cannot turn has no axis -- = the spin of the ring, about axis k, is DEFERRED in this launch.  The tiles of the particles
+// that were in the ring before the launch treat it as a ring that cannot turn -- nothing of rotation or angular velocity is loaded,
+// integrated or stored --, the workgroups that spawn integrate their particles once and store every plane.  Nothing else an update
+// computes reads the spin where the age rule holds (no instance record, no destroyed record, no collider, no Nested entry), and the spin
+// at frame n is a function of the spin at frame m < n and the dt of frames m+1..n: the host logs the dt of every deferred frame and, per
+// spawn cohort, the first logged step its particles lack (fw_spin.h); fw_k_fifo_spin replays them -- fw_spin_step, the update's own
+// statements -- before anybody reads the planes or a launch without the pair runs: ensure_spin, fw_engine_mem.cpp.  The axis rule's
+// proof is what makes the replay bit-safe: under axis_dt_ok every lane takes fw_quat_step's polynomial arm, so no bit depends on
+// which lanes share a wave.)
 #define FW_TYPE_IDX_MASK 0x0FFFFFFFu
 // collision_settings of a particle type (core.rs:137-138, 240-248), in a table of its own next to FwType: only the
 // collision kernels read it, the streaming kernels' per-type record (and their scalar-register budget) stays as it was

@@ -50,6 +50,7 @@
 #include "fw_kernels.h"
 #include "fw_math.h"
 #include "fw_ages.h"
+#include "fw_spin.h"
 
 namespace fwh {
 
@@ -440,12 +441,21 @@ struct alignas(64) SegHost {
         float age;
         uint64_t frame = 0;  // frame the cohort was added in
         bool known = true;   // false: a cohort of Nested children whose size the device has not been asked for yet
+        uint64_t spin_from = 0;  // first entry of `spin`'s log the cohort's particles have not had applied (fw_spin.h; read while spin.stale)
     };
     std::deque<Cohort> coh;  // oldest first
     // The age rule (fw_device.h: FW_TYPE_IDX_AGELESS): the ring's latest launches neither loaded nor stored the age plane -- the cohort
     // ages above stand for it.  ensure_ages writes them back (fw_k_fifo_ages) before anybody reads the plane, before a launch that
     // does not carry the bit, and before the ring is copied or changes its kind.  ageless_last: the latest launch carried the bit.
     bool ages_stale = false, ageless_last = false;
+    // The deferred spin (fw_spin.h; FW_TYPE_IDX_NOSPIN together with FW_TYPE_IDX_AXIS): the ring's latest launches under the age rule AND
+    // the axis rule left rotation and angular velocity of the particles they did not spawn alone and logged their dt.  ensure_spin
+    // replays the log per particle (fw_k_fifo_spin) before anybody reads those planes, before a launch that does not defer, and before
+    // the ring is copied, changes its kind or gets a new type record.  spin_streak: consecutive launches that met every condition of
+    // the rule since anybody last asked for the planes (fw_ctx::spin_defer_after); spin_last: the latest launch was deferred.
+    FwSpinBook spin;
+    uint32_t spin_streak = 0;
+    bool spin_last = false;
     bool q0pl = false;  // the ring keeps Q0 (position, age) as four component planes (FwSeg::cpl bit 2): set where the ring is built
     // A ring in a spawner WITH Nested entries: in frames that run the Nested pass its new particles are materialised in
     // the ring before the update (fw_k_spawn / fw_k_nest address it through the head) and fw_k_update_fifo gives them
@@ -775,6 +785,20 @@ struct fw_ctx {
     hipStream_t ages_busy = nullptr;
     bool ages_pending = false;
     uint64_t age_launches = 0;  // fw_debug_age_launches
+    // the deferred spin of FIFO rings nobody reads (fw_spin.h).  FW_SPIN_DEFER=0: no ring defers (A/B in one build); spin_defer_min:
+    // live particles from which a ring may (FW_SPIN_DEFER_MIN; the size from which a launch counts as bound by bandwidth);
+    // spin_defer_after: qualifying launches in a row, with nobody asking for the planes, before the first deferred one
+    // (FW_SPIN_DEFER_AFTER: a host that reads every few frames never pays a replay; 32 = the smallest power of two not below the cost of
+    // one replay of the 1 M ring after a full lifetime unread over the kernel time a deferred frame saves, 72 us / 2.9 us, profiles/r19);
+    // spin_log_cap: frames a ring may fall behind
+    // (FW_SPIN_LOG: bounds the replay loop and the table).  The table and the log of the latest ensure_spin travel like the age table.
+    bool use_spin_defer = true;
+    uint32_t spin_defer_min = 384u * FW_TILE, spin_defer_after = 32u, spin_log_cap = 256u;
+    HipBuf<char> h_spin, d_spin;
+    size_t spin_cap = 0;
+    hipStream_t spin_busy = nullptr;
+    bool spin_pending = false;
+    uint64_t spin_launches = 0;  // fw_debug_spin_launches
     bool use_axis = true;      // FW_AXIS_SPIN=0: no ring runs under the axis-spin rule (A/B in one build)
     bool use_derived = true;   // FW_DERIVED=0: every type stores its scale / colour planes, attached instance buffer or not (A/B)
     // Round 6: scale, base colour and emissive colour are pure functions of (age, lifetime, initial_scale) (core.rs:601-605,
@@ -1204,6 +1228,10 @@ fw_status join_side(fw_ctx *ctx);
 // stream, which first waits for the ring launches on the side stream (join_side)
 fw_status ensure_ages(fw_ctx *ctx, uint32_t si, hipStream_t stream = nullptr);
 bool ageless_dt_ok(float dt);
+// ... and a FIFO ring whose spin is deferred (SegHost::spin) gets its log replayed.  keep_streak: the log reached its cap -- the ring
+// goes on deferring; everybody else asks because the planes are wanted, and the ring has to earn the rule again (spin_defer_after)
+fw_status ensure_spin(fw_ctx *ctx, uint32_t si, hipStream_t stream = nullptr, bool keep_streak = false);
+bool spin_dt_ok(float dt);
 fw_status ensure_max_seg(fw_ctx *ctx, uint32_t need);
 uint32_t seg_live_tiles(const SegHost &s);
 uint32_t seg_tiles(const SegHost &s, uint32_t vt_rounds = 1);

@@ -65,9 +65,11 @@ fw_ctx::~fw_ctx() {
 // overflowed: the call goes on and reports it at its end, unless a later error takes precedence).
 // Ages: whether the call reads or copies particles.  Ages::write -- a ring under the age rule gets its ages written back first
 // (ensure_ages; nothing where none is stale).  Ages::leave -- the call looks at counts, records or last_emitted planes only: a stale
-// age plane stays stale, and a host that polls every frame keeps the rule.
+// age plane stays stale, and a host that polls every frame keeps the rule.  Ages::ages -- the call reads positions, ages and what
+// derives from them, never rotation or angular velocity (fw_spawner_aabb, what a culling host calls every frame): the ages are
+// written back, a deferred spin (ensure_spin) stays deferred.  Ages::write replays that too.
 enum class Then { nothing, sync, join, counts };
-enum class Ages { leave, write };
+enum class Ages { leave, ages, write };
 struct SpawnerCall {
     SpawnerHost *sp = nullptr;
     std::vector<uint32_t> c;  // per segment (Then::counts)
@@ -79,8 +81,8 @@ static bool begin_call(fw_ctx *ctx, fw_spawner h, SpawnerCall &r, Then then, Age
     if (!r.sp || !args_ok(*r.sp)) return r.st = FW_EINVAL, false;
     if (poll_device_error(ctx), r.sp->poisoned) return r.st = poisoned_status(ctx), false;
     hipSetDevice(ctx->device);
-    for (size_t t = 0; ages == Ages::write && t < r.sp->seg.size(); t++)
-        if ((r.st = ensure_ages(ctx, r.sp->seg[t]))) return false;
+    for (size_t t = 0; ages != Ages::leave && t < r.sp->seg.size(); t++)
+        if ((ages == Ages::write && (r.st = ensure_spin(ctx, r.sp->seg[t]))) || (r.st = ensure_ages(ctx, r.sp->seg[t]))) return false;
     r.st = then == Then::sync ? sync(ctx) : then == Then::join ? join_side(ctx) : then == Then::counts ? read_counts(ctx, r.c) : FW_OK;
     return !r.st || (then == Then::counts && r.st == FW_ECAPACITY);
 }
@@ -205,6 +207,10 @@ fw_status fw_ctx_create(int device, uint32_t seed, void *stream, fw_ctx **out) {
     if (const char *m = getenv("FW_NOSPIN")) ctx->use_nospin = atoi(m) != 0;
     if (const char *m = getenv("FW_AXIS_SPIN")) ctx->use_axis = atoi(m) != 0;
     if (const char *m = getenv("FW_AGELESS")) ctx->use_ageless = atoi(m) != 0;
+    if (const char *m = getenv("FW_SPIN_DEFER")) ctx->use_spin_defer = atoi(m) != 0;
+    if (const char *m = getenv("FW_SPIN_DEFER_MIN")) ctx->spin_defer_min = (uint32_t)strtoul(m, nullptr, 10);
+    if (const char *m = getenv("FW_SPIN_DEFER_AFTER")) ctx->spin_defer_after = (uint32_t)strtoul(m, nullptr, 10);
+    if (const char *m = getenv("FW_SPIN_LOG")) ctx->spin_log_cap = (uint32_t)strtoul(m, nullptr, 10);
     // 0: scale / colour planes always stored; 1: not stored for types with an attached instance buffer; 2 (default): for no type
     if (const char *m = getenv("FW_DERIVED")) ctx->use_derived = atoi(m) != 0, ctx->derive_all = atoi(m) >= 2;
     if (const char *m = getenv("FW_NEST_FUSE")) ctx->nest_fuse = atoi(m) != 0;
@@ -355,6 +361,8 @@ fw_status fw_spawner_update_settings(fw_ctx *ctx, fw_spawner h, const fw_spawner
             hipMemcpy(&s, ctx->d_emit_serial + e.emit_slot, sizeof s, hipMemcpyDeviceToHost);
         serials.push_back(s);
     }
+    // (no ensure_spin / ensure_ages here: the spawner's particles are dropped with its segments, and build_spawner starts every SegHost --
+    // its spin log and cohorts included -- from SegHost{}: nothing is left that a deferred spin could be replayed into)
     if ((st = release_spawner_segments(ctx, *sp))) return st;
     const bool finished_notified = sp->finished_notified;
     SpawnerHost keep = *sp;
@@ -703,7 +711,7 @@ fw_status fw_spawner_pack_instances(fw_ctx *ctx, fw_spawner h, uint32_t type, fw
 
 fw_status fw_spawner_aabb(fw_ctx *ctx, fw_spawner h, float out_min[3], float out_max[3], int32_t *any) {
     SpawnerCall call;  // (Then::join: the query kernels run on the main stream and may read rings)
-    if (!begin_call(ctx, h, call, Then::join, Ages::write, [&](const SpawnerHost &) { return out_min && out_max; })) return call.st;
+    if (!begin_call(ctx, h, call, Then::join, Ages::ages, [&](const SpawnerHost &) { return out_min && out_max; })) return call.st;
     const SpawnerHost *const sp = call.sp;
     if (!ctx->h_aabb)
         if (fw_status st = alloc_buf(ctx, ctx->h_aabb, 8, Mem::pinned)) return st;
@@ -925,6 +933,8 @@ fw_status fw_debug_update_path(fw_ctx *ctx, fw_spawner h, uint32_t type, int32_t
         if (S.fifo && S.axis != 0u) moved = 28u + 12u + 28u + (spins ? 8u : 0u) + (q3 ? 4u : 0u) + (T.scale.kind != 0 ? 4u : 0u) + colours;
         // (round 18, a FIFO ring whose latest launch ran under the age rule -- SegHost::ageless_last: the age plane moved neither way)
         if (S.fifo && S.ageless_last) moved -= 8u;
+        // (round 19, ... and deferred its spin -- SegHost::spin_last: of rotation and angular velocity nothing moved either way)
+        if (S.fifo && S.spin_last && S.axis != 0u) moved -= 12u + (spins ? 8u : 0u) + (q3 ? 4u : 0u);
         algo = moved;
         // (a range ring: the part of the list that may lose particles, a fifth of configs[2], is compacted in place and reads and
         // rewrites every plane it keeps, the 4-byte lifetime included: the figure is the young part's)
@@ -972,6 +982,12 @@ fw_status fw_debug_recovered_rings(fw_ctx *ctx, uint64_t *n) {
 fw_status fw_debug_age_launches(fw_ctx *ctx, uint64_t *n) {
     if (!ctx || !n) return FW_EINVAL;
     *n = ctx->age_launches;
+    return FW_OK;
+}
+// launches of fw_k_fifo_spin so far (ensure_spin: a ring whose spin was deferred had its log replayed)
+fw_status fw_debug_spin_launches(fw_ctx *ctx, uint64_t *n) {
+    if (!ctx || !n) return FW_EINVAL;
+    *n = ctx->spin_launches;
     return FW_OK;
 }
 fw_status fw_debug_tf_frames(fw_ctx *ctx, uint64_t *n) {

@@ -491,6 +491,23 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
             if (!ageless && (st = ensure_ages(ctx, si, fstream))) return st;
             if (ageless) S.ages_stale = true;
             S.ageless_last = ageless;
+            // the deferred spin (fw_device.h: FW_TYPE_IDX_NOSPIN with FW_TYPE_IDX_AXIS; fw_spin.h), per launch: everything the age rule asks,
+            // the axis rule in force for this dt (its proof makes the replay independent of who shares a wave), a positive normal dt (no
+            // cohort then takes a later frame's spawn in: its age is above +0), a ring large enough to be bound by bandwidth -- and one
+            // that has met all of this for spin_defer_after launches in a row without anybody asking for its planes.  Any other launch
+            // finds the true spin in the planes: replayed first, under the axis the log was written for (before S.axis is cleared).
+            const bool spin_ok = ageless && ctx->use_spin_defer && S.axis != 0u && axis_dt_ok(S, dt) && spin_dt_ok(dt) && n_in >= ctx->spin_defer_min &&
+                                 !(S.frame_spawn && !S.coh.empty() && S.coh.back().age == 0.0f);
+            const bool spin_defer = spin_ok && S.spin_streak >= ctx->spin_defer_after;
+            if (!spin_ok) {
+                if ((st = ensure_spin(ctx, si, fstream))) return st;
+            } else if (!spin_defer) {
+                S.spin_streak++;
+            } else if (fw_spin_full(S.spin.log.size(), std::max(1u, ctx->spin_log_cap)) && (st = ensure_spin(ctx, si, fstream, true))) {
+                return st;  // (the log at its cap: replayed, and the ring goes on deferring)
+            }
+            const uint64_t spin_from_new = spin_defer ? S.spin.defer(S.coh, dt) : S.spin.end();
+            S.spin_last = spin_defer;
             // the cohorts age by this dt exactly as their particles do (fp32 additions, fw_survives); the oldest die first
             if (S.fifo_dev) {
                 S.coh.push_back(SegHost::Cohort{0u, 0.0f, ctx->frame, false});  // size: whatever the device appends
@@ -498,7 +515,7 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
                 if (!S.coh.empty() && S.coh.back().age == 0.0f && !std::signbit(S.coh.back().age))
                     S.coh.back().n += S.frame_spawn;
                 else
-                    S.coh.push_back(SegHost::Cohort{S.frame_spawn, 0.0f, ctx->frame, true});
+                    S.coh.push_back(SegHost::Cohort{S.frame_spawn, 0.0f, ctx->frame, true, spin_from_new});
             }
             for (auto &c : S.coh) c.age = c.age + dt;
             uint32_t dead = 0;
@@ -509,12 +526,13 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
                 dead += c.n;
                 S.coh.pop_front();
             }
+            if (S.spin.stale) S.spin.trim(S.coh);  // (log entries only dead particles lacked: a particle that dies unread never has the work done)
             FwFifoSeg &F = fa.s[fa.n_segs++];
             F.buf = S.buf[0], F.destroyed = S.destroyed, F.inst = S.inst;
             F.inst_cap = S.inst_cap, F.capacity = S.capacity, F.seg = si;
             // (the axis-spin rule travels per launch: a frame whose dt voids its proof runs without it, and so does every frame after it)
             if (S.axis != 0u && !axis_dt_ok(S, dt)) S.axis = 0u;
-            F.type_idx = S.type_idx | (S.nospin ? FW_TYPE_IDX_NOSPIN : 0u) | (S.axis << FW_TYPE_IDX_AXIS_SHIFT) | (ageless ? FW_TYPE_IDX_AGELESS : 0u), F.life = S.fifo_life;
+            F.type_idx = S.type_idx | ((S.nospin || spin_defer) ? FW_TYPE_IDX_NOSPIN : 0u) | (S.axis << FW_TYPE_IDX_AXIS_SHIFT) | (ageless ? FW_TYPE_IDX_AGELESS : 0u), F.life = S.fifo_life;
             F.keys_off = S.keys_off, F.keys_len = S.keys_len;
             F.head = S.head, F.n_in = n_in, F.n_spawn = n_spawn, F.dead = dead;
             F.mat = mat ? 1u : 0u;

@@ -73,6 +73,55 @@ fw_status ensure_ages(fw_ctx *ctx, uint32_t si, hipStream_t stream) {
     return FW_OK;
 }
 
+// the deferred spin's per-frame condition on dt: a positive normal fp32 (after a frame of +0 the newest cohort would take the next
+// frame's spawn in, and one cohort would hold particles with different numbers of pending steps)
+bool spin_dt_ok(float dt) { return !std::signbit(dt) && std::isnormal(dt); }
+
+fw_status ensure_spin(fw_ctx *ctx, uint32_t si, hipStream_t stream, bool keep_streak) {
+    SegHost &S = ctx->segs[si];
+    if (!keep_streak) S.spin_streak = 0;
+    if (!S.spin.stale) return FW_OK;
+    fw_status st;
+    if (!stream) {
+        if ((st = join_side(ctx))) return st;
+        stream = ctx->stream;
+    }
+    // one entry per cohort that holds particles, then the log (fw_spin.h); a ring that was emptied since has nothing to replay
+    const size_t n_max = S.coh.size(), log_n = S.spin.log.size();
+    if (S.fifo && S.axis != 0u && n_max && log_n) {
+        if (ctx->spin_pending) {  // (the previous table may still be on its way to the device)
+            FW_HIP(ctx, hipStreamSynchronize(ctx->spin_busy));
+            ctx->spin_pending = false;
+        }
+        const size_t need = n_max * sizeof(FwSpinEntry) + log_n * sizeof(float);
+        if (need > ctx->spin_cap) {
+            const size_t cap = std::max<size_t>(need * 2, 16384);
+            ctx->spin_cap = 0;
+            if ((st = sync(ctx)) || (st = alloc_buf(ctx, ctx->h_spin, cap, Mem::pinned)) || (st = alloc_buf(ctx, ctx->d_spin, cap))) return st;
+            ctx->spin_cap = cap;
+        }
+        FwSpinEntry *tab = (FwSpinEntry *)ctx->h_spin.get();
+        uint64_t live = 0;
+        const uint32_t n = S.spin.table(S.coh, tab, &live);
+        if (live > S.capacity) return poison_segment(ctx, si, "a FIFO ring's cohorts hold more particles than the ring");
+        if (n) {
+            float *log = (float *)(tab + n);
+            for (size_t k = 0; k < log_n; k++) log[k] = S.spin.log[k];
+            const size_t bytes = n * sizeof(FwSpinEntry) + log_n * sizeof(float);
+            FW_HIP(ctx, hipMemcpyAsync(ctx->d_spin, tab, bytes, hipMemcpyHostToDevice, stream));
+            FW_HIP(ctx, fw_launch_fifo_spin(stream, S.buf[0], S.capacity, S.head, (uint32_t)live, ctx->d_types + S.type_idx, S.axis, ctx->d_spin, n,
+                                            (uint32_t)log_n));
+            ctx->spin_pending = true, ctx->spin_busy = stream;
+            ctx->spin_launches++;
+        }
+    } else if (S.fifo && S.axis == 0u && n_max && log_n) {
+        return poison_segment(ctx, si, "a FIFO ring with a deferred spin lost its axis");
+    }
+    S.spin.current(S.coh);
+    S.spin_last = false;
+    return FW_OK;
+}
+
 // grows the [2][max_seg] bookkeeping arrays and the snapshot ring: every new array is made (and filled) before any is installed --
 // the rows of the [2][max_seg] ones sit max_seg apart
 fw_status ensure_max_seg(fw_ctx *ctx, uint32_t need) {

@@ -10,6 +10,7 @@ fw_status realloc_segment(fw_ctx *ctx, uint32_t si, uint32_t ncap, bool make_gen
     SegHost &s = ctx->segs[si];
     ctx->fc_ok = false, ctx->boxes_epoch = 0;
     fw_status st = ensure_ages(ctx, si);  // (the copies below take the age plane as it is: the refresh waits for the kernel)
+    if (!st) st = ensure_spin(ctx, si);   // (... and rotation and angular velocity)
     if (!st) st = refresh_counts_exact(ctx);
     if (st) return st;
     if (s.fifo && ncap >= 0x40000000u) make_general = true;  // ring slots are computed in 32 bits: head + index < 2^32
@@ -124,6 +125,7 @@ bool nested_fed_wants_growth(const SegHost &S) {
 // continues as an ordinary segment
 fw_status fifo_to_general(fw_ctx *ctx, uint32_t si) {
     if (!ctx->segs[si].ring()) return FW_OK;
+    if (fw_status st = ensure_spin(ctx, si)) return st;  // (a deferred spin is replayed about the axis the next line gives up)
     ctx->segs[si].axis = 0u;  // (the axis-spin rule is the FIFO kernel's: void for good once the ring leaves it)
     return realloc_segment(ctx, si, ctx->segs[si].capacity, true);
 }
@@ -211,6 +213,7 @@ bool fifo_may_become_range(const fw_ctx *ctx, const SegHost &S) {
 fw_status fifo_to_range(fw_ctx *ctx, uint32_t si) {
     if (!fifo_may_become_range(ctx, ctx->segs[si])) return FW_OK;
     fw_status st = ensure_ages(ctx, si);  // (the range kernel reads every particle's age: written back first)
+    if (!st) st = ensure_spin(ctx, si);   // (... and its spin: replayed under the axis the next lines give up)
     if (st) return st;
     ctx->segs[si].ageless_last = false;
     st = refresh_counts_exact(ctx);  // (a ring that receives Nested children: only the device knows its count)
@@ -335,7 +338,8 @@ fw_status leave_nospin(fw_ctx *ctx, uint32_t si) {
 fw_status set_derived(fw_ctx *ctx, uint32_t si, bool on, bool refill) {
     SegHost &s = ctx->segs[si];
     if (s.derived == on) return FW_OK;
-    fw_status st = sync(ctx);
+    fw_status st = ensure_spin(ctx, si);  // (the rule asks for FW_TYPE_DERIVED: replayed before the type's record changes)
+    if (!st) st = sync(ctx);
     if (st) return st;
     if (!on && refill) {
         if ((st = ensure_ages(ctx, si))) return st;  // (scale and colours are functions of the age)

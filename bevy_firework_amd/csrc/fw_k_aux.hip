@@ -2,6 +2,7 @@
 // (gfx950 only; device helpers in fw_dev.h, launch interface in fw_kernels.h)
 #include "fw_dev.h"
 #include "fw_ages.h"
+#include "fw_spin.h"
 
 // ---------------------------------------------------------------------------------
 // readback / upload / render hand-off helpers
@@ -117,6 +118,46 @@ __global__ void fw_k_fifo_ages(char *buf, uint32_t C, uint32_t head, uint32_t li
 hipError_t fw_launch_fifo_ages(hipStream_t s, char *buf, uint32_t capacity, uint32_t head, uint32_t live, const void *d_table, uint32_t n) {
     if (!live || !n || live > capacity || head >= capacity) return hipSuccess;
     hipLaunchKernelGGL(fw_k_fifo_ages, dim3((live + 255) / 256), dim3(256), 0, s, buf, capacity, head, live, (const FwAgeEntry *)d_table, n);
+    return hipGetLastError();
+}
+
+// The spin of a FIFO ring whose launches deferred it (FW_TYPE_IDX_NOSPIN with FW_TYPE_IDX_AXIS, fw_device.h), replayed from the host's log:
+// logical particle li < live has had every update's spin step except those of log entries [from, log_n) (fw_spin.h: per cohort).  One
+// load of the three planes the axis rule moves, fw_spin_step once per pending dt -- the statements and the registers of the update
+// that skipped it: the axis' own component and the rotation's w loaded, +0 everywhere else --, one store.  Every logged dt passed
+// axis_dt_ok: each lane takes fw_quat_step's polynomial arm whoever shares its wave (axis_spin_rule, fw_engine_build.cpp), so the
+// grouping of lanes, which differs from the update's, changes no bit.  (The update stores a plane only where a bit of it changed in
+// some lane of the wave; storing the same values unconditionally leaves the same planes.)
+// (T.angacc is +0 / 0 in every ring that reaches this kernel: axis_spin_rule's C3 refuses a type with an angular acceleration, along the
+// axis included, so the replay of an ACCELERATING ring is not a tested path -- whoever relaxes C3 has to add that test.)
+__global__ void fw_k_fifo_spin(char *buf, uint32_t C, uint32_t head, uint32_t live, const FwType *type, uint32_t axis, const FwSpinEntry *tab,
+                               uint32_t n, uint32_t log_n) {
+    const uint32_t li = blockIdx.x * blockDim.x + threadIdx.x;
+    const float *log = reinterpret_cast<const float *>(tab + n);
+    uint32_t from = 0;
+    const uint32_t steps = fw_spin_steps(tab, n, live, log_n, li, &from);
+    if (!steps) return;
+    const FwType T = *type;
+    const uint32_t s = fw_ring_slot(head, li, C), k = axis - 1u;
+    char *p2 = buf + FW_OFF_Q2(C), *p3 = buf + FW_OFF_Q3(C);
+    const size_t cp = FW_CP(C);
+    const float rk = fw_ld1(p2 + k * cp, s), wk = fw_ld1(p3 + k * cp, s);
+    float4 q2 = make_float4(k == 0u ? rk : 0.0f, k == 1u ? rk : 0.0f, k == 2u ? rk : 0.0f, fw_ld1(p2 + 3 * cp, s));
+    float4 q3 = make_float4(k == 0u ? wk : 0.0f, k == 1u ? wk : 0.0f, k == 2u ? wk : 0.0f, 0.0f);
+    for (uint32_t e = from; e < log_n; e++) {
+        const FwSpin sp = fw_spin_step(T, log[e], q2, q3);
+        q2 = make_float4(sp.rot.x, sp.rot.y, sp.rot.z, sp.rot.w), q3 = make_float4(sp.wx, sp.wy, sp.wz, 0.0f);
+    }
+    fw_st1(p2 + k * cp, s, k == 0u ? q2.x : k == 1u ? q2.y : q2.z);
+    fw_st1(p2 + 3 * cp, s, q2.w);
+    fw_st1(p3 + k * cp, s, k == 0u ? q3.x : k == 1u ? q3.y : q3.z);
+}
+hipError_t fw_launch_fifo_spin(hipStream_t s, char *buf, uint32_t capacity, uint32_t head, uint32_t live, const FwType *type, uint32_t axis,
+                               const void *d_table, uint32_t n, uint32_t log_n) {
+    if (live > capacity || (capacity && head >= capacity) || axis < 1u || axis > 3u || !type) return hipErrorInvalidValue;  // (never a silent skip)
+    if (!live || !n || !log_n) return hipSuccess;  // nothing pending
+    hipLaunchKernelGGL(fw_k_fifo_spin, dim3((live + 255) / 256), dim3(256), 0, s, buf, capacity, head, live, type, axis, (const FwSpinEntry *)d_table, n,
+                       log_n);
     return hipGetLastError();
 }
 

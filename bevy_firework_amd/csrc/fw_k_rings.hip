@@ -358,7 +358,16 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
         if (a.live_next) *a.live_next = 0ull;
         if (a.done_tag) *a.done_tag = a.done_value;
     }
-    const FwType T = g.types[F.type_idx & FW_TYPE_IDX_MASK];
+    FwType T = g.types[F.type_idx & FW_TYPE_IDX_MASK];
+    // (round 19: a ring whose spin this launch defers -- FW_TYPE_IDX_NOSPIN together with an axis, fw_device.h -- is a ring that cannot
+    // turn to the tiles of the particles that were here before: nothing of Q2 / Q3 loaded above, and with the flag in the workgroup's
+    // copy of the type record neither the window nor fw_integrate_store evaluates or stores any of it.  The spawning workgroups keep the
+    // true record: a new particle gets its one update whole, every plane stored.  Workgroup-uniform, a scalar OR -- compiled into the
+    // launches of rings with Q0 in planes alone, the only ones the rule is ever set for (it asks for the age rule): the colliding, the
+    // instance-writing float4 and the Nested instantiations keep the parent's code, which the branch cost the Nested one 4.7 % of its time.)
+    if constexpr (Q0PL) {
+        if (!spawner && nospin && axis != 0u) T.flags |= FW_TYPE_NOSPIN;
+    }
     const FwCollArm CA = fw_coll_arm<COLL>(g, F.type_idx & FW_TYPE_IDX_MASK);
     if (tid < F.keys_len) s_keys[tid] = key0;
     for (uint32_t i = tid + BLK; i < F.keys_len; i += BLK) s_keys[i] = g.keys[F.keys_off + i];

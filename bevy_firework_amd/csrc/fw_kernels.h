@@ -392,6 +392,10 @@ hipError_t fw_launch_gather(hipStream_t s, const FwSegView &v, uint32_t n, int32
 hipError_t fw_launch_rederive(hipStream_t s, const FwSegView &v);
 // the age plane of a FIFO ring from its cohort table (fw_ages.h: n FwAgeEntry records in device memory), for logical particles [0, live)
 hipError_t fw_launch_fifo_ages(hipStream_t s, char *buf, uint32_t capacity, uint32_t head, uint32_t live, const void *d_table, uint32_t n);
+// the deferred spin of a FIFO ring replayed (fw_spin.h: n FwSpinEntry records, then log_n fp32 dt values, in device memory), for logical
+// particles [0, live): rotation component axis - 1, rotation w and angular-velocity component axis - 1 of every particle with pending steps
+hipError_t fw_launch_fifo_spin(hipStream_t s, char *buf, uint32_t capacity, uint32_t head, uint32_t live, const FwType *type, uint32_t axis,
+                               const void *d_table, uint32_t n, uint32_t log_n);
 hipError_t fw_launch_fill_plane1(hipStream_t s, char *buf0, char *buf1, size_t plane_off, uint32_t capacity, float v);
 // A type leaves FW_TYPE_NOSPIN, in one (buf1 == nullptr) or both buffers of its segment: Q3 = {0, 0, 0, lifetime} again, and the
 // rotation plane, which nobody maintained, filled with the type's one rotation.  cpl, life_plane, life_const: as in FwSegView

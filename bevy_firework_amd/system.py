@@ -501,6 +501,12 @@ class ParticleSystem:
         self._check(self._lib.fw_debug_age_launches(self._ctx, C.byref(n)))
         return int(n.value)
 
+    def spin_launches(self) -> int:
+        """launches of fw_k_fifo_spin so far: a FIFO ring whose spin was deferred had its log of frames replayed for a reader"""
+        n = C.c_uint64()
+        self._check(self._lib.fw_debug_spin_launches(self._ctx, C.byref(n)))
+        return int(n.value)
+
     def recovered_rings(self) -> int:
         """rings moved to the compacting path (particles kept) because a cohort report was missing when it was due"""
         n = C.c_uint64()

@@ -68,6 +68,11 @@ fw_status fw_debug_tf_frames(fw_ctx *ctx, uint64_t *n);
  * asks for counts */
 fw_status fw_debug_age_launches(fw_ctx *ctx, uint64_t *n);
 
+/* *n = launches of the kernel that replays the deferred spin of a FIFO ring (fw_k_fifo_spin) so far: one per call that reads or copies
+ * the particles of a ring whose latest frames left rotation and angular velocity alone, none for
+ * fw_spawner_aabb or a call that only asks for counts */
+fw_status fw_debug_spin_launches(fw_ctx *ctx, uint64_t *n);
+
 /* *on = 1: the context keeps the per-frame records of its range launches and its small op tables in DEVICE memory that the host writes
  * through the large BAR; 0: in pinned host memory (the platform does not map device memory for the host, or
  * FW_PARAM_BAR=0) */
