@@ -102,6 +102,18 @@ class PathResult(C.Structure):
                 ("kind", C.c_int32), ("index", C.c_uint32), ("triangle", C.c_uint32), ("n_contacts", C.c_uint32)]
 
 
+class SortView(C.Structure):
+    _fields_ = [("eye", C.c_float * 3), ("order", C.c_uint32), ("forward", C.c_float * 3), ("reserved", C.c_uint32)]
+
+
+def make_sort_view(view):
+    d = SortView()
+    d.eye[:] = [float(x) for x in view.eye]
+    d.forward[:] = [float(x) for x in view.forward]
+    d.order, d.reserved = int(view.order) & 0xFFFFFFFF, int(view.reserved) & 0xFFFFFFFF
+    return d
+
+
 def fill_collision(d, cs):
     d.enabled = 1 if cs is not None else 0
     if cs is not None:
@@ -316,6 +328,9 @@ SYMBOLS = [
     ("fw_spawner_attach_instances", C.c_int, [_P, C.c_int32, C.c_uint32, _P, C.c_uint64]),
     ("fw_spawner_attach_instances_window", C.c_int, [_P, C.c_int32, C.c_uint32, _P, C.c_uint64]),
     ("fw_spawner_instance_window", C.c_int, [_P, C.c_int32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("fw_ctx_depth_order_device", C.c_int, [_P, C.c_int32, C.c_uint32, C.POINTER(SortView), _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("fw_ctx_pack_instances_sorted_device", C.c_int, [_P, C.c_int32, C.c_uint32, C.POINTER(SortView), _P, C.c_uint64, C.POINTER(C.c_uint64)]),
+    ("fw_ctx_pack_instances_sorted", C.c_int, [_P, C.c_int32, C.c_uint32, C.POINTER(SortView), _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("fw_spawner_aabb", C.c_int, [_P, C.c_int32, _F3, _F3, C.POINTER(C.c_int32)]),
     ("fw_ctx_track_aabbs", C.c_int, [_P, C.c_int32]),
     ("fw_ctx_live_count", C.c_int, [_P, C.POINTER(C.c_uint64)]),

@@ -22,7 +22,7 @@
 //   fw_engine_step.cpp   fw_step and the plan of a frame: mode exits, lifetime windows, emission clocks, ring-op routing, the
 //                        tile table -- everything that can still be rolled back
 //   fw_engine_launch.cpp the enqueue of a planned frame (FwFrame): op tables, cohort replay, every launch, the frame's bookkeeping
-//   fw_engine_api.cpp    every other entry point of include/firework_hip.h (+ the debug hooks)
+//   fw_engine_api.cpp    every other entry point of include/firework_hip.h (+ the debug hooks), the depth-sorted records among them
 //   fw_engine_mesh.cpp   the collider meshes: fw_ctx_create_mesh / fw_ctx_create_deformable_mesh / fw_ctx_update_mesh_vertices /
 //                        fw_ctx_destroy_mesh / fw_ctx_set_mesh_colliders (the
 //                        hierarchy itself is built by fw_bvh.cpp, plain C++)
@@ -51,6 +51,7 @@
 #include "fw_math.h"
 #include "fw_ages.h"
 #include "fw_spin.h"
+#include "fw_sort.h"
 
 namespace fwh {
 
@@ -630,6 +631,9 @@ struct fw_ctx {
     // only ever grows, instead of a hipMalloc + hipFree pair per call (each a device-wide synchronisation and an address-
     // space change; profiles/r02/shared_gpu.txt)
     HipBuf<char> d_stage;
+    // scratch of the depth sort (fw_ctx_depth_order_device, fw_ctx_pack_instances_sorted[_device]; fw_sort.h: fw_sort_scratch_words): two
+    // (key, idx) pairs and the histogram table, laid out per call; only ever grows, and growing is the one case in which those calls wait
+    HipBuf<uint32_t> d_sort;
     bool seg_kind_changed = false;       // a ring left its mode inside the current fw_step (realloc_segment)
     bool derive_ready_any = false;       // some SegHost::derive_ready is set
     // undo log of fw_step's host half: spawn_particles is all-or-nothing per frame in the reference, so a frame that

@@ -709,6 +709,71 @@ fw_status fw_spawner_pack_instances(fw_ctx *ctx, fw_spawner h, uint32_t type, fw
     return st2 ? st2 : r.st;
 }
 
+// ---- depth-sorted records (firework_hip.h: DEPTH-SORTED INSTANCES; fw_sort.h, fw_k_sort.hip)
+static_assert(sizeof(fw_sort_view) == 32 && sizeof(FwSortView) == sizeof(fw_sort_view), "fw_sort_view: 32 bytes, mirrored by FwSortView");
+static bool sort_view_ok(const fw_sort_view *view) { return view && view->order <= FW_SORT_FRONT_TO_BACK && view->reserved == 0u; }
+
+// The two device forms: fw_spawner_pack_instances_device's prologue, then keys -> sort -> (records: the gather; order: the sorted
+// indices straight into d_out), all on the context's stream.  An order reads positions only, which no launch defers: Ages::leave.
+static fw_status sorted_device(fw_ctx *ctx, fw_spawner h, uint32_t type, const fw_sort_view *view, void *d_out, uint64_t cap, uint64_t *n_upper_bound,
+                               bool records) {
+    SpawnerCall r;
+    if (!begin_call(ctx, h, r, Then::nothing, records ? Ages::write : Ages::leave,
+                    [&](const SpawnerHost &sp) { return type < sp.seg.size() && d_out && sort_view_ok(view); }))
+        return r.st;
+    const uint32_t si = r.sp->seg[type];
+    const SegHost &S = ctx->segs[si];
+    const uint32_t ub = (uint32_t)std::min<uint64_t>(S.nested_fed ? S.capacity : std::min(S.ub, S.capacity), cap);
+    const size_t words = fw_sort_scratch_words(ub);
+    if (words > ctx->d_sort.cap()) {  // more than any call before: the one case that waits (launches in flight may use the old scratch)
+        fw_status st;
+        if ((st = sync(ctx)) || (st = alloc_buf(ctx, ctx->d_sort, (words + words / 4 + 16383u) & ~(size_t)16383u))) return st;
+    }
+    if (n_upper_bound) *n_upper_bound = ub;
+    if (S.fifo || S.small) {  // (whose launches may run on the ring stream)
+        fw_status jst = join_side(ctx);
+        if (jst) return jst;
+    }
+    FwSortView sv;
+    memcpy(&sv, view, sizeof sv);
+    const FwSegView v = seg_view(ctx, si, ctx->parity);
+    uint32_t *const scratch = ctx->d_sort;
+    // (no synchronisation: every launch reads the count -- and a range ring's old part -- from the device)
+    FW_HIP(ctx, fw_launch_depth_keys(ctx->stream, v, count_slot(ctx, si), ub, sv, scratch, scratch + ub));
+    FW_HIP(ctx, fw_launch_sort_pairs(ctx->stream, count_slot(ctx, si), ub, scratch, records ? nullptr : (uint32_t *)d_out));
+    if (records) FW_HIP(ctx, fw_launch_pack_instances_sorted(ctx->stream, v, count_slot(ctx, si), ub, scratch + ub, d_out));
+    return FW_OK;
+}
+
+fw_status fw_ctx_depth_order_device(fw_ctx *ctx, fw_spawner h, uint32_t type, const fw_sort_view *view, void *d_order, uint64_t cap,
+                                    uint64_t *n_upper_bound) {
+    return sorted_device(ctx, h, type, view, d_order, cap, n_upper_bound, false);
+}
+
+fw_status fw_ctx_pack_instances_sorted_device(fw_ctx *ctx, fw_spawner h, uint32_t type, const fw_sort_view *view, void *d_out, uint64_t cap,
+                                              uint64_t *n_upper_bound) {
+    return sorted_device(ctx, h, type, view, d_out, cap, n_upper_bound, true);
+}
+
+fw_status fw_ctx_pack_instances_sorted(fw_ctx *ctx, fw_spawner h, uint32_t type, const fw_sort_view *view, fw_particle_instance *out, uint64_t cap,
+                                       uint64_t *n_out) {
+    SpawnerCall r;
+    if (!begin_call(ctx, h, r, Then::counts, Ages::write, [&](const SpawnerHost &sp) { return type < sp.seg.size() && sort_view_ok(view); })) return r.st;
+    const uint32_t n = r.c[r.sp->seg[type]];
+    if (n_out) *n_out = n;
+    const uint64_t m = std::min<uint64_t>(n, cap);
+    if (!m || !out) return r.st;
+    void *tmp = nullptr;
+    fw_status st = stage_buffer(ctx, m * sizeof(fw_particle_instance), &tmp);
+    if (st) return st;
+    uint64_t ub = 0;
+    if ((st = sorted_device(ctx, h, type, view, tmp, m, &ub, true))) return st;
+    hipError_t e = hipMemcpyAsync(out, tmp, m * sizeof(fw_particle_instance), hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    FW_HIP(ctx, e);
+    return r.st;
+}
+
 fw_status fw_spawner_aabb(fw_ctx *ctx, fw_spawner h, float out_min[3], float out_max[3], int32_t *any) {
     SpawnerCall call;  // (Then::join: the query kernels run on the main stream and may read rings)
     if (!begin_call(ctx, h, call, Then::join, Ages::ages, [&](const SpawnerHost &) { return out_min && out_max; })) return call.st;

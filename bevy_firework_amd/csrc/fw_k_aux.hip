@@ -1,8 +1,9 @@
-// fw_k_aux.hip -- readback / upload (AoS <-> planes), plane fills, render hand-off (fw_k_pack), AABB queries, live totals, the copy-bandwidth probe
+// fw_k_aux.hip -- readback / upload (AoS <-> planes), plane fills, render hand-off (fw_k_pack, fw_k_depth_keys), AABB queries, live totals, the copy-bandwidth probe
 // (gfx950 only; device helpers in fw_dev.h, launch interface in fw_kernels.h)
 #include "fw_dev.h"
 #include "fw_ages.h"
 #include "fw_spin.h"
+#include "fw_sort.h"
 
 // ---------------------------------------------------------------------------------
 // readback / upload / render hand-off helpers
@@ -193,13 +194,18 @@ __global__ void fw_k_restore_q3(FwSegView v, char *buf1) {
 // SoA planes -> ParticleInstance records (render.rs:95-115).  Loads are plane-wise coalesced; the 64-byte records are
 // transposed through LDS so that every store instruction of a wave writes 1 KiB of consecutive bytes (a lane writing
 // its own record with four float4 stores would touch 64 lines a quarter at a time).
-__global__ __launch_bounds__(256) void fw_k_pack(FwSegView v, const uint32_t *d_count, uint32_t n_upper, float4 *out) {
+// SORTED (depth-sorted records, fw_sort.h): record j is that of list particle order[j] -- the indices the sort of fw_k_sort.hip left,
+// each below n (clamped all the same: no address depends on trusting them) -- instead of list particle j; everything else is the same
+// statements.
+template <bool SORTED>
+__global__ __launch_bounds__(256) void fw_k_pack(FwSegView v, const uint32_t *d_count, uint32_t n_upper, const uint32_t *order, float4 *out) {
     __shared__ float4 s_rec[256 * 4];
     const uint32_t head = fw_view_head(v);
     const uint32_t n = min(*d_count, n_upper);
     const uint32_t tid = threadIdx.x;
     for (uint32_t b = blockIdx.x * 256u; b < n; b += gridDim.x * 256u) {
-        const uint32_t i = fw_view_slot(v, head, min(b + tid, n - 1u));
+        const uint32_t j = min(b + tid, n - 1u);
+        const uint32_t i = fw_view_slot(v, head, SORTED ? min(order[j], n - 1u) : j);
         const float4 q0 = fw_view_q0(v, i), q2 = fw_view_rot(v, i);
         float4 q5, q6;
         float sc;
@@ -216,6 +222,17 @@ __global__ __launch_bounds__(256) void fw_k_pack(FwSegView v, const uint32_t *d_
             if (e < cnt4) out[(size_t)b * 4 + e] = s_rec[e];
         }
         __syncthreads();
+    }
+}
+
+// The sort key of every particle of the first min(*d_count, n_upper) of a segment (fw_sort.h: view depth of the position the pack writes
+// into its record, mapped to 32 bits that sort ascending) and the particle's own list index beside it: what fw_k_sort.hip orders.
+__global__ __launch_bounds__(256) void fw_k_depth_keys(FwSegView v, const uint32_t *d_count, uint32_t n_upper, FwSortView sv, uint32_t *key, uint32_t *idx) {
+    const uint32_t head = fw_view_head(v);
+    const uint32_t n = min(*d_count, n_upper);
+    for (uint32_t li = blockIdx.x * 256u + threadIdx.x; li < n; li += gridDim.x * 256u) {
+        const float4 q0 = fw_view_q0(v, fw_view_slot(v, head, li));
+        key[li] = fw_sort_key(q0.x, q0.y, q0.z, sv), idx[li] = li;
     }
 }
 
@@ -410,7 +427,22 @@ hipError_t fw_launch_pack_instances(hipStream_t s, const FwSegView &v, const uin
     if (!n_upper) return hipSuccess;
     uint32_t blocks = (n_upper + 255) / 256;
     if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(fw_k_pack, dim3(blocks), dim3(256), 0, s, v, d_count, n_upper, (float4 *)d_out);
+    hipLaunchKernelGGL(fw_k_pack<false>, dim3(blocks), dim3(256), 0, s, v, d_count, n_upper, (const uint32_t *)nullptr, (float4 *)d_out);
+    return hipGetLastError();
+}
+
+hipError_t fw_launch_depth_keys(hipStream_t s, const FwSegView &v, const uint32_t *d_count, uint32_t n_upper, const FwSortView &sv, uint32_t *d_key,
+                                uint32_t *d_idx) {
+    if (!n_upper) return hipSuccess;
+    hipLaunchKernelGGL(fw_k_depth_keys, dim3(std::min((n_upper + 255u) / 256u, 8192u)), dim3(256), 0, s, v, d_count, n_upper, sv, d_key, d_idx);
+    return hipGetLastError();
+}
+
+hipError_t fw_launch_pack_instances_sorted(hipStream_t s, const FwSegView &v, const uint32_t *d_count, uint32_t n_upper, const uint32_t *d_order,
+                                           void *d_out) {
+    if (!n_upper) return hipSuccess;
+    if (!d_order) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(fw_k_pack<true>, dim3(std::min((n_upper + 255u) / 256u, 8192u)), dim3(256), 0, s, v, d_count, n_upper, d_order, (float4 *)d_out);
     return hipGetLastError();
 }
 

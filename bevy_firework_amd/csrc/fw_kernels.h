@@ -1,5 +1,5 @@
 // fw_kernels.h -- launch interface between the host engine (fw_engine.h, fw_engine_*.cpp) and the
-// gfx950 kernels (fw_k_general.hip, fw_k_rings.hip, fw_k_nested.hip, fw_k_aux.hip, fw_k_refit.hip, fw_k_query.hip; shared device
+// gfx950 kernels (fw_k_general.hip, fw_k_rings.hip, fw_k_nested.hip, fw_k_aux.hip, fw_k_refit.hip, fw_k_query.hip, fw_k_sort.hip; shared device
 // helpers: fw_dev.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -407,6 +407,18 @@ hipError_t fw_launch_scatter(hipStream_t s, char *buf, uint32_t capacity, uint32
 hipError_t fw_launch_fill_colors(hipStream_t s, char *buf0, char *buf1, uint32_t capacity, const float bc[4], const float em[4]);
 // ParticleInstance records of the first min(*d_count, n_upper) particles of a segment (the count is the device's: no synchronisation)
 hipError_t fw_launch_pack_instances(hipStream_t s, const FwSegView &v, const uint32_t *d_count, uint32_t n_upper, void *d_out);
+// Depth-sorted records (fw_sort.h; the sort itself: fw_k_sort.hip).  All three take n = min(*d_count, n_upper) from the device.
+//   keys:   d_key[li] = sort key of list particle li under `sv`, d_idx[li] = li, for li < n
+//   sort:   the n pairs at the start of `scratch` (keys at [0, n_upper), indices at [n_upper, 2 * n_upper); fw_sort_scratch_words(n_upper)
+//           words in all) sorted by ascending key, ties in incoming order; the sorted indices end at scratch + n_upper or, d_idx_out
+//           not null, there instead (n entries; nothing at or beyond n is written)
+//   pack:   as fw_launch_pack_instances, record j that of list particle d_order[j]
+struct FwSortView;
+hipError_t fw_launch_depth_keys(hipStream_t s, const FwSegView &v, const uint32_t *d_count, uint32_t n_upper, const FwSortView &sv, uint32_t *d_key,
+                                uint32_t *d_idx);
+hipError_t fw_launch_sort_pairs(hipStream_t s, const uint32_t *d_count, uint32_t n_upper, uint32_t *scratch, uint32_t *d_idx_out);
+hipError_t fw_launch_pack_instances_sorted(hipStream_t s, const FwSegView &v, const uint32_t *d_count, uint32_t n_upper, const uint32_t *d_order,
+                                           void *d_out);
 // box of position -/+ scale over up to eight segments: seg_ids, views: host arrays of n_segs (views[i] for buffer `parity` of
 // seg_ids[i]); d_part: device scratch of 256 * 8 floats; h_out8: PINNED host {min.xyz, any, max.xyz, -}
 hipError_t fw_launch_aabb(hipStream_t s, const FwGlobals &g, const uint32_t *seg_ids, const FwSegView *views, uint32_t n_segs,

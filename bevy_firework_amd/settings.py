@@ -419,6 +419,21 @@ INSTANCE_DTYPE = np.dtype(
 )
 assert INSTANCE_DTYPE.itemsize == 64
 
+# fw_sort_view (include/firework_hip.h: DEPTH-SORTED INSTANCES): the camera SpawnerData.instances_sorted sorts for
+SORT_BACK_TO_FRONT, SORT_FRONT_TO_BACK = 0, 1
+
+
+@dataclass
+class SortView:
+    """fw_sort_view: depth = (position - eye) . forward in fp32 (forward used as given, not normalised); `order` says which end is drawn
+    first (SORT_*; back to front is what an alpha-blended draw wants); reserved must be 0."""
+
+    eye: Vec3 = (0.0, 0.0, 0.0)
+    forward: Vec3 = (0.0, 0.0, -1.0)
+    order: int = SORT_BACK_TO_FRONT
+    reserved: int = 0
+
+
 # fw_ray / fw_ray_hit (include/firework_hip.h): the records of ParticleSystem.cast_rays
 RAY_DTYPE = np.dtype(
     [

@@ -129,6 +129,18 @@ class SpawnerData:
                                                          n.value, C.byref(n)))
         return out
 
+    def instances_sorted(self, view: S.SortView, particle_type: int = 0) -> np.ndarray:
+        """``instances()`` sorted by view depth for an alpha-blended draw (include/firework_hip.h: DEPTH-SORTED INSTANCES): the same
+        records, byte for byte, in ascending key order of ``view``, ties in particle-list order.  Synchronises."""
+        n = C.c_uint64()
+        L, ctx, v = self._sys._lib, self._sys._ctx, _ffi.make_sort_view(view)
+        self._sys._check(L.fw_ctx_pack_instances_sorted(ctx, self.handle, particle_type, C.byref(v), None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=S.INSTANCE_DTYPE)
+        if n.value:
+            self._sys._check(L.fw_ctx_pack_instances_sorted(ctx, self.handle, particle_type, C.byref(v), out.ctypes.data_as(C.c_void_p),
+                                                            n.value, C.byref(n)))
+        return out
+
     def attach_instances(self, device_ptr: int, capacity: int, particle_type: int = 0) -> None:
         """From the next step on the update kernel also writes this type's ParticleInstance records (render.rs:95-115)
         into the caller's device buffer (`capacity` 64-byte records); 0 detaches."""
@@ -356,6 +368,25 @@ class ParticleSystem:
         self._check(self._lib.fw_ctx_trace_paths_device(self._ctx, C.byref(_ffi.make_path_settings(settings)), C.c_void_p(int(paths_ptr)) if paths_ptr else None,
                                                         int(n), C.c_void_p(int(out_ptr)) if out_ptr else None,
                                                         C.c_void_p(int(samples_ptr)) if samples_ptr else None))
+
+    def pack_instances_sorted_device(self, data: SpawnerData, view: S.SortView, out_ptr: int, capacity: int, particle_type: int = 0) -> int:
+        """The depth-sorted ParticleInstance records of (data, particle_type) into `capacity` 64-byte records at device address out_ptr:
+        the first min(count, capacity) particles of the list, sorted among themselves (SpawnerData.instances_sorted has the order).
+        Enqueued on this context's stream; never synchronises, except once when the sort's scratch has to grow.  -> the host's upper
+        bound of the number of records written (the count itself is the device's)."""
+        ub = C.c_uint64()
+        self._check(self._lib.fw_ctx_pack_instances_sorted_device(self._ctx, data.handle, int(particle_type), C.byref(_ffi.make_sort_view(view)),
+                                                                  C.c_void_p(int(out_ptr)) if out_ptr else None, int(capacity), C.byref(ub)))
+        return int(ub.value)
+
+    def depth_order_device(self, data: SpawnerData, view: S.SortView, order_ptr: int, capacity: int, particle_type: int = 0) -> int:
+        """The permutation alone: order[j] (uint32 at device address order_ptr, `capacity` entries) = list index of the particle drawn
+        j-th -- for a host that draws fused records (attach_instances) through an index.  Same stream rule and return value as
+        pack_instances_sorted_device."""
+        ub = C.c_uint64()
+        self._check(self._lib.fw_ctx_depth_order_device(self._ctx, data.handle, int(particle_type), C.byref(_ffi.make_sort_view(view)),
+                                                        C.c_void_p(int(order_ptr)) if order_ptr else None, int(capacity), C.byref(ub)))
+        return int(ub.value)
 
     # -- ECS-like surface ------------------------------------------------------------------------
     def spawn(self, spawner: S.ParticleSpawner, transform: Optional[S.Transform] = None,

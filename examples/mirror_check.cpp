@@ -12,7 +12,8 @@
 // another -- a fixed small world (one collider of each kind plus one mesh instance), a fixed list of points projected onto it
 // (project_points, and project_points_device through device buffers of its own), every field's bits printed per point
 // (tests/test_cpp_host_project.py); `paths` another -- the same world, a fixed list of hypothetical particles traced through it
-// (trace_paths, trace_paths_device), every field's bits printed per path (tests/test_cpp_host_paths.py).  Prints, every tenth frame, the live counts and an
+// (trace_paths, trace_paths_device), every field's bits printed per path (tests/test_cpp_host_paths.py); `sorted` another -- one spawner whose
+// instance records are sorted by view depth every tenth frame through all three forms (tests/test_cpp_host_sorted.py).  Prints, every tenth frame, the live counts and an
 // FNV-1a digest of every particle record; tests/test_cpp_host.py runs the same scenario through the Python mirror and
 // expects the same lines: both mirrors marshal the reference's settings into the C ABI the same way.
 //
@@ -193,7 +194,67 @@ static int paths_scenario() {
     return 0;
 }
 
+// `mirror_check sorted`: one spawner (a sphere of sparks under gravity and drag), and every tenth frame its instance records sorted by
+// view depth in both orders through all three forms (instances_sorted; pack_instances_sorted_device and depth_order_device through
+// device buffers of its own): one line per frame and order with the digest of each
+static int sorted_scenario() {
+    try {
+        ParticleSystemPlugin app(0, /*seed*/ 0x00C0FFEE);
+        ParticleSpawner sp;
+        sp.particle_settings.resize(1);
+        sp.particle_settings[0].lifetime = RandF32::constant(0.75f);
+        sp.particle_settings[0].linear_drag = 0.125f;
+        sp.emission_settings.resize(1);
+        {
+            EmissionSettings &e = sp.emission_settings[0];
+            e.particle_index = 0;
+            e.emission_pacing = EmissionPacing::rate(2000.0f);
+            e.emission_shape = EmissionShape::Sphere(0.75f);
+            e.initial_velocity = {{1.0f, 6.0f}, {0.0f, 1.0f, 0.0f}, 0.5f};
+        }
+        ParticleSpawnerData *d = app.spawn(sp, Transform{{0.25f, 3.0f, 0.125f}, {}}, 7u);
+        const uint64_t cap = 4096;
+        void *d_rec = nullptr, *d_ord = nullptr;
+        if (hipMalloc(&d_rec, cap * sizeof(fw_particle_instance)) != hipSuccess || hipMalloc(&d_ord, cap * sizeof(uint32_t)) != hipSuccess)
+            throw Error(FW_EHIP, "hipMalloc");
+        hipStream_t st = (hipStream_t)app.stream();
+        const float dt = 1.0f / 60.0f;
+        for (int fr = 0; fr < 40; fr++) {
+            app.update(dt);
+            if (fr % 10 != 9) continue;
+            const auto unsorted = d->instances(0);
+            for (uint32_t order : {(uint32_t)FW_SORT_BACK_TO_FRONT, (uint32_t)FW_SORT_FRONT_TO_BACK}) {
+                fw_sort_view view{};
+                view.eye[0] = 0.25f, view.eye[1] = 3.5f, view.eye[2] = 0.125f;
+                view.forward[0] = 0.5f, view.forward[1] = -0.25f, view.forward[2] = 1.0f;
+                view.order = order;
+                const auto host = d->instances_sorted(view, 0);
+                const uint64_t ub_r = app.pack_instances_sorted_device(*d, view, d_rec, cap);
+                const uint64_t ub_o = app.depth_order_device(*d, view, d_ord, cap);
+                std::vector<fw_particle_instance> rec(host.size());
+                std::vector<uint32_t> ord(host.size());
+                if (host.size() > cap || ub_r < host.size() || ub_o < host.size()) throw Error(FW_EHIP, "bound below the count");
+                if (hipMemcpyAsync(rec.data(), d_rec, rec.size() * sizeof(fw_particle_instance), hipMemcpyDeviceToHost, st) != hipSuccess ||
+                    hipMemcpyAsync(ord.data(), d_ord, ord.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st) != hipSuccess)
+                    throw Error(FW_EHIP, "hipMemcpyAsync");
+                app.synchronize();
+                std::printf("frame %d order %u count %zu unsorted %016llx host %016llx device %016llx index %016llx\n", fr, order, host.size(),
+                            (unsigned long long)fnv(unsorted.data(), unsorted.size() * sizeof(fw_particle_instance)),
+                            (unsigned long long)fnv(host.data(), host.size() * sizeof(fw_particle_instance)),
+                            (unsigned long long)fnv(rec.data(), rec.size() * sizeof(fw_particle_instance)),
+                            (unsigned long long)fnv(ord.data(), ord.size() * sizeof(uint32_t)));
+            }
+        }
+        (void)hipFree(d_rec), (void)hipFree(d_ord);
+    } catch (const Error &e) {
+        std::fprintf(stderr, "firework error %d: %s\n", (int)e.status, e.what());
+        return 1;
+    }
+    return 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc > 1 && std::strcmp(argv[1], "sorted") == 0) return sorted_scenario();
     if (argc > 1 && std::strcmp(argv[1], "project") == 0) return project_scenario();
     if (argc > 1 && std::strcmp(argv[1], "paths") == 0) return paths_scenario();
     if (argc > 1 && std::strcmp(argv[1], "capsule") == 0) return capsule_scenario();

@@ -269,6 +269,15 @@ class ParticleSpawnerData {
     std::vector<fw_particle> particles(uint32_t particle_type);  // data.particles[i]
     std::vector<fw_particle> destroyed(uint32_t particle_type);
     std::vector<fw_particle_instance> instances(uint32_t particle_type);  // render.rs:95-115
+    // ... sorted by view depth for an alpha-blended draw (firework_hip.h: DEPTH-SORTED INSTANCES): the same records, ascending key of
+    // `view`, ties in particle-list order.  Waits for the result.
+    std::vector<fw_particle_instance> instances_sorted(const fw_sort_view &view, uint32_t particle_type = 0) {
+        uint64_t n = 0;
+        check_(fw_ctx_pack_instances_sorted(raw_(), handle, particle_type, &view, nullptr, 0, &n));
+        std::vector<fw_particle_instance> v(n);
+        if (n) check_(fw_ctx_pack_instances_sorted(raw_(), handle, particle_type, &view, v.data(), n, &n));
+        return v;
+    }
     // render hand-off fused into the update (fw_spawner_attach_instances): device buffer of `cap` 64-byte records
     void attach_instances(void *device_buffer, uint64_t cap, uint32_t particle_type = 0);
     // ... for a renderer that draws an instance sub-range: the live records are buffer[first, first + count) (instance_window);
@@ -478,6 +487,21 @@ class ParticleSystemPlugin {
     // ... paths, results and samples (or null) in device memory, enqueued on stream(): never waits
     void trace_paths_device(const fw_path_settings &settings, const void *d_paths, uint64_t n, void *d_out, void *d_samples = nullptr) {
         check(fw_ctx_trace_paths_device(ctx_, &settings, d_paths, n, d_out, d_samples));
+    }
+
+    // Depth-sorted records of (data, particle_type) into `cap` 64-byte records of device memory, enqueued on stream(): never waits
+    // (but once when the sort's scratch has to grow); -> the host's upper bound of the records written (the count is the device's)
+    uint64_t pack_instances_sorted_device(const ParticleSpawnerData &data, const fw_sort_view &view, void *d_out, uint64_t cap, uint32_t particle_type = 0) {
+        uint64_t ub = 0;
+        check(fw_ctx_pack_instances_sorted_device(ctx_, data.handle, particle_type, &view, d_out, cap, &ub));
+        return ub;
+    }
+    // ... the permutation alone: d_order[j] (uint32, device memory) = list index of the particle drawn j-th, for fused records drawn
+    // through an index
+    uint64_t depth_order_device(const ParticleSpawnerData &data, const fw_sort_view &view, void *d_order, uint64_t cap, uint32_t particle_type = 0) {
+        uint64_t ub = 0;
+        check(fw_ctx_depth_order_device(ctx_, data.handle, particle_type, &view, d_order, cap, &ub));
+        return ub;
     }
 
     // update_aabbs (render.rs:677-703) fused into the update: every frame leaves per-tile boxes, ParticleSpawnerData::aabb

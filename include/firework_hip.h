@@ -460,6 +460,40 @@ typedef struct fw_particle_instance {
     float emissive_color[4];
 } fw_particle_instance;
 
+/* DEPTH-SORTED INSTANCES (an alpha-blended draw with depth writes off -- the reference's default BlendMode, render.rs:775-779 -- shows
+ * its particles in the order of the buffer: every other hand-off delivers list order, that is spawn order, and the picture changes
+ * with the camera angle).  fw_ctx_pack_instances_sorted[_device] deliver the ParticleInstance records of one particle type sorted by
+ * view depth, fw_ctx_depth_order_device the permutation alone, for a host that already has the records.
+ *   DEPTH     d = ((p.x - eye.x) * forward.x + (p.y - eye.y) * forward.y) + (p.z - eye.z) * forward.z in fp32: three subtractions, three
+ *             products, the sum of the x and y products, then that sum plus the z product; every operation rounded, none fused.  p is
+ *             the position the unsorted pack writes into the particle's record.  `forward` is used as given, not normalised (as
+ *             fw_ray.dir is): a zero vector gives every particle depth 0.
+ *   KEY       a uint32 k per particle; ascending k = drawn first.  b = the bits of d, with b = 0 when d == 0 (so -0 and +0 tie);
+ *             a = (b >> 31) ? ~b : (b | 0x80000000), which ascends with d from -inf (0x007FFFFF) to +inf (0xFF800000);
+ *             k = a for FW_SORT_FRONT_TO_BACK, k = ~a for FW_SORT_BACK_TO_FRONT.  A NaN depth has k = 0xFFFFFFFF in either order:
+ *             drawn last; no other depth reaches that value.
+ *   ORDER     ascending k, particles of equal k in particle-list order (a stable sort): the permutation is unique.  order[j] is the list
+ *             index of the particle drawn j-th; sorted record j is the unsorted pack's record order[j], byte for byte.
+ *   WHICH     exactly the particles fw_spawner_pack_instances_device writes for the same `cap`: the first min(count, cap) of the list,
+ *             sorted among themselves.  *n_upper_bound means what it means there (the count is the device's; the host learns a bound).
+ *             Records and order entries at and beyond min(count, cap) are not written.
+ *   STREAM    the device forms enqueue on the context's main stream and answer for their place in it, as the unsorted device pack
+ *             does: behind every fw_step called before, in front of every one called after.  They never wait -- with ONE exception,
+ *             the one fw_ctx_set_colliders has: the sort's scratch (16 bytes per particle of the bound, plus a table) belongs to the
+ *             context and only grows; a call that needs more than any call before it waits for the stream once and reallocates.
+ *             The host form stages through the context's staging buffer and waits for its result.
+ *   INDEXED   a host that keeps fused records (fw_spawner_attach_instances) draws them through the order: the record of list index i
+ *             is d_out[i] there, and d_out[first + i] with the windowed attach (`first` of fw_spawner_instance_window).
+ *   ERRORS    a null context, an unknown spawner or type, a null view or buffer, an `order` that is no FW_SORT_* value, reserved != 0:
+ *             FW_EINVAL, nothing enqueued, nothing written.  (The host form takes out = NULL or cap = 0 to ask for the count alone.) */
+enum { FW_SORT_BACK_TO_FRONT = 0, FW_SORT_FRONT_TO_BACK = 1 };
+typedef struct fw_sort_view { /* 32 bytes */
+    float eye[3];
+    uint32_t order; /* FW_SORT_*; anything else: FW_EINVAL */
+    float forward[3];
+    uint32_t reserved; /* must be 0 */
+} fw_sort_view;
+
 /* ---- context ---------------------------------------------------------------- */
 /* `stream` = an existing hipStream_t to enqueue on (e.g. torch's current stream),
  * or NULL to let the context create its own. */
@@ -595,6 +629,17 @@ fw_status fw_spawner_attach_instances(fw_ctx *ctx, fw_spawner h, uint32_t type, 
  * d_out = NULL detaches. */
 fw_status fw_spawner_attach_instances_window(fw_ctx *ctx, fw_spawner h, uint32_t type, void *d_out, uint64_t cap);
 fw_status fw_spawner_instance_window(fw_ctx *ctx, fw_spawner h, uint32_t type, uint64_t *first, uint64_t *count);
+/* DEPTH-SORTED INSTANCES above.  `view` is host memory, read inside the call.
+ * order[j] = list index of the particle drawn j-th: uint32 in DEVICE memory, enqueued on the context's stream, never waits (but for
+ * the growth of the scratch) */
+fw_status fw_ctx_depth_order_device(fw_ctx *ctx, fw_spawner h, uint32_t type, const fw_sort_view *view, void *d_order, uint64_t cap,
+                                    uint64_t *n_upper_bound);
+/* the ParticleInstance records in that order, into a DEVICE buffer (16-byte aligned); never waits (but for the growth of the scratch) */
+fw_status fw_ctx_pack_instances_sorted_device(fw_ctx *ctx, fw_spawner h, uint32_t type, const fw_sort_view *view, void *d_out, uint64_t cap,
+                                              uint64_t *n_upper_bound);
+/* the same into a HOST buffer; waits; copies min(count, cap) records, *n_out = count, as fw_spawner_pack_instances */
+fw_status fw_ctx_pack_instances_sorted(fw_ctx *ctx, fw_spawner h, uint32_t type, const fw_sort_view *view, fw_particle_instance *out,
+                                       uint64_t cap, uint64_t *n_out);
 /* update_aabbs reduction (render.rs:677-703), world space; *any = 0 when no particles */
 fw_status fw_spawner_aabb(fw_ctx *ctx, fw_spawner h, float out_min[3], float out_max[3], int32_t *any);
 /* AABB fused into the update: from the next fw_step on, every tile of the update kernel also leaves the box of

@@ -84,6 +84,11 @@ pub const FW_PATH_MAX_STEPS: u32 = 4096;
 pub struct fw_particle_instance {                      // == render::ParticleInstance, render.rs:95-103
     pub position: [f32; 3], pub scale: f32, pub rotation: [f32; 4], pub base_color: [f32; 4], pub emissive_color: [f32; 4],
 }
+#[repr(C)] #[derive(Clone, Copy)] pub struct fw_sort_view {       // the camera of a depth sort (32 bytes); order: FW_SORT_*, reserved: 0
+    pub eye: [f32; 3], pub order: u32, pub forward: [f32; 3], pub reserved: u32,
+}
+pub const FW_SORT_BACK_TO_FRONT: u32 = 0;
+pub const FW_SORT_FRONT_TO_BACK: u32 = 1;
 
 extern "C" {
     pub fn fw_abi_version() -> c_int;
@@ -131,6 +136,9 @@ extern "C" {
     pub fn fw_spawner_attach_instances(ctx: *mut fw_ctx, h: fw_spawner, ty: u32, d_out: *mut c_void, cap: u64) -> c_int;
     pub fn fw_spawner_attach_instances_window(ctx: *mut fw_ctx, h: fw_spawner, ty: u32, d_out: *mut c_void, cap: u64) -> c_int;
     pub fn fw_spawner_instance_window(ctx: *mut fw_ctx, h: fw_spawner, ty: u32, first: *mut u64, count: *mut u64) -> c_int;
+    pub fn fw_ctx_depth_order_device(ctx: *mut fw_ctx, h: fw_spawner, ty: u32, view: *const fw_sort_view, d_order: *mut c_void, cap: u64, n_ub: *mut u64) -> c_int;
+    pub fn fw_ctx_pack_instances_sorted_device(ctx: *mut fw_ctx, h: fw_spawner, ty: u32, view: *const fw_sort_view, d_out: *mut c_void, cap: u64, n_ub: *mut u64) -> c_int;
+    pub fn fw_ctx_pack_instances_sorted(ctx: *mut fw_ctx, h: fw_spawner, ty: u32, view: *const fw_sort_view, out: *mut fw_particle_instance, cap: u64, n: *mut u64) -> c_int;
     pub fn fw_spawner_aabb(ctx: *mut fw_ctx, h: fw_spawner, min: *mut f32, max: *mut f32, any: *mut i32) -> c_int;
     pub fn fw_ctx_track_aabbs(ctx: *mut fw_ctx, enable: i32) -> c_int;
     pub fn fw_ctx_live_count(ctx: *mut fw_ctx, out: *mut u64) -> c_int;

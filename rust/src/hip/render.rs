@@ -23,6 +23,15 @@
 //! `(first, count)` (`fw_spawner_instance_window`).  The draw becomes the sub-range below.  `HipInstanceWindow` carries the
 //! range through the render world; the interop calls themselves are outside this crate (wgpu-hal `Device::buffer_from_raw`).
 //!
+//! **Sorted draws (alpha blending).**  The default `BlendMode::Blend` pipeline writes no depth (src/render.rs:775-779) and the reference
+//! sorts whole spawner entities only (src/render.rs:541-560), so the particles of one system blend in buffer order -- spawn order with
+//! both forms above.  For a back-to-front draw from a camera (`fw_sort_view { eye, order: FW_SORT_BACK_TO_FRONT, forward, reserved: 0 }`):
+//! form A calls `fw_ctx_pack_instances_sorted` in `hip_fill_instances` where it calls `fw_spawner_pack_instances` -- same buffer, same count,
+//! the records arrive sorted and nothing else changes.  Form B keeps its attached records and asks for the permutation alone,
+//! `fw_ctx_depth_order_device`, into a second shared buffer of `u32` (enqueued on the context's stream, no wait): the vertex shader then
+//! reads instance `first + order[instance_index]` instead of `first + instance_index`.  A host without a fused buffer that shares memory
+//! with HIP uses `fw_ctx_pack_instances_sorted_device` where it would use `fw_spawner_pack_instances_device`.  Not implemented in this file.
+//!
 //! Both forms leave `ParticleInstance`'s layout (src/render.rs:95-103) and the vertex attributes (src/render.rs:737-766)
 //! untouched: `fw_particle_instance` is that struct.
 use super::ffi::*;
