@@ -7,6 +7,7 @@ boundaries inside a tile -- whose head wraps every few frames.  Needs an MI355X.
 import numpy as np
 import pytest
 
+import first_readers
 import oracle  # noqa: F401
 from bevy_firework_amd import settings as S
 from bevy_firework_amd import workloads
@@ -368,3 +369,66 @@ def test_non_temporal_forms(monkeypatch, knob):
 
     on, off = both(monkeypatch, _spawner(spin=True), scenario, **{knob: "0"})
     assert on[1] == off[1] - 8
+
+
+# ---- the packed and the depth-sorted forms as the first reader of stale ages ------------------------------------------------------------
+@pytest.mark.parametrize("spin", [False, True], ids=["cannot turn", "spins about y"])
+@pytest.mark.parametrize("name", list(first_readers.PACK_READERS))
+def test_a_pack_is_the_first_reader_of_stale_ages(monkeypatch, name, spin):
+    """twelve frames nobody read (2.5-frame lifetimes: the head has wrapped, particles died unread), then ONE call that packs records:
+    scale and colours are evaluated from the age, so the ages are written back first, exactly once, and the particles() read behind
+    it writes nothing again.  The records are those of the run without the rule, whose own unsorted pack -- permuted by
+    tests/sort_ref.py where the reader sorts -- they must equal byte for byte"""
+    reader, is_sorted = first_readers.PACK_READERS[name]
+
+    def scenario(run):
+        before = run.bytes_moved()
+        run.step(n=12)
+        _expect_rule(run, before)
+        launches = run.system.age_launches()
+        first = reader(run)
+        assert run.system.age_launches() == launches + (1 if run.rule else 0), (name, "the first reader", run.rule)
+        run.keep(f"records of {name}", first)
+        run.read("behind the first reader", exact=not spin)
+        assert run.system.age_launches() == launches + (1 if run.rule else 0), (name, "the read behind it wrote the ages again", run.rule)
+        unsorted = run.pair.gpu.instances(0)
+        run.keep("unsorted", unsorted)
+        return first, unsorted, run.pair.gpu.particles(0)
+
+    on, off = both(monkeypatch, _spawner(spin=spin), scenario)
+    for first, _, _ in (on, off):
+        first_readers.check_records(first, off[1], is_sorted, name)
+    first_readers.stale_planes_would_show(off[2], off[1], (0.0, 0.0, 0.0, 1.0) if spin else None, DT)
+
+
+@pytest.mark.parametrize("spin", [False, True], ids=["cannot turn", "spins about y"])
+def test_the_depth_order_every_frame_leaves_the_ages_alone(monkeypatch, spin):
+    """the order reads positions, which every launch moves: twelve frames of fw_ctx_depth_order_device write no age back and the ring
+    stays under the rule; the particles() read behind them writes them once.  (The run without the rule also takes the unsorted pack
+    of every frame: what each order is checked against.)"""
+    def scenario(run):
+        before = run.bytes_moved()
+        run.step(n=9)
+        flagged = _expect_rule(run, before)
+        launches = run.system.age_launches()
+        buf = first_readers.order_buffer(run, 16384)
+        orders, unsorted = [], []
+        for k in range(12):
+            run.step()
+            orders.append(first_readers.depth_order(run, buf, 16384))
+            run.keep(f"order {k}", orders[-1])
+            assert run.bytes_moved() == flagged and run.system.age_launches() == launches
+            if not run.rule:
+                unsorted.append(run.pair.gpu.instances(0))
+        run.read("behind the orders", exact=not spin)
+        assert run.system.age_launches() == launches + (1 if run.rule else 0)
+        run.read("again", exact=not spin)
+        assert run.system.age_launches() == launches + (1 if run.rule else 0)
+        return orders, unsorted, run.pair.gpu.instances(0), run.pair.gpu.particles(0)
+
+    on, off = both(monkeypatch, _spawner(spin=spin), scenario)
+    assert len(off[1]) == 12
+    for orders in (on[0], off[0]):
+        for k, (got, u) in enumerate(zip(orders, off[1])):
+            assert np.array_equal(got, first_readers.want_order(u)) and not np.array_equal(got, np.arange(len(u))), f"order {k}"
+    first_readers.stale_planes_would_show(off[3], off[2], (0.0, 0.0, 0.0, 1.0) if spin else None, DT)

@@ -10,6 +10,7 @@ import dataclasses
 import numpy as np
 import pytest
 
+import first_readers
 import oracle  # noqa: F401
 from bevy_firework_amd import settings as S
 from bevy_firework_amd import workloads
@@ -497,3 +498,70 @@ def test_a_small_ring_at_product_defaults_keeps_its_figure(monkeypatch):
 
     on, off = both(monkeypatch, _spawner(), scenario, fifo_small=None, product=True)
     assert on == off and on[0] == "fifo"
+
+
+# ---- the packed and the depth-sorted forms as the first reader of a deferred spin -------------------------------------------------------
+@pytest.mark.parametrize("name", list(first_readers.PACK_READERS))
+def test_a_pack_is_the_first_reader_of_a_deferred_spin(monkeypatch, name):
+    """fourteen frames nobody read (2.5-frame lifetimes: the head has wrapped, particles died unread), then ONE call that packs
+    records: it replays the spin (and writes the ages back: both runs are under the age rule) before it packs, exactly once, and
+    the particles() read behind it finds nothing left to replay.  The records are those of the run without the rule, whose own
+    unsorted pack -- permuted by tests/sort_ref.py where the reader sorts -- they must equal byte for byte"""
+    reader, is_sorted = first_readers.PACK_READERS[name]
+
+    def scenario(run):
+        before = run.bytes_moved()
+        run.step(n=14)
+        run.expect(before)
+        spins, ages = run.spins(), run.system.age_launches()
+        first = reader(run)
+        after = (spins + (1 if run.rule else 0), ages + 1)
+        assert (run.spins(), run.system.age_launches()) == after, (name, "the first reader", run.rule)
+        run.keep(f"records of {name}", first)
+        run.read("behind the first reader")
+        assert (run.spins(), run.system.age_launches()) == after, (name, "the read behind it replayed again", run.rule)
+        unsorted = run.pair.gpu.instances(0)
+        run.keep("unsorted", unsorted)
+        return first, unsorted, run.pair.gpu.particles(0)
+
+    on, off = both(monkeypatch, _spawner(), scenario)
+    for first, _, _ in (on, off):
+        first_readers.check_records(first, off[1], is_sorted, name)
+    first_readers.stale_planes_would_show(off[2], off[1], _rot_about(Y, 0.7), DT)
+
+
+def test_the_depth_order_every_frame_leaves_the_spin_deferred(monkeypatch):
+    """a host that draws through an index asks for the order every frame: it reads positions, which no launch defers -- neither the
+    spin nor the ages are written back, the ring keeps the deferred figure frame after frame, and the particles() read behind the
+    twelve frames causes the one replay.  (The run without the rule also takes the unsorted pack of every frame: what each order is
+    checked against.)"""
+    def scenario(run):
+        before = run.bytes_moved()
+        run.step(n=9)
+        flagged = run.expect(before)
+        spins, ages = run.spins(), run.system.age_launches()
+        buf = first_readers.order_buffer(run, 16384)
+        orders, unsorted = [], []
+        for k in range(12):
+            run.step()
+            orders.append(first_readers.depth_order(run, buf, 16384))
+            run.keep(f"order {k}", orders[-1])
+            assert run.bytes_moved() == flagged and run.spins() == spins
+            if run.rule:
+                assert run.system.age_launches() == ages
+            else:
+                unsorted.append(run.pair.gpu.instances(0))
+        ages = run.system.age_launches()  # (both runs are under the age rule, and the run without this rule has read this frame already)
+        after = (spins + 1, ages + 1) if run.rule else (spins, ages)
+        run.read("behind the orders")
+        assert (run.spins(), run.system.age_launches()) == after
+        run.read("again")
+        assert (run.spins(), run.system.age_launches()) == after
+        return orders, unsorted, run.pair.gpu.instances(0), run.pair.gpu.particles(0)
+
+    on, off = both(monkeypatch, _spawner(), scenario)
+    assert len(off[1]) == 12
+    for orders in (on[0], off[0]):
+        for k, (got, u) in enumerate(zip(orders, off[1])):
+            assert np.array_equal(got, first_readers.want_order(u)) and not np.array_equal(got, np.arange(len(u))), f"order {k}"
+    first_readers.stale_planes_would_show(off[3], off[2], _rot_about(Y, 0.7), DT)
