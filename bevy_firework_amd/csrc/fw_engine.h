@@ -148,6 +148,38 @@ private:
     bool own_ = false;
 };
 
+// ---- what is in flight, on top of the handles.  The host hands small tables to the device by writing pinned memory and enqueueing ONE
+// hipMemcpyAsync (or a kernel that reads the memory in place) on a stream: no frame in flight stalls.  The one invariant of every such
+// site: the pinned memory -- and a single device table it feeds -- is not rewritten while the copy or kernel that reads it may still be
+// running.  A Fence holds it: whoever enqueues the reader marks the fence behind it, whoever writes the memory next waits first (a
+// single branch unless that reader was enqueued since the last wait), and whoever has waited for everything (sync) before the buffers
+// are replaced forgets it.  (methods: below FW_HIP)
+class Fence {
+public:
+    fw_status wait(fw_ctx *ctx) { return pending_ ? wait_pending(ctx) : FW_OK; }
+    fw_status mark(fw_ctx *ctx, hipStream_t stream);  // (creates the event on first use)
+    void forget() { pending_ = false; }
+
+private:
+    fw_status wait_pending(fw_ctx *ctx);
+    HipEvent ev_;
+    bool pending_ = false;
+};
+
+// N pinned staging slots used in turn, a fence each: with two, a set that changes every call is written while the previous one is still
+// on its way, and a call waits only for the copy N calls back.  take: the slot of this turn, free and grown to hold n elements (the
+// only allocation); commit: the copy went to `stream` -- only now is the turn used up (a call that is refused in between finds the
+// same slot again).  With `dev`, the single device table the slot feeds grows with it, all or nothing, behind a sync: the capacity of
+// the pair is the smaller of the two.
+template <typename T, int N>
+struct Staging {
+    HipBuf<T> h[N];
+    Fence fence[N];
+    uint64_t turn = 0;  // commits so far
+    fw_status take(fw_ctx *ctx, size_t n, size_t grow_to, T **out = nullptr, HipBuf<T> *dev = nullptr);
+    fw_status commit(fw_ctx *ctx, hipStream_t stream);
+};
+
 constexpr int kParamRing = 8;    // per-frame parameter buffers in flight
 #ifndef FW_BAR_PARAM_KB
 #define FW_BAR_PARAM_KB 64
@@ -707,8 +739,8 @@ struct fw_ctx {
     size_t param_bytes = 0;
     HipBuf<char> h_param[kParamRing];  // (pinned)
     HipBuf<char> d_param[kParamRing];
-    HipEvent ev_copied[kParamRing], ev_consumed[kParamRing];
-    bool consumed_pending[kParamRing] = {};
+    HipEvent ev_copied[kParamRing];
+    Fence consumed[kParamRing];  // marked behind the last launch that reads the slot (end_frame; a small launch on the side stream)
     // Global-only frames with more ops than fit the kernel arguments: the kernel reads the op table straight from the
     // pinned ring slot (no copy, no events); a slot is free again once the launch after its frame has started, which
     // that launch reports through a pinned word (FwUpdateArgs::done_tag).
@@ -739,8 +771,7 @@ struct fw_ctx {
     HipBuf<uint4> d_tile_desc;  // per tile: {segment, first tile, tile count, 0}
     HipBuf<uint4> h_desc[kTabRing];
     size_t tile_desc_cap = 0;
-    HipEvent ev_tab[kTabRing];
-    bool tab_pending[kTabRing] = {};
+    Fence tab_fence[kTabRing];  // one per slot, over its three arrays
     uint64_t tab_seq = 0, ring_seq = 0;
     uint32_t vt_rounds = 1;  // new-particle tile size of the current frame (rounds of 256)
     bool tab_force = false;  // a segment was (re)built: re-send the descriptors even if the tile counts are equal
@@ -783,12 +814,13 @@ struct fw_ctx {
     bool use_nospin = true;    // FW_NOSPIN=0: every type keeps its rotation plane (A/B)
     bool use_ageless = true;   // FW_AGELESS=0: no ring runs under the age rule (A/B in one build)
     // the cohort table of the latest ensure_ages: written in pinned memory, copied to the device in the stream of the kernel that reads
-    // it; ages_busy: that stream, until it has been waited for (the next table is written into the same pinned words)
-    HipBuf<char> h_ages, d_ages;
-    size_t ages_cap = 0;
-    hipStream_t ages_busy = nullptr;
-    bool ages_pending = false;
-    uint64_t age_launches = 0;  // fw_debug_age_launches
+    // it; the fence is marked behind that kernel, main stream or side stream (the next table goes through the same pinned AND device words)
+    struct CohortTable {
+        Staging<char, 1> h;
+        HipBuf<char> d;
+        uint64_t launches = 0;  // fw_debug_age_launches / fw_debug_spin_launches
+    };
+    CohortTable age_tab;
     // the deferred spin of FIFO rings nobody reads (fw_spin.h).  FW_SPIN_DEFER=0: no ring defers (A/B in one build); spin_defer_min:
     // live particles from which a ring may (FW_SPIN_DEFER_MIN; the size from which a launch counts as bound by bandwidth);
     // spin_defer_after: qualifying launches in a row, with nobody asking for the planes, before the first deferred one
@@ -798,11 +830,7 @@ struct fw_ctx {
     // (FW_SPIN_LOG: bounds the replay loop and the table).  The table and the log of the latest ensure_spin travel like the age table.
     bool use_spin_defer = true;
     uint32_t spin_defer_min = 384u * FW_TILE, spin_defer_after = 32u, spin_log_cap = 256u;
-    HipBuf<char> h_spin, d_spin;
-    size_t spin_cap = 0;
-    hipStream_t spin_busy = nullptr;
-    bool spin_pending = false;
-    uint64_t spin_launches = 0;  // fw_debug_spin_launches
+    CohortTable spin_tab;
     bool use_axis = true;      // FW_AXIS_SPIN=0: no ring runs under the axis-spin rule (A/B in one build)
     bool use_derived = true;   // FW_DERIVED=0: every type stores its scale / colour planes, attached instance buffer or not (A/B)
     // Round 6: scale, base colour and emissive colour are pure functions of (age, lifetime, initial_scale) (core.rs:601-605,
@@ -892,8 +920,7 @@ struct fw_ctx {
     bool small_dirty = true;
     HipBuf<uint32_t> d_small, h_small;  // device list / pinned staging
     size_t small_cap = 0;               // (of both)
-    HipEvent ev_small;
-    bool small_pending = false;
+    Fence small_fence;                  // (of h_small)
     std::vector<FwOp> fifo_ops;  // this frame's Global ops that feed FIFO segments (spawned inside fw_k_update_fifo)
     std::vector<std::pair<uint32_t, FwOp>> range_mat_ops;  // the same for range rings other particles' entries emit from
     std::vector<std::pair<uint32_t, FwOp>> fifo_mat_ops;  // {emission index, op}: rings of spawners with Nested entries -- the
@@ -943,8 +970,7 @@ struct fw_ctx {
     size_t rdesc_cap = 0;            // (of both and d_rstatus)
     uint32_t r_total = 0;            // workgroups of the range launch
     bool r_force = true;             // a range segment was (re)built: re-send the table
-    HipEvent ev_rtab;
-    bool rtab_pending = false;
+    Fence rtab_fence;                // (of h_rdesc)
     HipBuf<unsigned long long> d_rstatus;     // look-back words of the OLD workgroups
     HipBuf<char> h_rparam[kParamRing];        // per-frame records + ops, written by the host, read by the kernel in place
     // ... in DEVICE memory the host writes through the large BAR (fine-grained, hipExtMallocWithFlags) when the platform maps it, in
@@ -1006,11 +1032,8 @@ struct fw_ctx {
     HipBuf<FwCollider> d_colliders;     // device-resident analytic colliders (fw_ctx_set_colliders)
     uint32_t n_colliders = 0;
     // a new set travels as ONE copy in the context's stream (ordered behind the frames that read the old set, in front of the
-    // frames that will read the new one: no synchronisation); the pinned staging is double-buffered
-    HipBuf<FwCollider> h_coll[2];
-    HipEvent ev_coll[2];
-    bool coll_pending[2] = {false, false};
-    uint64_t coll_seq = 0;
+    // frames that will read the new one: no synchronisation)
+    Staging<FwCollider, 2> h_coll;
     // collider meshes (fw_engine_mesh.cpp): the meshes behind fw_mesh handles, and the instance set, staged and copied like the
     // analytic set
     struct MeshHost {
@@ -1019,17 +1042,14 @@ struct fw_ctx {
         uint32_t n_nodes = 0, n_tris = 0;
         float center[3] = {0.0f, 0.0f, 0.0f}, radius = 0.0f;  // a sphere that contains the mesh, in its own frame
         // a deformable mesh (fw_ctx_create_deformable_mesh) keeps what fw_ctx_update_mesh_vertices needs: the refit's tables
-        // (fw_refit.h) and the device vertices; the new vertices are staged in pinned memory, double-buffered, and travel as one
-        // copy in the context's stream like an instance set.  All of it is allocated at creation: an update allocates nothing.
+        // (fw_refit.h) and the device vertices; the new vertices are staged in pinned memory and travel as one copy in the
+        // context's stream like an instance set.  All of it is allocated at creation: an update allocates nothing.
         bool deformable = false;
         uint32_t n_vertices = 0;
         HipBuf<FwSlotIdx> slots;
         HipBuf<uint32_t> order, level_off;
         HipBuf<float> xyz;
-        HipBuf<float> h_xyz[2];
-        HipEvent ev_xyz[2];
-        bool xyz_pending[2] = {false, false};
-        uint64_t xyz_seq = 0;
+        Staging<float, 2> h_xyz;
         std::vector<uint32_t> h_level_off;  // the host's copy: which levels get a launch of their own (fw_launch_mesh_refit)
         std::vector<uint8_t> referenced;    // per vertex: some triangle uses it (the pad and the bounding sphere go by these)
         float lo[3] = {0.0f, 0.0f, 0.0f}, hi[3] = {0.0f, 0.0f, 0.0f}, pad = 0.0f;  // the root's padded box and the pad, as the host last knew them
@@ -1043,17 +1063,14 @@ struct fw_ctx {
         // host-form update takes them back.  stage_instances then stages the mesh's instances as never skipped and has
         // fw_k_mesh_spheres fix them behind the copy.
         bool dev_bounds = false;
-        uint64_t sphere_stamp = 0;  // stage_instances: the instance set (fw_ctx::mesh_seq) this mesh's sphere launch was last enqueued for
+        uint64_t sphere_stamp = 0;  // stage_instances: the instance set (fw_ctx::h_mesh_inst.turn) this mesh's sphere launch was last enqueued for
     };
     static constexpr int kMeshDeviceAllocs = 4;  // d_rec, d_partials, d_referenced, h_report
     std::vector<MeshHost> meshes;
     std::vector<fw_mesh> mesh_set;  // the meshes the current instance set places (fw_ctx_destroy_mesh refuses them)
     std::vector<fw_mesh_collider> mesh_insts;  // ... and the set itself as the caller gave it: restaged when a placed mesh deforms
     HipBuf<FwMeshInst> d_mesh_inst;
-    HipBuf<FwMeshInst> h_mesh_inst[2];
-    HipEvent ev_mesh[2];
-    bool mesh_pending[2] = {false, false};
-    uint64_t mesh_seq = 0;
+    Staging<FwMeshInst, 2> h_mesh_inst;
     // the host forms of the queries (fw_engine_query.cpp: query_staged): pinned staging and device buffers for the input and the
     // output records, grown on demand and kept; the device forms need nothing of their own
     HipBuf<float4> q_in_h, q_out_h, q_in_d, q_out_d;
@@ -1138,6 +1155,38 @@ fw_status grow_buf(fw_ctx *ctx, HipBuf<T> &b, size_t n, bool zero, size_t used, 
     b = std::move(nb);
     if (view) *view = b.get();
     return FW_OK;
+}
+
+inline fw_status Fence::wait_pending(fw_ctx *ctx) {
+    FW_HIP(ctx, hipEventSynchronize(ev_));
+    pending_ = false;
+    return FW_OK;
+}
+inline fw_status Fence::mark(fw_ctx *ctx, hipStream_t stream) {
+    if (!ev_) FW_HIP(ctx, ev_.create());
+    FW_HIP(ctx, hipEventRecord(ev_, stream));
+    pending_ = true;
+    return FW_OK;
+}
+
+fw_status sync(fw_ctx *ctx);  // (fw_engine_mem.cpp)
+template <typename T, int N>
+fw_status Staging<T, N>::take(fw_ctx *ctx, size_t n, size_t grow_to, T **out, HipBuf<T> *dev) {
+    HipBuf<T> &b = h[turn % N];
+    fw_status st = fence[turn % N].wait(ctx);
+    if (st) return st;
+    if (n > (dev ? std::min(b.cap(), dev->cap()) : b.cap())) {
+        if (dev && (st = sync(ctx))) return st;
+        if ((st = alloc_buf(ctx, b, grow_to, Mem::pinned)) || (dev && (st = alloc_buf(ctx, *dev, grow_to)))) return st;
+    }
+    if (out) *out = b;
+    return FW_OK;
+}
+template <typename T, int N>
+fw_status Staging<T, N>::commit(fw_ctx *ctx, hipStream_t stream) {
+    fw_status st = fence[turn % N].mark(ctx, stream);
+    if (!st) turn++;
+    return st;
 }
 
 // The epoch of frame f: the tag of every word its launches publish (snapshot rows, cohort reports, forecast sums) -- 30 bits, never 0
@@ -1225,8 +1274,7 @@ struct FwFrame {
     }
 };
 
-// ---- shared functions (definitions: see the list of translation units above)
-fw_status sync(fw_ctx *ctx);
+// ---- shared functions (definitions: see the list of translation units above; sync: declared above Staging::take)
 fw_status join_side(fw_ctx *ctx);
 // a FIFO ring whose age plane is stale (SegHost::ages_stale) gets it written back; stream: where the kernel goes -- null: the main
 // stream, which first waits for the ring launches on the side stream (join_side)

@@ -34,12 +34,8 @@ static fw_status create_resources(fw_ctx *ctx, hipStream_t stream) {
         FW_HIP(ctx, ctx->stream.create());
     FW_HIP(ctx, ctx->copy_stream.create());
     FW_HIP(ctx, ctx->fifo_stream.create());
-    for (HipEvent *ev : {&ctx->ev_side, &ctx->ev_rtab, &ctx->ev_small, &ctx->ev_main}) FW_HIP(ctx, ev->create());
-    for (int i = 0; i < kParamRing; i++) {
-        FW_HIP(ctx, ctx->ev_copied[i].create());
-        FW_HIP(ctx, ctx->ev_consumed[i].create());
-    }
-    for (int i = 0; i < kTabRing; i++) FW_HIP(ctx, ctx->ev_tab[i].create());
+    for (HipEvent *ev : {&ctx->ev_side, &ctx->ev_main}) FW_HIP(ctx, ev->create());
+    for (int i = 0; i < kParamRing; i++) FW_HIP(ctx, ctx->ev_copied[i].create());
     fw_status st;
     if ((st = alloc_buf(ctx, ctx->h_done, 8, Mem::pinned, true))) return st;
     ctx->h_err = ctx->h_done + 4, ctx->g.err_host = ctx->h_err;
@@ -277,21 +273,17 @@ fw_status fw_ctx_set_colliders(fw_ctx *ctx, const fw_collider *colliders, uint32
             return fail(ctx, FW_EINVAL, "unknown collider kind");
     // The reference asks the live physics world every frame (core.rs:756-765): a set that changes every frame must not
     // stall the frames in flight.  The new set is staged in pinned memory and copied by the stream itself.
-    const int slot = (int)(ctx->coll_seq++ & 1u);
-    if (ctx->coll_pending[slot]) {  // the copy of two calls ago: long done unless the caller replaces the set in a tight loop
-        FW_HIP(ctx, hipEventSynchronize(ctx->ev_coll[slot]));
-        ctx->coll_pending[slot] = false;
-    }
-    if (!ctx->ev_coll[slot]) FW_HIP(ctx, ctx->ev_coll[slot].create());
+    // (the wait of take: for the copy of two sets ago, long done unless the caller replaces the set in a tight loop)
     const size_t ncap = std::max<size_t>(64, (size_t)n * 2);
-    fw_status st;
-    if (n > ctx->h_coll[slot].cap() && (st = alloc_buf(ctx, ctx->h_coll[slot], ncap, Mem::pinned))) return st;
+    FwCollider *h;
+    fw_status st = ctx->h_coll.take(ctx, n, ncap, &h);
+    if (st) return st;
     if (n > ctx->d_colliders.cap()) {  // a larger world than ever before: the one case that waits (kernels in flight read the old table)
         if ((st = sync(ctx)) || (st = alloc_buf(ctx, ctx->d_colliders, ncap, Mem::device, false, &ctx->g.colliders))) return st;
     }
     for (uint32_t i = 0; i < n; i++) {
         const fw_collider &c = colliders[i];
-        FwCollider &d = ctx->h_coll[slot][i];
+        FwCollider &d = h[i];
         d = FwCollider{};
         d.kind = c.kind, d.layers = c.layers, d.radius = c.radius;
         // (the sphere around `position` that contains it: a wave skips a collider none of its rays can reach, fw_cast_ray)
@@ -307,9 +299,8 @@ fw_status fw_ctx_set_colliders(fw_ctx *ctx, const fw_collider *colliders, uint32
         memcpy(d.half_extents, c.half_extents, sizeof c.half_extents);
     }
     if (n) {
-        FW_HIP(ctx, hipMemcpyAsync(ctx->d_colliders, ctx->h_coll[slot], n * sizeof(FwCollider), hipMemcpyHostToDevice, ctx->stream));
-        FW_HIP(ctx, hipEventRecord(ctx->ev_coll[slot], ctx->stream));
-        ctx->coll_pending[slot] = true;
+        FW_HIP(ctx, hipMemcpyAsync(ctx->d_colliders, h, n * sizeof(FwCollider), hipMemcpyHostToDevice, ctx->stream));
+        if ((st = ctx->h_coll.commit(ctx, ctx->stream))) return st;
     }
     ctx->n_colliders = n;
     ctx->g.n_colliders = n;
@@ -1046,13 +1037,13 @@ fw_status fw_debug_recovered_rings(fw_ctx *ctx, uint64_t *n) {
 // launches of fw_k_fifo_ages so far (ensure_ages: a ring under the age rule had its ages written back)
 fw_status fw_debug_age_launches(fw_ctx *ctx, uint64_t *n) {
     if (!ctx || !n) return FW_EINVAL;
-    *n = ctx->age_launches;
+    *n = ctx->age_tab.launches;
     return FW_OK;
 }
 // launches of fw_k_fifo_spin so far (ensure_spin: a ring whose spin was deferred had its log replayed)
 fw_status fw_debug_spin_launches(fw_ctx *ctx, uint64_t *n) {
     if (!ctx || !n) return FW_EINVAL;
-    *n = ctx->spin_launches;
+    *n = ctx->spin_tab.launches;
     return FW_OK;
 }
 fw_status fw_debug_tf_frames(fw_ctx *ctx, uint64_t *n) {

@@ -534,7 +534,7 @@ fw_status build_spawner(fw_ctx *ctx, int h, const fw_spawner_desc *d, const std:
     if (ctx->segs.size() > ctx->small_cap) {  // the small-type list (fw_ctx::d_small): room for every segment slot; fw_step never allocates
         if ((st = sync(ctx))) return st;
         const size_t ncap = ctx->segs.size() * 2 + 256;
-        ctx->small_cap = 0, ctx->small_pending = false;
+        ctx->small_cap = 0, ctx->small_fence.forget();
         if ((st = alloc_buf(ctx, ctx->d_small, ncap)) || (st = alloc_buf(ctx, ctx->h_small, ncap, Mem::pinned))) return st;
         ctx->small_cap = ncap, ctx->small_dirty = true;
     }

@@ -781,17 +781,14 @@ fw_status launch_small(fw_ctx *ctx, FwFrame &fr) {
             if (!wide) ctx->n_narrow = (uint32_t)ctx->small_list.size();
         }
         if (ctx->small_list.size() > ctx->small_cap) return poison_segment(ctx, kNoSeg, "small-type list overflow");
-        if (ctx->small_pending) {
-            FW_HIP(ctx, hipEventSynchronize(ctx->ev_small));
-            ctx->small_pending = false;
-        }
+        if ((st = ctx->small_fence.wait(ctx))) return st;
         // the previous frame's small launch ran on the ring stream and may not have read the OLD list yet: the copy below
         // (main stream) comes after it (the join used to be enqueued only further down, after the copy)
         if (ctx->small_last_side && ctx->side_dirty && (st = main_waits_side(ctx))) return st;
         memcpy(ctx->h_small, ctx->small_list.data(), ctx->small_list.size() * sizeof(uint32_t));
         FW_HIP(ctx, hipMemcpyAsync(ctx->d_small, ctx->h_small, ctx->small_list.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
-        FW_HIP(ctx, hipEventRecord(ctx->ev_small, ctx->stream));
-        ctx->small_pending = true, ctx->small_dirty = false;
+        if ((st = ctx->small_fence.mark(ctx, ctx->stream))) return st;
+        ctx->small_dirty = false;
     }
     FwSmallArgs sa{};
     sa.list = ctx->d_small, sa.n = (uint32_t)ctx->small_list.size(), sa.n_narrow = ctx->n_narrow, sa.parity = fr.p, sa.epoch = a.epoch, sa.dt = fr.dt;
@@ -813,8 +810,7 @@ fw_status launch_small(fw_ctx *ctx, FwFrame &fr) {
     if (small_side) ctx->side_dirty = true;
     if (fr.small_tslot >= 0) {
         if (small_side) {
-            FW_HIP(ctx, hipEventRecord(ctx->ev_consumed[fr.small_tslot], ctx->fifo_stream));
-            ctx->consumed_pending[fr.small_tslot] = true;
+            if ((st = ctx->consumed[fr.small_tslot].mark(ctx, ctx->fifo_stream))) return st;
         } else {
             ctx->slot_frame[fr.small_tslot] = ctx->frame + 1;  // free once a launch after this frame has started
         }
@@ -857,10 +853,8 @@ fw_status launch_general(fw_ctx *ctx, FwFrame &fr) {
 
 // ---- the frame's bookkeeping: recycled slot, armed snapshot row, what the next frame's forecast finds, the counters
 fw_status end_frame(fw_ctx *ctx, FwFrame &fr) {
-    if (fr.slot >= 0) {
-        FW_HIP(ctx, hipEventRecord(ctx->ev_consumed[fr.slot], ctx->stream));
-        ctx->consumed_pending[fr.slot] = true;
-    }
+    fw_status st;
+    if (fr.slot >= 0 && (st = ctx->consumed[fr.slot].mark(ctx, ctx->stream))) return st;
     if (fr.snap >= 0) {
         ctx->snap_pending[fr.snap] = true;
         ctx->snap_seen[fr.snap] = false;

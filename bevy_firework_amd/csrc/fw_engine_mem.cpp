@@ -30,45 +30,52 @@ fw_status join_side(fw_ctx *ctx) {
 // neither side may treat dt differently -- +0, or a positive normal finite value (a denormal may be flushed on one side only)
 bool ageless_dt_ok(float dt) { return !std::signbit(dt) && (dt == 0.0f || std::isnormal(dt)); }
 
-fw_status ensure_ages(fw_ctx *ctx, uint32_t si, hipStream_t stream) {
-    SegHost &S = ctx->segs[si];
-    if (!S.ages_stale) return FW_OK;
+// What ensure_ages and ensure_spin share: one entry (E) per cohort that holds particles -- the ring's live particles are its cohorts laid
+// end to end, oldest first -- and `tail` bytes behind them, through the one staging buffer of `T` into its device table, in the stream
+// of the kernel that reads it.  stream null: the main stream, which first waits for the ring launches on the side stream.  `work`
+// false: only that.  build(entries, &live) writes the entries (and what follows them) and returns their number; launch(stream, live,
+// table, n) enqueues the kernel, and the fence goes behind it: it covers the pinned words (the copy) and the device table (the kernel).
+template <typename E, typename Build, typename Launch>
+static fw_status replay_cohorts(fw_ctx *ctx, uint32_t si, hipStream_t stream, bool work, fw_ctx::CohortTable &T, size_t tail, size_t floor,
+                                Build build, Launch launch) {
+    const SegHost &S = ctx->segs[si];
     fw_status st;
     if (!stream) {
         if ((st = join_side(ctx))) return st;
         stream = ctx->stream;
     }
-    // one entry per cohort that holds particles: the ring's live particles are its cohorts laid end to end, oldest first (fw_ages.h)
-    const size_t n_max = S.coh.size();
-    if (S.fifo && n_max) {
-        if (ctx->ages_pending) {  // (the previous table may still be on its way to the device)
-            FW_HIP(ctx, hipStreamSynchronize(ctx->ages_busy));
-            ctx->ages_pending = false;
-        }
-        if (n_max > ctx->ages_cap) {
-            const size_t cap = std::max<size_t>(n_max * 2, 1024);
-            ctx->ages_cap = 0;
-            if ((st = sync(ctx)) || (st = alloc_buf(ctx, ctx->h_ages, cap * sizeof(FwAgeEntry), Mem::pinned)) ||
-                (st = alloc_buf(ctx, ctx->d_ages, cap * sizeof(FwAgeEntry))))
-                return st;
-            ctx->ages_cap = cap;
-        }
-        FwAgeEntry *tab = (FwAgeEntry *)ctx->h_ages.get();
-        uint32_t n = 0;
-        uint64_t live = 0;
-        for (const SegHost::Cohort &c : S.coh) {
-            if (!c.n) continue;
-            tab[n++] = FwAgeEntry{(uint32_t)live, c.age};
-            live += c.n;
-        }
-        if (live > S.capacity) return poison_segment(ctx, si, "a FIFO ring's cohorts hold more particles than the ring");
-        if (n) {
-            FW_HIP(ctx, hipMemcpyAsync(ctx->d_ages, tab, n * sizeof(FwAgeEntry), hipMemcpyHostToDevice, stream));
-            FW_HIP(ctx, fw_launch_fifo_ages(stream, S.buf[0], S.capacity, S.head, (uint32_t)live, ctx->d_ages, n));
-            ctx->ages_pending = true, ctx->ages_busy = stream;
-            ctx->age_launches++;
-        }
+    if (!work) return FW_OK;
+    const size_t need = S.coh.size() * sizeof(E) + tail;
+    char *h;
+    if ((st = T.h.take(ctx, need, std::max(need * 2, floor), &h, &T.d))) return st;
+    uint64_t live = 0;
+    const uint32_t n = build(reinterpret_cast<E *>(h), &live);
+    if (live > S.capacity) return poison_segment(ctx, si, "a FIFO ring's cohorts hold more particles than the ring");
+    if (n) {
+        FW_HIP(ctx, hipMemcpyAsync(T.d, h, n * sizeof(E) + tail, hipMemcpyHostToDevice, stream));
+        FW_HIP(ctx, launch(stream, (uint32_t)live, reinterpret_cast<const E *>(T.d.get()), n));
+        if ((st = T.h.commit(ctx, stream))) return st;
+        T.launches++;
     }
+    return FW_OK;
+}
+
+fw_status ensure_ages(fw_ctx *ctx, uint32_t si, hipStream_t stream) {
+    SegHost &S = ctx->segs[si];
+    if (!S.ages_stale) return FW_OK;
+    fw_status st = replay_cohorts<FwAgeEntry>(
+        ctx, si, stream, S.fifo && !S.coh.empty(), ctx->age_tab, 0, 1024 * sizeof(FwAgeEntry),
+        [&](FwAgeEntry *tab, uint64_t *live) {  // (fw_ages.h)
+            uint32_t n = 0;
+            for (const SegHost::Cohort &c : S.coh) {
+                if (!c.n) continue;
+                tab[n++] = FwAgeEntry{(uint32_t)*live, c.age};
+                *live += c.n;
+            }
+            return n;
+        },
+        [&](hipStream_t s, uint32_t live, const FwAgeEntry *tab, uint32_t n) { return fw_launch_fifo_ages(s, S.buf[0], S.capacity, S.head, live, tab, n); });
+    if (st) return st;
     S.ages_stale = false;
     return FW_OK;
 }
@@ -81,42 +88,21 @@ fw_status ensure_spin(fw_ctx *ctx, uint32_t si, hipStream_t stream, bool keep_st
     SegHost &S = ctx->segs[si];
     if (!keep_streak) S.spin_streak = 0;
     if (!S.spin.stale) return FW_OK;
-    fw_status st;
-    if (!stream) {
-        if ((st = join_side(ctx))) return st;
-        stream = ctx->stream;
-    }
-    // one entry per cohort that holds particles, then the log (fw_spin.h); a ring that was emptied since has nothing to replay
-    const size_t n_max = S.coh.size(), log_n = S.spin.log.size();
-    if (S.fifo && S.axis != 0u && n_max && log_n) {
-        if (ctx->spin_pending) {  // (the previous table may still be on its way to the device)
-            FW_HIP(ctx, hipStreamSynchronize(ctx->spin_busy));
-            ctx->spin_pending = false;
-        }
-        const size_t need = n_max * sizeof(FwSpinEntry) + log_n * sizeof(float);
-        if (need > ctx->spin_cap) {
-            const size_t cap = std::max<size_t>(need * 2, 16384);
-            ctx->spin_cap = 0;
-            if ((st = sync(ctx)) || (st = alloc_buf(ctx, ctx->h_spin, cap, Mem::pinned)) || (st = alloc_buf(ctx, ctx->d_spin, cap))) return st;
-            ctx->spin_cap = cap;
-        }
-        FwSpinEntry *tab = (FwSpinEntry *)ctx->h_spin.get();
-        uint64_t live = 0;
-        const uint32_t n = S.spin.table(S.coh, tab, &live);
-        if (live > S.capacity) return poison_segment(ctx, si, "a FIFO ring's cohorts hold more particles than the ring");
-        if (n) {
-            float *log = (float *)(tab + n);
-            for (size_t k = 0; k < log_n; k++) log[k] = S.spin.log[k];
-            const size_t bytes = n * sizeof(FwSpinEntry) + log_n * sizeof(float);
-            FW_HIP(ctx, hipMemcpyAsync(ctx->d_spin, tab, bytes, hipMemcpyHostToDevice, stream));
-            FW_HIP(ctx, fw_launch_fifo_spin(stream, S.buf[0], S.capacity, S.head, (uint32_t)live, ctx->d_types + S.type_idx, S.axis, ctx->d_spin, n,
-                                            (uint32_t)log_n));
-            ctx->spin_pending = true, ctx->spin_busy = stream;
-            ctx->spin_launches++;
-        }
-    } else if (S.fifo && S.axis == 0u && n_max && log_n) {
-        return poison_segment(ctx, si, "a FIFO ring with a deferred spin lost its axis");
-    }
+    // behind the entries: the log (fw_spin.h); a ring that was emptied since has nothing to replay
+    const size_t log_n = S.spin.log.size();
+    const bool pending = S.fifo && !S.coh.empty() && log_n;
+    fw_status st = replay_cohorts<FwSpinEntry>(
+        ctx, si, stream, pending && S.axis != 0u, ctx->spin_tab, log_n * sizeof(float), 16384,
+        [&](FwSpinEntry *tab, uint64_t *live) {
+            const uint32_t n = S.spin.table(S.coh, tab, live);
+            std::copy(S.spin.log.begin(), S.spin.log.end(), reinterpret_cast<float *>(tab + n));
+            return n;
+        },
+        [&](hipStream_t s, uint32_t live, const FwSpinEntry *tab, uint32_t n) {
+            return fw_launch_fifo_spin(s, S.buf[0], S.capacity, S.head, live, ctx->d_types + S.type_idx, S.axis, tab, n, (uint32_t)log_n);
+        });
+    if (st) return st;
+    if (pending && S.axis == 0u) return poison_segment(ctx, si, "a FIFO ring with a deferred spin lost its axis");
     S.spin.current(S.coh);
     S.spin_last = false;
     return FW_OK;
@@ -241,7 +227,7 @@ fw_status ensure_range_arrays(fw_ctx *ctx) {
         // per-workgroup timestamps of the last range launch (tools/range_timeline.py)
         if ((ctx->dbg & 8u) && (st = alloc_buf(ctx, ctx->d_rts, ncap * 8, Mem::device, true))) return st;
         ctx->rdesc_cap = ncap;
-        ctx->r_force = true, ctx->rtab_pending = false;
+        ctx->r_force = true, ctx->rtab_fence.forget();
     }
     // one record per segment slot + one op per emission entry of the context
     const size_t need = round_up((uint32_t)(ctx->max_seg * sizeof(FwRangeRec)), 64) + (size_t)(ctx->n_emits + 8) * sizeof(FwOp) + 64;
@@ -301,7 +287,7 @@ fw_status ensure_param_ring(fw_ctx *ctx, size_t bytes) {
     ctx->param_bytes = 0;
     for (int i = 0; i < kParamRing; i++) {
         if ((st = alloc_buf(ctx, ctx->h_param[i], nb, Mem::pinned)) || (st = alloc_buf(ctx, ctx->d_param[i], nb))) return st;
-        ctx->consumed_pending[i] = false;
+        ctx->consumed[i].forget();
     }
     ctx->param_bytes = nb;
     return FW_OK;
@@ -322,12 +308,8 @@ fw_status wait_slot_free(fw_ctx *ctx, uint64_t &tag) {
 // it last has been consumed.
 fw_status acquire_slot(fw_ctx *ctx, int *out) {
     const int slot = (int)(ctx->ring_seq++ % kParamRing);
-    if (ctx->consumed_pending[slot]) {
-        FW_HIP(ctx, hipEventSynchronize(ctx->ev_consumed[slot]));
-        ctx->consumed_pending[slot] = false;
-    }
-    fw_status st = wait_slot_free(ctx, ctx->slot_frame[slot]);  // (zero-copy use)
-    if (st) return st;
+    fw_status st;
+    if ((st = ctx->consumed[slot].wait(ctx)) || (st = wait_slot_free(ctx, ctx->slot_frame[slot]))) return st;  // (... zero-copy use)
     *out = slot;
     return FW_OK;
 }

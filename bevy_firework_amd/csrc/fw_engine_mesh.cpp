@@ -52,10 +52,8 @@ fw_status create_mesh(fw_ctx *ctx, const char *who, bool deformable, const float
             const size_t nf = (size_t)n_vertices * 3;
             if ((st = alloc_buf(ctx, m.slots, (size_t)bvh.n_tris)) || (st = alloc_buf(ctx, m.order, (size_t)bvh.n_nodes)) ||
                 (st = alloc_buf(ctx, m.level_off, bvh.level_off.size())) || (st = alloc_buf(ctx, m.xyz, nf)) ||
-                (st = alloc_buf(ctx, m.h_xyz[0], nf, Mem::pinned)) || (st = alloc_buf(ctx, m.h_xyz[1], nf, Mem::pinned)))
+                (st = alloc_buf(ctx, m.h_xyz.h[0], nf, Mem::pinned)) || (st = alloc_buf(ctx, m.h_xyz.h[1], nf, Mem::pinned)))
                 return st;
-            FW_HIP(ctx, m.ev_xyz[0].create());
-            FW_HIP(ctx, m.ev_xyz[1].create());
             FW_HIP(ctx, hipMemcpy(m.slots, bvh.slots.data(), bvh.slots.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
             FW_HIP(ctx, hipMemcpy(m.order, bvh.order.data(), bvh.order.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
             FW_HIP(ctx, hipMemcpy(m.level_off, bvh.level_off.data(), bvh.level_off.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
@@ -81,29 +79,21 @@ fw_status create_mesh(fw_ctx *ctx, const char *who, bool deformable, const float
     }
 }
 
-// The instance set into the staging slot of its turn and, as one copy, into the context's stream: pinned memory, double-buffered,
-// like fw_ctx_set_colliders -- moving instances every frame does not stall the frames in flight.  The device table must hold n.
 // the staging slot of the next set, free and large enough for n instances (the one wait: the copy before the previous one)
-fw_status reserve_staging(fw_ctx *ctx, uint32_t n) {
-    const int slot = (int)(ctx->mesh_seq & 1u);
-    if (ctx->mesh_pending[slot]) {
-        FW_HIP(ctx, hipEventSynchronize(ctx->ev_mesh[slot]));
-        ctx->mesh_pending[slot] = false;
-    }
-    if (!ctx->ev_mesh[slot]) FW_HIP(ctx, ctx->ev_mesh[slot].create());
-    if (n > ctx->h_mesh_inst[slot].cap()) return alloc_buf(ctx, ctx->h_mesh_inst[slot], std::max<size_t>(16, (size_t)n * 2), Mem::pinned);
-    return FW_OK;
+fw_status reserve_staging(fw_ctx *ctx, uint32_t n, FwMeshInst **out = nullptr) {
+    return ctx->h_mesh_inst.take(ctx, n, std::max<size_t>(16, (size_t)n * 2), out);
 }
 
+// The instance set into the staging slot of its turn and, as one copy, into the context's stream, like fw_ctx_set_colliders -- moving
+// instances every frame does not stall the frames in flight.  The device table must hold n.
 fw_status stage_instances(fw_ctx *ctx, const fw_mesh_collider *inst, uint32_t n) {
-    const int slot = (int)(ctx->mesh_seq & 1u);
-    fw_status st = reserve_staging(ctx, n);
+    FwMeshInst *h;
+    fw_status st = reserve_staging(ctx, n, &h);
     if (st) return st;
-    ctx->mesh_seq++;
     for (uint32_t i = 0; i < n; i++) {
         const fw_mesh_collider &c = inst[i];
         const fw_ctx::MeshHost &m = ctx->meshes[c.mesh];
-        FwMeshInst &d = ctx->h_mesh_inst[slot][i];
+        FwMeshInst &d = h[i];
         d = FwMeshInst{};
         memcpy(d.position, c.position, sizeof c.position);
         memcpy(d.rotation, c.rotation, sizeof c.rotation);
@@ -129,14 +119,13 @@ fw_status stage_instances(fw_ctx *ctx, const fw_mesh_collider *inst, uint32_t n)
             d.position[3] = INFINITY, memcpy(d.center, c.position, sizeof c.position);  // (never skipped)
     }
     if (n) {
-        FW_HIP(ctx, hipMemcpyAsync(ctx->d_mesh_inst, ctx->h_mesh_inst[slot], n * sizeof(FwMeshInst), hipMemcpyHostToDevice, ctx->stream));
-        FW_HIP(ctx, hipEventRecord(ctx->ev_mesh[slot], ctx->stream));
-        ctx->mesh_pending[slot] = true;
+        FW_HIP(ctx, hipMemcpyAsync(ctx->d_mesh_inst, h, n * sizeof(FwMeshInst), hipMemcpyHostToDevice, ctx->stream));
+        if ((st = ctx->h_mesh_inst.commit(ctx, ctx->stream))) return st;
         // behind the copy, in the same stream: the spheres of the meshes whose bounds are the device's, one launch per such mesh
         for (uint32_t i = 0; i < n; i++) {
             fw_ctx::MeshHost &m = ctx->meshes[inst[i].mesh];
-            if (!m.dev_bounds || m.sphere_stamp == ctx->mesh_seq) continue;
-            m.sphere_stamp = ctx->mesh_seq;
+            if (!m.dev_bounds || m.sphere_stamp == ctx->h_mesh_inst.turn) continue;
+            m.sphere_stamp = ctx->h_mesh_inst.turn;
             FW_HIP(ctx, fw_launch_mesh_spheres(ctx->stream, ctx->d_mesh_inst, n, m.nodes, m.d_rec, false));
         }
     }
@@ -189,21 +178,14 @@ fw_status fw_ctx_update_mesh_vertices(fw_ctx *ctx, fw_mesh mesh, const float *xy
     const bool placed = std::find(ctx->mesh_set.begin(), ctx->mesh_set.end(), mesh) != ctx->mesh_set.end();
     fw_status st;  // (the one allocation an update can need comes first: a failure leaves the mesh as it was)
     if (placed && (st = reserve_staging(ctx, (uint32_t)ctx->mesh_insts.size()))) return st;
-    // the staging slot of this call's turn: the one wait of the call, and only when the copy before the previous one is still in
-    // flight.  Then ONE pass over the caller's array: finite check, copy into the slot, bounds and pad (a refused call leaves the
-    // slot unused: its turn comes again)
-    const int slot = (int)(m.xyz_seq & 1u);
-    if (m.xyz_pending[slot]) {
-        FW_HIP(ctx, hipEventSynchronize(m.ev_xyz[slot]));
-        m.xyz_pending[slot] = false;
-    }
-    float lo[3], hi[3], pad;
-    const int64_t bad = fw_bvh_stage_vertices(xyz, m.referenced.data(), n_vertices, m.h_xyz[slot], lo, hi, &pad);
+    // the staging slot of this call's turn (sized at creation), then ONE pass over the caller's array: finite check, copy into the
+    // slot, bounds and pad (a refused call leaves the slot unused: its turn comes again)
+    float *h, lo[3], hi[3], pad;
+    if ((st = m.h_xyz.take(ctx, nf, nf, &h))) return st;
+    const int64_t bad = fw_bvh_stage_vertices(xyz, m.referenced.data(), n_vertices, h, lo, hi, &pad);
     if (bad >= 0) return fail(ctx, FW_EINVAL, "fw_ctx_update_mesh_vertices: non-finite vertex " + std::to_string(bad));
-    m.xyz_seq++;
-    FW_HIP(ctx, hipMemcpyAsync(m.xyz, m.h_xyz[slot], nf * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    FW_HIP(ctx, hipEventRecord(m.ev_xyz[slot], ctx->stream));
-    m.xyz_pending[slot] = true;
+    FW_HIP(ctx, hipMemcpyAsync(m.xyz, h, nf * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    if ((st = m.h_xyz.commit(ctx, ctx->stream))) return st;
     // The refit behind the copy, IN PLACE: nodes and triangles are rewritten where the frames walk them.  That is safe because
     // every launch that casts rays runs on this same stream (a colliding ring or small type never goes to the side stream:
     // launch_fifo, fw_ctx::small_last_side), so the frames enqueued before this call have read the old shape before the refit

@@ -441,7 +441,7 @@ fw_status update_tile_table(fw_ctx *ctx) {
         if ((st = alloc_buf(ctx, ctx->d_tile_first, ncap)) || (st = alloc_buf(ctx, ctx->d_tile_keys, ncap))) return st;
         for (int i = 0; i < kTabRing; i++) {
             if ((st = alloc_buf(ctx, ctx->h_tab[i], ncap, Mem::pinned)) || (st = alloc_buf(ctx, ctx->h_keys[i], ncap, Mem::pinned))) return st;
-            ctx->tab_pending[i] = false;
+            ctx->tab_fence[i].forget();
         }
         ctx->tile_first_cap = ncap;
     }
@@ -454,15 +454,12 @@ fw_status update_tile_table(fw_ctx *ctx) {
         if ((st = alloc_buf(ctx, ctx->d_tile_desc, ncap))) return st;
         for (int i = 0; i < kTabRing; i++) {
             if ((st = alloc_buf(ctx, ctx->h_desc[i], ncap, Mem::pinned))) return st;
-            ctx->tab_pending[i] = false;
+            ctx->tab_fence[i].forget();
         }
         ctx->tile_desc_cap = ncap;
     }
     const int slot = (int)(ctx->tab_seq++ % kTabRing);
-    if (ctx->tab_pending[slot]) {
-        FW_HIP(ctx, hipEventSynchronize(ctx->ev_tab[slot]));
-        ctx->tab_pending[slot] = false;
-    }
+    if ((st = ctx->tab_fence[slot].wait(ctx))) return st;
     uint32_t *h = ctx->h_tab[slot];
     uint32_t total = 0;
     for (uint32_t i = 0; i < n_seg; i++) {
@@ -485,9 +482,7 @@ fw_status update_tile_table(fw_ctx *ctx) {
     if (total)
         FW_HIP(ctx, hipMemcpyAsync(ctx->d_tile_desc, hd, (size_t)total * sizeof(uint4), hipMemcpyHostToDevice,
                                    ctx->stream));
-    FW_HIP(ctx, hipEventRecord(ctx->ev_tab[slot], ctx->stream));
-    ctx->tab_pending[slot] = true;
-    return FW_OK;
+    return ctx->tab_fence[slot].mark(ctx, ctx->stream);
 }
 
 // The workgroup table of the range launch (fw_ctx::h_rdesc -> d_rdesc), from the roles each range segment provides for
@@ -501,10 +496,8 @@ fw_status update_tile_table(fw_ctx *ctx) {
 // so that a context with ONE large segment would not start with a front of old tiles -- was measured: 381 -> 384 us
 // at 1 x 16M, 96 -> 100 us at 512 x 8192: no.)  Look-back words are indexed per segment (old_first + k).
 fw_status upload_range_table(fw_ctx *ctx, uint32_t n_seg) {
-    if (ctx->rtab_pending) {  // (one staging buffer: the previous upload must have left it)
-        FW_HIP(ctx, hipEventSynchronize(ctx->ev_rtab));
-        ctx->rtab_pending = false;
-    }
+    fw_status st = ctx->rtab_fence.wait(ctx);  // (one staging buffer: the previous upload must have left it)
+    if (st) return st;
     size_t t = 0;
     bool ok = true;
     auto put = [&](uint32_t si, uint32_t role, uint32_t k) {
@@ -574,8 +567,7 @@ fw_status upload_range_table(fw_ctx *ctx, uint32_t n_seg) {
     if (!ok) return poison_segment(ctx, kNoSeg, "range table overflow");
     ctx->r_total = (uint32_t)t;
     if (t) FW_HIP(ctx, hipMemcpyAsync(ctx->d_rdesc, ctx->h_rdesc, t * sizeof(FwRangeDesc), hipMemcpyHostToDevice, ctx->stream));
-    FW_HIP(ctx, hipEventRecord(ctx->ev_rtab, ctx->stream));
-    ctx->rtab_pending = true;
+    if ((st = ctx->rtab_fence.mark(ctx, ctx->stream))) return st;
     ctx->r_force = false;
     ctx->r_uploads++;
     return FW_OK;

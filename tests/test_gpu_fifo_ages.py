@@ -4,6 +4,8 @@ the same system twice -- with the rule and with FW_AGELESS=0 -- against the CPU 
 read, `age` first of all, must carry the same bits in both runs.  The four-round form is forced at small sizes (FW_FIFO_SMALL=1): a ring
 built with 8192 slots (it grows to what its lifetime needs, 1.5 to 16 frames), ~5000 particles per spawn cohort -- one or two cohort
 boundaries inside a tile -- whose head wraps every few frames.  Needs an MI355X."""
+import dataclasses
+
 import numpy as np
 import pytest
 
@@ -432,3 +434,35 @@ def test_the_depth_order_every_frame_leaves_the_ages_alone(monkeypatch, spin):
         for k, (got, u) in enumerate(zip(orders, off[1])):
             assert np.array_equal(got, first_readers.want_order(u)) and not np.array_equal(got, np.arange(len(u))), f"order {k}"
     first_readers.stale_planes_would_show(off[3], off[2], (0.0, 0.0, 0.0, 1.0) if spin else None, DT)
+
+
+def _two_rings(make, long_frames, per_frame=4.0):
+    """one spawner, two types of `make`, each fed by its own Global entry at `per_frame` particles per frame of dt / 64: 320 frames of
+    life and `long_frames` -- as many spawn cohorts each"""
+    rate = per_frame * 64.0 * 60.0
+    a, b = make(life_frames=5.0, rate=rate), make(life_frames=long_frames / 64.0, rate=rate)
+    return S.ParticleSpawner(a.particle_settings + b.particle_settings,
+                             a.emission_settings + [dataclasses.replace(e, particle_index=1) for e in b.emission_settings])
+
+
+def test_two_rings_are_read_back_to_back(monkeypatch):
+    """two rings of one context after an unread stretch of 1200 frames of dt / 64: the reads write both cohort tables back one right
+    after the other through the ONE staging buffer and the one device table (fw_engine.h: Staging), the second waiting for the fence
+    behind the first's kernel -- and with 1152 cohorts behind 320 it needs more than the 1024 entries the pair starts with: the table
+    grows in between.  Then the same inside a launch: a denormal dt drops the rule for both rings in one frame"""
+    small, tiny = np.float32(DT / 64), np.float32(1e-40)
+
+    def scenario(run):
+        run.step(small, n=1200)
+        launches = run.system.age_launches()
+        run.read("both rings")
+        assert run.system.age_launches() == launches + (2 if run.rule else 0)
+        counts = run.pair.gpu.counts()
+        assert 1150 < counts[0] < 1400 and 4300 < counts[1] < 4900, counts
+        run.step(small, n=5)
+        run.step(tiny)
+        assert run.system.age_launches() == launches + (4 if run.rule else 0)
+        run.read("after the denormal")
+        assert run.system.age_launches() == launches + (4 if run.rule else 0)
+
+    both(monkeypatch, _two_rings(_spawner, 1152), scenario)

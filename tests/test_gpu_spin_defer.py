@@ -565,3 +565,29 @@ def test_the_depth_order_every_frame_leaves_the_spin_deferred(monkeypatch):
         for k, (got, u) in enumerate(zip(orders, off[1])):
             assert np.array_equal(got, first_readers.want_order(u)) and not np.array_equal(got, np.arange(len(u))), f"order {k}"
     first_readers.stale_planes_would_show(off[3], off[2], _rot_about(Y, 0.7), DT)
+
+
+def test_two_rings_are_read_back_to_back(monkeypatch):
+    """two rings of one context whose spin nobody asked for over 2300 frames of dt / 64 (the log reaches its cap on the way: replays inside
+    fw_step), then both read back to back: two tables and logs through the ONE staging buffer and the one device table (fw_engine.h:
+    Staging), the second waiting for the fence behind the first's kernel -- and with 2176 cohorts behind 320 the pair outgrows the
+    16 KiB it starts with while the first's fence is pending.  Then the same inside a launch: a denormal dt ends the deferral of both rings"""
+    from test_gpu_fifo_ages import _two_rings
+
+    small, tiny = np.float32(DT / 64), np.float32(1e-40)
+
+    def scenario(run):
+        run.step(small, n=2300)
+        n = run.spins()
+        assert (n > 0) == run.rule
+        run.read("both rings")
+        assert run.spins() == n + (2 if run.rule else 0)
+        counts = run.pair.gpu.counts()
+        assert 550 < counts[0] < 720 and 4200 < counts[1] < 4500, counts
+        run.step(small, n=5)
+        run.step(tiny)
+        assert run.spins() == n + (4 if run.rule else 0)
+        run.read("after the denormal")
+        assert run.spins() == n + (4 if run.rule else 0)
+
+    both(monkeypatch, _two_rings(_spawner, 2176, per_frame=2.0), scenario)
