@@ -831,6 +831,10 @@ struct fw_ctx {
     bool use_spin_defer = true;
     uint32_t spin_defer_min = 384u * FW_TILE, spin_defer_after = 32u, spin_log_cap = 256u;
     CohortTable spin_tab;
+    // FIFO launches none of whose ring tiles touches rotation or angular velocity run the kernel form compiled for that (FwFifoArgs::
+    // spinless).  FW_SPINLESS=0: they keep the form that finds out per workgroup (A/B in one build)
+    bool use_spinless = true;
+    uint64_t spinless_launches = 0;  // fw_debug_spinless_launches
     bool use_axis = true;      // FW_AXIS_SPIN=0: no ring runs under the axis-spin rule (A/B in one build)
     bool use_derived = true;   // FW_DERIVED=0: every type stores its scale / colour planes, attached instance buffer or not (A/B)
     // Round 6: scale, base colour and emissive colour are pure functions of (age, lifetime, initial_scale) (core.rs:601-605,

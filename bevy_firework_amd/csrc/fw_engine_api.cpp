@@ -207,6 +207,7 @@ fw_status fw_ctx_create(int device, uint32_t seed, void *stream, fw_ctx **out) {
     if (const char *m = getenv("FW_SPIN_DEFER_MIN")) ctx->spin_defer_min = (uint32_t)strtoul(m, nullptr, 10);
     if (const char *m = getenv("FW_SPIN_DEFER_AFTER")) ctx->spin_defer_after = (uint32_t)strtoul(m, nullptr, 10);
     if (const char *m = getenv("FW_SPIN_LOG")) ctx->spin_log_cap = (uint32_t)strtoul(m, nullptr, 10);
+    if (const char *m = getenv("FW_SPINLESS")) ctx->use_spinless = atoi(m) != 0;
     // 0: scale / colour planes always stored; 1: not stored for types with an attached instance buffer; 2 (default): for no type
     if (const char *m = getenv("FW_DERIVED")) ctx->use_derived = atoi(m) != 0, ctx->derive_all = atoi(m) >= 2;
     if (const char *m = getenv("FW_NEST_FUSE")) ctx->nest_fuse = atoi(m) != 0;
@@ -1044,6 +1045,12 @@ fw_status fw_debug_age_launches(fw_ctx *ctx, uint64_t *n) {
 fw_status fw_debug_spin_launches(fw_ctx *ctx, uint64_t *n) {
     if (!ctx || !n) return FW_EINVAL;
     *n = ctx->spin_tab.launches;
+    return FW_OK;
+}
+// FIFO launches so far that ran a SPINLESS form of fw_k_update_fifo (launch_fifo: FwFifoArgs::spinless)
+fw_status fw_debug_spinless_launches(fw_ctx *ctx, uint64_t *n) {
+    if (!ctx || !n) return FW_EINVAL;
+    *n = ctx->spinless_launches;
     return FW_OK;
 }
 fw_status fw_debug_tf_frames(fw_ctx *ctx, uint64_t *n) {

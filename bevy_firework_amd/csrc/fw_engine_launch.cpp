@@ -439,6 +439,7 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
     const bool fifo_coll = fifo_coll_real || fifo_small;  // (the same tile grid; which instantiation runs: FwFifoArgs::any_coll / small_tiles)
     uint32_t f_ops = 0, f_tiles = 0;
     uint64_t f_bytes = 0;  // what the launch streams, roughly: its tiles x the bytes a particle of the type moves
+    bool f_nospin = true;  // every ring of the launch so far carries FW_TYPE_IDX_NOSPIN in it (FwFifoArgs::spinless)
     uint32_t nest_status_next = 0;  // look-back words handed to the Nested entries of this launch so far (FwFifoNest::status_first)
     const uint32_t nest_tag = fr.fuse ? next_nest_seq(ctx) : 0u;
     auto flush = [&]() -> hipError_t {
@@ -449,12 +450,16 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
         fa.done_tag = side ? nullptr : a.done_tag, fa.done_value = a.done_value;
         fa.host_counts = a.host_counts;
         fa.live_out = a.live_out, fa.live_next = a.live_next;
+        // (no ring tile of the launch touches rotation or angular velocity: the kernel form compiled for that -- rings with Q0 in planes,
+        // four-round tiles, no instance records)
+        fa.spinless = (ctx->use_spinless && f_nospin && fa.q0pl && !fa.any_inst && !fa.small_tiles) ? 1u : 0u;
+        ctx->spinless_launches += fa.spinless;
         hipEvent_t e0, e1;
         next_timing_pair(ctx, fr, &e0, &e1);
         const hipError_t e = fw_launch_update_fifo(fstream, ctx->g, fa, fio, f_tiles, f_bytes > ctx->nt_bytes ? 2 : f_bytes > ctx->nt_wo_bytes ? 1 : 0, e0, e1);
         if (side) ctx->side_dirty = true;
         fa = FwFifoArgs{};
-        f_ops = f_tiles = 0, f_bytes = 0;
+        f_ops = f_tiles = 0, f_bytes = 0, f_nospin = true;
         fr.fifo_launched = true;
         return e;
     };
@@ -537,6 +542,7 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
             F.head = S.head, F.n_in = n_in, F.n_spawn = n_spawn, F.dead = dead;
             F.mat = mat ? 1u : 0u;
             fa.q0pl = S.q0pl ? 1u : 0u;  // (the same for every ring of a launch: the two passes)
+            f_nospin &= (F.type_idx & FW_TYPE_IDX_NOSPIN) != 0u;
             F.n_lplanes = S.n_lplanes;
             F.report = S.fifo_dev ? S.h_report + (ctx->frame % kReportRing) : nullptr;
             F.op0 = f_ops;

@@ -226,7 +226,11 @@ __device__ __forceinline__ void fw_fifo_nest_parents(const FwGlobals &g, const F
 // NEST: some Nested entry runs inside this launch (FwFifoArgs::nest): the parents' ring tiles run fw_fifo_nest_parents first
 // Q0PL: every ring of the launch keeps Q0 (position, age) as four component planes (FwFifoArgs::q0pl) -- the rings that may run under the
 // age rule, which the host launches by themselves; never with COLL or NEST
-template <bool INST, int WM, int NT, int COLL, int TR, bool NEST, bool Q0PL = false>
+// SPINLESS: no ring tile of the launch touches rotation or angular velocity (FwFifoArgs::spinless: every ring carries FW_TYPE_IDX_NOSPIN in
+// this launch -- a type that cannot turn, or a spin this launch defers).  The FIFO twin of ALLNOSPIN in fw_k_update_range: what the other
+// forms find out per workgroup is a fact of the instantiation, so a tile reserves no register for Q2 / Q3 -- 88 VGPRs instead of 110, a
+// fifth workgroup per CU.  The spawning workgroups keep the type's true record: a new particle gets its one update whole.
+template <bool INST, int WM, int NT, int COLL, int TR, bool NEST, bool Q0PL = false, bool SPINLESS = false>
 __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl) {
     constexpr int BLK = FW_BLOCK;
     constexpr int NW = BLK / 64;
@@ -271,7 +275,8 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
     // a type that cannot turn (FW_TYPE_NOSPIN): rotation is FwType::const_rot, angular velocity 0, the lifetime the type's one
     // value -- neither the Q2 nor the Q3 plane is read (every lane asks for the tile's first slot instead: one line per
     // wave, loads stay unconditional)
-    const bool nospin = (F.type_idx & FW_TYPE_IDX_NOSPIN) != 0u;
+    static_assert(!SPINLESS || (Q0PL && !INST && TR == FW_ROUNDS), "the spin-less form: streaming launches of rings with Q0 in planes");
+    const bool nospin = SPINLESS || (F.type_idx & FW_TYPE_IDX_NOSPIN) != 0u;  // (only ring tiles ask)
     // a ring under the axis rule (FW_TYPE_IDX_AXIS, fw_device.h: host-proved, per launch): of rotation and angular velocity only the
     // axis' own component -- and the rotation's w -- is loaded; the other registers get the +0 their planes hold.  Workgroup-uniform
     // branches, like nospin: no template parameter, one code for every axis.
@@ -365,7 +370,8 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
     // true record: a new particle gets its one update whole, every plane stored.  Workgroup-uniform, a scalar OR -- compiled into the
     // launches of rings with Q0 in planes alone, the only ones the rule is ever set for (it asks for the age rule): the colliding, the
     // instance-writing float4 and the Nested instantiations keep the parent's code, which the branch cost the Nested one 4.7 % of its time.)
-    if constexpr (Q0PL) {
+    // (SPINLESS: the same OR for every ring tile of the launch, and a fact of the code -- the tiles' copy of the record and of the window, below)
+    if constexpr (Q0PL && !SPINLESS) {
         if (!spawner && nospin && axis != 0u) T.flags |= FW_TYPE_NOSPIN;
     }
     const FwCollArm CA = fw_coll_arm<COLL>(g, F.type_idx & FW_TYPE_IDX_MASK);
@@ -421,6 +427,16 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
             fw_store_destroyed(F.destroyed, buf, C, s, false, T, s_keys, so.q0, so.q1, so.q2, so.q3, age_new, i);
         fw_fifo_inst_out<INST, NT == 2>(F, inst, s_inst_wave, rec, lane, m, alive, i - n_dead);
     } else {
+        // (the record and the window a ring tile works with: the workgroup's own -- or, SPINLESS, copies in which "cannot turn" is known
+        // when the tile's code is compiled: neither fw_integrate_store's spin nor a store to Q2 / Q3 is left in it)
+        FwType Ts;
+        FwOutWin Ws;
+        if constexpr (SPINLESS) {
+            Ts = T, Ts.flags |= FW_TYPE_NOSPIN;
+            Ws = W, Ws.wr2 = false, Ws.wr3 = false;
+        }
+        const FwType &Tt = SPINLESS ? Ts : T;
+        const FwOutWin &Wt = SPINLESS ? Ws : W;
         // ---- (1) records of the particles this update destroys (core.rs:596-599).  Kept out of the streaming loop:
         // memory reads inside a divergent branch make the compiler drain every outstanding load -- the prefetch
         // included -- where the branches join.
@@ -439,7 +455,7 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
                     // (a materialised particle that dies in its first update carries the spawn-time colours and scale, like any
                     // particle born and destroyed in one frame: evaluated, not read -- the planes of a FW_TYPE_DERIVED type
                     // are not maintained, and for everybody else they hold exactly these values)
-                    fw_store_destroyed(F.destroyed, buf, C, s, i < full_from, T, s_keys, q0, q1, q2, q3, q0.w + a.dt, i);
+                    fw_store_destroyed(F.destroyed, buf, C, s, i < full_from, Tt, s_keys, q0, q1, q2, q3, q0.w + a.dt, i);
                 }
             }
         }
@@ -468,19 +484,19 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
             fw_coll_step<COLL>(g, CA, alive, a.dt, q0c, q1c, &cpos, &cvel);
             if (alive) {
                 if FW_DBG(a.dbg, 2u) {  // profiling only: stream without arithmetic
-                    const uint32_t b16 = (s - W.first) * 16u;
-                    if (W.q0pl) {
-                        fw_stc3w<NT == 2>(W.q0, W.cp, b16 / 4u, q0c.x, q0c.y, q0c.z);
-                        if (W.wr_age) fw_st1w<NT == 2>(W.q0 + 3 * W.cp, b16 / 4u, age_new);
+                    const uint32_t b16 = (s - Wt.first) * 16u;
+                    if (Wt.q0pl) {
+                        fw_stc3w<NT == 2>(Wt.q0, Wt.cp, b16 / 4u, q0c.x, q0c.y, q0c.z);
+                        if (Wt.wr_age) fw_st1w<NT == 2>(Wt.q0 + 3 * Wt.cp, b16 / 4u, age_new);
                     } else {
-                        fw_st4w<NT == 2>(W.q0, b16, make_float4(q0c.x, q0c.y, q0c.z, age_new));
+                        fw_st4w<NT == 2>(Wt.q0, b16, make_float4(q0c.x, q0c.y, q0c.z, age_new));
                     }
-                    fw_stc3w<NT == 2>(W.q1, W.cp, b16 / 4u, q1c.x, q1c.y, q1c.z);
-                    if (WM >= 0 ? (WM & 1) != 0 : W.wr5) fw_st4w<NT != 0>(W.q5, b16, q0c);
-                    if (WM >= 0 ? (WM & 2) != 0 : W.wr6) fw_st4w<NT != 0>(W.q6, b16, q1c);
-                    if (WM >= 0 ? (WM & 4) != 0 : T.sc_kind != 0) fw_st1w<NT != 0>(W.s4, (s - W.first) * 4u, q1c.w);
+                    fw_stc3w<NT == 2>(Wt.q1, Wt.cp, b16 / 4u, q1c.x, q1c.y, q1c.z);
+                    if (WM >= 0 ? (WM & 1) != 0 : Wt.wr5) fw_st4w<NT != 0>(Wt.q5, b16, q0c);
+                    if (WM >= 0 ? (WM & 2) != 0 : Wt.wr6) fw_st4w<NT != 0>(Wt.q6, b16, q1c);
+                    if (WM >= 0 ? (WM & 4) != 0 : Tt.sc_kind != 0) fw_st1w<NT != 0>(Wt.s4, (s - Wt.first) * 4u, q1c.w);
                 } else {
-                    fw_integrate_store<true, WM, NT, true>(T, s_keys, a.dt, q0c, q1c, q2c, q3c, age_new, W, s, rec, COLL ? &cpos : nullptr,
+                    fw_integrate_store<true, WM, NT, true>(Tt, s_keys, a.dt, q0c, q1c, q2c, q3c, age_new, Wt, s, rec, COLL ? &cpos : nullptr,
                                                  COLL ? &cvel : nullptr, nullptr, false, i >= full_from, CA.on, INST ? FW_W_MEM : FW_W_MEM_LAZY);
                 }
             }
@@ -531,17 +547,20 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
     }
 }
 
-// (FW_FIFO_WAVES: compile-time A/B -- a minimum of waves per SIMD for the plain streaming instantiations: configs[1]'s grid is 1042
-// workgroups, 18 more than the 1024 slots that 4 workgroups per CU give)
+// (FW_FIFO_WAVES: compile-time A/B -- a minimum of waves per SIMD for the plain streaming instantiations, which sit at 110 VGPRs: 4 waves
+// per SIMD, 4 workgroups per CU, 1024 resident workgroups.  Round 21 measured the grid: configs[1]'s steady launch is 1011 workgroups -- 945
+// ring tiles from the first survivor on plus 66 of new particles -- not the 1042 earlier rounds wrote down, so it never waited for a slot.
+// The SPINLESS forms get their fifth wave from needing 88 registers, not from a pin, and still gain 1.05 us per launch at that grid: the
+// kernel is short of waves in flight, not of slots -- profiles/r21.  Nothing is pinned here.)
 #ifndef FW_FIFO_WAVES
 #define FW_FIFO_WAVES 1
 #endif
 // (the colliding one-round instantiations sit at the 128-register step: with the capsule arm in the cast the instance-writing ones took
 // 130 registers, 4 -> 3 waves per SIMD, until they were asked for four waves like the plain ones -- 128 again, no scratch)
-template <bool INST, int WM, int NT = 0, int COLL = 0, int TR = FW_ROUNDS, bool Q0PL = false>
+template <bool INST, int WM, int NT = 0, int COLL = 0, int TR = FW_ROUNDS, bool Q0PL = false, bool SPINLESS = false>
 __global__ __launch_bounds__(FW_BLOCK) __attribute__((amdgpu_waves_per_eu((!INST && !COLL && TR == FW_ROUNDS) ? FW_FIFO_WAVES : (COLL == 1 && TR == 1) ? 4 : 1)))
 void fw_k_update_fifo(FwGlobals g, FwFifoArgs a, FwInlineOps inl) {
-    fw_update_fifo_body<INST, WM, NT, COLL, TR, false, Q0PL>(g, a, inl);
+    fw_update_fifo_body<INST, WM, NT, COLL, TR, false, Q0PL, SPINLESS>(g, a, inl);
 }
 // ... with Nested entries inside the launch (FwFifoNest).  A kernel of its own so that the plain instantiations keep their code
 // and their register budget; pinned at 4 waves per SIMD (the nest phase took the four-round form to 133 VGPRs: the bulk of such
@@ -1095,6 +1114,9 @@ void fw_k_update_range(FwGlobals g, FwRangeArgs a) {
 }
 
 // ---- launch wrappers
+// (FW_RINGS_TEMPLATES_ONLY: a translation unit that includes this file for the kernel templates alone and instantiates the few it wants to
+// look at -- tests/test_rings_occupancy.py reads the compiler's resource remarks of the headline forms in seconds instead of the unit's minutes)
+#ifndef FW_RINGS_TEMPLATES_ONLY
 
 // the launches without a collider or a Nested entry; Q0PL: every ring of the launch keeps Q0 in component planes (FwFifoArgs::q0pl)
 template <bool Q0PL>
@@ -1106,6 +1128,21 @@ static hipError_t fw_launch_update_fifo_plain(hipStream_t s, const FwGlobals &g,
         else
             FW_LAUNCH_T((fw_k_update_fifo<false, -1, 0, 0, 1, Q0PL>), grid, block, s, e0, e1, g, a, inl);
         return hipGetLastError();
+    }
+    if constexpr (Q0PL) {
+        // no ring tile of the launch touches rotation or angular velocity (FwFifoArgs::spinless; the host sets it for launches without an
+        // instance buffer only): the forms compiled for that -- five workgroups per CU
+        if (a.spinless && !a.any_inst) {
+            if (nt == 2)
+                FW_LAUNCH_T((fw_k_update_fifo<false, -1, 2, 0, FW_ROUNDS, true, true>), grid, block, s, e0, e1, g, a, inl);
+            else if (nt)
+                FW_LAUNCH_T((fw_k_update_fifo<false, -1, 1, 0, FW_ROUNDS, true, true>), grid, block, s, e0, e1, g, a, inl);
+            else if (a.write_mask == 0)
+                FW_LAUNCH_T((fw_k_update_fifo<false, 0, 0, 0, FW_ROUNDS, true, true>), grid, block, s, e0, e1, g, a, inl);
+            else
+                FW_LAUNCH_T((fw_k_update_fifo<false, -1, 0, 0, FW_ROUNDS, true, true>), grid, block, s, e0, e1, g, a, inl);
+            return hipGetLastError();
+        }
     }
     if (nt) {  // non-temporal forms (fw_ld4w): the generic write mask only -- beyond the Infinity Cache the compile-time one buys nothing
         if (a.any_inst && nt == 2)
@@ -1252,4 +1289,4 @@ hipError_t fw_launch_update_range(hipStream_t s, const FwGlobals &g, const FwRan
     else fw_launch_update_range_t<0>(s, g, a, all_nospin, e0, e1);
     return hipGetLastError();
 }
-
+#endif  // FW_RINGS_TEMPLATES_ONLY

@@ -250,6 +250,10 @@ struct FwFifoArgs {
                                        // SegHost::q0pl: the rings that may run under the age rule -- the host launches them by themselves,
                                        // never with a collider or a Nested entry: the Q0PL instantiations); 0: none does
     FwFifoNest nest[FW_FIFO_NEST_MAX];
+    uint32_t spinless;                 // 1: EVERY ring of this q0pl launch carries FW_TYPE_IDX_NOSPIN in it (a type that cannot turn, or a spin
+                                       // the launch defers), none has an instance buffer, four-round tiles: no ring tile touches Q2 / Q3 -- the
+                                       // SPINLESS instantiations, compiled without registers for them (fw_k_rings.hip); 0: the workgroups find out
+                                       // (behind everything else: no other field of the kernel argument moves)
 };
 
 // ---- range rings: particle types whose lifetime is a RANGE, updated in place ---------------------------------------

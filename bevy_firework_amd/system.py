@@ -538,6 +538,13 @@ class ParticleSystem:
         self._check(self._lib.fw_debug_spin_launches(self._ctx, C.byref(n)))
         return int(n.value)
 
+    def spinless_launches(self) -> int:
+        """FIFO launches so far that ran the kernel form compiled for launches whose ring tiles touch neither rotation nor angular
+        velocity (every ring cannot turn or has its spin deferred)"""
+        n = C.c_uint64()
+        self._check(self._lib.fw_debug_spinless_launches(self._ctx, C.byref(n)))
+        return int(n.value)
+
     def recovered_rings(self) -> int:
         """rings moved to the compacting path (particles kept) because a cohort report was missing when it was due"""
         n = C.c_uint64()

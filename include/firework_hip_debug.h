@@ -73,6 +73,11 @@ fw_status fw_debug_age_launches(fw_ctx *ctx, uint64_t *n);
  * fw_spawner_aabb or a call that only asks for counts */
 fw_status fw_debug_spin_launches(fw_ctx *ctx, uint64_t *n);
 
+/* *n = FIFO launches so far that ran the kernel form compiled for launches in which no ring tile touches rotation or angular velocity
+ * (DESIGN.md 4.0, round 21): every ring of the launch cannot turn or has its spin deferred in it, none has an instance buffer attached,
+ * four-round tiles.  FW_SPINLESS=0 (with FW_ENABLE_KNOBS) keeps such launches on the form that finds out per workgroup: 0 then */
+fw_status fw_debug_spinless_launches(fw_ctx *ctx, uint64_t *n);
+
 /* *on = 1: the context keeps the per-frame records of its range launches and its small op tables in DEVICE memory that the host writes
  * through the large BAR; 0: in pinned host memory (the platform does not map device memory for the host, or
  * FW_PARAM_BAR=0) */
