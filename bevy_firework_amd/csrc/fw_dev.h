@@ -453,6 +453,22 @@ __device__ __forceinline__ FwSpin fw_spin_step(const FwType &T, float dt, float4
     return o;
 }
 
+// one frame of a particle's translation without a collider: explicit Euler with the OLD velocity (core.rs:626-631, 641-643).  The statements
+// of fw_integrate_store, which keeps its own: routed through this definition, 20 existing kernels -- the colliding ring forms and the small
+// types' -- changed their register counts (profiles/r22/move_step_shared.txt), and the round may not move them.  The fused two-frame form
+// of the FIFO kernel runs these for the first frame of a pair -- no contraction in this build: the same bits
+struct FwMove {
+    float px, py, pz, vx, vy, vz;
+};
+__device__ __forceinline__ FwMove fw_move_step(const FwType &T, float dt, float4 q0, float4 q1) {
+    FwMove o;
+    o.px = q0.x + q1.x * dt, o.py = q0.y + q1.y * dt, o.pz = q0.z + q1.z * dt;
+    o.vx = q1.x + (T.acc[0] - q1.x * T.lin_drag) * dt;
+    o.vy = q1.y + (T.acc[1] - q1.y * T.lin_drag) * dt;
+    o.vz = q1.z + (T.acc[2] - q1.z * T.lin_drag) * dt;
+    return o;
+}
+
 // INPLACE (FIFO segments, fw_k_update_fifo): the output slot is the input slot, so a plane whose new value is
 // bit-identical to the loaded one for every lane of the wave is not written (rotation and angular velocity of particles
 // that do not spin, the scale under a constant curve); rotation and angular velocity, whose components are planes of their own, are

@@ -51,6 +51,7 @@
 #include "fw_math.h"
 #include "fw_ages.h"
 #include "fw_spin.h"
+#include "fw_fuse2.h"
 #include "fw_sort.h"
 
 namespace fwh {
@@ -489,6 +490,7 @@ struct alignas(64) SegHost {
     FwSpinBook spin;
     uint32_t spin_streak = 0;
     bool spin_last = false;
+    bool fuse_last = false;  // the latest launch ran two frames of the ring in one pass (fw_ctx::pend): fw_debug_update_path
     bool q0pl = false;  // the ring keeps Q0 (position, age) as four component planes (FwSeg::cpl bit 2): set where the ring is built
     // A ring in a spawner WITH Nested entries: in frames that run the Nested pass its new particles are materialised in
     // the ring before the update (fw_k_spawn / fw_k_nest address it through the head) and fw_k_update_fifo gives them
@@ -835,6 +837,22 @@ struct fw_ctx {
     // spinless).  FW_SPINLESS=0: they keep the form that finds out per workgroup (A/B in one build)
     bool use_spinless = true;
     uint64_t spinless_launches = 0;  // fw_debug_spinless_launches
+    // Two frames of unread rings in one launch (fw_fuse2.h).  A frame whose only GPU work would be one spin-less FIFO launch
+    // of rings that all deferred their spin in it -- each with at least fuse2_min live particles (FW_FUSE2_MIN: its own knob, the default
+    // of spin_defer_min) -- is WITHHELD: all of its bookkeeping done, the complete launch kept here instead of enqueued.  The next fw_step
+    // runs both frames in one launch when it qualifies too and the pair passes fw_fuse2_ok; anything else that touches the stream or
+    // particle state enqueues the kept launch first, exactly as built (flush_withheld).  Depth one.  FW_FUSE2=0: nothing is withheld.
+    bool use_fuse2 = true;
+    uint32_t fuse2_min = 384u * FW_TILE;
+    struct PendingFifo {
+        bool on = false;
+        FwFifoArgs fa;
+        FwInlineOps fio;
+        uint32_t tiles = 0, n_ops = 0;
+        int nt = 0;
+        uint64_t frame = 0;  // fw_ctx::frame of the withheld frame (what its cohorts carry)
+    } pend;
+    uint64_t fused_launches = 0, fuse2_flushed = 0;  // fw_debug_fuse2: launches that ran two frames / withheld frames enqueued alone
     bool use_axis = true;      // FW_AXIS_SPIN=0: no ring runs under the axis-spin rule (A/B in one build)
     bool use_derived = true;   // FW_DERIVED=0: every type stores its scale / colour planes, attached instance buffer or not (A/B)
     // Round 6: scale, base colour and emissive colour are pure functions of (age, lifetime, initial_scale) (core.rs:601-605,
@@ -1174,6 +1192,10 @@ inline fw_status Fence::mark(fw_ctx *ctx, hipStream_t stream) {
 }
 
 fw_status sync(fw_ctx *ctx);  // (fw_engine_mem.cpp)
+// a withheld frame (fw_ctx::pend) goes to the stream, exactly as built: before anything else that touches the stream or particle state
+fw_status flush_withheld(fw_ctx *ctx);  // (fw_engine_launch.cpp)
+// ... or is dropped with the particles it would have updated (the spawner is rebuilt, the context destroyed)
+void drop_withheld(fw_ctx *ctx);
 template <typename T, int N>
 fw_status Staging<T, N>::take(fw_ctx *ctx, size_t n, size_t grow_to, T **out, HipBuf<T> *dev) {
     HipBuf<T> &b = h[turn % N];
@@ -1264,6 +1286,7 @@ struct FwFrame {
     int snap = -1;         // the snapshot row the frame's launches fill (-1: none)
     bool timed = false;    // a launch of the frame carries a timing pair
     bool fifo_launched = false, range_launched = false, small_launched = false;
+    bool quiet = false;  // the frame's only GPU work can be one FIFO launch: it may be withheld, or take the withheld one in (enqueue_frame)
     std::chrono::steady_clock::time_point prof_t;
     // FW_HOST_PROF: the time since the previous point goes to column i
     void prof(fw_ctx *ctx, int i) {

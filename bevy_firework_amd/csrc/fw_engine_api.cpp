@@ -77,6 +77,7 @@ static bool begin_call(fw_ctx *ctx, fw_spawner h, SpawnerCall &r, Then then, Age
     if (!r.sp || !args_ok(*r.sp)) return r.st = FW_EINVAL, false;
     if (poll_device_error(ctx), r.sp->poisoned) return r.st = poisoned_status(ctx), false;
     hipSetDevice(ctx->device);
+    if ((r.st = flush_withheld(ctx))) return false;  // (a withheld frame goes to the stream before anybody looks: fw_ctx::pend)
     for (size_t t = 0; ages != Ages::leave && t < r.sp->seg.size(); t++)
         if ((ages == Ages::write && (r.st = ensure_spin(ctx, r.sp->seg[t]))) || (r.st = ensure_ages(ctx, r.sp->seg[t]))) return false;
     r.st = then == Then::sync ? sync(ctx) : then == Then::join ? join_side(ctx) : then == Then::counts ? read_counts(ctx, r.c) : FW_OK;
@@ -208,6 +209,8 @@ fw_status fw_ctx_create(int device, uint32_t seed, void *stream, fw_ctx **out) {
     if (const char *m = getenv("FW_SPIN_DEFER_AFTER")) ctx->spin_defer_after = (uint32_t)strtoul(m, nullptr, 10);
     if (const char *m = getenv("FW_SPIN_LOG")) ctx->spin_log_cap = (uint32_t)strtoul(m, nullptr, 10);
     if (const char *m = getenv("FW_SPINLESS")) ctx->use_spinless = atoi(m) != 0;
+    if (const char *m = getenv("FW_FUSE2")) ctx->use_fuse2 = atoi(m) != 0;
+    if (const char *m = getenv("FW_FUSE2_MIN")) ctx->fuse2_min = (uint32_t)strtoul(m, nullptr, 10);
     // 0: scale / colour planes always stored; 1: not stored for types with an attached instance buffer; 2 (default): for no type
     if (const char *m = getenv("FW_DERIVED")) ctx->use_derived = atoi(m) != 0, ctx->derive_all = atoi(m) >= 2;
     if (const char *m = getenv("FW_NEST_FUSE")) ctx->nest_fuse = atoi(m) != 0;
@@ -243,6 +246,7 @@ fw_status fw_ctx_create(int device, uint32_t seed, void *stream, fw_ctx **out) {
 fw_status fw_ctx_destroy(fw_ctx *ctx) {
     if (!ctx) return FW_EINVAL;
     hipSetDevice(ctx->device);
+    drop_withheld(ctx);  // (a withheld frame goes with the particles)
     if (ctx->host_prof && ctx->prof_frames) {
         static const char *names[10] = {"windows+reset", "spawner loop", "tile table", "commit", "args", "op tables", "launch", "post", "", ""};
         fprintf(stderr, "[fw] host half of fw_step over %llu frames (ns per frame):", (unsigned long long)ctx->prof_frames);
@@ -269,6 +273,7 @@ fw_status fw_ctx_synchronize(fw_ctx *ctx) {
 fw_status fw_ctx_set_colliders(fw_ctx *ctx, const fw_collider *colliders, uint32_t n) {
     if (!ctx || (n && !colliders)) return fail(ctx, FW_EINVAL, "bad collider set");
     hipSetDevice(ctx->device);
+    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::pend)
     for (uint32_t i = 0; i < n; i++)
         if (colliders[i].kind < FW_COLLIDER_PLANE || colliders[i].kind > FW_COLLIDER_CAPSULE)
             return fail(ctx, FW_EINVAL, "unknown collider kind");
@@ -312,6 +317,7 @@ fw_status fw_ctx_set_colliders(fw_ctx *ctx, const fw_collider *colliders, uint32
 fw_status fw_spawner_create(fw_ctx *ctx, const fw_spawner_desc *desc, fw_spawner *out) {
     if (!ctx || !out) return FW_EINVAL;
     hipSetDevice(ctx->device);
+    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::pend)
     fw_status st = validate_desc(ctx, desc);
     if (st) return st;
     if ((st = sync(ctx))) return st;
@@ -341,6 +347,7 @@ fw_status fw_spawner_update_settings(fw_ctx *ctx, fw_spawner h, const fw_spawner
     SpawnerHost *sp = get_spawner(ctx, h);
     if (!sp) return FW_EINVAL;
     hipSetDevice(ctx->device);
+    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::pend)
     fw_status st = validate_desc(ctx, desc);
     if (st) return st;
     if ((st = sync(ctx))) return st;
@@ -385,6 +392,7 @@ fw_status fw_spawner_destroy(fw_ctx *ctx, fw_spawner h) {
     SpawnerHost *sp = get_spawner(ctx, h);
     if (!sp) return FW_EINVAL;
     hipSetDevice(ctx->device);
+    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::pend)
     fw_status st = sync(ctx);
     if (st) return st;
     if (sp->poisoned && (st = clear_poison_report(ctx))) return st;
@@ -827,6 +835,7 @@ fw_status fw_ctx_track_aabbs(fw_ctx *ctx, int32_t enable) {
 fw_status fw_ctx_live_count(fw_ctx *ctx, uint64_t *out) {
     if (!ctx || !out) return FW_EINVAL;
     hipSetDevice(ctx->device);
+    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::pend)
     std::vector<uint32_t> c;
     fw_status st = read_counts(ctx, c);
     if (st && st != FW_ECAPACITY) return st;
@@ -840,6 +849,7 @@ fw_status fw_ctx_live_count(fw_ctx *ctx, uint64_t *out) {
 fw_status fw_ctx_live_count_device(fw_ctx *ctx, void *d_out_u64) {
     if (!ctx || !d_out_u64) return FW_EINVAL;
     hipSetDevice(ctx->device);
+    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::pend)
     fw_status jst = join_side(ctx);  // the counts of ring segments are written by the side stream's launches
     if (jst) return jst;
     FW_HIP(ctx, fw_launch_total(ctx->stream, count_slot(ctx), (uint32_t)ctx->segs.size(), (unsigned long long *)d_out_u64));
@@ -849,6 +859,7 @@ fw_status fw_ctx_live_count_device(fw_ctx *ctx, void *d_out_u64) {
 fw_status fw_ctx_live_count_ring(fw_ctx *ctx, void *d_ring_u64, uint32_t n_slots) {
     if (!ctx || (d_ring_u64 && n_slots < 2)) return FW_EINVAL;
     hipSetDevice(ctx->device);
+    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::pend)
     fw_status st = sync(ctx);
     if (!st && d_ring_u64) FW_HIP(ctx, hipDeviceSynchronize());  // (the caller's zero-fill of the ring, on whatever stream)
     if (st) return st;
@@ -862,6 +873,7 @@ fw_status fw_ctx_live_count_ring(fw_ctx *ctx, void *d_ring_u64, uint32_t n_slots
 fw_status fw_ctx_last_step_updated(fw_ctx *ctx, uint64_t *out) {
     if (!ctx || !out) return FW_EINVAL;
     hipSetDevice(ctx->device);
+    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::pend)
     fw_status st = sync(ctx);
     if (st) return st;
     return read_stat_total(ctx, out);
@@ -870,6 +882,7 @@ fw_status fw_ctx_last_step_updated(fw_ctx *ctx, uint64_t *out) {
 fw_status fw_ctx_kernel_timing(fw_ctx *ctx, int32_t enable) {
     if (!ctx) return FW_EINVAL;
     hipSetDevice(ctx->device);
+    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::pend)
     fw_status st = sync(ctx);
     if (st) return st;
     if (enable && ctx->tev.empty()) {
@@ -902,6 +915,7 @@ fw_status fw_ctx_kernel_timing(fw_ctx *ctx, int32_t enable) {
 fw_status fw_ctx_kernel_timing_read(fw_ctx *ctx, double *ms_total, uint64_t *launches, uint64_t *particles) {
     if (!ctx) return FW_EINVAL;
     hipSetDevice(ctx->device);
+    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::pend)
     fw_status st = sync(ctx);
     if (st) return st;
     double ms = 0;
@@ -1012,6 +1026,9 @@ fw_status fw_debug_update_path(fw_ctx *ctx, fw_spawner h, uint32_t type, int32_t
     }
     // an attached instance buffer: the update also writes the 64-byte ParticleInstance record of every survivor (render.rs:95-103)
     if (S.inst != nullptr) moved += 64u, algo += 64u;
+    // (round 22, a FIFO ring whose latest launch ran two frames of it -- SegHost::fuse_last, never with an instance buffer: one load and
+    // one store of every plane the launch moves for two updates of the particle)
+    if (S.fifo && S.fuse_last) moved /= 2u, algo /= 2u;
     if (moved_bytes) *moved_bytes = moved;
     if (algorithmic_bytes) *algorithmic_bytes = algo;
     return FW_OK;
@@ -1053,6 +1070,13 @@ fw_status fw_debug_spinless_launches(fw_ctx *ctx, uint64_t *n) {
     *n = ctx->spinless_launches;
     return FW_OK;
 }
+// FIFO launches so far that ran two frames in one pass (fw_ctx::pend, FwFifoArgs::fused) / withheld frames that went to the stream alone
+fw_status fw_debug_fuse2(fw_ctx *ctx, uint64_t *fused, uint64_t *flushed) {
+    if (!ctx) return FW_EINVAL;
+    if (fused) *fused = ctx->fused_launches;
+    if (flushed) *flushed = ctx->fuse2_flushed;
+    return FW_OK;
+}
 fw_status fw_debug_tf_frames(fw_ctx *ctx, uint64_t *n) {
     if (!ctx || !n) return FW_EINVAL;
     *n = ctx->tf_frames;
@@ -1076,6 +1100,7 @@ fw_status fw_ctx_kernel_timing_overhead(fw_ctx *ctx, double *ms_per_pair) {
 fw_status fw_ctx_measure_copy_bandwidth(fw_ctx *ctx, uint64_t bytes, int32_t iters, double *bytes_per_s) {
     if (!ctx || !bytes_per_s || bytes < 4096 || iters < 1) return FW_EINVAL;
     hipSetDevice(ctx->device);
+    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::pend)
     bytes &= ~(uint64_t)0xFFF;
     HipBuf<char> a, b;
     fw_status st = alloc_buf(ctx, a, bytes);

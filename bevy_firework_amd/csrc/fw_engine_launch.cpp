@@ -410,6 +410,64 @@ fw_status take_report(fw_ctx *ctx, uint32_t si, Cohort &c, const char *what) {
     return FW_OK;
 }
 
+// Two frames in one launch (fw_ctx::pend, fw_fuse2.h): B -- the launch `fa` / `fio` this frame has just built, complete -- takes the
+// withheld frame A in when every ring of B is the ring of A at the same place, the pair passes fw_fuse2_ok and the ops of both fit.
+// The fused launch is B's with A's head, live count, input row and dt in front; A's ops first, B's behind them (rel_base shifted by
+// A's new particles).  false: declined, nothing changed.
+bool fuse_pair(fw_ctx *ctx, FwFifoArgs &fa, FwInlineOps &fio, uint32_t n_ops, uint32_t *tiles) {
+    const fw_ctx::PendingFifo &P = ctx->pend;
+    if (P.fa.n_segs != fa.n_segs || P.n_ops + n_ops > FW_INLINE_OPS || P.fa.write_mask != fa.write_mask) return false;
+    for (uint32_t j = 0; j < fa.n_segs; j++) {
+        const FwFifoSeg &A = P.fa.s[j], &B = fa.s[j];
+        if (A.buf != B.buf || A.seg != B.seg || A.capacity != B.capacity || A.type_idx != B.type_idx || A.keys_off != B.keys_off ||
+            A.keys_len != B.keys_len || A.life != B.life || A.mat || B.mat || A.destroyed || B.destroyed || A.nest || B.nest)
+            return false;
+        if (!fw_fuse2_ok(B.capacity, FwFifoFrame{A.head, A.n_in, A.n_spawn, A.dead}, FwFifoFrame{B.head, B.n_in, B.n_spawn, B.dead})) return false;
+    }
+    FwInlineOps ops;
+    uint32_t n = 0, t = 0;
+    for (uint32_t j = 0; j < fa.n_segs; j++) {
+        const FwFifoSeg &A = P.fa.s[j];
+        FwFifoSeg &F = fa.s[j];
+        const uint32_t o0 = n;
+        for (uint32_t x = A.op0; x < A.op1; x++) ops.ops[n++] = P.fio.ops[x];
+        for (uint32_t x = F.op0; x < F.op1; x++) ops.ops[n] = fio.ops[x], ops.ops[n++].rel_base += A.n_spawn;
+        const FwFifoFrame U = fw_fuse2_frame(FwFifoFrame{A.head, A.n_in, A.n_spawn, A.dead}, FwFifoFrame{F.head, F.n_in, F.n_spawn, F.dead});
+        const FwFifoLayout L = fw_fifo_layout(F.capacity, FW_TILE, FW_BLOCK, U.head, U.dead, U.n_in, U.n_in, U.n_spawn);
+        F.head = U.head, F.n_in = U.n_in, F.n_spawn = U.n_spawn, F.dead = U.dead;
+        fa.fuse_spawn[j] = A.n_spawn, fa.fuse_dead[j] = A.dead;
+        F.op0 = o0, F.op1 = n;
+        F.spawn_a = L.spawn_a, F.n_vt_a = L.n_vt_a, F.n_vt_b = L.n_vt_b, F.tile0 = L.tile0, F.n_tiles = L.n_tiles;
+        F.tile_first = t;
+        t += F.n_tiles;
+    }
+    fio = ops;
+    fa.parity = P.fa.parity, fa.dt_a = P.fa.dt, fa.fused = 1u;
+    *tiles = t;
+    return true;
+}
+
+}  // namespace
+
+namespace fwh {
+
+fw_status flush_withheld(fw_ctx *ctx) {
+    fw_ctx::PendingFifo &P = ctx->pend;
+    if (!P.on) return FW_OK;
+    P.on = false;
+    ctx->fuse2_flushed++;
+    for (uint32_t j = 0; j < P.fa.n_segs; j++)
+        if (P.fa.s[j].seg < ctx->segs.size()) ctx->segs[P.fa.s[j].seg].fuse_last = false;
+    FW_HIP(ctx, fw_launch_update_fifo(ctx->stream, ctx->g, P.fa, P.fio, P.tiles, P.nt, nullptr, nullptr));
+    return FW_OK;
+}
+
+void drop_withheld(fw_ctx *ctx) { ctx->pend.on = false; }
+
+}  // namespace fwh
+
+namespace {
+
 // ---- FIFO segments: in place, everything they need in the kernel arguments (fw_kernels.h: FwFifoSeg)
 fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
     const FwUpdateArgs &a = fr.a;
@@ -440,10 +498,19 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
     uint32_t f_ops = 0, f_tiles = 0;
     uint64_t f_bytes = 0;  // what the launch streams, roughly: its tiles x the bytes a particle of the type moves
     bool f_nospin = true;  // every ring of the launch so far carries FW_TYPE_IDX_NOSPIN in it (FwFifoArgs::spinless)
+    // two frames in one launch (fw_ctx::pend): every ring of the launch so far deferred its spin in it and holds fuse2_min particles; the
+    // launches of this frame so far; what a cohort this frame spawns carries as its spin pointer, per ring of the launch
+    bool f_fusable = true;
+    uint32_t n_launches = 0;
+    uint64_t f_spin_from[FW_FIFO_PER_LAUNCH] = {};
+    // (a frame whose only GPU work is this one launch: no compacting, range or small segment, no separate pass, no colour fill, nobody
+    // who wants a count or a time per frame)
+    const bool quiet = fr.quiet && fr.spawn_form == FW_SPAWN_NONE && !side;
+    if (!quiet && (st = flush_withheld(ctx))) return st;
     uint32_t nest_status_next = 0;  // look-back words handed to the Nested entries of this launch so far (FwFifoNest::status_first)
     const uint32_t nest_tag = fr.fuse ? next_nest_seq(ctx) : 0u;
-    auto flush = [&]() -> hipError_t {
-        if (!fa.n_segs) return hipSuccess;
+    auto flush = [&]() -> fw_status {
+        if (!fa.n_segs) return FW_OK;
         fa.parity = fr.p, fa.epoch = a.epoch, fa.dbg = ctx->dbg, fa.dt = dt;
         // (the pinned "frame F has started" word recycles host buffers the GENERAL launch reads: when the two launches
         // run on different streams only that one reports)
@@ -453,15 +520,44 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
         // (no ring tile of the launch touches rotation or angular velocity: the kernel form compiled for that -- rings with Q0 in planes,
         // four-round tiles, no instance records)
         fa.spinless = (ctx->use_spinless && f_nospin && fa.q0pl && !fa.any_inst && !fa.small_tiles) ? 1u : 0u;
-        ctx->spinless_launches += fa.spinless;
-        hipEvent_t e0, e1;
-        next_timing_pair(ctx, fr, &e0, &e1);
-        const hipError_t e = fw_launch_update_fifo(fstream, ctx->g, fa, fio, f_tiles, f_bytes > ctx->nt_bytes ? 2 : f_bytes > ctx->nt_wo_bytes ? 1 : 0, e0, e1);
+        const int nt = f_bytes > ctx->nt_bytes ? 2 : f_bytes > ctx->nt_wo_bytes ? 1 : 0;
+        // the frame's one launch, spin-less, every ring unread and large: it may wait for the next frame, or take the waiting one in
+        const bool candidate = fw_fuse2_candidate(ctx->use_fuse2, quiet, n_launches == 0 && fa.n_segs == ctx->n_fifo, fa.spinless != 0u, f_fusable);
+        n_launches++;
+        fr.fifo_launched = true;
+        fw_status fst = FW_OK;
+        if (ctx->pend.on && candidate && fuse_pair(ctx, fa, fio, f_ops, &f_tiles)) {
+            // (the cohort the withheld frame spawned got both frames' spin from the launch: its pointer is this frame's cohort's)
+            for (uint32_t j = 0; j < fa.n_segs; j++) {
+                SegHost &S = ctx->segs[fa.s[j].seg];
+                for (auto c = S.coh.rbegin(); c != S.coh.rend() && c->frame >= ctx->pend.frame; ++c)
+                    if (c->frame == ctx->pend.frame) c->spin_from = f_spin_from[j];
+                S.fuse_last = true;
+            }
+            ctx->pend.on = false;
+            ctx->fused_launches++, ctx->spinless_launches++;
+            FW_HIP(ctx, fw_launch_update_fifo(fstream, ctx->g, fa, fio, f_tiles, nt, nullptr, nullptr));
+        } else if ((fst = flush_withheld(ctx))) {
+            return fst;
+        } else if (candidate) {
+            // withheld: the complete launch is kept.  It arms no snapshot row and reports no counts (the launch that runs the frame,
+            // fused or alone, leaves the device's counters as they must be; a row nobody fills would stay armed)
+            fa.host_counts = nullptr;
+            fr.snap = -1, fr.a.host_counts = nullptr;
+            fw_ctx::PendingFifo &P = ctx->pend;
+            P.fa = fa, P.fio = fio, P.tiles = f_tiles, P.n_ops = f_ops, P.nt = nt, P.frame = ctx->frame, P.on = true;
+            ctx->spinless_launches++;
+        } else {
+            ctx->spinless_launches += fa.spinless;
+            for (uint32_t j = 0; j < fa.n_segs; j++) ctx->segs[fa.s[j].seg].fuse_last = false;
+            hipEvent_t e0, e1;
+            next_timing_pair(ctx, fr, &e0, &e1);
+            FW_HIP(ctx, fw_launch_update_fifo(fstream, ctx->g, fa, fio, f_tiles, nt, e0, e1));
+        }
         if (side) ctx->side_dirty = true;
         fa = FwFifoArgs{};
-        f_ops = f_tiles = 0, f_bytes = 0, f_nospin = true;
-        fr.fifo_launched = true;
-        return e;
+        f_ops = f_tiles = 0, f_bytes = 0, f_nospin = true, f_fusable = true;
+        return FW_OK;
     };
     // (two passes: the rings that keep Q0 in planes -- SegHost::q0pl, the ones that may run under the age rule -- get a launch of their own,
     // behind everybody else's: the colliding and the Nested instantiations of the kernel never meet that layout)
@@ -473,7 +569,7 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
             for (const FwOp &op : ctx->fifo_ops) k_ops += op.seg == si ? 1u : 0u;
             if (k_ops > FW_INLINE_OPS)  // (build_spawner never makes such a type a ring)
                 return poison_segment(ctx, si, "a FIFO ring with more spawn ops than its launch can carry");
-            if (fa.n_segs == FW_FIFO_PER_LAUNCH || f_ops + k_ops > FW_INLINE_OPS) FW_HIP(ctx, flush());
+            if ((fa.n_segs == FW_FIFO_PER_LAUNCH || f_ops + k_ops > FW_INLINE_OPS) && (st = flush())) return st;
             const int32_t wm = S.derived ? 0 : S.fifo_wm;  // (FW_TYPE_DERIVED: none of the optional planes is stored)
             if (!fa.n_segs) fa.write_mask = wm;
             else if (fa.write_mask != wm) fa.write_mask = -1;
@@ -513,6 +609,8 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
             }
             const uint64_t spin_from_new = spin_defer ? S.spin.defer(S.coh, dt) : S.spin.end();
             S.spin_last = spin_defer;
+            f_fusable &= spin_defer && n_in >= ctx->fuse2_min;
+            f_spin_from[fa.n_segs] = spin_from_new;
             // the cohorts age by this dt exactly as their particles do (fp32 additions, fw_survives); the oldest die first
             if (S.fifo_dev) {
                 S.coh.push_back(SegHost::Cohort{0u, 0.0f, ctx->frame, false});  // size: whatever the device appends
@@ -562,15 +660,11 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
                 if (fr.fuse_plan[k].parent_seg == si) nest_parent = (int)k;
                 if (fr.fuse_plan[k].child_seg == si) nest_child = (int)k;
             }
-            const uint32_t lo = std::min((S.destroyed || nest_parent >= 0) ? 0u : dead, n_old), cnt = n_old - lo;
+            const uint32_t lo = std::min((S.destroyed || nest_parent >= 0) ? 0u : dead, n_old);
             const uint32_t ftile = fifo_coll ? FW_FIFO_COLL_TILE : FW_TILE;
-            const uint32_t ps = (uint32_t)(((uint64_t)S.head + lo) % S.capacity), ring_tiles = S.capacity / ftile;
-            const uint32_t ns0 = (uint32_t)(((uint64_t)S.head + (S.fifo_dev ? 0u : n_in)) % S.capacity);  // slot of the first new particle
-            F.spawn_a = std::min(n_spawn, S.capacity - ns0);
-            F.n_vt_a = (F.spawn_a + FW_BLOCK - 1) / FW_BLOCK, F.n_vt_b = (n_spawn - F.spawn_a + FW_BLOCK - 1) / FW_BLOCK;
-            F.tile0 = ps / ftile;
-            const uint32_t live_tiles = cnt ? std::min<uint32_t>(ring_tiles, (ps % ftile + cnt + ftile - 1) / ftile) : 0u;
-            F.n_tiles = std::max(1u, F.n_vt_a + F.n_vt_b + live_tiles);
+            const FwFifoLayout L = fw_fifo_layout(S.capacity, ftile, FW_BLOCK, S.head, lo, n_old, S.fifo_dev ? 0u : n_in, n_spawn);  // (fw_fuse2.h)
+            F.spawn_a = L.spawn_a, F.n_vt_a = L.n_vt_a, F.n_vt_b = L.n_vt_b, F.tile0 = L.tile0, F.n_tiles = L.n_tiles;
+            const uint32_t live_tiles = L.live_tiles;
             F.tile_first = f_tiles;
             f_tiles += F.n_tiles;
             F.nest = 0u;
@@ -591,6 +685,8 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
                 F.nest = ((uint32_t)nest_child + 1u) | FW_FIFO_NEST_CHILD;
                 fa.nest[nest_child].child = fa.n_segs - 1u;
             }
+            // (the estimate fw_ctx::nt_bytes / nt_wo_bytes were calibrated against in round 3 -- 104 / 164 B whatever the launch moves, two to
+            // seven times the truth by now: the thresholds and it go together, and a fused launch takes the form its second frame would have)
             f_bytes += (uint64_t)live_tiles * ftile * (S.nospin ? 104u : 164u);
             fa.any_inst |= S.inst != nullptr ? 1u : 0u;
             // (a launch of q0pl rings -- none of them collides -- in a context with a colliding ring: the plain one-round form on the same tile grid)
@@ -599,7 +695,7 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
             S.head = (uint32_t)(((uint64_t)S.head + dead) % S.capacity);
             if (!S.fifo_dev) S.ub = n_in + n_spawn - std::min(dead, n_in + n_spawn);  // exact
         }
-        FW_HIP(ctx, flush());
+        if ((st = flush())) return st;
     }
     return FW_OK;
 }
@@ -888,7 +984,12 @@ namespace fwh {
 fw_status enqueue_frame(fw_ctx *ctx, FwFrame &fr) {
     fr.p = ctx->parity;
     update_args(ctx, fr);
-    fw_status st = set_forecast(ctx, fr);
+    // a frame whose only GPU work can be one FIFO launch (fw_ctx::pend, launch_fifo): no compacting, range or small segment, no separate
+    // pass, no colour fill, nobody who wants a count or a time per frame.  Any other frame puts a withheld one on the stream first.
+    fr.quiet = ctx->use_fuse2 && ctx->n_fifo != 0 && ctx->n_in_use == ctx->n_fifo && !ctx->n_range && !ctx->n_small && !fr.total_tiles && !fr.legacy &&
+               !fr.fuse && !ctx->colors_dirty && ctx->live_ring == nullptr && !ctx->timing;
+    fw_status st = fr.quiet ? FW_OK : flush_withheld(ctx);
+    if (!st) st = set_forecast(ctx, fr);
     if (st) return st;
     pick_snapshot(ctx, fr);
     fr.prof(ctx, 4);

@@ -1,0 +1,69 @@
+// fw_fuse2.h -- two frames of an unread FIFO ring in one launch (round 22, FwFifoArgs::fused: fw_kernels.h).
+// A particle of a FIFO ring never moves: frame n + 1 of a slot needs nothing but frame n of the same slot.  A ring whose spin is deferred is
+// a ring nobody has looked at for a while, so the host may withhold the launch of a frame A -- all of its bookkeeping done -- and run it
+// inside the launch of the frame B that follows: one load and one store per plane for two updates.  Here: what a launch lays out for a
+// ring (the arithmetic launch_fifo has always done), when a pair may be fused, and the fused frame.
+// Plain C++ behind FW_HD, like fw_spin.h: the host (launch_fifo) and a host test (tests/test_cpp_host_fuse2.py) compile the same lines.
+#pragma once
+#include <stdint.h>
+
+#ifndef FW_HD
+#ifdef __HIPCC__
+#define FW_HD __host__ __device__ __forceinline__
+#else
+#define FW_HD inline
+#endif
+#endif
+
+// one frame of a ring as its launch sees it (FwFifoSeg): slot of logical particle 0 and live particles BEFORE the frame, the particles the
+// frame spawns behind them (logical indices [n_in, n_in + n_spawn)) and the number it destroys (logical indices [0, dead))
+struct FwFifoFrame {
+    uint32_t head, n_in, n_spawn, dead;
+};
+
+// the workgroups of a ring in a launch (FwFifoSeg: tile0, spawn_a, n_vt_a, n_vt_b, n_tiles): first the new particles, `block` each, in
+// two groups of consecutive slots -- [0, spawn_a) up to the end of the buffer, the rest from slot 0 --, then `live_tiles` ring tiles of
+// `tile` slots from tile0 on, which cover the logical indices [lo, n_old); at least one workgroup in all (it publishes the counts)
+struct FwFifoLayout {
+    uint32_t tile0, live_tiles, spawn_a, n_vt_a, n_vt_b, n_tiles;
+};
+// (head < capacity, a multiple of `tile`; lo <= n_old <= capacity; first_new: logical index of the first new particle)
+FW_HD FwFifoLayout fw_fifo_layout(uint32_t capacity, uint32_t tile, uint32_t block, uint32_t head, uint32_t lo, uint32_t n_old, uint32_t first_new,
+                                  uint32_t n_spawn) {
+    FwFifoLayout L;
+    const uint32_t cnt = n_old - lo;
+    const uint32_t ps = (uint32_t)(((uint64_t)head + lo) % capacity), ring_tiles = capacity / tile;
+    const uint32_t ns0 = (uint32_t)(((uint64_t)head + first_new) % capacity);  // slot of the first new particle
+    L.spawn_a = n_spawn < capacity - ns0 ? n_spawn : capacity - ns0;
+    L.n_vt_a = (L.spawn_a + block - 1) / block, L.n_vt_b = (n_spawn - L.spawn_a + block - 1) / block;
+    L.tile0 = ps / tile;
+    const uint32_t need = (ps % tile + cnt + tile - 1) / tile;
+    L.live_tiles = cnt ? (ring_tiles < need ? ring_tiles : need) : 0u;
+    L.n_tiles = L.n_vt_a + L.n_vt_b + L.live_tiles;
+    if (L.n_tiles == 0u) L.n_tiles = 1u;
+    return L;
+}
+
+// Is a frame's launch one that may be withheld, or take the withheld one in?  enabled: fw_ctx::use_fuse2 (FW_FUSE2); quiet: the frame's only
+// GPU work is FIFO launches; only_launch: this is the one launch of the frame and holds every FIFO ring of the context; spinless: it takes
+// the spin-less form; unread_and_large: every ring of it deferred its spin in it and holds fw_ctx::fuse2_min live particles
+FW_HD bool fw_fuse2_candidate(bool enabled, bool quiet, bool only_launch, bool spinless, bool unread_and_large) {
+    return enabled && quiet && only_launch && spinless && unread_and_large;
+}
+
+// May the launch of frame A wait for frame B and run inside B's?  (Both frames qualify by themselves -- launch_fifo's rule; this is what
+// the PAIR adds.)  B continues A.  No particle spawned in A or B dies within the pair: every dead particle of either frame was in the ring
+// before A, so "dead" stays a prefix of the logical indices the fused launch counts from A's head.  And the new particles of both frames
+// fit behind A's live particles without reaching the slots of A's own dead, which the fused view has not vacated: declined, not grown.
+FW_HD bool fw_fuse2_ok(uint32_t capacity, const FwFifoFrame &A, const FwFifoFrame &B) {
+    if (A.head >= capacity || A.n_in > capacity || A.n_spawn > capacity - A.n_in) return false;
+    if (A.dead > A.n_in) return false;  // (a newborn of A dies in A)
+    if (B.head != (uint32_t)(((uint64_t)A.head + A.dead) % capacity) || B.n_in != A.n_in + A.n_spawn - A.dead) return false;
+    if ((uint64_t)A.dead + B.dead > A.n_in) return false;
+    if ((uint64_t)A.n_in + A.n_spawn + B.n_spawn > capacity) return false;
+    return true;
+}
+
+// the fused frame: counted from A's head over A's live particles, both frames' new particles behind them (A's first: FwFifoArgs::fuse_spawn
+// = A.n_spawn), both frames' dead in front (FwFifoArgs::fuse_dead = A.dead)
+FW_HD FwFifoFrame fw_fuse2_frame(const FwFifoFrame &A, const FwFifoFrame &B) { return FwFifoFrame{A.head, A.n_in, A.n_spawn + B.n_spawn, A.dead + B.dead}; }

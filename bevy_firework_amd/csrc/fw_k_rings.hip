@@ -230,7 +230,11 @@ __device__ __forceinline__ void fw_fifo_nest_parents(const FwGlobals &g, const F
 // this launch -- a type that cannot turn, or a spin this launch defers).  The FIFO twin of ALLNOSPIN in fw_k_update_range: what the other
 // forms find out per workgroup is a fact of the instantiation, so a tile reserves no register for Q2 / Q3 -- 88 VGPRs instead of 110, a
 // fifth workgroup per CU.  The spawning workgroups keep the type's true record: a new particle gets its one update whole.
-template <bool INST, int WM, int NT, int COLL, int TR, bool NEST, bool Q0PL = false, bool SPINLESS = false>
+// FUSE2: the launch runs TWO frames of every ring in one pass (FwFifoArgs::fused; the host withheld the first one: fw_fuse2.h).
+// A particle of a FIFO ring never moves, so frame n + 1 of a slot needs nothing but frame n of the same slot: a ring tile loads position and
+// velocity once, applies dt_a and then dt with the update's own statements, and stores once; the spawning workgroups cover both frames' new
+// particles -- the first frame's get their first update whole in registers, then the store path with the second dt.  Spin-less launches only.
+template <bool INST, int WM, int NT, int COLL, int TR, bool NEST, bool Q0PL = false, bool SPINLESS = false, bool FUSE2 = false>
 __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl) {
     constexpr int BLK = FW_BLOCK;
     constexpr int NW = BLK / 64;
@@ -276,6 +280,7 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
     // value -- neither the Q2 nor the Q3 plane is read (every lane asks for the tile's first slot instead: one line per
     // wave, loads stay unconditional)
     static_assert(!SPINLESS || (Q0PL && !INST && TR == FW_ROUNDS), "the spin-less form: streaming launches of rings with Q0 in planes");
+    static_assert(!FUSE2 || SPINLESS, "two frames in one pass: the spin-less forms only");
     const bool nospin = SPINLESS || (F.type_idx & FW_TYPE_IDX_NOSPIN) != 0u;  // (only ring tiles ask)
     // a ring under the axis rule (FW_TYPE_IDX_AXIS, fw_device.h: host-proved, per launch): of rotation and angular velocity only the
     // axis' own component -- and the rotation's w -- is loaded; the other registers get the +0 their planes hold.  Workgroup-uniform
@@ -410,6 +415,23 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
                               fw_q4{op.origin_rot[0], op.origin_rot[1], op.origin_rot[2], op.origin_rot[3]},
                               fw_v3{op.parent_vel[0], op.parent_vel[1], op.parent_vel[2]}, op.speed, op.scale);
         }
+        if constexpr (FUSE2) {
+            // a particle of the FIRST frame of the pair: its first update whole, with that frame's dt, in registers -- translation, spin,
+            // age: what the spawning workgroup of the withheld launch would have stored -- and then, below, the second frame's update
+            // through the store path everybody takes (the host gives its cohort the second frame's spin with it: launch_fifo)
+            if (is_new && k < a.fuse_spawn[j]) {
+                float age_a;
+                bad |= !fw_survives(so.q0.w, a.dt_a, so.q3.w, &age_a);  // (the host fuses no pair in which a newborn dies)
+                const FwMove mv = fw_move_step(T, a.dt_a, so.q0, so.q1);
+                if (!(T.flags & FW_TYPE_NOSPIN)) {
+                    const FwSpin sp = fw_spin_step(T, a.dt_a, so.q2, so.q3);
+                    so.q2 = make_float4(sp.rot.x, sp.rot.y, sp.rot.z, sp.rot.w);
+                    so.q3.x = sp.wx, so.q3.y = sp.wy, so.q3.z = sp.wz;
+                }
+                so.q0 = make_float4(mv.px, mv.py, mv.pz, age_a);
+                so.q1.x = mv.vx, so.q1.y = mv.vy, so.q1.z = mv.vz;
+            }
+        }
         float age_new;
         const bool surv = fw_survives(so.q0.w, a.dt, so.q3.w, &age_new);
         const bool dead = i < n_dead;
@@ -473,6 +495,11 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
             if (nospin) q3c = q3s;
             uint32_t i = s - head;  // logical index of the slot
             if (s < head) i += C;
+            if constexpr (FUSE2) {  // the first frame of the pair, in registers: nothing of a spin-less tile but the translation (and the age, where kept)
+                const FwMove mv = fw_move_step(Tt, a.dt_a, q0c, q1c);
+                q0c = make_float4(mv.px, mv.py, mv.pz, q0c.w + a.dt_a);
+                q1c.x = mv.vx, q1c.y = mv.vy, q1c.z = mv.vz;
+            }
             float age_new;
             const bool surv = fw_survives(q0c.w, a.dt, q3c.w, &age_new);
             const bool mine = i < n_in, dead = i < n_dead;
@@ -536,6 +563,20 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
             }
         }
         if (F.report) *F.report = ((unsigned long long)a.epoch << 32) | added;
+        if constexpr (FUSE2) {
+            // the counters as the two launches would have left them: the first frame's output row (the other parity), then the second
+            // frame's -- which is the row checked above --, the second frame's destroyed count, both frames' particles in the statistics
+            const uint32_t all_a = n_in + a.fuse_spawn[j], nc_a = all_a - min(a.fuse_dead[j], all_a);
+            const uint32_t all_b = nc_a + (F.n_spawn - a.fuse_spawn[j]), nc_b = all_b - min(n_dead - a.fuse_dead[j], all_b);
+            g.count[oidx] = nc_a, g.count[sidx] = nc_b;
+            g.spawned[oidx] = 0, g.spawned[sidx] = 0;
+            g.appended[oidx] = 0, g.appended[sidx] = 0;
+            g.ndestroyed[F.seg] = all_b - nc_b;
+            if (a.host_counts) a.host_counts[F.seg] = ((unsigned long long)a.epoch << 32) | nc_b;
+            if (a.live_out) atomicAdd(a.live_out, (unsigned long long)nc_b);  // (the host fuses in no context that keeps a ring of live counts)
+            if (!FW_DBG(a.dbg, 128u)) atomicAdd(g.stats + (F.seg % FW_STAT_SLOTS), (unsigned long long)all_a + all_b);
+            return;
+        }
         const uint32_t nc = n_all - min(n_dead, n_all);
         g.count[oidx] = nc;
         g.spawned[oidx] = 0;
@@ -561,6 +602,14 @@ template <bool INST, int WM, int NT = 0, int COLL = 0, int TR = FW_ROUNDS, bool 
 __global__ __launch_bounds__(FW_BLOCK) __attribute__((amdgpu_waves_per_eu((!INST && !COLL && TR == FW_ROUNDS) ? FW_FIFO_WAVES : (COLL == 1 && TR == 1) ? 4 : 1)))
 void fw_k_update_fifo(FwGlobals g, FwFifoArgs a, FwInlineOps inl) {
     fw_update_fifo_body<INST, WM, NT, COLL, TR, false, Q0PL, SPINLESS>(g, a, inl);
+}
+// ... two frames of a spin-less launch in one pass (FwFifoArgs::fused, the FUSE2 arm of the body).  A kernel of its own, like the Nested
+// one, instantiated in a unit of its own (fw_k_rings_fuse2.hip): the plain instantiations keep their names, their code, their register
+// budget and their place in this unit's code object.  90 VGPRs, five waves, no scratch -- two more registers than the spin-less forms,
+// nothing pinned (profiles/r22/resource_usage.txt)
+template <int WM, int NT>
+__global__ __launch_bounds__(FW_BLOCK) __attribute__((amdgpu_waves_per_eu(FW_FIFO_WAVES))) void fw_k_update_fifo2(FwGlobals g, FwFifoArgs a, FwInlineOps inl) {
+    fw_update_fifo_body<false, WM, NT, 0, FW_ROUNDS, false, true, true, true>(g, a, inl);
 }
 // ... with Nested entries inside the launch (FwFifoNest).  A kernel of its own so that the plain instantiations keep their code
 // and their register budget; pinned at 4 waves per SIMD (the nest phase took the four-round form to 133 VGPRs: the bulk of such
@@ -636,7 +685,9 @@ __device__ __forceinline__ void fw_range_inst_out(char *inst, uint32_t inst_cap,
 #define FW_RANGE_PF_ALL 1  // a YOUNG workgroup of an all-NOSPIN launch requests all its rounds up front (0: two rounds in flight;
                           // configs[2] 321 -> 316 us, one GPU's share of configs[4] 87.9 -> 86.6 us, profiles/r04/strip_pf_ab.txt)
 #endif
+#ifndef FW_RINGS_TEMPLATES_ONLY  // (a unit that takes the templates alone does not define the host's functions again)
 uint32_t fw_range_young_tile(void) { return FW_RANGE_YR * FW_BLOCK; }
+#endif
 
 // INST: some segment of the launch has a WINDOWED instance buffer attached (fw_spawner_attach_instances_window): every
 // survivor's ParticleInstance record goes to index  n_old_in + (its position in the young part)  /  n_old_in - 1 - (its
@@ -1132,6 +1183,8 @@ static hipError_t fw_launch_update_fifo_plain(hipStream_t s, const FwGlobals &g,
     if constexpr (Q0PL) {
         // no ring tile of the launch touches rotation or angular velocity (FwFifoArgs::spinless; the host sets it for launches without an
         // instance buffer only): the forms compiled for that -- five workgroups per CU
+        if (a.fused && !(a.spinless && !a.any_inst)) return hipErrorInvalidValue;  // (the host fuses spin-less launches only)
+        if (a.spinless && !a.any_inst && a.fused) return fw_launch_update_fifo2(s, g, a, inl, grid.x, nt, e0, e1);  // (fw_k_rings_fuse2.hip)
         if (a.spinless && !a.any_inst) {
             if (nt == 2)
                 FW_LAUNCH_T((fw_k_update_fifo<false, -1, 2, 0, FW_ROUNDS, true, true>), grid, block, s, e0, e1, g, a, inl);
@@ -1182,6 +1235,7 @@ hipError_t fw_launch_update_fifo(hipStream_t s, const FwGlobals &g, const FwFifo
     if (!total_tiles || !a.n_segs) return hipErrorInvalidValue;
     const dim3 grid(total_tiles), block(FW_BLOCK);
     if (a.q0pl && (a.n_nest || a.any_coll)) return hipErrorInvalidValue;  // (the host launches rings with Q0 in planes by themselves)
+    if (a.fused && (!a.q0pl || a.small_tiles)) return hipErrorInvalidValue;
     if (a.n_nest) {  // Nested entries inside the launch (FwFifoNest): generic write mask; the host keeps instance buffers and colliders out
         // (... and such a launch holds a ring whose count only the device knows: never laid out on one-round tiles)
         if (a.any_inst || a.any_coll || a.small_tiles) return hipErrorInvalidValue;

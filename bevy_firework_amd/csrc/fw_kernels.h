@@ -254,7 +254,21 @@ struct FwFifoArgs {
                                        // the launch defers), none has an instance buffer, four-round tiles: no ring tile touches Q2 / Q3 -- the
                                        // SPINLESS instantiations, compiled without registers for them (fw_k_rings.hip); 0: the workgroups find out
                                        // (behind everything else: no other field of the kernel argument moves)
+    uint32_t fused;                    // 1: the launch runs the frame the host withheld (dt_a, parity: its input rows) and the frame after it (dt, epoch,
+                                       // done_tag, host_counts) in one pass over the planes -- spin-less launches only, the FUSE2 instantiations
+    float dt_a;
+    // ... per ring of such a launch (FwFifoSeg: head / n_in are the first frame's, n_spawn and dead the sums over both), the first frame's
+    // own share: new particles [0, fuse_spawn) get both updates, logical indices [0, fuse_dead) are the first frame's dead (the bookkeeping
+    // workgroup leaves the counters as the two launches would have).  Here and not in FwFifoSeg: the records keep the size and the offsets
+    // every other form of the kernel was measured with
+    uint32_t fuse_spawn[FW_FIFO_PER_LAUNCH], fuse_dead[FW_FIFO_PER_LAUNCH];
+    // FwInlineOps follows this record in the kernel arguments (FwGlobals, FwFifoArgs, FwInlineOps) and began on a 64-byte line of the
+    // scalar cache, which the spawning workgroups -- the launch's longest chain -- read their ops through.  Measured, round 22
+    // (profiles/r22/fuse2_ab.txt): with the 72 bytes above alone configs[0]'s launch took 1.2-1.4 % longer in three builds, with the
+    // record grown by two whole lines it keeps the parent's time
+    uint32_t fuse_pad[14];
 };
+static_assert((sizeof(FwGlobals) + sizeof(FwFifoArgs)) % 64 == 0, "FwInlineOps starts on a 64-byte line of the kernel arguments");
 
 // ---- range rings: particle types whose lifetime is a RANGE, updated in place ---------------------------------------
 // Ages never increase along the particle list (everybody is born with age 0 behind all older particles and every update
@@ -358,6 +372,9 @@ hipError_t fw_launch_fc_resolve(hipStream_t s, const FwGlobals &g, const FwResol
 hipError_t fw_launch_update(hipStream_t s, const FwGlobals &g, const FwUpdateArgs &a, const FwInlineOps *inl,
                             int spawn_form, int mode, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 // in-place update of up to FW_FIFO_PER_LAUNCH FIFO segments (their spawn ops in `inl`)
+// (the spin-less launch that runs two frames, FwFifoArgs::fused: fw_k_rings_fuse2.hip; reached through fw_launch_update_fifo)
+hipError_t fw_launch_update_fifo2(hipStream_t s, const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl, uint32_t total_tiles, int nt,
+                                  hipEvent_t e0, hipEvent_t e1);
 hipError_t fw_launch_update_fifo(hipStream_t s, const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl,
                                  uint32_t total_tiles, int nt, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 uint32_t fw_range_young_tile(void);  // ring slots a YOUNG workgroup of fw_k_update_range covers (a build-time choice)

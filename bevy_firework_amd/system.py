@@ -545,6 +545,13 @@ class ParticleSystem:
         self._check(self._lib.fw_debug_spinless_launches(self._ctx, C.byref(n)))
         return int(n.value)
 
+    def fuse2_launches(self):
+        """(fused, flushed): FIFO launches so far that ran two frames of unread rings in one pass, and withheld frames that went to the
+        stream alone"""
+        fused, flushed = C.c_uint64(), C.c_uint64()
+        self._check(self._lib.fw_debug_fuse2(self._ctx, C.byref(fused), C.byref(flushed)))
+        return int(fused.value), int(flushed.value)
+
     def recovered_rings(self) -> int:
         """rings moved to the compacting path (particles kept) because a cohort report was missing when it was due"""
         n = C.c_uint64()

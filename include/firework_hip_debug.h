@@ -78,6 +78,13 @@ fw_status fw_debug_spin_launches(fw_ctx *ctx, uint64_t *n);
  * four-round tiles.  FW_SPINLESS=0 (with FW_ENABLE_KNOBS) keeps such launches on the form that finds out per workgroup: 0 then */
 fw_status fw_debug_spinless_launches(fw_ctx *ctx, uint64_t *n);
 
+/* Two frames of unread FIFO rings in one launch.  *fused = launches so far that ran a withheld frame and the
+ * frame after it in one pass over the planes; *flushed = withheld frames that went to the stream alone, because the next frame did
+ * not qualify, the pair was declined, or somebody touched the stream or the particles first.  A frame is withheld only when its one
+ * launch is spin-less, every ring of it deferred its spin in it and holds FW_FUSE2_MIN particles (default 384 tiles);
+ * FW_FUSE2=0 (with FW_ENABLE_KNOBS) withholds nothing: both stay 0.  Either pointer may be null */
+fw_status fw_debug_fuse2(fw_ctx *ctx, uint64_t *fused, uint64_t *flushed);
+
 /* *on = 1: the context keeps the per-frame records of its range launches and its small op tables in DEVICE memory that the host writes
  * through the large BAR; 0: in pinned host memory (the platform does not map device memory for the host, or
  * FW_PARAM_BAR=0) */
