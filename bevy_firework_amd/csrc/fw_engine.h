@@ -490,7 +490,7 @@ struct alignas(64) SegHost {
     FwSpinBook spin;
     uint32_t spin_streak = 0;
     bool spin_last = false;
-    bool fuse_last = false;  // the latest launch ran two frames of the ring in one pass (fw_ctx::pend): fw_debug_update_path
+    uint32_t fuse_last = 0;  // the frames of the ring the latest launch ran in one pass, 2 .. FW_FUSE_MAX, or 0: one, unfused (fw_ctx::pend): fw_debug_update_path
     bool q0pl = false;  // the ring keeps Q0 (position, age) as four component planes (FwSeg::cpl bit 2): set where the ring is built
     // A ring in a spawner WITH Nested entries: in frames that run the Nested pass its new particles are materialised in
     // the ring before the update (fw_k_spawn / fw_k_nest address it through the head) and fw_k_update_fifo gives them
@@ -837,22 +837,32 @@ struct fw_ctx {
     // spinless).  FW_SPINLESS=0: they keep the form that finds out per workgroup (A/B in one build)
     bool use_spinless = true;
     uint64_t spinless_launches = 0;  // fw_debug_spinless_launches
-    // Two frames of unread rings in one launch (fw_fuse2.h).  A frame whose only GPU work would be one spin-less FIFO launch
-    // of rings that all deferred their spin in it -- each with at least fuse2_min live particles (FW_FUSE2_MIN: its own knob, the default
-    // of spin_defer_min) -- is WITHHELD: all of its bookkeeping done, the complete launch kept here instead of enqueued.  The next fw_step
-    // runs both frames in one launch when it qualifies too and the pair passes fw_fuse2_ok; anything else that touches the stream or
-    // particle state enqueues the kept launch first, exactly as built (flush_withheld).  Depth one.  FW_FUSE2=0: nothing is withheld.
+    // Up to fuse_depth frames of unread rings in one launch (fw_fuse2.h).  A frame whose only GPU work would be one spin-less
+    // FIFO launch of rings that all deferred their spin in it -- each with at least fuse2_min live particles (FW_FUSE2_MIN: its own knob, the
+    // default of spin_defer_min) -- is WITHHELD: all of its bookkeeping done, the complete launch kept here instead of enqueued.  The next
+    // fw_step's launch takes it in when it qualifies too and the group passes the rule (fw_fuse_push): it runs the group -- or, while the
+    // group is short of its depth, is withheld with it: `pend` is the GROUP so far, the fused launch of its frames.  The depth is two
+    // frames, or fuse_depth (FW_FUSE_DEPTH, 2 .. FW_FUSE_MAX) where every ring of the launch holds fuse_deep_min live particles
+    // (FW_FUSE_DEEP_MIN): a deeper group pays where the pass over the planes dominates the launch.  Anything else that touches the
+    // stream or particle state enqueues the group first (flush_withheld): one frame exactly as built, two or three as ONE fused launch.
+    // FW_FUSE2=0: nothing is withheld.
     bool use_fuse2 = true;
     uint32_t fuse2_min = 384u * FW_TILE;
+    uint32_t fuse_depth = FW_FUSE_MAX, fuse_deep_min = 768u * FW_TILE;
     struct PendingFifo {
         bool on = false;
-        FwFifoArgs fa;
+        uint32_t depth = 0;  // withheld frames: 1 .. FW_FUSE_MAX - 1
+        FwFifoArgs fa;       // depth 1: the frame's launch as built; deeper: the fused launch of the group so far (fa.fused = depth, fa.dt the last frame's)
         FwInlineOps fio;
+        FwFuseArgs fz;       // ... and its fourth argument: the dt and boundaries of frames 0 .. depth - 2
+        FwFuseGroup grp[FW_FIFO_PER_LAUNCH];  // per ring of the launch: the fused frame and every frame's share (fw_fuse2.h)
         uint32_t tiles = 0, n_ops = 0;
-        int nt = 0;
-        uint64_t frame = 0;  // fw_ctx::frame of the withheld frame (what its cohorts carry)
+        int nt = 0;          // the non-temporal form the LAST withheld frame's launch would have taken
+        uint64_t frame[FW_FUSE_MAX] = {};  // fw_ctx::frame of each withheld frame (what its cohorts carry)
+        uint64_t spin_from[FW_FIFO_PER_LAUNCH] = {};  // per ring: what a cohort of the last withheld frame carries as its spin pointer
     } pend;
-    uint64_t fused_launches = 0, fuse2_flushed = 0;  // fw_debug_fuse2: launches that ran two frames / withheld frames enqueued alone
+    // fw_debug_fuse2: launches that ran two or more frames / withheld frames enqueued alone; fw_debug_fuse_frames: frames run by fused launches
+    uint64_t fused_launches = 0, fuse2_flushed = 0, fuse_frames = 0;
     bool use_axis = true;      // FW_AXIS_SPIN=0: no ring runs under the axis-spin rule (A/B in one build)
     bool use_derived = true;   // FW_DERIVED=0: every type stores its scale / colour planes, attached instance buffer or not (A/B)
     // Round 6: scale, base colour and emissive colour are pure functions of (age, lifetime, initial_scale) (core.rs:601-605,
@@ -1192,7 +1202,8 @@ inline fw_status Fence::mark(fw_ctx *ctx, hipStream_t stream) {
 }
 
 fw_status sync(fw_ctx *ctx);  // (fw_engine_mem.cpp)
-// a withheld frame (fw_ctx::pend) goes to the stream, exactly as built: before anything else that touches the stream or particle state
+// the withheld frames (fw_ctx::pend) go to the stream -- one exactly as built, two or three as one fused launch --: before anything else that
+// touches the stream or particle state
 fw_status flush_withheld(fw_ctx *ctx);  // (fw_engine_launch.cpp)
 // ... or is dropped with the particles it would have updated (the spawner is rebuilt, the context destroyed)
 void drop_withheld(fw_ctx *ctx);

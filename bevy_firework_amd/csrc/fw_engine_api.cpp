@@ -211,6 +211,8 @@ fw_status fw_ctx_create(int device, uint32_t seed, void *stream, fw_ctx **out) {
     if (const char *m = getenv("FW_SPINLESS")) ctx->use_spinless = atoi(m) != 0;
     if (const char *m = getenv("FW_FUSE2")) ctx->use_fuse2 = atoi(m) != 0;
     if (const char *m = getenv("FW_FUSE2_MIN")) ctx->fuse2_min = (uint32_t)strtoul(m, nullptr, 10);
+    if (const char *m = getenv("FW_FUSE_DEPTH")) ctx->fuse_depth = (uint32_t)std::min(std::max(atoi(m), 2), (int)FW_FUSE_MAX);
+    if (const char *m = getenv("FW_FUSE_DEEP_MIN")) ctx->fuse_deep_min = (uint32_t)strtoul(m, nullptr, 10);
     // 0: scale / colour planes always stored; 1: not stored for types with an attached instance buffer; 2 (default): for no type
     if (const char *m = getenv("FW_DERIVED")) ctx->use_derived = atoi(m) != 0, ctx->derive_all = atoi(m) >= 2;
     if (const char *m = getenv("FW_NEST_FUSE")) ctx->nest_fuse = atoi(m) != 0;
@@ -1026,9 +1028,9 @@ fw_status fw_debug_update_path(fw_ctx *ctx, fw_spawner h, uint32_t type, int32_t
     }
     // an attached instance buffer: the update also writes the 64-byte ParticleInstance record of every survivor (render.rs:95-103)
     if (S.inst != nullptr) moved += 64u, algo += 64u;
-    // (round 22, a FIFO ring whose latest launch ran two frames of it -- SegHost::fuse_last, never with an instance buffer: one load and
-    // one store of every plane the launch moves for two updates of the particle)
-    if (S.fifo && S.fuse_last) moved /= 2u, algo /= 2u;
+    // (rounds 22 and 23, a FIFO ring whose latest launch ran several frames of it -- SegHost::fuse_last, never with an instance buffer: one
+    // load and one store of every plane the launch moves for that many updates of the particle)
+    if (S.fifo && S.fuse_last >= 2u) moved /= S.fuse_last, algo /= S.fuse_last;
     if (moved_bytes) *moved_bytes = moved;
     if (algorithmic_bytes) *algorithmic_bytes = algo;
     return FW_OK;
@@ -1070,11 +1072,17 @@ fw_status fw_debug_spinless_launches(fw_ctx *ctx, uint64_t *n) {
     *n = ctx->spinless_launches;
     return FW_OK;
 }
-// FIFO launches so far that ran two frames in one pass (fw_ctx::pend, FwFifoArgs::fused) / withheld frames that went to the stream alone
+// FIFO launches so far that ran two or more frames in one pass (fw_ctx::pend, FwFifoArgs::fused) / withheld frames that went to the stream alone
 fw_status fw_debug_fuse2(fw_ctx *ctx, uint64_t *fused, uint64_t *flushed) {
     if (!ctx) return FW_EINVAL;
     if (fused) *fused = ctx->fused_launches;
     if (flushed) *flushed = ctx->fuse2_flushed;
+    return FW_OK;
+}
+// ... and the frames those launches ran: a launch of depth D counts D
+fw_status fw_debug_fuse_frames(fw_ctx *ctx, uint64_t *frames) {
+    if (!ctx || !frames) return FW_EINVAL;
+    *frames = ctx->fuse_frames;
     return FW_OK;
 }
 fw_status fw_debug_tf_frames(fw_ctx *ctx, uint64_t *n) {

@@ -410,54 +410,80 @@ fw_status take_report(fw_ctx *ctx, uint32_t si, Cohort &c, const char *what) {
     return FW_OK;
 }
 
-// Two frames in one launch (fw_ctx::pend, fw_fuse2.h): B -- the launch `fa` / `fio` this frame has just built, complete -- takes the
-// withheld frame A in when every ring of B is the ring of A at the same place, the pair passes fw_fuse2_ok and the ops of both fit.
-// The fused launch is B's with A's head, live count, input row and dt in front; A's ops first, B's behind them (rel_base shifted by
-// A's new particles).  false: declined, nothing changed.
-bool fuse_pair(fw_ctx *ctx, FwFifoArgs &fa, FwInlineOps &fio, uint32_t n_ops, uint32_t *tiles) {
+// Several frames in one launch (fw_ctx::pend, fw_fuse2.h): B -- the launch `fa` / `fio` this frame has just built, complete -- joins the
+// group of withheld frames when every ring of B is the ring of the group at the same place, every ring's group takes B's frame in
+// (fw_fuse_push: the pair rule between the fused frame so far and B) and the ops of all frames fit.  The fused launch is B's with the
+// group's head, live count and input row in front; the group's ops first, in frame order, B's behind them (rel_base shifted by the new
+// particles in front of them); `fz`: the withheld frames' dt and boundaries.  false: declined, nothing changed.
+bool fuse_join(fw_ctx *ctx, FwFifoArgs &fa, FwInlineOps &fio, uint32_t n_ops, uint32_t *tiles, FwFuseArgs &fz, FwFuseGroup *grp) {
     const fw_ctx::PendingFifo &P = ctx->pend;
+    if (P.depth < 1u || P.depth >= FW_FUSE_MAX) return false;
     if (P.fa.n_segs != fa.n_segs || P.n_ops + n_ops > FW_INLINE_OPS || P.fa.write_mask != fa.write_mask) return false;
     for (uint32_t j = 0; j < fa.n_segs; j++) {
         const FwFifoSeg &A = P.fa.s[j], &B = fa.s[j];
         if (A.buf != B.buf || A.seg != B.seg || A.capacity != B.capacity || A.type_idx != B.type_idx || A.keys_off != B.keys_off ||
             A.keys_len != B.keys_len || A.life != B.life || A.mat || B.mat || A.destroyed || B.destroyed || A.nest || B.nest)
             return false;
-        if (!fw_fuse2_ok(B.capacity, FwFifoFrame{A.head, A.n_in, A.n_spawn, A.dead}, FwFifoFrame{B.head, B.n_in, B.n_spawn, B.dead})) return false;
+        grp[j] = P.grp[j];
+        if (!fw_fuse_push(B.capacity, grp[j], FwFifoFrame{B.head, B.n_in, B.n_spawn, B.dead})) return false;
     }
+    const uint32_t d = P.depth;  // (withheld frames: B is frame d of the group)
+    fz = P.fz;
+    fz.dt_pre[d - 1u] = P.fa.dt;
     FwInlineOps ops;
     uint32_t n = 0, t = 0;
     for (uint32_t j = 0; j < fa.n_segs; j++) {
         const FwFifoSeg &A = P.fa.s[j];
         FwFifoSeg &F = fa.s[j];
+        const FwFifoFrame &U = grp[j].U;
         const uint32_t o0 = n;
         for (uint32_t x = A.op0; x < A.op1; x++) ops.ops[n++] = P.fio.ops[x];
-        for (uint32_t x = F.op0; x < F.op1; x++) ops.ops[n] = fio.ops[x], ops.ops[n++].rel_base += A.n_spawn;
-        const FwFifoFrame U = fw_fuse2_frame(FwFifoFrame{A.head, A.n_in, A.n_spawn, A.dead}, FwFifoFrame{F.head, F.n_in, F.n_spawn, F.dead});
+        for (uint32_t x = F.op0; x < F.op1; x++) ops.ops[n] = fio.ops[x], ops.ops[n++].rel_base += grp[j].spawn_end[d - 1u];
         const FwFifoLayout L = fw_fifo_layout(F.capacity, FW_TILE, FW_BLOCK, U.head, U.dead, U.n_in, U.n_in, U.n_spawn);
         F.head = U.head, F.n_in = U.n_in, F.n_spawn = U.n_spawn, F.dead = U.dead;
-        fa.fuse_spawn[j] = A.n_spawn, fa.fuse_dead[j] = A.dead;
+        fz.spawn_end[j][d - 1u] = grp[j].spawn_end[d - 1u], fz.dead[j][d - 1u] = grp[j].dead[d - 1u];
         F.op0 = o0, F.op1 = n;
         F.spawn_a = L.spawn_a, F.n_vt_a = L.n_vt_a, F.n_vt_b = L.n_vt_b, F.tile0 = L.tile0, F.n_tiles = L.n_tiles;
         F.tile_first = t;
         t += F.n_tiles;
     }
     fio = ops;
-    fa.parity = P.fa.parity, fa.dt_a = P.fa.dt, fa.fused = 1u;
+    fa.parity = P.fa.parity, fa.fused = d + 1u;
     *tiles = t;
     return true;
+}
+
+// the cohorts the withheld frames of a group spawned got every later frame's spin from the launch: their pointer is the last frame's
+// cohort's (`spin_from`, per ring of the launch); the rings' latest launch ran `depth` frames
+void group_launched(fw_ctx *ctx, const FwFifoArgs &fa, const uint64_t *frames, uint32_t n_withheld, const uint64_t *spin_from, uint32_t depth) {
+    for (uint32_t j = 0; j < fa.n_segs; j++) {
+        if (fa.s[j].seg >= ctx->segs.size()) continue;
+        SegHost &S = ctx->segs[fa.s[j].seg];
+        for (auto c = S.coh.rbegin(); n_withheld && c != S.coh.rend() && c->frame >= frames[0]; ++c)
+            for (uint32_t f = 0; f < n_withheld; f++)
+                if (c->frame == frames[f]) c->spin_from = spin_from[j];
+        S.fuse_last = depth;
+    }
 }
 
 }  // namespace
 
 namespace fwh {
 
+// the group so far goes to the stream: one withheld frame exactly as it was built (the unfused launch), two or three as ONE fused launch
+// of that depth -- whoever reads first pays one launch
 fw_status flush_withheld(fw_ctx *ctx) {
     fw_ctx::PendingFifo &P = ctx->pend;
     if (!P.on) return FW_OK;
     P.on = false;
+    if (P.depth >= 2u) {
+        ctx->fused_launches++, ctx->fuse_frames += P.depth;
+        group_launched(ctx, P.fa, P.frame, P.depth - 1u, P.spin_from, P.depth);
+        FW_HIP(ctx, fw_launch_update_fifo(ctx->stream, ctx->g, P.fa, P.fio, P.tiles, P.nt, nullptr, nullptr, &P.fz));
+        return FW_OK;
+    }
     ctx->fuse2_flushed++;
-    for (uint32_t j = 0; j < P.fa.n_segs; j++)
-        if (P.fa.s[j].seg < ctx->segs.size()) ctx->segs[P.fa.s[j].seg].fuse_last = false;
+    group_launched(ctx, P.fa, P.frame, 0u, P.spin_from, 0u);
     FW_HIP(ctx, fw_launch_update_fifo(ctx->stream, ctx->g, P.fa, P.fio, P.tiles, P.nt, nullptr, nullptr));
     return FW_OK;
 }
@@ -498,9 +524,10 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
     uint32_t f_ops = 0, f_tiles = 0;
     uint64_t f_bytes = 0;  // what the launch streams, roughly: its tiles x the bytes a particle of the type moves
     bool f_nospin = true;  // every ring of the launch so far carries FW_TYPE_IDX_NOSPIN in it (FwFifoArgs::spinless)
-    // two frames in one launch (fw_ctx::pend): every ring of the launch so far deferred its spin in it and holds fuse2_min particles; the
+    // several frames in one launch (fw_ctx::pend): every ring of the launch so far deferred its spin in it and holds fuse2_min particles; the
     // launches of this frame so far; what a cohort this frame spawns carries as its spin pointer, per ring of the launch
     bool f_fusable = true;
+    bool f_deep = true;  // ... and holds fuse_deep_min: a group of the launch may be deeper than two frames
     uint32_t n_launches = 0;
     uint64_t f_spin_from[FW_FIFO_PER_LAUNCH] = {};
     // (a frame whose only GPU work is this one launch: no compacting, range or small segment, no separate pass, no colour fill, nobody
@@ -526,17 +553,26 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
         n_launches++;
         fr.fifo_launched = true;
         fw_status fst = FW_OK;
-        if (ctx->pend.on && candidate && fuse_pair(ctx, fa, fio, f_ops, &f_tiles)) {
-            // (the cohort the withheld frame spawned got both frames' spin from the launch: its pointer is this frame's cohort's)
-            for (uint32_t j = 0; j < fa.n_segs; j++) {
-                SegHost &S = ctx->segs[fa.s[j].seg];
-                for (auto c = S.coh.rbegin(); c != S.coh.rend() && c->frame >= ctx->pend.frame; ++c)
-                    if (c->frame == ctx->pend.frame) c->spin_from = f_spin_from[j];
-                S.fuse_last = true;
+        // (how deep a group this launch may close or continue: two frames, or fw_ctx::fuse_depth where the pass dominates the launch)
+        const uint32_t depth_max = f_deep ? std::max(2u, std::min(ctx->fuse_depth, (uint32_t)FW_FUSE_MAX)) : 2u;
+        fw_ctx::PendingFifo &P = ctx->pend;
+        FwFuseArgs fz{};
+        FwFuseGroup grp[FW_FIFO_PER_LAUNCH];
+        if (P.on && candidate && P.depth < depth_max && fuse_join(ctx, fa, fio, f_ops, &f_tiles, fz, grp)) {
+            const uint32_t depth = P.depth + 1u;
+            ctx->spinless_launches++;
+            if (depth >= depth_max) {  // the frame that completes the group launches it
+                P.on = false;
+                group_launched(ctx, fa, P.frame, P.depth, f_spin_from, depth);
+                ctx->fused_launches++, ctx->fuse_frames += depth;
+                FW_HIP(ctx, fw_launch_update_fifo(fstream, ctx->g, fa, fio, f_tiles, nt, nullptr, nullptr, &fz));
+            } else {  // withheld too: the group so far is the fused launch, kept (what flush_withheld enqueues)
+                fa.host_counts = nullptr;
+                fr.snap = -1, fr.a.host_counts = nullptr;
+                P.fa = fa, P.fio = fio, P.fz = fz, P.tiles = f_tiles, P.n_ops += f_ops, P.nt = nt;
+                P.frame[P.depth] = ctx->frame, P.depth = depth;
+                for (uint32_t j = 0; j < fa.n_segs; j++) P.grp[j] = grp[j], P.spin_from[j] = f_spin_from[j];
             }
-            ctx->pend.on = false;
-            ctx->fused_launches++, ctx->spinless_launches++;
-            FW_HIP(ctx, fw_launch_update_fifo(fstream, ctx->g, fa, fio, f_tiles, nt, nullptr, nullptr));
         } else if ((fst = flush_withheld(ctx))) {
             return fst;
         } else if (candidate) {
@@ -544,19 +580,20 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
             // fused or alone, leaves the device's counters as they must be; a row nobody fills would stay armed)
             fa.host_counts = nullptr;
             fr.snap = -1, fr.a.host_counts = nullptr;
-            fw_ctx::PendingFifo &P = ctx->pend;
-            P.fa = fa, P.fio = fio, P.tiles = f_tiles, P.n_ops = f_ops, P.nt = nt, P.frame = ctx->frame, P.on = true;
+            P.fa = fa, P.fio = fio, P.fz = FwFuseArgs{}, P.tiles = f_tiles, P.n_ops = f_ops, P.nt = nt, P.frame[0] = ctx->frame, P.depth = 1u, P.on = true;
+            for (uint32_t j = 0; j < fa.n_segs; j++)
+                P.grp[j] = fw_fuse_begin(FwFifoFrame{fa.s[j].head, fa.s[j].n_in, fa.s[j].n_spawn, fa.s[j].dead}), P.spin_from[j] = f_spin_from[j];
             ctx->spinless_launches++;
         } else {
             ctx->spinless_launches += fa.spinless;
-            for (uint32_t j = 0; j < fa.n_segs; j++) ctx->segs[fa.s[j].seg].fuse_last = false;
+            for (uint32_t j = 0; j < fa.n_segs; j++) ctx->segs[fa.s[j].seg].fuse_last = 0u;
             hipEvent_t e0, e1;
             next_timing_pair(ctx, fr, &e0, &e1);
             FW_HIP(ctx, fw_launch_update_fifo(fstream, ctx->g, fa, fio, f_tiles, nt, e0, e1));
         }
         if (side) ctx->side_dirty = true;
         fa = FwFifoArgs{};
-        f_ops = f_tiles = 0, f_bytes = 0, f_nospin = true, f_fusable = true;
+        f_ops = f_tiles = 0, f_bytes = 0, f_nospin = true, f_fusable = true, f_deep = true;
         return FW_OK;
     };
     // (two passes: the rings that keep Q0 in planes -- SegHost::q0pl, the ones that may run under the age rule -- get a launch of their own,
@@ -610,6 +647,7 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
             const uint64_t spin_from_new = spin_defer ? S.spin.defer(S.coh, dt) : S.spin.end();
             S.spin_last = spin_defer;
             f_fusable &= spin_defer && n_in >= ctx->fuse2_min;
+            f_deep &= n_in >= ctx->fuse_deep_min;
             f_spin_from[fa.n_segs] = spin_from_new;
             // the cohorts age by this dt exactly as their particles do (fp32 additions, fw_survives); the oldest die first
             if (S.fifo_dev) {

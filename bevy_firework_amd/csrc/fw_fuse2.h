@@ -1,9 +1,13 @@
-// fw_fuse2.h -- two frames of an unread FIFO ring in one launch (round 22, FwFifoArgs::fused: fw_kernels.h).
+// fw_fuse2.h -- up to FW_FUSE_MAX frames of an unread FIFO ring in one launch (rounds 22 and 23, FwFifoArgs::fused, FwFuseArgs: fw_kernels.h,
+// DESIGN.md 4.0).
 // A particle of a FIFO ring never moves: frame n + 1 of a slot needs nothing but frame n of the same slot.  A ring whose spin is deferred is
 // a ring nobody has looked at for a while, so the host may withhold the launch of a frame A -- all of its bookkeeping done -- and run it
-// inside the launch of the frame B that follows: one load and one store per plane for two updates.  Here: what a launch lays out for a
-// ring (the arithmetic launch_fifo has always done), when a pair may be fused, and the fused frame.
-// Plain C++ behind FW_HD, like fw_spin.h: the host (launch_fifo) and a host test (tests/test_cpp_host_fuse2.py) compile the same lines.
+// inside the launch of a frame that follows: one load and one store per plane for two, three or four updates.  The group grows frame by
+// frame: the withheld frames so far are ONE fused frame (fw_fuse2_frame, folded), and the pair rule between it and the next frame is the
+// rule of the group (FwFuseGroup, fw_fuse_push).  Here: what a launch lays out for a ring (the arithmetic launch_fifo has always done),
+// when a frame may join, and the fused frame with the per-frame boundaries the kernel needs.
+// Plain C++ behind FW_HD, like fw_spin.h: the host (launch_fifo) and two host tests (tests/test_cpp_host_fuse2.py, test_cpp_host_fuse_deep.py)
+// compile the same lines.
 #pragma once
 #include <stdint.h>
 
@@ -67,3 +71,29 @@ FW_HD bool fw_fuse2_ok(uint32_t capacity, const FwFifoFrame &A, const FwFifoFram
 // the fused frame: counted from A's head over A's live particles, both frames' new particles behind them (A's first: FwFifoArgs::fuse_spawn
 // = A.n_spawn), both frames' dead in front (FwFifoArgs::fuse_dead = A.dead)
 FW_HD FwFifoFrame fw_fuse2_frame(const FwFifoFrame &A, const FwFifoFrame &B) { return FwFifoFrame{A.head, A.n_in, A.n_spawn + B.n_spawn, A.dead + B.dead}; }
+
+// ---- a group of up to FW_FUSE_MAX consecutive frames (round 23).  The frames fold from the left: the group so far is the fused frame U of
+// its members, and frame B may join exactly when fw_fuse2_ok(capacity, U, B) -- B continues U, the summed dead stay within the FIRST
+// frame's live particles (nobody born in the group dies in it), and the first frame's live particles plus every frame's spawns fit the
+// ring.  What the kernel needs beside U: where each frame's new particles end among the group's (cumulative: new particle k belongs to the
+// first frame f with k < spawn_end[f]) and how many each frame destroys.
+#define FW_FUSE_MAX 4
+struct FwFuseGroup {
+    FwFifoFrame U;                   // the fused frame of the members so far
+    uint32_t depth;                  // members: 1 .. FW_FUSE_MAX
+    uint32_t spawn_end[FW_FUSE_MAX]; // new particles of frames 0 .. f (spawn_end[depth - 1] == U.n_spawn)
+    uint32_t dead[FW_FUSE_MAX];      // per frame (their sum == U.dead)
+};
+FW_HD FwFuseGroup fw_fuse_begin(const FwFifoFrame &A) {
+    FwFuseGroup G{};
+    G.U = A, G.depth = 1u, G.spawn_end[0] = A.n_spawn, G.dead[0] = A.dead;
+    return G;
+}
+// may frame B join the group?  true: joined (G is the longer group); false: declined, G unchanged
+FW_HD bool fw_fuse_push(uint32_t capacity, FwFuseGroup &G, const FwFifoFrame &B) {
+    if (G.depth < 1u || G.depth >= FW_FUSE_MAX || !fw_fuse2_ok(capacity, G.U, B)) return false;
+    G.U = fw_fuse2_frame(G.U, B);
+    G.spawn_end[G.depth] = G.U.n_spawn, G.dead[G.depth] = B.dead;
+    G.depth++;
+    return true;
+}

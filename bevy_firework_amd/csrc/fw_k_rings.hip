@@ -230,12 +230,15 @@ __device__ __forceinline__ void fw_fifo_nest_parents(const FwGlobals &g, const F
 // this launch -- a type that cannot turn, or a spin this launch defers).  The FIFO twin of ALLNOSPIN in fw_k_update_range: what the other
 // forms find out per workgroup is a fact of the instantiation, so a tile reserves no register for Q2 / Q3 -- 88 VGPRs instead of 110, a
 // fifth workgroup per CU.  The spawning workgroups keep the type's true record: a new particle gets its one update whole.
-// FUSE2: the launch runs TWO frames of every ring in one pass (FwFifoArgs::fused; the host withheld the first one: fw_fuse2.h).
+// FUSE: 0, or the launch runs FUSE = 2 .. FW_FUSE_MAX frames of every ring in one pass (FwFifoArgs::fused; the host withheld all but the last:
+// fw_fuse2.h; `fz`: their dt and boundaries, FwFuseArgs -- the fused kernels' fourth argument, null for everybody else).
 // A particle of a FIFO ring never moves, so frame n + 1 of a slot needs nothing but frame n of the same slot: a ring tile loads position and
-// velocity once, applies dt_a and then dt with the update's own statements, and stores once; the spawning workgroups cover both frames' new
-// particles -- the first frame's get their first update whole in registers, then the store path with the second dt.  Spin-less launches only.
-template <bool INST, int WM, int NT, int COLL, int TR, bool NEST, bool Q0PL = false, bool SPINLESS = false, bool FUSE2 = false>
-__device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl) {
+// velocity once, applies dt_pre[0 .. FUSE - 2] and then dt with the update's own statements, and stores once; the spawning workgroups cover
+// every frame's new particles -- a withheld frame's get their first update and the withheld ones behind it whole in registers, then the
+// store path with the last dt.  The depth is a fact of the instantiation: the loops over the withheld frames unroll, and the depth-2 form
+// is round 22's code with its arguments read from `fz`.  Spin-less launches only.
+template <bool INST, int WM, int NT, int COLL, int TR, bool NEST, bool Q0PL = false, bool SPINLESS = false, int FUSE = 0>
+__device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl, const FwFuseArgs *fz = nullptr) {
     constexpr int BLK = FW_BLOCK;
     constexpr int NW = BLK / 64;
     constexpr int R = TR;  // (smaller ring tiles were measured for the streaming case: 2 rounds 26.7 us, 1 round 26.2 us, 4 rounds 24.6 us)
@@ -280,7 +283,7 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
     // value -- neither the Q2 nor the Q3 plane is read (every lane asks for the tile's first slot instead: one line per
     // wave, loads stay unconditional)
     static_assert(!SPINLESS || (Q0PL && !INST && TR == FW_ROUNDS), "the spin-less form: streaming launches of rings with Q0 in planes");
-    static_assert(!FUSE2 || SPINLESS, "two frames in one pass: the spin-less forms only");
+    static_assert(FUSE == 0 || (SPINLESS && FUSE >= 2 && FUSE <= FW_FUSE_MAX), "several frames in one pass: the spin-less forms only, two to FW_FUSE_MAX");
     const bool nospin = SPINLESS || (F.type_idx & FW_TYPE_IDX_NOSPIN) != 0u;  // (only ring tiles ask)
     // a ring under the axis rule (FW_TYPE_IDX_AXIS, fw_device.h: host-proved, per launch): of rotation and angular velocity only the
     // axis' own component -- and the rotation's w -- is loaded; the other registers get the +0 their planes hold.  Workgroup-uniform
@@ -415,21 +418,26 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
                               fw_q4{op.origin_rot[0], op.origin_rot[1], op.origin_rot[2], op.origin_rot[3]},
                               fw_v3{op.parent_vel[0], op.parent_vel[1], op.parent_vel[2]}, op.speed, op.scale);
         }
-        if constexpr (FUSE2) {
-            // a particle of the FIRST frame of the pair: its first update whole, with that frame's dt, in registers -- translation, spin,
-            // age: what the spawning workgroup of the withheld launch would have stored -- and then, below, the second frame's update
-            // through the store path everybody takes (the host gives its cohort the second frame's spin with it: launch_fifo)
-            if (is_new && k < a.fuse_spawn[j]) {
-                float age_a;
-                bad |= !fw_survives(so.q0.w, a.dt_a, so.q3.w, &age_a);  // (the host fuses no pair in which a newborn dies)
-                const FwMove mv = fw_move_step(T, a.dt_a, so.q0, so.q1);
-                if (!(T.flags & FW_TYPE_NOSPIN)) {
-                    const FwSpin sp = fw_spin_step(T, a.dt_a, so.q2, so.q3);
-                    so.q2 = make_float4(sp.rot.x, sp.rot.y, sp.rot.z, sp.rot.w);
-                    so.q3.x = sp.wx, so.q3.y = sp.wy, so.q3.z = sp.wz;
+        if constexpr (FUSE != 0) {
+            // a particle of a WITHHELD frame f of the group (k < spawn_end[f]: spawned by frame f or an earlier one): the update of frame f
+            // whole, with that frame's dt, in registers -- translation, spin, age: what the spawning workgroup of the withheld launch
+            // would have stored, and what the launches behind it would have made of it -- and then, below, the last frame's update
+            // through the store path everybody takes (the host gives its cohort the last frame's spin with it: launch_fifo)
+#pragma unroll
+            for (int f = 0; f < FUSE - 1; f++) {
+                const float dt_f = fz->dt_pre[f];
+                if (is_new && k < fz->spawn_end[j][f]) {
+                    float age_a;
+                    bad |= !fw_survives(so.q0.w, dt_f, so.q3.w, &age_a);  // (the host fuses no group in which a newborn dies)
+                    const FwMove mv = fw_move_step(T, dt_f, so.q0, so.q1);
+                    if (!(T.flags & FW_TYPE_NOSPIN)) {
+                        const FwSpin sp = fw_spin_step(T, dt_f, so.q2, so.q3);
+                        so.q2 = make_float4(sp.rot.x, sp.rot.y, sp.rot.z, sp.rot.w);
+                        so.q3.x = sp.wx, so.q3.y = sp.wy, so.q3.z = sp.wz;
+                    }
+                    so.q0 = make_float4(mv.px, mv.py, mv.pz, age_a);
+                    so.q1.x = mv.vx, so.q1.y = mv.vy, so.q1.z = mv.vz;
                 }
-                so.q0 = make_float4(mv.px, mv.py, mv.pz, age_a);
-                so.q1.x = mv.vx, so.q1.y = mv.vy, so.q1.z = mv.vz;
             }
         }
         float age_new;
@@ -495,10 +503,14 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
             if (nospin) q3c = q3s;
             uint32_t i = s - head;  // logical index of the slot
             if (s < head) i += C;
-            if constexpr (FUSE2) {  // the first frame of the pair, in registers: nothing of a spin-less tile but the translation (and the age, where kept)
-                const FwMove mv = fw_move_step(Tt, a.dt_a, q0c, q1c);
-                q0c = make_float4(mv.px, mv.py, mv.pz, q0c.w + a.dt_a);
-                q1c.x = mv.vx, q1c.y = mv.vy, q1c.z = mv.vz;
+            if constexpr (FUSE != 0) {  // the withheld frames, in order, in registers: nothing of a spin-less tile but the translation (and the age, where kept)
+#pragma unroll
+                for (int f = 0; f < FUSE - 1; f++) {
+                    const float dt_f = fz->dt_pre[f];
+                    const FwMove mv = fw_move_step(Tt, dt_f, q0c, q1c);
+                    q0c = make_float4(mv.px, mv.py, mv.pz, q0c.w + dt_f);
+                    q1c.x = mv.vx, q1c.y = mv.vy, q1c.z = mv.vz;
+                }
             }
             float age_new;
             const bool surv = fw_survives(q0c.w, a.dt, q3c.w, &age_new);
@@ -563,18 +575,29 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
             }
         }
         if (F.report) *F.report = ((unsigned long long)a.epoch << 32) | added;
-        if constexpr (FUSE2) {
-            // the counters as the two launches would have left them: the first frame's output row (the other parity), then the second
-            // frame's -- which is the row checked above --, the second frame's destroyed count, both frames' particles in the statistics
-            const uint32_t all_a = n_in + a.fuse_spawn[j], nc_a = all_a - min(a.fuse_dead[j], all_a);
-            const uint32_t all_b = nc_a + (F.n_spawn - a.fuse_spawn[j]), nc_b = all_b - min(n_dead - a.fuse_dead[j], all_b);
-            g.count[oidx] = nc_a, g.count[sidx] = nc_b;
+        if constexpr (FUSE != 0) {
+            // the counters as FUSE launches one after another would have left them: frame f reads row parity ^ (f & 1) -- the first
+            // frame's is the row checked above -- and writes the other, so the row the last frame wrote holds its count and the other one
+            // the count of the frame before it; the last frame's destroyed count; every frame's particles in the statistics
+            uint32_t nc_prev = n_in, nc = n_in, all_f = 0u, sp_done = 0u, dead_done = 0u;
+            unsigned long long all_sum = 0ull;
+#pragma unroll
+            for (int f = 0; f < FUSE; f++) {
+                const uint32_t sp_end = f < FUSE - 1 ? fz->spawn_end[j][f] : F.n_spawn;
+                const uint32_t dead_f = f < FUSE - 1 ? fz->dead[j][f] : n_dead - dead_done;
+                nc_prev = nc;
+                all_f = nc_prev + (sp_end - sp_done);
+                nc = all_f - min(dead_f, all_f);
+                sp_done = sp_end, dead_done += dead_f, all_sum += all_f;
+            }
+            const uint32_t last = (FUSE & 1) ? oidx : sidx, other = (FUSE & 1) ? sidx : oidx;  // (frame FUSE - 1 wrote `last`)
+            g.count[other] = nc_prev, g.count[last] = nc;
             g.spawned[oidx] = 0, g.spawned[sidx] = 0;
             g.appended[oidx] = 0, g.appended[sidx] = 0;
-            g.ndestroyed[F.seg] = all_b - nc_b;
-            if (a.host_counts) a.host_counts[F.seg] = ((unsigned long long)a.epoch << 32) | nc_b;
-            if (a.live_out) atomicAdd(a.live_out, (unsigned long long)nc_b);  // (the host fuses in no context that keeps a ring of live counts)
-            if (!FW_DBG(a.dbg, 128u)) atomicAdd(g.stats + (F.seg % FW_STAT_SLOTS), (unsigned long long)all_a + all_b);
+            g.ndestroyed[F.seg] = all_f - nc;
+            if (a.host_counts) a.host_counts[F.seg] = ((unsigned long long)a.epoch << 32) | nc;
+            if (a.live_out) atomicAdd(a.live_out, (unsigned long long)nc);  // (the host fuses in no context that keeps a ring of live counts)
+            if (!FW_DBG(a.dbg, 128u)) atomicAdd(g.stats + (F.seg % FW_STAT_SLOTS), all_sum);
             return;
         }
         const uint32_t nc = n_all - min(n_dead, n_all);
@@ -603,13 +626,13 @@ __global__ __launch_bounds__(FW_BLOCK) __attribute__((amdgpu_waves_per_eu((!INST
 void fw_k_update_fifo(FwGlobals g, FwFifoArgs a, FwInlineOps inl) {
     fw_update_fifo_body<INST, WM, NT, COLL, TR, false, Q0PL, SPINLESS>(g, a, inl);
 }
-// ... two frames of a spin-less launch in one pass (FwFifoArgs::fused, the FUSE2 arm of the body).  A kernel of its own, like the Nested
-// one, instantiated in a unit of its own (fw_k_rings_fuse2.hip): the plain instantiations keep their names, their code, their register
-// budget and their place in this unit's code object.  90 VGPRs, five waves, no scratch -- two more registers than the spin-less forms,
-// nothing pinned (profiles/r22/resource_usage.txt)
-template <int WM, int NT>
-__global__ __launch_bounds__(FW_BLOCK) __attribute__((amdgpu_waves_per_eu(FW_FIFO_WAVES))) void fw_k_update_fifo2(FwGlobals g, FwFifoArgs a, FwInlineOps inl) {
-    fw_update_fifo_body<false, WM, NT, 0, FW_ROUNDS, false, true, true, true>(g, a, inl);
+// ... D = 2 .. FW_FUSE_MAX frames of a spin-less launch in one pass (FwFifoArgs::fused, the FUSE arm of the body; FwFuseArgs: a fourth
+// argument of these kernels alone).  A kernel of its own, like the Nested one, instantiated in a unit of its own (fw_k_rings_fuse2.hip):
+// the plain instantiations keep their names, their code, their register budget and their place in this unit's code object.  At most 96
+// VGPRs, five waves, no scratch, nothing pinned (profiles/r23/resource_usage.txt)
+template <int D, int WM, int NT>
+__global__ __launch_bounds__(FW_BLOCK) __attribute__((amdgpu_waves_per_eu(FW_FIFO_WAVES))) void fw_k_update_fifo2(FwGlobals g, FwFifoArgs a, FwInlineOps inl, FwFuseArgs fz) {
+    fw_update_fifo_body<false, WM, NT, 0, FW_ROUNDS, false, true, true, D>(g, a, inl, &fz);
 }
 // ... with Nested entries inside the launch (FwFifoNest).  A kernel of its own so that the plain instantiations keep their code
 // and their register budget; pinned at 4 waves per SIMD (the nest phase took the four-round form to 133 VGPRs: the bulk of such
@@ -1172,7 +1195,7 @@ void fw_k_update_range(FwGlobals g, FwRangeArgs a) {
 // the launches without a collider or a Nested entry; Q0PL: every ring of the launch keeps Q0 in component planes (FwFifoArgs::q0pl)
 template <bool Q0PL>
 static hipError_t fw_launch_update_fifo_plain(hipStream_t s, const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl, dim3 grid, dim3 block,
-                                              int nt, hipEvent_t e0, hipEvent_t e1) {
+                                              int nt, hipEvent_t e0, hipEvent_t e1, const FwFuseArgs *fz) {
     if (a.small_tiles) {  // a launch of a few hundred four-round workgroups at most: one round each instead (generic write mask)
         if (a.any_inst)
             FW_LAUNCH_T((fw_k_update_fifo<true, -1, 0, 0, 1, Q0PL>), grid, block, s, e0, e1, g, a, inl);
@@ -1184,7 +1207,7 @@ static hipError_t fw_launch_update_fifo_plain(hipStream_t s, const FwGlobals &g,
         // no ring tile of the launch touches rotation or angular velocity (FwFifoArgs::spinless; the host sets it for launches without an
         // instance buffer only): the forms compiled for that -- five workgroups per CU
         if (a.fused && !(a.spinless && !a.any_inst)) return hipErrorInvalidValue;  // (the host fuses spin-less launches only)
-        if (a.spinless && !a.any_inst && a.fused) return fw_launch_update_fifo2(s, g, a, inl, grid.x, nt, e0, e1);  // (fw_k_rings_fuse2.hip)
+        if (a.spinless && !a.any_inst && a.fused) return fz ? fw_launch_update_fifo2(s, g, a, inl, *fz, grid.x, nt, e0, e1) : hipErrorInvalidValue;  // (fw_k_rings_fuse2.hip)
         if (a.spinless && !a.any_inst) {
             if (nt == 2)
                 FW_LAUNCH_T((fw_k_update_fifo<false, -1, 2, 0, FW_ROUNDS, true, true>), grid, block, s, e0, e1, g, a, inl);
@@ -1231,7 +1254,7 @@ static hipError_t fw_launch_update_fifo_plain(hipStream_t s, const FwGlobals &g,
 }
 
 hipError_t fw_launch_update_fifo(hipStream_t s, const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl,
-                                 uint32_t total_tiles, int nt, hipEvent_t e0, hipEvent_t e1) {
+                                 uint32_t total_tiles, int nt, hipEvent_t e0, hipEvent_t e1, const FwFuseArgs *fz) {
     if (!total_tiles || !a.n_segs) return hipErrorInvalidValue;
     const dim3 grid(total_tiles), block(FW_BLOCK);
     if (a.q0pl && (a.n_nest || a.any_coll)) return hipErrorInvalidValue;  // (the host launches rings with Q0 in planes by themselves)
@@ -1271,8 +1294,8 @@ hipError_t fw_launch_update_fifo(hipStream_t s, const FwGlobals &g, const FwFifo
             FW_LAUNCH_T((fw_k_update_fifo<false, -1, 0, 1, 1>), grid, block, s, e0, e1, g, a, inl);
         return hipGetLastError();
     }
-    if (a.q0pl) return fw_launch_update_fifo_plain<true>(s, g, a, inl, grid, block, nt, e0, e1);
-    return fw_launch_update_fifo_plain<false>(s, g, a, inl, grid, block, nt, e0, e1);
+    if (a.q0pl) return fw_launch_update_fifo_plain<true>(s, g, a, inl, grid, block, nt, e0, e1, fz);
+    return fw_launch_update_fifo_plain<false>(s, g, a, inl, grid, block, nt, e0, e1, nullptr);
 }
 
 template <int NT>

@@ -8,6 +8,7 @@
 #include "fw_collide.h"
 #include "fw_refit.h"
 #include "fw_mesh_bounds.h"
+#include "fw_fuse2.h"
 
 // The product build (the default `make`) carries no experiment surface: the FW_DEBUG profiling modes (kernel ablations, in-kernel
 // timestamps) and the A/B switches of measured-and-rejected variants exist only in the `make ab` build (-DFW_AB,
@@ -254,21 +255,30 @@ struct FwFifoArgs {
                                        // the launch defers), none has an instance buffer, four-round tiles: no ring tile touches Q2 / Q3 -- the
                                        // SPINLESS instantiations, compiled without registers for them (fw_k_rings.hip); 0: the workgroups find out
                                        // (behind everything else: no other field of the kernel argument moves)
-    uint32_t fused;                    // 1: the launch runs the frame the host withheld (dt_a, parity: its input rows) and the frame after it (dt, epoch,
-                                       // done_tag, host_counts) in one pass over the planes -- spin-less launches only, the FUSE2 instantiations
-    float dt_a;
-    // ... per ring of such a launch (FwFifoSeg: head / n_in are the first frame's, n_spawn and dead the sums over both), the first frame's
-    // own share: new particles [0, fuse_spawn) get both updates, logical indices [0, fuse_dead) are the first frame's dead (the bookkeeping
-    // workgroup leaves the counters as the two launches would have).  Here and not in FwFifoSeg: the records keep the size and the offsets
-    // every other form of the kernel was measured with
-    uint32_t fuse_spawn[FW_FIFO_PER_LAUNCH], fuse_dead[FW_FIFO_PER_LAUNCH];
+    uint32_t fused;                    // 0, or the DEPTH of a fused launch, 2 .. FW_FUSE_MAX: it runs the frames the host withheld (parity: the first
+                                       // one's input rows; their dt and boundaries: FwFuseArgs) and the frame after them (dt, epoch, done_tag,
+                                       // host_counts) in one pass over the planes -- spin-less launches only, the fused instantiations
+    // (round 22 kept the first frame's dt, spawns and dead of a pair in the 17 words that follow; a group's travel in a record of its own,
+    // FwFuseArgs, a fourth kernel argument of the fused kernels alone.  The words stay: this record keeps its size.)
     // FwInlineOps follows this record in the kernel arguments (FwGlobals, FwFifoArgs, FwInlineOps) and began on a 64-byte line of the
     // scalar cache, which the spawning workgroups -- the launch's longest chain -- read their ops through.  Measured, round 22
-    // (profiles/r22/fuse2_ab.txt): with the 72 bytes above alone configs[0]'s launch took 1.2-1.4 % longer in three builds, with the
+    // (profiles/r22/fuse2_ab.txt): with 72 bytes more configs[0]'s launch took 1.2-1.4 % longer in three builds, with the
     // record grown by two whole lines it keeps the parent's time
-    uint32_t fuse_pad[14];
+    uint32_t fuse_pad[31];
 };
 static_assert((sizeof(FwGlobals) + sizeof(FwFifoArgs)) % 64 == 0, "FwInlineOps starts on a 64-byte line of the kernel arguments");
+static_assert(sizeof(FwFifoArgs) == 1440, "the size every form of the FIFO kernel was measured with (profiles/r22/fuse2_ab.txt)");
+// What a fused launch of depth D = FwFifoArgs::fused knows beside FwFifoArgs (round 23): the FOURTH argument of the fused kernels, behind
+// FwInlineOps -- no other kernel's arguments move.  Frames 0 .. D - 2 are the withheld ones, frame D - 1 is the launch's own (FwFifoArgs::dt).
+// Per ring of the launch (FwFifoSeg: head / n_in are the first frame's, n_spawn and dead the sums over the group): new particle k of the
+// ring was spawned by the first frame f with k < spawn_end[f] (cumulative; the last frame's bound is FwFifoSeg::n_spawn) and gets the
+// updates of the frames f .. D - 1; frame f destroys dead[f] particles, all of them in the ring before the group (fw_fuse2.h).
+struct FwFuseArgs {
+    float dt_pre[FW_FUSE_MAX - 1];
+    uint32_t pad;
+    uint32_t spawn_end[FW_FIFO_PER_LAUNCH][FW_FUSE_MAX - 1];
+    uint32_t dead[FW_FIFO_PER_LAUNCH][FW_FUSE_MAX - 1];
+};
 
 // ---- range rings: particle types whose lifetime is a RANGE, updated in place ---------------------------------------
 // Ages never increase along the particle list (everybody is born with age 0 behind all older particles and every update
@@ -372,11 +382,12 @@ hipError_t fw_launch_fc_resolve(hipStream_t s, const FwGlobals &g, const FwResol
 hipError_t fw_launch_update(hipStream_t s, const FwGlobals &g, const FwUpdateArgs &a, const FwInlineOps *inl,
                             int spawn_form, int mode, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
 // in-place update of up to FW_FIFO_PER_LAUNCH FIFO segments (their spawn ops in `inl`)
-// (the spin-less launch that runs two frames, FwFifoArgs::fused: fw_k_rings_fuse2.hip; reached through fw_launch_update_fifo)
-hipError_t fw_launch_update_fifo2(hipStream_t s, const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl, uint32_t total_tiles, int nt,
-                                  hipEvent_t e0, hipEvent_t e1);
+// (the spin-less launch that runs FwFifoArgs::fused = 2 .. FW_FUSE_MAX frames: fw_k_rings_fuse2.hip; reached through fw_launch_update_fifo,
+// which wants `fz` for such a launch and for no other)
+hipError_t fw_launch_update_fifo2(hipStream_t s, const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl, const FwFuseArgs &fz,
+                                  uint32_t total_tiles, int nt, hipEvent_t e0, hipEvent_t e1);
 hipError_t fw_launch_update_fifo(hipStream_t s, const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl,
-                                 uint32_t total_tiles, int nt, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
+                                 uint32_t total_tiles, int nt, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, const FwFuseArgs *fz = nullptr);
 uint32_t fw_range_young_tile(void);  // ring slots a YOUNG workgroup of fw_k_update_range covers (a build-time choice)
 // in-place update of every range ring of the context (all_nospin: no segment of the launch keeps a rotation plane)
 // nt: which form of the kernel (fw_dev.h: fw_ld4w): 0 plain, 1 the write-only planes non-temporal, 2 every plane access

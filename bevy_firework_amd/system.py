@@ -552,6 +552,12 @@ class ParticleSystem:
         self._check(self._lib.fw_debug_fuse2(self._ctx, C.byref(fused), C.byref(flushed)))
         return int(fused.value), int(flushed.value)
 
+    def fuse_frames(self) -> int:
+        """frames run by fused launches so far: a launch that ran D frames of unread rings in one pass counts D"""
+        n = C.c_uint64()
+        self._check(self._lib.fw_debug_fuse_frames(self._ctx, C.byref(n)))
+        return int(n.value)
+
     def recovered_rings(self) -> int:
         """rings moved to the compacting path (particles kept) because a cohort report was missing when it was due"""
         n = C.c_uint64()
