@@ -842,16 +842,18 @@ struct fw_ctx {
     // default of spin_defer_min) -- is WITHHELD: all of its bookkeeping done, the complete launch kept here instead of enqueued.  The next
     // fw_step's launch takes it in when it qualifies too and the group passes the rule (fw_fuse_push): it runs the group -- or, while the
     // group is short of its depth, is withheld with it: `pend` is the GROUP so far, the fused launch of its frames.  The depth is two
-    // frames, or fuse_depth (FW_FUSE_DEPTH, 2 .. FW_FUSE_MAX) where every ring of the launch holds fuse_deep_min live particles
-    // (FW_FUSE_DEEP_MIN): a deeper group pays where the pass over the planes dominates the launch.  Anything else that touches the
-    // stream or particle state enqueues the group first (flush_withheld): one frame exactly as built, two or three as ONE fused launch.
+    // frames; min(fuse_depth, FW_FUSE_NARROW) where every ring of the launch holds fuse_deep_min live particles (FW_FUSE_DEEP_MIN); and
+    // fuse_depth (FW_FUSE_DEPTH, 2 .. FW_FUSE_MAX) where every ring holds fuse_wide_min as well (FW_FUSE_WIDE_MIN, round 24): a deeper group
+    // pays where the pass over the planes dominates the launch.  (No depth above four has been measured between 768 tiles and the
+    // headline's 983 333 particles: fuse_wide_min reuses fuse_deep_min's figure for want of another.)  Anything else that touches the
+    // stream or particle state enqueues the group first (flush_withheld): one frame exactly as built, two to seven as ONE fused launch.
     // FW_FUSE2=0: nothing is withheld.
     bool use_fuse2 = true;
     uint32_t fuse2_min = 384u * FW_TILE;
-    uint32_t fuse_depth = FW_FUSE_MAX, fuse_deep_min = 768u * FW_TILE;
+    uint32_t fuse_depth = FW_FUSE_MAX, fuse_deep_min = 768u * FW_TILE, fuse_wide_min = 768u * FW_TILE;
     struct PendingFifo {
         bool on = false;
-        uint32_t depth = 0;  // withheld frames: 1 .. FW_FUSE_MAX - 1
+        uint32_t depth = 0;  // withheld frames: 1 .. FW_FUSE_MAX - 1 (up to seven)
         FwFifoArgs fa;       // depth 1: the frame's launch as built; deeper: the fused launch of the group so far (fa.fused = depth, fa.dt the last frame's)
         FwInlineOps fio;
         FwFuseArgs fz;       // ... and its fourth argument: the dt and boundaries of frames 0 .. depth - 2

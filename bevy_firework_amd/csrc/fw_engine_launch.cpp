@@ -412,9 +412,10 @@ fw_status take_report(fw_ctx *ctx, uint32_t si, Cohort &c, const char *what) {
 
 // Several frames in one launch (fw_ctx::pend, fw_fuse2.h): B -- the launch `fa` / `fio` this frame has just built, complete -- joins the
 // group of withheld frames when every ring of B is the ring of the group at the same place, every ring's group takes B's frame in
-// (fw_fuse_push: the pair rule between the fused frame so far and B) and the ops of all frames fit.  The fused launch is B's with the
-// group's head, live count and input row in front; the group's ops first, in frame order, B's behind them (rel_base shifted by the new
-// particles in front of them); `fz`: the withheld frames' dt and boundaries.  false: declined, nothing changed.
+// (fw_fuse_push: the pair rule between the fused frame so far and B) and the ops of all frames fit (FW_INLINE_OPS = 8: one ring with one
+// op per frame reaches FW_FUSE_MAX frames, a launch that carries two ops per frame closes its groups at four).  The fused launch is B's
+// with the group's head, live count and input row in front; the group's ops first, in frame order, B's behind them (rel_base shifted by
+// the new particles in front of them); `fz`: the withheld frames' dt and boundaries.  false: declined, nothing changed.
 bool fuse_join(fw_ctx *ctx, FwFifoArgs &fa, FwInlineOps &fio, uint32_t n_ops, uint32_t *tiles, FwFuseArgs &fz, FwFuseGroup *grp) {
     const fw_ctx::PendingFifo &P = ctx->pend;
     if (P.depth < 1u || P.depth >= FW_FUSE_MAX) return false;
@@ -470,7 +471,7 @@ void group_launched(fw_ctx *ctx, const FwFifoArgs &fa, const uint64_t *frames, u
 
 namespace fwh {
 
-// the group so far goes to the stream: one withheld frame exactly as it was built (the unfused launch), two or three as ONE fused launch
+// the group so far goes to the stream: one withheld frame exactly as it was built (the unfused launch), two to seven as ONE fused launch
 // of that depth -- whoever reads first pays one launch
 fw_status flush_withheld(fw_ctx *ctx) {
     fw_ctx::PendingFifo &P = ctx->pend;
@@ -527,7 +528,8 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
     // several frames in one launch (fw_ctx::pend): every ring of the launch so far deferred its spin in it and holds fuse2_min particles; the
     // launches of this frame so far; what a cohort this frame spawns carries as its spin pointer, per ring of the launch
     bool f_fusable = true;
-    bool f_deep = true;  // ... and holds fuse_deep_min: a group of the launch may be deeper than two frames
+    bool f_deep = true;  // ... and holds fuse_deep_min: a group of the launch may be deeper than two frames, up to FW_FUSE_NARROW
+    bool f_wide = true;  // ... and fuse_wide_min: up to fw_ctx::fuse_depth
     uint32_t n_launches = 0;
     uint64_t f_spin_from[FW_FIFO_PER_LAUNCH] = {};
     // (a frame whose only GPU work is this one launch: no compacting, range or small segment, no separate pass, no colour fill, nobody
@@ -553,8 +555,10 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
         n_launches++;
         fr.fifo_launched = true;
         fw_status fst = FW_OK;
-        // (how deep a group this launch may close or continue: two frames, or fw_ctx::fuse_depth where the pass dominates the launch)
-        const uint32_t depth_max = f_deep ? std::max(2u, std::min(ctx->fuse_depth, (uint32_t)FW_FUSE_MAX)) : 2u;
+        // (how deep a group this launch may close or continue: two frames, or fw_ctx::fuse_depth where the pass dominates the launch -- beyond
+        // FW_FUSE_NARROW only where every ring holds fuse_wide_min too)
+        const uint32_t depth_knob = std::max(2u, std::min(ctx->fuse_depth, (uint32_t)FW_FUSE_MAX));
+        const uint32_t depth_max = !f_deep ? 2u : !f_wide ? std::min(depth_knob, (uint32_t)FW_FUSE_NARROW) : depth_knob;
         fw_ctx::PendingFifo &P = ctx->pend;
         FwFuseArgs fz{};
         FwFuseGroup grp[FW_FIFO_PER_LAUNCH];
@@ -593,7 +597,7 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
         }
         if (side) ctx->side_dirty = true;
         fa = FwFifoArgs{};
-        f_ops = f_tiles = 0, f_bytes = 0, f_nospin = true, f_fusable = true, f_deep = true;
+        f_ops = f_tiles = 0, f_bytes = 0, f_nospin = true, f_fusable = true, f_deep = true, f_wide = true;
         return FW_OK;
     };
     // (two passes: the rings that keep Q0 in planes -- SegHost::q0pl, the ones that may run under the age rule -- get a launch of their own,
@@ -648,6 +652,7 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
             S.spin_last = spin_defer;
             f_fusable &= spin_defer && n_in >= ctx->fuse2_min;
             f_deep &= n_in >= ctx->fuse_deep_min;
+            f_wide &= n_in >= ctx->fuse_wide_min;
             f_spin_from[fa.n_segs] = spin_from_new;
             // the cohorts age by this dt exactly as their particles do (fp32 additions, fw_survives); the oldest die first
             if (S.fifo_dev) {

@@ -1,13 +1,13 @@
-// fw_fuse2.h -- up to FW_FUSE_MAX frames of an unread FIFO ring in one launch (rounds 22 and 23, FwFifoArgs::fused, FwFuseArgs: fw_kernels.h,
+// fw_fuse2.h -- up to FW_FUSE_MAX frames of an unread FIFO ring in one launch (rounds 22 to 24, FwFifoArgs::fused, FwFuseArgs: fw_kernels.h,
 // DESIGN.md 4.0).
 // A particle of a FIFO ring never moves: frame n + 1 of a slot needs nothing but frame n of the same slot.  A ring whose spin is deferred is
 // a ring nobody has looked at for a while, so the host may withhold the launch of a frame A -- all of its bookkeeping done -- and run it
-// inside the launch of a frame that follows: one load and one store per plane for two, three or four updates.  The group grows frame by
+// inside the launch of a frame that follows: one load and one store per plane for two to eight updates.  The group grows frame by
 // frame: the withheld frames so far are ONE fused frame (fw_fuse2_frame, folded), and the pair rule between it and the next frame is the
 // rule of the group (FwFuseGroup, fw_fuse_push).  Here: what a launch lays out for a ring (the arithmetic launch_fifo has always done),
 // when a frame may join, and the fused frame with the per-frame boundaries the kernel needs.
-// Plain C++ behind FW_HD, like fw_spin.h: the host (launch_fifo) and two host tests (tests/test_cpp_host_fuse2.py, test_cpp_host_fuse_deep.py)
-// compile the same lines.
+// Plain C++ behind FW_HD, like fw_spin.h: the host (launch_fifo) and three host tests (tests/test_cpp_host_fuse2.py, test_cpp_host_fuse_deep.py,
+// test_cpp_host_fuse_wide.py) compile the same lines.
 #pragma once
 #include <stdint.h>
 
@@ -72,12 +72,15 @@ FW_HD bool fw_fuse2_ok(uint32_t capacity, const FwFifoFrame &A, const FwFifoFram
 // = A.n_spawn), both frames' dead in front (FwFifoArgs::fuse_dead = A.dead)
 FW_HD FwFifoFrame fw_fuse2_frame(const FwFifoFrame &A, const FwFifoFrame &B) { return FwFifoFrame{A.head, A.n_in, A.n_spawn + B.n_spawn, A.dead + B.dead}; }
 
-// ---- a group of up to FW_FUSE_MAX consecutive frames (round 23).  The frames fold from the left: the group so far is the fused frame U of
+// ---- a group of up to FW_FUSE_MAX consecutive frames (round 23: four; round 24: eight).  The frames fold from the left: the group so far is the fused frame U of
 // its members, and frame B may join exactly when fw_fuse2_ok(capacity, U, B) -- B continues U, the summed dead stay within the FIRST
 // frame's live particles (nobody born in the group dies in it), and the first frame's live particles plus every frame's spawns fit the
 // ring.  What the kernel needs beside U: where each frame's new particles end among the group's (cumulative: new particle k belongs to the
 // first frame f with k < spawn_end[f]) and how many each frame destroys.
-#define FW_FUSE_MAX 4
+// FW_FUSE_NARROW: the depth a group may reach where round 23's threshold alone holds (fw_ctx::fuse_deep_min); beyond it every ring of the
+// launch must hold fw_ctx::fuse_wide_min as well (launch_fifo)
+#define FW_FUSE_MAX 8
+#define FW_FUSE_NARROW 4
 struct FwFuseGroup {
     FwFifoFrame U;                   // the fused frame of the members so far
     uint32_t depth;                  // members: 1 .. FW_FUSE_MAX

@@ -42,7 +42,8 @@ fw_status fw_debug_read_launches(fw_ctx *ctx, unsigned long long *out32768, uint
 fw_status fw_debug_read_range_timestamps(fw_ctx *ctx, unsigned long long *out, uint64_t max_tiles, uint64_t *n_tiles);
 /* which update path a particle type is on (1 = FIFO ring updated in place, 2 = range ring: young part in place, old part
  * compacted in place, 0 = general compacting path), the bytes one
- * update of a live particle moves on it, and how many of those are algorithmic (bench.py's roofline accounting) */
+ * update of a live particle moves on it, and how many of those are algorithmic (bench.py's roofline accounting).  A FIFO ring
+ * whose latest launch ran D = 2 .. 8 frames of it in one pass (fw_debug_fuse2) reports that launch's bytes divided by D */
 fw_status fw_debug_update_path(fw_ctx *ctx, fw_spawner spawner, uint32_t type, int32_t *mode, uint32_t *moved_bytes,
                                uint32_t *algorithmic_bytes);
 
@@ -78,12 +79,14 @@ fw_status fw_debug_spin_launches(fw_ctx *ctx, uint64_t *n);
  * four-round tiles.  FW_SPINLESS=0 (with FW_ENABLE_KNOBS) keeps such launches on the form that finds out per workgroup: 0 then */
 fw_status fw_debug_spinless_launches(fw_ctx *ctx, uint64_t *n);
 
-/* Several frames of unread FIFO rings in one launch (rounds 22 and 23).  *fused = launches so far that ran one or more
+/* Several frames of unread FIFO rings in one launch (rounds 22 to 24).  *fused = launches so far that ran one or more
  * withheld frames and the frame after them in one pass over the planes; *flushed = withheld frames that went to the stream alone,
  * because the next frame did not qualify, the pair was declined, or somebody touched the stream or the particles first.  A frame is
  * withheld only when its one launch is spin-less, every ring of it deferred its spin in it and holds FW_FUSE2_MIN particles (default
- * 384 tiles); a group grows beyond two frames, up to FW_FUSE_DEPTH (2 to 4, default 4), only where every ring holds FW_FUSE_DEEP_MIN
- * particles (default 768 tiles).  FW_FUSE2=0 (with FW_ENABLE_KNOBS) withholds nothing: both stay 0.  Either pointer may be null */
+ * 384 tiles); a group grows beyond two frames, up to FW_FUSE_DEPTH (2 to 8, default 8), only where every ring holds FW_FUSE_DEEP_MIN
+ * particles (default 768 tiles), and beyond four only where every ring holds FW_FUSE_WIDE_MIN as well (default 768 tiles).  A launch
+ * whose rings carry more than one spawn op per frame closes its groups earlier: eight ops travel in a launch.  FW_FUSE2=0 (with
+ * FW_ENABLE_KNOBS) withholds nothing: both stay 0.  Either pointer may be null */
 fw_status fw_debug_fuse2(fw_ctx *ctx, uint64_t *fused, uint64_t *flushed);
 /* *frames = the frames run by fused launches so far: a launch that ran D frames counts D (so *frames / *fused is the mean depth) */
 fw_status fw_debug_fuse_frames(fw_ctx *ctx, uint64_t *frames);
