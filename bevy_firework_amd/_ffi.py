@@ -106,6 +106,10 @@ class SortView(C.Structure):
     _fields_ = [("eye", C.c_float * 3), ("order", C.c_uint32), ("forward", C.c_float * 3), ("reserved", C.c_uint32)]
 
 
+class Aabb(C.Structure):
+    _fields_ = [("min", C.c_float * 3), ("any", C.c_int32), ("max", C.c_float * 3), ("reserved", C.c_uint32)]
+
+
 def make_sort_view(view):
     d = SortView()
     d.eye[:] = [float(x) for x in view.eye]
@@ -333,6 +337,8 @@ SYMBOLS = [
     ("fw_ctx_pack_instances_sorted", C.c_int, [_P, C.c_int32, C.c_uint32, C.POINTER(SortView), _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("fw_spawner_aabb", C.c_int, [_P, C.c_int32, _F3, _F3, C.POINTER(C.c_int32)]),
     ("fw_ctx_track_aabbs", C.c_int, [_P, C.c_int32]),
+    ("fw_ctx_aabbs", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_int32), _P]),
+    ("fw_ctx_aabbs_device", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_int32), _P]),
     ("fw_ctx_live_count", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("fw_ctx_live_count_device", C.c_int, [_P, _P]),
     ("fw_ctx_live_count_ring", C.c_int, [_P, _P, C.c_uint32]),
@@ -356,12 +362,13 @@ SYMBOLS = [
     ("fw_debug_spinless_launches", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("fw_debug_fuse2", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("fw_debug_fuse_frames", C.c_int, [_P, C.POINTER(C.c_uint64)]),
+    ("fw_debug_aabb_batch", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
     ("fw_compute_emission_count", C.c_uint64,
      [C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float)]),
 ]
 
 # entry points added after round 4 (ABI 5 + a measurement hook): absent from the older builds the A/B tools load through FW_LIB_PATH
-NEWER_THAN_R04 = {"fw_debug_nest_frames", "fw_debug_param_bar", "fw_debug_tile_scratch", "fw_debug_recovered_rings", "fw_debug_tf_frames", "fw_debug_age_launches", "fw_debug_spin_launches", "fw_debug_spinless_launches", "fw_debug_fuse2", "fw_debug_fuse_frames", "fw_ctx_set_parent_velocities", "fw_ctx_set_modifiers", "fw_ctx_queue"}
+NEWER_THAN_R04 = {"fw_debug_nest_frames", "fw_debug_param_bar", "fw_debug_tile_scratch", "fw_debug_recovered_rings", "fw_debug_tf_frames", "fw_debug_age_launches", "fw_debug_spin_launches", "fw_debug_spinless_launches", "fw_debug_fuse2", "fw_debug_fuse_frames", "fw_debug_aabb_batch", "fw_ctx_aabbs", "fw_ctx_aabbs_device", "fw_ctx_set_parent_velocities", "fw_ctx_set_modifiers", "fw_ctx_queue"}
 _lib = None
 
 

@@ -53,6 +53,7 @@
 #include "fw_spin.h"
 #include "fw_fuse2.h"
 #include "fw_sort.h"
+#include "fw_boxes.h"
 
 namespace fwh {
 
@@ -1111,6 +1112,17 @@ struct fw_ctx {
     HipBuf<float4> q_out2_h, q_out2_d;  // ... and for the optional second output (the path query's samples): untouched until one is asked for
     HipBuf<float> d_aabb;      // 256 partial boxes of the AABB query
     HipBuf<float> h_aabb;      // pinned result {min.xyz, any, max.xyz, -}
+    // the batched boxes (fw_ctx_aabbs[_device]; fw_boxes.h): the entry and place tables of a call travel as ONE copy in the context's
+    // stream, staged like a collider set; the scratch of partial boxes and the host form's pinned records only ever grow (growing is
+    // the one case in which the device form waits)
+    struct {
+        Staging<char, 2> h_tab;
+        HipBuf<char> d_tab;
+        HipBuf<float> d_part;              // one partial box {min.xyz, -, max.xyz, -} per chunk
+        HipBuf<float> h_out;               // pinned: the fw_aabb records of the host form
+        std::vector<uint32_t> place_first; // per-call scratch: the first entry of every output place
+        uint64_t launches = 0, last_chunks = 0;  // fw_debug_aabb_batch
+    } boxes;
     HipBuf<unsigned long long> d_total;
     HipBuf<uint32_t> d_segids;
 

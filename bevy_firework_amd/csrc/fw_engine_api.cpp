@@ -835,6 +835,101 @@ fw_status fw_ctx_track_aabbs(fw_ctx *ctx, int32_t enable) {
     return FW_OK;
 }
 
+// ---- the boxes of many spawners in one call (firework_hip.h: BATCHED BOXES; fw_boxes.h, fw_k_boxes / fw_k_boxes_fold)
+static_assert(sizeof(fw_aabb) == 32 && sizeof(FwBoxPlace) == 16 && sizeof(FwBoxEntry) % 16 == 0, "fw_aabb: 32 bytes; the two tables share one 16-byte aligned copy");
+
+// What the two forms share, behind their argument checks (n > 0, every handle names a live spawner): fw_spawner_aabb's prologue for
+// the whole list at once -- Ages::ages: a withheld group goes out once, stale ages are written back, a deferred spin stays deferred,
+// the side stream is joined once where a listed segment's launches may run there --, then one entry per listed (spawner, type)
+// segment and one place per handle into the staging slot of this turn, ONE copy, two launches; `records`: n fw_aabb records the fold
+// kernel writes, device or pinned host memory.  Host work per listed segment, none per particle; waits only to grow.
+static fw_status boxes_enqueue(fw_ctx *ctx, uint32_t n, const fw_spawner *handles, void *records, const char *who) {
+    poll_device_error(ctx);
+    size_t ne = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        const SpawnerHost &sp = ctx->spawners[(size_t)handles[i]];
+        if (sp.poisoned) return poisoned_status(ctx);
+        ne += sp.seg.size();
+    }
+    if (n > FW_BOX_MAX_CHUNKS || ne > 0xFFFFFFFFull) return fail(ctx, FW_EINVAL, std::string(who) + ": more places than one batch holds");
+    hipSetDevice(ctx->device);
+    fw_status st;
+    if ((st = flush_withheld(ctx))) return st;  // (fw_ctx::pend)
+    bool side = false;  // a listed segment is a FIFO ring or a small type: its launches may run on the ring stream
+    for (uint32_t i = 0; i < n; i++)
+        for (uint32_t si : ctx->spawners[(size_t)handles[i]].seg) {
+            if ((st = ensure_ages(ctx, si))) return st;
+            side |= ctx->segs[si].fifo || ctx->segs[si].small;
+        }
+    if (side && (st = join_side(ctx))) return st;
+    const size_t bytes = ne * sizeof(FwBoxEntry) + (size_t)n * sizeof(FwBoxPlace);
+    char *h;
+    if ((st = ctx->boxes.h_tab.take(ctx, bytes, std::max<size_t>(bytes * 2, 16384), &h, &ctx->boxes.d_tab))) return st;
+    FwBoxEntry *const tab = reinterpret_cast<FwBoxEntry *>(h);
+    FwBoxPlace *const places = reinterpret_cast<FwBoxPlace *>(h + ne * sizeof(FwBoxEntry));
+    std::vector<uint32_t> &first = ctx->boxes.place_first;
+    try {
+        first.resize((size_t)n + 1);
+    } catch (const std::bad_alloc &) {
+        return fail(ctx, FW_ENOMEM, std::string(who) + ": out of host memory");
+    }
+    uint32_t e = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        first[i] = e;
+        for (uint32_t si : ctx->spawners[(size_t)handles[i]].seg) {
+            const SegHost &S = ctx->segs[si];
+            FwBoxEntry &E = tab[e++];
+            E.v = seg_view(ctx, si, ctx->parity), E.d_count = count_slot(ctx, si);
+            E.bound = S.nested_fed ? S.capacity : std::min(S.ub, S.capacity);  // (the bound of fw_spawner_pack_instances_device)
+            E.chunk0 = 0;
+        }
+    }
+    first[n] = e;
+    const uint64_t total = fw_boxes_plan(tab, e, first.data(), n, places);
+    if (total > FW_BOX_MAX_CHUNKS) return fail(ctx, FW_EINVAL, std::string(who) + ": more particles than one batch holds");
+    if (total * 8 > ctx->boxes.d_part.cap()) {  // more than any call before: the one case that waits (launches in flight may use the old scratch)
+        if ((st = sync(ctx)) || (st = alloc_buf(ctx, ctx->boxes.d_part, (size_t)((total + total / 4 + 1023u) & ~1023ull) * 8))) return st;
+    }
+    char *const d = ctx->boxes.d_tab;
+    FW_HIP(ctx, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, ctx->stream));
+    uint32_t launches = 0;
+    // (no synchronisation: the kernels read every count -- and a range ring's old part -- from the device)
+    const hipError_t le = fw_launch_boxes(ctx->stream, reinterpret_cast<const FwBoxEntry *>(d), e, reinterpret_cast<const FwBoxPlace *>(d + ne * sizeof(FwBoxEntry)), n,
+                                          (uint32_t)total, ctx->boxes.d_part, records, &launches);
+    ctx->boxes.launches += launches, ctx->boxes.last_chunks = total;
+    if ((st = ctx->boxes.h_tab.commit(ctx, ctx->stream))) return st;  // (behind the kernels: they read the device table the slot fed)
+    FW_HIP(ctx, le);
+    return FW_OK;
+}
+
+static fw_status boxes_args(fw_ctx *ctx, uint32_t n, const fw_spawner *handles, const void *out, const char *bad_handle) {
+    if (!ctx || (n && (!handles || !out))) return FW_EINVAL;
+    return check_handles(ctx, n, handles, bad_handle);
+}
+
+fw_status fw_ctx_aabbs(fw_ctx *ctx, uint32_t n, const fw_spawner *handles, fw_aabb *out) {
+    if (fw_status st = boxes_args(ctx, n, handles, out, "fw_ctx_aabbs: invalid spawner handle")) return st;
+    if (!n) return FW_OK;
+    fw_status st;
+    if ((size_t)n * 8 > ctx->boxes.h_out.cap()) {  // (nothing of an earlier call may still be on its way into the old records)
+        if ((st = sync(ctx)) || (st = alloc_buf(ctx, ctx->boxes.h_out, std::max<size_t>(64, (size_t)n * 2) * 8, Mem::pinned))) return st;
+    }
+    if ((st = boxes_enqueue(ctx, n, handles, ctx->boxes.h_out.get(), "fw_ctx_aabbs"))) return st;
+    // the records land in pinned memory: one synchronisation for the whole batch, then a host copy
+    st = sync(ctx);
+    if (!st) st = check_device_errors(ctx);
+    if (st && st != FW_ECAPACITY) return st;
+    memcpy(out, ctx->boxes.h_out.get(), (size_t)n * sizeof(fw_aabb));
+    return st;
+}
+
+fw_status fw_ctx_aabbs_device(fw_ctx *ctx, uint32_t n, const fw_spawner *handles, void *d_out) {
+    if (fw_status st = boxes_args(ctx, n, handles, d_out, "fw_ctx_aabbs_device: invalid spawner handle")) return st;
+    if (n && (reinterpret_cast<uintptr_t>(d_out) & 15u)) return fail(ctx, FW_EINVAL, "fw_ctx_aabbs_device: d_out is not 16-byte aligned");
+    if (!n) return FW_OK;
+    return boxes_enqueue(ctx, n, handles, d_out, "fw_ctx_aabbs_device");
+}
+
 fw_status fw_ctx_live_count(fw_ctx *ctx, uint64_t *out) {
     if (!ctx || !out) return FW_EINVAL;
     hipSetDevice(ctx->device);
@@ -1094,6 +1189,14 @@ fw_status fw_debug_tf_frames(fw_ctx *ctx, uint64_t *n) {
 fw_status fw_debug_param_bar(fw_ctx *ctx, int32_t *on) {  // fw_ctx::param_bar
     if (!ctx || !on) return FW_EINVAL;
     *on = ctx->param_bar ? 1 : 0;
+    return FW_OK;
+}
+// the batched boxes: launches of fw_k_boxes / fw_k_boxes_fold so far, the chunks of the latest call, list positions per chunk (fw_boxes.h)
+fw_status fw_debug_aabb_batch(fw_ctx *ctx, uint64_t *launches, uint64_t *chunks, uint32_t *chunk_size) {
+    if (!ctx) return FW_EINVAL;
+    if (launches) *launches = ctx->boxes.launches;
+    if (chunks) *chunks = ctx->boxes.last_chunks;
+    if (chunk_size) *chunk_size = FW_BOX_CHUNK;
     return FW_OK;
 }
 fw_status fw_debug_read_timestamps(fw_ctx *ctx, unsigned long long *out, uint64_t max_tiles, uint64_t *n_tiles) {

@@ -4,6 +4,7 @@
 #include "fw_ages.h"
 #include "fw_spin.h"
 #include "fw_sort.h"
+#include "fw_boxes.h"
 
 // ---------------------------------------------------------------------------------
 // readback / upload / render hand-off helpers
@@ -346,6 +347,49 @@ __global__ __launch_bounds__(FW_BLOCK) void fw_k_aabb_from_tiles(FwGlobals g, Fw
 fw_box_answer<FW_BLOCK>(g, L, parity, v, host8);
 }
 
+// The boxes of MANY spawners in two launches (fw_ctx_aabbs[_device]; fw_boxes.h): the host lists every (spawner, type) segment once
+// per output place it belongs to -- view, count word, upper bound, running sum of chunks -- and one WAVE takes one chunk of
+// FW_BOX_CHUNK list positions of one segment: a 733-particle emitter occupies two waves, not fw_k_aabb's 256 workgroups.  The wave
+// finds its entry by binary search, reads the device's count and leaves the box of [first, first + chunk) below min(count, bound)
+// -- fw_k_aabb's initial values where that is empty -- in its own 32-byte slot of the scratch.  No atomics, nobody waits for anybody.
+__global__ __launch_bounds__(64) void fw_k_boxes(const FwBoxEntry *tab, uint32_t n_entries, float *part8) {
+    const uint32_t chunk = blockIdx.x;
+    uint32_t first;
+    const FwBoxEntry &E = tab[fw_boxes_locate(tab, n_entries, chunk, &first)];
+    const FwSegView v = E.v;
+    const uint32_t n = min(*E.d_count, E.bound);
+    const uint32_t end = (n > first && n - first > FW_BOX_CHUNK) ? first + FW_BOX_CHUNK : n;
+    float m[6] = {3.40282347e+38f, 3.40282347e+38f, 3.40282347e+38f, FW_F32_MIN, FW_F32_MIN, FW_F32_MIN};
+    const uint32_t head = fw_view_head(v);
+    for (uint32_t li = first + threadIdx.x; li < end; li += 64u) {
+        const uint32_t i = fw_view_slot(v, head, li);
+        const float4 q0 = fw_view_q0(v, i);
+        const float sc = fw_view_scale(v, i, q0.w);
+        m[0] = fminf(m[0], q0.x - sc), m[1] = fminf(m[1], q0.y - sc), m[2] = fminf(m[2], q0.z - sc);
+        m[3] = fmaxf(m[3], q0.x + sc), m[4] = fmaxf(m[4], q0.y + sc), m[5] = fmaxf(m[5], q0.z + sc);
+    }
+    const float r = fw_box_fold<64>(m);
+    if (threadIdx.x < 6) part8[(size_t)chunk * 8u + (threadIdx.x < 3 ? threadIdx.x : threadIdx.x + 1u)] = r;  // {min.xyz, -, max.xyz, -}
+}
+// ... and one wave per output place folds the partial boxes of the place's chunks, ORs the counts of its entries for `any` and writes
+// the fw_aabb record {min.xyz, any, max.xyz, 0} -- to device memory, or to pinned host memory (the host form: no copy)
+__global__ __launch_bounds__(64) void fw_k_boxes_fold(const FwBoxEntry *tab, const FwBoxPlace *places, const float *part8, float *out8) {
+    const FwBoxPlace P = places[blockIdx.x];
+    float m[6] = {3.40282347e+38f, 3.40282347e+38f, 3.40282347e+38f, FW_F32_MIN, FW_F32_MIN, FW_F32_MIN};
+    for (uint32_t c = P.c0 + threadIdx.x; c < P.c1; c += 64u) {
+        const float4 lo = reinterpret_cast<const float4 *>(part8)[(size_t)c * 2], hi = reinterpret_cast<const float4 *>(part8)[(size_t)c * 2 + 1];
+        m[0] = fminf(m[0], lo.x), m[1] = fminf(m[1], lo.y), m[2] = fminf(m[2], lo.z);
+        m[3] = fmaxf(m[3], hi.x), m[4] = fmaxf(m[4], hi.y), m[5] = fmaxf(m[5], hi.z);
+    }
+    uint32_t any = 0;
+    for (uint32_t e = P.e0 + threadIdx.x; e < P.e1; e += 64u) any |= *tab[e].d_count;
+    const int got = __any(any != 0u);
+    const float r = fw_box_fold<64>(m);
+    float *rec = out8 + (size_t)blockIdx.x * 8u;
+    if (threadIdx.x < 6) rec[threadIdx.x < 3 ? threadIdx.x : threadIdx.x + 1u] = r;
+    if (threadIdx.x == 0) reinterpret_cast<int32_t *>(rec)[3] = got ? 1 : 0, reinterpret_cast<uint32_t *>(rec)[7] = 0u;
+}
+
 __global__ void fw_k_total(const uint32_t *counts, uint32_t n_seg, unsigned long long *out) {
     __shared__ unsigned long long s[4];
     unsigned long long t = 0;
@@ -467,7 +511,21 @@ hipError_t fw_launch_aabb_from_tiles(hipStream_t s, const FwGlobals &g, const ui
     return hipGetLastError();
 }
 
-hipError_t fw_launch_total(hipStream_t s, const uint32_t *counts, uint32_t n_seg, unsigned long long *d_out) {
+hipError_t fw_launch_boxes(hipStream_t s, const FwBoxEntry *d_tab, uint32_t n_entries, const FwBoxPlace *d_places, uint32_t n_places,
+                           uint32_t total_chunks, float *d_part, void *out_records, uint32_t *launches) {
+    *launches = 0;
+    if (!n_places) return hipSuccess;
+    if (total_chunks > FW_BOX_MAX_CHUNKS || (total_chunks && !n_entries)) return hipErrorInvalidValue;
+    if (total_chunks) {  // (no listed type can hold a particle: nothing to read, the fold alone answers)
+        hipLaunchKernelGGL(fw_k_boxes, dim3(total_chunks), dim3(64), 0, s, d_tab, n_entries, d_part);
+        ++*launches;
+    }
+    hipLaunchKernelGGL(fw_k_boxes_fold, dim3(n_places), dim3(64), 0, s, d_tab, d_places, (const float *)d_part, (float *)out_records);
+    ++*launches;
+    return hipGetLastError();
+}
+
+hipError_t fw_launch_total(hipStream_t s,const uint32_t *counts, uint32_t n_seg, unsigned long long *d_out) {
     hipLaunchKernelGGL(fw_k_total, dim3(1), dim3(256), 0, s, counts, n_seg, d_out);
     return hipGetLastError();
 }

@@ -462,6 +462,18 @@ hipError_t fw_launch_aabb(hipStream_t s, const FwGlobals &g, const uint32_t *seg
 // the same query answered from the per-tile boxes of the last update (epoch = that update's)
 hipError_t fw_launch_aabb_from_tiles(hipStream_t s, const FwGlobals &g, const uint32_t *seg_ids, uint32_t n_segs,
                                      uint32_t parity, uint32_t epoch, const uint32_t *d_seg_tile_first, float *h_out8);
+// The boxes of many spawners in two launches (fw_boxes.h; fw_k_boxes / fw_k_boxes_fold).  One entry per listed (spawner, type) segment:
+struct FwBoxEntry {
+    FwSegView v;
+    const uint32_t *d_count;  // the segment's live count, as the kernels keep it (count_slot)
+    uint32_t bound;           // host-known upper bound of that count: list positions at or beyond it are never read
+    uint32_t chunk0;          // chunks of the entries in front of this one (fw_boxes_plan)
+};
+struct FwBoxPlace;
+// d_tab, d_places: the two tables in device memory (n_entries, n_places records; total_chunks: the plan's); d_part: device scratch of
+// total_chunks * 8 floats; out_records: n_places fw_aabb records, device memory or PINNED host memory.  *launches: kernels enqueued
+hipError_t fw_launch_boxes(hipStream_t s, const FwBoxEntry *d_tab, uint32_t n_entries, const FwBoxPlace *d_places, uint32_t n_places,
+                           uint32_t total_chunks, float *d_part, void *out_records, uint32_t *launches);
 hipError_t fw_launch_total(hipStream_t s, const uint32_t *counts, uint32_t n_seg, unsigned long long *d_out);
 hipError_t fw_launch_copy_probe(hipStream_t s, const void *src, void *dst, size_t bytes);
 // Refit of a deformable mesh (fw_k_refit.hip): the levels of R.order, lowest first -- one launch per level of more than

@@ -419,6 +419,17 @@ INSTANCE_DTYPE = np.dtype(
 )
 assert INSTANCE_DTYPE.itemsize == 64
 
+# fw_aabb (include/firework_hip.h: BATCHED BOXES): the record ParticleSystem.aabb_records returns, one per listed spawner
+AABB_DTYPE = np.dtype(
+    [
+        ("min", np.float32, 3),
+        ("any", np.int32),
+        ("max", np.float32, 3),
+        ("reserved", np.uint32),
+    ]
+)
+assert AABB_DTYPE.itemsize == 32
+
 # fw_sort_view (include/firework_hip.h: DEPTH-SORTED INSTANCES): the camera SpawnerData.instances_sorted sorts for
 SORT_BACK_TO_FRONT, SORT_FRONT_TO_BACK = 0, 1
 

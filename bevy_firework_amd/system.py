@@ -475,6 +475,36 @@ class ParticleSystem:
         those instead of re-reading the particles."""
         self._check(self._lib.fw_ctx_track_aabbs(self._ctx, 1 if enable else 0))
 
+    # the boxes of MANY spawners in one call (include/firework_hip.h: BATCHED BOXES): what update_aabbs (render.rs:677-703) computes
+    # for every spawner every frame.  `spawners`: SpawnerData objects or raw handles, in any order, duplicates allowed
+    @staticmethod
+    def _handle_array(spawners):
+        n = len(spawners)
+        return n, (C.c_int32 * max(n, 1))(*[int(getattr(d, "handle", d)) for d in spawners])
+
+    def aabb_records(self, spawners) -> np.ndarray:
+        """records[i] (settings.AABB_DTYPE) = the box of spawners[i], as `SpawnerData.aabb()` answers it.  One wait for the batch."""
+        n, handles = self._handle_array(spawners)
+        out = np.zeros(n, dtype=S.AABB_DTYPE)
+        self._check(self._lib.fw_ctx_aabbs(self._ctx, n, handles, out.ctypes.data_as(C.c_void_p) if n else None))
+        return out
+
+    def aabbs(self, spawners):
+        """(any[n] bool, min[n, 3], max[n, 3]) of the spawners' boxes"""
+        r = self.aabb_records(spawners)
+        return r["any"] != 0, r["min"].copy(), r["max"].copy()
+
+    def aabbs_device(self, spawners, out_ptr: int) -> None:
+        """the same records into DEVICE memory at out_ptr (n x 32 bytes, 16-byte aligned), enqueued on the context's stream: no wait"""
+        n, handles = self._handle_array(spawners)
+        self._check(self._lib.fw_ctx_aabbs_device(self._ctx, n, handles, C.c_void_p(out_ptr) if out_ptr else None))
+
+    def debug_aabb_batch(self):
+        """(launches the batched box calls have enqueued so far, chunks of the latest call, list positions per chunk)"""
+        launches, chunks, size = C.c_uint64(), C.c_uint64(), C.c_uint32()
+        self._check(self._lib.fw_debug_aabb_batch(self._ctx, C.byref(launches), C.byref(chunks), C.byref(size)))
+        return int(launches.value), int(chunks.value), int(size.value)
+
     # -- statistics / measurement ----------------------------------------------------------------
     def live_count(self) -> int:
         out = C.c_uint64()

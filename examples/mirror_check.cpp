@@ -253,7 +253,62 @@ static int sorted_scenario() {
     return 0;
 }
 
+// `mirror_check aabbs`: three spawners -- two sphere emitters of different rates and an OnDemand one that is fed in frame 15 -- and every
+// tenth frame their boxes through all three forms (ParticleSpawnerData::aabb per spawner; ParticleSystemPlugin::aabbs and ::aabbs_device
+// over a list that names one spawner twice): one line per frame with the `any` flags, the digest of the batched records of either form
+// and the digest of the records the per-spawner calls make
+static int aabbs_scenario() {
+    try {
+        ParticleSystemPlugin app(0, /*seed*/ 0x00C0FFEE);
+        std::vector<ParticleSpawnerData *> ds;
+        for (int k = 0; k < 3; k++) {
+            ParticleSpawner sp;
+            sp.particle_settings.resize(1);
+            sp.particle_settings[0].lifetime = RandF32::constant(0.75f);
+            sp.particle_settings[0].linear_drag = 0.125f;
+            sp.emission_settings.resize(1);
+            EmissionSettings &e = sp.emission_settings[0];
+            e.particle_index = 0;
+            e.emission_pacing = k == 2 ? EmissionPacing::OnDemand() : EmissionPacing::rate(k == 0 ? 2000.0f : 150.0f);
+            e.emission_shape = EmissionShape::Sphere(0.75f);
+            e.initial_velocity = {{1.0f, 6.0f}, {0.0f, 1.0f, 0.0f}, 0.5f};
+            ds.push_back(app.spawn(sp, Transform{{0.25f + 4.0f * (float)k, 3.0f, 0.125f}, {}}, 7u + (uint32_t)k));
+        }
+        const std::vector<ParticleSpawnerData *> list = {ds[2], ds[0], ds[1], ds[0]};
+        void *d_rec = nullptr;
+        if (hipMalloc(&d_rec, list.size() * sizeof(fw_aabb)) != hipSuccess) throw Error(FW_EHIP, "hipMalloc");
+        hipStream_t st = (hipStream_t)app.stream();
+        const float dt = 1.0f / 60.0f;
+        for (int fr = 0; fr < 40; fr++) {
+            if (fr == 15) ds[2]->queue_particles(33);
+            app.update(dt);
+            if (fr % 10 != 9) continue;
+            app.aabbs_device(list, d_rec);  // (right behind the step: no wait in between)
+            const std::vector<fw_aabb> host = app.aabbs(list);
+            std::vector<fw_aabb> dev(list.size()), single(list.size());
+            if (hipMemcpyAsync(dev.data(), d_rec, dev.size() * sizeof(fw_aabb), hipMemcpyDeviceToHost, st) != hipSuccess) throw Error(FW_EHIP, "hipMemcpyAsync");
+            app.synchronize();
+            for (size_t i = 0; i < list.size(); i++) {
+                Vec3 mn, mx;
+                single[i] = fw_aabb{};
+                single[i].any = list[i]->aabb(mn, mx) ? 1 : 0;
+                single[i].min[0] = mn.x, single[i].min[1] = mn.y, single[i].min[2] = mn.z;
+                single[i].max[0] = mx.x, single[i].max[1] = mx.y, single[i].max[2] = mx.z;
+            }
+            std::printf("frame %d any %d%d%d%d host %016llx device %016llx single %016llx\n", fr, host[0].any, host[1].any, host[2].any, host[3].any,
+                        (unsigned long long)fnv(host.data(), host.size() * sizeof(fw_aabb)), (unsigned long long)fnv(dev.data(), dev.size() * sizeof(fw_aabb)),
+                        (unsigned long long)fnv(single.data(), single.size() * sizeof(fw_aabb)));
+        }
+        (void)hipFree(d_rec);
+    } catch (const Error &e) {
+        std::fprintf(stderr, "firework error %d: %s\n", (int)e.status, e.what());
+        return 1;
+    }
+    return 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc > 1 && std::strcmp(argv[1], "aabbs") == 0) return aabbs_scenario();
     if (argc > 1 && std::strcmp(argv[1], "sorted") == 0) return sorted_scenario();
     if (argc > 1 && std::strcmp(argv[1], "project") == 0) return project_scenario();
     if (argc > 1 && std::strcmp(argv[1], "paths") == 0) return paths_scenario();

@@ -507,6 +507,21 @@ class ParticleSystemPlugin {
     // update_aabbs (render.rs:677-703) fused into the update: every frame leaves per-tile boxes, ParticleSpawnerData::aabb
     // folds them instead of re-reading the particles
     void track_aabbs(bool enable) { check(fw_ctx_track_aabbs(ctx_, enable ? 1 : 0)); }
+    // the boxes of MANY spawners in one call (firework_hip.h: BATCHED BOXES; update_aabbs walks every spawner, render.rs:677-703):
+    // record i belongs to ds[i] -- any order, duplicates answered -- and equals what ds[i]->aabb answers.  Two launches, one wait
+    std::vector<fw_aabb> aabbs(const std::vector<ParticleSpawnerData *> &ds) {
+        std::vector<fw_spawner> h;
+        for (const ParticleSpawnerData *d : ds) h.push_back(d->handle);
+        std::vector<fw_aabb> out(h.size());
+        check(fw_ctx_aabbs(ctx_, (uint32_t)h.size(), h.data(), out.data()));
+        return out;
+    }
+    // ... the same records into DEVICE memory (ds.size() x 32 bytes, 16-byte aligned) on the context's stream: no wait
+    void aabbs_device(const std::vector<ParticleSpawnerData *> &ds, void *d_out) {
+        std::vector<fw_spawner> h;
+        for (const ParticleSpawnerData *d : ds) h.push_back(d->handle);
+        check(fw_ctx_aabbs_device(ctx_, (uint32_t)h.size(), h.data(), d_out));
+    }
 
     // one run of the chained systems (plugin.rs:46-60)
     void update(float dt) {

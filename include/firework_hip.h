@@ -648,6 +648,37 @@ fw_status fw_spawner_aabb(fw_ctx *ctx, fw_spawner h, float out_min[3], float out
  * bit.  Frames with colliding particle types, and queries after the state was touched outside fw_step, fall back to the
  * two-pass reduction. */
 fw_status fw_ctx_track_aabbs(fw_ctx *ctx, int32_t enable);
+/* BATCHED BOXES (update_aabbs recomputes the box of EVERY spawner every frame, render.rs:677-703, and frustum culling reads them: a
+ * host with thousands of emitters cannot cross the FFI, launch and wait once per spawner).  fw_ctx_aabbs answers the boxes of
+ * handles[n] in one call, two kernel launches and one wait; fw_ctx_aabbs_device leaves the same records in DEVICE memory without
+ * waiting, for a host that culls or builds indirect draws on the GPU.
+ *   SAME BOX  out[i] is what fw_spawner_aabb(handles[i]) answers at the same place in the stream: min / max of position -/+ scale over
+ *             every particle of every particle type, scale as every reader evaluates it; any = 1 exactly where that call sets *any.
+ *             A spawner that holds no particle gets any = 0, min = {FLT_MAX, FLT_MAX, FLT_MAX} and max = {-FLT_MAX, -FLT_MAX,
+ *             -FLT_MAX} (3.40282347e+38: the values the reduction starts from).  min / max skip a NaN as fminf / fmaxf do.  Equal means
+ *             equal as floats: -0 and +0 are the same answer (the order of a min over the two is nobody's to promise).  `reserved` is
+ *             written as 0.  The batched forms always read the particles: the answer is the same with fw_ctx_track_aabbs on or off.
+ *   ORDER     out[i] belongs to handles[i]; a handle may appear more than once, and each place is answered.
+ *   RULES     as fw_spawner_aabb: frames a FIFO ring withheld are enqueued first (once), stale ages of such a ring are written back, a
+ *             deferred spin stays deferred -- a host that asks every frame keeps those rules.
+ *   STREAM    the device form enqueues on the context's main stream (fw_ctx_stream), behind every fw_step called before it and in front
+ *             of every one called after; its host work grows with the number of listed particle types, never with the particles.  It
+ *             never waits -- with the ONE exception fw_ctx_depth_order_device has: the tables and the scratch (32 bytes per 512
+ *             particles of the listed types' bounds) belong to the context and only grow; a call that needs more than any call before
+ *             it waits for the stream once and reallocates.  d_out: n records, 16-byte aligned.  The host form has the records
+ *             written to pinned memory the context keeps, waits once and copies; it reports FW_ECAPACITY as fw_spawner_aabb does: the
+ *             boxes are written and the status is returned.
+ *   ERRORS    a null context, n > 0 with null handles or a null (or misaligned) output, ONE invalid handle anywhere in the list
+ *             (all-or-nothing, as fw_ctx_set_origins): FW_EINVAL, nothing enqueued, nothing written.  n == 0: FW_OK, nothing touched.
+ *             A poisoned spawner in the list ends the call with the status fw_spawner_aabb gives for it, and nothing is written. */
+typedef struct fw_aabb { /* 32 bytes */
+    float min[3];
+    int32_t any; /* 0: the spawner holds no particle */
+    float max[3];
+    uint32_t reserved; /* written as 0 */
+} fw_aabb;
+fw_status fw_ctx_aabbs(fw_ctx *ctx, uint32_t n, const fw_spawner *handles, fw_aabb *out);
+fw_status fw_ctx_aabbs_device(fw_ctx *ctx, uint32_t n, const fw_spawner *handles, void *d_out);
 
 /* ---- whole-context statistics ---------------------------------------------------- */
 /* total live particles over all spawners (host value; synchronises) */

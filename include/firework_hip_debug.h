@@ -96,6 +96,11 @@ fw_status fw_debug_fuse_frames(fw_ctx *ctx, uint64_t *frames);
  * FW_PARAM_BAR=0) */
 fw_status fw_debug_param_bar(fw_ctx *ctx, int32_t *on);
 
+/* The batched boxes (firework_hip.h: BATCHED BOXES).  *launches = kernel launches fw_ctx_aabbs and fw_ctx_aabbs_device have enqueued so
+ * far: two per call whatever n is (one where no listed particle type can hold a particle: there is nothing to read); *chunks = the
+ * chunks -- waves of the first launch -- of the latest call; *chunk_size = list positions per chunk.  Any pointer may be null */
+fw_status fw_debug_aabb_batch(fw_ctx *ctx, uint64_t *launches, uint64_t *chunks, uint32_t *chunk_size);
+
 #ifdef __cplusplus
 }
 #endif

@@ -87,6 +87,9 @@ pub struct fw_particle_instance {                      // == render::ParticleIns
 #[repr(C)] #[derive(Clone, Copy)] pub struct fw_sort_view {       // the camera of a depth sort (32 bytes); order: FW_SORT_*, reserved: 0
     pub eye: [f32; 3], pub order: u32, pub forward: [f32; 3], pub reserved: u32,
 }
+#[repr(C)] #[derive(Clone, Copy, Default)] pub struct fw_aabb {     // one box of fw_ctx_aabbs[_device] (32 bytes); any: 0 = no particle, reserved: written as 0
+    pub min: [f32; 3], pub any: i32, pub max: [f32; 3], pub reserved: u32,
+}
 pub const FW_SORT_BACK_TO_FRONT: u32 = 0;
 pub const FW_SORT_FRONT_TO_BACK: u32 = 1;
 
@@ -141,6 +144,8 @@ extern "C" {
     pub fn fw_ctx_pack_instances_sorted(ctx: *mut fw_ctx, h: fw_spawner, ty: u32, view: *const fw_sort_view, out: *mut fw_particle_instance, cap: u64, n: *mut u64) -> c_int;
     pub fn fw_spawner_aabb(ctx: *mut fw_ctx, h: fw_spawner, min: *mut f32, max: *mut f32, any: *mut i32) -> c_int;
     pub fn fw_ctx_track_aabbs(ctx: *mut fw_ctx, enable: i32) -> c_int;
+    pub fn fw_ctx_aabbs(ctx: *mut fw_ctx, n: u32, handles: *const fw_spawner, out: *mut fw_aabb) -> c_int;
+    pub fn fw_ctx_aabbs_device(ctx: *mut fw_ctx, n: u32, handles: *const fw_spawner, d_out: *mut c_void) -> c_int;
     pub fn fw_ctx_live_count(ctx: *mut fw_ctx, out: *mut u64) -> c_int;
     pub fn fw_ctx_live_count_device(ctx: *mut fw_ctx, d_out_u64: *mut c_void) -> c_int;
     pub fn fw_ctx_live_count_ring(ctx: *mut fw_ctx, d_ring_u64: *mut c_void, n_slots: u32) -> c_int;

@@ -133,17 +133,22 @@ pub struct SharedInstanceBuffer {
 //     pass.set_vertex_buffer(0, instance_buffer.unwrap().buffer.slice(..));
 //     pass.draw(0..6, w.first..w.first + w.count);            // was: pass.draw(0..6, 0..buffer_length)
 
-/// update_aabbs (src/render.rs:677-703) through `fw_spawner_aabb`: min / max of `position -/+ scale` over every particle of every
-/// type of the spawner come from the device -- fused into the update when `fw_ctx_track_aabbs(ctx, 1)` was called once after
-/// `HipBackend::new` (a few hundred 32-byte tile boxes folded per query instead of two passes over the particles; same bits,
-/// min / max are exact) -- and the centre is brought into the entity's local space as in the reference.
+/// update_aabbs (src/render.rs:677-703) through ONE `fw_ctx_aabbs` over every queried spawner (round 25; a `fw_spawner_aabb` per
+/// spawner costs a launch pair and a wait each): min / max of `position -/+ scale` over every particle of every type of each spawner
+/// come from the device in two launches and one wait for the whole query, record i for handle i, and the centre is brought into
+/// the entity's local space as in the reference.  A spawner without particles (`any == 0`) keeps its box, as before.
 pub fn hip_update_aabbs(backend: NonSend<HipBackend>, mut q: Query<(&mut Aabb, &GlobalTransform, &HipSpawner)>) {
-    for (mut aabb, global_transform, h) in &mut q {
-        let (mut mn, mut mx, mut any) = ([0f32; 3], [0f32; 3], 0i32);
-        if backend.check(unsafe { fw_spawner_aabb(backend.ctx, h.0, mn.as_mut_ptr(), mx.as_mut_ptr(), &mut any) }).is_err() || any == 0 {
+    let handles: Vec<fw_spawner> = q.iter().map(|(_, _, h)| h.0).collect();
+    let mut boxes = vec![fw_aabb::default(); handles.len()];
+    if backend.check(unsafe { fw_ctx_aabbs(backend.ctx, handles.len() as u32, handles.as_ptr(), boxes.as_mut_ptr()) }).is_err() {
+        return; // (all-or-nothing: nothing was written)
+    }
+    // (a Query iterates in the same order while nothing changes its archetypes in between: record i is entity i's)
+    for ((mut aabb, global_transform, _), b) in q.iter_mut().zip(boxes.iter()) {
+        if b.any == 0 {
             continue; // (the reference `continue`s on a spawner without particle vectors, src/render.rs:679-681)
         }
-        let (min, max) = (Vec3::from_array(mn), Vec3::from_array(mx));
+        let (min, max) = (Vec3::from_array(b.min), Vec3::from_array(b.max));
         let center = (min + max) / 2.;
         let half_extents = (max - min) / 2.;
         aabb.center = global_transform.to_matrix().inverse().transform_point3(center).into(); // src/render.rs:696-700
