@@ -838,6 +838,11 @@ struct fw_ctx {
     // spinless).  FW_SPINLESS=0: they keep the form that finds out per workgroup (A/B in one build)
     bool use_spinless = true;
     uint64_t spinless_launches = 0;  // fw_debug_spinless_launches
+    // ... and their WHOLE ring tiles -- every slot a particle that lives through the launch (fw_fifo_tile_whole, fw_fuse2.h) -- take an arm of
+    // the fused forms that issues all of a tile's loads first and never waits for a store (FwFifoArgs::fuse_pad[FW_FIFO_WHOLE], round 26).
+    // FW_WHOLE_TILES=0: every tile keeps the streaming loop (A/B in one build).  whole_launches / whole_tiles: fw_debug_whole_tiles
+    bool use_whole_tiles = true;
+    uint64_t whole_launches = 0, whole_tiles = 0;
     // Up to fuse_depth frames of unread rings in one launch (fw_fuse2.h).  A frame whose only GPU work would be one spin-less
     // FIFO launch of rings that all deferred their spin in it -- each with at least fuse2_min live particles (FW_FUSE2_MIN: its own knob, the
     // default of spin_defer_min) -- is WITHHELD: all of its bookkeeping done, the complete launch kept here instead of enqueued.  The next

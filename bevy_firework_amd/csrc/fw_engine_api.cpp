@@ -209,6 +209,7 @@ fw_status fw_ctx_create(int device, uint32_t seed, void *stream, fw_ctx **out) {
     if (const char *m = getenv("FW_SPIN_DEFER_AFTER")) ctx->spin_defer_after = (uint32_t)strtoul(m, nullptr, 10);
     if (const char *m = getenv("FW_SPIN_LOG")) ctx->spin_log_cap = (uint32_t)strtoul(m, nullptr, 10);
     if (const char *m = getenv("FW_SPINLESS")) ctx->use_spinless = atoi(m) != 0;
+    if (const char *m = getenv("FW_WHOLE_TILES")) ctx->use_whole_tiles = atoi(m) != 0;
     if (const char *m = getenv("FW_FUSE2")) ctx->use_fuse2 = atoi(m) != 0;
     if (const char *m = getenv("FW_FUSE2_MIN")) ctx->fuse2_min = (uint32_t)strtoul(m, nullptr, 10);
     if (const char *m = getenv("FW_FUSE_DEPTH")) ctx->fuse_depth = (uint32_t)std::min(std::max(atoi(m), 2), (int)FW_FUSE_MAX);
@@ -1166,6 +1167,13 @@ fw_status fw_debug_spin_launches(fw_ctx *ctx, uint64_t *n) {
 fw_status fw_debug_spinless_launches(fw_ctx *ctx, uint64_t *n) {
     if (!ctx || !n) return FW_EINVAL;
     *n = ctx->spinless_launches;
+    return FW_OK;
+}
+// spin-less FIFO launches so far in which the host's evaluation of fw_fifo_tile_whole found a whole ring tile, and those tiles
+fw_status fw_debug_whole_tiles(fw_ctx *ctx, uint64_t *launches, uint64_t *tiles) {
+    if (!ctx) return FW_EINVAL;
+    if (launches) *launches = ctx->whole_launches;
+    if (tiles) *tiles = ctx->whole_tiles;
     return FW_OK;
 }
 // FIFO launches so far that ran two or more frames in one pass (fw_ctx::pend, FwFifoArgs::fused) / withheld frames that went to the stream alone

@@ -467,6 +467,22 @@ void group_launched(fw_ctx *ctx, const FwFifoArgs &fa, const uint64_t *frames, u
     }
 }
 
+// fw_debug_whole_tiles: the ring tiles of a launch that is about to go to the stream which the predicate calls whole -- the kernel's own
+// lines (fw_fifo_tile_whole over the tiles FwFifoSeg lays out) and its own conditions (fw_update_fifo_body).  The workgroups of a FUSED
+// launch take the arm for exactly these tiles; an unfused launch's are counted too, and keep the streaming loop (the arm lost there)
+void count_whole_tiles(fw_ctx *ctx, const FwFifoArgs &fa) {
+    if (!fa.fuse_pad[FW_FIFO_WHOLE] || fa.dbg != 0u) return;
+    uint64_t n = 0;
+    for (uint32_t j = 0; j < fa.n_segs; j++) {
+        const FwFifoSeg &F = fa.s[j];
+        if (F.mat) continue;
+        const uint32_t ring_tiles = F.capacity / FW_TILE, live_tiles = F.n_tiles - std::min(F.n_tiles, F.n_vt_a + F.n_vt_b);
+        for (uint32_t t = 0; t < live_tiles; t++)
+            n += fw_fifo_tile_whole(F.capacity, FW_TILE, F.head, F.n_in, F.dead, (F.tile0 + t) % ring_tiles) ? 1u : 0u;
+    }
+    ctx->whole_tiles += n, ctx->whole_launches += n ? 1u : 0u;
+}
+
 }  // namespace
 
 namespace fwh {
@@ -480,11 +496,13 @@ fw_status flush_withheld(fw_ctx *ctx) {
     if (P.depth >= 2u) {
         ctx->fused_launches++, ctx->fuse_frames += P.depth;
         group_launched(ctx, P.fa, P.frame, P.depth - 1u, P.spin_from, P.depth);
+        count_whole_tiles(ctx, P.fa);
         FW_HIP(ctx, fw_launch_update_fifo(ctx->stream, ctx->g, P.fa, P.fio, P.tiles, P.nt, nullptr, nullptr, &P.fz));
         return FW_OK;
     }
     ctx->fuse2_flushed++;
     group_launched(ctx, P.fa, P.frame, 0u, P.spin_from, 0u);
+    count_whole_tiles(ctx, P.fa);
     FW_HIP(ctx, fw_launch_update_fifo(ctx->stream, ctx->g, P.fa, P.fio, P.tiles, P.nt, nullptr, nullptr));
     return FW_OK;
 }
@@ -525,6 +543,7 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
     uint32_t f_ops = 0, f_tiles = 0;
     uint64_t f_bytes = 0;  // what the launch streams, roughly: its tiles x the bytes a particle of the type moves
     bool f_nospin = true;  // every ring of the launch so far carries FW_TYPE_IDX_NOSPIN in it (FwFifoArgs::spinless)
+    bool f_derived = true; // ... and is of a FW_TYPE_DERIVED type (FwFifoArgs::fuse_pad[FW_FIFO_WHOLE])
     // several frames in one launch (fw_ctx::pend): every ring of the launch so far deferred its spin in it and holds fuse2_min particles; the
     // launches of this frame so far; what a cohort this frame spawns carries as its spin pointer, per ring of the launch
     bool f_fusable = true;
@@ -549,6 +568,8 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
         // (no ring tile of the launch touches rotation or angular velocity: the kernel form compiled for that -- rings with Q0 in planes,
         // four-round tiles, no instance records)
         fa.spinless = (ctx->use_spinless && f_nospin && fa.q0pl && !fa.any_inst && !fa.small_tiles) ? 1u : 0u;
+        // (... and its whole ring tiles owe nothing but position, age and velocity: the arm without a divergent lane, fw_fifo_tile_whole)
+        fa.fuse_pad[FW_FIFO_WHOLE] = (ctx->use_whole_tiles && fa.spinless && f_derived && fa.write_mask == 0) ? 1u : 0u;
         const int nt = f_bytes > ctx->nt_bytes ? 2 : f_bytes > ctx->nt_wo_bytes ? 1 : 0;
         // the frame's one launch, spin-less, every ring unread and large: it may wait for the next frame, or take the waiting one in
         const bool candidate = fw_fuse2_candidate(ctx->use_fuse2, quiet, n_launches == 0 && fa.n_segs == ctx->n_fifo, fa.spinless != 0u, f_fusable);
@@ -569,6 +590,7 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
                 P.on = false;
                 group_launched(ctx, fa, P.frame, P.depth, f_spin_from, depth);
                 ctx->fused_launches++, ctx->fuse_frames += depth;
+                count_whole_tiles(ctx, fa);
                 FW_HIP(ctx, fw_launch_update_fifo(fstream, ctx->g, fa, fio, f_tiles, nt, nullptr, nullptr, &fz));
             } else {  // withheld too: the group so far is the fused launch, kept (what flush_withheld enqueues)
                 fa.host_counts = nullptr;
@@ -593,11 +615,12 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
             for (uint32_t j = 0; j < fa.n_segs; j++) ctx->segs[fa.s[j].seg].fuse_last = 0u;
             hipEvent_t e0, e1;
             next_timing_pair(ctx, fr, &e0, &e1);
+            count_whole_tiles(ctx, fa);
             FW_HIP(ctx, fw_launch_update_fifo(fstream, ctx->g, fa, fio, f_tiles, nt, e0, e1));
         }
         if (side) ctx->side_dirty = true;
         fa = FwFifoArgs{};
-        f_ops = f_tiles = 0, f_bytes = 0, f_nospin = true, f_fusable = true, f_deep = true, f_wide = true;
+        f_ops = f_tiles = 0, f_bytes = 0, f_nospin = true, f_derived = true, f_fusable = true, f_deep = true, f_wide = true;
         return FW_OK;
     };
     // (two passes: the rings that keep Q0 in planes -- SegHost::q0pl, the ones that may run under the age rule -- get a launch of their own,
@@ -684,6 +707,7 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
             F.mat = mat ? 1u : 0u;
             fa.q0pl = S.q0pl ? 1u : 0u;  // (the same for every ring of a launch: the two passes)
             f_nospin &= (F.type_idx & FW_TYPE_IDX_NOSPIN) != 0u;
+            f_derived &= S.derived;
             F.n_lplanes = S.n_lplanes;
             F.report = S.fifo_dev ? S.h_report + (ctx->frame % kReportRing) : nullptr;
             F.op0 = f_ops;

@@ -6,8 +6,8 @@
 // frame: the withheld frames so far are ONE fused frame (fw_fuse2_frame, folded), and the pair rule between it and the next frame is the
 // rule of the group (FwFuseGroup, fw_fuse_push).  Here: what a launch lays out for a ring (the arithmetic launch_fifo has always done),
 // when a frame may join, and the fused frame with the per-frame boundaries the kernel needs.
-// Plain C++ behind FW_HD, like fw_spin.h: the host (launch_fifo) and three host tests (tests/test_cpp_host_fuse2.py, test_cpp_host_fuse_deep.py,
-// test_cpp_host_fuse_wide.py) compile the same lines.
+// Plain C++ behind FW_HD, like fw_spin.h: the host (launch_fifo) and four host tests (tests/test_cpp_host_fuse2.py, test_cpp_host_fuse_deep.py,
+// test_cpp_host_fuse_wide.py, test_cpp_host_whole_tiles.py) compile the same lines -- and so does the kernel, for fw_fifo_tile_whole (round 26).
 #pragma once
 #include <stdint.h>
 
@@ -46,6 +46,20 @@ FW_HD FwFifoLayout fw_fifo_layout(uint32_t capacity, uint32_t tile, uint32_t blo
     L.n_tiles = L.n_vt_a + L.n_vt_b + L.live_tiles;
     if (L.n_tiles == 0u) L.n_tiles = 1u;
     return L;
+}
+
+// Is ring tile `pt` (slots [pt * tile, (pt + 1) * tile)) of a launch WHOLE: does every one of its slots hold a particle that was in the ring
+// before the launch and lives through it -- a logical index, counted from the launch's head with the ring's wrap, in [dead, n_in)?  (round 26:
+// such a tile's update has no divergent lane, fw_update_fifo_body; head / n_in / dead: FwFifoSeg's, the fused frame's in a fused launch.)
+// The logical indices of a tile's slots are consecutive unless the head lies strictly inside the tile: then the slots in front of it carry
+// the LAST indices of the ring and the tile is whole only in a ring that is full and loses nobody.
+// (head < capacity, a multiple of `tile`; pt < capacity / tile; dead <= n_in <= capacity)
+FW_HD bool fw_fifo_tile_whole(uint32_t capacity, uint32_t tile, uint32_t head, uint32_t n_in, uint32_t dead, uint32_t pt) {
+    const uint32_t s0 = pt * tile;
+    if (n_in > capacity || dead > n_in) return false;  // (a count only the device knows, FwFifoSeg::n_in = 0xFFFFFFFF: never whole)
+    if (head > s0 && head - s0 < tile) return dead == 0u && n_in == capacity;
+    const uint32_t i0 = s0 >= head ? s0 - head : s0 + (capacity - head);  // (<= capacity - tile)
+    return i0 >= dead && i0 + tile <= n_in;
 }
 
 // Is a frame's launch one that may be withheld, or take the withheld one in?  enabled: fw_ctx::use_fuse2 (FW_FUSE2); quiet: the frame's only

@@ -271,7 +271,18 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
     uint32_t sbase = spawner ? head + n_in + k0 : pt * TILE;
     if (sbase >= C) sbase -= C;
     if (spawner && sbase >= C) sbase -= C;  // (head + n_in + k0 < 3 C)
-    const float key0 = tid < F.keys_len ? g.keys[F.keys_off + tid] : 0.0f;
+    // WHOLE: a ring tile of a fused spin-less launch every slot of which holds a particle that lives through the launch (fw_fifo_tile_whole,
+    // fw_fuse2.h; round 26) -- and which owes nothing but position, age and velocity: FwFifoArgs::fuse_pad[FW_FIFO_WHOLE] says
+    // that every ring of the launch is of a FW_TYPE_DERIVED type (no optional plane is stored, whatever WM), the ring's new particles are
+    // not materialised (so nobody is `full`, and `defer` is off), no profiling mode.  Workgroup-uniform, from the kernel arguments alone.
+    // Such a tile has no divergent lane: all of its loads are issued before anything else and none of its waits counts a store (below).
+    // The FUSED forms only: measured, the unfused spin-less forms lose 1.2 to 4.5 % with the arm (one frame of arithmetic per load is too
+    // little to pay for giving up the loop's overlap of a round's stores with the next round's arithmetic: profiles/r26/whole_tiles_ab.txt)
+    constexpr bool WT = SPINLESS && FUSE != 0;
+    bool whole = false;
+    if constexpr (WT) whole = !spawner && a.fuse_pad[FW_FIFO_WHOLE] != 0u && F.mat == 0u && a.dbg == 0u && fw_fifo_tile_whole(C, TILE, head, F.n_in, n_dead, pt);
+    // (a whole tile evaluates no curve: neither the keys nor the barrier)
+    const float key0 = (!whole && tid < F.keys_len) ? g.keys[F.keys_off + tid] : 0.0f;
     char *buf = F.buf;
     // round 0 of a live tile (every slot of a tile exists -- the capacity is a multiple of FW_TILE -- so the loads
     // need no bounds; a spawning workgroup loads nothing)
@@ -348,7 +359,17 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
         if (!nospin) v.w = fw_ld1w<NT == 2>(iw2 + 3 * cp, o16 / 4u);
         return v;
     };
-    if (!spawner && !defer) {
+    // a whole tile: position (and age, where kept) of all R rounds, then the velocities -- 6 or 7 R loads in flight before anything else
+    float4 wq0[R], wq1[R];  // (nobody's registers in the other forms: `whole` is false when they are compiled)
+    if constexpr (WT) {
+        if (whole) {
+#pragma unroll
+            for (int r = 0; r < R; r++) wq0[r] = ld0((uint32_t)(r * BLK + (int)tid) * 16u);
+#pragma unroll
+            for (int r = 0; r < R; r++) wq1[r] = ld1((uint32_t)(r * BLK + (int)tid) * 16u);
+        }
+    }
+    if (!spawner && !defer && !whole) {
         q0c = ld0(tid * 16u), q3c = ld3(tid * 16u);
         q1c = ld1(tid * 16u), q2c = ld2(tid * 16u);
         if constexpr (R > 1) {
@@ -383,9 +404,46 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
         if (!spawner && nospin && axis != 0u) T.flags |= FW_TYPE_NOSPIN;
     }
     const FwCollArm CA = fw_coll_arm<COLL>(g, F.type_idx & FW_TYPE_IDX_MASK);
-    if (tid < F.keys_len) s_keys[tid] = key0;
-    for (uint32_t i = tid + BLK; i < F.keys_len; i += BLK) s_keys[i] = g.keys[F.keys_off + i];
-    __syncthreads();
+    bool bad = false;
+    if (whole) {
+        // ---- a WHOLE tile (round 26): every lane of every round is `mine` and not `dead`, so nothing diverges.  The loads are all in flight
+        // (above); the rounds run unrolled -- the withheld frames through fw_move_step, the last frame through the same statements (what
+        // fw_integrate_store evaluates for a type that cannot turn and stores no optional plane; no contraction in this build: the same
+        // bits), the age chain and the `bad` test of the streaming loop -- and the stores, unconditional and in place, come behind the
+        // last round's arithmetic: every wait of the arm counts loads alone, and no wave waits for a store.  Here, in front of the
+        // spawning workgroups' code, so that the tile's 24 to 28 registers of data are nobody else's.
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            float4 q0w = wq0[r], q1w = wq1[r];
+            if constexpr (FUSE != 0) {
+#pragma unroll
+                for (int f = 0; f < FUSE - 1; f++) {
+                    const float dt_f = fz->dt_pre[f];
+                    const FwMove mv = fw_move_step(T, dt_f, q0w, q1w);
+                    q0w = make_float4(mv.px, mv.py, mv.pz, q0w.w + dt_f);
+                    q1w.x = mv.vx, q1w.y = mv.vy, q1w.z = mv.vz;
+                }
+            }
+            float age_new;
+            const bool surv = fw_survives(q0w.w, a.dt, q3s.w, &age_new);
+            bad |= !ageless && !surv;  // (mine, not dead: the host's cohort ages and the particle disagree)
+            const FwMove mv = fw_move_step(T, a.dt, q0w, q1w);
+            wq0[r] = make_float4(mv.px, mv.py, mv.pz, age_new);
+            wq1[r].x = mv.vx, wq1[r].y = mv.vy, wq1[r].z = mv.vz;
+        }
+        char *ow0 = buf + FW_OFF_Q0(C) + sfirst / 4u, *ow1 = buf + FW_OFF_Q1(C) + sfirst / 4u;  // (fw_out_window's q0 / q1 of a ring with Q0 in planes)
+#pragma unroll
+        for (int r = 0; r < R; r++) {
+            const uint32_t b4 = (uint32_t)(r * BLK + (int)tid) * 4u;
+            fw_stc3w<NT == 2>(ow0, cp, b4, wq0[r].x, wq0[r].y, wq0[r].z);
+            if (!ageless) fw_st1w<NT == 2>(ow0 + 3 * cp, b4, wq0[r].w);
+            fw_stc3w<NT == 2>(ow1, cp, b4, wq1[r].x, wq1[r].y, wq1[r].z);
+        }
+    } else {  // (workgroup-uniform)
+        if (tid < F.keys_len) s_keys[tid] = key0;
+        for (uint32_t i = tid + BLK; i < F.keys_len; i += BLK) s_keys[i] = g.keys[F.keys_off + i];
+        __syncthreads();
+    }
     const bool want_destroyed = T.report_destroyed && F.destroyed != nullptr;
     if (!spawner && tis != 0u) {
         // a tile without a single particle (the grid of a segment whose count only the device knows covers its ring)
@@ -396,7 +454,6 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
     char *inst = INST ? F.inst : nullptr;
     float4 *s_inst_wave = s_inst + (INST ? wave * 256u : 0u);
     const FwOutWin W = fw_out_window(buf, C, sbase, T, 0u, 0u, true, true, q0pl, ageless);
-    bool bad = false;
     if (spawner) {
         // ---- this frame's new particles: spawn_particles (core.rs:437-469) right before update_particles, each in the
         // slot it will live in.  One round per workgroup: spawning is ~5x the arithmetic of an update.
@@ -456,7 +513,7 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
         } else if (is_new && want_destroyed)  // born and destroyed in the same frame (dt >= lifetime)
             fw_store_destroyed(F.destroyed, buf, C, s, false, T, s_keys, so.q0, so.q1, so.q2, so.q3, age_new, i);
         fw_fifo_inst_out<INST, NT == 2>(F, inst, s_inst_wave, rec, lane, m, alive, i - n_dead);
-    } else {
+    } else if (!whole) {
         // (the record and the window a ring tile works with: the workgroup's own -- or, SPINLESS, copies in which "cannot turn" is known
         // when the tile's code is compiled: neither fw_integrate_store's spin nor a store to Q2 / Q3 is left in it)
         FwType Ts;

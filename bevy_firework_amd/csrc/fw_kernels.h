@@ -264,8 +264,12 @@ struct FwFifoArgs {
     // scalar cache, which the spawning workgroups -- the launch's longest chain -- read their ops through.  Measured, round 22
     // (profiles/r22/fuse2_ab.txt): with 72 bytes more configs[0]'s launch took 1.2-1.4 % longer in three builds, with the
     // record grown by two whole lines it keeps the parent's time
+    // (round 26: word FW_FIFO_WHOLE of them is 1 in a spin-less launch whose whole ring tiles may take the arm without a divergent lane --
+    // fw_update_fifo_body, fw_fifo_tile_whole: fw_ctx::use_whole_tiles, and every ring of the launch is of a FW_TYPE_DERIVED type, the fact
+    // write_mask == 0 travels with -- and 0 everywhere else; the fused forms alone look at it.  No argument moves.)
     uint32_t fuse_pad[31];
 };
+#define FW_FIFO_WHOLE 0
 static_assert((sizeof(FwGlobals) + sizeof(FwFifoArgs)) % 64 == 0, "FwInlineOps starts on a 64-byte line of the kernel arguments");
 static_assert(sizeof(FwFifoArgs) == 1440, "the size every form of the FIFO kernel was measured with (profiles/r22/fuse2_ab.txt)");
 // What a fused launch of depth D = FwFifoArgs::fused knows beside FwFifoArgs (round 23): the FOURTH argument of the fused kernels, behind

@@ -575,6 +575,13 @@ class ParticleSystem:
         self._check(self._lib.fw_debug_spinless_launches(self._ctx, C.byref(n)))
         return int(n.value)
 
+    def whole_tiles(self):
+        """(launches, tiles): spin-less FIFO launches so far in which the host found a whole ring tile -- every slot a particle that lives
+        through the launch -- and those tiles: they take the arm that issues all loads first"""
+        launches, tiles = C.c_uint64(), C.c_uint64()
+        self._check(self._lib.fw_debug_whole_tiles(self._ctx, C.byref(launches), C.byref(tiles)))
+        return int(launches.value), int(tiles.value)
+
     def fuse2_launches(self):
         """(fused, flushed): FIFO launches so far that ran two frames of unread rings in one pass, and withheld frames that went to the
         stream alone"""

@@ -79,6 +79,15 @@ fw_status fw_debug_spin_launches(fw_ctx *ctx, uint64_t *n);
  * four-round tiles.  FW_SPINLESS=0 (with FW_ENABLE_KNOBS) keeps such launches on the form that finds out per workgroup: 0 then */
 fw_status fw_debug_spinless_launches(fw_ctx *ctx, uint64_t *n);
 
+/* Whole ring tiles: a ring tile of a spin-less launch every slot of which holds a particle that was in the ring
+ * before the launch and lives through it issues all of its loads first and never waits for a store.  *tiles = the ring tiles so far that
+ * the host's evaluation of the kernel's predicate (fw_fifo_tile_whole) called whole, in launches that allow the arm (every ring of a type
+ * whose scale and colours are left to its readers, new particles not materialised); *launches = the launches with at least one.
+ * The kernels that run two to eight frames in one launch take the arm for exactly these tiles; a launch of one frame counts its whole
+ * tiles too and keeps the streaming loop for them (measured: the arm loses there).
+ * FW_WHOLE_TILES=0 (with FW_ENABLE_KNOBS) keeps every tile on the streaming loop: both stay 0.  Either pointer may be null */
+fw_status fw_debug_whole_tiles(fw_ctx *ctx, uint64_t *launches, uint64_t *tiles);
+
 /* Several frames of unread FIFO rings in one launch (rounds 22 to 24).  *fused = launches so far that ran one or more
  * withheld frames and the frame after them in one pass over the planes; *flushed = withheld frames that went to the stream alone,
  * because the next frame did not qualify, the pair was declined, or somebody touched the stream or the particles first.  A frame is
