@@ -361,6 +361,7 @@ SYMBOLS = [
     ("fw_debug_spin_launches", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("fw_debug_spinless_launches", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("fw_debug_whole_tiles", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    ("fw_debug_newborn_spin", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("fw_debug_fuse2", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("fw_debug_fuse_frames", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("fw_debug_aabb_batch", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
@@ -369,7 +370,7 @@ SYMBOLS = [
 ]
 
 # entry points added after round 4 (ABI 5 + a measurement hook): absent from the older builds the A/B tools load through FW_LIB_PATH
-NEWER_THAN_R04 = {"fw_debug_nest_frames", "fw_debug_param_bar", "fw_debug_tile_scratch", "fw_debug_recovered_rings", "fw_debug_tf_frames", "fw_debug_age_launches", "fw_debug_spin_launches", "fw_debug_spinless_launches", "fw_debug_whole_tiles", "fw_debug_fuse2", "fw_debug_fuse_frames", "fw_debug_aabb_batch", "fw_ctx_aabbs", "fw_ctx_aabbs_device", "fw_ctx_set_parent_velocities", "fw_ctx_set_modifiers", "fw_ctx_queue"}
+NEWER_THAN_R04 = {"fw_debug_nest_frames", "fw_debug_param_bar", "fw_debug_tile_scratch", "fw_debug_recovered_rings", "fw_debug_tf_frames", "fw_debug_age_launches", "fw_debug_spin_launches", "fw_debug_spinless_launches", "fw_debug_whole_tiles", "fw_debug_newborn_spin", "fw_debug_fuse2", "fw_debug_fuse_frames", "fw_debug_aabb_batch", "fw_ctx_aabbs", "fw_ctx_aabbs_device", "fw_ctx_set_parent_velocities", "fw_ctx_set_modifiers", "fw_ctx_queue"}
 _lib = None
 
 

@@ -488,7 +488,8 @@ __device__ __forceinline__ void fw_integrate_store(const FwType &T, const float 
                                                    float4 q2, float4 q3, float age_new, const FwOutWin &W, uint32_t o,
                                                    float4 *rec = nullptr, const fw_v3 *cpos = nullptr,
                                                    const fw_v3 *cvel = nullptr, float *box = nullptr,
-                                                   bool box_on = false, bool full = false, bool use_c = true, int wmode = FW_W_REGS) {
+                                                   bool box_on = false, bool full = false, bool use_c = true, int wmode = FW_W_REGS,
+                                                   bool spin = true) {
     if (T.flags & FW_TYPE_NOSPIN) q2 = make_float4(T.const_rot[0], T.const_rot[1], T.const_rot[2], T.const_rot[3]);
     const float lifetime = q3.w;
     // scale and colours (core.rs:601-605, 652-655).  A FW_TYPE_DERIVED type stores none of them: unless this launch writes an
@@ -523,9 +524,15 @@ __device__ __forceinline__ void fw_integrate_store(const FwType &T, const float 
     // components carry no negative zero, fw_engine_build.cpp -- and neither plane is stored: nothing to evaluate; workgroup-uniform)
     fw_q4 nr{q2.x, q2.y, q2.z, q2.w};
     float wx = 0.0f, wy = 0.0f, wz = 0.0f;
+    // (`spin` false -- workgroup-uniform, the spawning workgroups of a launch that defers the spin of its newborns, fw_spin.h: rotation and
+    // angular velocity are stored as they came, the step is owed to the ring's log)
     if (!(T.flags & FW_TYPE_NOSPIN)) {
-        const FwSpin sp = fw_spin_step(T, dt, q2, q3);
-        nr = sp.rot, wx = sp.wx, wy = sp.wy, wz = sp.wz;
+        if (spin) {
+            const FwSpin sp = fw_spin_step(T, dt, q2, q3);
+            nr = sp.rot, wx = sp.wx, wy = sp.wy, wz = sp.wz;
+        } else {
+            wx = q3.x, wy = q3.y, wz = q3.z;
+        }
     }
     const uint32_t b16 = (o - W.first) * 16u;  // < 16 KiB + a tile: the window starts at the tile's first output slot
     const uint32_t b4 = (o - W.first) * 4u;

@@ -843,6 +843,11 @@ struct fw_ctx {
     // FW_WHOLE_TILES=0: every tile keeps the streaming loop (A/B in one build).  whole_launches / whole_tiles: fw_debug_whole_tiles
     bool use_whole_tiles = true;
     uint64_t whole_launches = 0, whole_tiles = 0;
+    // The particles a deferring launch spawns into the ring owe their spin to the log too (fw_spin_newborn_deferred, fw_spin.h; round 27):
+    // the spawning workgroups run no spin step, the cohort points at the frame's own log entry.  FW_NEWBORN_SPIN=1: the eager rule of
+    // rounds 19 to 26, in the host's pointer and the kernel's flag together (A/B in one build).  newborn_launches: fw_debug_newborn_spin
+    bool newborn_spin = false;
+    uint64_t newborn_launches = 0;
     // Up to fuse_depth frames of unread rings in one launch (fw_fuse2.h).  A frame whose only GPU work would be one spin-less
     // FIFO launch of rings that all deferred their spin in it -- each with at least fuse2_min live particles (FW_FUSE2_MIN: its own knob, the
     // default of spin_defer_min) -- is WITHHELD: all of its bookkeeping done, the complete launch kept here instead of enqueued.  The next
@@ -867,7 +872,7 @@ struct fw_ctx {
         uint32_t tiles = 0, n_ops = 0;
         int nt = 0;          // the non-temporal form the LAST withheld frame's launch would have taken
         uint64_t frame[FW_FUSE_MAX] = {};  // fw_ctx::frame of each withheld frame (what its cohorts carry)
-        uint64_t spin_from[FW_FIFO_PER_LAUNCH] = {};  // per ring: what a cohort of the last withheld frame carries as its spin pointer
+        uint64_t spin_from[FW_FIFO_PER_LAUNCH] = {};  // per ring: what a cohort of the last withheld frame carries as its spin pointer (the eager rule's, group_launched)
     } pend;
     // fw_debug_fuse2: launches that ran two or more frames / withheld frames enqueued alone; fw_debug_fuse_frames: frames run by fused launches
     uint64_t fused_launches = 0, fuse2_flushed = 0, fuse_frames = 0;

@@ -210,6 +210,7 @@ fw_status fw_ctx_create(int device, uint32_t seed, void *stream, fw_ctx **out) {
     if (const char *m = getenv("FW_SPIN_LOG")) ctx->spin_log_cap = (uint32_t)strtoul(m, nullptr, 10);
     if (const char *m = getenv("FW_SPINLESS")) ctx->use_spinless = atoi(m) != 0;
     if (const char *m = getenv("FW_WHOLE_TILES")) ctx->use_whole_tiles = atoi(m) != 0;
+    if (const char *m = getenv("FW_NEWBORN_SPIN")) ctx->newborn_spin = atoi(m) != 0;
     if (const char *m = getenv("FW_FUSE2")) ctx->use_fuse2 = atoi(m) != 0;
     if (const char *m = getenv("FW_FUSE2_MIN")) ctx->fuse2_min = (uint32_t)strtoul(m, nullptr, 10);
     if (const char *m = getenv("FW_FUSE_DEPTH")) ctx->fuse_depth = (uint32_t)std::min(std::max(atoi(m), 2), (int)FW_FUSE_MAX);
@@ -1174,6 +1175,12 @@ fw_status fw_debug_whole_tiles(fw_ctx *ctx, uint64_t *launches, uint64_t *tiles)
     if (!ctx) return FW_EINVAL;
     if (launches) *launches = ctx->whole_launches;
     if (tiles) *tiles = ctx->whole_tiles;
+    return FW_OK;
+}
+// FIFO launches so far whose spawning workgroups deferred the spin of the particles they spawned (fw_spin_newborn_deferred, fw_spin.h)
+fw_status fw_debug_newborn_spin(fw_ctx *ctx, uint64_t *launches) {
+    if (!ctx || !launches) return FW_EINVAL;
+    *launches = ctx->newborn_launches;
     return FW_OK;
 }
 // FIFO launches so far that ran two or more frames in one pass (fw_ctx::pend, FwFifoArgs::fused) / withheld frames that went to the stream alone

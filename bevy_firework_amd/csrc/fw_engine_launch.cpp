@@ -454,13 +454,15 @@ bool fuse_join(fw_ctx *ctx, FwFifoArgs &fa, FwInlineOps &fio, uint32_t n_ops, ui
     return true;
 }
 
-// the cohorts the withheld frames of a group spawned got every later frame's spin from the launch: their pointer is the last frame's
-// cohort's (`spin_from`, per ring of the launch); the rings' latest launch ran `depth` frames
+// the rings' latest launch ran `depth` frames.  The cohorts the withheld frames of a group spawned keep the pointer of their birth frame:
+// the launch spun none of them, every frame of the group from their own on is in the log (fw_spin_newborn_deferred, fw_spin.h; every
+// ring of a group defers and spawns for itself).  Under the eager rule alone (FW_NEWBORN_SPIN=1) the launch gave them every later
+// frame's spin as well: their pointer is the last frame's cohort's (`spin_from`, per ring of the launch)
 void group_launched(fw_ctx *ctx, const FwFifoArgs &fa, const uint64_t *frames, uint32_t n_withheld, const uint64_t *spin_from, uint32_t depth) {
     for (uint32_t j = 0; j < fa.n_segs; j++) {
         if (fa.s[j].seg >= ctx->segs.size()) continue;
         SegHost &S = ctx->segs[fa.s[j].seg];
-        for (auto c = S.coh.rbegin(); n_withheld && c != S.coh.rend() && c->frame >= frames[0]; ++c)
+        for (auto c = S.coh.rbegin(); ctx->newborn_spin && n_withheld && c != S.coh.rend() && c->frame >= frames[0]; ++c)
             for (uint32_t f = 0; f < n_withheld; f++)
                 if (c->frame == frames[f]) c->spin_from = spin_from[j];
         S.fuse_last = depth;
@@ -483,6 +485,17 @@ void count_whole_tiles(fw_ctx *ctx, const FwFifoArgs &fa) {
     ctx->whole_tiles += n, ctx->whole_launches += n ? 1u : 0u;
 }
 
+// fw_debug_newborn_spin: a launch that is about to go to the stream in which some ring's spawning workgroups defer the spin of what they
+// spawn -- the kernel's own condition (fw_update_fifo_body: nb_defer), from the kernel's own arguments
+void count_newborn(fw_ctx *ctx, const FwFifoArgs &fa) {
+    bool any = false;
+    for (uint32_t j = 0; j < fa.n_segs; j++) {
+        const FwFifoSeg &F = fa.s[j];
+        any |= fa.q0pl != 0u && fa.fuse_pad[FW_FIFO_NEWBORN] != 0u && (F.type_idx & FW_TYPE_IDX_NOSPIN) != 0u && (F.type_idx & FW_TYPE_IDX_AXIS) != 0u && F.mat == 0u;
+    }
+    ctx->newborn_launches += any ? 1u : 0u;
+}
+
 }  // namespace
 
 namespace fwh {
@@ -496,13 +509,13 @@ fw_status flush_withheld(fw_ctx *ctx) {
     if (P.depth >= 2u) {
         ctx->fused_launches++, ctx->fuse_frames += P.depth;
         group_launched(ctx, P.fa, P.frame, P.depth - 1u, P.spin_from, P.depth);
-        count_whole_tiles(ctx, P.fa);
+        count_whole_tiles(ctx, P.fa), count_newborn(ctx, P.fa);
         FW_HIP(ctx, fw_launch_update_fifo(ctx->stream, ctx->g, P.fa, P.fio, P.tiles, P.nt, nullptr, nullptr, &P.fz));
         return FW_OK;
     }
     ctx->fuse2_flushed++;
     group_launched(ctx, P.fa, P.frame, 0u, P.spin_from, 0u);
-    count_whole_tiles(ctx, P.fa);
+    count_whole_tiles(ctx, P.fa), count_newborn(ctx, P.fa);
     FW_HIP(ctx, fw_launch_update_fifo(ctx->stream, ctx->g, P.fa, P.fio, P.tiles, P.nt, nullptr, nullptr));
     return FW_OK;
 }
@@ -570,6 +583,9 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
         fa.spinless = (ctx->use_spinless && f_nospin && fa.q0pl && !fa.any_inst && !fa.small_tiles) ? 1u : 0u;
         // (... and its whole ring tiles owe nothing but position, age and velocity: the arm without a divergent lane, fw_fifo_tile_whole)
         fa.fuse_pad[FW_FIFO_WHOLE] = (ctx->use_whole_tiles && fa.spinless && f_derived && fa.write_mask == 0) ? 1u : 0u;
+        // (... and whose spawning workgroups leave the spin of what they spawn into a deferring ring to its log: fw_spin_newborn_deferred)
+        // (one rule for the whole context: a fused launch, every ring of which defers under it, takes the set of kernels the word names)
+        fa.fuse_pad[FW_FIFO_NEWBORN] = ctx->newborn_spin ? 0u : 1u;
         const int nt = f_bytes > ctx->nt_bytes ? 2 : f_bytes > ctx->nt_wo_bytes ? 1 : 0;
         // the frame's one launch, spin-less, every ring unread and large: it may wait for the next frame, or take the waiting one in
         const bool candidate = fw_fuse2_candidate(ctx->use_fuse2, quiet, n_launches == 0 && fa.n_segs == ctx->n_fifo, fa.spinless != 0u, f_fusable);
@@ -590,7 +606,7 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
                 P.on = false;
                 group_launched(ctx, fa, P.frame, P.depth, f_spin_from, depth);
                 ctx->fused_launches++, ctx->fuse_frames += depth;
-                count_whole_tiles(ctx, fa);
+                count_whole_tiles(ctx, fa), count_newborn(ctx, fa);
                 FW_HIP(ctx, fw_launch_update_fifo(fstream, ctx->g, fa, fio, f_tiles, nt, nullptr, nullptr, &fz));
             } else {  // withheld too: the group so far is the fused launch, kept (what flush_withheld enqueues)
                 fa.host_counts = nullptr;
@@ -615,7 +631,7 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
             for (uint32_t j = 0; j < fa.n_segs; j++) ctx->segs[fa.s[j].seg].fuse_last = 0u;
             hipEvent_t e0, e1;
             next_timing_pair(ctx, fr, &e0, &e1);
-            count_whole_tiles(ctx, fa);
+            count_whole_tiles(ctx, fa), count_newborn(ctx, fa);
             FW_HIP(ctx, fw_launch_update_fifo(fstream, ctx->g, fa, fio, f_tiles, nt, e0, e1));
         }
         if (side) ctx->side_dirty = true;
@@ -671,9 +687,15 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
             } else if (fw_spin_full(S.spin.log.size(), std::max(1u, ctx->spin_log_cap)) && (st = ensure_spin(ctx, si, fstream, true))) {
                 return st;  // (the log at its cap: replayed, and the ring goes on deferring)
             }
-            const uint64_t spin_from_new = spin_defer ? S.spin.defer(S.coh, dt) : S.spin.end();
+            // (what this frame spawns into a deferring ring defers its spin too, its cohort points at the frame's own log entry: unless
+            // somebody else writes the ring's new particles, or the eager rule is asked for -- fw_spin_newborn_deferred, which the kernel's
+            // flag follows as well: FwFifoArgs::fuse_pad[FW_FIFO_NEWBORN] with the ring's type_idx and FwFifoSeg::mat, below)
+            const bool newborn_defer = fw_spin_newborn_deferred(spin_defer, !mat, ctx->newborn_spin);
+            const uint64_t spin_from_new = spin_defer ? S.spin.defer_spawn(S.coh, dt, newborn_defer) : S.spin.end();
             S.spin_last = spin_defer;
-            f_fusable &= spin_defer && n_in >= ctx->fuse2_min;
+            // (a fused launch's kernels hold the rule as a fact of their code: a ring that defers its spin and not its newborns' -- none exists
+            // today, `mat` is false wherever spin_ok holds -- would not be fused)
+            f_fusable &= spin_defer && n_in >= ctx->fuse2_min && (newborn_defer || ctx->newborn_spin);
             f_deep &= n_in >= ctx->fuse_deep_min;
             f_wide &= n_in >= ctx->fuse_wide_min;
             f_spin_from[fa.n_segs] = spin_from_new;

@@ -229,7 +229,8 @@ __device__ __forceinline__ void fw_fifo_nest_parents(const FwGlobals &g, const F
 // SPINLESS: no ring tile of the launch touches rotation or angular velocity (FwFifoArgs::spinless: every ring carries FW_TYPE_IDX_NOSPIN in
 // this launch -- a type that cannot turn, or a spin this launch defers).  The FIFO twin of ALLNOSPIN in fw_k_update_range: what the other
 // forms find out per workgroup is a fact of the instantiation, so a tile reserves no register for Q2 / Q3 -- 88 VGPRs instead of 110, a
-// fifth workgroup per CU.  The spawning workgroups keep the type's true record: a new particle gets its one update whole.
+// fifth workgroup per CU.  The spawning workgroups keep the type's true record: a new particle gets its one update whole -- but for the
+// spin, where the launch defers its newborns' too (round 27: nb_defer, below).
 // FUSE: 0, or the launch runs FUSE = 2 .. FW_FUSE_MAX frames of every ring in one pass (FwFifoArgs::fused; the host withheld all but the last:
 // fw_fuse2.h; `fz`: their dt and boundaries, FwFuseArgs -- the fused kernels' fourth argument, null for everybody else).
 // A particle of a FIFO ring never moves, so frame n + 1 of a slot needs nothing but frame n of the same slot: a ring tile loads position and
@@ -237,7 +238,10 @@ __device__ __forceinline__ void fw_fifo_nest_parents(const FwGlobals &g, const F
 // every frame's new particles -- a withheld frame's get their first update and the withheld ones behind it whole in registers, then the
 // store path with the last dt.  The depth is a fact of the instantiation: the loops over the withheld frames unroll, and the depth-2 form
 // is round 22's code with its arguments read from `fz`.  Spin-less launches only.
-template <bool INST, int WM, int NT, int COLL, int TR, bool NEST, bool Q0PL = false, bool SPINLESS = false, int FUSE = 0>
+// NBFACT: every spawning workgroup of the launch defers the spin of what it spawns (round 27: nb_defer, below) -- a fact of the code in the
+// fused forms the product launches (fw_k_update_fifo2), which then hold no spin step at all; false: a fused form spins what it spawns
+// (fw_k_update_fifo2_eager, the parent's lines), an unfused form finds out per workgroup.
+template <bool INST, int WM, int NT, int COLL, int TR, bool NEST, bool Q0PL = false, bool SPINLESS = false, int FUSE = 0, bool NBFACT = false>
 __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl, const FwFuseArgs *fz = nullptr) {
     constexpr int BLK = FW_BLOCK;
     constexpr int NW = BLK / 64;
@@ -396,13 +400,27 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
     // (round 19: a ring whose spin this launch defers -- FW_TYPE_IDX_NOSPIN together with an axis, fw_device.h -- is a ring that cannot
     // turn to the tiles of the particles that were here before: nothing of Q2 / Q3 loaded above, and with the flag in the workgroup's
     // copy of the type record neither the window nor fw_integrate_store evaluates or stores any of it.  The spawning workgroups keep the
-    // true record: a new particle gets its one update whole, every plane stored.  Workgroup-uniform, a scalar OR -- compiled into the
+    // true record: a new particle has every plane stored (its spin step: nb_defer, below).  Workgroup-uniform, a scalar OR -- compiled into the
     // launches of rings with Q0 in planes alone, the only ones the rule is ever set for (it asks for the age rule): the colliding, the
     // instance-writing float4 and the Nested instantiations keep the parent's code, which the branch cost the Nested one 4.7 % of its time.)
     // (SPINLESS: the same OR for every ring tile of the launch, and a fact of the code -- the tiles' copy of the record and of the window, below)
     if constexpr (Q0PL && !SPINLESS) {
         if (!spawner && nospin && axis != 0u) T.flags |= FW_TYPE_NOSPIN;
     }
+    // (round 27: ... and the particles the launch SPAWNS into such a ring owe their spin to the same log -- fw_spin_newborn_deferred, fw_spin.h:
+    // the spawning workgroups run no fw_spin_step, neither for the withheld frames of a fused launch nor for the last one, and store the
+    // spawn-time rotation and angular velocity in every plane; the host points the cohort at this frame's own log entry.  The axis rule
+    // proved the spawn-time values of the other two components +0, which is what the eager update leaves there: the replay, which reloads
+    // the axis' component and w alone, finds the planes it assumes.  Workgroup-uniform, from the kernel arguments alone; 0 in the pad word:
+    // FW_NEWBORN_SPIN=1, the eager rule of rounds 19 to 26.  Read at run time by the UNFUSED forms of rings with Q0 in planes alone, the only
+    // ones the deferral is ever set for.  (F.mat is 0 wherever the host defers today -- the age rule, which the deferral asks for, refuses a
+    // materialised ring --: tested all the same, it is the condition's own clause and costs a scalar compare.)
+    // A FUSED launch needs no flag: the host fuses a frame only where every ring of it defers its spin, under one rule for the whole
+    // context (launch_fifo: f_fusable), so the word decides the KERNEL -- NBFACT, fw_k_update_fifo2: the deferral a fact of the code, no
+    // spin step in it; fw_k_update_fifo2_eager: the eager rule a fact of the code, the parent's lines.)
+    static_assert(!NBFACT || (SPINLESS && FUSE != 0), "the newborns' deferral as a fact of the code: the fused forms");
+    bool nb_defer = NBFACT;
+    if constexpr (Q0PL && FUSE == 0) nb_defer = spawner && a.fuse_pad[FW_FIFO_NEWBORN] != 0u && (F.type_idx & FW_TYPE_IDX_NOSPIN) != 0u && axis != 0u && F.mat == 0u;
     const FwCollArm CA = fw_coll_arm<COLL>(g, F.type_idx & FW_TYPE_IDX_MASK);
     bool bad = false;
     if (whole) {
@@ -477,9 +495,11 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
         }
         if constexpr (FUSE != 0) {
             // a particle of a WITHHELD frame f of the group (k < spawn_end[f]: spawned by frame f or an earlier one): the update of frame f
-            // whole, with that frame's dt, in registers -- translation, spin, age: what the spawning workgroup of the withheld launch
-            // would have stored, and what the launches behind it would have made of it -- and then, below, the last frame's update
-            // through the store path everybody takes (the host gives its cohort the last frame's spin with it: launch_fifo)
+            // whole, with that frame's dt, in registers -- translation, age, and the spin unless the launch defers its newborns' (nb_defer:
+            // the cohort then keeps the pointer of its birth frame and the log owes it every frame of the group): what the spawning
+            // workgroup of the withheld launch would have stored, and what the launches behind it would have made of it -- and then,
+            // below, the last frame's update through the store path everybody takes (the eager rule: the host gives the cohort the last
+            // frame's pointer with it, group_launched)
 #pragma unroll
             for (int f = 0; f < FUSE - 1; f++) {
                 const float dt_f = fz->dt_pre[f];
@@ -487,7 +507,7 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
                     float age_a;
                     bad |= !fw_survives(so.q0.w, dt_f, so.q3.w, &age_a);  // (the host fuses no group in which a newborn dies)
                     const FwMove mv = fw_move_step(T, dt_f, so.q0, so.q1);
-                    if (!(T.flags & FW_TYPE_NOSPIN)) {
+                    if (!nb_defer && !(T.flags & FW_TYPE_NOSPIN)) {
                         const FwSpin sp = fw_spin_step(T, dt_f, so.q2, so.q3);
                         so.q2 = make_float4(sp.rot.x, sp.rot.y, sp.rot.z, sp.rot.w);
                         so.q3.x = sp.wx, so.q3.y = sp.wy, so.q3.z = sp.wz;
@@ -508,7 +528,7 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
         fw_coll_step<COLL>(g, CA, alive, a.dt, so.q0, so.q1, &cpos, &cvel);
         if (alive) {
             fw_integrate_store<true, -1, NT, true>(T, s_keys, a.dt, so.q0, so.q1, so.q2, so.q3, age_new, W, s, rec, COLL ? &cpos : nullptr,
-                                         COLL ? &cvel : nullptr, nullptr, false, true, CA.on);
+                                         COLL ? &cvel : nullptr, nullptr, false, true, CA.on, FW_W_REGS, !nb_defer);
             if (F.n_lplanes) fw_init_last_emitted(g, g.segs[F.seg], buf, s, new_ei, so.q3.w);  // (a type other particles' entries emit from)
         } else if (is_new && want_destroyed)  // born and destroyed in the same frame (dt >= lifetime)
             fw_store_destroyed(F.destroyed, buf, C, s, false, T, s_keys, so.q0, so.q1, so.q2, so.q3, age_new, i);
@@ -687,9 +707,15 @@ void fw_k_update_fifo(FwGlobals g, FwFifoArgs a, FwInlineOps inl) {
 // argument of these kernels alone).  A kernel of its own, like the Nested one, instantiated in a unit of its own (fw_k_rings_fuse2.hip):
 // the plain instantiations keep their names, their code, their register budget and their place in this unit's code object.  At most 96
 // VGPRs, five waves, no scratch, nothing pinned (profiles/r23/resource_usage.txt)
+// (round 27: these are the forms of a launch ALL of whose spawning workgroups defer the spin of what they spawn -- NBFACT, what the product
+// launches; fw_k_update_fifo2_eager, instantiated in fw_k_rings_fuse2_eager.hip, spins what it spawns, as the parent did: FW_NEWBORN_SPIN=1)
 template <int D, int WM, int NT>
 __global__ __launch_bounds__(FW_BLOCK) __attribute__((amdgpu_waves_per_eu(FW_FIFO_WAVES))) void fw_k_update_fifo2(FwGlobals g, FwFifoArgs a, FwInlineOps inl, FwFuseArgs fz) {
-    fw_update_fifo_body<false, WM, NT, 0, FW_ROUNDS, false, true, true, D>(g, a, inl, &fz);
+    fw_update_fifo_body<false, WM, NT, 0, FW_ROUNDS, false, true, true, D, true>(g, a, inl, &fz);
+}
+template <int D, int WM, int NT>
+__global__ __launch_bounds__(FW_BLOCK) __attribute__((amdgpu_waves_per_eu(FW_FIFO_WAVES))) void fw_k_update_fifo2_eager(FwGlobals g, FwFifoArgs a, FwInlineOps inl, FwFuseArgs fz) {
+    fw_update_fifo_body<false, WM, NT, 0, FW_ROUNDS, false, true, true, D, false>(g, a, inl, &fz);
 }
 // ... with Nested entries inside the launch (FwFifoNest).  A kernel of its own so that the plain instantiations keep their code
 // and their register budget; pinned at 4 waves per SIMD (the nest phase took the four-round form to 133 VGPRs: the bulk of such

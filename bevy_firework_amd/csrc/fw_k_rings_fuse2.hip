@@ -5,27 +5,42 @@
 // One instantiation per depth, never a run-time depth: with the loops over FwFuseArgs left rolled the compiler indexes the by-value
 // argument record dynamically and copies it to private memory -- 141 VGPRs, 1928 B of scratch per lane, three waves (round 24).  Every
 // depth is launched: the default groups close at fw_ctx::fuse_depth, and a reader may flush a group of any depth from 2 to 7.
+// (round 27: two sets of them.  This unit holds fw_k_update_fifo2, the forms in which "the spawning workgroups run no spin step" is a fact
+// of the code -- FwFifoArgs::fuse_pad[FW_FIFO_NEWBORN] != 0, what the product launches; fw_k_rings_fuse2_eager.hip compiles the same
+// lines with FW_FUSE2_EAGER into fw_k_update_fifo2_eager, the forms that spin what they spawn: the word is 0, FW_NEWBORN_SPIN=1.)
+#ifndef FW_RINGS_TEMPLATES_ONLY
 #define FW_RINGS_TEMPLATES_ONLY
+#endif
 #include "fw_k_rings.hip"
+#ifdef FW_FUSE2_EAGER
+#define FW_FUSE2_KERNEL fw_k_update_fifo2_eager
+#define FW_FUSE2_LAUNCH fw_launch_update_fifo2_eager
+#else
+#define FW_FUSE2_KERNEL fw_k_update_fifo2
+#define FW_FUSE2_LAUNCH fw_launch_update_fifo2
+#endif
 
 // (the forms of the spin-less launch: fully and write-only non-temporal, write mask 0 and generic)
 template <int D>
 static hipError_t fw_launch_fifo2_depth(hipStream_t s, const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl, const FwFuseArgs &fz, dim3 grid,
                                         dim3 block, int nt, hipEvent_t e0, hipEvent_t e1) {
     if (nt == 2)
-        FW_LAUNCH_T((fw_k_update_fifo2<D, -1, 2>), grid, block, s, e0, e1, g, a, inl, fz);
+        FW_LAUNCH_T((FW_FUSE2_KERNEL<D, -1, 2>), grid, block, s, e0, e1, g, a, inl, fz);
     else if (nt)
-        FW_LAUNCH_T((fw_k_update_fifo2<D, -1, 1>), grid, block, s, e0, e1, g, a, inl, fz);
+        FW_LAUNCH_T((FW_FUSE2_KERNEL<D, -1, 1>), grid, block, s, e0, e1, g, a, inl, fz);
     else if (a.write_mask == 0)
-        FW_LAUNCH_T((fw_k_update_fifo2<D, 0, 0>), grid, block, s, e0, e1, g, a, inl, fz);
+        FW_LAUNCH_T((FW_FUSE2_KERNEL<D, 0, 0>), grid, block, s, e0, e1, g, a, inl, fz);
     else
-        FW_LAUNCH_T((fw_k_update_fifo2<D, -1, 0>), grid, block, s, e0, e1, g, a, inl, fz);
+        FW_LAUNCH_T((FW_FUSE2_KERNEL<D, -1, 0>), grid, block, s, e0, e1, g, a, inl, fz);
     return hipGetLastError();
 }
 
-hipError_t fw_launch_update_fifo2(hipStream_t s, const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl, const FwFuseArgs &fz,
-                                  uint32_t total_tiles, int nt, hipEvent_t e0, hipEvent_t e1) {
+hipError_t FW_FUSE2_LAUNCH(hipStream_t s, const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl, const FwFuseArgs &fz,
+                           uint32_t total_tiles, int nt, hipEvent_t e0, hipEvent_t e1) {
     if (!total_tiles || !a.n_segs || !a.spinless || !a.q0pl || a.any_inst || a.small_tiles) return hipErrorInvalidValue;
+#ifndef FW_FUSE2_EAGER
+    if (a.fuse_pad[FW_FIFO_NEWBORN] == 0u) return fw_launch_update_fifo2_eager(s, g, a, inl, fz, total_tiles, nt, e0, e1);
+#endif
     const dim3 grid(total_tiles), block(FW_BLOCK);
     static_assert(FW_FUSE_MAX == 8, "one instantiation per depth");
     switch (a.fused) {

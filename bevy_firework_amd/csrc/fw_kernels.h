@@ -267,9 +267,14 @@ struct FwFifoArgs {
     // (round 26: word FW_FIFO_WHOLE of them is 1 in a spin-less launch whose whole ring tiles may take the arm without a divergent lane --
     // fw_update_fifo_body, fw_fifo_tile_whole: fw_ctx::use_whole_tiles, and every ring of the launch is of a FW_TYPE_DERIVED type, the fact
     // write_mask == 0 travels with -- and 0 everywhere else; the fused forms alone look at it.  No argument moves.)
+    // (round 27: word FW_FIFO_NEWBORN is 1 in a launch whose spawning workgroups defer the spin of the particles they spawn into every
+    // ring whose spin the launch defers -- FW_TYPE_IDX_NOSPIN with an axis, not FwFifoSeg::mat: fw_spin_newborn_deferred, fw_spin.h -- and
+    // 0 under FW_NEWBORN_SPIN=1.  The unfused forms for rings with Q0 in planes read it in their spawning workgroups; for a fused launch,
+    // every ring of which defers, the launcher picks the set of kernels by it: fw_k_update_fifo2 or fw_k_update_fifo2_eager.)
     uint32_t fuse_pad[31];
 };
 #define FW_FIFO_WHOLE 0
+#define FW_FIFO_NEWBORN 1
 static_assert((sizeof(FwGlobals) + sizeof(FwFifoArgs)) % 64 == 0, "FwInlineOps starts on a 64-byte line of the kernel arguments");
 static_assert(sizeof(FwFifoArgs) == 1440, "the size every form of the FIFO kernel was measured with (profiles/r22/fuse2_ab.txt)");
 // What a fused launch of depth D = FwFifoArgs::fused knows beside FwFifoArgs (round 23): the FOURTH argument of the fused kernels, behind
@@ -394,6 +399,9 @@ hipError_t fw_launch_update(hipStream_t s, const FwGlobals &g, const FwUpdateArg
 // which wants `fz` for such a launch and for no other)
 hipError_t fw_launch_update_fifo2(hipStream_t s, const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl, const FwFuseArgs &fz,
                                   uint32_t total_tiles, int nt, hipEvent_t e0, hipEvent_t e1);
+// (... and its forms whose spawning workgroups find out whether they spin what they spawn: fw_k_rings_fuse2_eager.hip, round 27)
+hipError_t fw_launch_update_fifo2_eager(hipStream_t s, const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl, const FwFuseArgs &fz,
+                                        uint32_t total_tiles, int nt, hipEvent_t e0, hipEvent_t e1);
 hipError_t fw_launch_update_fifo(hipStream_t s, const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl,
                                  uint32_t total_tiles, int nt, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, const FwFuseArgs *fz = nullptr);
 uint32_t fw_range_young_tile(void);  // ring slots a YOUNG workgroup of fw_k_update_range covers (a build-time choice)

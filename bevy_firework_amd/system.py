@@ -582,6 +582,13 @@ class ParticleSystem:
         self._check(self._lib.fw_debug_whole_tiles(self._ctx, C.byref(launches), C.byref(tiles)))
         return int(launches.value), int(tiles.value)
 
+    def newborn_spin_launches(self) -> int:
+        """FIFO launches so far whose spawning workgroups deferred the spin of the particles they spawned into a ring that defers its
+        spin: the replay applies the frame's own log entry to them"""
+        n = C.c_uint64()
+        self._check(self._lib.fw_debug_newborn_spin(self._ctx, C.byref(n)))
+        return int(n.value)
+
     def fuse2_launches(self):
         """(fused, flushed): FIFO launches so far that ran two frames of unread rings in one pass, and withheld frames that went to the
         stream alone"""

@@ -88,6 +88,14 @@ fw_status fw_debug_spinless_launches(fw_ctx *ctx, uint64_t *n);
  * FW_WHOLE_TILES=0 (with FW_ENABLE_KNOBS) keeps every tile on the streaming loop: both stay 0.  Either pointer may be null */
 fw_status fw_debug_whole_tiles(fw_ctx *ctx, uint64_t *launches, uint64_t *tiles);
 
+/* The spin of newborn particles: a launch that defers a ring's spin defers it for the particles it spawns into
+ * that ring as well -- its spawning workgroups store the spawn-time rotation and angular velocity, and the replay applies the frame's own
+ * log entry to them.  *launches = the launches so far, of one frame or of several, that went to the stream with at least one ring under
+ * the rule.  A ring of a type that cannot turn, a ring that does not defer and a ring whose new particles are materialised by another
+ * kernel are not under it.  FW_NEWBORN_SPIN=1 (with FW_ENABLE_KNOBS) restores the eager rule -- a new particle gets its first update's
+ * spin from the launch -- everywhere: 0 then */
+fw_status fw_debug_newborn_spin(fw_ctx *ctx, uint64_t *launches);
+
 /* Several frames of unread FIFO rings in one launch (rounds 22 to 24).  *fused = launches so far that ran one or more
  * withheld frames and the frame after them in one pass over the planes; *flushed = withheld frames that went to the stream alone,
  * because the next frame did not qualify, the pair was declined, or somebody touched the stream or the particles first.  A frame is
