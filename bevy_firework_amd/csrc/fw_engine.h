@@ -52,6 +52,7 @@
 #include "fw_ages.h"
 #include "fw_spin.h"
 #include "fw_fuse2.h"
+#include "fw_withheld.h"
 #include "fw_sort.h"
 #include "fw_boxes.h"
 
@@ -491,7 +492,7 @@ struct alignas(64) SegHost {
     FwSpinBook spin;
     uint32_t spin_streak = 0;
     bool spin_last = false;
-    uint32_t fuse_last = 0;  // the frames of the ring the latest launch ran in one pass, 2 .. FW_FUSE_MAX, or 0: one, unfused (fw_ctx::pend): fw_debug_update_path
+    uint32_t fuse_last = 0;  // the frames of the ring the latest launch ran in one pass, 2 .. FW_FUSE_MAX, or 0: one, unfused (fw_ctx::withheld): fw_debug_update_path
     bool q0pl = false;  // the ring keeps Q0 (position, age) as four component planes (FwSeg::cpl bit 2): set where the ring is built
     // A ring in a spawner WITH Nested entries: in frames that run the Nested pass its new particles are materialised in
     // the ring before the update (fw_k_spawn / fw_k_nest address it through the head) and fw_k_update_fifo gives them
@@ -852,28 +853,17 @@ struct fw_ctx {
     // FIFO launch of rings that all deferred their spin in it -- each with at least fuse2_min live particles (FW_FUSE2_MIN: its own knob, the
     // default of spin_defer_min) -- is WITHHELD: all of its bookkeeping done, the complete launch kept here instead of enqueued.  The next
     // fw_step's launch takes it in when it qualifies too and the group passes the rule (fw_fuse_push): it runs the group -- or, while the
-    // group is short of its depth, is withheld with it: `pend` is the GROUP so far, the fused launch of its frames.  The depth is two
+    // group is short of its depth, is withheld with it: `withheld` holds the GROUP so far, the fused launch of its frames.  The depth is two
     // frames; min(fuse_depth, FW_FUSE_NARROW) where every ring of the launch holds fuse_deep_min live particles (FW_FUSE_DEEP_MIN); and
     // fuse_depth (FW_FUSE_DEPTH, 2 .. FW_FUSE_MAX) where every ring holds fuse_wide_min as well (FW_FUSE_WIDE_MIN, round 24): a deeper group
     // pays where the pass over the planes dominates the launch.  (No depth above four has been measured between 768 tiles and the
     // headline's 983 333 particles: fuse_wide_min reuses fuse_deep_min's figure for want of another.)  Anything else that touches the
-    // stream or particle state enqueues the group first (flush_withheld): one frame exactly as built, two to seven as ONE fused launch.
+    // stream or particle state enqueues the group first (flush_withheld): one frame exactly as built, two to FW_FUSE_MAX - 1 as ONE fused launch.
     // FW_FUSE2=0: nothing is withheld.
     bool use_fuse2 = true;
     uint32_t fuse2_min = 384u * FW_TILE;
     uint32_t fuse_depth = FW_FUSE_MAX, fuse_deep_min = 768u * FW_TILE, fuse_wide_min = 768u * FW_TILE;
-    struct PendingFifo {
-        bool on = false;
-        uint32_t depth = 0;  // withheld frames: 1 .. FW_FUSE_MAX - 1 (up to seven)
-        FwFifoArgs fa;       // depth 1: the frame's launch as built; deeper: the fused launch of the group so far (fa.fused = depth, fa.dt the last frame's)
-        FwInlineOps fio;
-        FwFuseArgs fz;       // ... and its fourth argument: the dt and boundaries of frames 0 .. depth - 2
-        FwFuseGroup grp[FW_FIFO_PER_LAUNCH];  // per ring of the launch: the fused frame and every frame's share (fw_fuse2.h)
-        uint32_t tiles = 0, n_ops = 0;
-        int nt = 0;          // the non-temporal form the LAST withheld frame's launch would have taken
-        uint64_t frame[FW_FUSE_MAX] = {};  // fw_ctx::frame of each withheld frame (what its cohorts carry)
-        uint64_t spin_from[FW_FIFO_PER_LAUNCH] = {};  // per ring: what a cohort of the last withheld frame carries as its spin pointer (the eager rule's, group_launched)
-    } pend;
+    FwWithheld withheld;  // (fw_withheld.h: the group and its transitions; launch_fifo offers, flush_withheld takes, drop_withheld drops)
     // fw_debug_fuse2: launches that ran two or more frames / withheld frames enqueued alone; fw_debug_fuse_frames: frames run by fused launches
     uint64_t fused_launches = 0, fuse2_flushed = 0, fuse_frames = 0;
     bool use_axis = true;      // FW_AXIS_SPIN=0: no ring runs under the axis-spin rule (A/B in one build)
@@ -1226,7 +1216,7 @@ inline fw_status Fence::mark(fw_ctx *ctx, hipStream_t stream) {
 }
 
 fw_status sync(fw_ctx *ctx);  // (fw_engine_mem.cpp)
-// the withheld frames (fw_ctx::pend) go to the stream -- one exactly as built, two or three as one fused launch --: before anything else that
+// the withheld frames (fw_ctx::withheld) go to the stream -- one exactly as built, two to FW_FUSE_MAX - 1 as one fused launch --: before anything else that
 // touches the stream or particle state
 fw_status flush_withheld(fw_ctx *ctx);  // (fw_engine_launch.cpp)
 // ... or is dropped with the particles it would have updated (the spawner is rebuilt, the context destroyed)

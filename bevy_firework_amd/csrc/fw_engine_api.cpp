@@ -77,7 +77,7 @@ static bool begin_call(fw_ctx *ctx, fw_spawner h, SpawnerCall &r, Then then, Age
     if (!r.sp || !args_ok(*r.sp)) return r.st = FW_EINVAL, false;
     if (poll_device_error(ctx), r.sp->poisoned) return r.st = poisoned_status(ctx), false;
     hipSetDevice(ctx->device);
-    if ((r.st = flush_withheld(ctx))) return false;  // (a withheld frame goes to the stream before anybody looks: fw_ctx::pend)
+    if ((r.st = flush_withheld(ctx))) return false;  // (a withheld frame goes to the stream before anybody looks: fw_ctx::withheld)
     for (size_t t = 0; ages != Ages::leave && t < r.sp->seg.size(); t++)
         if ((ages == Ages::write && (r.st = ensure_spin(ctx, r.sp->seg[t]))) || (r.st = ensure_ages(ctx, r.sp->seg[t]))) return false;
     r.st = then == Then::sync ? sync(ctx) : then == Then::join ? join_side(ctx) : then == Then::counts ? read_counts(ctx, r.c) : FW_OK;
@@ -278,7 +278,7 @@ fw_status fw_ctx_synchronize(fw_ctx *ctx) {
 fw_status fw_ctx_set_colliders(fw_ctx *ctx, const fw_collider *colliders, uint32_t n) {
     if (!ctx || (n && !colliders)) return fail(ctx, FW_EINVAL, "bad collider set");
     hipSetDevice(ctx->device);
-    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::pend)
+    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::withheld)
     for (uint32_t i = 0; i < n; i++)
         if (colliders[i].kind < FW_COLLIDER_PLANE || colliders[i].kind > FW_COLLIDER_CAPSULE)
             return fail(ctx, FW_EINVAL, "unknown collider kind");
@@ -322,7 +322,7 @@ fw_status fw_ctx_set_colliders(fw_ctx *ctx, const fw_collider *colliders, uint32
 fw_status fw_spawner_create(fw_ctx *ctx, const fw_spawner_desc *desc, fw_spawner *out) {
     if (!ctx || !out) return FW_EINVAL;
     hipSetDevice(ctx->device);
-    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::pend)
+    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::withheld)
     fw_status st = validate_desc(ctx, desc);
     if (st) return st;
     if ((st = sync(ctx))) return st;
@@ -352,7 +352,7 @@ fw_status fw_spawner_update_settings(fw_ctx *ctx, fw_spawner h, const fw_spawner
     SpawnerHost *sp = get_spawner(ctx, h);
     if (!sp) return FW_EINVAL;
     hipSetDevice(ctx->device);
-    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::pend)
+    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::withheld)
     fw_status st = validate_desc(ctx, desc);
     if (st) return st;
     if ((st = sync(ctx))) return st;
@@ -397,7 +397,7 @@ fw_status fw_spawner_destroy(fw_ctx *ctx, fw_spawner h) {
     SpawnerHost *sp = get_spawner(ctx, h);
     if (!sp) return FW_EINVAL;
     hipSetDevice(ctx->device);
-    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::pend)
+    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::withheld)
     fw_status st = sync(ctx);
     if (st) return st;
     if (sp->poisoned && (st = clear_poison_report(ctx))) return st;
@@ -856,7 +856,7 @@ static fw_status boxes_enqueue(fw_ctx *ctx, uint32_t n, const fw_spawner *handle
     if (n > FW_BOX_MAX_CHUNKS || ne > 0xFFFFFFFFull) return fail(ctx, FW_EINVAL, std::string(who) + ": more places than one batch holds");
     hipSetDevice(ctx->device);
     fw_status st;
-    if ((st = flush_withheld(ctx))) return st;  // (fw_ctx::pend)
+    if ((st = flush_withheld(ctx))) return st;  // (fw_ctx::withheld)
     bool side = false;  // a listed segment is a FIFO ring or a small type: its launches may run on the ring stream
     for (uint32_t i = 0; i < n; i++)
         for (uint32_t si : ctx->spawners[(size_t)handles[i]].seg) {
@@ -935,7 +935,7 @@ fw_status fw_ctx_aabbs_device(fw_ctx *ctx, uint32_t n, const fw_spawner *handles
 fw_status fw_ctx_live_count(fw_ctx *ctx, uint64_t *out) {
     if (!ctx || !out) return FW_EINVAL;
     hipSetDevice(ctx->device);
-    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::pend)
+    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::withheld)
     std::vector<uint32_t> c;
     fw_status st = read_counts(ctx, c);
     if (st && st != FW_ECAPACITY) return st;
@@ -949,7 +949,7 @@ fw_status fw_ctx_live_count(fw_ctx *ctx, uint64_t *out) {
 fw_status fw_ctx_live_count_device(fw_ctx *ctx, void *d_out_u64) {
     if (!ctx || !d_out_u64) return FW_EINVAL;
     hipSetDevice(ctx->device);
-    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::pend)
+    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::withheld)
     fw_status jst = join_side(ctx);  // the counts of ring segments are written by the side stream's launches
     if (jst) return jst;
     FW_HIP(ctx, fw_launch_total(ctx->stream, count_slot(ctx), (uint32_t)ctx->segs.size(), (unsigned long long *)d_out_u64));
@@ -959,7 +959,7 @@ fw_status fw_ctx_live_count_device(fw_ctx *ctx, void *d_out_u64) {
 fw_status fw_ctx_live_count_ring(fw_ctx *ctx, void *d_ring_u64, uint32_t n_slots) {
     if (!ctx || (d_ring_u64 && n_slots < 2)) return FW_EINVAL;
     hipSetDevice(ctx->device);
-    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::pend)
+    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::withheld)
     fw_status st = sync(ctx);
     if (!st && d_ring_u64) FW_HIP(ctx, hipDeviceSynchronize());  // (the caller's zero-fill of the ring, on whatever stream)
     if (st) return st;
@@ -973,7 +973,7 @@ fw_status fw_ctx_live_count_ring(fw_ctx *ctx, void *d_ring_u64, uint32_t n_slots
 fw_status fw_ctx_last_step_updated(fw_ctx *ctx, uint64_t *out) {
     if (!ctx || !out) return FW_EINVAL;
     hipSetDevice(ctx->device);
-    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::pend)
+    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::withheld)
     fw_status st = sync(ctx);
     if (st) return st;
     return read_stat_total(ctx, out);
@@ -982,7 +982,7 @@ fw_status fw_ctx_last_step_updated(fw_ctx *ctx, uint64_t *out) {
 fw_status fw_ctx_kernel_timing(fw_ctx *ctx, int32_t enable) {
     if (!ctx) return FW_EINVAL;
     hipSetDevice(ctx->device);
-    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::pend)
+    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::withheld)
     fw_status st = sync(ctx);
     if (st) return st;
     if (enable && ctx->tev.empty()) {
@@ -1015,7 +1015,7 @@ fw_status fw_ctx_kernel_timing(fw_ctx *ctx, int32_t enable) {
 fw_status fw_ctx_kernel_timing_read(fw_ctx *ctx, double *ms_total, uint64_t *launches, uint64_t *particles) {
     if (!ctx) return FW_EINVAL;
     hipSetDevice(ctx->device);
-    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::pend)
+    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::withheld)
     fw_status st = sync(ctx);
     if (st) return st;
     double ms = 0;
@@ -1183,7 +1183,7 @@ fw_status fw_debug_newborn_spin(fw_ctx *ctx, uint64_t *launches) {
     *launches = ctx->newborn_launches;
     return FW_OK;
 }
-// FIFO launches so far that ran two or more frames in one pass (fw_ctx::pend, FwFifoArgs::fused) / withheld frames that went to the stream alone
+// FIFO launches so far that ran two or more frames in one pass (fw_ctx::withheld, FwFifoArgs::fused) / withheld frames that went to the stream alone
 fw_status fw_debug_fuse2(fw_ctx *ctx, uint64_t *fused, uint64_t *flushed) {
     if (!ctx) return FW_EINVAL;
     if (fused) *fused = ctx->fused_launches;
@@ -1227,7 +1227,7 @@ fw_status fw_ctx_kernel_timing_overhead(fw_ctx *ctx, double *ms_per_pair) {
 fw_status fw_ctx_measure_copy_bandwidth(fw_ctx *ctx, uint64_t bytes, int32_t iters, double *bytes_per_s) {
     if (!ctx || !bytes_per_s || bytes < 4096 || iters < 1) return FW_EINVAL;
     hipSetDevice(ctx->device);
-    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::pend)
+    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::withheld)
     bytes &= ~(uint64_t)0xFFF;
     HipBuf<char> a, b;
     fw_status st = alloc_buf(ctx, a, bytes);

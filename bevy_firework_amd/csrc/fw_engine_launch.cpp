@@ -410,62 +410,19 @@ fw_status take_report(fw_ctx *ctx, uint32_t si, Cohort &c, const char *what) {
     return FW_OK;
 }
 
-// Several frames in one launch (fw_ctx::pend, fw_fuse2.h): B -- the launch `fa` / `fio` this frame has just built, complete -- joins the
-// group of withheld frames when every ring of B is the ring of the group at the same place, every ring's group takes B's frame in
-// (fw_fuse_push: the pair rule between the fused frame so far and B) and the ops of all frames fit (FW_INLINE_OPS = 8: one ring with one
-// op per frame reaches FW_FUSE_MAX frames, a launch that carries two ops per frame closes its groups at four).  The fused launch is B's
-// with the group's head, live count and input row in front; the group's ops first, in frame order, B's behind them (rel_base shifted by
-// the new particles in front of them); `fz`: the withheld frames' dt and boundaries.  false: declined, nothing changed.
-bool fuse_join(fw_ctx *ctx, FwFifoArgs &fa, FwInlineOps &fio, uint32_t n_ops, uint32_t *tiles, FwFuseArgs &fz, FwFuseGroup *grp) {
-    const fw_ctx::PendingFifo &P = ctx->pend;
-    if (P.depth < 1u || P.depth >= FW_FUSE_MAX) return false;
-    if (P.fa.n_segs != fa.n_segs || P.n_ops + n_ops > FW_INLINE_OPS || P.fa.write_mask != fa.write_mask) return false;
-    for (uint32_t j = 0; j < fa.n_segs; j++) {
-        const FwFifoSeg &A = P.fa.s[j], &B = fa.s[j];
-        if (A.buf != B.buf || A.seg != B.seg || A.capacity != B.capacity || A.type_idx != B.type_idx || A.keys_off != B.keys_off ||
-            A.keys_len != B.keys_len || A.life != B.life || A.mat || B.mat || A.destroyed || B.destroyed || A.nest || B.nest)
-            return false;
-        grp[j] = P.grp[j];
-        if (!fw_fuse_push(B.capacity, grp[j], FwFifoFrame{B.head, B.n_in, B.n_spawn, B.dead})) return false;
-    }
-    const uint32_t d = P.depth;  // (withheld frames: B is frame d of the group)
-    fz = P.fz;
-    fz.dt_pre[d - 1u] = P.fa.dt;
-    FwInlineOps ops;
-    uint32_t n = 0, t = 0;
-    for (uint32_t j = 0; j < fa.n_segs; j++) {
-        const FwFifoSeg &A = P.fa.s[j];
-        FwFifoSeg &F = fa.s[j];
-        const FwFifoFrame &U = grp[j].U;
-        const uint32_t o0 = n;
-        for (uint32_t x = A.op0; x < A.op1; x++) ops.ops[n++] = P.fio.ops[x];
-        for (uint32_t x = F.op0; x < F.op1; x++) ops.ops[n] = fio.ops[x], ops.ops[n++].rel_base += grp[j].spawn_end[d - 1u];
-        const FwFifoLayout L = fw_fifo_layout(F.capacity, FW_TILE, FW_BLOCK, U.head, U.dead, U.n_in, U.n_in, U.n_spawn);
-        F.head = U.head, F.n_in = U.n_in, F.n_spawn = U.n_spawn, F.dead = U.dead;
-        fz.spawn_end[j][d - 1u] = grp[j].spawn_end[d - 1u], fz.dead[j][d - 1u] = grp[j].dead[d - 1u];
-        F.op0 = o0, F.op1 = n;
-        F.spawn_a = L.spawn_a, F.n_vt_a = L.n_vt_a, F.n_vt_b = L.n_vt_b, F.tile0 = L.tile0, F.n_tiles = L.n_tiles;
-        F.tile_first = t;
-        t += F.n_tiles;
-    }
-    fio = ops;
-    fa.parity = P.fa.parity, fa.fused = d + 1u;
-    *tiles = t;
-    return true;
-}
-
-// the rings' latest launch ran `depth` frames.  The cohorts the withheld frames of a group spawned keep the pointer of their birth frame:
-// the launch spun none of them, every frame of the group from their own on is in the log (fw_spin_newborn_deferred, fw_spin.h; every
-// ring of a group defers and spawns for itself).  Under the eager rule alone (FW_NEWBORN_SPIN=1) the launch gave them every later
-// frame's spin as well: their pointer is the last frame's cohort's (`spin_from`, per ring of the launch)
-void group_launched(fw_ctx *ctx, const FwFifoArgs &fa, const uint64_t *frames, uint32_t n_withheld, const uint64_t *spin_from, uint32_t depth) {
-    for (uint32_t j = 0; j < fa.n_segs; j++) {
-        if (fa.s[j].seg >= ctx->segs.size()) continue;
-        SegHost &S = ctx->segs[fa.s[j].seg];
-        for (auto c = S.coh.rbegin(); ctx->newborn_spin && n_withheld && c != S.coh.rend() && c->frame >= frames[0]; ++c)
+// the rings' latest launch ran L.depth frames.  The cohorts the withheld frames of a group spawned -- every frame of the launch but the last
+// -- keep the pointer of their birth frame: the launch spun none of them, every frame of the group from their own on is in the log
+// (fw_spin_newborn_deferred, fw_spin.h; every ring of a group defers and spawns for itself).  Under the eager rule alone (FW_NEWBORN_SPIN=1)
+// the launch gave them every later frame's spin as well: their pointer is the last frame's cohort's (L.spin_from, per ring of the launch)
+void group_launched(fw_ctx *ctx, const FwFifoLaunch &L) {
+    const uint32_t n_withheld = L.depth - 1u;
+    for (uint32_t j = 0; j < L.fa.n_segs; j++) {
+        if (L.fa.s[j].seg >= ctx->segs.size()) continue;
+        SegHost &S = ctx->segs[L.fa.s[j].seg];
+        for (auto c = S.coh.rbegin(); ctx->newborn_spin && n_withheld && c != S.coh.rend() && c->frame >= L.frame[0]; ++c)
             for (uint32_t f = 0; f < n_withheld; f++)
-                if (c->frame == frames[f]) c->spin_from = spin_from[j];
-        S.fuse_last = depth;
+                if (c->frame == L.frame[f]) c->spin_from = L.spin_from[j];
+        S.fuse_last = L.depth >= 2u ? L.depth : 0u;
     }
 }
 
@@ -496,37 +453,273 @@ void count_newborn(fw_ctx *ctx, const FwFifoArgs &fa) {
     ctx->newborn_launches += any ? 1u : 0u;
 }
 
+// A FIFO launch goes to the stream -- a frame's own, a group closed by its last frame, the group somebody who reads asked for: everything
+// that happens then.  fw_debug_fuse2: launches that ran two or more frames / withheld frames that went alone
+fw_status enqueue_fifo(fw_ctx *ctx, const FwFifoLaunch &L, hipStream_t stream, hipEvent_t e0, hipEvent_t e1) {
+    const bool fused = L.depth >= 2u;
+    group_launched(ctx, L);
+    if (fused) ctx->fused_launches++, ctx->fuse_frames += L.depth;
+    else if (L.held) ctx->fuse2_flushed++;
+    count_whole_tiles(ctx, L.fa), count_newborn(ctx, L.fa);
+    FW_HIP(ctx, fw_launch_update_fifo(stream, ctx->g, L.fa, L.fio, L.tiles, L.nt, e0, e1, fused ? &L.fz : nullptr));
+    return FW_OK;
+}
+
 }  // namespace
 
 namespace fwh {
 
-// the group so far goes to the stream: one withheld frame exactly as it was built (the unfused launch), two to seven as ONE fused launch
-// of that depth -- whoever reads first pays one launch
+// (a group only ever waits behind quiet frames, whose launches go to the main stream: launch_fifo)
 fw_status flush_withheld(fw_ctx *ctx) {
-    fw_ctx::PendingFifo &P = ctx->pend;
-    if (!P.on) return FW_OK;
-    P.on = false;
-    if (P.depth >= 2u) {
-        ctx->fused_launches++, ctx->fuse_frames += P.depth;
-        group_launched(ctx, P.fa, P.frame, P.depth - 1u, P.spin_from, P.depth);
-        count_whole_tiles(ctx, P.fa), count_newborn(ctx, P.fa);
-        FW_HIP(ctx, fw_launch_update_fifo(ctx->stream, ctx->g, P.fa, P.fio, P.tiles, P.nt, nullptr, nullptr, &P.fz));
-        return FW_OK;
-    }
-    ctx->fuse2_flushed++;
-    group_launched(ctx, P.fa, P.frame, 0u, P.spin_from, 0u);
-    count_whole_tiles(ctx, P.fa), count_newborn(ctx, P.fa);
-    FW_HIP(ctx, fw_launch_update_fifo(ctx->stream, ctx->g, P.fa, P.fio, P.tiles, P.nt, nullptr, nullptr));
-    return FW_OK;
+    const FwFifoLaunch *L = ctx->withheld.take();
+    return L ? enqueue_fifo(ctx, *L, ctx->stream, nullptr, nullptr) : FW_OK;
 }
 
-void drop_withheld(fw_ctx *ctx) { ctx->pend.on = false; }
+void drop_withheld(fw_ctx *ctx) { ctx->withheld.drop(); }
 
 }  // namespace fwh
 
 namespace {
 
 // ---- FIFO segments: in place, everything they need in the kernel arguments (fw_kernels.h: FwFifoSeg)
+
+// what the ring launches of one frame share: their stream and their tile grid
+struct FifoFrame {
+    hipStream_t stream;
+    // (with a colliding ring in the context every FIFO launch of it runs the COLL instantiation, whose workgroups cover one
+    // round -- FW_FIFO_COLL_TILE slots -- each: the tile grid of all of them follows)
+    // ... and so do the launches of a context whose rings hold too few particles to fill the chip with four-round workgroups
+    // (the reference's own stress_test: 157k particles = 154 of them on 256 CUs, each lane working through four particles one
+    // after the other): below FW_FIFO_SMALL four-round tiles in all, one round per workgroup.  Not with a ring whose count
+    // only the device knows (its grid covers its capacity: four times the idle workgroups).
+    // (counted in the first pass over the segments of this frame; a ring that changed its kind since then: next frame)
+    bool small, coll_real;
+    bool coll;  // (the same tile grid; which instantiation runs: FwFifoArgs::any_coll / small_tiles)
+};
+
+// the launch being accumulated, ring by ring: its arguments built in place, and what every ring of it so far has in common
+struct FifoAccum {
+    FwFifoLaunch L;        // fa, fio, tiles, n_ops; spin_from: what a cohort this frame spawns carries as its spin pointer, per ring
+    uint64_t bytes = 0;    // what the launch streams, roughly: its tiles x the bytes a particle of the type moves
+    bool nospin = true;    // every ring of the launch so far carries FW_TYPE_IDX_NOSPIN in it (FwFifoArgs::spinless)
+    bool derived = true;   // ... and is of a FW_TYPE_DERIVED type (FwFifoArgs::fuse_pad[FW_FIFO_WHOLE])
+    bool fusable = true;   // several frames in one launch: every ring so far deferred its spin in it and holds fuse2_min particles
+    bool deep = true;      // ... and holds fuse_deep_min: a group of the launch may be deeper than two frames, up to FW_FUSE_NARROW
+    bool wide = true;      // ... and fuse_wide_min: up to fw_ctx::fuse_depth
+    uint32_t n_launches = 0;  // the launches of this frame so far
+    bool sent = false;     // the launch has been offered: a ring that follows starts the frame's next one (most frames have one: cleared for nobody)
+
+    void restart() {
+        const uint32_t n = n_launches;
+        *this = FifoAccum{};
+        n_launches = n;
+    }
+    // the launch-wide words, once every ring is in: FwFifoArgs::spinless and fuse_pad, L.nt; may the launch wait or take the waiting ones
+    // in, and how deep a group it may close or continue
+    struct Words {
+        bool candidate;
+        uint32_t depth_max;
+    };
+    Words derive(const fw_ctx *ctx, bool quiet) {
+        FwFifoArgs &fa = L.fa;
+        // (no ring tile of the launch touches rotation or angular velocity: the kernel form compiled for that -- rings with Q0 in planes,
+        // four-round tiles, no instance records)
+        fa.spinless = (ctx->use_spinless && nospin && fa.q0pl && !fa.any_inst && !fa.small_tiles) ? 1u : 0u;
+        // (... and its whole ring tiles owe nothing but position, age and velocity: the arm without a divergent lane, fw_fifo_tile_whole)
+        fa.fuse_pad[FW_FIFO_WHOLE] = (ctx->use_whole_tiles && fa.spinless && derived && fa.write_mask == 0) ? 1u : 0u;
+        // (... and whose spawning workgroups leave the spin of what they spawn into a deferring ring to its log: fw_spin_newborn_deferred)
+        // (one rule for the whole context: a fused launch, every ring of which defers under it, takes the set of kernels the word names)
+        fa.fuse_pad[FW_FIFO_NEWBORN] = ctx->newborn_spin ? 0u : 1u;
+        L.nt = bytes > ctx->nt_bytes ? 2 : bytes > ctx->nt_wo_bytes ? 1 : 0;
+        // the frame's one launch, spin-less, every ring unread and large: it may wait for the next frame, or take the waiting one in
+        const bool candidate = fw_fuse2_candidate(ctx->use_fuse2, quiet, n_launches == 0 && fa.n_segs == ctx->n_fifo, fa.spinless != 0u, fusable);
+        // (how deep: two frames, or fw_ctx::fuse_depth where the pass dominates the launch -- beyond FW_FUSE_NARROW only where every ring
+        // holds fuse_wide_min too)
+        const uint32_t depth_knob = std::max(2u, std::min(ctx->fuse_depth, (uint32_t)FW_FUSE_MAX));
+        return Words{candidate, !deep ? 2u : !wide ? std::min(depth_knob, (uint32_t)FW_FUSE_NARROW) : depth_knob};
+    }
+};
+
+// what a ring brings into this frame's launch
+struct RingInput {
+    bool mat_frame;    // frames that materialise (Nested pass): the segment's Global particles of this frame already sit in the ring
+    bool mat;
+    uint32_t n_spawn;  // spawned by fw_k_update_fifo itself
+    uint32_t n_in;     // live particles before fw_k_update_fifo's own spawns (a type that receives children: only the device knows)
+};
+RingInput ring_input(const SegHost &S, const FwFrame &fr) {
+    RingInput in;
+    in.mat_frame = S.fifo_mat && fr.nested_frame && !S.virt_parent;
+    in.mat = S.fifo_dev || in.mat_frame;
+    in.n_spawn = in.mat_frame ? 0u : S.frame_spawn;
+    in.n_in = S.fifo_dev ? 0xFFFFFFFFu : S.ub - in.n_spawn;
+    return in;
+}
+
+// the Nested entries of this frame that run inside the FIFO launch (FwFrame::fuse_plan) and emit from the ring / into it, or -1
+struct NestRole {
+    int parent = -1, child = -1;
+    bool any() const { return parent >= 0 || child >= 0; }
+};
+NestRole nest_role(const FwFrame &fr, uint32_t si) {
+    NestRole r;
+    for (uint32_t k = 0; fr.fuse && k < fr.n_fuse; k++) {
+        if (fr.fuse_plan[k].parent_seg == si) r.parent = (int)k;
+        if (fr.fuse_plan[k].child_seg == si) r.child = (int)k;
+    }
+    return r;
+}
+
+// the rules that hold for a ring in this launch; the planes of a ring that leaves a rule are made true first (ensure_ages, ensure_spin)
+struct RingRules {
+    bool ageless, spin_defer, newborn_defer;
+    uint64_t spin_from_new;  // what a cohort this frame spawns carries as its spin pointer
+};
+fw_status ring_rules(fw_ctx *ctx, uint32_t si, float dt, const FifoFrame &ff, const RingInput &in, bool nest_touches, RingRules &R) {
+    SegHost &S = ctx->segs[si];
+    fw_status st = FW_OK;
+    // the age rule (fw_device.h: FW_TYPE_IDX_AGELESS), per launch: a streaming launch -- four-round tiles, no collider, no instance
+    // records of this ring --, a ring fed by Global entries alone that no Nested entry touches, a FW_TYPE_DERIVED type that reports
+    // no destroyed particles, a dt both sides add alike.  Any other launch finds the true ages in the plane: written back first,
+    // from the cohorts as they stand BEFORE this frame's spawns and dt (what the ring holds).
+    // ("streaming" is judged by the context's own threshold, fw_ctx::fifo_small_tiles: with FW_FIFO_SMALL=0 -- no threshold, four-round
+    // tiles at any size -- nothing says the launch is bound by bandwidth, and the rule stays off)
+    R.ageless = ctx->use_ageless && S.q0pl && ctx->fifo_small_tiles != 0u && !ff.small && !ff.coll_real && S.inst == nullptr && !S.collides && !S.fifo_dev && !S.fifo_mat &&
+                !S.nested_fed && S.n_lplanes == 0 && !nest_touches && S.derived && S.destroyed == nullptr && ageless_dt_ok(dt);
+    if (!R.ageless && (st = ensure_ages(ctx, si, ff.stream))) return st;
+    if (R.ageless) S.ages_stale = true;
+    S.ageless_last = R.ageless;
+    // the deferred spin (fw_device.h: FW_TYPE_IDX_NOSPIN with FW_TYPE_IDX_AXIS; fw_spin.h), per launch: everything the age rule asks,
+    // the axis rule in force for this dt (its proof makes the replay independent of who shares a wave), a positive normal dt (no
+    // cohort then takes a later frame's spawn in: its age is above +0), a ring large enough to be bound by bandwidth -- and one
+    // that has met all of this for spin_defer_after launches in a row without anybody asking for its planes.  Any other launch
+    // finds the true spin in the planes: replayed first, under the axis the log was written for (before S.axis is cleared).
+    const bool spin_ok = R.ageless && ctx->use_spin_defer && S.axis != 0u && axis_dt_ok(S, dt) && spin_dt_ok(dt) && in.n_in >= ctx->spin_defer_min &&
+                         !(S.frame_spawn && !S.coh.empty() && S.coh.back().age == 0.0f);
+    R.spin_defer = spin_ok && S.spin_streak >= ctx->spin_defer_after;
+    if (!spin_ok) {
+        if ((st = ensure_spin(ctx, si, ff.stream))) return st;
+    } else if (!R.spin_defer) {
+        S.spin_streak++;
+    } else if (fw_spin_full(S.spin.log.size(), std::max(1u, ctx->spin_log_cap)) && (st = ensure_spin(ctx, si, ff.stream, true))) {
+        return st;  // (the log at its cap: replayed, and the ring goes on deferring)
+    }
+    // (what this frame spawns into a deferring ring defers its spin too, its cohort points at the frame's own log entry: unless
+    // somebody else writes the ring's new particles, or the eager rule is asked for -- fw_spin_newborn_deferred, which the kernel's
+    // flag follows as well: FwFifoArgs::fuse_pad[FW_FIFO_NEWBORN] with the ring's type_idx and FwFifoSeg::mat, ring_record)
+    R.newborn_defer = fw_spin_newborn_deferred(R.spin_defer, !in.mat, ctx->newborn_spin);
+    R.spin_from_new = R.spin_defer ? S.spin.defer_spawn(S.coh, dt, R.newborn_defer) : S.spin.end();
+    S.spin_last = R.spin_defer;
+    return FW_OK;
+}
+
+// the cohorts age by this dt exactly as their particles do (fp32 additions, fw_survives); the oldest die first.  *dead: how many
+fw_status age_cohorts(fw_ctx *ctx, uint32_t si, float dt, uint64_t spin_from_new, uint32_t *dead) {
+    SegHost &S = ctx->segs[si];
+    fw_status st = FW_OK;
+    if (S.fifo_dev) {
+        S.coh.push_back(SegHost::Cohort{0u, 0.0f, ctx->frame, false});  // size: whatever the device appends
+    } else if (S.frame_spawn) {
+        if (!S.coh.empty() && S.coh.back().age == 0.0f && !std::signbit(S.coh.back().age))
+            S.coh.back().n += S.frame_spawn;
+        else
+            S.coh.push_back(SegHost::Cohort{S.frame_spawn, 0.0f, ctx->frame, true, spin_from_new});
+    }
+    for (auto &c : S.coh) c.age = c.age + dt;
+    *dead = 0;
+    while (!S.coh.empty() && S.coh.front().age >= S.fifo_life) {
+        SegHost::Cohort &c = S.coh.front();
+        // (children added `lifetime` ago)
+        if (!c.known && c.frame != ctx->frame && (st = take_report(ctx, si, c, "cohort report missing"))) return st;
+        *dead += c.n;
+        S.coh.pop_front();
+    }
+    if (S.spin.stale) S.spin.trim(S.coh);  // (log entries only dead particles lacked: a particle that dies unread never has the work done)
+    return FW_OK;
+}
+
+// the ring's record in the launch -- FwFifoSeg, its ops and its workgroups --, what the ring adds to the launch-wide facts, and the ring's
+// head and bound behind the frame
+void ring_record(fw_ctx *ctx, const FifoFrame &ff, FifoAccum &acc, uint32_t si, float dt, const RingInput &in, const RingRules &R, uint32_t dead,
+                 bool nest_parent) {
+    SegHost &S = ctx->segs[si];
+    FwFifoArgs &fa = acc.L.fa;
+    const int32_t wm = S.derived ? 0 : S.fifo_wm;  // (FW_TYPE_DERIVED: none of the optional planes is stored)
+    if (!fa.n_segs) fa.write_mask = wm;
+    else if (fa.write_mask != wm) fa.write_mask = -1;
+    // (a fused launch's kernels hold the rule as a fact of their code: a ring that defers its spin and not its newborns' -- none exists
+    // today, `mat` is false wherever spin_ok holds -- would not be fused)
+    acc.fusable &= R.spin_defer && in.n_in >= ctx->fuse2_min && (R.newborn_defer || ctx->newborn_spin);
+    acc.deep &= in.n_in >= ctx->fuse_deep_min;
+    acc.wide &= in.n_in >= ctx->fuse_wide_min;
+    acc.L.spin_from[fa.n_segs] = R.spin_from_new;
+    FwFifoSeg &F = fa.s[fa.n_segs++];
+    F.buf = S.buf[0], F.destroyed = S.destroyed, F.inst = S.inst;
+    F.inst_cap = S.inst_cap, F.capacity = S.capacity, F.seg = si;
+    // (the axis-spin rule travels per launch: a frame whose dt voids its proof runs without it, and so does every frame after it)
+    if (S.axis != 0u && !axis_dt_ok(S, dt)) S.axis = 0u;
+    F.type_idx = S.type_idx | ((S.nospin || R.spin_defer) ? FW_TYPE_IDX_NOSPIN : 0u) | (S.axis << FW_TYPE_IDX_AXIS_SHIFT) | (R.ageless ? FW_TYPE_IDX_AGELESS : 0u), F.life = S.fifo_life;
+    F.keys_off = S.keys_off, F.keys_len = S.keys_len;
+    F.head = S.head, F.n_in = in.n_in, F.n_spawn = in.n_spawn, F.dead = dead;
+    F.mat = in.mat ? 1u : 0u;
+    fa.q0pl = S.q0pl ? 1u : 0u;  // (the same for every ring of a launch: the two passes)
+    acc.nospin &= (F.type_idx & FW_TYPE_IDX_NOSPIN) != 0u;
+    acc.derived &= S.derived;
+    F.n_lplanes = S.n_lplanes;
+    F.report = S.fifo_dev ? S.h_report + (ctx->frame % kReportRing) : nullptr;
+    F.op0 = acc.L.n_ops;
+    if (!in.mat_frame)
+        for (const FwOp &op : ctx->fifo_ops)
+            if (op.seg == si) acc.L.fio.ops[acc.L.n_ops++] = op;
+    F.op1 = acc.L.n_ops;
+    // workgroups: the new particles first, FW_BLOCK each, in two groups of consecutive slots (up to the end of the
+    // buffer / from slot 0); then the ring tiles from the first slot the update touches (the first destroyed particle
+    // when their records are wanted, the first survivor otherwise) to the last old particle (a type whose count
+    // only the device knows: the whole ring, empty tiles leave at once); at least one in all (it publishes the counts)
+    const uint32_t n_old = S.fifo_dev ? S.capacity : in.n_in;
+    // (... or a ring whose particles a Nested entry of this launch emits from: the ones about to die still emit, and the
+    // tiles' ranks count from the ring's head)
+    const uint32_t lo = std::min((S.destroyed || nest_parent) ? 0u : dead, n_old);
+    const uint32_t ftile = ff.coll ? FW_FIFO_COLL_TILE : FW_TILE;
+    const FwFifoLayout L = fw_fifo_layout(S.capacity, ftile, FW_BLOCK, S.head, lo, n_old, S.fifo_dev ? 0u : in.n_in, in.n_spawn);  // (fw_fuse2.h)
+    F.spawn_a = L.spawn_a, F.n_vt_a = L.n_vt_a, F.n_vt_b = L.n_vt_b, F.tile0 = L.tile0, F.n_tiles = L.n_tiles;
+    F.tile_first = acc.L.tiles;
+    acc.L.tiles += F.n_tiles;
+    F.nest = 0u;
+    // (the estimate fw_ctx::nt_bytes / nt_wo_bytes were calibrated against in round 3 -- 104 / 164 B whatever the launch moves, two to
+    // seven times the truth by now: the thresholds and it go together, and a fused launch takes the form its last frame would have)
+    acc.bytes += (uint64_t)L.live_tiles * ftile * (S.nospin ? 104u : 164u);
+    fa.any_inst |= S.inst != nullptr ? 1u : 0u;
+    // (a launch of q0pl rings -- none of them collides -- in a context with a colliding ring: the plain one-round form on the same tile grid)
+    fa.any_coll |= (ff.coll_real && !S.q0pl) ? 1u : 0u;
+    fa.small_tiles = (ff.coll && !(ff.coll_real && !S.q0pl)) ? 1u : 0u;
+    S.head = (uint32_t)(((uint64_t)S.head + dead) % S.capacity);
+    if (!S.fifo_dev) S.ub = in.n_in + in.n_spawn - std::min(dead, in.n_in + in.n_spawn);  // exact
+}
+
+// the latest ring of the launch is the parents' or the children's ring of a Nested entry that runs inside it (FwFifoNest).
+// *status_next: look-back words handed to the Nested entries of this frame so far (FwFifoNest::status_first)
+void wire_nest(fw_ctx *ctx, const FwFrame &fr, FwFifoArgs &fa, const NestRole &nest, uint32_t nest_tag, uint32_t *status_next) {
+    FwFifoSeg &F = fa.s[fa.n_segs - 1u];
+    if (nest.parent >= 0) {
+        const FwNestOp &op = fr.fuse_plan[nest.parent];
+        FwFifoNest &N = fa.nest[nest.parent];
+        F.nest = (uint32_t)nest.parent + 1u;
+        N.parent = fa.n_segs - 1u;
+        N.emit = op.emit, N.emit_slot = op.emit_slot, N.parent_lplane = op.parent_lplane;
+        N.n_count = op.n_count, N.n_start = op.n_start, N.n_end = op.n_end, N.speed = op.speed, N.scale = op.scale;
+        N.status_first = *status_next, N.n_ptiles = F.n_tiles - (F.n_vt_a + F.n_vt_b);
+        *status_next += N.n_ptiles;
+        N.ticket_base = ctx->nest_ticket_base[op.emit_slot], ctx->nest_ticket_base[op.emit_slot] += N.n_ptiles;
+        N.tag = nest_tag, N.spin_limit = ctx->spin_limit;
+        fa.n_nest = fr.n_fuse;
+    }
+    if (nest.child >= 0) {
+        F.nest = ((uint32_t)nest.child + 1u) | FW_FIFO_NEST_CHILD;
+        fa.nest[nest.child].child = fa.n_segs - 1u;
+    }
+}
+
 fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
     const FwUpdateArgs &a = fr.a;
     const float dt = fr.dt;
@@ -540,249 +733,71 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
     for (const SegHost &S : ctx->segs) side &= !(S.in_use && S.fifo && (S.fifo_mat || S.inst != nullptr || S.collides));
     fw_status st = order_side(ctx, side, ctx->fifo_last_side);
     if (st) return st;
-    const hipStream_t fstream = side ? ctx->fifo_stream : ctx->stream;
-    FwFifoArgs fa{};
-    FwInlineOps fio;
-    // (with a colliding ring in the context every FIFO launch of it runs the COLL instantiation, whose workgroups cover one
-    // round -- FW_FIFO_COLL_TILE slots -- each: the tile grid of all of them follows)
-    // ... and so do the launches of a context whose rings hold too few particles to fill the chip with four-round workgroups
-    // (the reference's own stress_test: 157k particles = 154 of them on 256 CUs, each lane working through four particles one
-    // after the other): below FW_FIFO_SMALL four-round tiles in all, one round per workgroup.  Not with a ring whose count
-    // only the device knows (its grid covers its capacity: four times the idle workgroups).
-    // (counted in the first pass over the segments of this frame; a ring that changed its kind since then: next frame)
-    const bool fifo_small = !fr.ring_stats.fifo_dev && fr.ring_stats.fifo_parts < (uint64_t)ctx->fifo_small_tiles * FW_TILE;
-    const bool fifo_coll_real = fr.ring_stats.fifo_coll;
-    const bool fifo_coll = fifo_coll_real || fifo_small;  // (the same tile grid; which instantiation runs: FwFifoArgs::any_coll / small_tiles)
-    uint32_t f_ops = 0, f_tiles = 0;
-    uint64_t f_bytes = 0;  // what the launch streams, roughly: its tiles x the bytes a particle of the type moves
-    bool f_nospin = true;  // every ring of the launch so far carries FW_TYPE_IDX_NOSPIN in it (FwFifoArgs::spinless)
-    bool f_derived = true; // ... and is of a FW_TYPE_DERIVED type (FwFifoArgs::fuse_pad[FW_FIFO_WHOLE])
-    // several frames in one launch (fw_ctx::pend): every ring of the launch so far deferred its spin in it and holds fuse2_min particles; the
-    // launches of this frame so far; what a cohort this frame spawns carries as its spin pointer, per ring of the launch
-    bool f_fusable = true;
-    bool f_deep = true;  // ... and holds fuse_deep_min: a group of the launch may be deeper than two frames, up to FW_FUSE_NARROW
-    bool f_wide = true;  // ... and fuse_wide_min: up to fw_ctx::fuse_depth
-    uint32_t n_launches = 0;
-    uint64_t f_spin_from[FW_FIFO_PER_LAUNCH] = {};
     // (a frame whose only GPU work is this one launch: no compacting, range or small segment, no separate pass, no colour fill, nobody
     // who wants a count or a time per frame)
     const bool quiet = fr.quiet && fr.spawn_form == FW_SPAWN_NONE && !side;
     if (!quiet && (st = flush_withheld(ctx))) return st;
-    uint32_t nest_status_next = 0;  // look-back words handed to the Nested entries of this launch so far (FwFifoNest::status_first)
+    // (a group is only ever pending in a quiet frame, and a quiet frame is never `side`: a group an offer of this frame sends out goes
+    // to the main stream through ff.stream, as flush_withheld's does)
+    FifoFrame ff;
+    ff.stream = side ? ctx->fifo_stream : ctx->stream;
+    ff.small = !fr.ring_stats.fifo_dev && fr.ring_stats.fifo_parts < (uint64_t)ctx->fifo_small_tiles * FW_TILE;
+    ff.coll_real = fr.ring_stats.fifo_coll;
+    ff.coll = ff.coll_real || ff.small;
+    FifoAccum acc{};
+    FwFifoArgs &fa = acc.L.fa;
+    uint32_t nest_status_next = 0;
     const uint32_t nest_tag = fr.fuse ? next_nest_seq(ctx) : 0u;
+    // the accumulated launch is complete: offered to the withheld group, and what the offer leaves goes to the stream
     auto flush = [&]() -> fw_status {
-        if (!fa.n_segs) return FW_OK;
+        if (acc.sent || !fa.n_segs) return FW_OK;
         fa.parity = fr.p, fa.epoch = a.epoch, fa.dbg = ctx->dbg, fa.dt = dt;
         // (the pinned "frame F has started" word recycles host buffers the GENERAL launch reads: when the two launches
         // run on different streams only that one reports)
         fa.done_tag = side ? nullptr : a.done_tag, fa.done_value = a.done_value;
         fa.host_counts = a.host_counts;
         fa.live_out = a.live_out, fa.live_next = a.live_next;
-        // (no ring tile of the launch touches rotation or angular velocity: the kernel form compiled for that -- rings with Q0 in planes,
-        // four-round tiles, no instance records)
-        fa.spinless = (ctx->use_spinless && f_nospin && fa.q0pl && !fa.any_inst && !fa.small_tiles) ? 1u : 0u;
-        // (... and its whole ring tiles owe nothing but position, age and velocity: the arm without a divergent lane, fw_fifo_tile_whole)
-        fa.fuse_pad[FW_FIFO_WHOLE] = (ctx->use_whole_tiles && fa.spinless && f_derived && fa.write_mask == 0) ? 1u : 0u;
-        // (... and whose spawning workgroups leave the spin of what they spawn into a deferring ring to its log: fw_spin_newborn_deferred)
-        // (one rule for the whole context: a fused launch, every ring of which defers under it, takes the set of kernels the word names)
-        fa.fuse_pad[FW_FIFO_NEWBORN] = ctx->newborn_spin ? 0u : 1u;
-        const int nt = f_bytes > ctx->nt_bytes ? 2 : f_bytes > ctx->nt_wo_bytes ? 1 : 0;
-        // the frame's one launch, spin-less, every ring unread and large: it may wait for the next frame, or take the waiting one in
-        const bool candidate = fw_fuse2_candidate(ctx->use_fuse2, quiet, n_launches == 0 && fa.n_segs == ctx->n_fifo, fa.spinless != 0u, f_fusable);
-        n_launches++;
+        const FifoAccum::Words w = acc.derive(ctx, quiet);
+        acc.n_launches++;
         fr.fifo_launched = true;
         fw_status fst = FW_OK;
-        // (how deep a group this launch may close or continue: two frames, or fw_ctx::fuse_depth where the pass dominates the launch -- beyond
-        // FW_FUSE_NARROW only where every ring holds fuse_wide_min too)
-        const uint32_t depth_knob = std::max(2u, std::min(ctx->fuse_depth, (uint32_t)FW_FUSE_MAX));
-        const uint32_t depth_max = !f_deep ? 2u : !f_wide ? std::min(depth_knob, (uint32_t)FW_FUSE_NARROW) : depth_knob;
-        fw_ctx::PendingFifo &P = ctx->pend;
-        FwFuseArgs fz{};
-        FwFuseGroup grp[FW_FIFO_PER_LAUNCH];
-        if (P.on && candidate && P.depth < depth_max && fuse_join(ctx, fa, fio, f_ops, &f_tiles, fz, grp)) {
-            const uint32_t depth = P.depth + 1u;
-            ctx->spinless_launches++;
-            if (depth >= depth_max) {  // the frame that completes the group launches it
-                P.on = false;
-                group_launched(ctx, fa, P.frame, P.depth, f_spin_from, depth);
-                ctx->fused_launches++, ctx->fuse_frames += depth;
-                count_whole_tiles(ctx, fa), count_newborn(ctx, fa);
-                FW_HIP(ctx, fw_launch_update_fifo(fstream, ctx->g, fa, fio, f_tiles, nt, nullptr, nullptr, &fz));
-            } else {  // withheld too: the group so far is the fused launch, kept (what flush_withheld enqueues)
-                fa.host_counts = nullptr;
-                fr.snap = -1, fr.a.host_counts = nullptr;
-                P.fa = fa, P.fio = fio, P.fz = fz, P.tiles = f_tiles, P.n_ops += f_ops, P.nt = nt;
-                P.frame[P.depth] = ctx->frame, P.depth = depth;
-                for (uint32_t j = 0; j < fa.n_segs; j++) P.grp[j] = grp[j], P.spin_from[j] = f_spin_from[j];
-            }
-        } else if ((fst = flush_withheld(ctx))) {
+        const FwOffered o = ctx->withheld.offer(acc.L, w.candidate, w.depth_max, ctx->frame);
+        if (o.first && (fst = enqueue_fifo(ctx, *o.first, ff.stream, nullptr, nullptr))) {
+            ctx->withheld.drop();  // (the frame went neither to the stream nor into a group)
             return fst;
-        } else if (candidate) {
-            // withheld: the complete launch is kept.  It arms no snapshot row and reports no counts (the launch that runs the frame,
-            // fused or alone, leaves the device's counters as they must be; a row nobody fills would stay armed)
-            fa.host_counts = nullptr;
-            fr.snap = -1, fr.a.host_counts = nullptr;
-            P.fa = fa, P.fio = fio, P.fz = FwFuseArgs{}, P.tiles = f_tiles, P.n_ops = f_ops, P.nt = nt, P.frame[0] = ctx->frame, P.depth = 1u, P.on = true;
-            for (uint32_t j = 0; j < fa.n_segs; j++)
-                P.grp[j] = fw_fuse_begin(FwFifoFrame{fa.s[j].head, fa.s[j].n_in, fa.s[j].n_spawn, fa.s[j].dead}), P.spin_from[j] = f_spin_from[j];
-            ctx->spinless_launches++;
-        } else {
-            ctx->spinless_launches += fa.spinless;
-            for (uint32_t j = 0; j < fa.n_segs; j++) ctx->segs[fa.s[j].seg].fuse_last = 0u;
-            hipEvent_t e0, e1;
-            next_timing_pair(ctx, fr, &e0, &e1);
-            count_whole_tiles(ctx, fa), count_newborn(ctx, fa);
-            FW_HIP(ctx, fw_launch_update_fifo(fstream, ctx->g, fa, fio, f_tiles, nt, e0, e1));
+        }
+        ctx->spinless_launches += fa.spinless;  // (a candidate is spin-less: a withheld frame counts when it is withheld)
+        // (a withheld frame arms no snapshot row and reports no counts: FwWithheld::keep)
+        if (o.withheld) fr.snap = -1, fr.a.host_counts = nullptr;
+        if (o.second) {
+            hipEvent_t e0 = nullptr, e1 = nullptr;
+            if (o.second->depth == 1u) next_timing_pair(ctx, fr, &e0, &e1);
+            if ((fst = enqueue_fifo(ctx, *o.second, ff.stream, e0, e1))) return fst;
         }
         if (side) ctx->side_dirty = true;
-        fa = FwFifoArgs{};
-        f_ops = f_tiles = 0, f_bytes = 0, f_nospin = true, f_derived = true, f_fusable = true, f_deep = true, f_wide = true;
+        acc.sent = true;
         return FW_OK;
     };
     // (two passes: the rings that keep Q0 in planes -- SegHost::q0pl, the ones that may run under the age rule -- get a launch of their own,
     // behind everybody else's: the colliding and the Nested instantiations of the kernel never meet that layout)
     for (int pass = 0; pass < 2; pass++) {
         for (uint32_t si = 0; si < n_seg; si++) {
-            SegHost &S = ctx->segs[si];
+            const SegHost &S = ctx->segs[si];
             if (!S.in_use || !S.fifo || S.q0pl != (pass == 1)) continue;
             uint32_t k_ops = 0;
             for (const FwOp &op : ctx->fifo_ops) k_ops += op.seg == si ? 1u : 0u;
             if (k_ops > FW_INLINE_OPS)  // (build_spawner never makes such a type a ring)
                 return poison_segment(ctx, si, "a FIFO ring with more spawn ops than its launch can carry");
-            if ((fa.n_segs == FW_FIFO_PER_LAUNCH || f_ops + k_ops > FW_INLINE_OPS) && (st = flush())) return st;
-            const int32_t wm = S.derived ? 0 : S.fifo_wm;  // (FW_TYPE_DERIVED: none of the optional planes is stored)
-            if (!fa.n_segs) fa.write_mask = wm;
-            else if (fa.write_mask != wm) fa.write_mask = -1;
-            // frames that materialise (Nested pass): the segment's Global particles of this frame already sit in the ring
-            const bool mat_frame = S.fifo_mat && fr.nested_frame && !S.virt_parent;
-            const bool mat = S.fifo_dev || mat_frame;
-            const uint32_t n_spawn = mat_frame ? 0u : S.frame_spawn;  // spawned by fw_k_update_fifo itself
-            // live particles before fw_k_update_fifo's own spawns (a type that receives children: only the device knows)
-            const uint32_t n_in = S.fifo_dev ? 0xFFFFFFFFu : S.ub - n_spawn;
-            // the age rule (fw_device.h: FW_TYPE_IDX_AGELESS), per launch: a streaming launch -- four-round tiles, no collider, no instance
-            // records of this ring --, a ring fed by Global entries alone that no Nested entry touches, a FW_TYPE_DERIVED type that reports
-            // no destroyed particles, a dt both sides add alike.  Any other launch finds the true ages in the plane: written back first,
-            // from the cohorts as they stand BEFORE this frame's spawns and dt (what the ring holds).
-            bool nest_touches = false;
-            for (uint32_t k = 0; fr.fuse && k < fr.n_fuse; k++) nest_touches |= fr.fuse_plan[k].parent_seg == si || fr.fuse_plan[k].child_seg == si;
-            // ("streaming" is judged by the context's own threshold, fw_ctx::fifo_small_tiles: with FW_FIFO_SMALL=0 -- no threshold, four-round
-            // tiles at any size -- nothing says the launch is bound by bandwidth, and the rule stays off)
-            const bool ageless = ctx->use_ageless && S.q0pl && ctx->fifo_small_tiles != 0u && !fifo_small && !fifo_coll_real && S.inst == nullptr && !S.collides && !S.fifo_dev && !S.fifo_mat &&
-                                 !S.nested_fed && S.n_lplanes == 0 && !nest_touches && S.derived && S.destroyed == nullptr && ageless_dt_ok(dt);
-            if (!ageless && (st = ensure_ages(ctx, si, fstream))) return st;
-            if (ageless) S.ages_stale = true;
-            S.ageless_last = ageless;
-            // the deferred spin (fw_device.h: FW_TYPE_IDX_NOSPIN with FW_TYPE_IDX_AXIS; fw_spin.h), per launch: everything the age rule asks,
-            // the axis rule in force for this dt (its proof makes the replay independent of who shares a wave), a positive normal dt (no
-            // cohort then takes a later frame's spawn in: its age is above +0), a ring large enough to be bound by bandwidth -- and one
-            // that has met all of this for spin_defer_after launches in a row without anybody asking for its planes.  Any other launch
-            // finds the true spin in the planes: replayed first, under the axis the log was written for (before S.axis is cleared).
-            const bool spin_ok = ageless && ctx->use_spin_defer && S.axis != 0u && axis_dt_ok(S, dt) && spin_dt_ok(dt) && n_in >= ctx->spin_defer_min &&
-                                 !(S.frame_spawn && !S.coh.empty() && S.coh.back().age == 0.0f);
-            const bool spin_defer = spin_ok && S.spin_streak >= ctx->spin_defer_after;
-            if (!spin_ok) {
-                if ((st = ensure_spin(ctx, si, fstream))) return st;
-            } else if (!spin_defer) {
-                S.spin_streak++;
-            } else if (fw_spin_full(S.spin.log.size(), std::max(1u, ctx->spin_log_cap)) && (st = ensure_spin(ctx, si, fstream, true))) {
-                return st;  // (the log at its cap: replayed, and the ring goes on deferring)
-            }
-            // (what this frame spawns into a deferring ring defers its spin too, its cohort points at the frame's own log entry: unless
-            // somebody else writes the ring's new particles, or the eager rule is asked for -- fw_spin_newborn_deferred, which the kernel's
-            // flag follows as well: FwFifoArgs::fuse_pad[FW_FIFO_NEWBORN] with the ring's type_idx and FwFifoSeg::mat, below)
-            const bool newborn_defer = fw_spin_newborn_deferred(spin_defer, !mat, ctx->newborn_spin);
-            const uint64_t spin_from_new = spin_defer ? S.spin.defer_spawn(S.coh, dt, newborn_defer) : S.spin.end();
-            S.spin_last = spin_defer;
-            // (a fused launch's kernels hold the rule as a fact of their code: a ring that defers its spin and not its newborns' -- none exists
-            // today, `mat` is false wherever spin_ok holds -- would not be fused)
-            f_fusable &= spin_defer && n_in >= ctx->fuse2_min && (newborn_defer || ctx->newborn_spin);
-            f_deep &= n_in >= ctx->fuse_deep_min;
-            f_wide &= n_in >= ctx->fuse_wide_min;
-            f_spin_from[fa.n_segs] = spin_from_new;
-            // the cohorts age by this dt exactly as their particles do (fp32 additions, fw_survives); the oldest die first
-            if (S.fifo_dev) {
-                S.coh.push_back(SegHost::Cohort{0u, 0.0f, ctx->frame, false});  // size: whatever the device appends
-            } else if (S.frame_spawn) {
-                if (!S.coh.empty() && S.coh.back().age == 0.0f && !std::signbit(S.coh.back().age))
-                    S.coh.back().n += S.frame_spawn;
-                else
-                    S.coh.push_back(SegHost::Cohort{S.frame_spawn, 0.0f, ctx->frame, true, spin_from_new});
-            }
-            for (auto &c : S.coh) c.age = c.age + dt;
+            if ((fa.n_segs == FW_FIFO_PER_LAUNCH || acc.L.n_ops + k_ops > FW_INLINE_OPS) && (st = flush())) return st;
+            if (acc.sent) acc.restart();
+            const RingInput in = ring_input(S, fr);
+            const NestRole nest = nest_role(fr, si);
+            RingRules rules;
             uint32_t dead = 0;
-            while (!S.coh.empty() && S.coh.front().age >= S.fifo_life) {
-                SegHost::Cohort &c = S.coh.front();
-                // (children added `lifetime` ago)
-                if (!c.known && c.frame != ctx->frame && (st = take_report(ctx, si, c, "cohort report missing"))) return st;
-                dead += c.n;
-                S.coh.pop_front();
-            }
-            if (S.spin.stale) S.spin.trim(S.coh);  // (log entries only dead particles lacked: a particle that dies unread never has the work done)
-            FwFifoSeg &F = fa.s[fa.n_segs++];
-            F.buf = S.buf[0], F.destroyed = S.destroyed, F.inst = S.inst;
-            F.inst_cap = S.inst_cap, F.capacity = S.capacity, F.seg = si;
-            // (the axis-spin rule travels per launch: a frame whose dt voids its proof runs without it, and so does every frame after it)
-            if (S.axis != 0u && !axis_dt_ok(S, dt)) S.axis = 0u;
-            F.type_idx = S.type_idx | ((S.nospin || spin_defer) ? FW_TYPE_IDX_NOSPIN : 0u) | (S.axis << FW_TYPE_IDX_AXIS_SHIFT) | (ageless ? FW_TYPE_IDX_AGELESS : 0u), F.life = S.fifo_life;
-            F.keys_off = S.keys_off, F.keys_len = S.keys_len;
-            F.head = S.head, F.n_in = n_in, F.n_spawn = n_spawn, F.dead = dead;
-            F.mat = mat ? 1u : 0u;
-            fa.q0pl = S.q0pl ? 1u : 0u;  // (the same for every ring of a launch: the two passes)
-            f_nospin &= (F.type_idx & FW_TYPE_IDX_NOSPIN) != 0u;
-            f_derived &= S.derived;
-            F.n_lplanes = S.n_lplanes;
-            F.report = S.fifo_dev ? S.h_report + (ctx->frame % kReportRing) : nullptr;
-            F.op0 = f_ops;
-            if (!mat_frame)
-                for (const FwOp &op : ctx->fifo_ops)
-                    if (op.seg == si) fio.ops[f_ops++] = op;
-            F.op1 = f_ops;
-            // workgroups: the new particles first, FW_BLOCK each, in two groups of consecutive slots (up to the end of the
-            // buffer / from slot 0); then the ring tiles from the first slot the update touches (the first destroyed particle
-            // when their records are wanted, the first survivor otherwise) to the last old particle (a type whose count
-            // only the device knows: the whole ring, empty tiles leave at once); at least one in all (it publishes the counts)
-            const uint32_t n_old = S.fifo_dev ? S.capacity : n_in;
-            // (... or a ring whose particles a Nested entry of this launch emits from: the ones about to die still emit, and the
-            // tiles' ranks count from the ring's head)
-            int nest_parent = -1, nest_child = -1;
-            for (uint32_t k = 0; fr.fuse && k < fr.n_fuse; k++) {
-                if (fr.fuse_plan[k].parent_seg == si) nest_parent = (int)k;
-                if (fr.fuse_plan[k].child_seg == si) nest_child = (int)k;
-            }
-            const uint32_t lo = std::min((S.destroyed || nest_parent >= 0) ? 0u : dead, n_old);
-            const uint32_t ftile = fifo_coll ? FW_FIFO_COLL_TILE : FW_TILE;
-            const FwFifoLayout L = fw_fifo_layout(S.capacity, ftile, FW_BLOCK, S.head, lo, n_old, S.fifo_dev ? 0u : n_in, n_spawn);  // (fw_fuse2.h)
-            F.spawn_a = L.spawn_a, F.n_vt_a = L.n_vt_a, F.n_vt_b = L.n_vt_b, F.tile0 = L.tile0, F.n_tiles = L.n_tiles;
-            const uint32_t live_tiles = L.live_tiles;
-            F.tile_first = f_tiles;
-            f_tiles += F.n_tiles;
-            F.nest = 0u;
-            if (nest_parent >= 0) {
-                const FwNestOp &op = fr.fuse_plan[nest_parent];
-                FwFifoNest &N = fa.nest[nest_parent];
-                F.nest = (uint32_t)nest_parent + 1u;
-                N.parent = fa.n_segs - 1u;
-                N.emit = op.emit, N.emit_slot = op.emit_slot, N.parent_lplane = op.parent_lplane;
-                N.n_count = op.n_count, N.n_start = op.n_start, N.n_end = op.n_end, N.speed = op.speed, N.scale = op.scale;
-                N.status_first = nest_status_next, N.n_ptiles = F.n_tiles - (F.n_vt_a + F.n_vt_b);
-                nest_status_next += N.n_ptiles;
-                N.ticket_base = ctx->nest_ticket_base[op.emit_slot], ctx->nest_ticket_base[op.emit_slot] += N.n_ptiles;
-                N.tag = nest_tag, N.spin_limit = ctx->spin_limit;
-                fa.n_nest = fr.n_fuse;
-            }
-            if (nest_child >= 0) {
-                F.nest = ((uint32_t)nest_child + 1u) | FW_FIFO_NEST_CHILD;
-                fa.nest[nest_child].child = fa.n_segs - 1u;
-            }
-            // (the estimate fw_ctx::nt_bytes / nt_wo_bytes were calibrated against in round 3 -- 104 / 164 B whatever the launch moves, two to
-            // seven times the truth by now: the thresholds and it go together, and a fused launch takes the form its second frame would have)
-            f_bytes += (uint64_t)live_tiles * ftile * (S.nospin ? 104u : 164u);
-            fa.any_inst |= S.inst != nullptr ? 1u : 0u;
-            // (a launch of q0pl rings -- none of them collides -- in a context with a colliding ring: the plain one-round form on the same tile grid)
-            fa.any_coll |= (fifo_coll_real && !S.q0pl) ? 1u : 0u;
-            fa.small_tiles = (fifo_coll && !(fifo_coll_real && !S.q0pl)) ? 1u : 0u;
-            S.head = (uint32_t)(((uint64_t)S.head + dead) % S.capacity);
-            if (!S.fifo_dev) S.ub = n_in + n_spawn - std::min(dead, n_in + n_spawn);  // exact
+            if ((st = ring_rules(ctx, si, dt, ff, in, nest.any(), rules))) return st;
+            if ((st = age_cohorts(ctx, si, dt, rules.spin_from_new, &dead))) return st;
+            ring_record(ctx, ff, acc, si, dt, in, rules, dead, nest.parent >= 0);
+            wire_nest(ctx, fr, fa, nest, nest_tag, &nest_status_next);
         }
         if ((st = flush())) return st;
     }
@@ -1073,7 +1088,7 @@ namespace fwh {
 fw_status enqueue_frame(fw_ctx *ctx, FwFrame &fr) {
     fr.p = ctx->parity;
     update_args(ctx, fr);
-    // a frame whose only GPU work can be one FIFO launch (fw_ctx::pend, launch_fifo): no compacting, range or small segment, no separate
+    // a frame whose only GPU work can be one FIFO launch (fw_ctx::withheld, launch_fifo): no compacting, range or small segment, no separate
     // pass, no colour fill, nobody who wants a count or a time per frame.  Any other frame puts a withheld one on the stream first.
     fr.quiet = ctx->use_fuse2 && ctx->n_fifo != 0 && ctx->n_in_use == ctx->n_fifo && !ctx->n_range && !ctx->n_small && !fr.total_tiles && !fr.legacy &&
                !fr.fuse && !ctx->colors_dirty && ctx->live_ring == nullptr && !ctx->timing;

@@ -5,7 +5,7 @@
 namespace fwh {
 
 fw_status sync(fw_ctx *ctx) {
-    if (fw_status fst = flush_withheld(ctx)) return fst;  // (what the caller waits for includes a withheld frame: fw_ctx::pend)
+    if (fw_status fst = flush_withheld(ctx)) return fst;  // (what the caller waits for includes a withheld frame: fw_ctx::withheld)
     FW_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->side_dirty) {
         FW_HIP(ctx, hipStreamSynchronize(ctx->fifo_stream));
@@ -18,7 +18,7 @@ fw_status sync(fw_ctx *ctx) {
 // before work that reads ring data is enqueued on the main stream without a synchronisation: the main stream waits for
 // the ring launches on the side stream (and the next ring launch will wait for that work)
 fw_status join_side(fw_ctx *ctx) {
-    if (fw_status fst = flush_withheld(ctx)) return fst;  // (work that reads ring data comes behind a withheld frame: fw_ctx::pend)
+    if (fw_status fst = flush_withheld(ctx)) return fst;  // (work that reads ring data comes behind a withheld frame: fw_ctx::withheld)
     if (ctx->side_dirty) {
         FW_HIP(ctx, hipEventRecord(ctx->ev_side, ctx->fifo_stream));
         FW_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_side, 0));
@@ -64,7 +64,7 @@ static fw_status replay_cohorts(fw_ctx *ctx, uint32_t si, hipStream_t stream, bo
 
 fw_status ensure_ages(fw_ctx *ctx, uint32_t si, hipStream_t stream) {
     SegHost &S = ctx->segs[si];
-    if (fw_status fst = flush_withheld(ctx)) return fst;  // (whoever asks is about to read, copy or launch over the ring: fw_ctx::pend)
+    if (fw_status fst = flush_withheld(ctx)) return fst;  // (whoever asks is about to read, copy or launch over the ring: fw_ctx::withheld)
     if (!S.ages_stale) return FW_OK;
     fw_status st = replay_cohorts<FwAgeEntry>(
         ctx, si, stream, S.fifo && !S.coh.empty(), ctx->age_tab, 0, 1024 * sizeof(FwAgeEntry),

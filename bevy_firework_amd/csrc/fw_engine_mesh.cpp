@@ -34,7 +34,7 @@ fw_status create_mesh(fw_ctx *ctx, const char *who, bool deformable, const float
     if (out) *out = -1;
     if (!ctx || !out) return fail(ctx, FW_EINVAL, std::string(who) + ": bad arguments");
     hipSetDevice(ctx->device);
-    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::pend)
+    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::withheld)
     try {
         FwBvh bvh;
         std::string why;
@@ -176,7 +176,7 @@ fw_status fw_ctx_update_mesh_vertices(fw_ctx *ctx, fw_mesh mesh, const float *xy
     if (!xyz || n_vertices != m.n_vertices) return fail(ctx, FW_EINVAL, "fw_ctx_update_mesh_vertices: the vertex count differs from the creation's");
     const size_t nf = (size_t)n_vertices * 3;
     hipSetDevice(ctx->device);
-    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::pend)
+    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::withheld)
     const bool placed = std::find(ctx->mesh_set.begin(), ctx->mesh_set.end(), mesh) != ctx->mesh_set.end();
     fw_status st;  // (the one allocation an update can need comes first: a failure leaves the mesh as it was)
     if (placed && (st = reserve_staging(ctx, (uint32_t)ctx->mesh_insts.size()))) return st;
@@ -220,7 +220,7 @@ fw_status fw_ctx_update_mesh_vertices_device(fw_ctx *ctx, fw_mesh mesh, const vo
     if (!d_xyz || n_vertices != m.n_vertices)
         return fail(ctx, FW_EINVAL, "fw_ctx_update_mesh_vertices_device: the vertex count differs from the creation's");
     hipSetDevice(ctx->device);
-    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::pend)
+    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::withheld)
     fw_status st;  // (the allocations of a mesh's first call come first: a failure leaves the mesh as it was, for both forms)
     if ((st = reserve_device_form(ctx, m))) return st;
     // Everything below is launches into the context's stream: no wait, no pass over the vertices, no copy of them.
@@ -263,7 +263,7 @@ fw_status fw_ctx_destroy_mesh(fw_ctx *ctx, fw_mesh mesh) {
     if (std::find(ctx->mesh_set.begin(), ctx->mesh_set.end(), mesh) != ctx->mesh_set.end())
         return fail(ctx, FW_EINVAL, "fw_ctx_destroy_mesh: the current instance set places this mesh");
     hipSetDevice(ctx->device);
-    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::pend)
+    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::withheld)
     fw_status st = sync(ctx);  // (frames in flight may still walk it under an older instance set)
     if (st) return st;
     ctx->meshes[mesh] = fw_ctx::MeshHost{};
@@ -275,7 +275,7 @@ fw_status fw_ctx_set_mesh_colliders(fw_ctx *ctx, const fw_mesh_collider *inst, u
     for (uint32_t i = 0; i < n; i++)
         if (!mesh_alive(ctx, inst[i].mesh)) return fail(ctx, FW_EINVAL, "fw_ctx_set_mesh_colliders: unknown mesh handle");
     hipSetDevice(ctx->device);
-    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::pend)
+    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::withheld)
     const size_t ncap = std::max<size_t>(16, (size_t)n * 2);
     fw_status st;
     try {

@@ -26,7 +26,7 @@ fw_status query_device(fw_ctx *ctx, const Launch &launch, const char *name, cons
     if (n == 0) return FW_OK;
     if (!d_in || !d_out) return fail(ctx, FW_EINVAL, std::string(name) + ": null pointer");
     hipSetDevice(ctx->device);
-    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::pend)
+    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::withheld)
     return launch_query(ctx, launch, name, d_in, n, d_out, d_out2);
 }
 
@@ -47,7 +47,7 @@ fw_status query_staged(fw_ctx *ctx, const Launch &launch, const char *name, cons
     if (n == 0) return FW_OK;
     if (!in || !out) return fail(ctx, FW_EINVAL, std::string(name) + ": null pointer");
     hipSetDevice(ctx->device);
-    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::pend)
+    if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::withheld)
     const uint64_t in_quads = in_size / sizeof(float4), out_quads = out_size / sizeof(float4), out2_quads = out2_size / sizeof(float4);
     if (out2_quads == 0) out2 = nullptr;
     fw_status st;

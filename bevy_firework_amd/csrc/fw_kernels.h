@@ -289,7 +289,7 @@ struct FwFuseArgs {
     uint32_t dead[FW_FIFO_PER_LAUNCH][FW_FUSE_MAX - 1];
 };
 // (round 24, FW_FUSE_MAX = 8: 480 bytes.  The record is the LAST argument, so its size moves nobody else's; FW_INLINE_OPS stays 8 -- FwInlineOps
-// sits in front of it -- so a launch whose rings carry two ops per frame closes its groups at four frames: fuse_join declines the fifth)
+// sits in front of it -- so a launch whose rings carry two ops per frame closes its groups at four frames: FwWithheld::join declines the fifth)
 static_assert(sizeof(FwFuseArgs) == 32 + 2 * FW_FIFO_PER_LAUNCH * (FW_FUSE_MAX - 1) * 4, "dt_pre and a pad word, then two tables of FW_FUSE_MAX - 1 words per ring");
 static_assert(sizeof(FwGlobals) + sizeof(FwFifoArgs) + sizeof(FwInlineOps) + sizeof(FwFuseArgs) <= 4096, "the fused kernels' arguments fit the 4096-byte kernel-argument limit");
 

@@ -1,6 +1,6 @@
 """The age of a FIFO-ring particle from the host's spawn cohorts without a GPU (csrc/fw_ages.h, the lookup fw_k_fifo_ages runs per lane):
 a stand-alone C++ program, compiled here with g++ -- once plainly, once with -fsanitize=address,undefined --, replays the cohorts of a
-frame sequence the way launch_fifo does (`age = age + dt` per cohort, -ffp-contract=off), lays the table out the way ensure_ages does
+frame sequence the way launch_fifo (age_cohorts) does (`age = age + dt` per cohort, -ffp-contract=off), lays the table out the way ensure_ages does
 (one entry per cohort that holds particles) and answers queries through fw_age_of; a plain Python loop of np.float32 additions over
 every single particle says what each answer must be, bit for bit."""
 import os

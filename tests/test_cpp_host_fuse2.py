@@ -1,5 +1,5 @@
 """Two frames of a FIFO ring in one launch without a GPU (csrc/fw_fuse2.h: the layout of a launch, the rule that admits a pair, the fused
-frame -- the lines launch_fifo compiles): a stand-alone C++ program, compiled here with g++ -- once plainly, once with
+frame -- the lines FwWithheld::join, csrc/fw_withheld.h, and launch_fifo compile): a stand-alone C++ program, compiled here with g++ -- once plainly, once with
 -fsanitize=address,undefined --, walks a reduced model of the kernel's grid (tiles of 4 slots, spawning workgroups of 2) slot by slot.
 For every capacity that is a multiple of the tile, every head, live count and every {spawn_A, dead_A, spawn_B, dead_B} two frames can
 carry, it asks fw_fuse2_ok; for every pair the rule admits it runs frame A and frame B as two launches and the fused frame as one, and

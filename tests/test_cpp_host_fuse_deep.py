@@ -1,5 +1,5 @@
 """Groups of three and four frames of a FIFO ring in one launch without a GPU (csrc/fw_fuse2.h: FwFuseGroup, fw_fuse_begin, fw_fuse_push --
-the lines launch_fifo compiles).  A stand-alone C++ program, compiled with g++ -Wall -Werror -- once plainly,
+the lines FwWithheld::join (csrc/fw_withheld.h) and launch_fifo compile).  A stand-alone C++ program, compiled with g++ -Wall -Werror -- once plainly,
 once with -fsanitize=address,undefined --, walks a reduced model of the kernel's grid (tiles of 4 slots, spawning workgroups of 2) slot by
 slot.  For rings of 8 to 64 slots it walks sequences of up to four frames {spawn, dead} from every head and live count -- all of them for
 the small rings, a grid of values that keeps the edges (0, 1, a tile + 1, a third, all but one, everything that fits) for the larger ones --

@@ -1,5 +1,5 @@
 """Groups of five to eight frames of a FIFO ring in one launch without a GPU (csrc/fw_fuse2.h: FwFuseGroup, fw_fuse_begin, fw_fuse_push --
-the lines launch_fifo compiles).  A stand-alone C++ program in the manner of tests/test_cpp_host_fuse_deep.py,
+the lines FwWithheld::join (csrc/fw_withheld.h) and launch_fifo compile).  A stand-alone C++ program in the manner of tests/test_cpp_host_fuse_deep.py,
 compiled with g++ -Wall -Werror -- once plainly, once with -fsanitize=address,undefined --, walks a reduced model of the kernel's grid
 (tiles of 4 slots, spawning workgroups of 2) slot by slot.  Every sequence of eight frames is too many, so: for rings of 8 and 16 slots
 each frame takes the edge values {0, 1, a tile + 1, a third, all but one, everything} for its spawns and its dead, to depth 8, from edge

@@ -1,6 +1,6 @@
 """The spin pointer of the cohort a deferring launch spawns, without a GPU (csrc/fw_spin.h: fw_spin_newborn_deferred, FwSpinBook::
 defer_spawn; round 27).  A stand-alone C++ program, compiled here with g++ -- once plainly, once with -fsanitize=address,undefined --,
-drives FwSpinBook the way launch_fifo, group_launched and ensure_spin do, over random hosts: deferring launches and stretches that end and
+drives FwSpinBook the way launch_fifo (ring_rules, age_cohorts), group_launched and ensure_spin do, over random hosts: deferring launches and stretches that end and
 begin again, frames withheld into groups of depth 1 to FW_FUSE_MAX that close by depth or are flushed early (by a reader, a launch that
 does not defer, a full log), cohorts that die and trim the log, a small log cap, frames whose ring falls back to the eager rule (somebody
 else writes its new particles), and whole hosts under the switch (FW_NEWBORN_SPIN=1).
@@ -38,7 +38,7 @@ struct Host {
     std::deque<Cohort> coh;
     unsigned frame = 0;
     bool eager = false;  // FW_NEWBORN_SPIN=1
-    // the withheld frames of the group so far (fw_ctx::pend): their numbers, and the pointer a cohort of the last one carries
+    // the withheld frames of the group so far (fw_ctx::withheld): their numbers, and the pointer a cohort of the last one carries
     unsigned held[FW_FUSE_MAX] = {}, depth = 0;
     uint64_t held_from = 0;
     unsigned long long total = 0;

@@ -1,6 +1,6 @@
 """The deferred spin of a FIFO ring without a GPU (csrc/fw_spin.h: the lookup fw_k_fifo_spin runs per lane and the log the host keeps):
 a stand-alone C++ program, compiled here with g++ -- once plainly, once with -fsanitize=address,undefined --, drives FwSpinBook through
-schedules of frames the way launch_fifo and ensure_spin do (a deferred frame logs its dt, a cohort spawned in it points behind that entry,
+schedules of frames the way launch_fifo (ring_rules, age_cohorts) and ensure_spin do (a deferred frame logs its dt, a cohort spawned in it points behind that entry,
 dead cohorts leave and the log is trimmed, a full log or a reader replays) and prints, at every replay, which log entries fw_spin_steps
 hands every single live index.  The dt of frame k is the number k, so an entry names its frame.  A brute-force Python model -- one list
 of pending frames PER PARTICLE -- says what every line must be: exactly the frames the particle lived through, and was not integrated

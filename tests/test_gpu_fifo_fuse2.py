@@ -1,4 +1,4 @@
-"""Two frames of an unread FIFO ring in one launch (fw_ctx::pend, FwFifoArgs::fused, the FUSE2 instantiations of fw_k_update_fifo;
+"""Two frames of an unread FIFO ring in one launch (fw_ctx::withheld, FwFifoArgs::fused, the FUSE2 instantiations of fw_k_update_fifo;
 csrc/fw_fuse2.h): a frame whose only GPU work is one spin-less launch of rings that all deferred their spin is
 withheld -- its bookkeeping done, its launch kept --, and the next frame's launch runs both: one load and one store per plane for two
 updates.  Whoever touches the stream or the particles first puts the kept launch on the stream as it was built.

@@ -1,4 +1,4 @@
-"""Up to four frames of an unread FIFO ring in one launch (fw_ctx::pend as a group, FwFuseArgs, the depth-3 and depth-4 instantiations of
+"""Up to four frames of an unread FIFO ring in one launch (fw_ctx::withheld as a group, FwFuseArgs, the depth-3 and depth-4 instantiations of
 fw_k_update_fifo2; csrc/fw_fuse2.h).  The cases, the two runs of each (FW_FUSE2=1 against FW_FUSE2=0, next to
 the CPU oracle) and the knobs that force the machinery at small sizes are tests/test_gpu_fifo_fuse2.py's, whose `both` and Run2 this
 file borrows; on top of them FW_FUSE_DEEP_MIN=1 (a group may be deeper than two frames at any size) and FW_FUSE_DEPTH.  Every field of

@@ -1,4 +1,4 @@
-"""Up to eight frames of an unread FIFO ring in one launch (fw_ctx::pend as a group of up to seven withheld frames, FwFuseArgs, the depth-5
+"""Up to eight frames of an unread FIFO ring in one launch (fw_ctx::withheld as a group of up to seven withheld frames, FwFuseArgs, the depth-5
 to depth-8 instantiations of fw_k_update_fifo2; csrc/fw_fuse2.h).  The cases, the two runs of each (FW_FUSE2=1
 against FW_FUSE2=0, next to the CPU oracle) and the knobs that force the machinery at small sizes are tests/test_gpu_fifo_fuse2.py's,
 whose `both` and Run2 this file borrows as tests/test_gpu_fifo_fuse_deep.py does (and that file's bookkeeping of the second counter);

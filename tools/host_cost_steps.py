@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Host-side cost of the individual fw_step calls of an unread stretch (configs[1]), split by what the call did: W -- the frame was
-withheld, bookkeeping alone (fw_ctx::pend) -- and L -- the call enqueued a launch.  Small batches between waits, as in
+withheld, bookkeeping alone (fw_ctx::withheld) -- and L -- the call enqueued a launch.  Small batches between waits, as in
 tools/host_cost.py, so the hardware queue never fills; the two debug counters are read outside the timed region.  Prints one JSON line:
 medians and means of W and L in us, the depth the launches ran at, and the projected host cost per step ((D-1) W + L) / D for D = 2 .. 8."""
 import os as _os; _os.environ.setdefault("FW_ENABLE_KNOBS", "1")  # the A/B switches are honoured only with this set
