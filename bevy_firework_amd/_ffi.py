@@ -65,6 +65,10 @@ def make_colliders(colliders):
     return arr
 
 
+class VolumePlace(C.Structure):  # fw_volume_place (VOLUME QUERIES): type -1 = every particle type of the spawner
+    _fields_ = [("spawner", C.c_int32), ("type", C.c_int32)]
+
+
 class MeshCollider(C.Structure):
     _fields_ = [("mesh", C.c_int32), ("layers", C.c_uint32), ("position", C.c_float * 3), ("rotation", C.c_float * 4)]
 
@@ -339,6 +343,8 @@ SYMBOLS = [
     ("fw_ctx_track_aabbs", C.c_int, [_P, C.c_int32]),
     ("fw_ctx_aabbs", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_int32), _P]),
     ("fw_ctx_aabbs_device", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_int32), _P]),
+    ("fw_ctx_count_in_volumes", C.c_int, [_P, C.c_uint32, _P, C.c_uint32, C.POINTER(Collider), _P]),
+    ("fw_ctx_count_in_volumes_device", C.c_int, [_P, C.c_uint32, _P, C.c_uint32, C.POINTER(Collider), _P]),
     ("fw_ctx_live_count", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("fw_ctx_live_count_device", C.c_int, [_P, _P]),
     ("fw_ctx_live_count_ring", C.c_int, [_P, _P, C.c_uint32]),
@@ -365,12 +371,13 @@ SYMBOLS = [
     ("fw_debug_fuse2", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("fw_debug_fuse_frames", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("fw_debug_aabb_batch", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32)]),
+    ("fw_debug_volume_query", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("fw_compute_emission_count", C.c_uint64,
      [C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.POINTER(C.c_float)]),
 ]
 
 # entry points added after round 4 (ABI 5 + a measurement hook): absent from the older builds the A/B tools load through FW_LIB_PATH
-NEWER_THAN_R04 = {"fw_debug_nest_frames", "fw_debug_param_bar", "fw_debug_tile_scratch", "fw_debug_recovered_rings", "fw_debug_tf_frames", "fw_debug_age_launches", "fw_debug_spin_launches", "fw_debug_spinless_launches", "fw_debug_whole_tiles", "fw_debug_newborn_spin", "fw_debug_fuse2", "fw_debug_fuse_frames", "fw_debug_aabb_batch", "fw_ctx_aabbs", "fw_ctx_aabbs_device", "fw_ctx_set_parent_velocities", "fw_ctx_set_modifiers", "fw_ctx_queue"}
+NEWER_THAN_R04 = {"fw_debug_nest_frames", "fw_debug_param_bar", "fw_debug_tile_scratch", "fw_debug_recovered_rings", "fw_debug_tf_frames", "fw_debug_age_launches", "fw_debug_spin_launches", "fw_debug_spinless_launches", "fw_debug_whole_tiles", "fw_debug_newborn_spin", "fw_debug_fuse2", "fw_debug_fuse_frames", "fw_debug_aabb_batch", "fw_ctx_aabbs", "fw_ctx_aabbs_device", "fw_debug_volume_query", "fw_ctx_count_in_volumes", "fw_ctx_count_in_volumes_device", "fw_ctx_set_parent_velocities", "fw_ctx_set_modifiers", "fw_ctx_queue"}
 _lib = None
 
 

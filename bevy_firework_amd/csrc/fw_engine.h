@@ -22,7 +22,8 @@
 //   fw_engine_step.cpp   fw_step and the plan of a frame: mode exits, lifetime windows, emission clocks, ring-op routing, the
 //                        tile table -- everything that can still be rolled back
 //   fw_engine_launch.cpp the enqueue of a planned frame (FwFrame): op tables, cohort replay, every launch, the frame's bookkeeping
-//   fw_engine_api.cpp    every other entry point of include/firework_hip.h (+ the debug hooks), the depth-sorted records among them
+//   fw_engine_api.cpp    every other entry point of include/firework_hip.h (+ the debug hooks), the depth-sorted records, the batched boxes and the
+//                        volume queries (which ask about the particles, not the collider world) among them
 //   fw_engine_mesh.cpp   the collider meshes: fw_ctx_create_mesh / fw_ctx_create_deformable_mesh / fw_ctx_update_mesh_vertices /
 //                        fw_ctx_destroy_mesh / fw_ctx_set_mesh_colliders (the
 //                        hierarchy itself is built by fw_bvh.cpp, plain C++)
@@ -55,6 +56,7 @@
 #include "fw_withheld.h"
 #include "fw_sort.h"
 #include "fw_boxes.h"
+#include "fw_volumes.h"
 
 namespace fwh {
 
@@ -1123,6 +1125,14 @@ struct fw_ctx {
         std::vector<uint32_t> place_first; // per-call scratch: the first entry of every output place
         uint64_t launches = 0, last_chunks = 0;  // fw_debug_aabb_batch
     } boxes;
+    // the volume queries (fw_ctx_count_in_volumes[_device]; fw_volumes.h): their tables and volume records travel through boxes.h_tab /
+    // boxes.d_tab -- the same plan, one slot per call whoever makes it; the scratch of per-chunk counts ([volume][chunk] words) and the
+    // host form's pinned counts are their own and only ever grow
+    struct {
+        HipBuf<uint32_t> d_part;
+        HipBuf<uint32_t> h_out;
+        uint64_t launches = 0, last_chunks = 0;  // fw_debug_volume_query
+    } volumes;
     HipBuf<unsigned long long> d_total;
     HipBuf<uint32_t> d_segids;
 

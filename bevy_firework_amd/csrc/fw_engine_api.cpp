@@ -275,13 +275,32 @@ fw_status fw_ctx_synchronize(fw_ctx *ctx) {
     return check_device_errors(ctx);
 }
 
+// An fw_collider as the device reads it (fw_collide.h: FwCollider) -- a member of the collider world (fw_ctx_set_colliders) or a volume
+// (fw_ctx_count_in_volumes)
+static bool collider_kind_ok(const fw_collider &c) { return c.kind >= FW_COLLIDER_PLANE && c.kind <= FW_COLLIDER_CAPSULE; }
+static FwCollider collider_record(const fw_collider &c) {
+    FwCollider d{};
+    d.kind = c.kind, d.layers = c.layers, d.radius = c.radius;
+    // (the sphere around `position` that contains it: a wave skips a collider none of its rays can reach, fw_cast_ray)
+    d.bound = c.kind == FW_COLLIDER_SPHERE ? c.radius
+              : c.kind == FW_COLLIDER_BOX ? std::sqrt(c.half_extents[0] * c.half_extents[0] + c.half_extents[1] * c.half_extents[1] + c.half_extents[2] * c.half_extents[2]) * 1.0001f
+              : (c.kind == FW_COLLIDER_CYLINDER || c.kind == FW_COLLIDER_CONE) ? std::sqrt(c.radius * c.radius + c.half_extents[1] * c.half_extents[1]) * 1.0001f  // (the rim of a cap / of the base)
+              : c.kind == FW_COLLIDER_CAPSULE ? (c.half_extents[1] + c.radius) * 1.0001f  // (the poles of the caps)
+                            : INFINITY;
+    if (!(d.bound >= 0.0f)) d.bound = INFINITY;  // (NaN / negative extents: never skipped)
+    memcpy(d.position, c.position, sizeof c.position);
+    memcpy(d.rotation, c.rotation, sizeof c.rotation);
+    memcpy(d.normal, c.normal, sizeof c.normal);
+    memcpy(d.half_extents, c.half_extents, sizeof c.half_extents);
+    return d;
+}
+
 fw_status fw_ctx_set_colliders(fw_ctx *ctx, const fw_collider *colliders, uint32_t n) {
     if (!ctx || (n && !colliders)) return fail(ctx, FW_EINVAL, "bad collider set");
     hipSetDevice(ctx->device);
     if (fw_status fst = flush_withheld(ctx)) return fst;  // (fw_ctx::withheld)
     for (uint32_t i = 0; i < n; i++)
-        if (colliders[i].kind < FW_COLLIDER_PLANE || colliders[i].kind > FW_COLLIDER_CAPSULE)
-            return fail(ctx, FW_EINVAL, "unknown collider kind");
+        if (!collider_kind_ok(colliders[i])) return fail(ctx, FW_EINVAL, "unknown collider kind");
     // The reference asks the live physics world every frame (core.rs:756-765): a set that changes every frame must not
     // stall the frames in flight.  The new set is staged in pinned memory and copied by the stream itself.
     // (the wait of take: for the copy of two sets ago, long done unless the caller replaces the set in a tight loop)
@@ -292,23 +311,7 @@ fw_status fw_ctx_set_colliders(fw_ctx *ctx, const fw_collider *colliders, uint32
     if (n > ctx->d_colliders.cap()) {  // a larger world than ever before: the one case that waits (kernels in flight read the old table)
         if ((st = sync(ctx)) || (st = alloc_buf(ctx, ctx->d_colliders, ncap, Mem::device, false, &ctx->g.colliders))) return st;
     }
-    for (uint32_t i = 0; i < n; i++) {
-        const fw_collider &c = colliders[i];
-        FwCollider &d = h[i];
-        d = FwCollider{};
-        d.kind = c.kind, d.layers = c.layers, d.radius = c.radius;
-        // (the sphere around `position` that contains it: a wave skips a collider none of its rays can reach, fw_cast_ray)
-        d.bound = c.kind == FW_COLLIDER_SPHERE ? c.radius
-                  : c.kind == FW_COLLIDER_BOX ? std::sqrt(c.half_extents[0] * c.half_extents[0] + c.half_extents[1] * c.half_extents[1] + c.half_extents[2] * c.half_extents[2]) * 1.0001f
-                  : (c.kind == FW_COLLIDER_CYLINDER || c.kind == FW_COLLIDER_CONE) ? std::sqrt(c.radius * c.radius + c.half_extents[1] * c.half_extents[1]) * 1.0001f  // (the rim of a cap / of the base)
-                  : c.kind == FW_COLLIDER_CAPSULE ? (c.half_extents[1] + c.radius) * 1.0001f  // (the poles of the caps)
-                                : INFINITY;
-        if (!(d.bound >= 0.0f)) d.bound = INFINITY;  // (NaN / negative extents: never skipped)
-        memcpy(d.position, c.position, sizeof c.position);
-        memcpy(d.rotation, c.rotation, sizeof c.rotation);
-        memcpy(d.normal, c.normal, sizeof c.normal);
-        memcpy(d.half_extents, c.half_extents, sizeof c.half_extents);
-    }
+    for (uint32_t i = 0; i < n; i++) h[i] = collider_record(colliders[i]);
     if (n) {
         FW_HIP(ctx, hipMemcpyAsync(ctx->d_colliders, h, n * sizeof(FwCollider), hipMemcpyHostToDevice, ctx->stream));
         if ((st = ctx->h_coll.commit(ctx, ctx->stream))) return st;
@@ -840,35 +843,55 @@ fw_status fw_ctx_track_aabbs(fw_ctx *ctx, int32_t enable) {
 // ---- the boxes of many spawners in one call (firework_hip.h: BATCHED BOXES; fw_boxes.h, fw_k_boxes / fw_k_boxes_fold)
 static_assert(sizeof(fw_aabb) == 32 && sizeof(FwBoxPlace) == 16 && sizeof(FwBoxEntry) % 16 == 0, "fw_aabb: 32 bytes; the two tables share one 16-byte aligned copy");
 
-// What the two forms share, behind their argument checks (n > 0, every handle names a live spawner): fw_spawner_aabb's prologue for
-// the whole list at once -- Ages::ages: a withheld group goes out once, stale ages are written back, a deferred spin stays deferred,
-// the side stream is joined once where a listed segment's launches may run there --, then one entry per listed (spawner, type)
-// segment and one place per handle into the staging slot of this turn, ONE copy, two launches; `records`: n fw_aabb records the fold
-// kernel writes, device or pinned host memory.  Host work per listed segment, none per particle; waits only to grow.
-static fw_status boxes_enqueue(fw_ctx *ctx, uint32_t n, const fw_spawner *handles, void *records, const char *who) {
+// What the batched boxes and the volume queries share, behind their argument checks (n > 0, every place names a live spawner and, unless
+// its type is -1 -- every particle type of the spawner --, one of its types): fw_spawner_aabb's prologue for the whole list at once -- a
+// withheld group goes out once, with `ages` (Ages::ages) stale ages are written back, a deferred spin stays deferred either way, the side
+// stream is joined once where a listed segment's launches may run there --, then one entry per listed (spawner, type) segment and one
+// place per list position into the staging slot of this turn, with room for `extra` bytes behind them (16-byte aligned: whatever else
+// the call sends along in the same copy), and the plan.  Host work per listed segment, none per particle; nothing is enqueued but what the
+// prologue flushes.
+struct ListedPlan {
+    char *h = nullptr, *d = nullptr;        // the staging slot of this turn, the device table it feeds
+    size_t bytes = 0, places = 0, extra = 0;  // of the slot in all; where the places and the extra bytes start
+    uint32_t entries = 0;
+    uint64_t chunks = 0;
+};
+// (the list: `places`, or -- null -- every type of handles[i])
+static fw_status plan_listed(fw_ctx *ctx, uint32_t n, const fw_spawner *handles, const fw_volume_place *places, bool ages, size_t extra, const char *who,
+                             ListedPlan *out) {
+    const auto at = [&](uint32_t i) { return places ? places[i] : fw_volume_place{handles[i], -1}; };
     poll_device_error(ctx);
     size_t ne = 0;
     for (uint32_t i = 0; i < n; i++) {
-        const SpawnerHost &sp = ctx->spawners[(size_t)handles[i]];
+        const fw_volume_place pl = at(i);
+        const SpawnerHost &sp = ctx->spawners[(size_t)pl.spawner];
         if (sp.poisoned) return poisoned_status(ctx);
-        ne += sp.seg.size();
+        ne += pl.type < 0 ? sp.seg.size() : 1u;
     }
     if (n > FW_BOX_MAX_CHUNKS || ne > 0xFFFFFFFFull) return fail(ctx, FW_EINVAL, std::string(who) + ": more places than one batch holds");
     hipSetDevice(ctx->device);
     fw_status st;
     if ((st = flush_withheld(ctx))) return st;  // (fw_ctx::withheld)
+    // the listed segments of place i, in type order
+    const auto each_seg = [&](uint32_t i, auto &&f) -> fw_status {
+        const fw_volume_place pl = at(i);
+        const std::vector<uint32_t> &seg = ctx->spawners[(size_t)pl.spawner].seg;
+        for (size_t t = pl.type < 0 ? 0 : (size_t)pl.type, t1 = pl.type < 0 ? seg.size() : t + 1; t < t1; t++)
+            if (fw_status fst = f(seg[t])) return fst;
+        return FW_OK;
+    };
     bool side = false;  // a listed segment is a FIFO ring or a small type: its launches may run on the ring stream
     for (uint32_t i = 0; i < n; i++)
-        for (uint32_t si : ctx->spawners[(size_t)handles[i]].seg) {
-            if ((st = ensure_ages(ctx, si))) return st;
-            side |= ctx->segs[si].fifo || ctx->segs[si].small;
-        }
+        if ((st = each_seg(i, [&](uint32_t si) -> fw_status {
+                side |= ctx->segs[si].fifo || ctx->segs[si].small;
+                return ages ? ensure_ages(ctx, si) : FW_OK;
+            })))
+            return st;
     if (side && (st = join_side(ctx))) return st;
-    const size_t bytes = ne * sizeof(FwBoxEntry) + (size_t)n * sizeof(FwBoxPlace);
-    char *h;
-    if ((st = ctx->boxes.h_tab.take(ctx, bytes, std::max<size_t>(bytes * 2, 16384), &h, &ctx->boxes.d_tab))) return st;
-    FwBoxEntry *const tab = reinterpret_cast<FwBoxEntry *>(h);
-    FwBoxPlace *const places = reinterpret_cast<FwBoxPlace *>(h + ne * sizeof(FwBoxEntry));
+    out->places = ne * sizeof(FwBoxEntry), out->extra = out->places + (size_t)n * sizeof(FwBoxPlace), out->bytes = out->extra + extra;
+    if ((st = ctx->boxes.h_tab.take(ctx, out->bytes, std::max<size_t>(out->bytes * 2, 16384), &out->h, &ctx->boxes.d_tab))) return st;
+    out->d = ctx->boxes.d_tab;
+    FwBoxEntry *const tab = reinterpret_cast<FwBoxEntry *>(out->h);
     std::vector<uint32_t> &first = ctx->boxes.place_first;
     try {
         first.resize((size_t)n + 1);
@@ -878,25 +901,36 @@ static fw_status boxes_enqueue(fw_ctx *ctx, uint32_t n, const fw_spawner *handle
     uint32_t e = 0;
     for (uint32_t i = 0; i < n; i++) {
         first[i] = e;
-        for (uint32_t si : ctx->spawners[(size_t)handles[i]].seg) {
+        (void)each_seg(i, [&](uint32_t si) -> fw_status {
             const SegHost &S = ctx->segs[si];
             FwBoxEntry &E = tab[e++];
             E.v = seg_view(ctx, si, ctx->parity), E.d_count = count_slot(ctx, si);
             E.bound = S.nested_fed ? S.capacity : std::min(S.ub, S.capacity);  // (the bound of fw_spawner_pack_instances_device)
             E.chunk0 = 0;
-        }
+            return FW_OK;
+        });
     }
     first[n] = e;
-    const uint64_t total = fw_boxes_plan(tab, e, first.data(), n, places);
-    if (total > FW_BOX_MAX_CHUNKS) return fail(ctx, FW_EINVAL, std::string(who) + ": more particles than one batch holds");
+    out->entries = e;
+    out->chunks = fw_boxes_plan(tab, e, first.data(), n, reinterpret_cast<FwBoxPlace *>(out->h + out->places));
+    if (out->chunks > FW_BOX_MAX_CHUNKS) return fail(ctx, FW_EINVAL, std::string(who) + ": more particles than one batch holds");
+    return FW_OK;
+}
+
+// The batched boxes behind plan_listed: every handle a place of all its types, ages written back; ONE copy, two launches; `records`: n
+// fw_aabb records the fold kernel writes, device or pinned host memory.  Waits only to grow.
+static fw_status boxes_enqueue(fw_ctx *ctx, uint32_t n, const fw_spawner *handles, void *records, const char *who) {
+    ListedPlan P;
+    fw_status st;
+    if ((st = plan_listed(ctx, n, handles, nullptr, true, 0, who, &P))) return st;
+    const uint64_t total = P.chunks;
     if (total * 8 > ctx->boxes.d_part.cap()) {  // more than any call before: the one case that waits (launches in flight may use the old scratch)
         if ((st = sync(ctx)) || (st = alloc_buf(ctx, ctx->boxes.d_part, (size_t)((total + total / 4 + 1023u) & ~1023ull) * 8))) return st;
     }
-    char *const d = ctx->boxes.d_tab;
-    FW_HIP(ctx, hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, ctx->stream));
+    FW_HIP(ctx, hipMemcpyAsync(P.d, P.h, P.bytes, hipMemcpyHostToDevice, ctx->stream));
     uint32_t launches = 0;
     // (no synchronisation: the kernels read every count -- and a range ring's old part -- from the device)
-    const hipError_t le = fw_launch_boxes(ctx->stream, reinterpret_cast<const FwBoxEntry *>(d), e, reinterpret_cast<const FwBoxPlace *>(d + ne * sizeof(FwBoxEntry)), n,
+    const hipError_t le = fw_launch_boxes(ctx->stream, reinterpret_cast<const FwBoxEntry *>(P.d), P.entries, reinterpret_cast<const FwBoxPlace *>(P.d + P.places), n,
                                           (uint32_t)total, ctx->boxes.d_part, records, &launches);
     ctx->boxes.launches += launches, ctx->boxes.last_chunks = total;
     if ((st = ctx->boxes.h_tab.commit(ctx, ctx->stream))) return st;  // (behind the kernels: they read the device table the slot fed)
@@ -930,6 +964,77 @@ fw_status fw_ctx_aabbs_device(fw_ctx *ctx, uint32_t n, const fw_spawner *handles
     if (n && (reinterpret_cast<uintptr_t>(d_out) & 15u)) return fail(ctx, FW_EINVAL, "fw_ctx_aabbs_device: d_out is not 16-byte aligned");
     if (!n) return FW_OK;
     return boxes_enqueue(ctx, n, handles, d_out, "fw_ctx_aabbs_device");
+}
+
+// ---- the particles inside analytic volumes (firework_hip.h: VOLUME QUERIES; fw_volumes.h, fw_k_volumes / fw_k_volumes_fold)
+static_assert(sizeof(fw_volume_place) == 8 && sizeof(FwCollider) % 16 == 0, "fw_volume_place: 8 bytes; the volume records ride behind the two tables in one 16-byte aligned copy");
+
+// The arguments of both forms: FW_OK with *none set where there is nothing to answer
+static fw_status volumes_args(fw_ctx *ctx, uint32_t n_places, const fw_volume_place *places, uint32_t n_volumes, const fw_collider *volumes, const void *out,
+                              bool *none) {
+    if (!ctx) return FW_EINVAL;
+    *none = !n_places || !n_volumes;
+    if (*none) return FW_OK;
+    if (!places || !volumes || !out) return fail(ctx, FW_EINVAL, "fw_ctx_count_in_volumes: null places, volumes or output");
+    if ((uint64_t)n_places * n_volumes > FW_VOLUME_MAX_ANSWERS) return fail(ctx, FW_EINVAL, "fw_ctx_count_in_volumes: more than FW_VOLUME_MAX_ANSWERS answers");
+    for (uint32_t i = 0; i < n_places; i++) {
+        const SpawnerHost *sp = get_spawner(ctx, places[i].spawner);
+        if (!sp) return fail(ctx, FW_EINVAL, "fw_ctx_count_in_volumes: invalid spawner handle");
+        if (places[i].type < -1 || (places[i].type >= 0 && (size_t)places[i].type >= sp->seg.size()))
+            return fail(ctx, FW_EINVAL, "fw_ctx_count_in_volumes: no such particle type");
+    }
+    for (uint32_t i = 0; i < n_volumes; i++)
+        if (!collider_kind_ok(volumes[i])) return fail(ctx, FW_EINVAL, "fw_ctx_count_in_volumes: unknown volume kind");
+    return FW_OK;
+}
+
+// Both forms behind plan_listed, WITHOUT the age step -- the kernels read positions only: stale ages stay stale --: the volume records
+// converted into the slot behind the two tables, ONE copy, two launches; `counts`: n_places * n_volumes uint32 the fold kernel writes,
+// device or pinned host memory.  Waits only to grow the scratch (chunks * volumes words) or the tables.
+static fw_status volumes_enqueue(fw_ctx *ctx, uint32_t n_places, const fw_volume_place *places, uint32_t n_volumes, const fw_collider *volumes, void *counts) {
+    ListedPlan P;
+    fw_status st;
+    if ((st = plan_listed(ctx, n_places, nullptr, places, false, (size_t)n_volumes * sizeof(FwCollider), "fw_ctx_count_in_volumes", &P))) return st;
+    FwCollider *const rec = reinterpret_cast<FwCollider *>(P.h + P.extra);
+    for (uint32_t i = 0; i < n_volumes; i++) rec[i] = collider_record(volumes[i]);
+    const uint64_t words = P.chunks * n_volumes;
+    if (words > ctx->volumes.d_part.cap()) {  // more than any call before: the one case that waits (launches in flight may use the old scratch)
+        if ((st = sync(ctx)) || (st = alloc_buf(ctx, ctx->volumes.d_part, (size_t)((words + words / 4 + 1023u) & ~1023ull)))) return st;
+    }
+    FW_HIP(ctx, hipMemcpyAsync(P.d, P.h, P.bytes, hipMemcpyHostToDevice, ctx->stream));
+    uint32_t launches = 0;
+    // (no synchronisation: the kernels read every count -- and a range ring's old part -- from the device)
+    const hipError_t le = fw_launch_volumes(ctx->stream, reinterpret_cast<const FwBoxEntry *>(P.d), P.entries, reinterpret_cast<const FwBoxPlace *>(P.d + P.places), n_places,
+                                            (uint32_t)P.chunks, reinterpret_cast<const FwCollider *>(P.d + P.extra), n_volumes, ctx->volumes.d_part, counts, &launches);
+    ctx->volumes.launches += launches, ctx->volumes.last_chunks = P.chunks;
+    if ((st = ctx->boxes.h_tab.commit(ctx, ctx->stream))) return st;  // (behind the kernels: they read the device table the slot fed)
+    FW_HIP(ctx, le);
+    return FW_OK;
+}
+
+fw_status fw_ctx_count_in_volumes(fw_ctx *ctx, uint32_t n_places, const fw_volume_place *places, uint32_t n_volumes, const fw_collider *volumes, uint32_t *out) {
+    bool none;
+    fw_status st = volumes_args(ctx, n_places, places, n_volumes, volumes, out, &none);
+    if (st || none) return st;
+    const size_t n = (size_t)n_places * n_volumes;
+    if (n > ctx->volumes.h_out.cap()) {  // (nothing of an earlier call may still be on its way into the old words)
+        if ((st = sync(ctx)) || (st = alloc_buf(ctx, ctx->volumes.h_out, std::max<size_t>(256, n * 2), Mem::pinned))) return st;
+    }
+    if ((st = volumes_enqueue(ctx, n_places, places, n_volumes, volumes, ctx->volumes.h_out.get()))) return st;
+    // the counts land in pinned memory: one synchronisation for the whole call, then a host copy
+    st = sync(ctx);
+    if (!st) st = check_device_errors(ctx);
+    if (st && st != FW_ECAPACITY) return st;
+    memcpy(out, ctx->volumes.h_out.get(), n * sizeof(uint32_t));
+    return st;
+}
+
+fw_status fw_ctx_count_in_volumes_device(fw_ctx *ctx, uint32_t n_places, const fw_volume_place *places, uint32_t n_volumes, const fw_collider *volumes, void *d_out) {
+    bool none;
+    const fw_status st = volumes_args(ctx, n_places, places, n_volumes, volumes, d_out, &none);
+    if (st || none) return st;
+    if (reinterpret_cast<uintptr_t>(d_out) & 3u) return fail(ctx, FW_EINVAL, "fw_ctx_count_in_volumes_device: d_out is not 4-byte aligned");
+    return volumes_enqueue(ctx, n_places, places, n_volumes, volumes, d_out);
 }
 
 fw_status fw_ctx_live_count(fw_ctx *ctx, uint64_t *out) {
@@ -1212,6 +1317,16 @@ fw_status fw_debug_aabb_batch(fw_ctx *ctx, uint64_t *launches, uint64_t *chunks,
     if (launches) *launches = ctx->boxes.launches;
     if (chunks) *chunks = ctx->boxes.last_chunks;
     if (chunk_size) *chunk_size = FW_BOX_CHUNK;
+    return FW_OK;
+}
+// the volume queries: launches of fw_k_volumes / fw_k_volumes_fold so far, the chunks of the latest call, list positions per chunk
+// (fw_boxes.h), volumes per tile (fw_volumes.h)
+fw_status fw_debug_volume_query(fw_ctx *ctx, uint64_t *launches, uint64_t *chunks, uint32_t *chunk_size, uint32_t *volume_tile) {
+    if (!ctx) return FW_EINVAL;
+    if (launches) *launches = ctx->volumes.launches;
+    if (chunks) *chunks = ctx->volumes.last_chunks;
+    if (chunk_size) *chunk_size = FW_BOX_CHUNK;
+    if (volume_tile) *volume_tile = FW_VOLUME_TILE;
     return FW_OK;
 }
 fw_status fw_debug_read_timestamps(fw_ctx *ctx, unsigned long long *out, uint64_t max_tiles, uint64_t *n_tiles) {

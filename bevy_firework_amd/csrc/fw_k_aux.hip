@@ -5,6 +5,7 @@
 #include "fw_spin.h"
 #include "fw_sort.h"
 #include "fw_boxes.h"
+#include "fw_volumes.h"
 
 // ---------------------------------------------------------------------------------
 // readback / upload / render hand-off helpers
@@ -24,6 +25,17 @@ __device__ __forceinline__ float fw_view_life(const FwSegView &v, uint32_t i) {
 }
 // position + age (a FIFO ring: component planes, FwSegView::cpl bit 2)
 __device__ __forceinline__ float4 fw_view_q0(const FwSegView &v, uint32_t i) { return fw_ldq0(v.buf, v.capacity, i, v.cpl); }
+// the position alone (the volume queries): three component loads where Q0 is four planes -- the age plane of a FIFO ring, which may be
+// stale under the age rule, is not touched --, the one float4 everywhere else
+__device__ __forceinline__ fw_v3 fw_view_pos(const FwSegView &v, uint32_t i) {
+    const char *q0 = v.buf + FW_OFF_Q0(v.capacity);
+    if (v.cpl & FW_CPL_Q0) {
+        const size_t cp = FW_CP(v.capacity);
+        return fw_v3{fw_ld1(q0, i), fw_ld1(q0 + cp, i), fw_ld1(q0 + 2 * cp, i)};
+    }
+    const float4 q = fw_ld4(q0, i);
+    return fw_v3{q.x, q.y, q.z};
+}
 // velocity + initial_scale, angular velocity + lifetime (cannot turn: 0), rotation (cannot turn: the type's one)
 __device__ __forceinline__ float4 fw_view_q1(const FwSegView &v, uint32_t i) { return fw_ldq(v.buf + FW_OFF_Q1(v.capacity), v.capacity, i, v.cpl != 0u); }
 __device__ __forceinline__ float fw_view_q1w(const FwSegView &v, uint32_t i) { return fw_ldq_w(v.buf + FW_OFF_Q1(v.capacity), v.capacity, i, v.cpl != 0u); }
@@ -390,6 +402,63 @@ __global__ __launch_bounds__(64) void fw_k_boxes_fold(const FwBoxEntry *tab, con
     if (threadIdx.x == 0) reinterpret_cast<int32_t *>(rec)[3] = got ? 1 : 0, reinterpret_cast<uint32_t *>(rec)[7] = 0u;
 }
 
+// VOLUME QUERIES (fw_ctx_count_in_volumes[_device]; fw_volumes.h): how many particles of every listed place lie inside every listed
+// volume, in two launches.  The chunks are the batched boxes' (fw_boxes.h: the same entry table, plan and locate): one WAVE takes one chunk
+// of FW_BOX_CHUNK list positions of one segment.  A lane loads its FW_BOX_CHUNK / 64 positions ONCE -- positions only, fw_view_pos -- and
+// keeps which of them lie below min(count, bound) as bits; the volumes then pass by in tiles of FW_VOLUME_TILE FwCollider records through
+// LDS, every lane tests its positions against the one record the wave is at, the wave adds its ballots, and lane v mod 64 keeps the count
+// of volume v.  Each tile ends in one store per lane into the scratch, which is laid out [volume][chunk]: the fold reads the chunks of
+// one (place, volume) side by side.  A chunk beyond the device's count tests nothing and stores zeros.  No atomics, no memset, nobody
+// waits for anybody.
+constexpr uint32_t FW_VOL_PER_LANE = FW_BOX_CHUNK / 64u;
+static_assert(FW_BOX_CHUNK % 64u == 0 && FW_VOL_PER_LANE >= 1u && FW_VOL_PER_LANE <= 32u, "a lane keeps the validity of its positions as bits of one word");
+static_assert(FW_VOLUME_TILE == 64u, "lane v mod 64 keeps the count of volume v");
+__global__ __launch_bounds__(64) void fw_k_volumes(const FwBoxEntry *tab, uint32_t n_entries, const FwCollider *vols, uint32_t n_vol, uint32_t total_chunks,
+                                                   uint32_t *part) {
+    __shared__ FwCollider s_vol[FW_VOLUME_TILE];
+    const uint32_t chunk = blockIdx.x, lane = threadIdx.x;
+    uint32_t first;
+    const FwBoxEntry &E = tab[fw_boxes_locate(tab, n_entries, chunk, &first)];
+    const FwSegView v = E.v;
+    const uint32_t n = min(*E.d_count, E.bound);
+    const uint32_t end = (n > first && n - first > FW_BOX_CHUNK) ? first + FW_BOX_CHUNK : n;
+    const uint32_t head = fw_view_head(v);
+    fw_v3 p[FW_VOL_PER_LANE];
+    uint32_t valid = 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < FW_VOL_PER_LANE; k++) {
+        const uint32_t li = first + k * 64u + lane;
+        p[k] = fw_v3{0.0f, 0.0f, 0.0f};
+        if (li < end) p[k] = fw_view_pos(v, fw_view_slot(v, head, li)), valid |= 1u << k;
+    }
+    for (uint32_t v0 = 0; v0 < n_vol; v0 += FW_VOLUME_TILE) {
+        const uint32_t m = min(FW_VOLUME_TILE, n_vol - v0);
+        if (lane < m) s_vol[lane] = vols[v0 + lane];
+        __syncthreads();
+        uint32_t mine = 0u;
+        for (uint32_t j = 0; j < (end > first ? m : 0u); j++) {
+            const FwCollider c = s_vol[j];
+            uint32_t cnt = 0u;
+#pragma unroll
+            for (uint32_t k = 0; k < FW_VOL_PER_LANE; k++) cnt += (uint32_t)__popcll(__ballot(((valid >> k) & 1u) != 0u && fw_collider_contains(c, p[k])));
+            if (lane == j) mine = cnt;
+        }
+        if (lane < m) part[(size_t)(v0 + lane) * total_chunks + chunk] = mine;
+        __syncthreads();  // (the next tile overwrites the records)
+    }
+}
+// ... and one wave per ANSWER (place p, volume v: workgroup p * n_vol + v) adds the counts of the place's chunks, which lie side by side
+// in the volume's row of the scratch, and writes out[p * n_vol + v] -- to device memory, or to pinned host memory (the host form: no copy)
+__global__ __launch_bounds__(64) void fw_k_volumes_fold(const FwBoxPlace *places, const uint32_t *part, uint32_t n_vol, uint32_t total_chunks, uint32_t *out) {
+    const FwBoxPlace P = places[blockIdx.x / n_vol];
+    const uint32_t *row = part + (size_t)(blockIdx.x % n_vol) * total_chunks;
+    uint32_t s = 0u;
+    for (uint32_t c = P.c0 + threadIdx.x; c < P.c1; c += 64u) s += row[c];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+    if (threadIdx.x == 0) out[blockIdx.x] = s;
+}
+
 __global__ void fw_k_total(const uint32_t *counts, uint32_t n_seg, unsigned long long *out) {
     __shared__ unsigned long long s[4];
     unsigned long long t = 0;
@@ -521,6 +590,20 @@ hipError_t fw_launch_boxes(hipStream_t s, const FwBoxEntry *d_tab, uint32_t n_en
         ++*launches;
     }
     hipLaunchKernelGGL(fw_k_boxes_fold, dim3(n_places), dim3(64), 0, s, d_tab, d_places, (const float *)d_part, (float *)out_records);
+    ++*launches;
+    return hipGetLastError();
+}
+
+hipError_t fw_launch_volumes(hipStream_t s, const FwBoxEntry *d_tab, uint32_t n_entries, const FwBoxPlace *d_places, uint32_t n_places, uint32_t total_chunks,
+                             const FwCollider *d_volumes, uint32_t n_volumes, uint32_t *d_part, void *out_counts, uint32_t *launches) {
+    *launches = 0;
+    if (!n_places || !n_volumes) return hipSuccess;
+    if (total_chunks > FW_BOX_MAX_CHUNKS || (total_chunks && !n_entries) || (uint64_t)n_places * n_volumes > FW_VOLUME_MAX_ANSWERS) return hipErrorInvalidValue;
+    if (total_chunks) {  // (no listed type can hold a particle: nothing to read, the fold alone answers -- with zeros)
+        hipLaunchKernelGGL(fw_k_volumes, dim3(total_chunks), dim3(64), 0, s, d_tab, n_entries, d_volumes, n_volumes, total_chunks, d_part);
+        ++*launches;
+    }
+    hipLaunchKernelGGL(fw_k_volumes_fold, dim3(n_places * n_volumes), dim3(64), 0, s, d_places, (const uint32_t *)d_part, n_volumes, total_chunks, (uint32_t *)out_counts);
     ++*launches;
     return hipGetLastError();
 }

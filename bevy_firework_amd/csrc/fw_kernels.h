@@ -486,6 +486,11 @@ struct FwBoxPlace;
 // total_chunks * 8 floats; out_records: n_places fw_aabb records, device memory or PINNED host memory.  *launches: kernels enqueued
 hipError_t fw_launch_boxes(hipStream_t s, const FwBoxEntry *d_tab, uint32_t n_entries, const FwBoxPlace *d_places, uint32_t n_places,
                            uint32_t total_chunks, float *d_part, void *out_records, uint32_t *launches);
+// The particles of many places inside many volumes in two launches (fw_volumes.h; fw_k_volumes / fw_k_volumes_fold).  The tables are the
+// batched boxes'; d_volumes: n_volumes records in device memory; d_part: device scratch of total_chunks * n_volumes uint32, [volume][chunk];
+// out_counts: n_places * n_volumes uint32, device or pinned host memory.  *launches: kernels enqueued -- two, or one where total_chunks == 0
+hipError_t fw_launch_volumes(hipStream_t s, const FwBoxEntry *d_tab, uint32_t n_entries, const FwBoxPlace *d_places, uint32_t n_places, uint32_t total_chunks,
+                             const FwCollider *d_volumes, uint32_t n_volumes, uint32_t *d_part, void *out_counts, uint32_t *launches);
 hipError_t fw_launch_total(hipStream_t s, const uint32_t *counts, uint32_t n_seg, unsigned long long *d_out);
 hipError_t fw_launch_copy_probe(hipStream_t s, const void *src, void *dst, size_t bytes);
 // Refit of a deformable mesh (fw_k_refit.hip): the levels of R.order, lowest first -- one launch per level of more than

@@ -6,24 +6,25 @@
 // helpers) and left unchanged.
 #pragma once
 #include "fw_collide.h"
+#include "fw_volumes.h"
 
 FW_HD float fw_clamp_sym(float x, float h) { return x < -h ? -h : (x > h ? h : x); }
 
-// One analytic collider.  Returns true when x lies inside or on the solid -- the expression fw_ray_collider tests for its
-// distance-0 case, kind by kind.  Otherwise *q is the nearest point of the solid -- in the collider's own frame for the framed
+// One analytic collider.  Returns true when x lies inside or on the solid -- fw_collider_contains (fw_volumes.h): the expression
+// fw_ray_collider tests for its distance-0 case, kind by kind; what follows states its operands again, which the compiler folds into
+// one evaluation.  Otherwise *q is the nearest point of the solid -- in the collider's own frame for the framed
 // kinds (BOX, CYLINDER, CONE, CAPSULE), in the world for PLANE and SPHERE -- and *d2 = dot(w, w) with w = o - q in that frame.
 FW_HD bool fw_project_collider(const FwCollider &c, fw_v3 x, fw_v3 *q, float *d2) {
+    if (fw_collider_contains(c, x)) return true;
     const fw_v3 cpos{c.position[0], c.position[1], c.position[2]};
     fw_v3 o, p;
     if (c.kind == 0) {  // PLANE
         const fw_v3 n{c.normal[0], c.normal[1], c.normal[2]};
-        if (fw_dot3(n, fw_sub3(cpos, x)) > 0.0f) return true;
         const float s = fw_dot3(n, fw_sub3(x, cpos));
         o = x, p = fw_sub3(x, fw_scale3(n, s));
     } else if (c.kind == 1) {  // SPHERE
         const fw_v3 v = fw_sub3(x, cpos);
         const float vv = fw_dot3(v, v);
-        if (vv - c.radius * c.radius <= 0.0f) return true;
         o = x, p = fw_add3(cpos, fw_scale3(v, c.radius / sqrtf(vv)));
     } else {
         const fw_q4 r{c.rotation[0], c.rotation[1], c.rotation[2], c.rotation[3]};
@@ -33,13 +34,6 @@ FW_HD bool fw_project_collider(const FwCollider &c, fw_v3 x, fw_v3 *q, float *d2
             // CYLINDER, CONE: solids of revolution about the local Y axis -- the nearest point of the profile in (r, y), taken back
             const float hh = c.half_extents[1], rr = c.radius * c.radius;
             const float xz = o.x * o.x + o.z * o.z;
-            if (c.kind == 3) {
-                if (fabsf(o.y) <= hh && xz - rr <= 0.0f) return true;
-            } else {
-                const float k = c.radius / (hh + hh), k2 = k * k;
-                const float wy = o.y - hh;
-                if (o.y >= -hh && wy <= 0.0f && xz - k2 * (wy * wy) <= 0.0f) return true;
-            }
             const float r0 = sqrtf(xz);
             // the cylinder's rectangle: r clamped to [0, radius], y to +-hh; the cone's base segment y = -hh, r in [0, radius] ...
             float pr = r0 > c.radius ? c.radius : r0, py = c.kind == 3 ? fw_clamp_sym(o.y, hh) : -hh;
@@ -58,17 +52,14 @@ FW_HD bool fw_project_collider(const FwCollider &c, fw_v3 x, fw_v3 *q, float *d2
             }
             p = r0 == 0.0f ? fw_v3{pr, py, 0.0f} : fw_v3{pr * o.x / r0, py, pr * o.z / r0};
         } else if (c.kind == 5) {  // CAPSULE
-            const float hl = c.half_extents[1], rr = c.radius * c.radius;
-            const float xz = o.x * o.x + o.z * o.z;
+            const float hl = c.half_extents[1];
             const float yc = o.y < -hl ? -hl : (o.y > hl ? hl : o.y);
             const float dy = o.y - yc;
-            if ((xz + dy * dy) - rr <= 0.0f) return true;
             const fw_v3 v{o.x, dy, o.z};
             const float s = c.radius / sqrtf(fw_dot3(v, v));
             p = fw_v3{v.x * s, yc + v.y * s, v.z * s};
         } else {  // BOX
             const float hx = c.half_extents[0], hy = c.half_extents[1], hz = c.half_extents[2];
-            if (fabsf(o.x) <= hx && fabsf(o.y) <= hy && fabsf(o.z) <= hz) return true;
             p = fw_v3{fw_clamp_sym(o.x, hx), fw_clamp_sym(o.y, hy), fw_clamp_sym(o.z, hz)};
         }
     }

@@ -430,6 +430,11 @@ AABB_DTYPE = np.dtype(
 )
 assert AABB_DTYPE.itemsize == 32
 
+# fw_volume_place (include/firework_hip.h: VOLUME QUERIES): one place of ParticleSystem.count_in_volumes -- a spawner handle and one of
+# its particle types, or -1 for all of them
+VOLUME_PLACE_DTYPE = np.dtype([("spawner", np.int32), ("type", np.int32)])
+assert VOLUME_PLACE_DTYPE.itemsize == 8
+
 # fw_sort_view (include/firework_hip.h: DEPTH-SORTED INSTANCES): the camera SpawnerData.instances_sorted sorts for
 SORT_BACK_TO_FRONT, SORT_FRONT_TO_BACK = 0, 1
 

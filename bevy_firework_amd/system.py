@@ -505,6 +505,40 @@ class ParticleSystem:
         self._check(self._lib.fw_debug_aabb_batch(self._ctx, C.byref(launches), C.byref(chunks), C.byref(size)))
         return int(launches.value), int(chunks.value), int(size.value)
 
+    # how many particles lie inside analytic volumes (include/firework_hip.h: VOLUME QUERIES).  `places`: a settings.VOLUME_PLACE_DTYPE
+    # array, or a sequence whose items are a SpawnerData / raw handle (every particle type) or a (spawner, type) pair (type -1: every
+    # type); any order, duplicates allowed.  `volumes`: settings.Collider objects of any kind; their layers are ignored
+    @staticmethod
+    def _place_array(places) -> np.ndarray:
+        if isinstance(places, np.ndarray) and places.dtype == S.VOLUME_PLACE_DTYPE:
+            return np.ascontiguousarray(places)
+        out = np.zeros(len(places), dtype=S.VOLUME_PLACE_DTYPE)
+        for k, p in enumerate(places):
+            d, t = p if isinstance(p, (tuple, list)) else (p, -1)
+            out[k] = (int(getattr(d, "handle", d)), int(t))
+        return out
+
+    def count_in_volumes(self, places, volumes) -> np.ndarray:
+        """counts[p, v] (uint32) = the particles of places[p] whose position lies inside volumes[v].  One wait for the call."""
+        pl = self._place_array(places)
+        out = np.zeros((len(pl), len(volumes)), dtype=np.uint32)
+        self._check(self._lib.fw_ctx_count_in_volumes(self._ctx, len(pl), pl.ctypes.data_as(C.c_void_p) if len(pl) else None, len(volumes),
+                                                      _ffi.make_colliders(volumes) if len(volumes) else None, out.ctypes.data_as(C.c_void_p) if out.size else None))
+        return out
+
+    def count_in_volumes_device(self, places, volumes, out_ptr: int) -> None:
+        """the same counts into DEVICE memory at out_ptr (n_places x n_volumes uint32, 4-byte aligned), enqueued on the context's stream:
+        no wait"""
+        pl = self._place_array(places)
+        self._check(self._lib.fw_ctx_count_in_volumes_device(self._ctx, len(pl), pl.ctypes.data_as(C.c_void_p) if len(pl) else None, len(volumes),
+                                                             _ffi.make_colliders(volumes) if len(volumes) else None, C.c_void_p(out_ptr) if out_ptr else None))
+
+    def debug_volume_query(self):
+        """(launches the volume queries have enqueued so far, chunks of the latest call, list positions per chunk, volumes per tile)"""
+        launches, chunks, size, tile = C.c_uint64(), C.c_uint64(), C.c_uint32(), C.c_uint32()
+        self._check(self._lib.fw_debug_volume_query(self._ctx, C.byref(launches), C.byref(chunks), C.byref(size), C.byref(tile)))
+        return int(launches.value), int(chunks.value), int(size.value), int(tile.value)
+
     # -- statistics / measurement ----------------------------------------------------------------
     def live_count(self) -> int:
         out = C.c_uint64()

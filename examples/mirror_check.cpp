@@ -307,7 +307,59 @@ static int aabbs_scenario() {
     return 0;
 }
 
+// `mirror_check volumes`: the three spawners of `aabbs` and every tenth frame how many of their particles lie inside six volumes -- a
+// half-space that holds everything, then one of every other kind, three of them rotated -- through ParticleSystemPlugin::count_in_volumes
+// and ::count_in_volumes_device over a list that names one spawner twice, once by its type and once by -1: one line per frame with the
+// counts inside the half-space and the digest of the counts of either form
+static int volumes_scenario() {
+    try {
+        ParticleSystemPlugin app(0, /*seed*/ 0x00C0FFEE);
+        std::vector<ParticleSpawnerData *> ds;
+        for (int k = 0; k < 3; k++) {
+            ParticleSpawner sp;
+            sp.particle_settings.resize(1);
+            sp.particle_settings[0].lifetime = RandF32::constant(0.75f);
+            sp.particle_settings[0].linear_drag = 0.125f;
+            sp.emission_settings.resize(1);
+            EmissionSettings &e = sp.emission_settings[0];
+            e.particle_index = 0;
+            e.emission_pacing = k == 2 ? EmissionPacing::OnDemand() : EmissionPacing::rate(k == 0 ? 2000.0f : 150.0f);
+            e.emission_shape = EmissionShape::Sphere(0.75f);
+            e.initial_velocity = {{1.0f, 6.0f}, {0.0f, 1.0f, 0.0f}, 0.5f};
+            ds.push_back(app.spawn(sp, Transform{{0.25f + 4.0f * (float)k, 3.0f, 0.125f}, {}}, 7u + (uint32_t)k));
+        }
+        const std::vector<ParticleSystemPlugin::VolumePlace> list = {{ds[2], -1}, {ds[0], 0}, {ds[1], -1}, {ds[0], -1}};
+        const Quat q{0.5f, 0.5f, 0.5f, 0.5f};
+        const std::vector<Collider> volumes = {Collider::Plane({0.0f, 1000.0f, 0.0f}, {0.0f, 1.0f, 0.0f}), Collider::Sphere({0.25f, 3.25f, 0.125f}, 0.625f),
+                                               Collider::Box({4.25f, 3.25f, 0.125f}, {0.5f, 0.625f, 0.375f}, q), Collider::Cylinder({0.25f, 3.25f, 0.125f}, 0.625f, 1.0f),
+                                               Collider::Cone({0.25f, 3.25f, 0.125f}, 0.75f, 1.5f, q), Collider::capsule({8.25f, 3.25f, 0.125f}, 0.375f, 0.75f, q)};
+        const size_t n = list.size() * volumes.size();
+        void *d_cnt = nullptr;
+        if (hipMalloc(&d_cnt, n * sizeof(uint32_t)) != hipSuccess) throw Error(FW_EHIP, "hipMalloc");
+        hipStream_t st = (hipStream_t)app.stream();
+        const float dt = 1.0f / 60.0f;
+        for (int fr = 0; fr < 40; fr++) {
+            if (fr == 15) ds[2]->queue_particles(33);
+            app.update(dt);
+            if (fr % 10 != 9) continue;
+            app.count_in_volumes_device(list, volumes, d_cnt);  // (right behind the step: no wait in between)
+            const std::vector<uint32_t> host = app.count_in_volumes(list, volumes);
+            std::vector<uint32_t> dev(n);
+            if (hipMemcpyAsync(dev.data(), d_cnt, n * sizeof(uint32_t), hipMemcpyDeviceToHost, st) != hipSuccess) throw Error(FW_EHIP, "hipMemcpyAsync");
+            app.synchronize();
+            std::printf("frame %d all %u %u %u %u host %016llx device %016llx\n", fr, host[0], host[volumes.size()], host[2 * volumes.size()], host[3 * volumes.size()],
+                        (unsigned long long)fnv(host.data(), n * sizeof(uint32_t)), (unsigned long long)fnv(dev.data(), n * sizeof(uint32_t)));
+        }
+        (void)hipFree(d_cnt);
+    } catch (const Error &e) {
+        std::fprintf(stderr, "firework error %d: %s\n", (int)e.status, e.what());
+        return 1;
+    }
+    return 0;
+}
+
 int main(int argc, char **argv) {
+    if (argc > 1 && std::strcmp(argv[1], "volumes") == 0) return volumes_scenario();
     if (argc > 1 && std::strcmp(argv[1], "aabbs") == 0) return aabbs_scenario();
     if (argc > 1 && std::strcmp(argv[1], "sorted") == 0) return sorted_scenario();
     if (argc > 1 && std::strcmp(argv[1], "project") == 0) return project_scenario();

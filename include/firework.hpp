@@ -396,6 +396,11 @@ class ParticleSystemPlugin {
 
     // the world particles collide with (stands in for avian's SpatialQuery; core.rs:581, 744-800)
     void set_colliders(const std::vector<Collider> &cs) {
+        const std::vector<fw_collider> v = collider_records(cs);
+        check(fw_ctx_set_colliders(ctx_, v.data(), (uint32_t)v.size()));
+    }
+    // (firework::Collider -> fw_collider: the collider world above and the volumes of count_in_volumes)
+    static std::vector<fw_collider> collider_records(const std::vector<Collider> &cs) {
         std::vector<fw_collider> v(cs.size());
         for (size_t i = 0; i < cs.size(); i++) {
             const Collider &c = cs[i];
@@ -407,7 +412,7 @@ class ParticleSystemPlugin {
             d.normal[0] = c.normal.x, d.normal[1] = c.normal.y, d.normal[2] = c.normal.z;
             d.half_extents[0] = c.half_extents.x, d.half_extents[1] = c.half_extents.y, d.half_extents[2] = c.half_extents.z;
         }
-        check(fw_ctx_set_colliders(ctx_, v.data(), (uint32_t)v.size()));
+        return v;
     }
 
     // triangle meshes of the collider world (fw_ctx_create_mesh): xyz = 3 floats per vertex, indices = 3 per triangle
@@ -521,6 +526,32 @@ class ParticleSystemPlugin {
         std::vector<fw_spawner> h;
         for (const ParticleSpawnerData *d : ds) h.push_back(d->handle);
         check(fw_ctx_aabbs_device(ctx_, (uint32_t)h.size(), h.data(), d_out));
+    }
+    // How many particles lie inside analytic volumes (firework_hip.h: VOLUME QUERIES; Unity's particle Triggers module): -> counts, that
+    // of place p and volume v at [p * volumes.size() + v].  A place is a spawner and one of its particle types, or -1 for all of them;
+    // any order, duplicates answered.  The volumes are firework::Collider of any kind, their layers ignored.  Two launches, one wait;
+    // an unread FIFO ring keeps its rules (positions only: no ages are written back, no spin is replayed)
+    struct VolumePlace {
+        const ParticleSpawnerData *data;
+        int32_t particle_type = -1;
+    };
+    static std::vector<fw_volume_place> volume_places(const std::vector<VolumePlace> &places) {
+        std::vector<fw_volume_place> p;
+        for (const VolumePlace &v : places) p.push_back(fw_volume_place{v.data->handle, v.particle_type});
+        return p;
+    }
+    std::vector<uint32_t> count_in_volumes(const std::vector<VolumePlace> &places, const std::vector<Collider> &volumes) {
+        const std::vector<fw_volume_place> p = volume_places(places);
+        const std::vector<fw_collider> v = collider_records(volumes);
+        std::vector<uint32_t> out(p.size() * v.size());
+        check(fw_ctx_count_in_volumes(ctx_, (uint32_t)p.size(), p.data(), (uint32_t)v.size(), v.data(), out.data()));
+        return out;
+    }
+    // ... the same counts into DEVICE memory (places.size() x volumes.size() uint32, 4-byte aligned) on the context's stream: no wait
+    void count_in_volumes_device(const std::vector<VolumePlace> &places, const std::vector<Collider> &volumes, void *d_out) {
+        const std::vector<fw_volume_place> p = volume_places(places);
+        const std::vector<fw_collider> v = collider_records(volumes);
+        check(fw_ctx_count_in_volumes_device(ctx_, (uint32_t)p.size(), p.data(), (uint32_t)v.size(), v.data(), d_out));
     }
 
     // one run of the chained systems (plugin.rs:46-60)

@@ -680,6 +680,52 @@ typedef struct fw_aabb { /* 32 bytes */
 fw_status fw_ctx_aabbs(fw_ctx *ctx, uint32_t n, const fw_spawner *handles, fw_aabb *out);
 fw_status fw_ctx_aabbs_device(fw_ctx *ctx, uint32_t n, const fw_spawner *handles, void *d_out);
 
+/* ---- VOLUME QUERIES ------------------------------------------------------------------ */
+/* How many particles lie inside analytic volumes -- "how many fire particles are in the player's capsule", "is this trigger box full of
+ * smoke" (Unity's particle Triggers module; on the CPU reference a loop over ParticleSpawnerData::particles).  Every other query asks
+ * about the collider world; this one asks about the particles, without moving them to the host and without ending an unread FIFO
+ * ring's rules.  out[p * n_volumes + v] is the number of particles of places[p] whose position lies inside volumes[v], counted at the
+ * call's place in the context's stream (modulo 2^32).
+ *   INSIDE    a volume is an fw_collider record of any of the six kinds; `layers` is ignored.  A particle is inside exactly when the
+ *             kind's INSIDE expression above holds for its position -- the expression the ray cast tests for its distance-0 case, and
+ *             what fw_point_projection.is_inside reports in a world that holds this collider alone -- operation by operation, fp32, no
+ *             fused a*b+c: PLANE dot(n, position - x) > 0; SPHERE (dot(v, v) - radius * radius) <= 0 with v = x - position; BOX
+ *             |o.x| <= hx and |o.y| <= hy and |o.z| <= hz; CYLINDER |o.y| <= hh and (xz - rr) <= 0; CONE o.y >= -hh and wy <= 0 and
+ *             (xz - k2 * (wy * wy)) <= 0; CAPSULE ((xz + (dy * dy)) - rr) <= 0, with o, xz, rr, k2, wy, dy as POINT QUERIES states them
+ *             (the identity rotation skips the product).  A point ON the boundary is inside: a sphere of radius 1 at the origin
+ *             contains (1, 0, 0).  The particle is a point: its scale plays no part.  A NaN position is inside nothing (every
+ *             comparison is false).  A volume with NaN or negative extents gives whatever the operations give, deterministically.
+ *             Meshes are surfaces and cannot be volumes.
+ *   WHICH     list positions [0, min(device count, host bound)) of each listed segment; the bound is fw_ctx_aabbs's (the capacity for a
+ *             type that Nested entries feed).  type = -1 lists every particle type of the spawner.  A spawner or type that holds
+ *             nothing counts 0.
+ *   ORDER     places may repeat and come in any order; every place is answered.
+ *   RULES     as fw_spawner_aabb, frames a FIFO ring withheld are enqueued first, once.  Unlike the boxes the query reads POSITIONS
+ *             only: stale ages of such a ring STAY stale (nothing is written back), a deferred spin stays deferred -- a host that asks
+ *             every frame keeps every rule of an unread ring, the fusing of frames aside.
+ *   STREAM    both forms enqueue on the context's main stream (fw_ctx_stream), behind every fw_step called before and in front of
+ *             every one called after.  `places` and `volumes` are host memory, copied inside the call.  The device form's host work
+ *             grows with the listed particle types plus the volumes, never with the particles; it never waits -- with the ONE exception
+ *             fw_ctx_aabbs_device has: the tables and the scratch (4 bytes per volume and 512 particles of the listed types' bounds)
+ *             belong to the context and only grow, and a call that needs more than any call before it waits for the stream once and
+ *             reallocates.  d_out: n_places * n_volumes uint32, 4-byte aligned.  Two kernel launches per call whatever the sizes (one
+ *             where no listed type can hold a particle: the answer is all zeros).  The host form has the counts written to pinned
+ *             memory the context keeps, waits once and copies; it reports FW_ECAPACITY as fw_ctx_aabbs does.
+ *   ERRORS    all-or-nothing: a null context; null places, volumes or output with n_places * n_volumes != 0; ONE invalid handle; a type
+ *             that is neither -1 nor below its spawner's number of particle types; a kind that is none of the six; a misaligned d_out;
+ *             n_places * n_volumes > FW_VOLUME_MAX_ANSWERS (every answer is a one-wave workgroup of the second launch): FW_EINVAL,
+ *             nothing enqueued, nothing written.  n_places == 0 or n_volumes == 0: FW_OK, nothing touched.  A poisoned spawner in the
+ *             list ends the call as it ends fw_ctx_aabbs. */
+#define FW_VOLUME_MAX_ANSWERS 0x3FFFFFFull
+typedef struct fw_volume_place { /* 8 bytes */
+    fw_spawner spawner;
+    int32_t type; /* -1: every particle type of the spawner */
+} fw_volume_place;
+fw_status fw_ctx_count_in_volumes(fw_ctx *ctx, uint32_t n_places, const fw_volume_place *places, uint32_t n_volumes, const fw_collider *volumes,
+                                  uint32_t *out);
+fw_status fw_ctx_count_in_volumes_device(fw_ctx *ctx, uint32_t n_places, const fw_volume_place *places, uint32_t n_volumes,
+                                         const fw_collider *volumes, void *d_out);
+
 /* ---- whole-context statistics ---------------------------------------------------- */
 /* total live particles over all spawners (host value; synchronises) */
 fw_status fw_ctx_live_count(fw_ctx *ctx, uint64_t *out);

@@ -118,6 +118,12 @@ fw_status fw_debug_param_bar(fw_ctx *ctx, int32_t *on);
  * chunks -- waves of the first launch -- of the latest call; *chunk_size = list positions per chunk.  Any pointer may be null */
 fw_status fw_debug_aabb_batch(fw_ctx *ctx, uint64_t *launches, uint64_t *chunks, uint32_t *chunk_size);
 
+/* The volume queries (firework_hip.h: VOLUME QUERIES).  *launches = kernel launches fw_ctx_count_in_volumes and
+ * fw_ctx_count_in_volumes_device have enqueued so far: two per call whatever the sizes (one where no listed particle type can hold a
+ * particle); *chunks = the chunks -- waves of the first launch -- of the latest call; *chunk_size = list positions per chunk;
+ * *volume_tile = volumes per tile of the first launch.  Any pointer may be null */
+fw_status fw_debug_volume_query(fw_ctx *ctx, uint64_t *launches, uint64_t *chunks, uint32_t *chunk_size, uint32_t *volume_tile);
+
 #ifdef __cplusplus
 }
 #endif

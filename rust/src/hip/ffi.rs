@@ -90,6 +90,10 @@ pub struct fw_particle_instance {                      // == render::ParticleIns
 #[repr(C)] #[derive(Clone, Copy, Default)] pub struct fw_aabb {     // one box of fw_ctx_aabbs[_device] (32 bytes); any: 0 = no particle, reserved: written as 0
     pub min: [f32; 3], pub any: i32, pub max: [f32; 3], pub reserved: u32,
 }
+#[repr(C)] #[derive(Clone, Copy)] pub struct fw_volume_place {     // one place of fw_ctx_count_in_volumes[_device] (8 bytes); r#type: -1 = every particle type of the spawner
+    pub spawner: fw_spawner, pub r#type: i32,
+}
+pub const FW_VOLUME_MAX_ANSWERS: u64 = 0x3FF_FFFF;     // the most answers (n_places * n_volumes) of one volume query
 pub const FW_SORT_BACK_TO_FRONT: u32 = 0;
 pub const FW_SORT_FRONT_TO_BACK: u32 = 1;
 
@@ -146,6 +150,8 @@ extern "C" {
     pub fn fw_ctx_track_aabbs(ctx: *mut fw_ctx, enable: i32) -> c_int;
     pub fn fw_ctx_aabbs(ctx: *mut fw_ctx, n: u32, handles: *const fw_spawner, out: *mut fw_aabb) -> c_int;
     pub fn fw_ctx_aabbs_device(ctx: *mut fw_ctx, n: u32, handles: *const fw_spawner, d_out: *mut c_void) -> c_int;
+    pub fn fw_ctx_count_in_volumes(ctx: *mut fw_ctx, n_places: u32, places: *const fw_volume_place, n_volumes: u32, volumes: *const fw_collider, out: *mut u32) -> c_int;
+    pub fn fw_ctx_count_in_volumes_device(ctx: *mut fw_ctx, n_places: u32, places: *const fw_volume_place, n_volumes: u32, volumes: *const fw_collider, d_out: *mut c_void) -> c_int;
     pub fn fw_ctx_live_count(ctx: *mut fw_ctx, out: *mut u64) -> c_int;
     pub fn fw_ctx_live_count_device(ctx: *mut fw_ctx, d_out_u64: *mut c_void) -> c_int;
     pub fn fw_ctx_live_count_ring(ctx: *mut fw_ctx, d_ring_u64: *mut c_void, n_slots: u32) -> c_int;
