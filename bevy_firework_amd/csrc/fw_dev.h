@@ -469,6 +469,20 @@ __device__ __forceinline__ FwMove fw_move_step(const FwType &T, float dt, float4
     return o;
 }
 
+// ... with the four words of the type record it reads handed over by themselves (round 30: FwFuseArgs::move, the whole-tile arm of the fused
+// FIFO forms takes them from the kernel arguments): the same statements in the same order, the same bits
+struct FwMoveK {
+    float acc[3], lin_drag;
+};
+__device__ __forceinline__ FwMove fw_move_step(const FwMoveK &T, float dt, float4 q0, float4 q1) {
+    FwMove o;
+    o.px = q0.x + q1.x * dt, o.py = q0.y + q1.y * dt, o.pz = q0.z + q1.z * dt;
+    o.vx = q1.x + (T.acc[0] - q1.x * T.lin_drag) * dt;
+    o.vy = q1.y + (T.acc[1] - q1.y * T.lin_drag) * dt;
+    o.vz = q1.z + (T.acc[2] - q1.z * T.lin_drag) * dt;
+    return o;
+}
+
 // INPLACE (FIFO segments, fw_k_update_fifo): the output slot is the input slot, so a plane whose new value is
 // bit-identical to the loaded one for every lane of the wave is not written (rotation and angular velocity of particles
 // that do not spin, the scale under a constant curve); rotation and angular velocity, whose components are planes of their own, are

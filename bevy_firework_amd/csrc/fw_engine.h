@@ -460,6 +460,7 @@ struct alignas(64) SegHost {
     // many particles each update destroys -- always the oldest ones.
     uint32_t head = 0;
     float fifo_life = 0.f;  // the lifetime every particle of the type gets (core.rs:455 with min == max)
+    float fifo_move[4] = {0.f, 0.f, 0.f, 0.f};  // FwType::acc[0 .. 2] and lin_drag of the type: FwFuseArgs::move of the ring (round 30)
     int32_t fifo_wm = 0;    // FwFifoArgs::write_mask of the type
     // FW_TYPE_NOSPIN (fw_device.h): no particle of the type can turn; the rotation plane is neither read nor written
     bool nospin = false;

@@ -388,6 +388,7 @@ fw_status build_spawner(fw_ctx *ctx, int h, const fw_spawner_desc *d, const std:
                     if ((st = alloc_buf(ctx, S.h_report, kReportRing, Mem::pinned, true))) return st;
                 }
                 S.fifo_life = 0.0f * (p.lifetime.max - p.lifetime.min) + p.lifetime.min;  // u * (max - min) + min, any u
+                memcpy(S.fifo_move, p.acceleration, 3 * sizeof(float)), S.fifo_move[3] = p.linear_drag;  // (what the type's record holds, above)
                 S.fifo_wm = (T.base.kind != 0 ? 1 : 0) | (T.emis.kind != 0 ? 2 : 0) | (T.scale.kind != 0 ? 4 : 0);
                 // Position + age in four planes (SegHost::q0pl) -- the layout the age rule needs -- only for a ring that can ever run
                 // under it: fed by Global entries alone, no Nested entry on it, no collisions, and large enough by itself for a streaming

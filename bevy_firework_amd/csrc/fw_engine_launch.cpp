@@ -427,21 +427,22 @@ void group_launched(fw_ctx *ctx, const FwFifoLaunch &L) {
 }
 
 // fw_debug_whole_tiles: the ring tiles of a launch that is about to go to the stream which the predicate calls whole -- the kernel's own
-// lines (fw_fifo_tile_whole over the tiles FwFifoSeg lays out) and its own conditions (fw_update_fifo_body).  The workgroups of a FUSED
-// launch take the arm for exactly these tiles; an unfused launch's are counted too, and keep the streaming loop (the arm lost there)
+// predicate (fw_fifo_tile_whole over the tiles FwFifoSeg lays out, in the closed form fw_fifo_whole_span: no walk over the tiles, round 30)
+// and its own conditions (fw_update_fifo_body).  The workgroups of a FUSED launch take the arm for exactly these tiles; an unfused launch's
+// are counted too, and keep the streaming loop (the arm lost there)
 void count_whole_tiles(fw_ctx *ctx, const FwFifoArgs &fa) {
     if (!fa.fuse_pad[FW_FIFO_WHOLE] || fa.dbg != 0u) return;
     uint64_t n = 0;
     for (uint32_t j = 0; j < fa.n_segs; j++) {
         const FwFifoSeg &F = fa.s[j];
         if (F.mat) continue;
-        const uint32_t ring_tiles = F.capacity / FW_TILE, live_tiles = F.n_tiles - std::min(F.n_tiles, F.n_vt_a + F.n_vt_b);
-        for (uint32_t t = 0; t < live_tiles; t++)
-            n += fw_fifo_tile_whole(F.capacity, FW_TILE, F.head, F.n_in, F.dead, (F.tile0 + t) % ring_tiles) ? 1u : 0u;
+        // (the arm of the fused forms asks for the age rule too -- every ring of a fused launch is under it: ring_rules)
+        if (fa.fused >= 2u && !(F.type_idx & FW_TYPE_IDX_AGELESS)) continue;
+        const uint32_t live_tiles = F.n_tiles - std::min(F.n_tiles, F.n_vt_a + F.n_vt_b);
+        n += fw_fifo_whole_span(F.capacity, FW_TILE, F.head, F.n_in, F.dead, F.tile0, live_tiles).count;
     }
     ctx->whole_tiles += n, ctx->whole_launches += n ? 1u : 0u;
 }
-
 // fw_debug_newborn_spin: a launch that is about to go to the stream in which some ring's spawning workgroups defer the spin of what they
 // spawn -- the kernel's own condition (fw_update_fifo_body: nb_defer), from the kernel's own arguments
 void count_newborn(fw_ctx *ctx, const FwFifoArgs &fa) {
@@ -529,8 +530,7 @@ struct FifoAccum {
         fa.fuse_pad[FW_FIFO_WHOLE] = (ctx->use_whole_tiles && fa.spinless && derived && fa.write_mask == 0) ? 1u : 0u;
         // (... and whose spawning workgroups leave the spin of what they spawn into a deferring ring to its log: fw_spin_newborn_deferred)
         // (one rule for the whole context: a fused launch, every ring of which defers under it, takes the set of kernels the word names)
-        fa.fuse_pad[FW_FIFO_NEWBORN] = ctx->newborn_spin ? 0u : 1u;
-        L.nt = bytes > ctx->nt_bytes ? 2 : bytes > ctx->nt_wo_bytes ? 1 : 0;
+        fa.fuse_pad[FW_FIFO_NEWBORN] = ctx->newborn_spin ? 0u : 1u;        L.nt = bytes > ctx->nt_bytes ? 2 : bytes > ctx->nt_wo_bytes ? 1 : 0;
         // the frame's one launch, spin-less, every ring unread and large: it may wait for the next frame, or take the waiting one in
         const bool candidate = fw_fuse2_candidate(ctx->use_fuse2, quiet, n_launches == 0 && fa.n_segs == ctx->n_fifo, fa.spinless != 0u, fusable);
         // (how deep: two frames, or fw_ctx::fuse_depth where the pass dominates the launch -- beyond FW_FUSE_NARROW only where every ring
@@ -653,6 +653,8 @@ void ring_record(fw_ctx *ctx, const FifoFrame &ff, FifoAccum &acc, uint32_t si, 
     acc.deep &= in.n_in >= ctx->fuse_deep_min;
     acc.wide &= in.n_in >= ctx->fuse_wide_min;
     acc.L.spin_from[fa.n_segs] = R.spin_from_new;
+    // (acceleration and drag of the ring's type, for the whole tiles of a fused launch this frame may close: FwFuseArgs::move)
+    memcpy(acc.L.fz.move[fa.n_segs], S.fifo_move, sizeof S.fifo_move);
     FwFifoSeg &F = fa.s[fa.n_segs++];
     F.buf = S.buf[0], F.destroyed = S.destroyed, F.inst = S.inst;
     F.inst_cap = S.inst_cap, F.capacity = S.capacity, F.seg = si;

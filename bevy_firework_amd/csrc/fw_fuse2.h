@@ -6,8 +6,9 @@
 // frame: the withheld frames so far are ONE fused frame (fw_fuse2_frame, folded), and the pair rule between it and the next frame is the
 // rule of the group (FwFuseGroup, fw_fuse_push).  Here: what a launch lays out for a ring (the arithmetic launch_fifo has always done),
 // when a frame may join, and the fused frame with the per-frame boundaries the kernel needs.
-// Plain C++ behind FW_HD, like fw_spin.h: the host (launch_fifo) and four host tests (tests/test_cpp_host_fuse2.py, test_cpp_host_fuse_deep.py,
-// test_cpp_host_fuse_wide.py, test_cpp_host_whole_tiles.py) compile the same lines -- and so does the kernel, for fw_fifo_tile_whole (round 26).
+// Plain C++ behind FW_HD, like fw_spin.h: the host (launch_fifo) and five host tests (tests/test_cpp_host_fuse2.py, test_cpp_host_fuse_deep.py,
+// test_cpp_host_fuse_wide.py, test_cpp_host_whole_tiles.py, test_cpp_host_whole_span.py) compile the same lines -- and so does the kernel,
+// for fw_fifo_tile_whole (round 26).
 #pragma once
 #include <stdint.h>
 
@@ -60,6 +61,36 @@ FW_HD bool fw_fifo_tile_whole(uint32_t capacity, uint32_t tile, uint32_t head, u
     if (head > s0 && head - s0 < tile) return dead == 0u && n_in == capacity;
     const uint32_t i0 = s0 >= head ? s0 - head : s0 + (capacity - head);  // (<= capacity - tile)
     return i0 >= dead && i0 + tile <= n_in;
+}
+
+// The whole tiles of a launch without a walk over its tiles (round 30).  The ring tiles fw_fifo_tile_whole calls whole are ONE cyclic run of
+// tile indices: every tile of a full ring that loses nobody (the tile its head lies inside included); otherwise the tiles between the first
+// tile boundary at or behind slot head + dead and the last one at or before slot head + n_in -- the survivors' slots, counted past the
+// ring's end without wrapping; the head's own tile is never among them.  first / len: that run, ring tiles first, first + 1, ... (mod
+// capacity / tile); count: how many of them lie among the `live_tiles` ring tiles the launch dispatches from tile0 on (fw_fifo_layout) --
+// all of them where the layout starts at or in front of the first survivor, as every launch's does: a whole tile holds survivors alone.
+// (head < capacity, a multiple of `tile`; tile0 < capacity / tile; live_tiles <= capacity / tile)
+struct FwWholeSpan {
+    uint32_t count, first, len;
+};
+FW_HD uint32_t fw_overlap(uint32_t a0, uint32_t a1, uint32_t b0, uint32_t b1) {  // of [a0, a1) and [b0, b1)
+    const uint32_t lo = a0 > b0 ? a0 : b0, hi = a1 < b1 ? a1 : b1;
+    return hi > lo ? hi - lo : 0u;
+}
+FW_HD FwWholeSpan fw_fifo_whole_span(uint32_t capacity, uint32_t tile, uint32_t head, uint32_t n_in, uint32_t dead, uint32_t tile0, uint32_t live_tiles) {
+    FwWholeSpan W{0u, 0u, 0u};
+    const uint32_t ring_tiles = capacity / tile;
+    if (n_in > capacity || dead > n_in) return W;  // (a count only the device knows, FwFifoSeg::n_in = 0xFFFFFFFF: never whole)
+    if (dead == 0u && n_in == capacity) {
+        W.len = ring_tiles;
+    } else {
+        const uint64_t lo = ((uint64_t)head + dead + tile - 1u) / tile, hi = ((uint64_t)head + n_in) / tile;  // (fewer than ring_tiles apart)
+        W.first = (uint32_t)(lo % ring_tiles), W.len = hi > lo ? (uint32_t)(hi - lo) : 0u;
+    }
+    // the run as offsets from tile0, [off, off + len) with off < ring_tiles, against the dispatched offsets [0, live_tiles) and their next turn
+    const uint32_t off = W.first >= tile0 ? W.first - tile0 : W.first + (ring_tiles - tile0);
+    W.count = fw_overlap(off, off + W.len, 0u, live_tiles) + fw_overlap(off, off + W.len, ring_tiles, ring_tiles + live_tiles);
+    return W;
 }
 
 // Is a frame's launch one that may be withheld, or take the withheld one in?  enabled: fw_ctx::use_fuse2 (FW_FUSE2); quiet: the frame's only

@@ -257,7 +257,9 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
     const uint32_t C = F.capacity, ring_tiles = C / TILE;
     const uint32_t tis = blockIdx.x - F.tile_first;
     const uint32_t n_vt = F.n_vt_a + F.n_vt_b;
-    const bool spawner = tis < n_vt;  // a workgroup of new particles (they come first: the longest job starts earliest)
+    // a workgroup of new particles (they come first: the longest job starts earliest -- in the fused forms too: with the ring tiles in
+    // front of them a launch of eight frames was measured 5 % LONGER, round 30, profiles/r30/tiles_first_ab.txt)
+    const bool spawner = tis < n_vt;
     uint32_t pt = F.tile0 + (tis - n_vt);
     if (pt >= ring_tiles) pt -= ring_tiles;
     const uint32_t head = F.head, n_dead = F.dead;
@@ -279,12 +281,18 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
     // fw_fuse2.h; round 26) -- and which owes nothing but position, age and velocity: FwFifoArgs::fuse_pad[FW_FIFO_WHOLE] says
     // that every ring of the launch is of a FW_TYPE_DERIVED type (no optional plane is stored, whatever WM), the ring's new particles are
     // not materialised (so nobody is `full`, and `defer` is off), no profiling mode.  Workgroup-uniform, from the kernel arguments alone.
-    // Such a tile has no divergent lane: all of its loads are issued before anything else and none of its waits counts a store (below).
+    // Such a tile has no divergent lane: all of its loads are issued before anything else and none of its waits waits for a store (below).
     // The FUSED forms only: measured, the unfused spin-less forms lose 1.2 to 4.5 % with the arm (one frame of arithmetic per load is too
     // little to pay for giving up the loop's overlap of a round's stores with the next round's arithmetic: profiles/r26/whole_tiles_ab.txt)
+    // (round 30: ... and under the age rule, FW_TYPE_IDX_AGELESS -- as every ring of a fused launch is: the host withholds a frame only of
+    // rings that defer their spin in it, and only a ring under the age rule does (launch_fifo: ring_rules).  So the arm holds no age at
+    // all -- no load, no chain of additions, no store, none of the uniform branches around them -- and a tile that does keep its age,
+    // should a host ever fuse one, takes the streaming loop.)
     constexpr bool WT = SPINLESS && FUSE != 0;
     bool whole = false;
-    if constexpr (WT) whole = !spawner && a.fuse_pad[FW_FIFO_WHOLE] != 0u && F.mat == 0u && a.dbg == 0u && fw_fifo_tile_whole(C, TILE, head, F.n_in, n_dead, pt);
+    if constexpr (WT)
+        whole = !spawner && a.fuse_pad[FW_FIFO_WHOLE] != 0u && F.mat == 0u && a.dbg == 0u && (F.type_idx & FW_TYPE_IDX_AGELESS) != 0u &&
+                fw_fifo_tile_whole(C, TILE, head, F.n_in, n_dead, pt);
     // (a whole tile evaluates no curve: neither the keys nor the barrier)
     const float key0 = (!whole && tid < F.keys_len) ? g.keys[F.keys_off + tid] : 0.0f;
     char *buf = F.buf;
@@ -363,17 +371,87 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
         if (!nospin) v.w = fw_ld1w<NT == 2>(iw2 + 3 * cp, o16 / 4u);
         return v;
     };
-    // a whole tile: position (and age, where kept) of all R rounds, then the velocities -- 6 or 7 R loads in flight before anything else
-    float4 wq0[R], wq1[R];  // (nobody's registers in the other forms: `whole` is false when they are compiled)
+    // what thread 0 of the workgroup with tis == 0 of a FUSED launch leaves in the counters -- behind a whole tile's arm, which ends the
+    // workgroup (below), and at the end of everybody else's work.  oidx: the segment's slot in the counters' other row
+    auto publish_fused = [&](uint32_t oidx) {
+        if constexpr (FUSE != 0) {
+            // the counters as FUSE launches one after another would have left them: frame f reads row parity ^ (f & 1) -- the first
+            // frame's is the row checked above -- and writes the other, so the row the last frame wrote holds its count and the other one
+            // the count of the frame before it; the last frame's destroyed count; every frame's particles in the statistics
+            uint32_t nc_prev = n_in, nc = n_in, all_f = 0u, sp_done = 0u, dead_done = 0u;
+            unsigned long long all_sum = 0ull;
+#pragma unroll
+            for (int f = 0; f < FUSE; f++) {
+                const uint32_t sp_end = f < FUSE - 1 ? fz->spawn_end[j][f] : F.n_spawn;
+                const uint32_t dead_f = f < FUSE - 1 ? fz->dead[j][f] : n_dead - dead_done;
+                nc_prev = nc;
+                all_f = nc_prev + (sp_end - sp_done);
+                nc = all_f - min(dead_f, all_f);
+                sp_done = sp_end, dead_done += dead_f, all_sum += all_f;
+            }
+            const uint32_t last = (FUSE & 1) ? oidx : sidx, other = (FUSE & 1) ? sidx : oidx;  // (frame FUSE - 1 wrote `last`)
+            g.count[other] = nc_prev, g.count[last] = nc;
+            g.spawned[oidx] = 0, g.spawned[sidx] = 0;
+            g.appended[oidx] = 0, g.appended[sidx] = 0;
+            g.ndestroyed[F.seg] = all_f - nc;
+            if (a.host_counts) a.host_counts[F.seg] = ((unsigned long long)a.epoch << 32) | nc;
+            if (a.live_out) atomicAdd(a.live_out, (unsigned long long)nc);  // (the host fuses in no context that keeps a ring of live counts)
+            if (!FW_DBG(a.dbg, 128u)) atomicAdd(g.stats + (F.seg % FW_STAT_SLOTS), all_sum);
+        }
+    };
     if constexpr (WT) {
         if (whole) {
+            // ---- a WHOLE tile (round 26): every lane of every round is `mine` and not `dead`, so nothing diverges.  All of its loads are
+            // issued first; the rounds run unrolled -- the withheld frames through fw_move_step, the last frame through the same statements
+            // (what fw_integrate_store evaluates for a type that cannot turn and stores no optional plane; no contraction in this build:
+            // the same bits) -- and the stores are unconditional, in place and never waited for.
+            // (round 30: the tile's whole work stands HERE, in one stretch of code without a branch, in front of everything the other
+            // workgroups do, and ends the workgroup.  The loads are issued round by round -- position and velocity of round 0, then round
+            // 1's, ... --, and acceleration and drag come from the kernel arguments -- FwFuseArgs::move, the ring's row: scalars the wave
+            // has before any load lands; nothing of the type record is asked for.  The memory counter retires loads and stores in the
+            // order of issue, so round r waits for its own six loads with ONE counted wait that leaves the later rounds' loads, and the
+            // earlier rounds' stores, in flight.  With the loads in front of the branches below and the rounds behind them, as round 26
+            // had them, the loads met other paths' pending loads where the paths join, and the compiler's waits drained everything.  The
+            // tile is under the age rule -- `whole` asks for it --: no age is loaded, added up, tested or stored.)
+            if (blockIdx.x == 0 && tid == 0) {  // (the launch's first workgroup is a ring tile where no frame of the group spawns: its two words, as below)
+                if (a.live_next) *a.live_next = 0ull;
+                if (a.done_tag) *a.done_tag = a.done_value;
+            }
+            float4 wq0[R], wq1[R];
 #pragma unroll
-            for (int r = 0; r < R; r++) wq0[r] = ld0((uint32_t)(r * BLK + (int)tid) * 16u);
+            for (int r = 0; r < R; r++) {
+                const uint32_t b4 = (uint32_t)(r * BLK + (int)tid) * 4u;
+                wq0[r] = fw_ldc3w<NT == 2>(iw0, cp, b4, 0.0f);
+                wq1[r] = fw_ldc3w<NT == 2>(iw1, cp, b4, 0.0f);
+                __builtin_amdgcn_sched_barrier(0);  // (left alone, the scheduler issues rounds 1 to 3 plane by plane: round 1 then waits for nearly all)
+            }
+            const FwMoveK K{{fz->move[j][0], fz->move[j][1], fz->move[j][2]}, fz->move[j][3]};
+            char *ow0 = buf + FW_OFF_Q0(C) + sfirst / 4u, *ow1 = buf + FW_OFF_Q1(C) + sfirst / 4u;  // (fw_out_window's q0 / q1 of a ring with Q0 in planes)
 #pragma unroll
-            for (int r = 0; r < R; r++) wq1[r] = ld1((uint32_t)(r * BLK + (int)tid) * 16u);
+            for (int r = 0; r < R; r++) {
+                float4 q0w = wq0[r], q1w = wq1[r];
+#pragma unroll
+                for (int f = 0; f < FUSE - 1; f++) {
+                    const FwMove mv = fw_move_step(K, fz->dt_pre[f], q0w, q1w);
+                    q0w.x = mv.px, q0w.y = mv.py, q0w.z = mv.pz;
+                    q1w.x = mv.vx, q1w.y = mv.vy, q1w.z = mv.vz;
+                }
+                const FwMove mv = fw_move_step(K, a.dt, q0w, q1w);
+                // (the round's stores behind its arithmetic, and the rounds one after the other: the next round's wait counts them)
+                const uint32_t b4 = (uint32_t)(r * BLK + (int)tid) * 4u;
+                fw_stc3w<NT == 2>(ow0, cp, b4, mv.px, mv.py, mv.pz);
+                fw_stc3w<NT == 2>(ow1, cp, b4, mv.vx, mv.vy, mv.vz);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if (tis == 0 && tid == 0) {  // (the duties of the segment's first workgroup, as at the end of this function: not materialised, no Nested entry)
+                if (g.count[sidx] != n_in) fw_raise(g, 5u, F.seg, n_in);
+                if (F.report) *F.report = (unsigned long long)a.epoch << 32;
+                publish_fused((a.parity ^ 1u) * g.max_seg + F.seg);
+            }
+            return;
         }
     }
-    if (!spawner && !defer && !whole) {
+    if (!spawner && !defer) {
         q0c = ld0(tid * 16u), q3c = ld3(tid * 16u);
         q1c = ld1(tid * 16u), q2c = ld2(tid * 16u);
         if constexpr (R > 1) {
@@ -396,7 +474,7 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
         if (a.live_next) *a.live_next = 0ull;
         if (a.done_tag) *a.done_tag = a.done_value;
     }
-    FwType T = g.types[F.type_idx & FW_TYPE_IDX_MASK];
+    FwType T = g.types[F.type_idx & FW_TYPE_IDX_MASK];  // (a whole tile has left: it asks for nothing of the record)
     // (round 19: a ring whose spin this launch defers -- FW_TYPE_IDX_NOSPIN together with an axis, fw_device.h -- is a ring that cannot
     // turn to the tiles of the particles that were here before: nothing of Q2 / Q3 loaded above, and with the flag in the workgroup's
     // copy of the type record neither the window nor fw_integrate_store evaluates or stores any of it.  The spawning workgroups keep the
@@ -423,45 +501,9 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
     if constexpr (Q0PL && FUSE == 0) nb_defer = spawner && a.fuse_pad[FW_FIFO_NEWBORN] != 0u && (F.type_idx & FW_TYPE_IDX_NOSPIN) != 0u && axis != 0u && F.mat == 0u;
     const FwCollArm CA = fw_coll_arm<COLL>(g, F.type_idx & FW_TYPE_IDX_MASK);
     bool bad = false;
-    if (whole) {
-        // ---- a WHOLE tile (round 26): every lane of every round is `mine` and not `dead`, so nothing diverges.  The loads are all in flight
-        // (above); the rounds run unrolled -- the withheld frames through fw_move_step, the last frame through the same statements (what
-        // fw_integrate_store evaluates for a type that cannot turn and stores no optional plane; no contraction in this build: the same
-        // bits), the age chain and the `bad` test of the streaming loop -- and the stores, unconditional and in place, come behind the
-        // last round's arithmetic: every wait of the arm counts loads alone, and no wave waits for a store.  Here, in front of the
-        // spawning workgroups' code, so that the tile's 24 to 28 registers of data are nobody else's.
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            float4 q0w = wq0[r], q1w = wq1[r];
-            if constexpr (FUSE != 0) {
-#pragma unroll
-                for (int f = 0; f < FUSE - 1; f++) {
-                    const float dt_f = fz->dt_pre[f];
-                    const FwMove mv = fw_move_step(T, dt_f, q0w, q1w);
-                    q0w = make_float4(mv.px, mv.py, mv.pz, q0w.w + dt_f);
-                    q1w.x = mv.vx, q1w.y = mv.vy, q1w.z = mv.vz;
-                }
-            }
-            float age_new;
-            const bool surv = fw_survives(q0w.w, a.dt, q3s.w, &age_new);
-            bad |= !ageless && !surv;  // (mine, not dead: the host's cohort ages and the particle disagree)
-            const FwMove mv = fw_move_step(T, a.dt, q0w, q1w);
-            wq0[r] = make_float4(mv.px, mv.py, mv.pz, age_new);
-            wq1[r].x = mv.vx, wq1[r].y = mv.vy, wq1[r].z = mv.vz;
-        }
-        char *ow0 = buf + FW_OFF_Q0(C) + sfirst / 4u, *ow1 = buf + FW_OFF_Q1(C) + sfirst / 4u;  // (fw_out_window's q0 / q1 of a ring with Q0 in planes)
-#pragma unroll
-        for (int r = 0; r < R; r++) {
-            const uint32_t b4 = (uint32_t)(r * BLK + (int)tid) * 4u;
-            fw_stc3w<NT == 2>(ow0, cp, b4, wq0[r].x, wq0[r].y, wq0[r].z);
-            if (!ageless) fw_st1w<NT == 2>(ow0 + 3 * cp, b4, wq0[r].w);
-            fw_stc3w<NT == 2>(ow1, cp, b4, wq1[r].x, wq1[r].y, wq1[r].z);
-        }
-    } else {  // (workgroup-uniform)
-        if (tid < F.keys_len) s_keys[tid] = key0;
-        for (uint32_t i = tid + BLK; i < F.keys_len; i += BLK) s_keys[i] = g.keys[F.keys_off + i];
-        __syncthreads();
-    }
+    if (tid < F.keys_len) s_keys[tid] = key0;
+    for (uint32_t i = tid + BLK; i < F.keys_len; i += BLK) s_keys[i] = g.keys[F.keys_off + i];
+    __syncthreads();
     const bool want_destroyed = T.report_destroyed && F.destroyed != nullptr;
     if (!spawner && tis != 0u) {
         // a tile without a single particle (the grid of a segment whose count only the device knows covers its ring)
@@ -533,7 +575,7 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
         } else if (is_new && want_destroyed)  // born and destroyed in the same frame (dt >= lifetime)
             fw_store_destroyed(F.destroyed, buf, C, s, false, T, s_keys, so.q0, so.q1, so.q2, so.q3, age_new, i);
         fw_fifo_inst_out<INST, NT == 2>(F, inst, s_inst_wave, rec, lane, m, alive, i - n_dead);
-    } else if (!whole) {
+    } else {
         // (the record and the window a ring tile works with: the workgroup's own -- or, SPINLESS, copies in which "cannot turn" is known
         // when the tile's code is compiled: neither fw_integrate_store's spin nor a store to Q2 / Q3 is left in it)
         FwType Ts;
@@ -653,28 +695,7 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
         }
         if (F.report) *F.report = ((unsigned long long)a.epoch << 32) | added;
         if constexpr (FUSE != 0) {
-            // the counters as FUSE launches one after another would have left them: frame f reads row parity ^ (f & 1) -- the first
-            // frame's is the row checked above -- and writes the other, so the row the last frame wrote holds its count and the other one
-            // the count of the frame before it; the last frame's destroyed count; every frame's particles in the statistics
-            uint32_t nc_prev = n_in, nc = n_in, all_f = 0u, sp_done = 0u, dead_done = 0u;
-            unsigned long long all_sum = 0ull;
-#pragma unroll
-            for (int f = 0; f < FUSE; f++) {
-                const uint32_t sp_end = f < FUSE - 1 ? fz->spawn_end[j][f] : F.n_spawn;
-                const uint32_t dead_f = f < FUSE - 1 ? fz->dead[j][f] : n_dead - dead_done;
-                nc_prev = nc;
-                all_f = nc_prev + (sp_end - sp_done);
-                nc = all_f - min(dead_f, all_f);
-                sp_done = sp_end, dead_done += dead_f, all_sum += all_f;
-            }
-            const uint32_t last = (FUSE & 1) ? oidx : sidx, other = (FUSE & 1) ? sidx : oidx;  // (frame FUSE - 1 wrote `last`)
-            g.count[other] = nc_prev, g.count[last] = nc;
-            g.spawned[oidx] = 0, g.spawned[sidx] = 0;
-            g.appended[oidx] = 0, g.appended[sidx] = 0;
-            g.ndestroyed[F.seg] = all_f - nc;
-            if (a.host_counts) a.host_counts[F.seg] = ((unsigned long long)a.epoch << 32) | nc;
-            if (a.live_out) atomicAdd(a.live_out, (unsigned long long)nc);  // (the host fuses in no context that keeps a ring of live counts)
-            if (!FW_DBG(a.dbg, 128u)) atomicAdd(g.stats + (F.seg % FW_STAT_SLOTS), all_sum);
+            publish_fused(oidx);
             return;
         }
         const uint32_t nc = n_all - min(n_dead, n_all);

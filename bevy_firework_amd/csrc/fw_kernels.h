@@ -287,10 +287,16 @@ struct FwFuseArgs {
     uint32_t pad;
     uint32_t spawn_end[FW_FIFO_PER_LAUNCH][FW_FUSE_MAX - 1];
     uint32_t dead[FW_FIFO_PER_LAUNCH][FW_FUSE_MAX - 1];
+    // (round 30) per ring, the four words of its type's record a WHOLE ring tile computes with -- FwType::acc[0 .. 2], FwType::lin_drag:
+    // constants of the type, copied where the ring's record is built (ring_record, like FwFifoSeg::life) -- so that such a tile loads
+    // nothing of the record (fw_update_fifo_body: FwMoveK)
+    float move[FW_FIFO_PER_LAUNCH][4];
 };
 // (round 24, FW_FUSE_MAX = 8: 480 bytes.  The record is the LAST argument, so its size moves nobody else's; FW_INLINE_OPS stays 8 -- FwInlineOps
 // sits in front of it -- so a launch whose rings carry two ops per frame closes its groups at four frames: FwWithheld::join declines the fifth)
-static_assert(sizeof(FwFuseArgs) == 32 + 2 * FW_FIFO_PER_LAUNCH * (FW_FUSE_MAX - 1) * 4, "dt_pre and a pad word, then two tables of FW_FUSE_MAX - 1 words per ring");
+// (round 30: + 128 bytes, four words per ring)
+static_assert(sizeof(FwFuseArgs) == 32 + 2 * FW_FIFO_PER_LAUNCH * (FW_FUSE_MAX - 1) * 4 + FW_FIFO_PER_LAUNCH * 16,
+              "dt_pre and a pad word, two tables of FW_FUSE_MAX - 1 words per ring, four words per ring");
 static_assert(sizeof(FwGlobals) + sizeof(FwFifoArgs) + sizeof(FwInlineOps) + sizeof(FwFuseArgs) <= 4096, "the fused kernels' arguments fit the 4096-byte kernel-argument limit");
 
 // ---- range rings: particle types whose lifetime is a RANGE, updated in place ---------------------------------------

@@ -4,6 +4,7 @@
 // Plain host C++: no HIP call, nothing of the engine (fw_ctx, SegHost).  The engine (fw_engine_launch.cpp: launch_fifo, flush_withheld)
 // and a host test that drives the group through random hosts beside a model of its own (tests/test_cpp_host_withheld.py) compile the same lines.
 #pragma once
+#include <string.h>
 #include "fw_kernels.h"
 
 // one FIFO launch ready for the stream: the kernel's arguments and what the host books when it goes
@@ -91,8 +92,11 @@ private:
             grp[j] = grp_[j];
             if (!fw_fuse_push(F.capacity, grp[j], FwFifoFrame{F.head, F.n_in, F.n_spawn, F.dead})) return false;
         }
-        if (d >= 2u) B.fz = P.fz;
-        else B.fz = FwFuseArgs{};  // (one withheld frame: its record is unused, whatever it holds)
+        {
+            FwFuseArgs fz = d >= 2u ? P.fz : FwFuseArgs{};  // (one withheld frame: its record is unused, whatever it holds)
+            memcpy(fz.move, B.fz.move, sizeof fz.move);     // (... but for the rings' constants, which every frame's launch carries: B's own)
+            B.fz = fz;
+        }
         B.fz.dt_pre[d - 1u] = P.fa.dt;
         FwInlineOps ops;
         uint32_t n = 0, t = 0;
