@@ -358,6 +358,7 @@ SYMBOLS = [
     ("fw_debug_read_launches", C.c_int, [_P, _P, C.POINTER(C.c_uint32)]),
     ("fw_debug_read_range_timestamps", C.c_int, [_P, _P, C.c_uint64, C.POINTER(C.c_uint64)]),
     ("fw_debug_update_path", C.c_int, [_P, C.c_int, C.c_uint32, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    ("fw_debug_path_census", C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("fw_debug_nest_frames", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     ("fw_debug_param_bar", C.c_int, [_P, C.POINTER(C.c_int32)]),
     ("fw_debug_tile_scratch", C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
@@ -377,7 +378,7 @@ SYMBOLS = [
 ]
 
 # entry points added after round 4 (ABI 5 + a measurement hook): absent from the older builds the A/B tools load through FW_LIB_PATH
-NEWER_THAN_R04 = {"fw_debug_nest_frames", "fw_debug_param_bar", "fw_debug_tile_scratch", "fw_debug_recovered_rings", "fw_debug_tf_frames", "fw_debug_age_launches", "fw_debug_spin_launches", "fw_debug_spinless_launches", "fw_debug_whole_tiles", "fw_debug_newborn_spin", "fw_debug_fuse2", "fw_debug_fuse_frames", "fw_debug_aabb_batch", "fw_ctx_aabbs", "fw_ctx_aabbs_device", "fw_debug_volume_query", "fw_ctx_count_in_volumes", "fw_ctx_count_in_volumes_device", "fw_ctx_set_parent_velocities", "fw_ctx_set_modifiers", "fw_ctx_queue"}
+NEWER_THAN_R04 = {"fw_debug_path_census", "fw_debug_nest_frames", "fw_debug_param_bar", "fw_debug_tile_scratch", "fw_debug_recovered_rings", "fw_debug_tf_frames", "fw_debug_age_launches", "fw_debug_spin_launches", "fw_debug_spinless_launches", "fw_debug_whole_tiles", "fw_debug_newborn_spin", "fw_debug_fuse2", "fw_debug_fuse_frames", "fw_debug_aabb_batch", "fw_ctx_aabbs", "fw_ctx_aabbs_device", "fw_debug_volume_query", "fw_ctx_count_in_volumes", "fw_ctx_count_in_volumes_device", "fw_ctx_set_parent_velocities", "fw_ctx_set_modifiers", "fw_ctx_queue"}
 _lib = None
 
 

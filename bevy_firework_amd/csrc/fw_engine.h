@@ -54,6 +54,7 @@
 #include "fw_spin.h"
 #include "fw_fuse2.h"
 #include "fw_withheld.h"
+#include "fw_update_path.h"
 #include "fw_sort.h"
 #include "fw_boxes.h"
 #include "fw_volumes.h"
@@ -198,7 +199,6 @@ constexpr uint32_t kMinCapacity = 4096;
 constexpr uint32_t kNoSeg = 0xFFFFFFFFu;  // SpawnerHost::seg entry not built yet
 constexpr uint64_t kMaxSpawnPerOp = 1ull << 30;
 constexpr uint32_t kTimingEvents = 4096;
-constexpr uint32_t kMaxFifoSegs = FW_FIFO_PER_LAUNCH;  // FIFO segments per context: one launch (beyond: the general path)
 constexpr size_t kMaxCohorts = 16384;    // spawn cohorts a FIFO segment tracks before it gives the mode up (tiny dt)
 constexpr uint32_t kReportRing = 32768;  // pinned per-frame cohort sizes of a ring that receives Nested children (> kMaxCohorts)
 
@@ -422,7 +422,7 @@ struct alignas(64) SegHost {
     bool dead_at_end = false;   // the last step left this type's destroyed records at the END of its buffer (a range ring's
                                 // update fills them from there, the youngest dead first: fw_k_update_range)
     bool solo = false;          // a small type ONE Global entry feeds: its frame-begin work (lifetime window, bound) happens where
-                                // fw_step's spawner loop makes its op -- the record is streamed once per frame, not twice (fw_ctx::n_solo)
+                                // fw_step's spawner loop makes its op -- the record is streamed once per frame, not twice (FwPathCensus::n_solo)
     uint32_t capacity = 0;
     uint32_t ub = 0;            // upper bound of the device count (after this frame's spawns)
     uint32_t frame_spawn = 0;   // Global particles appended this frame
@@ -517,10 +517,10 @@ struct alignas(64) SegHost {
     };
     Ring<YCohort> ycoh;  // the young cohorts, oldest first
     bool few_ring = false;  // a range ring below fw_ctx::range_min: only because the context holds few segments (fw_ctx::range_few)
-    bool spilled = false;   // a range ring that qualifies for a FIFO ring: the context holds more such types than one FIFO launch (fw_ctx::n_spilled)
+    bool spilled = false;   // a range ring that qualifies for a FIFO ring: the context holds more such types than one FIFO launch (FwPathCensus::n_spilled)
     // A SMALL type (fw_k_small.hip, round 5): a few hundred particles, updated by ONE WAVE (four types per workgroup) instead of a
     // workgroup of the compacting kernels -- no tile table entry, no forecast.  Same buffers and layout as a compacting segment:
-    // entering and leaving the mode is this flag (fw_ctx::n_small, small_eligible / leave_small).
+    // entering and leaving the mode is this flag (FwPathCensus::n_small, small_eligible / leave_small).
     bool small = false;
     bool small_ok = false;    // ... qualifies for it (small_eligible); `small` follows the context's mode (fw_ctx::small_on)
     bool wide = false;        // ... as a WIDE type: up to a few thousand particles, a workgroup instead of a wave (fw_ctx::wide_max)
@@ -884,20 +884,20 @@ struct fw_ctx {
     // a mixed context run one after the other and a small ring costs a few microseconds more than it saves.
     uint32_t fifo_small_tiles = 384;  // FIFO launches of a context with fewer four-round tiles than this use one-round tiles (FW_FIFO_SMALL)
     uint32_t fifo_min = 32768;
-    uint32_t n_fifo = 0;       // FIFO segments in use (at most kMaxFifoSegs: their records travel in kernel arguments)
+    // The segments of the context by update path (fw_update_path.h: n_in_use, n_fifo, n_range, n_few, n_spilled, n_small, n_small_ok,
+    // n_small_coll, n_inst, n_solo and the few_blocked hysteresis).  Everybody reads its fields; it changes through SegPathEdit alone (below)
+    FwPathCensus census;
     // A context with MORE one-lifetime types than one FIFO launch holds (round 5).  The ninth used to land on a range ring next to
     // eight FIFO rings: two kinds of launch per frame, one after the other -- 9 emitters of 22 000 particles 20.7 us per frame
     // where nine range rings take 13.2 (profiles/r04/few_small_emitters.txt).  Now the type that does not fit takes a range ring
     // AND every FIFO ring of the context becomes one where it stands (fifo_to_range: no copy, particles and order kept; build time,
     // the context is synchronised): one kind of launch again.  While such rings exist, further one-lifetime types join them.
-    uint32_t n_spilled = 0;    // SegHost::spilled segments
     // ---- small types (SegHost::small): the wave-per-type kernel.  A type is one when it is built (or when it leaves a small ring:
     // drop_few_rings) if the emitters that feed it sustain at most small_max / 2 particles and nothing else claims it (no ring, no
     // Nested entry on or from it, no collisions, no instance buffer, no per-tile AABBs); it leaves for good when its live bound
     // passes small_max (it simply becomes a compacting segment: same buffers).  FW_SMALL=0 / FW_SMALL_MAX=n
     bool use_small = true;
     uint32_t small_max = 768;
-    uint32_t n_small = 0;
     // The kernel pays from a few hundred small types on: a wave walks its type's list round by round, ~15.6 us per launch whatever the
     // number of types up to ~600, where a workgroup per type (the compacting kernels) takes 11.9 us for 96 types, 14.3 for 256, 18.9
     // for 512 (profiles/r05/mid_emitters_paths.txt).  The context runs its eligible types (SegHost::small_ok, n_small_ok of them) on
@@ -930,9 +930,6 @@ struct fw_ctx {
     uint32_t wide_max = 2048;
     uint32_t n_narrow = 0;   // of small_list (narrow types first)
     uint32_t small_min = 352;
-    uint32_t n_small_ok = 0;
-    uint32_t n_inst = 0;     // segments with an instance buffer attached (SegHost::inst): which instantiation the small launch runs
-    uint32_t n_small_coll = 0;  // types on the kernel that have collision settings: its COLL instantiation
     // In frames that run the collision passes (materialise -> count -> scan -> update: four dependent launches on the main stream, 49 us
     // for a destroy_on_collision type of 20 000 particles) the small launch -- which touches nothing those passes touch -- runs next to
     // them on the ring stream (fifo_stream): 512 / 2048 small emitters next to such a type 66.9 / 84.3 -> 53.1 / 67.3 us per frame
@@ -951,7 +948,6 @@ struct fw_ctx {
     // became small, never before (the pass still owes it one ordinary frame begin).  FW_HOST_FAST=0: no solo segments, no ops
     // written in place (OpList).
     bool host_fast = true;
-    uint32_t n_solo = 0;
     std::vector<uint32_t> big_list;
     bool big_dirty = true;
     std::vector<uint32_t> small_list;   // the segments, ascending (rebuilt when small_dirty)
@@ -969,7 +965,6 @@ struct fw_ctx {
     uint32_t range_min = 8192;   // smallest capacity that makes one (FW_RANGE_MIN; the tests use 0): a range ring costs a
                                  // small segment three workgroups where the compacting path needs one.  Swept on many equal
                                  // emitters (profiles/r04/range_min_sweep.txt): 8192 is where the one-round tiles start to win
-    uint32_t n_range = 0;
     // A context with FEW segments -- the reference's own regime: examples/sparks.rs is one spawner of ~730 particles -- runs a small
     // type on a range ring too: one emitter of 733 particles 13.2 -> 9.1 us per frame, 8-64 such emitters 16 -> 10-11
     // (profiles/r04/few_small_emitters.txt), where with thousands of small emitters the compacting path wins (range_min above).
@@ -977,10 +972,6 @@ struct fw_ctx {
     // type becomes a range ring whatever its size (SegHost::few_ring); the spawner that takes the context past either condition
     // sends those rings to the compacting path (drop_few_rings: build time, the context is synchronised).  FW_RANGE_FEW; 0: off
     uint32_t range_few = 192;  // (64 until the range launch read its records from device memory: profiles/r05/mid_emitters_paths.txt)
-    uint32_t n_few = 0;     // SegHost::few_ring segments
-    bool few_blocked = false;  // the context has outgrown the rule: no new small rings until it is back at half of range_few (a
-                               // context whose spawners come and go around the limit would convert rings at every crossing)
-    uint32_t n_in_use = 0;  // SegHost::in_use segments
     // A range launch whose rings hold fewer than range_small_tiles four-round tiles in all (FW_RANGE_SMALL; not with a ring whose
     // count only the device knows), or with a colliding ring, runs on OLD / YOUNG tiles of ONE round (fw_k_update_range: TR): a
     // quarter of hysteresis, a change re-sends the table.
@@ -1165,6 +1156,39 @@ inline fw_status fail(fw_ctx *ctx, fw_status s, const std::string &msg) {
 }
 
 inline uint32_t round_up(uint32_t x, uint32_t m) { return (x + m - 1) / m * m; }
+
+// the device state changed under the host: the survivor forecast of the previous frame and the per-tile boxes describe it no longer
+inline void drop_forecast_and_boxes(fw_ctx *ctx) { ctx->fc_ok = false, ctx->boxes_epoch = 0; }
+
+// ---- which update path a segment is on (fw_update_path.h): the context's knobs as the rule reads them, a segment's share of the census,
+// and the ONE way that share changes
+inline FwPathPolicy path_policy(const fw_ctx *ctx) {
+    FwPathPolicy p;
+    p.use_fifo = ctx->use_fifo, p.fifo_min = ctx->fifo_min, p.fifo_nested = ctx->fifo_nested, p.fifo_small_tiles = ctx->fifo_small_tiles;
+    p.use_ageless = ctx->use_ageless, p.use_range = ctx->use_range, p.range_min = ctx->range_min, p.range_few = ctx->range_few;
+    return p;
+}
+inline uint32_t path_bits(const SegHost &S) {
+    return (S.in_use ? FW_PATH_IN_USE : 0u) | (S.fifo ? FW_PATH_FIFO : 0u) | (S.range ? FW_PATH_RANGE : 0u) | (S.few_ring ? FW_PATH_FEW_RING : 0u) |
+           (S.spilled ? FW_PATH_SPILLED : 0u) | (S.small ? FW_PATH_SMALL : 0u) | (S.small_ok ? FW_PATH_SMALL_OK : 0u) |
+           (S.collides ? FW_PATH_COLLIDES : 0u) | (S.inst != nullptr ? FW_PATH_INST : 0u) | (S.solo ? FW_PATH_SOLO : 0u);
+}
+// Whoever changes one of the SegHost flags path_bits reads does so inside the scope of one of these: the segment's share leaves the
+// census when the scope opens and comes back, as the flags then stand, when it closes -- on every way out, a failure's included, which is
+// what lets release_spawner_segments undo a build that stopped half-way.  Dirty flags (tab_force, r_force, ...) stay with the site.
+class SegPathEdit {
+public:
+    SegPathEdit(fw_ctx *ctx, const SegHost &S) : census_(ctx->census), S_(S) { (void)census_.remove(path_bits(S_)); }
+    SegPathEdit(const SegPathEdit &) = delete;
+    SegPathEdit &operator=(const SegPathEdit &) = delete;
+    ~SegPathEdit() { census_.add(path_bits(S_)); }
+
+private:
+    FwPathCensus &census_;
+    const SegHost &S_;
+};
+// ... but for fw_step's frame-begin pass, which makes a small type with one feeder a solo one (segment_pass): one increment
+inline void seg_becomes_solo(fw_ctx *ctx, SegHost &S) { S.solo = true, ctx->census.add(FW_PATH_SOLO); }
 
 // The one allocation call of the engine: `bytes` of `kind` memory (fw_ctx::fail_alloc: the `ab` build's simulated failure).
 inline hipError_t hip_alloc(fw_ctx *ctx, void **p, size_t bytes, Mem kind, const char **call) {
@@ -1373,7 +1397,7 @@ bool small_eligible(const fw_ctx *ctx, const SegHost &S);
 void enter_small(fw_ctx *ctx, SegHost &S);
 void leave_small(fw_ctx *ctx, SegHost &S);
 void update_small_mode(fw_ctx *ctx);
-void small_suspend(fw_ctx *ctx, SegHost &S);  // off the kernel, still eligible (a narrow type that became wide while wide_on is off)
+void small_deactivate(fw_ctx *ctx, SegHost &S);  // off the kernel, still eligible (update_small_mode; a narrow type that became wide while wide_on is off)
 fw_status drop_few_rings(fw_ctx *ctx);
 bool fifo_may_become_range(const fw_ctx *ctx, const SegHost &S);
 fw_status fifo_to_range(fw_ctx *ctx, uint32_t si);

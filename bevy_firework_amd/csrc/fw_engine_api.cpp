@@ -318,7 +318,7 @@ fw_status fw_ctx_set_colliders(fw_ctx *ctx, const fw_collider *colliders, uint32
     }
     ctx->n_colliders = n;
     ctx->g.n_colliders = n;
-    ctx->fc_ok = false, ctx->boxes_epoch = 0;
+    drop_forecast_and_boxes(ctx);
     return FW_OK;
 }
 
@@ -567,7 +567,7 @@ fw_status fw_spawner_write_particles(fw_ctx *ctx, fw_spawner h, uint32_t type, c
         return r.st;
     fw_status st;
     const uint32_t si = r.sp->seg[type];
-    ctx->fc_ok = false, ctx->boxes_epoch = 0;
+    drop_forecast_and_boxes(ctx);
     if ((st = fifo_to_general(ctx, si))) return st;  // ages and lifetimes will be whatever the caller writes
     leave_small(ctx, ctx->segs[si]);                  // (any number of particles, any colours: the compacting kernels take it from here)
     if ((st = leave_nospin(ctx, si))) return st;      // ... and so will rotations and angular velocities
@@ -664,8 +664,10 @@ static fw_status attach_instances(fw_ctx *ctx, fw_spawner h, uint32_t type, void
     }
     SegHost &S = ctx->segs[sp->seg[type]];
     // (a small type keeps its kernel: fw_k_update_small<INST> writes the records of its survivors itself)
-    ctx->n_inst += (d_out != nullptr ? 1u : 0u) - (S.inst != nullptr ? 1u : 0u);
-    S.inst = (char *)d_out;
+    {
+        SegPathEdit edit(ctx, S);
+        S.inst = (char *)d_out;
+    }
     S.inst_cap = d_out ? (uint32_t)std::min<uint64_t>(cap, 0xFFFFFFFFull) : 0u;
     S.inst_window = d_out != nullptr && window;
     if (S.range) ctx->r_force = true;  // (the range descriptors carry FW_TYPE_IDX_NOLIFE: derived AND no buffer attached)
@@ -1276,6 +1278,17 @@ fw_status fw_debug_spinless_launches(fw_ctx *ctx, uint64_t *n) {
     return FW_OK;
 }
 // spin-less FIFO launches so far in which the host's evaluation of fw_fifo_tile_whole found a whole ring tile, and those tiles
+fw_status fw_debug_path_census(fw_ctx *ctx, uint32_t *kept, uint32_t *recounted) {
+    if (!ctx) return FW_EINVAL;
+    if (kept) ctx->census.words(kept);
+    if (recounted) {
+        std::vector<uint32_t> bits;
+        for (const SegHost &S : ctx->segs) bits.push_back(path_bits(S));
+        FwPathCensus::recount(bits.data(), bits.size(), ctx->census.few_blocked).words(recounted);
+    }
+    return FW_OK;
+}
+
 fw_status fw_debug_whole_tiles(fw_ctx *ctx, uint64_t *launches, uint64_t *tiles) {
     if (!ctx) return FW_EINVAL;
     if (launches) *launches = ctx->whole_launches;

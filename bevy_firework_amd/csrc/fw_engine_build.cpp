@@ -188,282 +188,253 @@ bool axis_dt_ok(const SegHost &S, float dt) {
     return h2 < 0.6f && S.axis_drag * dt <= 1.0f;
 }
 
+// FW_TYPE_NOSPIN (fw_device.h): no particle of type t can ever turn -- no angular acceleration, a finite angular drag (0 * inf = NaN,
+// core.rs:648-650 would turn a zero angular velocity into NaN), and every entry that feeds the type spawns with zero angular velocity
+// and the same rotation, which const_rot receives
+static bool nospin_rule(const fw_spawner_desc *d, uint32_t t, float const_rot[4]) {
+    const fw_particle_settings &p = d->particle_settings[t];
+    if (!(p.angular_acceleration[0] == 0.f && p.angular_acceleration[1] == 0.f && p.angular_acceleration[2] == 0.f && std::isfinite(p.angular_drag)))
+        return false;
+    const fw_emission_settings *first = nullptr;
+    for (uint32_t i = 0; i < d->n_emission_settings; i++) {
+        const fw_emission_settings &e = d->emission_settings[i];
+        if ((uint32_t)e.particle_index != t) continue;
+        if (!(e.initial_angular_velocity.magnitude.min == 0.f && e.initial_angular_velocity.magnitude.max == 0.f &&
+              (!first || memcmp(first->initial_rotation, e.initial_rotation, sizeof e.initial_rotation) == 0)))
+            return false;
+        if (!first) first = &e;
+    }
+    if (!first) return false;
+    // (+ 0.0f: a negative zero component becomes +0, which is what from_scaled_axis(0) * rotation makes of it in all but contrived
+    // cases; every reader then sees the same bits)
+    for (int c = 0; c < 4; c++) const_rot[c] = first->initial_rotation[c] + 0.0f;
+    return true;
+}
+
 uint32_t pad4(uint32_t n) { return (n + 3u) & ~3u; }
 
-// builds the device tables (types, keys, emits, segments) of one spawner
-fw_status build_spawner(fw_ctx *ctx, int h, const fw_spawner_desc *d, const std::vector<uint64_t> *carry_serial) {
-    SpawnerHost &sp = ctx->spawners[h];
-    ctx->fc_ok = false, ctx->boxes_epoch = 0;
-    ctx->tab_force = true;
-    const uint32_t nt = d->n_particle_settings, ne = d->n_emission_settings;
-    sp.uid = d->uid;
-    sp.starts_enabled = d->starts_enabled;
-    if (ctx->levels.size() < d->n_emission_settings) ctx->levels.resize(d->n_emission_settings);
-    sp.types.assign(nt, TypeHost{});
-    sp.em.assign(ne, EmissionHost{});
-    sp.seg.assign(nt, kNoSeg);
+// ---- build_spawner: the device tables (types, keys, emits, segments) of one spawner, step by step.  The order of the device
+// allocations and copies is part of the contract: tests/test_gpu_resources.py walks FW_FAIL_ALLOC=k over it.
 
-    // a device table with room for `need` entries, the first `used` kept (amortised growth, zero-filled) and its FwGlobals view
-    auto reserve = [ctx](auto &b, size_t need, size_t used, auto **view) -> fw_status {
-        return need <= b.cap() ? FW_OK : grow_buf(ctx, b, std::max<size_t>(need, b.cap() * 2 + 64), true, used, view);
-    };
+// a device table with room for `need` entries, the first `used` kept (amortised growth, zero-filled) and its FwGlobals view
+template <typename B, typename V>
+static fw_status reserve_table(fw_ctx *ctx, B &b, size_t need, size_t used, V **view) {
+    return need <= b.cap() ? FW_OK : grow_buf(ctx, b, std::max<size_t>(need, b.cap() * 2 + 64), true, used, view);
+}
+
+// room in every table of the context for nt more types and ne more emission entries
+static fw_status reserve_tables(fw_ctx *ctx, uint32_t nt, uint32_t ne) {
+    if (ctx->levels.size() < ne) ctx->levels.resize(ne);
     fw_status st;
-    if ((st = reserve(ctx->d_types, ctx->n_types + nt, ctx->n_types, &ctx->g.types))) return st;
-    if ((st = reserve(ctx->d_type_coll, ctx->n_types + nt, ctx->n_types, &ctx->g.type_coll))) return st;
-    if ((st = reserve(ctx->d_emits, ctx->n_emits + ne, ctx->n_emits, &ctx->g.emits))) return st;
-    if ((st = reserve(ctx->d_emit_serial, ctx->n_emit_slots + ne, ctx->n_emit_slots, &ctx->g.emit_serial))) return st;
-    if ((st = reserve(ctx->d_nest_start, ctx->n_emit_slots + ne, ctx->n_emit_slots, &ctx->g.nest_start))) return st;
+    if ((st = reserve_table(ctx, ctx->d_types, ctx->n_types + nt, ctx->n_types, &ctx->g.types))) return st;
+    if ((st = reserve_table(ctx, ctx->d_type_coll, ctx->n_types + nt, ctx->n_types, &ctx->g.type_coll))) return st;
+    if ((st = reserve_table(ctx, ctx->d_emits, ctx->n_emits + ne, ctx->n_emits, &ctx->g.emits))) return st;
+    if ((st = reserve_table(ctx, ctx->d_emit_serial, ctx->n_emit_slots + ne, ctx->n_emit_slots, &ctx->g.emit_serial))) return st;
+    if ((st = reserve_table(ctx, ctx->d_nest_start, ctx->n_emit_slots + ne, ctx->n_emit_slots, &ctx->g.nest_start))) return st;
     if (ctx->nest_ticket_base.size() < ctx->n_emit_slots + ne) ctx->nest_ticket_base.resize(ctx->n_emit_slots + ne, 0u);
-    if ((st = reserve(ctx->d_segs, ctx->segs.size() + nt, ctx->segs.size(), &ctx->g.segs))) return st;
-    if ((st = ensure_max_seg(ctx, (uint32_t)ctx->segs.size() + nt))) return st;
+    if ((st = reserve_table(ctx, ctx->d_segs, ctx->segs.size() + nt, ctx->segs.size(), &ctx->g.segs))) return st;
+    return ensure_max_seg(ctx, (uint32_t)ctx->segs.size() + nt);
+}
 
-    std::vector<uint32_t> caps(nt, 0);
-    for (int pass = 0; pass < 2; pass++)
-        for (uint32_t t = 0; t < nt; t++) caps[t] = derive_capacity(d, t, caps);
+// what the steps of one type's build hand each other
+struct TypeBuild {
+    uint32_t t = 0, capacity = 0;
+    FwType dt{};
+    FwTypeColl dc{};
+    bool nospin = false, bigkeys = false;
+    std::vector<float> keys;
+    uint32_t type_idx = 0, keys_cap = 0;
+    uint32_t si = kNoSeg;
+};
 
-    for (uint32_t t = 0; t < nt; t++) {
-        TypeHost &T = sp.types[t];
-        const fw_particle_settings &p = d->particle_settings[t];
-        T.ps = p;
-        copy_curve(T.scale, p.scale_curve.kind, p.scale_curve.n, p.scale_curve.times, p.scale_curve.values, 1);
-        copy_curve(T.base, p.base_color.kind, p.base_color.n, p.base_color.times, p.base_color.rgba, 4);
-        copy_curve(T.emis, p.emissive_color.kind, p.emissive_color.n, p.emissive_color.times, p.emissive_color.rgba, 4);
-        T.life_lo_safe = (std::isfinite(p.lifetime.min) && std::isfinite(p.lifetime.max))
-                             ? std::nextafterf(std::nextafterf(std::min(p.lifetime.min, p.lifetime.max), -INFINITY), -INFINITY)
-                             : NAN;
-        T.ps.scale_curve.times = T.ps.scale_curve.values = nullptr;  // descriptors are copied, never kept
-        T.ps.base_color.times = T.ps.base_color.rgba = nullptr;
-        T.ps.emissive_color.times = T.ps.emissive_color.rgba = nullptr;
+// the host's copy of the type's settings (descriptors are copied, never kept) and the device records FwType / FwTypeColl, but for
+// what the next steps add: the key offsets, FW_TYPE_DERIVED
+static void make_type_records(const fw_ctx *ctx, const fw_spawner_desc *d, TypeHost &T, TypeBuild &b) {
+    const fw_particle_settings &p = d->particle_settings[b.t];
+    T.ps = p;
+    copy_curve(T.scale, p.scale_curve.kind, p.scale_curve.n, p.scale_curve.times, p.scale_curve.values, 1);
+    copy_curve(T.base, p.base_color.kind, p.base_color.n, p.base_color.times, p.base_color.rgba, 4);
+    copy_curve(T.emis, p.emissive_color.kind, p.emissive_color.n, p.emissive_color.times, p.emissive_color.rgba, 4);
+    T.life_lo_safe = fw_life_lo_safe(p.lifetime.min, p.lifetime.max);
+    T.ps.scale_curve.times = T.ps.scale_curve.values = nullptr;
+    T.ps.base_color.times = T.ps.base_color.rgba = nullptr;
+    T.ps.emissive_color.times = T.ps.emissive_color.rgba = nullptr;
 
-        FwType dt{};
-        memcpy(dt.acc, p.acceleration, sizeof dt.acc);
-        memcpy(dt.angacc, p.angular_acceleration, sizeof dt.angacc);
-        dt.lin_drag = p.linear_drag, dt.ang_drag = p.angular_drag;
-        dt.sc_kind = T.scale.kind, dt.sc_n = T.scale.n;
-        dt.bc_kind = T.base.kind, dt.bc_n = T.base.n;
-        dt.em_kind = T.emis.kind, dt.em_n = T.emis.n;
-        dt.pbr = p.pbr, dt.report_destroyed = p.report_destroyed;
-        // (angular_drag must be finite: 0 * inf = NaN, core.rs:648-650 would turn a zero angular velocity into NaN)
-        bool nospin = ctx->use_nospin && p.angular_acceleration[0] == 0.f && p.angular_acceleration[1] == 0.f &&
-                      p.angular_acceleration[2] == 0.f && std::isfinite(p.angular_drag);
-        {  // FW_TYPE_NOSPIN: every entry that feeds the type spawns with zero angular velocity and the same rotation
-            const fw_emission_settings *first = nullptr;
-            for (uint32_t i = 0; i < ne && nospin; i++) {
-                const fw_emission_settings &e = d->emission_settings[i];
-                if ((uint32_t)e.particle_index != t) continue;
-                nospin = e.initial_angular_velocity.magnitude.min == 0.f && e.initial_angular_velocity.magnitude.max == 0.f &&
-                         (!first || memcmp(first->initial_rotation, e.initial_rotation, sizeof e.initial_rotation) == 0);
-                if (!first) first = &e;
-            }
-            nospin = nospin && first != nullptr;
-            if (nospin) {
-                dt.flags |= FW_TYPE_NOSPIN;
-                // (+ 0.0f: a negative zero component becomes +0, which is what from_scaled_axis(0) * rotation makes of it in
-                // all but contrived cases; every reader then sees the same bits)
-                for (int c = 0; c < 4; c++) dt.const_rot[c] = first->initial_rotation[c] + 0.0f;
-            }
-        }
-        FwTypeColl dc{};
-        dc.coll_flags = (p.collision.enabled ? FW_COLL_ENABLED : 0u) |
-                        (p.collision.enabled && p.collision.destroy_on_collision ? FW_COLL_DESTROY : 0u);
-        dc.coll_mask = p.collision.filter_mask;
-        dc.coll_restitution = p.collision.restitution, dc.coll_friction = p.collision.friction;
-        std::vector<float> keys;
-        auto put = [&](const std::vector<float> &v, uint32_t padded) {
-            uint32_t off = (uint32_t)keys.size();
-            keys.insert(keys.end(), v.begin(), v.end());
-            keys.resize(off + padded, 0.f);
-            return off;
-        };
-        put(T.scale.times, pad4(T.scale.n));
-        dt.o_sc_v = put(T.scale.values, pad4(T.scale.n));
-        dt.o_bc_t = put(T.base.times, pad4(T.base.n));
-        dt.o_bc_v = put(T.base.values, 4 * T.base.n);
-        dt.o_em_t = put(T.emis.times, pad4(T.emis.n));
-        dt.o_em_v = put(T.emis.values, 4 * T.emis.n);
-        if (keys.size() >= (1u << 30)) return fail(ctx, FW_EINVAL, "curve keys exceed 2^30 floats");
-        const bool bigkeys = keys.size() > FW_KEYS_MAX;  // beyond the LDS staging area of the streaming kernels
-        uint32_t type_idx;
-        if (!ctx->free_types.empty()) {
-            type_idx = ctx->free_types.back();
-            ctx->free_types.pop_back();
-        } else {
-            type_idx = ctx->n_types++;
-        }
-        // a window of the key pool: the first released one that is large enough, or fresh floats at the end
-        uint32_t kwin_off = 0, kwin_cap = 0;
-        for (size_t fi = 0; fi < ctx->free_keys.size(); fi++)
-            if (ctx->free_keys[fi].second >= keys.size()) {
-                kwin_off = ctx->free_keys[fi].first, kwin_cap = ctx->free_keys[fi].second;
-                ctx->free_keys.erase(ctx->free_keys.begin() + (long)fi);
-                break;
-            }
-        if (!kwin_cap) {
-            kwin_cap = std::max<uint32_t>(64u, pad4((uint32_t)keys.size()));
-            if ((st = reserve(ctx->d_keys, ctx->keys_end + kwin_cap, ctx->keys_end, &ctx->g.keys))) return st;
-            kwin_off = (uint32_t)ctx->keys_end;
-            ctx->keys_end += kwin_cap;
-        }
-        dt.keys_off = kwin_off;
-        dt.keys_len = (uint32_t)keys.size();
-        // segment: the slot, its type index and the spawner's reference to it are recorded BEFORE anything that can
-        // fail, so that release_spawner_segments undoes a build that stops half-way (nothing leaks, nothing dangles)
-        uint32_t si = (uint32_t)ctx->segs.size();
-        for (uint32_t k = 0; k < ctx->segs.size(); k++)
-            if (!ctx->segs[k].in_use) {
-                si = k;
-                break;
-            }
-        if (si == ctx->segs.size()) ctx->segs.push_back(SegHost{});
-        SegHost &S = ctx->segs[si];
-        S = SegHost{};
-        S.in_use = true, S.spawner = h, S.type = (int)t, S.type_idx = type_idx;
-        ctx->n_in_use++, ctx->big_dirty = true;
-        S.keys_off = dt.keys_off, S.keys_len = dt.keys_len, S.keys_cap = kwin_cap, S.bigkeys = bigkeys;
-        S.nospin = nospin, S.n_xplanes = nospin ? 1u : 0u;
-        if (ctx->use_axis && !nospin) S.axis = axis_spin_rule(d, t, &S.axis_wmax), S.axis_drag = p.angular_drag;
-        if (type_idx > FW_TYPE_IDX_MASK) return fail(ctx, FW_EINVAL, "more particle types than a type index holds");
-        // scale and colours are left to the readers from the first frame on (fw_ctx::derive_all; wants_derived: not for a type that
-        // runs on the collision kernels)
-        S.derived = ctx->use_derived && ctx->derive_all && !(p.collision.enabled != 0 || bigkeys);
-        if (S.derived) dt.flags |= FW_TYPE_DERIVED;
-        memcpy(S.const_rot, dt.const_rot, sizeof S.const_rot);
-        sp.seg[t] = si;
-        FW_HIP(ctx, hipMemcpy(ctx->d_keys + dt.keys_off, keys.data(), keys.size() * sizeof(float),
-                              hipMemcpyHostToDevice));
-        FW_HIP(ctx, hipMemcpy(ctx->d_types + type_idx, &dt, sizeof dt, hipMemcpyHostToDevice));
-        FW_HIP(ctx, hipMemcpy(ctx->d_type_coll + type_idx, &dc, sizeof dc, hipMemcpyHostToDevice));
-        S.lplane_emission.clear();
-        for (uint32_t i = 0; i < ne; i++) {
-            const fw_emission_settings &e = d->emission_settings[i];
-            if (e.mode == FW_MODE_NESTED && (uint32_t)e.target_particle_type == t)
-                S.lplane_emission.push_back((int32_t)i), S.n_lplanes++;
-            if (e.mode == FW_MODE_NESTED && (uint32_t)e.particle_index == t) S.nested_fed = true;
-        }
-        S.auto_capacity = p.capacity == 0;
-        S.collides = p.collision.enabled != 0 || bigkeys;
-        S.coll_inplace = p.collision.enabled != 0 && p.collision.destroy_on_collision == 0 && !bigkeys;
-        S.life_bound = (double)std::max(p.lifetime.min, p.lifetime.max);  // lifetime = lerp(min, max, u), u in [0, 1)
-        S.win_ok = !S.nested_fed && std::isfinite(S.life_bound);
-        {  // FIFO ring (SegHost::fifo): one lifetime value, no collisions; spawners whose particles emit onto their own
-            // type stay on the general path (a parent would see this frame's children as parents)
-            // ... and so does a type that receives Nested children AND Global particles (its Global particles would have to be
-            // placed behind a live count only the device knows)
-            bool any_nested = false, self_nested = false, mixed_feed = false;
-            uint32_t n_global_feed = 0;  // Global entries that feed the type: each may add one op to a frame
-            for (uint32_t i = 0; i < ne; i++) {
-                const fw_emission_settings &e = d->emission_settings[i];
-                n_global_feed += (e.mode == FW_MODE_GLOBAL && (uint32_t)e.particle_index == t) ? 1u : 0u;
-                any_nested |= e.mode == FW_MODE_NESTED;
-                self_nested |= e.mode == FW_MODE_NESTED && e.target_particle_type == e.particle_index;
-                mixed_feed |= S.nested_fed && e.mode == FW_MODE_GLOBAL && (uint32_t)e.particle_index == t;
-            }
-            // (a ring's spawn ops of a frame travel in the kernel arguments of its launch -- FwInlineOps, FW_INLINE_OPS of
-            // them: a type fed by more Global entries than that takes the range or the compacting path, whose tiles read op
-            // tables from memory)
-            S.fifo = ctx->use_fifo && !sp.no_rings && !self_nested && !mixed_feed && (!S.collides || S.coll_inplace) && p.lifetime.min == p.lifetime.max &&
-                     n_global_feed <= FW_INLINE_OPS &&
-                     std::isfinite(p.lifetime.min) &&
-                     caps[t] >= ctx->fifo_min && caps[t] < 0x40000000u &&  // (head + index stays far from 2^32)
-                     (!any_nested || ctx->fifo_nested);
-            // more such types than one FIFO launch holds (fw_ctx::n_spilled): this one takes a range ring -- if it qualifies for
-            // one: the rule below -- and the FIFO rings of the context follow it at the end of the build
-            const bool spill = S.fifo && (ctx->n_spilled != 0 || ctx->n_fifo >= kMaxFifoSegs);
-            if (spill) S.fifo = false;
-            // (fw_ctx::range_few) the capacity of a type that receives Nested children is derived from its parents' CAPACITY -- the
-            // host cannot bound their number -- and passes fifo_min for a handful of parents already (examples/textures.rs: 55
-            // bullet cases, 110 puffs, 32 768 slots): in a context of few segments such a type stays with its small parent type on
-            // range rings (one kind of launch per frame) unless its derived capacity is really large
-            bool few_nested = false;  // ... a range ring only because of that: it leaves with the other small rings (drop_few_rings)
-            if (S.fifo && S.nested_fed && ctx->use_range && ctx->range_few != 0 && !ctx->few_blocked && ctx->n_in_use <= ctx->range_few && ctx->n_fifo == 0 &&
-                caps[t] < 8u * ctx->fifo_min && caps[t] < ctx->range_min * 32u &&
-                S.n_lplanes <= 2 && T.life_lo_safe > 0.0f && caps[t] <= FW_RANGE_MAX_CAPACITY)  // (it does qualify for a range ring)
-                S.fifo = false, few_nested = true;
-            if (S.fifo) {
-                ctx->n_fifo++;
-                S.win_ok = false;
-                S.fifo_mat = any_nested;
-                S.fifo_dev = S.nested_fed;
-                if (S.fifo_dev) {
-                    if ((st = alloc_buf(ctx, S.h_report, kReportRing, Mem::pinned, true))) return st;
-                }
-                S.fifo_life = 0.0f * (p.lifetime.max - p.lifetime.min) + p.lifetime.min;  // u * (max - min) + min, any u
-                memcpy(S.fifo_move, p.acceleration, 3 * sizeof(float)), S.fifo_move[3] = p.linear_drag;  // (what the type's record holds, above)
-                S.fifo_wm = (T.base.kind != 0 ? 1 : 0) | (T.emis.kind != 0 ? 2 : 0) | (T.scale.kind != 0 ? 4 : 0);
-                // Position + age in four planes (SegHost::q0pl) -- the layout the age rule needs -- only for a ring that can ever run
-                // under it: fed by Global entries alone, no Nested entry on it, no collisions, and large enough by itself for a streaming
-                // launch (fw_ctx::fifo_small_tiles).  Everybody else keeps the float4: four dword accesses where one dwordx4 did cost
-                // the one-round and the Nested launches 1.5-1.8 % (profiles/r18/ageless_ab.txt).  Decided once, here.
-                S.q0pl = ctx->use_ageless && ctx->fifo_small_tiles != 0u && !any_nested && !S.nested_fed && S.n_lplanes == 0 && !S.collides &&
-                         (uint64_t)caps[t] >= (uint64_t)ctx->fifo_small_tiles * FW_TILE;
-            }
-            // Range ring (SegHost::range): any finite lifetime range -- a single value included, for the types the eight
-            // FIFO records of a launch have no room for -- in a spawner without Nested entries; the young part of the
-            // list is updated in place, only the part that can lose particles this frame is compacted
-            // In a spawner WITH Nested entries (round 4): types other particles' entries emit FROM (range_mat: fw_k_spawn /
-            // fw_k_nest address their particles by list index through the size of the old part, which the device keeps --
-            // FwGlobals::rold) and types that RECEIVE children (range_dev: the device alone knows their count) qualify too;
-            // as for FIFO rings, not a type that emits onto itself, nor one that receives children AND Global particles; at
-            // most two last_emitted_age planes (the old tiles carry them in registers).
-            S.range = ctx->use_range && !sp.no_rings && !S.fifo && !self_nested && !mixed_feed && S.n_lplanes <= 2 &&
-                      (!S.collides || S.coll_inplace) && std::isfinite(p.lifetime.min) &&
-                      std::isfinite(p.lifetime.max) && T.life_lo_safe > 0.0f &&
-                      (caps[t] >= ctx->range_min || (ctx->range_few != 0 && !ctx->few_blocked && ctx->n_in_use <= ctx->range_few && ctx->n_fifo == 0)) &&
-                      caps[t] <= FW_RANGE_MAX_CAPACITY;
-            if (S.range) {
-                if (caps[t] < ctx->range_min || few_nested) S.few_ring = true, ctx->n_few++;  // (fw_ctx::range_few)
-                if (spill) S.spilled = true, ctx->n_spilled++;
-                ctx->n_range++;
-                S.range_life_lo = T.life_lo_safe;
-                ctx->range_life_max = std::max(ctx->range_life_max, S.range_life_lo);
-                ctx->r_force = true;
-                S.range_mat = S.n_lplanes != 0;
-                S.range_dev = S.nested_fed;
-                if (S.range_dev) {
-                    S.win_ok = false;
-                    ctx->range_age_keep = std::max(ctx->range_age_keep, (float)(S.life_bound * 1.01 + 1e-3));
-                    if ((st = alloc_buf(ctx, S.h_report, kReportRing, Mem::pinned, true))) return st;
-                }
-            }
-        }
-        for (int c = 0; c < 4; c++) {  // the first key is the colour at age 0 (and, for one key, at every age)
-            S.fill_bc[c] = T.base.values.empty() ? 0.f : T.base.values[c];
-            S.fill_em[c] = T.emis.values.empty() ? 0.f : T.emis.values[c];
-        }
-        S.colors_dirty = false;
-        {
-            double expect = 0.0;
-            derive_capacity(d, t, caps, &expect);
-            S.expect_live = (float)std::min(expect, 3.0e9);
-            uint32_t feeders = 0, global_feeders = 0;
-            for (uint32_t i = 0; i < d->n_emission_settings; i++)
-                if ((uint32_t)d->emission_settings[i].particle_index == t) feeders++, global_feeders += d->emission_settings[i].mode == FW_MODE_GLOBAL ? 1u : 0u;
-            S.one_feeder = feeders == 1 && global_feeders == 1;
-        }
-        {
-            SegBufs nb;
-            if ((st = alloc_seg_buffers(ctx, S, caps[t], S.ring(), p.report_destroyed != 0, nb))) return st;
-            S.take(std::move(nb));
-        }
-        if (small_eligible(ctx, S)) enter_small(ctx, S);  // (fw_ctx::n_small: the wave-per-type kernel)
-        if ((st = upload_seg(ctx, si))) return st;
-        const uint32_t zero2[2] = {0, 0};
-        for (int r = 0; r < 2; r++) {
-            FW_HIP(ctx, hipMemcpy(ctx->g.count + (size_t)r * ctx->max_seg + si, zero2, 4, hipMemcpyHostToDevice));
-            FW_HIP(ctx, hipMemcpy(ctx->g.spawned + (size_t)r * ctx->max_seg + si, zero2, 4, hipMemcpyHostToDevice));
-            FW_HIP(ctx, hipMemcpy(ctx->g.appended + (size_t)r * ctx->max_seg + si, zero2, 4, hipMemcpyHostToDevice));
-            FW_HIP(ctx, hipMemcpy(ctx->g.rold + (size_t)r * ctx->max_seg + si, zero2, 4, hipMemcpyHostToDevice));
-        }
-        FW_HIP(ctx, hipMemcpy(ctx->g.ndestroyed + si, zero2, 4, hipMemcpyHostToDevice));
-        FW_HIP(ctx, hipMemcpy(ctx->g.range_ticket + si, zero2, 4, hipMemcpyHostToDevice));  // (S.ticket_base is 0: a fresh SegHost)
+    FwType &dt = b.dt;
+    memcpy(dt.acc, p.acceleration, sizeof dt.acc);
+    memcpy(dt.angacc, p.angular_acceleration, sizeof dt.angacc);
+    dt.lin_drag = p.linear_drag, dt.ang_drag = p.angular_drag;
+    dt.sc_kind = T.scale.kind, dt.sc_n = T.scale.n;
+    dt.bc_kind = T.base.kind, dt.bc_n = T.base.n;
+    dt.em_kind = T.emis.kind, dt.em_n = T.emis.n;
+    dt.pbr = p.pbr, dt.report_destroyed = p.report_destroyed;
+    b.nospin = ctx->use_nospin && nospin_rule(d, b.t, dt.const_rot);
+    if (b.nospin) dt.flags |= FW_TYPE_NOSPIN;
+    b.dc.coll_flags = (p.collision.enabled ? FW_COLL_ENABLED : 0u) | (p.collision.enabled && p.collision.destroy_on_collision ? FW_COLL_DESTROY : 0u);
+    b.dc.coll_mask = p.collision.filter_mask;
+    b.dc.coll_restitution = p.collision.restitution, b.dc.coll_friction = p.collision.friction;
+}
+
+// the curve keys of the type, packed; a type index (a released one first) and a window of the key pool: the first released one that
+// is large enough, or fresh floats at the end
+static fw_status pack_keys_take_window(fw_ctx *ctx, const TypeHost &T, TypeBuild &b) {
+    std::vector<float> &keys = b.keys;
+    FwType &dt = b.dt;
+    auto put = [&](const std::vector<float> &v, uint32_t padded) {
+        uint32_t off = (uint32_t)keys.size();
+        keys.insert(keys.end(), v.begin(), v.end());
+        keys.resize(off + padded, 0.f);
+        return off;
+    };
+    put(T.scale.times, pad4(T.scale.n));
+    dt.o_sc_v = put(T.scale.values, pad4(T.scale.n));
+    dt.o_bc_t = put(T.base.times, pad4(T.base.n));
+    dt.o_bc_v = put(T.base.values, 4 * T.base.n);
+    dt.o_em_t = put(T.emis.times, pad4(T.emis.n));
+    dt.o_em_v = put(T.emis.values, 4 * T.emis.n);
+    if (keys.size() >= (1u << 30)) return fail(ctx, FW_EINVAL, "curve keys exceed 2^30 floats");
+    b.bigkeys = keys.size() > FW_KEYS_MAX;  // beyond the LDS staging area of the streaming kernels
+    if (!ctx->free_types.empty()) {
+        b.type_idx = ctx->free_types.back();
+        ctx->free_types.pop_back();
+    } else {
+        b.type_idx = ctx->n_types++;
     }
+    uint32_t kwin_off = 0;
+    for (size_t fi = 0; fi < ctx->free_keys.size(); fi++)
+        if (ctx->free_keys[fi].second >= keys.size()) {
+            kwin_off = ctx->free_keys[fi].first, b.keys_cap = ctx->free_keys[fi].second;
+            ctx->free_keys.erase(ctx->free_keys.begin() + (long)fi);
+            break;
+        }
+    if (!b.keys_cap) {
+        b.keys_cap = std::max<uint32_t>(64u, pad4((uint32_t)keys.size()));
+        if (fw_status st = reserve_table(ctx, ctx->d_keys, ctx->keys_end + b.keys_cap, ctx->keys_end, &ctx->g.keys)) return st;
+        kwin_off = (uint32_t)ctx->keys_end;
+        ctx->keys_end += b.keys_cap;
+    }
+    dt.keys_off = kwin_off;
+    dt.keys_len = (uint32_t)keys.size();
+    return FW_OK;
+}
 
-    for (uint32_t i = 0; i < ne; i++) {
+// The segment: the slot, its type index, its key window and the spawner's reference to it are recorded BEFORE anything that can fail,
+// so that release_spawner_segments undoes a build that stops half-way (nothing leaks, nothing dangles).  Then what the type's records
+// say of the segment, and the records themselves go to the device.
+static fw_status take_segment_slot(fw_ctx *ctx, SpawnerHost &sp, int h, const fw_spawner_desc *d, TypeBuild &b) {
+    const fw_particle_settings &p = d->particle_settings[b.t];
+    FwType &dt = b.dt;
+    uint32_t si = (uint32_t)ctx->segs.size();
+    for (uint32_t k = 0; k < ctx->segs.size(); k++)
+        if (!ctx->segs[k].in_use) {
+            si = k;
+            break;
+        }
+    if (si == ctx->segs.size()) ctx->segs.push_back(SegHost{});
+    SegHost &S = ctx->segs[si];
+    {
+        SegPathEdit edit(ctx, S);
+        S = SegHost{};
+        S.in_use = true, S.spawner = h, S.type = (int)b.t, S.type_idx = b.type_idx;
+    }
+    ctx->big_dirty = true;
+    S.keys_off = dt.keys_off, S.keys_len = dt.keys_len, S.keys_cap = b.keys_cap, S.bigkeys = b.bigkeys;
+    sp.seg[b.t] = b.si = si;
+    S.nospin = b.nospin, S.n_xplanes = b.nospin ? 1u : 0u;
+    if (ctx->use_axis && !b.nospin) S.axis = axis_spin_rule(d, b.t, &S.axis_wmax), S.axis_drag = p.angular_drag;
+    if (b.type_idx > FW_TYPE_IDX_MASK) return fail(ctx, FW_EINVAL, "more particle types than a type index holds");
+    // scale and colours are left to the readers from the first frame on (fw_ctx::derive_all; wants_derived: not for a type that
+    // runs on the collision kernels)
+    S.derived = ctx->use_derived && ctx->derive_all && !(p.collision.enabled != 0 || b.bigkeys);
+    if (S.derived) dt.flags |= FW_TYPE_DERIVED;
+    memcpy(S.const_rot, dt.const_rot, sizeof S.const_rot);
+    FW_HIP(ctx, hipMemcpy(ctx->d_keys + dt.keys_off, b.keys.data(), b.keys.size() * sizeof(float), hipMemcpyHostToDevice));
+    FW_HIP(ctx, hipMemcpy(ctx->d_types + b.type_idx, &dt, sizeof dt, hipMemcpyHostToDevice));
+    FW_HIP(ctx, hipMemcpy(ctx->d_type_coll + b.type_idx, &b.dc, sizeof b.dc, hipMemcpyHostToDevice));
+    return FW_OK;
+}
+
+// Which update path the type runs on: the rule (fw_update_path.h: fw_choose_path, from the knobs, the census as it stands -- this
+// segment counted as in use, its path not yet -- and the facts of the type) and what the choice means for the segment and the context
+static fw_status choose_segment_path(fw_ctx *ctx, const SpawnerHost &sp, const fw_spawner_desc *d, const TypeBuild &b) {
+    const fw_particle_settings &p = d->particle_settings[b.t];
+    const TypeHost &T = sp.types[b.t];
+    SegHost &S = ctx->segs[b.si];
+    const FwTypeFacts f = fw_type_facts(d, b.t, b.capacity, b.bigkeys, sp.no_rings);
+    const FwPathChoice c = fw_choose_path(path_policy(ctx), ctx->census, f);
+    for (uint32_t i = 0; i < d->n_emission_settings; i++)  // the emission entry each last_emitted_age plane belongs to
+        if (d->emission_settings[i].mode == FW_MODE_NESTED && (uint32_t)d->emission_settings[i].target_particle_type == b.t)
+            S.lplane_emission.push_back((int32_t)i);
+    S.auto_capacity = p.capacity == 0;
+    S.life_bound = (double)fw_life_bound(p.lifetime.min, p.lifetime.max);
+    S.one_feeder = f.n_feeders == 1 && f.n_global_feed == 1;
+    fw_status st;
+    SegPathEdit edit(ctx, S);
+    S.n_lplanes = f.n_lplanes, S.nested_fed = f.nested_fed, S.collides = f.collides, S.coll_inplace = f.coll_inplace;
+    S.fifo = c.fifo, S.range = c.range, S.few_ring = c.few_ring, S.spilled = c.spilled;
+    S.fifo_mat = c.fifo_mat, S.fifo_dev = c.fifo_dev, S.range_mat = c.range_mat, S.range_dev = c.range_dev;
+    S.q0pl = c.q0pl, S.win_ok = c.win_ok;
+    if (S.fifo) {
+        if (S.fifo_dev && (st = alloc_buf(ctx, S.h_report, kReportRing, Mem::pinned, true))) return st;
+        S.fifo_life = 0.0f * (p.lifetime.max - p.lifetime.min) + p.lifetime.min;  // u * (max - min) + min, any u
+        memcpy(S.fifo_move, p.acceleration, 3 * sizeof(float)), S.fifo_move[3] = p.linear_drag;  // (what the type's record holds)
+        S.fifo_wm = (T.base.kind != 0 ? 1 : 0) | (T.emis.kind != 0 ? 2 : 0) | (T.scale.kind != 0 ? 4 : 0);
+    }
+    if (S.range) {
+        S.range_life_lo = T.life_lo_safe;
+        ctx->range_life_max = std::max(ctx->range_life_max, S.range_life_lo);
+        ctx->r_force = true;
+        if (S.range_dev) {
+            ctx->range_age_keep = std::max(ctx->range_age_keep, (float)(S.life_bound * 1.01 + 1e-3));
+            if ((st = alloc_buf(ctx, S.h_report, kReportRing, Mem::pinned, true))) return st;
+        }
+    }
+    return FW_OK;
+}
+
+// the particle memory of the segment, and what the host keeps next to it: the colours its planes are filled with, what its emitters
+// sustain; a small type joins the wave-per-type kernel
+static fw_status alloc_type_buffers(fw_ctx *ctx, const SpawnerHost &sp, const fw_spawner_desc *d, const std::vector<uint32_t> &caps, const TypeBuild &b) {
+    const TypeHost &T = sp.types[b.t];
+    SegHost &S = ctx->segs[b.si];
+    for (int c = 0; c < 4; c++) {  // the first key is the colour at age 0 (and, for one key, at every age)
+        S.fill_bc[c] = T.base.values.empty() ? 0.f : T.base.values[c];
+        S.fill_em[c] = T.emis.values.empty() ? 0.f : T.emis.values[c];
+    }
+    S.colors_dirty = false;
+    double expect = 0.0;
+    derive_capacity(d, b.t, caps, &expect);
+    S.expect_live = (float)std::min(expect, 3.0e9);
+    SegBufs nb;
+    if (fw_status st = alloc_seg_buffers(ctx, S, b.capacity, S.ring(), d->particle_settings[b.t].report_destroyed != 0, nb)) return st;
+    S.take(std::move(nb));
+    if (small_eligible(ctx, S)) enter_small(ctx, S);  // (the wave-per-type kernel)
+    return FW_OK;
+}
+
+// the segment's record goes to the device; its counters start at zero
+static fw_status upload_segment_zeroed(fw_ctx *ctx, uint32_t si) {
+    if (fw_status st = upload_seg(ctx, si)) return st;
+    const uint32_t zero2[2] = {0, 0};
+    for (int r = 0; r < 2; r++) {
+        FW_HIP(ctx, hipMemcpy(ctx->g.count + (size_t)r * ctx->max_seg + si, zero2, 4, hipMemcpyHostToDevice));
+        FW_HIP(ctx, hipMemcpy(ctx->g.spawned + (size_t)r * ctx->max_seg + si, zero2, 4, hipMemcpyHostToDevice));
+        FW_HIP(ctx, hipMemcpy(ctx->g.appended + (size_t)r * ctx->max_seg + si, zero2, 4, hipMemcpyHostToDevice));
+        FW_HIP(ctx, hipMemcpy(ctx->g.rold + (size_t)r * ctx->max_seg + si, zero2, 4, hipMemcpyHostToDevice));
+    }
+    FW_HIP(ctx, hipMemcpy(ctx->g.ndestroyed + si, zero2, 4, hipMemcpyHostToDevice));
+    FW_HIP(ctx, hipMemcpy(ctx->g.range_ticket + si, zero2, 4, hipMemcpyHostToDevice));  // (S.ticket_base is 0: a fresh SegHost)
+    return FW_OK;
+}
+
+// the emission entries: their host clocks (sync_spawner_data core.rs:350-358) and their device records
+static fw_status build_emit_records(fw_ctx *ctx, SpawnerHost &sp, const fw_spawner_desc *d, const std::vector<uint64_t> *carry_serial) {
+    for (uint32_t i = 0; i < d->n_emission_settings; i++) {
         EmissionHost &E = sp.em[i];
         const fw_emission_settings &e = d->emission_settings[i];
         E.es = e;
         E.between = (e.offset_end - e.offset_start) / e.count;
-        E.last_emission = 0.f, E.time_passed_in_cycle = 0.f;  // sync_spawner_data core.rs:350-358
+        E.last_emission = 0.f, E.time_passed_in_cycle = 0.f;
         E.enabled = d->starts_enabled != 0;
         E.emits_on_other_particles = e.mode == FW_MODE_NESTED;
         E.dst_seg = sp.seg[e.particle_index];
@@ -511,8 +482,12 @@ fw_status build_spawner(fw_ctx *ctx, int h, const fw_spawner_desc *d, const std:
         FW_HIP(ctx, hipMemcpy(ctx->d_nest_start + E.emit_slot, &t0, sizeof t0, hipMemcpyHostToDevice));
         ctx->nest_ticket_base[E.emit_slot] = 0u;
     }
-    // ring types other particles' entries emit from that need no materialisation (SegHost::virt_parent)
-    for (uint32_t t = 0; t < nt; t++) {
+    return FW_OK;
+}
+
+// ring types other particles' entries emit from that need no materialisation (SegHost::virt_parent)
+static fw_status mark_virtual_parents(fw_ctx *ctx, const SpawnerHost &sp, const fw_spawner_desc *d) {
+    for (uint32_t t = 0; t < d->n_particle_settings; t++) {
         SegHost &S = ctx->segs[sp.seg[t]];
         if (!S.ring() || S.nested_fed || S.n_lplanes > 2) continue;
         if (S.n_lplanes == 0) {  // (no entry emits from it or onto it: nothing in a Nested pass ever looks at its particles)
@@ -527,9 +502,16 @@ fw_status build_spawner(fw_ctx *ctx, int h, const fw_spawner_desc *d, const std:
                  std::isfinite(e.count) && std::isfinite(e.offset_end);
         }
         S.virt_parent = ok;
-        if (ok && (st = upload_seg(ctx, sp.seg[t]))) return st;
+        if (fw_status st = ok ? upload_seg(ctx, sp.seg[t]) : FW_OK) return st;
     }
-    sp.initialized = true;
+    return FW_OK;
+}
+
+// What the new segments mean for the context as a whole (callers of build_spawner have synchronised it): the arrays sized by the
+// segments; FIFO rings that follow a spilled type onto range rings; small rings that leave because the context is no longer one of
+// few segments without a FIFO ring (FwPathCensus::spawner_built); the small-type kernel's mode
+static fw_status context_follow_ups(fw_ctx *ctx) {
+    fw_status st;
     if ((st = ensure_range_arrays(ctx))) return st;
     if ((st = ensure_tile_arrays(ctx))) return st;
     if (ctx->segs.size() > ctx->small_cap) {  // the small-type list (fw_ctx::d_small): room for every segment slot; fw_step never allocates
@@ -539,22 +521,47 @@ fw_status build_spawner(fw_ctx *ctx, int h, const fw_spawner_desc *d, const std:
         if ((st = alloc_buf(ctx, ctx->d_small, ncap)) || (st = alloc_buf(ctx, ctx->h_small, ncap, Mem::pinned))) return st;
         ctx->small_cap = ncap, ctx->small_dirty = true;
     }
-    // the context is no longer one of few segments without a FIFO ring: its small range rings continue on the compacting path
-    // (fw_ctx::range_few; callers of build_spawner have synchronised the context)
-    if (ctx->n_spilled && ctx->n_fifo && (st = spill_fifo_rings(ctx))) return st;  // (fw_ctx::n_spilled)
-    if (ctx->n_in_use > ctx->range_few) ctx->few_blocked = true;
-    if (ctx->n_few && (ctx->n_fifo != 0 || ctx->n_in_use > ctx->range_few)) {
-        // (the hysteresis covers the arrival of a FIFO ring as well: a context in which one comes and goes would otherwise
-        // convert its small rings at every arrival -- ADVICE r04)
-        ctx->few_blocked = true;
-        if ((st = drop_few_rings(ctx))) return st;
-    }
+    if (ctx->census.n_spilled && ctx->census.n_fifo && (st = spill_fifo_rings(ctx))) return st;
+    if (ctx->census.spawner_built(ctx->range_few) && (st = drop_few_rings(ctx))) return st;
     update_small_mode(ctx);
     return FW_OK;
 }
 
+fw_status build_spawner(fw_ctx *ctx, int h, const fw_spawner_desc *d, const std::vector<uint64_t> *carry_serial) {
+    SpawnerHost &sp = ctx->spawners[h];
+    drop_forecast_and_boxes(ctx);
+    ctx->tab_force = true;
+    const uint32_t nt = d->n_particle_settings, ne = d->n_emission_settings;
+    sp.uid = d->uid;
+    sp.starts_enabled = d->starts_enabled;
+    sp.types.assign(nt, TypeHost{});
+    sp.em.assign(ne, EmissionHost{});
+    sp.seg.assign(nt, kNoSeg);
+    fw_status st;
+    if ((st = reserve_tables(ctx, nt, ne))) return st;
+
+    std::vector<uint32_t> caps(nt, 0);
+    for (int pass = 0; pass < 2; pass++)
+        for (uint32_t t = 0; t < nt; t++) caps[t] = derive_capacity(d, t, caps);
+
+    for (uint32_t t = 0; t < nt; t++) {
+        TypeBuild b;
+        b.t = t, b.capacity = caps[t];
+        make_type_records(ctx, d, sp.types[t], b);
+        if ((st = pack_keys_take_window(ctx, sp.types[t], b))) return st;
+        if ((st = take_segment_slot(ctx, sp, h, d, b))) return st;
+        if ((st = choose_segment_path(ctx, sp, d, b))) return st;
+        if ((st = alloc_type_buffers(ctx, sp, d, caps, b))) return st;
+        if ((st = upload_segment_zeroed(ctx, b.si))) return st;
+    }
+    if ((st = build_emit_records(ctx, sp, d, carry_serial))) return st;
+    if ((st = mark_virtual_parents(ctx, sp, d))) return st;
+    sp.initialized = true;
+    return context_follow_ups(ctx);
+}
+
 fw_status release_spawner_segments(fw_ctx *ctx, SpawnerHost &sp) {
-    ctx->fc_ok = false, ctx->boxes_epoch = 0;
+    drop_forecast_and_boxes(ctx);
     ctx->tab_force = true;
     for (int i = 0; i < kSnapRing; i++) ctx->snap_pending[i] = false;  // rows in flight describe the old segments
     for (const EmissionHost &e : sp.em) {
@@ -570,17 +577,14 @@ fw_status release_spawner_segments(fw_ctx *ctx, SpawnerHost &sp) {
         if (!S.in_use) continue;
         ctx->free_types.push_back(S.type_idx);
         if (S.keys_cap) ctx->free_keys.push_back({S.keys_off, S.keys_cap});
-        if (S.fifo) ctx->n_fifo--;
-        if (S.range) ctx->n_range--, ctx->r_force = true;
-        if (S.few_ring) ctx->n_few--;
-        if (S.spilled) ctx->n_spilled--;
-        if (S.small) ctx->n_small--, ctx->small_dirty = true, ctx->n_small_coll -= S.collides ? 1u : 0u;
-        if (S.small_ok) ctx->n_small_ok--;
-        if (S.inst) ctx->n_inst--;
-        if (S.solo) ctx->n_solo--;
-        ctx->n_in_use--, ctx->big_dirty = true;
-        if (ctx->n_in_use <= ctx->range_few / 2) ctx->few_blocked = false;
-        S = SegHost{};  // (releases its buffers)
+        if (S.range) ctx->r_force = true;
+        if (S.small) ctx->small_dirty = true;
+        ctx->big_dirty = true;
+        {
+            SegPathEdit edit(ctx, S);
+            S = SegHost{};  // (releases its buffers)
+        }
+        ctx->census.segment_released(ctx->range_few);
         const uint32_t zero = 0;
         for (int r = 0; r < 2 && e == hipSuccess; r++) e = hipMemcpy(ctx->g.count + (size_t)r * ctx->max_seg + si, &zero, 4, hipMemcpyHostToDevice);
     }

@@ -215,7 +215,7 @@ void pick_snapshot(fw_ctx *ctx, FwFrame &fr) {
             if (!ctx->snap_pending[k]) snap = k;
     // (small types are bounded by their lifetime windows and have no grid to size: a context of nothing else takes no snapshots --
     // a row is a pass over every segment record on the host and a store over the bus per segment on the device)
-    if (ctx->n_in_use == ctx->n_small) snap = -1;
+    if (ctx->census.n_in_use == ctx->census.n_small) snap = -1;
     fr.snap = snap;
     fr.a.host_counts = snap >= 0 ? ctx->h_snap + (size_t)snap * ctx->max_seg : nullptr;
 }
@@ -230,7 +230,7 @@ fw_status spawn_passes(fw_ctx *ctx, FwFrame &fr) {
     auto &levels = ctx->levels;
     const uint32_t n_seg = fr.n_seg, p = fr.p;
     fw_status st = FW_OK;
-    const bool small_virtual = ctx->n_small != 0 && ctx->host_fast;
+    const bool small_virtual = ctx->census.n_small != 0 && ctx->host_fast;
     auto stays_virtual = [&](const FwOp &op) { return small_virtual && ctx->segs[op.seg].small; };
     size_t n_virtual = 0;
     if (small_virtual)
@@ -372,7 +372,7 @@ fw_status op_table(fw_ctx *ctx, FwFrame &fr) {
     const bool hdr_done = in_place && fr.pre_hdr_ok && fr.pre_tracked == ops.size();
     if (!hdr_done) sort_by_segment(ops.begin(), ops.end());
     a.n_ops = (uint32_t)ops.size();
-    if (ops.size() <= FW_INLINE_OPS && (ops.empty() || !ctx->n_small)) {  // (small types read their ops from the table: fw_k_update_small)
+    if (ops.size() <= FW_INLINE_OPS && (ops.empty() || !ctx->census.n_small)) {  // (small types read their ops from the table: fw_k_update_small)
         fr.spawn_form = ops.empty() ? FW_SPAWN_NONE : FW_SPAWN_INLINE;
         for (size_t i = 0; i < ops.size(); i++) fr.inl.ops[i] = ops[i];
         return FW_OK;
@@ -532,7 +532,7 @@ struct FifoAccum {
         // (one rule for the whole context: a fused launch, every ring of which defers under it, takes the set of kernels the word names)
         fa.fuse_pad[FW_FIFO_NEWBORN] = ctx->newborn_spin ? 0u : 1u;        L.nt = bytes > ctx->nt_bytes ? 2 : bytes > ctx->nt_wo_bytes ? 1 : 0;
         // the frame's one launch, spin-less, every ring unread and large: it may wait for the next frame, or take the waiting one in
-        const bool candidate = fw_fuse2_candidate(ctx->use_fuse2, quiet, n_launches == 0 && fa.n_segs == ctx->n_fifo, fa.spinless != 0u, fusable);
+        const bool candidate = fw_fuse2_candidate(ctx->use_fuse2, quiet, n_launches == 0 && fa.n_segs == ctx->census.n_fifo, fa.spinless != 0u, fusable);
         // (how deep: two frames, or fw_ctx::fuse_depth where the pass dominates the launch -- beyond FW_FUSE_NARROW only where every ring
         // holds fuse_wide_min too)
         const uint32_t depth_knob = std::max(2u, std::min(ctx->fuse_depth, (uint32_t)FW_FUSE_MAX));
@@ -730,7 +730,7 @@ fw_status launch_fifo(fw_ctx *ctx, FwFrame &fr) {
     // (never on a caller-supplied stream: work the caller orders behind fw_step on ITS stream must cover the whole
     // frame, as it did before the side stream existed)
     // (the wave-per-type launch of small types counts as "a general launch" here: it touches none of the rings either)
-    bool side = ctx->use_fifo_stream && ctx->stream.owned() && (fr.total_tiles != 0 || ctx->n_small != 0) && ctx->live_ring == nullptr;
+    bool side = ctx->use_fifo_stream && ctx->stream.owned() && (fr.total_tiles != 0 || ctx->census.n_small != 0) && ctx->live_ring == nullptr;
     // (... nor with a colliding ring: a new collider set travels in the MAIN stream, fw_ctx_set_colliders)
     for (const SegHost &S : ctx->segs) side &= !(S.in_use && S.fifo && (S.fifo_mat || S.inst != nullptr || S.collides));
     fw_status st = order_side(ctx, side, ctx->fifo_last_side);
@@ -848,7 +848,7 @@ fw_status launch_range(fw_ctx *ctx, FwFrame &fr) {
         const bool small = any_coll_r || (!any_dev && parts < (ctx->range_small ? lim + lim / 4 : lim));
         if (small != ctx->range_small) ctx->range_small = small, dirty = true;
         // ... and of its YOUNG workgroups (fw_ctx::range_young_rounds)
-        const uint64_t mean = parts / std::max<uint32_t>(1u, ctx->n_range), big = ctx->range_young_big;
+        const uint64_t mean = parts / std::max<uint32_t>(1u, ctx->census.n_range), big = ctx->range_young_big;
         uint32_t yr = ctx->range_young_rounds;
         if (small || any_dev || fr.ring_stats.range_inst || big == 0) yr = 4;
         else if (yr == 4 && mean >= big) yr = 2;
@@ -1002,13 +1002,13 @@ fw_status launch_small(fw_ctx *ctx, FwFrame &fr) {
     sa.list = ctx->d_small, sa.n = (uint32_t)ctx->small_list.size(), sa.n_narrow = ctx->n_narrow, sa.parity = fr.p, sa.epoch = a.epoch, sa.dt = fr.dt;
     sa.seg_op_first = fr.small_hdr, sa.ops = fr.small_ops;
     sa.force_colors = a.force_colors, sa.dbg = ctx->dbg;
-    sa.any_inst = ctx->n_inst != 0 ? 1u : 0u;
-    sa.any_coll = ctx->n_small_coll != 0 ? 1u : 0u;
+    sa.any_inst = ctx->census.n_inst != 0 ? 1u : 0u;
+    sa.any_coll = ctx->census.n_small_coll != 0 ? 1u : 0u;
     sa.done_tag = a.done_tag, sa.done_value = a.done_value;
     sa.host_counts = a.host_counts, sa.live_out = a.live_out, sa.live_next = a.live_next;
     // next to the collision passes of the frame, on the ring stream (fw_ctx::small_last_side)
     const bool small_side = fr.legacy && fr.frame_mode != FW_MODE_FUSED && sa.n != 0 && ctx->host_fast && ctx->use_fifo_stream && ctx->stream.owned() &&
-                            ctx->live_ring == nullptr && ctx->n_small_coll == 0 && !list_resent;
+                            ctx->live_ring == nullptr && ctx->census.n_small_coll == 0 && !list_resent;
     if (!sa.n) return FW_OK;
     if ((st = order_side(ctx, small_side, ctx->small_last_side))) return st;
     if (small_side) sa.done_tag = nullptr;  // (the "frame has started" word recycles buffers the MAIN stream's launches read)
@@ -1092,7 +1092,7 @@ fw_status enqueue_frame(fw_ctx *ctx, FwFrame &fr) {
     update_args(ctx, fr);
     // a frame whose only GPU work can be one FIFO launch (fw_ctx::withheld, launch_fifo): no compacting, range or small segment, no separate
     // pass, no colour fill, nobody who wants a count or a time per frame.  Any other frame puts a withheld one on the stream first.
-    fr.quiet = ctx->use_fuse2 && ctx->n_fifo != 0 && ctx->n_in_use == ctx->n_fifo && !ctx->n_range && !ctx->n_small && !fr.total_tiles && !fr.legacy &&
+    fr.quiet = ctx->use_fuse2 && ctx->census.n_fifo != 0 && ctx->census.n_in_use == ctx->census.n_fifo && !ctx->census.n_range && !ctx->census.n_small && !fr.total_tiles && !fr.legacy &&
                !fr.fuse && !ctx->colors_dirty && ctx->live_ring == nullptr && !ctx->timing;
     fw_status st = fr.quiet ? FW_OK : flush_withheld(ctx);
     if (!st) st = set_forecast(ctx, fr);
@@ -1102,9 +1102,9 @@ fw_status enqueue_frame(fw_ctx *ctx, FwFrame &fr) {
     if ((st = fr.legacy ? spawn_passes(ctx, fr) : op_table(ctx, fr))) return st;
     if (ctx->h_done) fr.a.done_tag = ctx->h_done, fr.a.done_value = ctx->frame;
     fr.prof(ctx, 5);
-    if (ctx->n_fifo && (st = launch_fifo(ctx, fr))) return st;
-    if (ctx->n_range && (st = launch_range(ctx, fr))) return st;
-    if (ctx->n_small && (st = launch_small(ctx, fr))) return st;
+    if (ctx->census.n_fifo && (st = launch_fifo(ctx, fr))) return st;
+    if (ctx->census.n_range && (st = launch_range(ctx, fr))) return st;
+    if (ctx->census.n_small && (st = launch_small(ctx, fr))) return st;
     if ((st = launch_general(ctx, fr))) return st;
     fr.prof(ctx, 6);
     return end_frame(ctx, fr);

@@ -190,7 +190,7 @@ fw_status ensure_tile_arrays(fw_ctx *ctx) {
         if ((st = sync(ctx))) return st;
         size_t ncap = tiles * 2;
         auto &m = ctx->gm;
-        ctx->tiles_cap = 0, ctx->fc_ok = false, ctx->boxes_epoch = 0;
+        ctx->tiles_cap = 0, drop_forecast_and_boxes(ctx);
         ctx->fc_len = ncap + (ncap / 64 + 2) * FW_FC_S2_STRIDE + 8;  // P | P2 | tag (64-bit words)
         if ((st = alloc_buf(ctx, m.tile_cnt, ncap, Mem::device, false, &ctx->g.tile_cnt)) ||
             (st = alloc_buf(ctx, m.tile_off, ncap, Mem::device, false, &ctx->g.tile_off)) ||
@@ -235,7 +235,7 @@ fw_status ensure_range_arrays(fw_ctx *ctx) {
     }
     // one record per segment slot + one op per emission entry of the context
     const size_t need = round_up((uint32_t)(ctx->max_seg * sizeof(FwRangeRec)), 64) + (size_t)(ctx->n_emits + 8) * sizeof(FwOp) + 64;
-    if (ctx->n_range && need > ctx->rparam_bytes) {
+    if (ctx->census.n_range && need > ctx->rparam_bytes) {
         if ((st = sync(ctx))) return st;
         const size_t nb = need * 2;
         ctx->rparam_bytes = 0;

@@ -208,7 +208,7 @@ fw_status fw_ctx_update_mesh_vertices(fw_ctx *ctx, fw_mesh mesh, const float *xy
         return st;
     }
     memcpy(m.lo, lo, sizeof lo), memcpy(m.hi, hi, sizeof hi), m.pad = pad;
-    ctx->fc_ok = false, ctx->boxes_epoch = 0;
+    drop_forecast_and_boxes(ctx);
     return FW_OK;
 }
 
@@ -241,7 +241,7 @@ fw_status fw_ctx_update_mesh_vertices_device(fw_ctx *ctx, fw_mesh mesh, const vo
     m.dev_bounds = true;
     if (std::find(ctx->mesh_set.begin(), ctx->mesh_set.end(), mesh) != ctx->mesh_set.end())
         FW_HIP(ctx, fw_launch_mesh_spheres(ctx->stream, ctx->d_mesh_inst, ctx->g.n_mesh_inst, m.nodes, m.d_rec, true));
-    ctx->fc_ok = false, ctx->boxes_epoch = 0;
+    drop_forecast_and_boxes(ctx);
     return FW_OK;
 }
 
@@ -296,7 +296,7 @@ fw_status fw_ctx_set_mesh_colliders(fw_ctx *ctx, const fw_mesh_collider *inst, u
         return fail(ctx, FW_ENOMEM, "fw_ctx_set_mesh_colliders: out of host memory");
     }
     ctx->g.n_mesh_inst = n;
-    ctx->fc_ok = false, ctx->boxes_epoch = 0;
+    drop_forecast_and_boxes(ctx);
     return FW_OK;
 }
 

@@ -8,7 +8,7 @@ namespace fwh {
 // is unwrapped); make_general: a FIFO segment leaves that mode (two buffers, compacting update) on the way
 fw_status realloc_segment(fw_ctx *ctx, uint32_t si, uint32_t ncap, bool make_general) {
     SegHost &s = ctx->segs[si];
-    ctx->fc_ok = false, ctx->boxes_epoch = 0;
+    drop_forecast_and_boxes(ctx);
     fw_status st = ensure_ages(ctx, si);  // (the copies below take the age plane as it is: the refresh waits for the kernel)
     if (!st) st = ensure_spin(ctx, si);   // (... and rotation and angular velocity)
     if (!st) st = refresh_counts_exact(ctx);
@@ -73,19 +73,18 @@ fw_status realloc_segment(fw_ctx *ctx, uint32_t si, uint32_t ncap, bool make_gen
     // ---- commit: the list now starts in slot 0 (a range ring's old part first, the young part right behind it)
     const uint32_t young_lo = s.range_dev ? std::min(s.rold_seen, n) : (n > s.young_n ? n - s.young_n : 0u);
     if (leaves_fifo) {
+        SegPathEdit edit(ctx, s);
         s.fifo = false, s.fifo_mat = s.fifo_dev = false, s.coh.clear();
         s.q0pl = false, s.ageless_last = false;
         s.win_ok = false;  // no lifetime window was kept: the bound follows the snapshots from here on
-        ctx->n_fifo--;
         ctx->tab_force = true;
         ctx->seg_kind_changed = true;
     }
     if (make_general && s.range) {
+        SegPathEdit edit(ctx, s);
         s.range = false, s.ycoh.clear(), s.dcoh.clear(), s.gcoh.clear(), s.gcoh_sum = 0, s.young_lo = s.young_n = 0;
         s.range_mat = s.range_dev = false;
-        ctx->n_range--;
-        if (s.few_ring) s.few_ring = false, ctx->n_few--;
-        if (s.spilled) s.spilled = false, ctx->n_spilled--;
+        s.few_ring = s.spilled = false;
         ctx->tab_force = true, ctx->r_force = true;
         ctx->seg_kind_changed = true;
     }
@@ -140,44 +139,48 @@ bool small_eligible(const fw_ctx *ctx, const SegHost &S) {
 // on the kernel / off it: a flag (the same buffers, the same layout; the tile table is re-sent)
 static void small_activate(fw_ctx *ctx, SegHost &S) {
     if (S.small) return;
-    S.small = true, ctx->n_small++, ctx->small_dirty = true;
-    if (S.collides) ctx->n_small_coll++;
-    ctx->tab_force = true, ctx->fc_ok = false, ctx->boxes_epoch = 0;
+    SegPathEdit edit(ctx, S);
+    S.small = true, ctx->small_dirty = true;
+    ctx->tab_force = true, drop_forecast_and_boxes(ctx);
 }
-static void small_deactivate(fw_ctx *ctx, SegHost &S) {
+void small_deactivate(fw_ctx *ctx, SegHost &S) {
     if (!S.small) return;
-    S.small = false, ctx->n_small--, ctx->small_dirty = true;
-    if (S.collides) ctx->n_small_coll--;
-    if (S.solo) S.solo = false, ctx->n_solo--;  // (fw_step's frame-begin pass visits it again: fw_ctx::big_list)
+    SegPathEdit edit(ctx, S);
+    S.small = false, ctx->small_dirty = true;
+    S.solo = false;  // (fw_step's frame-begin pass visits it again: fw_ctx::big_list)
     ctx->big_dirty = true;
-    ctx->tab_force = true, ctx->fc_ok = false, ctx->boxes_epoch = 0;
+    ctx->tab_force = true, drop_forecast_and_boxes(ctx);
 }
 // the segment qualifies (small_eligible): on the kernel at once if the context runs it (fw_ctx::small_on), else with the others
 // when there are enough of them (update_small_mode)
 void enter_small(fw_ctx *ctx, SegHost &S) {
-    if (!S.small_ok)
-        S.small_ok = true, ctx->n_small_ok++, S.wide = S.expect_live * 2.0f > (float)ctx->small_max, S.wide_big = S.expect_live > (float)ctx->wide_mid;
+    if (!S.small_ok) {
+        SegPathEdit edit(ctx, S);
+        S.small_ok = true, S.wide = S.expect_live * 2.0f > (float)ctx->small_max, S.wide_big = S.expect_live > (float)ctx->wide_mid;
+    }
     if (S.wide ? (S.wide_big ? ctx->wide_on : ctx->wide_mid_on) : ctx->small_on) small_activate(ctx, S);
 }
-void small_suspend(fw_ctx *ctx, SegHost &S) { small_deactivate(ctx, S); }
 // ... and no longer does: a compacting segment from here on
 void leave_small(fw_ctx *ctx, SegHost &S) {
-    if (S.small_ok) S.small_ok = false, ctx->n_small_ok--;
+    if (S.small_ok) {
+        SegPathEdit edit(ctx, S);
+        S.small_ok = false;
+    }
     small_deactivate(ctx, S);
 }
 // fw_ctx::small_min, with hysteresis; called where spawners are built and destroyed (the context is synchronised)
 void update_small_mode(fw_ctx *ctx) {
     const uint32_t on_at = ctx->small_min, off_below = ctx->small_min - ctx->small_min / 4;
-    const bool want = ctx->use_small && (ctx->small_on ? ctx->n_small_ok >= off_below : ctx->n_small_ok >= on_at);
+    const bool want = ctx->use_small && (ctx->small_on ? ctx->census.n_small_ok >= off_below : ctx->census.n_small_ok >= on_at);
     // ... and its wide role from wide_min of them on (fw_ctx::wide_min)
     const bool want_wide = ctx->use_small && ctx->wide_max != 0 &&
-                           (ctx->wide_on ? ctx->n_small_ok >= ctx->wide_min - ctx->wide_min / 4 : ctx->n_small_ok >= ctx->wide_min);
+                           (ctx->wide_on ? ctx->census.n_small_ok >= ctx->wide_min - ctx->wide_min / 4 : ctx->census.n_small_ok >= ctx->wide_min);
     const uint32_t mid_at = ctx->wide_min / 3;  // (fw_ctx::wide_mid)
     const bool want_mid = ctx->use_small && ctx->wide_max != 0 &&
-                          (ctx->wide_mid_on ? ctx->n_small_ok >= mid_at - mid_at / 4 : ctx->n_small_ok >= mid_at);
+                          (ctx->wide_mid_on ? ctx->census.n_small_ok >= mid_at - mid_at / 4 : ctx->census.n_small_ok >= mid_at);
     // ... and from wave_all_min types on EVERY type of the kernel -- wide ones included -- is walked by a wave (fw_ctx::wave_all_min)
     const bool want_wave_all = ctx->use_small && ctx->wave_all_min != 0 &&
-                               (ctx->wave_all_on ? ctx->n_small_ok >= ctx->wave_all_min - ctx->wave_all_min / 6 : ctx->n_small_ok >= ctx->wave_all_min);
+                               (ctx->wave_all_on ? ctx->census.n_small_ok >= ctx->wave_all_min - ctx->wave_all_min / 6 : ctx->census.n_small_ok >= ctx->wave_all_min);
     if (want_wave_all != ctx->wave_all_on) ctx->wave_all_on = want_wave_all, ctx->small_dirty = true;  // (the list is laid out by role)
     if (want == ctx->small_on && want_wide == ctx->wide_on && want_mid == ctx->wide_mid_on) return;
     ctx->small_on = want, ctx->wide_on = want_wide, ctx->wide_mid_on = want_mid;
@@ -187,24 +190,25 @@ void update_small_mode(fw_ctx *ctx) {
 
 // every SegHost::few_ring segment leaves its ring (fw_ctx::range_few), particles and order kept
 fw_status drop_few_rings(fw_ctx *ctx) {
-    for (uint32_t si = 0; si < ctx->segs.size() && ctx->n_few; si++) {
+    for (uint32_t si = 0; si < ctx->segs.size() && ctx->census.n_few; si++) {
         if (!ctx->segs[si].in_use || !ctx->segs[si].few_ring) continue;
-        const fw_status st = fifo_to_general(ctx, si);  // (realloc_segment clears the flag and the count)
+        const fw_status st = fifo_to_general(ctx, si);  // (realloc_segment clears the flag)
         if (st) return st;
         if (small_eligible(ctx, ctx->segs[si])) enter_small(ctx, ctx->segs[si]);  // (a small type: the wave-per-type kernel from here on)
     }
     return FW_OK;
 }
 
-// can this FIFO ring continue as a RANGE ring (build_spawner's rule for range rings, for a type that is a FIFO ring already)
+// can this FIFO ring continue as a RANGE ring: what the rule asks of a range ring that a FIFO ring may fail (fw_path_range_basics, at the
+// capacity the ring has by now), a capacity the young tiles divide, and no plain instance buffer (attach_instances)
 bool fifo_may_become_range(const fw_ctx *ctx, const SegHost &S) {
-    if (!S.in_use || !S.fifo || !ctx->use_range || S.spawner < 0) return false;
+    if (!S.in_use || !S.fifo || S.spawner < 0) return false;
     const SpawnerHost &sp = ctx->spawners[S.spawner];
-    return !sp.no_rings && S.n_lplanes <= 2 && sp.types[S.type].life_lo_safe > 0.0f && S.capacity <= FW_RANGE_MAX_CAPACITY &&
+    return fw_path_range_basics(path_policy(ctx), sp.no_rings, S.n_lplanes, sp.types[S.type].life_lo_safe, S.capacity) &&
            S.capacity % std::max<uint32_t>(FW_TILE, fw_range_young_tile()) == 0u && !(S.inst != nullptr && !S.inst_window);
 }
 
-// A FIFO ring becomes a RANGE ring where it stands (fw_ctx::n_spilled): the same buffer, the same slots, nothing copied.  A FIFO
+// A FIFO ring becomes a RANGE ring where it stands (FwPathCensus::n_spilled): the same buffer, the same slots, nothing copied.  A FIFO
 // ring is a range ring whose particles are all "young" -- nobody has been told yet that it may die -- with an empty old part: the
 // slot of the first young particle is the head, the young cohorts are the FIFO cohorts (frame of birth + size; sizes the device
 // alone knows stay in the pinned report ring), their ages -- one table for all range rings of the context, fw_ctx::birth_age -- are
@@ -221,7 +225,7 @@ fw_status fifo_to_range(fw_ctx *ctx, uint32_t si) {
     SegHost &S = ctx->segs[si];
     S.axis = 0u;  // (the axis-spin rule is the FIFO kernel's: the range kernel loads every plane)
     const TypeHost &T = ctx->spawners[S.spawner].types[S.type];
-    ctx->fc_ok = false, ctx->boxes_epoch = 0;
+    drop_forecast_and_boxes(ctx);
     // ---- the ages of the frames its cohorts were born in: fw_ctx::birth_age holds one entry per frame, contiguous up to the
     // current frame; it is extended backwards to the oldest cohort.  Frames in which this ring received nothing get the age of
     // the next older cohort (never asked for by it; at least as old as the true one, so the pruning order holds) -- and are
@@ -260,10 +264,11 @@ fw_status fifo_to_range(fw_ctx *ctx, uint32_t si) {
         if ((st = planes_to_float4(FW_OFF_Q2(C)))) return st;
     }
     // ---- the ring's own bookkeeping
-    S.fifo = false, ctx->n_fifo--;
+    {
+        SegPathEdit edit(ctx, S);
+        S.fifo = false, S.range = true, S.spilled = true;
+    }
     S.q0pl = false;
-    S.range = true, ctx->n_range++;
-    S.spilled = true, ctx->n_spilled++;
     S.young_lo = S.head, S.head = 0;
     S.range_life_lo = T.life_lo_safe;
     ctx->range_life_max = std::max(ctx->range_life_max, S.range_life_lo);
@@ -305,9 +310,9 @@ fw_status fifo_to_range(fw_ctx *ctx, uint32_t si) {
     return ensure_range_arrays(ctx);
 }
 
-// every FIFO ring of the context that may becomes a range ring (fw_ctx::n_spilled)
+// every FIFO ring of the context that may becomes a range ring (FwPathCensus::n_spilled)
 fw_status spill_fifo_rings(fw_ctx *ctx) {
-    for (uint32_t si = 0; si < ctx->segs.size() && ctx->n_fifo; si++) {
+    for (uint32_t si = 0; si < ctx->segs.size() && ctx->census.n_fifo; si++) {
         const fw_status st = fifo_to_range(ctx, si);
         if (st) return st;
     }
@@ -329,7 +334,7 @@ fw_status leave_nospin(fw_ctx *ctx, uint32_t si) {
     FW_HIP(ctx, hipMemcpy((char *)(ctx->d_types + s.type_idx) + offsetof(FwType, flags), &flags, sizeof flags, hipMemcpyHostToDevice));
     s.nospin = false;
     ctx->tab_force = true, ctx->r_force = true;  // (the tile descriptors carry the flag)
-    ctx->fc_ok = false, ctx->boxes_epoch = 0;
+    drop_forecast_and_boxes(ctx);
     return FW_OK;
 }
 
@@ -349,7 +354,7 @@ fw_status set_derived(fw_ctx *ctx, uint32_t si, bool on, bool refill) {
     uint32_t flags = (s.nospin ? FW_TYPE_NOSPIN : 0u) | (on ? FW_TYPE_DERIVED : 0u);
     FW_HIP(ctx, hipMemcpy((char *)(ctx->d_types + s.type_idx) + offsetof(FwType, flags), &flags, sizeof flags, hipMemcpyHostToDevice));
     s.derived = on;
-    ctx->fc_ok = false, ctx->boxes_epoch = 0;
+    drop_forecast_and_boxes(ctx);
     if (s.range) ctx->r_force = true;  // (the range descriptors carry FW_TYPE_IDX_NOLIFE)
     return FW_OK;
 }
@@ -390,7 +395,7 @@ fw_status update_tile_table(fw_ctx *ctx) {
     // (a context of rings and small types only -- thousands of small emitters: nothing for the compacting launch, whose table is
     // empty already: not a pass over every segment record per frame)
     if (!ctx->tab_force && ctx->total_tiles_dev == 0 && ctx->d_tile_first && ctx->tiles_dev.size() == n_seg &&
-        ctx->n_in_use == ctx->n_fifo + ctx->n_range + ctx->n_small) {
+        ctx->census.n_in_use == ctx->census.n_fifo + ctx->census.n_range + ctx->census.n_small) {
         ctx->vt_rounds = 1u;
         return FW_OK;
     }

@@ -40,7 +40,7 @@ fw_status begin_frame(fw_ctx *ctx, float dt) {
                 fw_status nst = leave_nospin(ctx, si);
                 if (nst) return nst;
             }
-    if (ctx->n_fifo) {
+    if (ctx->census.n_fifo) {
         // the FIFO order rests on ages that never decrease: a negative or non-finite dt ends the mode (as does a dt so
         // small that the cohort list grows without bound)
         const bool dt_ok = dt >= 0.0f && std::isfinite(dt);
@@ -54,7 +54,7 @@ fw_status begin_frame(fw_ctx *ctx, float dt) {
         }
     }
     ctx->range_ops.clear();
-    if (ctx->n_range) {
+    if (ctx->census.n_range) {
         // The in-place young part of a range ring rests on ages that never decrease and on nobody -- a particle spawned this
         // frame included -- dying before its age reaches lifetime.min: a negative or non-finite dt, a step as long as the
         // shortest lifetime, or a cohort list that grows without bound (a dt thousands of times smaller than the
@@ -68,7 +68,7 @@ fw_status begin_frame(fw_ctx *ctx, float dt) {
             if (cst) return cst;
         }
     }
-    if (!ctx->n_range) ctx->birth_age.clear();
+    if (!ctx->census.n_range) ctx->birth_age.clear();
     return FW_OK;
 }
 
@@ -87,7 +87,7 @@ bool report_missing(fw_ctx *ctx, const SegHost &S, uint64_t frame) {
 }
 
 fw_status recover_missing_reports(fw_ctx *ctx, float dt) {
-    if (!ctx->n_fifo && !ctx->n_range) return FW_OK;
+    if (!ctx->census.n_fifo && !ctx->census.n_range) return FW_OK;
     for (uint32_t si = 0; si < ctx->segs.size(); si++) {
         SegHost &S = ctx->segs[si];
         if (!S.in_use || !S.h_report) continue;
@@ -137,7 +137,7 @@ fw_status segment_pass(fw_ctx *ctx, FwFrame &fr) {
     ctx->grow_scratch.clear();
     // (solo segments -- small types with one feeder, thousands of them -- are not visited: the spawner loop does this for
     // them where it makes their op; fw_ctx::big_list holds everybody else)
-    const bool by_list = ctx->n_solo != 0;
+    const bool by_list = ctx->census.n_solo != 0;
     if (by_list && ctx->big_dirty) {
         ctx->big_list.clear();
         for (uint32_t si = 0; si < ctx->segs.size(); si++)
@@ -164,7 +164,7 @@ fw_status segment_pass(fw_ctx *ctx, FwFrame &fr) {
         if (S.nested_fed && nested_fed_wants_growth(S)) ctx->grow_scratch.push_back((uint32_t)si);
         if (S.win_ok) expire_window(ctx, S);
         // a small type with one feeder: solo from here on (this was its last visit by this pass)
-        if (S.small && S.one_feeder && solo_ok) S.solo = true, ctx->n_solo++, ctx->big_dirty = true;
+        if (S.small && S.one_feeder && solo_ok) seg_becomes_solo(ctx, S), ctx->big_dirty = true;
     }
 
     // Nested-fed segments whose count (or its growth) nears their derived capacity: nested_fed_wants_growth.  By half again,
@@ -192,11 +192,11 @@ fw_status segment_pass(fw_ctx *ctx, FwFrame &fr) {
 fw_status take_op_slot(fw_ctx *ctx, FwFrame &fr) {
     auto &levels = ctx->levels;
     // (not a table small enough for host-written device memory -- fw_ctx::b_param: that one is copied there in one sequential pass)
-    if (!(ctx->host_fast && ctx->n_small != 0 && ctx->update_mode == FW_MODE_FUSED && !levels.empty() &&
-          !(ctx->param_bar && ctx->segs.size() * sizeof(OpHdr) + ((size_t)ctx->n_in_use + 16) * sizeof(FwOp) <= kBarParamBytes)))
+    if (!(ctx->host_fast && ctx->census.n_small != 0 && ctx->update_mode == FW_MODE_FUSED && !levels.empty() &&
+          !(ctx->param_bar && ctx->segs.size() * sizeof(OpHdr) + ((size_t)ctx->census.n_in_use + 16) * sizeof(FwOp) <= kBarParamBytes)))
         return FW_OK;
     const size_t n_seg0 = ctx->segs.size(), off_ops0 = n_seg0 * sizeof(OpHdr);
-    const size_t want_ops = (size_t)ctx->n_in_use + 16;
+    const size_t want_ops = (size_t)ctx->census.n_in_use + 16;
     fw_status pst = FW_OK;
     if (ctx->param_bytes < off_ops0 + want_ops * sizeof(FwOp)) pst = ensure_param_ring(ctx, off_ops0 + (want_ops * 2 + 64) * sizeof(FwOp));
     if (!pst) pst = acquire_slot(ctx, &fr.pre_slot);
@@ -260,7 +260,7 @@ inline void note_spawned(fw_ctx *ctx, SegHost &S, uint64_t n) {
 // a refresh of the exact counts drops this frame's appends from every bound: back in they go
 void readd_frame_spawns(fw_ctx *ctx) {
     for (auto &X : ctx->segs) X.ub += X.frame_spawn;
-    if (ctx->n_solo)  // (a solo segment's appends of the frame are in its op)
+    if (ctx->census.n_solo)  // (a solo segment's appends of the frame are in its op)
         for (auto &L : ctx->levels)
             for (const FwOp &op : L.g)
                 if (ctx->segs[op.seg].solo) ctx->segs[op.seg].ub += op.n;
@@ -321,7 +321,7 @@ fw_status spawner_loop(fw_ctx *ctx, FwFrame &fr) {
                 if (!n) continue;
                 if (n > kMaxSpawnPerOp) return fail(ctx, FW_ECAPACITY, "emission count exceeds 2^30 particles in one frame");
                 SegHost &S = ctx->segs[dst];
-                if (S.solo && S.win_ok) expire_window(ctx, S);  // its frame begins here (fw_ctx::n_solo)
+                if (S.solo && S.win_ok) expire_window(ctx, S);  // its frame begins here (FwPathCensus::n_solo)
                 if (S.nested_fed && S.auto_capacity && S.capacity < 0x70000000u) {
                     // A type that receives Nested children too: its children are counted on the device, but its Global
                     // particles are counted right here.  Count of the latest snapshot row + every Global particle since
@@ -405,7 +405,7 @@ fw_status spawner_loop(fw_ctx *ctx, FwFrame &fr) {
                     S.wide = true, S.wide_big = false, ctx->small_dirty = true;
                     if (!ctx->wide_mid_on) {
                         const bool was_solo = S.solo;
-                        small_suspend(ctx, S);
+                        small_deactivate(ctx, S);
                         if (was_solo) S.frame_spawn = (uint32_t)n;
                     }
                 }
@@ -507,8 +507,8 @@ void route_ring_ops(fw_ctx *ctx, FwFrame &fr) {
 // general launch spawns them itself).  Otherwise the frame runs the separate passes (fw_k_spawn / fw_k_nest), as before.
 void plan_fuse(fw_ctx *ctx, FwFrame &fr) {
     const float dt = fr.dt;
-    if (fr.nested_frame && ctx->nest_fuse && !fr.any_coll && !ctx->seg_kind_changed && ctx->update_mode == FW_MODE_FUSED && ctx->n_fifo != 0 &&
-        ctx->n_fifo <= FW_FIFO_PER_LAUNCH && ctx->fifo_ops.size() <= FW_INLINE_OPS && !fr.ring_stats.fifo_coll && !fr.ring_stats.fifo_inst &&
+    if (fr.nested_frame && ctx->nest_fuse && !fr.any_coll && !ctx->seg_kind_changed && ctx->update_mode == FW_MODE_FUSED && ctx->census.n_fifo != 0 &&
+        ctx->census.n_fifo <= FW_FIFO_PER_LAUNCH && ctx->fifo_ops.size() <= FW_INLINE_OPS && !fr.ring_stats.fifo_coll && !fr.ring_stats.fifo_inst &&
         dt >= 0.0f && std::isfinite(dt)) {
         bool fuse = true;
         for (auto &L : ctx->levels) {

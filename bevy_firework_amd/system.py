@@ -609,6 +609,17 @@ class ParticleSystem:
         self._check(self._lib.fw_debug_spinless_launches(self._ctx, C.byref(n)))
         return int(n.value)
 
+    PATH_CENSUS_FIELDS = ("n_in_use", "n_fifo", "n_range", "n_few", "n_spilled", "n_small", "n_small_ok", "n_small_coll", "n_inst", "n_solo",
+                          "few_blocked")
+
+    def path_census(self):
+        """(kept, recounted): the context's segments by update path as the host keeps the census and as a recount over its segment
+        records gives it, each a dict over PATH_CENSUS_FIELDS; equal at all times (csrc/fw_update_path.h).  Host state only: nothing is
+        synchronised or flushed"""
+        kept, again = (C.c_uint32 * 11)(), (C.c_uint32 * 11)()
+        self._check(self._lib.fw_debug_path_census(self._ctx, kept, again))
+        return dict(zip(self.PATH_CENSUS_FIELDS, map(int, kept))), dict(zip(self.PATH_CENSUS_FIELDS, map(int, again)))
+
     def whole_tiles(self):
         """(launches, tiles): spin-less FIFO launches so far in which the host found a whole ring tile -- every slot a particle that lives
         through the launch -- and those tiles: they take the arm that issues all loads first"""

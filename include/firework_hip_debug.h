@@ -46,6 +46,11 @@ fw_status fw_debug_read_range_timestamps(fw_ctx *ctx, unsigned long long *out, u
  * whose latest launch ran D = 2 .. 8 frames of it in one pass (fw_debug_fuse2) reports that launch's bytes divided by D */
 fw_status fw_debug_update_path(fw_ctx *ctx, fw_spawner spawner, uint32_t type, int32_t *mode, uint32_t *moved_bytes,
                                uint32_t *algorithmic_bytes);
+/* the context's segments by update path, as the host keeps the census (kept[11]) and as a recount over its segment records gives it
+ * (recounted[11]): in use, FIFO rings, range rings, few-rings, spilled rings, on the wave-per-type kernel, eligible for it, colliding
+ * ones on it, with an instance buffer, solo; then the few-segments hysteresis (1: blocked), which is history and the same in both.
+ * The two halves are equal at all times.  Host state only: no synchronisation, a withheld launch stays withheld */
+fw_status fw_debug_path_census(fw_ctx *ctx, uint32_t *kept, uint32_t *recounted);
 
 /* frames with Nested entries stepped so far: those whose entries ran INSIDE the FIFO ring launch (one launch per frame, DESIGN.md
  * 4.0) and those that ran the separate fw_k_spawn / fw_k_nest passes first */

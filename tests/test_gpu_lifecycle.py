@@ -116,6 +116,8 @@ class World:
         """the state of (up to `limit` randomly chosen) spawners against the oracle -- the large ones always"""
         for row in self.paths():
             self.seen.update(row)
+        kept, recounted = self.system.path_census()
+        assert kept == recounted, f"case {self.case} frame {self.frames} ({what}): the census of update paths drifted from its recount"
         order = [k for k, kind in enumerate(self.kinds) if kind in ("fifo", "nested_big", "mid", "two")]
         rest = [k for k in range(len(self.pairs)) if k not in order]
         self.rng.shuffle(rest)
@@ -369,6 +371,8 @@ class MeshWorld(World):
 
     def check(self, what, limit=14):
         rows = self.paths()
+        kept, recounted = self.system.path_census()
+        assert kept == recounted, f"case {self.case} frame {self.frames} ({what}): the census of update paths drifted from its recount"
         if self.placed:
             self.with_meshes.update(p for row in rows for p in row)
         order = [k for k, kind in enumerate(self.kinds) if kind == "ctiny"]
