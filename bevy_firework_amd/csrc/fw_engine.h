@@ -495,7 +495,7 @@ struct alignas(64) SegHost {
     FwSpinBook spin;
     uint32_t spin_streak = 0;
     bool spin_last = false;
-    uint32_t fuse_last = 0;  // the frames of the ring the latest launch ran in one pass, 2 .. FW_FUSE_MAX, or 0: one, unfused (fw_ctx::withheld): fw_debug_update_path
+    uint32_t fuse_last = 0;  // the frames of the ring the latest launch ran in one pass, 2 .. FW_FUSE_FAR, or 0: one, unfused (fw_ctx::withheld): fw_debug_update_path
     bool q0pl = false;  // the ring keeps Q0 (position, age) as four component planes (FwSeg::cpl bit 2): set where the ring is built
     // A ring in a spawner WITH Nested entries: in frames that run the Nested pass its new particles are materialised in
     // the ring before the update (fw_k_spawn / fw_k_nest address it through the head) and fw_k_update_fifo gives them
@@ -866,6 +866,14 @@ struct fw_ctx {
     bool use_fuse2 = true;
     uint32_t fuse2_min = 384u * FW_TILE;
     uint32_t fuse_depth = FW_FUSE_MAX, fuse_deep_min = 768u * FW_TILE, fuse_wide_min = 768u * FW_TILE;
+    // The far tier (round 32): a group may grow beyond FW_FUSE_MAX frames, up to fuse_far_depth (FW_FUSE_FAR_DEPTH, FW_FUSE_MAX .. FW_FUSE_FAR;
+    // FW_FUSE_MAX: the tier is off), where fuse_depth is FW_FUSE_MAX (the knob unset, or 8), the launch takes the forms that defer their
+    // newborns' spin (not FW_NEWBORN_SPIN=1: the tier has no eager kernels) and every ring of it holds fuse_far_min live particles
+    // (FW_FUSE_FAR_MIN; 768 tiles like the two thresholds above, and as unmeasured between that and the headline's size).  In such a launch,
+    // and in no other, a frame's op that continues the group's last op of its ring is merged into it (fw_op_continues, fw_withheld.h): the
+    // launch carries FW_INLINE_OPS ops, so a ring with a still emitter reaches sixteen frames and one whose emitter moves every frame
+    // closes at eight, as before.  (Below the threshold two rings with one op each close at four frames; above it they may reach sixteen.)
+    uint32_t fuse_far_depth = FW_FUSE_FAR_DEFAULT, fuse_far_min = 768u * FW_TILE;
     FwWithheld withheld;  // (fw_withheld.h: the group and its transitions; launch_fifo offers, flush_withheld takes, drop_withheld drops)
     // fw_debug_fuse2: launches that ran two or more frames / withheld frames enqueued alone; fw_debug_fuse_frames: frames run by fused launches
     uint64_t fused_launches = 0, fuse2_flushed = 0, fuse_frames = 0;

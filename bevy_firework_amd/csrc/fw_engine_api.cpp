@@ -216,6 +216,8 @@ fw_status fw_ctx_create(int device, uint32_t seed, void *stream, fw_ctx **out) {
     if (const char *m = getenv("FW_FUSE_DEPTH")) ctx->fuse_depth = (uint32_t)std::min(std::max(atoi(m), 2), (int)FW_FUSE_MAX);
     if (const char *m = getenv("FW_FUSE_DEEP_MIN")) ctx->fuse_deep_min = (uint32_t)strtoul(m, nullptr, 10);
     if (const char *m = getenv("FW_FUSE_WIDE_MIN")) ctx->fuse_wide_min = (uint32_t)strtoul(m, nullptr, 10);
+    if (const char *m = getenv("FW_FUSE_FAR_DEPTH")) ctx->fuse_far_depth = (uint32_t)std::min(std::max(atoi(m), (int)FW_FUSE_MAX), (int)FW_FUSE_FAR);
+    if (const char *m = getenv("FW_FUSE_FAR_MIN")) ctx->fuse_far_min = (uint32_t)strtoul(m, nullptr, 10);
     // 0: scale / colour planes always stored; 1: not stored for types with an attached instance buffer; 2 (default): for no type
     if (const char *m = getenv("FW_DERIVED")) ctx->use_derived = atoi(m) != 0, ctx->derive_all = atoi(m) >= 2;
     if (const char *m = getenv("FW_NEST_FUSE")) ctx->nest_fuse = atoi(m) != 0;

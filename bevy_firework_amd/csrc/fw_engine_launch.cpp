@@ -462,7 +462,10 @@ fw_status enqueue_fifo(fw_ctx *ctx, const FwFifoLaunch &L, hipStream_t stream, h
     if (fused) ctx->fused_launches++, ctx->fuse_frames += L.depth;
     else if (L.held) ctx->fuse2_flushed++;
     count_whole_tiles(ctx, L.fa), count_newborn(ctx, L.fa);
-    FW_HIP(ctx, fw_launch_update_fifo(stream, ctx->g, L.fa, L.fio, L.tiles, L.nt, e0, e1, fused ? &L.fz : nullptr));
+    if (L.depth > FW_FUSE_MAX)  // (the far tier's kernels, a unit of their own: fw_k_rings_far.hip)
+        FW_HIP(ctx, fw_launch_update_fifo_far(stream, ctx->g, L.fa, L.fio, L.fz, L.far, L.tiles, L.nt, e0, e1));
+    else
+        FW_HIP(ctx, fw_launch_update_fifo(stream, ctx->g, L.fa, L.fio, L.tiles, L.nt, e0, e1, fused ? &L.fz : nullptr));
     return FW_OK;
 }
 
@@ -507,6 +510,7 @@ struct FifoAccum {
     bool fusable = true;   // several frames in one launch: every ring so far deferred its spin in it and holds fuse2_min particles
     bool deep = true;      // ... and holds fuse_deep_min: a group of the launch may be deeper than two frames, up to FW_FUSE_NARROW
     bool wide = true;      // ... and fuse_wide_min: up to fw_ctx::fuse_depth
+    bool far = true;       // ... and fuse_far_min: up to fw_ctx::fuse_far_depth, the far tier
     uint32_t n_launches = 0;  // the launches of this frame so far
     bool sent = false;     // the launch has been offered: a ring that follows starts the frame's next one (most frames have one: cleared for nobody)
 
@@ -536,6 +540,10 @@ struct FifoAccum {
         // (how deep: two frames, or fw_ctx::fuse_depth where the pass dominates the launch -- beyond FW_FUSE_NARROW only where every ring
         // holds fuse_wide_min too)
         const uint32_t depth_knob = std::max(2u, std::min(ctx->fuse_depth, (uint32_t)FW_FUSE_MAX));
+        // (... and beyond FW_FUSE_MAX, the far tier: the knob at FW_FUSE_MAX, the forms that defer their newborns' spin, every ring at
+        // fuse_far_min.  A depth_max above FW_FUSE_MAX is also what lets the group merge its ops: FwWithheld::offer)
+        const bool go_far = deep && wide && far && ctx->fuse_depth == (uint32_t)FW_FUSE_MAX && fa.fuse_pad[FW_FIFO_NEWBORN] != 0u && ctx->fuse_far_depth > (uint32_t)FW_FUSE_MAX;
+        if (go_far) return Words{candidate, std::min(ctx->fuse_far_depth, (uint32_t)FW_FUSE_FAR)};
         return Words{candidate, !deep ? 2u : !wide ? std::min(depth_knob, (uint32_t)FW_FUSE_NARROW) : depth_knob};
     }
 };
@@ -652,6 +660,7 @@ void ring_record(fw_ctx *ctx, const FifoFrame &ff, FifoAccum &acc, uint32_t si, 
     acc.fusable &= R.spin_defer && in.n_in >= ctx->fuse2_min && (R.newborn_defer || ctx->newborn_spin);
     acc.deep &= in.n_in >= ctx->fuse_deep_min;
     acc.wide &= in.n_in >= ctx->fuse_wide_min;
+    acc.far &= in.n_in >= ctx->fuse_far_min;
     acc.L.spin_from[fa.n_segs] = R.spin_from_new;
     // (acceleration and drag of the ring's type, for the whole tiles of a fused launch this frame may close: FwFuseArgs::move)
     memcpy(acc.L.fz.move[fa.n_segs], S.fifo_move, sizeof S.fifo_move);

@@ -145,3 +145,30 @@ FW_HD bool fw_fuse_push(uint32_t capacity, FwFuseGroup &G, const FwFifoFrame &B)
     G.depth++;
     return true;
 }
+
+// ---- the far tier (round 32): a group of up to FW_FUSE_FAR frames, the same fold with longer tables.  fw_fuse2_ok and fw_fuse2_frame ask
+// nothing of the depth; FwFuseGroup, fw_fuse_push and FW_FUSE_MAX stay what they were -- the first tier's kernels, their argument record
+// (FwFuseArgs) and the tests that pin them hold eight frames.  What the kernels of the far tier read of frames 7 to FW_FUSE_FAR - 2 travels
+// in a record of its own (FwFarArgs, fw_kernels.h); who may go this deep: launch_fifo (fw_ctx::fuse_far_min, fuse_far_depth).
+#define FW_FUSE_FAR 16
+// (what fw_ctx::fuse_far_depth starts at: FW_FUSE_MAX = the tier is off; profiles/r32/fuse_far_ab.txt says how it was chosen)
+#define FW_FUSE_FAR_DEFAULT 16
+struct FwFarGroup {
+    FwFifoFrame U;                   // the fused frame of the members so far
+    uint32_t depth;                  // members: 1 .. FW_FUSE_FAR
+    uint32_t spawn_end[FW_FUSE_FAR]; // as FwFuseGroup's
+    uint32_t dead[FW_FUSE_FAR];
+};
+FW_HD FwFarGroup fw_far_begin(const FwFifoFrame &A) {
+    FwFarGroup G{};
+    G.U = A, G.depth = 1u, G.spawn_end[0] = A.n_spawn, G.dead[0] = A.dead;
+    return G;
+}
+// may frame B join the group?  true: joined (G is the longer group); false: declined, G unchanged
+FW_HD bool fw_far_push(uint32_t capacity, FwFarGroup &G, const FwFifoFrame &B) {
+    if (G.depth < 1u || G.depth >= FW_FUSE_FAR || !fw_fuse2_ok(capacity, G.U, B)) return false;
+    G.U = fw_fuse2_frame(G.U, B);
+    G.spawn_end[G.depth] = G.U.n_spawn, G.dead[G.depth] = B.dead;
+    G.depth++;
+    return true;
+}

@@ -231,7 +231,7 @@ __device__ __forceinline__ void fw_fifo_nest_parents(const FwGlobals &g, const F
 // forms find out per workgroup is a fact of the instantiation, so a tile reserves no register for Q2 / Q3 -- 88 VGPRs instead of 110, a
 // fifth workgroup per CU.  The spawning workgroups keep the type's true record: a new particle gets its one update whole -- but for the
 // spin, where the launch defers its newborns' too (round 27: nb_defer, below).
-// FUSE: 0, or the launch runs FUSE = 2 .. FW_FUSE_MAX frames of every ring in one pass (FwFifoArgs::fused; the host withheld all but the last:
+// FUSE: 0, or the launch runs FUSE = 2 .. FW_FUSE_MAX (the far tier: up to FW_FUSE_FAR) frames of every ring in one pass (FwFifoArgs::fused; the host withheld all but the last:
 // fw_fuse2.h; `fz`: their dt and boundaries, FwFuseArgs -- the fused kernels' fourth argument, null for everybody else).
 // A particle of a FIFO ring never moves, so frame n + 1 of a slot needs nothing but frame n of the same slot: a ring tile loads position and
 // velocity once, applies dt_pre[0 .. FUSE - 2] and then dt with the update's own statements, and stores once; the spawning workgroups cover
@@ -242,7 +242,8 @@ __device__ __forceinline__ void fw_fifo_nest_parents(const FwGlobals &g, const F
 // fused forms the product launches (fw_k_update_fifo2), which then hold no spin step at all; false: a fused form spins what it spawns
 // (fw_k_update_fifo2_eager, the parent's lines), an unfused form finds out per workgroup.
 template <bool INST, int WM, int NT, int COLL, int TR, bool NEST, bool Q0PL = false, bool SPINLESS = false, int FUSE = 0, bool NBFACT = false>
-__device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl, const FwFuseArgs *fz = nullptr) {
+__device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl, const FwFuseArgs *fz = nullptr,
+                                                    const FwFarArgs *far = nullptr) {
     constexpr int BLK = FW_BLOCK;
     constexpr int NW = BLK / 64;
     constexpr int R = TR;  // (smaller ring tiles were measured for the streaming case: 2 rounds 26.7 us, 1 round 26.2 us, 4 rounds 24.6 us)
@@ -306,7 +307,25 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
     // value -- neither the Q2 nor the Q3 plane is read (every lane asks for the tile's first slot instead: one line per
     // wave, loads stay unconditional)
     static_assert(!SPINLESS || (Q0PL && !INST && TR == FW_ROUNDS), "the spin-less form: streaming launches of rings with Q0 in planes");
-    static_assert(FUSE == 0 || (SPINLESS && FUSE >= 2 && FUSE <= FW_FUSE_MAX), "several frames in one pass: the spin-less forms only, two to FW_FUSE_MAX");
+    static_assert(FUSE == 0 || (SPINLESS && FUSE >= 2 && FUSE <= FW_FUSE_FAR), "several frames in one pass: the spin-less forms only, two to FW_FUSE_FAR");
+    // dt / spawn_end / dead of WITHHELD frame f of a fused launch (f < FUSE - 1, a constant once the loops over the frames are unrolled):
+    // frames 0 .. FW_FUSE_MAX - 2 from `fz`; the frames behind them -- the far tier alone, FUSE > FW_FUSE_MAX -- from `far` (FwFarArgs,
+    // round 32).  For FUSE <= FW_FUSE_MAX `far` is null and never looked at: the code of those forms is what it was.
+    auto dt_w = [&](int f) -> float {
+        if constexpr (FUSE > FW_FUSE_MAX)
+            if (f >= FW_FAR_FIRST) return far->dt[f - FW_FAR_FIRST];
+        return fz->dt_pre[f];
+    };
+    auto spawn_end_w = [&](uint32_t jj, int f) -> uint32_t {
+        if constexpr (FUSE > FW_FUSE_MAX)
+            if (f >= FW_FAR_FIRST) return far->spawn_end[jj][f - FW_FAR_FIRST];
+        return fz->spawn_end[jj][f];
+    };
+    auto dead_w = [&](uint32_t jj, int f) -> uint32_t {
+        if constexpr (FUSE > FW_FUSE_MAX)
+            if (f >= FW_FAR_FIRST) return far->dead[jj][f - FW_FAR_FIRST];
+        return fz->dead[jj][f];
+    };
     const bool nospin = SPINLESS || (F.type_idx & FW_TYPE_IDX_NOSPIN) != 0u;  // (only ring tiles ask)
     // a ring under the axis rule (FW_TYPE_IDX_AXIS, fw_device.h: host-proved, per launch): of rotation and angular velocity only the
     // axis' own component -- and the rotation's w -- is loaded; the other registers get the +0 their planes hold.  Workgroup-uniform
@@ -382,8 +401,8 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
             unsigned long long all_sum = 0ull;
 #pragma unroll
             for (int f = 0; f < FUSE; f++) {
-                const uint32_t sp_end = f < FUSE - 1 ? fz->spawn_end[j][f] : F.n_spawn;
-                const uint32_t dead_f = f < FUSE - 1 ? fz->dead[j][f] : n_dead - dead_done;
+                const uint32_t sp_end = f < FUSE - 1 ? spawn_end_w(j, f) : F.n_spawn;
+                const uint32_t dead_f = f < FUSE - 1 ? dead_w(j, f) : n_dead - dead_done;
                 nc_prev = nc;
                 all_f = nc_prev + (sp_end - sp_done);
                 nc = all_f - min(dead_f, all_f);
@@ -432,7 +451,7 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
                 float4 q0w = wq0[r], q1w = wq1[r];
 #pragma unroll
                 for (int f = 0; f < FUSE - 1; f++) {
-                    const FwMove mv = fw_move_step(K, fz->dt_pre[f], q0w, q1w);
+                    const FwMove mv = fw_move_step(K, dt_w(f), q0w, q1w);
                     q0w.x = mv.px, q0w.y = mv.py, q0w.z = mv.pz;
                     q1w.x = mv.vx, q1w.y = mv.vy, q1w.z = mv.vz;
                 }
@@ -544,8 +563,8 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
             // frame's pointer with it, group_launched)
 #pragma unroll
             for (int f = 0; f < FUSE - 1; f++) {
-                const float dt_f = fz->dt_pre[f];
-                if (is_new && k < fz->spawn_end[j][f]) {
+                const float dt_f = dt_w(f);
+                if (is_new && k < spawn_end_w(j, f)) {
                     float age_a;
                     bad |= !fw_survives(so.q0.w, dt_f, so.q3.w, &age_a);  // (the host fuses no group in which a newborn dies)
                     const FwMove mv = fw_move_step(T, dt_f, so.q0, so.q1);
@@ -625,7 +644,7 @@ __device__ __forceinline__ void fw_update_fifo_body(const FwGlobals &g, const Fw
             if constexpr (FUSE != 0) {  // the withheld frames, in order, in registers: nothing of a spin-less tile but the translation (and the age, where kept)
 #pragma unroll
                 for (int f = 0; f < FUSE - 1; f++) {
-                    const float dt_f = fz->dt_pre[f];
+                    const float dt_f = dt_w(f);
                     const FwMove mv = fw_move_step(Tt, dt_f, q0c, q1c);
                     q0c = make_float4(mv.px, mv.py, mv.pz, q0c.w + dt_f);
                     q1c.x = mv.vx, q1c.y = mv.vy, q1c.z = mv.vz;
@@ -737,6 +756,15 @@ __global__ __launch_bounds__(FW_BLOCK) __attribute__((amdgpu_waves_per_eu(FW_FIF
 template <int D, int WM, int NT>
 __global__ __launch_bounds__(FW_BLOCK) __attribute__((amdgpu_waves_per_eu(FW_FIFO_WAVES))) void fw_k_update_fifo2_eager(FwGlobals g, FwFifoArgs a, FwInlineOps inl, FwFuseArgs fz) {
     fw_update_fifo_body<false, WM, NT, 0, FW_ROUNDS, false, true, true, D, false>(g, a, inl, &fz);
+}
+// ... and the far tier (round 32): D = FW_FUSE_MAX + 1 .. FW_FUSE_FAR frames, the same arm with the withheld frames from FW_FAR_FIRST on in
+// a FIFTH argument, FwFarArgs.  Instantiated in fw_k_rings_far.hip and nowhere else; the NBFACT forms only.  Five waves, no scratch, nothing
+// pinned (profiles/r32/resource_usage.txt, tests/test_fuse_far_occupancy.py)
+template <int D, int WM, int NT>
+__global__ __launch_bounds__(FW_BLOCK) __attribute__((amdgpu_waves_per_eu(FW_FIFO_WAVES))) void fw_k_update_fifo_far(FwGlobals g, FwFifoArgs a, FwInlineOps inl, FwFuseArgs fz,
+                                                                                                                    FwFarArgs far) {
+    static_assert(D > FW_FUSE_MAX && D <= FW_FUSE_FAR, "the far tier's depths");
+    fw_update_fifo_body<false, WM, NT, 0, FW_ROUNDS, false, true, true, D, true>(g, a, inl, &fz, &far);
 }
 // ... with Nested entries inside the launch (FwFifoNest).  A kernel of its own so that the plain instantiations keep their code
 // and their register budget; pinned at 4 waves per SIMD (the nest phase took the four-round form to 133 VGPRs: the bulk of such

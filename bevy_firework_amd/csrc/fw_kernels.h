@@ -298,6 +298,19 @@ struct FwFuseArgs {
 static_assert(sizeof(FwFuseArgs) == 32 + 2 * FW_FIFO_PER_LAUNCH * (FW_FUSE_MAX - 1) * 4 + FW_FIFO_PER_LAUNCH * 16,
               "dt_pre and a pad word, two tables of FW_FUSE_MAX - 1 words per ring, four words per ring");
 static_assert(sizeof(FwGlobals) + sizeof(FwFifoArgs) + sizeof(FwInlineOps) + sizeof(FwFuseArgs) <= 4096, "the fused kernels' arguments fit the 4096-byte kernel-argument limit");
+// The far tier (round 32): a launch of depth 9 .. FW_FUSE_FAR.  Withheld frames 0 .. FW_FUSE_MAX - 2 stay where the first tier keeps them,
+// FwFuseArgs -- no argument of anybody moves --; withheld frames FW_FUSE_MAX - 1 .. FW_FUSE_FAR - 2 travel here, a FIFTH argument of the
+// far kernels alone (fw_k_rings_far.hip): index f - (FW_FUSE_MAX - 1).  fw_update_fifo_body reads a withheld frame through one accessor
+// that picks the record by the frame's compile-time index.
+#define FW_FAR_FIRST (FW_FUSE_MAX - 1)
+struct FwFarArgs {
+    float dt[FW_FUSE_FAR - FW_FUSE_MAX];
+    uint32_t spawn_end[FW_FIFO_PER_LAUNCH][FW_FUSE_FAR - FW_FUSE_MAX];
+    uint32_t dead[FW_FIFO_PER_LAUNCH][FW_FUSE_FAR - FW_FUSE_MAX];
+};
+static_assert(sizeof(FwFarArgs) == (FW_FUSE_FAR - FW_FUSE_MAX) * 4 * (1 + 2 * FW_FIFO_PER_LAUNCH), "one dt and, per ring, two boundaries per far frame");
+static_assert(sizeof(FwGlobals) + sizeof(FwFifoArgs) + sizeof(FwInlineOps) + sizeof(FwFuseArgs) + sizeof(FwFarArgs) <= 4096,
+              "the far kernels' arguments fit the 4096-byte kernel-argument limit");
 
 // ---- range rings: particle types whose lifetime is a RANGE, updated in place ---------------------------------------
 // Ages never increase along the particle list (everybody is born with age 0 behind all older particles and every update
@@ -408,6 +421,11 @@ hipError_t fw_launch_update_fifo2(hipStream_t s, const FwGlobals &g, const FwFif
 // (... and its forms whose spawning workgroups find out whether they spin what they spawn: fw_k_rings_fuse2_eager.hip, round 27)
 hipError_t fw_launch_update_fifo2_eager(hipStream_t s, const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl, const FwFuseArgs &fz,
                                         uint32_t total_tiles, int nt, hipEvent_t e0, hipEvent_t e1);
+// (the far tier, FwFifoArgs::fused = FW_FUSE_MAX + 1 .. FW_FUSE_FAR: fw_k_rings_far.hip; the host calls it for such a launch itself --
+// enqueue_fifo --, so fw_launch_update_fifo and the units behind it compile to what they compiled to.  No eager forms: under
+// FW_NEWBORN_SPIN=1 the host closes its groups at FW_FUSE_MAX)
+hipError_t fw_launch_update_fifo_far(hipStream_t s, const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl, const FwFuseArgs &fz,
+                                     const FwFarArgs &far, uint32_t total_tiles, int nt, hipEvent_t e0, hipEvent_t e1);
 hipError_t fw_launch_update_fifo(hipStream_t s, const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl,
                                  uint32_t total_tiles, int nt, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, const FwFuseArgs *fz = nullptr);
 uint32_t fw_range_young_tile(void);  // ring slots a YOUNG workgroup of fw_k_update_range covers (a build-time choice)

@@ -107,7 +107,10 @@ fw_status fw_debug_newborn_spin(fw_ctx *ctx, uint64_t *launches);
  * withheld only when its one launch is spin-less, every ring of it deferred its spin in it and holds FW_FUSE2_MIN particles (default
  * 384 tiles); a group grows beyond two frames, up to FW_FUSE_DEPTH (2 to 8, default 8), only where every ring holds FW_FUSE_DEEP_MIN
  * particles (default 768 tiles), and beyond four only where every ring holds FW_FUSE_WIDE_MIN as well (default 768 tiles).  A launch
- * whose rings carry more than one spawn op per frame closes its groups earlier: eight ops travel in a launch.  FW_FUSE2=0 (with
+ * whose rings carry more than one spawn op per frame closes its groups earlier: eight ops travel in a launch.  Round 32, the far
+ * tier: with FW_FUSE_DEPTH unset or 8 a group grows up to FW_FUSE_FAR_DEPTH frames (8 to 16, 8 = off, default 16) where every ring holds
+ * FW_FUSE_FAR_MIN particles too (default 768 tiles); there, consecutive frames' ops of an emitter that stands still travel as one op.
+ * FW_FUSE2=0 (with
  * FW_ENABLE_KNOBS) withholds nothing: both stay 0.  Either pointer may be null */
 fw_status fw_debug_fuse2(fw_ctx *ctx, uint64_t *fused, uint64_t *flushed);
 /* *frames = the frames run by fused launches so far: a launch that ran D frames counts D (so *frames / *fused is the mean depth) */

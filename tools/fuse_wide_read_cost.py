@@ -4,7 +4,8 @@ configs[1]'s 1M-particle ring at product thresholds, 40 unread frames to earn th
 frames, stepped on until seven frames are pending (the counters say so), and fw_spawner_pack_instances_device + a wait for the stream.
 The device is waited for before the clock starts WITHOUT going through the library (torch.cuda.synchronize: the group stays kept), so the
 figure is the group's one fused launch, the replay of the spin and the pack.  FW_FUSE2=1 against FW_FUSE2=0, medians of six.  Prints
-one JSON line per setting."""
+one JSON line per setting.
+(round 32: FW_READ_PENDING=15 waits for fifteen pending frames instead -- the far tier at its default depth of sixteen.)"""
 import os as _os; _os.environ.setdefault("FW_ENABLE_KNOBS", "1"); _os.environ.setdefault("FW_FUSE_DEPTH", "8")  # (seven pending needs a depth of eight, the default or not)
 import json, os, sys, time
 import numpy as np
@@ -14,6 +15,7 @@ from bevy_firework_amd import workloads
 from bevy_firework_amd.system import ParticleSystem
 
 dt = np.float32(1 / 60)
+PENDING = int(os.environ.get("FW_READ_PENDING", "7"))
 for rule in ("1", "0"):
     os.environ["FW_FUSE2"] = rule
     ps = ParticleSystem(seed=workloads.SEED)
@@ -30,7 +32,7 @@ for rule in ("1", "0"):
                 f0 = ps.fuse2_launches()
                 ps.step(dt)
                 pending = pending + 1 if ps.fuse2_launches() == f0 else 0
-                if k >= 40 + unread and (pending == 7 or rule == "0"):
+                if k >= 40 + unread and (pending == PENDING or rule == "0"):
                     break
             torch.cuda.synchronize()
             f0, n0 = ps.fuse2_launches(), ps.fuse_frames()
