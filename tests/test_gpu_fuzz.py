@@ -1,6 +1,8 @@
 """Randomised parity: random spawner settings (curve kinds and key counts, shapes, pacings with offsets, several
 emission entries per type, Nested entries, drag / acceleration, modifiers, transforms) and irregular step sequences,
 HIP path against the CPU oracle through the C ABI.  Sizes are kept where the oracle finishes in about a second per case.
+(Deferred spin and fused FIFO launches have their own random suite, tests/test_gpu_fifo_fuzz.py: these cases run at the product's
+thresholds, draw angular velocities with a cone and read every sixth frame, so none of them ever meets that machinery.)
 Needs an MI355X."""
 import math
 import os
