@@ -37,7 +37,14 @@ struct FwRayHit {
     fw_v3 normal;
 };
 
+// WATERTIGHT (include/firework_hip.h: fw_mesh_collider): the margin of the triangle test is FW_WT_K |s|_1 (|e1|_1 + |e2|_1) / |det|,
+// at most FW_WT_CAP.  8 * 2^-24 is 15 times the largest margin any leaking ray of tests/mesh_exact.py's families needed.
+#define FW_WT_K 4.76837158203125e-07f  // 8 * 2^-24
+#define FW_WT_CAP 0.00390625f          // 2^-8
+#define FW_WT_BOX 0.015625f            // 2^-6 = 2 * (2 * FW_WT_CAP): what the walk grows a box by, as a share of its extent (fw_cast_ray)
+
 FW_HD float fw_len3(fw_v3 a) { return sqrtf(fw_dot3(a, a)); }
+FW_HD float fw_abs1(fw_v3 a) { return (fabsf(a.x) + fabsf(a.y)) + fabsf(a.z); }
 FW_HD fw_v3 fw_scale3(fw_v3 a, float s) { return fw_v3{a.x * s, a.y * s, a.z * s}; }
 FW_HD fw_v3 fw_add3(fw_v3 a, fw_v3 b) { return fw_v3{a.x + b.x, a.y + b.y, a.z + b.z}; }
 FW_HD fw_v3 fw_sub3(fw_v3 a, fw_v3 b) { return fw_v3{a.x - b.x, a.y - b.y, a.z - b.z}; }
@@ -317,7 +324,8 @@ FW_HD bool fw_cast_ray(const FwCollider *colliders, uint32_t n, const FwMeshInst
 #ifdef __HIP_DEVICE_COMPILE__
         {  // the wave skip of the analytic loop, against the sphere that contains the placed mesh
             const fw_v3 dc = fw_sub3(origin, fw_v3{M.center[0], M.center[1], M.center[2]});
-            const float reach = M.position[3] + max_distance;
+            // (WATERTIGHT: a ray the margin accepts may end that far outside the root's box)
+            const float reach = M.position[3] * (1.0f + 2.0f * FW_WT_BOX) + max_distance;
             const bool far = fw_dot3(dc, dc) > reach * reach * 1.0001f + 1e-12f;
             if (__ballot(!far) == 0ull) continue;
         }
@@ -340,13 +348,19 @@ FW_HD bool fw_cast_ray(const FwCollider *colliders, uint32_t n, const FwMeshInst
             const float cut = (any ? bd : max_distance) * 1.0001f;
             float tn = -INFINITY, tf = INFINITY;
             bool hit = true;
+            // (WATERTIGHT: the triangle test accepts a ray that passes up to FW_WT_CAP of a triangle's edges outside it, and the
+            // rounding it covers is as large again: such a ray is within FW_WT_BOX of the extent of every box that holds the
+            // triangle, on every axis -- each box is tested grown by that much of its own extent)
 #define FW_NODE_SLAB(o, d, inv, l, h)                                          \
-    if ((d) == 0.0f) {                                                         \
-        if ((o) < (l) || (o) > (h)) hit = false;                               \
-    } else {                                                                   \
-        const float t1 = ((l) - (o)) * (inv), t2 = ((h) - (o)) * (inv);        \
-        tn = fmaxf(tn, fminf(t1, t2));                                         \
-        tf = fminf(tf, fmaxf(t1, t2));                                         \
+    {                                                                          \
+        const float g = ((h) - (l)) * FW_WT_BOX, gl = (l) - g, gh = (h) + g;   \
+        if ((d) == 0.0f) {                                                     \
+            if ((o) < gl || (o) > gh) hit = false;                             \
+        } else {                                                               \
+            const float t1 = (gl - (o)) * (inv), t2 = (gh - (o)) * (inv);      \
+            tn = fmaxf(tn, fminf(t1, t2));                                     \
+            tf = fminf(tf, fmaxf(t1, t2));                                     \
+        }                                                                      \
     }
             FW_NODE_SLAB(ol.x, dl.x, ix, lo.x, hi.x)
             FW_NODE_SLAB(ol.y, dl.y, iy, lo.y, hi.y)
@@ -369,7 +383,11 @@ FW_HD bool fw_cast_ray(const FwCollider *colliders, uint32_t n, const FwMeshInst
                     const fw_v3 qv = fw_cross(s, e1);
                     const float v = fw_dot3(dl, qv) * inv;
                     const float t = fw_dot3(e2, qv) * inv;
-                    if (!(u >= 0.0f && v >= 0.0f && u + v <= 1.0f && t >= 0.0f && t <= max_distance)) continue;
+                    // WATERTIGHT (include/firework_hip.h): two triangles evaluate their shared edge with different operands, so
+                    // an exact `u >= 0` lets a ray near the edge be rejected by both.  The margin is the rounding of u and v scaled
+                    // by their own operands; the cap keeps an accepted ray inside the leaf's box as the walk grows it (FW_WT_BOX).
+                    const float wm = fminf(((FW_WT_K * fw_abs1(s)) * (fw_abs1(e1) + fw_abs1(e2))) * fabsf(inv), FW_WT_CAP);
+                    if (!(u >= -wm && v >= -wm && u + v <= 1.0f + wm && t >= 0.0f && t <= max_distance)) continue;
                     const uint32_t orig = __builtin_bit_cast(uint32_t, a.w);
                     if (!any || t < bd || (t == bd && borig != 0xFFFFFFFFu && orig < borig)) {
                         bd = t, any = true, bslot = k, borig = orig;

@@ -173,8 +173,25 @@ typedef struct fw_collider {
  *               p = cross(d, e2); det = dot(e1, p); det == 0 is a miss; inv = 1 / det; s = o - v0; u = dot(s, p) * inv;
  *               q = cross(s, e1); v = dot(d, q) * inv; t = dot(e2, q) * inv
  *             (dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z; cross(a, b) = (a.y b.z - b.y a.z, a.z b.x - b.z a.x, a.x b.y - b.x a.y));
- *             a hit needs u >= 0, v >= 0, u + v <= 1 and 0 <= t <= max_distance.
- *   NORMAL    c = cross(e1, e2); n = c * (1 / sqrt(dot(c, c))), rotated by R, and negated when dot(n, dir) > 0.
+ *             a hit needs u >= -m, v >= -m, u + v <= 1 + m and 0 <= t <= max_distance, with the margin m of WATERTIGHT.
+ *   WATERTIGHT  two triangles that share an edge evaluate it with different operands (their own v0, e1, e2), so with m = 0 a
+ *             ray near the edge can be rejected by both and pass through a closed surface.  The margin is the rounding of u and
+ *             v stated in their own operands:
+ *               m = min(((2^-21 * |s|_1) * (|e1|_1 + |e2|_1)) * |inv|, 2^-8),   |a|_1 = (|a.x| + |a.y|) + |a.z|
+ *             (2^-21 = 8 * 2^-24: fifteen times the largest margin any ray that used to leak needed; fmin, so a NaN product gives
+ *             the cap).  What it buys, against a float64 cast over every triangle: a ray whose line passes inside the mesh's
+ *             silhouette by 0.05 of the mesh's largest |coordinate| and crosses the surface within max_distance reports a hit no
+ *             later than t_ref + 2^-14 (t_ref + that coordinate) -- NO LEAK.  What it costs: a ray may hit a triangle it passes up
+ *             to m of its edges outside of; a hit met at |cos| >= 0.5 still lies within 2^-13 (|o - v0| + |e1| + |e2|) of its
+ *             triangle, and a ray farther than that from every triangle hits nothing -- NO INVENTION.  Every ray the rule with
+ *             m = 0 hits is still hit, no later, and the same triangle gives the same distance and normal bit for bit.
+ *             DOMAIN: the brute force over every triangle (the C oracle's) is held to NO LEAK for origins up to 1024 times the
+ *             mesh's largest |coordinate| away.  The device walks a hierarchy of boxes and tests each box grown by 2^-6 of its
+ *             own extent, which holds every ray the margin accepts while its rounding stays below the cap: the walk is held to
+ *             NO LEAK, and to the brute force's result bit for bit, wherever |s|_1 (|e1|_1 + |e2|_1) <= 2^13 |det| for the
+ *             triangle crossed (the margin is then below its cap) -- a well-shaped triangle of edge e met at angle cos from
+ *             a distance of up to about 2^11 e cos.  (tests/test_mesh_watertight_cpu.py, tests/test_gpu_mesh_watertight.py)
+ *   NORMAL   c = cross(e1, e2); n = c * (1 / sqrt(dot(c, c))), rotated by R, and negated when dot(n, dir) > 0.
  *   TIES      the nearest hit wins; at equal distance analytic colliders come before mesh instances, lower instance indices
  *             before higher ones, and within an instance the lower ORIGINAL triangle index (position in `indices`) wins.
  *   FILTER    an instance takes part when (filter_mask & layers) != 0, as a collider does.

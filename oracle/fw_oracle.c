@@ -157,6 +157,7 @@ void fwo_gradient_sample_clamped(const fwo_gradient *g, float t, float out[4]) {
 /* ------------------------------------------------------------------------- */
 
 static float v3_dot(const float a[3], const float b[3]) { return (a[0] * b[0]) + (a[1] * b[1]) + (a[2] * b[2]); }
+static float v3_abs1(const float a[3]) { return (fabsf(a[0]) + fabsf(a[1])) + fabsf(a[2]); }
 static void v3_cross(const float a[3], const float b[3], float o[3]) {
     float x = a[1] * b[2] - b[1] * a[2];
     float y = a[2] * b[0] - b[2] * a[0];
@@ -613,7 +614,9 @@ static int ray_mesh_instance(const fwo_mesh_collider *in, const float o[3], cons
         v3_cross(s, e1, q);
         float v = v3_dot(dl, q) * inv;
         float t = v3_dot(e2, q) * inv;
-        if (!(u >= 0.0f && v >= 0.0f && u + v <= 1.0f && t >= 0.0f && t <= max_distance)) continue;
+        /* WATERTIGHT: the margin 8 * 2^-24 |s|_1 (|e1|_1 + |e2|_1) / |det|, at most 2^-8 */
+        float wm = fminf(((4.76837158203125e-07f * v3_abs1(s)) * (v3_abs1(e1) + v3_abs1(e2))) * fabsf(inv), 0.00390625f);
+        if (!(u >= -wm && v >= -wm && u + v <= 1.0f + wm && t >= 0.0f && t <= max_distance)) continue;
         if (!any || t < best_t) best_t = t, best = k, any = 1; /* kept triangles are in input order: `<` keeps the lower index */
     }
     if (!any) return 0;

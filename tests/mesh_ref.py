@@ -41,6 +41,7 @@ class Mesh:
         keep = np.isfinite(cc) & (cc > 0)
         self.vertices, self.indices = xyz, idx
         self.v0, self.e1, self.e2, self.orig = v0[keep], e1[keep], e2[keep], np.flatnonzero(keep)
+        self.ee = (abs1(self.e1) + abs1(self.e2)).astype(f32)  # WATERTIGHT: |e1|_1 + |e2|_1
         with np.errstate(divide="ignore", invalid="ignore"):
             self.normal = (c[keep] * (ONE / np.sqrt(cc[keep]).astype(f32)).astype(f32)[:, None]).astype(f32)
 
@@ -59,17 +60,39 @@ class World:
     instances: List[Instance] = field(default_factory=list)
 
 
-def cast_instance(inst: Instance, origin, d, max_distance, chunk_elems=1 << 21):
-    """-> (hit, t, normal) of the nearest triangle of one instance for each ray (lowest original index on ties)"""
-    n = len(origin)
+WT_K = f32(2.0 ** -21)  # WATERTIGHT: 8 * 2^-24, the margin's factor
+WT_CAP = f32(2.0 ** -8)  # ... and its cap
+
+
+def abs1(a):
+    """(|a.x| + |a.y|) + |a.z|, fp32"""
+    a = np.abs(a)
+    return ((a[..., 0] + a[..., 1]).astype(f32) + a[..., 2]).astype(f32)
+
+
+def into_frame(inst: Instance, origin, d):
+    """the header's FRAME: o = R^-1 (origin - position), d = R^-1 dir; the identity rotation skips both products"""
     q = np.asarray(inst.rotation, dtype=f32)
     pos = np.asarray(inst.position, dtype=f32)
+    if q[0] == 0 and q[1] == 0 and q[2] == 0 and q[3] == 1:
+        return (origin - pos).astype(f32), d.astype(f32)
+    qi = np.broadcast_to(np.array([-q[0], -q[1], -q[2], q[3]], dtype=f32), (len(origin), 4))
+    return quat_mul_vec3(qi, (origin - pos).astype(f32)), quat_mul_vec3(qi, d)
+
+
+def cast_instance(inst: Instance, origin, d, max_distance, chunk_elems=1 << 21):
+    """-> (hit, t, normal) of the nearest triangle of one instance for each ray (lowest original index on ties)"""
+    return cast_instance_full(inst, origin, d, max_distance, chunk_elems)[:3]
+
+
+def cast_instance_full(inst: Instance, origin, d, max_distance, chunk_elems=1 << 21, watertight=True):
+    """-> (hit, t, normal, k): cast_instance and the index k, among the KEPT triangles, of the one that was hit.  watertight=False:
+    the header's TRIANGLE without its WATERTIGHT margin (u >= 0, v >= 0, u + v <= 1) -- the rule before the margin, kept so that
+    the two can be compared (tests/mesh_exact.py: strict_cast)"""
+    n = len(origin)
+    q = np.asarray(inst.rotation, dtype=f32)
     aligned = q[0] == 0 and q[1] == 0 and q[2] == 0 and q[3] == 1
-    if aligned:
-        ol, dl = (origin - pos).astype(f32), d.astype(f32)
-    else:
-        qi = np.broadcast_to(np.array([-q[0], -q[1], -q[2], q[3]], dtype=f32), (n, 4))
-        ol, dl = quat_mul_vec3(qi, (origin - pos).astype(f32)), quat_mul_vec3(qi, d)
+    ol, dl = into_frame(inst, origin, d)
     m = inst.mesh
     hit = np.zeros(n, dtype=bool)
     best_t = np.full(n, np.inf, dtype=f32)
@@ -90,7 +113,11 @@ def cast_instance(inst: Instance, origin, d, max_distance, chunk_elems=1 << 21):
             v = (dot3(np.broadcast_to(D, qv.shape), qv) * inv).astype(f32)
             t = (dot3(np.broadcast_to(m.e2[None], qv.shape), qv) * inv).astype(f32)
             mdc = md[a:b, None] if md.ndim else md
-            ok = (det != 0) & (u >= 0) & (v >= 0) & ((u + v).astype(f32) <= 1) & (t >= 0) & (t <= mdc)
+            if watertight:
+                mg = np.fmin((((WT_K * abs1(s)).astype(f32) * m.ee[None]).astype(f32) * np.abs(inv)).astype(f32), WT_CAP)
+            else:
+                mg = ZERO
+            ok = (det != 0) & (u >= -mg) & (v >= -mg) & ((u + v).astype(f32) <= (ONE + mg).astype(f32)) & (t >= 0) & (t <= mdc)
             tt = np.where(ok, t, f32(np.inf))
             j = np.argmin(tt, axis=1)  # the first minimum: the lowest original index (kept triangles are in input order)
             hit[a:b] = ok.any(axis=1)
@@ -101,7 +128,7 @@ def cast_instance(inst: Instance, origin, d, max_distance, chunk_elems=1 << 21):
             nrm = quat_mul_vec3(np.broadcast_to(q, (n, 4)), nrm)
         flip = dot3(nrm, d) > 0
         nrm = np.where(flip[:, None], (-nrm).astype(f32), nrm).astype(f32)
-    return hit, best_t, nrm
+    return hit, best_t, nrm, best_j
 
 
 def cast_ray(world, mask, origin, d, max_distance):

@@ -15,6 +15,7 @@ import mesh_ref  # noqa: E402
 from mesh_ref import np_sim  # noqa: E402
 
 f32 = np.float32
+WT_BOX = f32(2.0 ** -6)  # fw_collide.h: FW_WT_BOX
 WRAPPER = r"""
 #include "fw_bvh.h"
 #include <cstring>
@@ -243,9 +244,10 @@ def test_mesh_ref_tie_rule():
             assert (nrm[0] == want).all(), nrm
 
 
-def device_walk(nodes, tris, o, d, maxd):
+def device_walk(nodes, tris, o, d, maxd, slots=False):
     """the kernels' stackless walk of one instance (fw_collide.h: fw_cast_ray), replayed in numpy fp32 over many rays at once:
-    slab test with the lane's running cut, the triangle test, the tie rule inside the instance -> (hit, t, normal)"""
+    slab test with the lane's running cut, the triangle test, the tie rule inside the instance -> (hit, t, normal), the normal
+    in the instance's frame; slots=True: -> (hit, t, slot of the triangle that was hit or -1)"""
     n, N = len(o), len(nodes)
     esc, leaf = u32(nodes[:, 3]).astype(np.int64), u32(nodes[:, 7]).astype(np.int64)
     i = np.zeros(n, dtype=np.int64)
@@ -270,9 +272,11 @@ def device_walk(nodes, tris, o, d, maxd):
             hit = np.ones(len(idx), dtype=bool)
             for a in range(3):
                 z = D[:, a] == 0
-                hit &= ~(z & ((O[:, a] < lo[:, a]) | (O[:, a] > hi[:, a])))
-                t1 = ((lo[:, a] - O[:, a]).astype(f32) * IV[:, a]).astype(f32)
-                t2 = ((hi[:, a] - O[:, a]).astype(f32) * IV[:, a]).astype(f32)
+                g = ((hi[:, a] - lo[:, a]).astype(f32) * WT_BOX).astype(f32)  # WATERTIGHT: each box grown by a share of its extent
+                gl, gh = (lo[:, a] - g).astype(f32), (hi[:, a] + g).astype(f32)
+                hit &= ~(z & ((O[:, a] < gl) | (O[:, a] > gh)))
+                t1 = ((gl - O[:, a]).astype(f32) * IV[:, a]).astype(f32)
+                t2 = ((gh - O[:, a]).astype(f32) * IV[:, a]).astype(f32)
                 tn = np.where(z, tn, np.fmax(tn, np.fmin(t1, t2))).astype(f32)
                 tf = np.where(z, tf, np.fmin(tf, np.fmax(t1, t2))).astype(f32)
             hit &= (tn <= tf) & (tf >= 0) & ~(tn > cut)
@@ -294,12 +298,16 @@ def device_walk(nodes, tris, o, d, maxd):
                 q = cross3(S_, e1)
                 v = (dot3(Dr, q) * iv).astype(f32)
                 t = (dot3(e2, q) * iv).astype(f32)
-                ok = (det != 0) & (u >= 0) & (v >= 0) & ((u + v).astype(f32) <= 1) & (t >= 0) & (t <= maxd[r])
+                ee = (mesh_ref.abs1(e1) + mesh_ref.abs1(e2)).astype(f32)
+                mg = np.fmin((((mesh_ref.WT_K * mesh_ref.abs1(S_)).astype(f32) * ee).astype(f32) * np.abs(iv)).astype(f32), mesh_ref.WT_CAP)  # WATERTIGHT
+                ok = (det != 0) & (u >= -mg) & (v >= -mg) & ((u + v).astype(f32) <= (f32(1) + mg).astype(f32)) & (t >= 0) & (t <= maxd[r])
                 orig = u32(tris[slot, 3]).astype(np.int64)
                 acc = ok & (~anyh[r] | (t < bd[r]) | ((t == bd[r]) & (borig[r] != 0xFFFFFFFF) & (orig < borig[r])))
                 ra = r[acc]
                 bd[ra], anyh[ra], bslot[ra], borig[ra] = t[acc], True, slot[acc], orig[acc]
             i[idx] = np.maximum(nxt, k + 1)
+        if slots:
+            return anyh, bd, bslot
         got = bslot >= 0
         c = cross3(tris[bslot[got], 4:7], tris[bslot[got], 8:11])
         nrm = np.zeros((n, 3), dtype=f32)

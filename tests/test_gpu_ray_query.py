@@ -233,7 +233,10 @@ def _moller_trumbore(o, d, v0, e1, e2, md):
         q = _cross(s, e1)
         v = (_dot(d, q).astype(f32) * inv).astype(f32)
         t = (_dot(e2, q).astype(f32) * inv).astype(f32)
-        hit = (det != 0) & (u >= 0) & (v >= 0) & ((u + v).astype(f32) <= 1) & (t >= 0) & (t <= md)
+        # WATERTIGHT: the margin 8 * 2^-24 |s|_1 (|e1|_1 + |e2|_1) / |det|, at most 2^-8
+        a1 = lambda a: ((np.abs(a[..., 0]) + np.abs(a[..., 1])).astype(f32) + np.abs(a[..., 2])).astype(f32)  # noqa: E731
+        m = np.fmin((((f32(2.0 ** -21) * a1(s)).astype(f32) * (a1(e1) + a1(e2)).astype(f32)).astype(f32) * np.abs(inv)).astype(f32), f32(2.0 ** -8))
+        hit = (det != 0) & (u >= -m) & (v >= -m) & ((u + v).astype(f32) <= (f32(1.0) + m).astype(f32)) & (t >= 0) & (t <= md)
     return hit, t
 
 

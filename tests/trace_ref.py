@@ -53,7 +53,9 @@ def _triangle(inst, o, d, md, t):
         qv = cross3(s, E1)
         v = (dot3(D, qv) * inv).astype(f32)
         tt = (dot3(E2, qv) * inv).astype(f32)
-        ok = (det != 0) & (u >= 0) & (v >= 0) & ((u + v).astype(f32) <= 1) & (tt >= 0) & (tt <= md[:, None]) & (tt == t[:, None])
+        mg = np.fmin((((mesh_ref.WT_K * mesh_ref.abs1(s)).astype(f32) * m.ee[None]).astype(f32) * np.abs(inv)).astype(f32), mesh_ref.WT_CAP)  # WATERTIGHT
+        ok = ((det != 0) & (u >= -mg) & (v >= -mg) & ((u + v).astype(f32) <= (f32(1.0) + mg).astype(f32)) & (tt >= 0) & (tt <= md[:, None])
+              & (tt == t[:, None]))
     assert ok.any(axis=1).all(), "a mesh hit no triangle reproduces"
     return m.orig[np.argmax(ok, axis=1)].astype(np.uint32)
 
