@@ -462,10 +462,7 @@ fw_status enqueue_fifo(fw_ctx *ctx, const FwFifoLaunch &L, hipStream_t stream, h
     if (fused) ctx->fused_launches++, ctx->fuse_frames += L.depth;
     else if (L.held) ctx->fuse2_flushed++;
     count_whole_tiles(ctx, L.fa), count_newborn(ctx, L.fa);
-    if (L.depth > FW_FUSE_MAX)  // (the far tier's kernels, a unit of their own: fw_k_rings_far.hip)
-        FW_HIP(ctx, fw_launch_update_fifo_far(stream, ctx->g, L.fa, L.fio, L.fz, L.far, L.tiles, L.nt, e0, e1));
-    else
-        FW_HIP(ctx, fw_launch_update_fifo(stream, ctx->g, L.fa, L.fio, L.tiles, L.nt, e0, e1, fused ? &L.fz : nullptr));
+    FW_HIP(ctx, fw_launch_update_fifo(stream, ctx->g, L.fa, L.fio, L.tiles, L.nt, e0, e1, fused ? &L.rec : nullptr));  // (every depth: routed there)
     return FW_OK;
 }
 
@@ -507,10 +504,8 @@ struct FifoAccum {
     uint64_t bytes = 0;    // what the launch streams, roughly: its tiles x the bytes a particle of the type moves
     bool nospin = true;    // every ring of the launch so far carries FW_TYPE_IDX_NOSPIN in it (FwFifoArgs::spinless)
     bool derived = true;   // ... and is of a FW_TYPE_DERIVED type (FwFifoArgs::fuse_pad[FW_FIFO_WHOLE])
-    bool fusable = true;   // several frames in one launch: every ring so far deferred its spin in it and holds fuse2_min particles
-    bool deep = true;      // ... and holds fuse_deep_min: a group of the launch may be deeper than two frames, up to FW_FUSE_NARROW
-    bool wide = true;      // ... and fuse_wide_min: up to fw_ctx::fuse_depth
-    bool far = true;       // ... and fuse_far_min: up to fw_ctx::fuse_far_depth, the far tier
+    uint32_t rung = FW_RUNG_FAR;  // several frames in one launch: the lowest rung of the depth ladder any ring so far stands on (fw_fuse_rung,
+                           // fw_fuse2.h; FW_RUNG_NONE: a ring that did not defer its spin in the launch, or holds fewer than fuse2_min particles)
     uint32_t n_launches = 0;  // the launches of this frame so far
     bool sent = false;     // the launch has been offered: a ring that follows starts the frame's next one (most frames have one: cleared for nobody)
 
@@ -536,15 +531,10 @@ struct FifoAccum {
         // (one rule for the whole context: a fused launch, every ring of which defers under it, takes the set of kernels the word names)
         fa.fuse_pad[FW_FIFO_NEWBORN] = ctx->newborn_spin ? 0u : 1u;        L.nt = bytes > ctx->nt_bytes ? 2 : bytes > ctx->nt_wo_bytes ? 1 : 0;
         // the frame's one launch, spin-less, every ring unread and large: it may wait for the next frame, or take the waiting one in
-        const bool candidate = fw_fuse2_candidate(ctx->use_fuse2, quiet, n_launches == 0 && fa.n_segs == ctx->census.n_fifo, fa.spinless != 0u, fusable);
-        // (how deep: two frames, or fw_ctx::fuse_depth where the pass dominates the launch -- beyond FW_FUSE_NARROW only where every ring
-        // holds fuse_wide_min too)
-        const uint32_t depth_knob = std::max(2u, std::min(ctx->fuse_depth, (uint32_t)FW_FUSE_MAX));
-        // (... and beyond FW_FUSE_MAX, the far tier: the knob at FW_FUSE_MAX, the forms that defer their newborns' spin, every ring at
-        // fuse_far_min.  A depth_max above FW_FUSE_MAX is also what lets the group merge its ops: FwWithheld::offer)
-        const bool go_far = deep && wide && far && ctx->fuse_depth == (uint32_t)FW_FUSE_MAX && fa.fuse_pad[FW_FIFO_NEWBORN] != 0u && ctx->fuse_far_depth > (uint32_t)FW_FUSE_MAX;
-        if (go_far) return Words{candidate, std::min(ctx->fuse_far_depth, (uint32_t)FW_FUSE_FAR)};
-        return Words{candidate, !deep ? 2u : !wide ? std::min(depth_knob, (uint32_t)FW_FUSE_NARROW) : depth_knob};
+        const bool candidate = fw_fuse2_candidate(ctx->use_fuse2, quiet, n_launches == 0 && fa.n_segs == ctx->census.n_fifo, fa.spinless != 0u, rung >= FW_RUNG_TWO);
+        // (how deep: the launch's rung of the ladder, the knobs, and for the far tier the forms that defer their newborns' spin.  A depth_max
+        // above FW_FUSE_MAX is also what lets the group merge its ops: FwWithheld::offer)
+        return Words{candidate, fw_fuse_depth_max(rung, ctx->fuse_depth, ctx->fuse_far_depth, fa.fuse_pad[FW_FIFO_NEWBORN] != 0u)};
     }
 };
 
@@ -657,13 +647,11 @@ void ring_record(fw_ctx *ctx, const FifoFrame &ff, FifoAccum &acc, uint32_t si, 
     else if (fa.write_mask != wm) fa.write_mask = -1;
     // (a fused launch's kernels hold the rule as a fact of their code: a ring that defers its spin and not its newborns' -- none exists
     // today, `mat` is false wherever spin_ok holds -- would not be fused)
-    acc.fusable &= R.spin_defer && in.n_in >= ctx->fuse2_min && (R.newborn_defer || ctx->newborn_spin);
-    acc.deep &= in.n_in >= ctx->fuse_deep_min;
-    acc.wide &= in.n_in >= ctx->fuse_wide_min;
-    acc.far &= in.n_in >= ctx->fuse_far_min;
+    const bool defers = R.spin_defer && (R.newborn_defer || ctx->newborn_spin);
+    acc.rung = std::min(acc.rung, defers ? fw_fuse_rung(in.n_in, ctx->fuse2_min, ctx->fuse_deep_min, ctx->fuse_wide_min, ctx->fuse_far_min) : (uint32_t)FW_RUNG_NONE);
     acc.L.spin_from[fa.n_segs] = R.spin_from_new;
     // (acceleration and drag of the ring's type, for the whole tiles of a fused launch this frame may close: FwFuseArgs::move)
-    memcpy(acc.L.fz.move[fa.n_segs], S.fifo_move, sizeof S.fifo_move);
+    memcpy(acc.L.rec.fz.move[fa.n_segs], S.fifo_move, sizeof S.fifo_move);
     FwFifoSeg &F = fa.s[fa.n_segs++];
     F.buf = S.buf[0], F.destroyed = S.destroyed, F.inst = S.inst;
     F.inst_cap = S.inst_cap, F.capacity = S.capacity, F.seg = si;

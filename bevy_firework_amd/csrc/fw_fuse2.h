@@ -1,14 +1,14 @@
-// fw_fuse2.h -- up to FW_FUSE_MAX frames of an unread FIFO ring in one launch (rounds 22 to 24, FwFifoArgs::fused, FwFuseArgs: fw_kernels.h,
+// fw_fuse2.h -- up to FW_FUSE_FAR frames of an unread FIFO ring in one launch (rounds 22 to 32, FwFifoArgs::fused, FwFuseArgs and FwFarArgs: fw_kernels.h,
 // DESIGN.md 4.0).
 // A particle of a FIFO ring never moves: frame n + 1 of a slot needs nothing but frame n of the same slot.  A ring whose spin is deferred is
 // a ring nobody has looked at for a while, so the host may withhold the launch of a frame A -- all of its bookkeeping done -- and run it
-// inside the launch of a frame that follows: one load and one store per plane for two to eight updates.  The group grows frame by
+// inside the launch of a frame that follows: one load and one store per plane for two to sixteen updates.  The group grows frame by
 // frame: the withheld frames so far are ONE fused frame (fw_fuse2_frame, folded), and the pair rule between it and the next frame is the
 // rule of the group (FwFuseGroup, fw_fuse_push).  Here: what a launch lays out for a ring (the arithmetic launch_fifo has always done),
 // when a frame may join, and the fused frame with the per-frame boundaries the kernel needs.
-// Plain C++ behind FW_HD, like fw_spin.h: the host (launch_fifo) and five host tests (tests/test_cpp_host_fuse2.py, test_cpp_host_fuse_deep.py,
-// test_cpp_host_fuse_wide.py, test_cpp_host_whole_tiles.py, test_cpp_host_whole_span.py) compile the same lines -- and so does the kernel,
-// for fw_fifo_tile_whole (round 26).
+// Plain C++ behind FW_HD, like fw_spin.h: the host (launch_fifo) and the host tests (tests/test_cpp_host_fuse2.py, test_cpp_host_fuse_deep.py,
+// test_cpp_host_fuse_wide.py, test_cpp_host_fuse_far.py, test_cpp_host_fuse_ladder.py, test_cpp_host_whole_tiles.py, test_cpp_host_whole_span.py)
+// compile the same lines -- and so does the kernel, for fw_fifo_tile_whole (round 26).
 #pragma once
 #include <stdint.h>
 
@@ -117,58 +117,58 @@ FW_HD bool fw_fuse2_ok(uint32_t capacity, const FwFifoFrame &A, const FwFifoFram
 // = A.n_spawn), both frames' dead in front (FwFifoArgs::fuse_dead = A.dead)
 FW_HD FwFifoFrame fw_fuse2_frame(const FwFifoFrame &A, const FwFifoFrame &B) { return FwFifoFrame{A.head, A.n_in, A.n_spawn + B.n_spawn, A.dead + B.dead}; }
 
-// ---- a group of up to FW_FUSE_MAX consecutive frames (round 23: four; round 24: eight).  The frames fold from the left: the group so far is the fused frame U of
-// its members, and frame B may join exactly when fw_fuse2_ok(capacity, U, B) -- B continues U, the summed dead stay within the FIRST
-// frame's live particles (nobody born in the group dies in it), and the first frame's live particles plus every frame's spawns fit the
-// ring.  What the kernel needs beside U: where each frame's new particles end among the group's (cumulative: new particle k belongs to the
-// first frame f with k < spawn_end[f]) and how many each frame destroys.
-// FW_FUSE_NARROW: the depth a group may reach where round 23's threshold alone holds (fw_ctx::fuse_deep_min); beyond it every ring of the
-// launch must hold fw_ctx::fuse_wide_min as well (launch_fifo)
+// ---- a group of up to FW_FUSE_FAR consecutive frames (round 23: four; round 24: eight; round 32: sixteen).  The frames fold from the left: the
+// group so far is the fused frame U of its members, and frame B may join exactly when fw_fuse2_ok(capacity, U, B) -- B continues U, the
+// summed dead stay within the FIRST frame's live particles (nobody born in the group dies in it), and the first frame's live particles
+// plus every frame's spawns fit the ring.  What the kernel needs beside U: where each frame's new particles end among the group's
+// (cumulative: new particle k belongs to the first frame f with k < spawn_end[f]) and how many each frame destroys.
+// The depths of the ladder (fw_fuse_depth_max): FW_FUSE_NARROW where round 23's threshold alone holds (fw_ctx::fuse_deep_min); FW_FUSE_MAX,
+// the first tier -- what its kernels and their argument record (FwFuseArgs) hold -- where every ring holds fw_ctx::fuse_wide_min as well;
+// FW_FUSE_FAR, the far tier, whose kernels read frames FW_FUSE_MAX - 1 .. FW_FUSE_FAR - 2 from a record of their own (FwFarArgs, fw_kernels.h).
 #define FW_FUSE_MAX 8
 #define FW_FUSE_NARROW 4
+#define FW_FUSE_FAR 16
+// (what fw_ctx::fuse_far_depth starts at: FW_FUSE_MAX = the tier is off; profiles/r32/fuse_far_ab.txt says how it was chosen)
+#define FW_FUSE_FAR_DEFAULT 16
 struct FwFuseGroup {
     FwFifoFrame U;                   // the fused frame of the members so far
-    uint32_t depth;                  // members: 1 .. FW_FUSE_MAX
-    uint32_t spawn_end[FW_FUSE_MAX]; // new particles of frames 0 .. f (spawn_end[depth - 1] == U.n_spawn)
-    uint32_t dead[FW_FUSE_MAX];      // per frame (their sum == U.dead)
+    uint32_t depth;                  // members: 1 .. FW_FUSE_FAR
+    uint32_t spawn_end[FW_FUSE_FAR]; // new particles of frames 0 .. f (spawn_end[depth - 1] == U.n_spawn)
+    uint32_t dead[FW_FUSE_FAR];      // per frame (their sum == U.dead)
 };
 FW_HD FwFuseGroup fw_fuse_begin(const FwFifoFrame &A) {
     FwFuseGroup G{};
     G.U = A, G.depth = 1u, G.spawn_end[0] = A.n_spawn, G.dead[0] = A.dead;
     return G;
 }
-// may frame B join the group?  true: joined (G is the longer group); false: declined, G unchanged
-FW_HD bool fw_fuse_push(uint32_t capacity, FwFuseGroup &G, const FwFifoFrame &B) {
-    if (G.depth < 1u || G.depth >= FW_FUSE_MAX || !fw_fuse2_ok(capacity, G.U, B)) return false;
+// may frame B join the group?  limit: the depth the group may reach (never beyond FW_FUSE_FAR, the tables' length; a caller that names
+// none gets FW_FUSE_MAX, the first tier's cap -- what the call meant before the far tier, and what the programs written then still
+// mean by it).  true: joined (G is the longer group); false: declined, G unchanged
+FW_HD bool fw_fuse_push(uint32_t capacity, FwFuseGroup &G, const FwFifoFrame &B, uint32_t limit = FW_FUSE_MAX) {
+    if (G.depth < 1u || G.depth >= limit || G.depth >= FW_FUSE_FAR || !fw_fuse2_ok(capacity, G.U, B)) return false;
     G.U = fw_fuse2_frame(G.U, B);
     G.spawn_end[G.depth] = G.U.n_spawn, G.dead[G.depth] = B.dead;
     G.depth++;
     return true;
 }
 
-// ---- the far tier (round 32): a group of up to FW_FUSE_FAR frames, the same fold with longer tables.  fw_fuse2_ok and fw_fuse2_frame ask
-// nothing of the depth; FwFuseGroup, fw_fuse_push and FW_FUSE_MAX stay what they were -- the first tier's kernels, their argument record
-// (FwFuseArgs) and the tests that pin them hold eight frames.  What the kernels of the far tier read of frames 7 to FW_FUSE_FAR - 2 travels
-// in a record of its own (FwFarArgs, fw_kernels.h); who may go this deep: launch_fifo (fw_ctx::fuse_far_min, fuse_far_depth).
-#define FW_FUSE_FAR 16
-// (what fw_ctx::fuse_far_depth starts at: FW_FUSE_MAX = the tier is off; profiles/r32/fuse_far_ab.txt says how it was chosen)
-#define FW_FUSE_FAR_DEFAULT 16
-struct FwFarGroup {
-    FwFifoFrame U;                   // the fused frame of the members so far
-    uint32_t depth;                  // members: 1 .. FW_FUSE_FAR
-    uint32_t spawn_end[FW_FUSE_FAR]; // as FwFuseGroup's
-    uint32_t dead[FW_FUSE_FAR];
-};
-FW_HD FwFarGroup fw_far_begin(const FwFifoFrame &A) {
-    FwFarGroup G{};
-    G.U = A, G.depth = 1u, G.spawn_end[0] = A.n_spawn, G.dead[0] = A.dead;
-    return G;
+// ---- the depth ladder: how deep a group of a launch may go.  Four rungs, each a threshold on the live particles of every ring of the launch,
+// taken in this order: fw_ctx::fuse2_min (two frames), fuse_deep_min (min(knob, FW_FUSE_NARROW)), fuse_wide_min (the knob, fw_ctx::fuse_depth)
+// and fuse_far_min (fw_ctx::fuse_far_depth, the far tier).  A ring's rung is the FIRST threshold its live count does not meet, whatever
+// the later ones say; a launch's is the lowest rung of any of its rings.
+enum { FW_RUNG_NONE = 0, FW_RUNG_TWO = 1, FW_RUNG_NARROW = 2, FW_RUNG_WIDE = 3, FW_RUNG_FAR = 4 };
+FW_HD uint32_t fw_fuse_rung(uint32_t n_in, uint32_t fuse2_min, uint32_t deep_min, uint32_t wide_min, uint32_t far_min) {
+    const uint32_t mins[FW_RUNG_FAR] = {fuse2_min, deep_min, wide_min, far_min};
+    uint32_t r = FW_RUNG_NONE;
+    while (r < FW_RUNG_FAR && n_in >= mins[r]) r++;
+    return r;
 }
-// may frame B join the group?  true: joined (G is the longer group); false: declined, G unchanged
-FW_HD bool fw_far_push(uint32_t capacity, FwFarGroup &G, const FwFifoFrame &B) {
-    if (G.depth < 1u || G.depth >= FW_FUSE_FAR || !fw_fuse2_ok(capacity, G.U, B)) return false;
-    G.U = fw_fuse2_frame(G.U, B);
-    G.spawn_end[G.depth] = G.U.n_spawn, G.dead[G.depth] = B.dead;
-    G.depth++;
-    return true;
+// the depth a launch on `rung` (FW_RUNG_TWO at least: a launch below it is no candidate, fw_fuse2_candidate) may reach.  fuse_depth and
+// fuse_far_depth: the knobs as fw_ctx holds them; the far rung counts only with the knob at FW_FUSE_MAX and the forms that defer their
+// newborns' spin in use (newborn_deferred: FwFifoArgs::fuse_pad[FW_FIFO_NEWBORN] != 0 -- the far tier has no eager kernels)
+FW_HD uint32_t fw_fuse_depth_max(uint32_t rung, uint32_t fuse_depth, uint32_t fuse_far_depth, bool newborn_deferred) {
+    const uint32_t knob = fuse_depth < 2u ? 2u : fuse_depth > FW_FUSE_MAX ? (uint32_t)FW_FUSE_MAX : fuse_depth;
+    if (rung >= FW_RUNG_FAR && fuse_depth == FW_FUSE_MAX && newborn_deferred && fuse_far_depth > FW_FUSE_MAX)
+        return fuse_far_depth < FW_FUSE_FAR ? fuse_far_depth : (uint32_t)FW_FUSE_FAR;
+    return rung >= FW_RUNG_WIDE ? knob : rung == FW_RUNG_NARROW ? (knob < FW_FUSE_NARROW ? knob : (uint32_t)FW_FUSE_NARROW) : 2u;
 }

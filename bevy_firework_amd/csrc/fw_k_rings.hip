@@ -778,6 +778,22 @@ template <int NT, int TR>
 __global__ __launch_bounds__(FW_BLOCK) __attribute__((amdgpu_waves_per_eu(FW_NEST_WAVES))) void fw_k_update_fifo_nest(FwGlobals g, FwFifoArgs a, FwInlineOps inl) {
     fw_update_fifo_body<false, -1, NT, false, TR, true>(g, a, inl);
 }
+// The four forms of a spin-less launch, chosen in ONE place for every set of kernels that has them (the unfused ones below, the fused ones of
+// fw_k_rings_fuse2.hip and fw_k_rings_fuse2_eager.hip, the far tier's of fw_k_rings_far.hip): fully non-temporal and write-only non-temporal
+// (fw_ld4w; the generic write mask -- beyond the Infinity Cache the compile-time one buys nothing), write mask 0, generic.  `launch` is
+// the caller's kernel, launched with (WM, NT) as compile-time values: launch(fw_int<WM>, fw_int<NT>).
+template <int V>
+struct fw_int {
+    static constexpr int value = V;
+};
+template <class F>
+static hipError_t fw_launch_spinless_form(int nt, int32_t write_mask, F &&launch) {
+    if (nt == 2) launch(fw_int<-1>{}, fw_int<2>{});
+    else if (nt) launch(fw_int<-1>{}, fw_int<1>{});
+    else if (write_mask == 0) launch(fw_int<0>{}, fw_int<0>{});
+    else launch(fw_int<-1>{}, fw_int<0>{});
+    return hipGetLastError();
+}
 
 
 // ---------------------------------------------------------------------------------
@@ -1327,7 +1343,7 @@ void fw_k_update_range(FwGlobals g, FwRangeArgs a) {
 // the launches without a collider or a Nested entry; Q0PL: every ring of the launch keeps Q0 in component planes (FwFifoArgs::q0pl)
 template <bool Q0PL>
 static hipError_t fw_launch_update_fifo_plain(hipStream_t s, const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl, dim3 grid, dim3 block,
-                                              int nt, hipEvent_t e0, hipEvent_t e1, const FwFuseArgs *fz) {
+                                              int nt, hipEvent_t e0, hipEvent_t e1, const FwFuseRecords *rec) {
     if (a.small_tiles) {  // a launch of a few hundred four-round workgroups at most: one round each instead (generic write mask)
         if (a.any_inst)
             FW_LAUNCH_T((fw_k_update_fifo<true, -1, 0, 0, 1, Q0PL>), grid, block, s, e0, e1, g, a, inl);
@@ -1339,18 +1355,16 @@ static hipError_t fw_launch_update_fifo_plain(hipStream_t s, const FwGlobals &g,
         // no ring tile of the launch touches rotation or angular velocity (FwFifoArgs::spinless; the host sets it for launches without an
         // instance buffer only): the forms compiled for that -- five workgroups per CU
         if (a.fused && !(a.spinless && !a.any_inst)) return hipErrorInvalidValue;  // (the host fuses spin-less launches only)
-        if (a.spinless && !a.any_inst && a.fused) return fz ? fw_launch_update_fifo2(s, g, a, inl, *fz, grid.x, nt, e0, e1) : hipErrorInvalidValue;  // (fw_k_rings_fuse2.hip)
-        if (a.spinless && !a.any_inst) {
-            if (nt == 2)
-                FW_LAUNCH_T((fw_k_update_fifo<false, -1, 2, 0, FW_ROUNDS, true, true>), grid, block, s, e0, e1, g, a, inl);
-            else if (nt)
-                FW_LAUNCH_T((fw_k_update_fifo<false, -1, 1, 0, FW_ROUNDS, true, true>), grid, block, s, e0, e1, g, a, inl);
-            else if (a.write_mask == 0)
-                FW_LAUNCH_T((fw_k_update_fifo<false, 0, 0, 0, FW_ROUNDS, true, true>), grid, block, s, e0, e1, g, a, inl);
-            else
-                FW_LAUNCH_T((fw_k_update_fifo<false, -1, 0, 0, FW_ROUNDS, true, true>), grid, block, s, e0, e1, g, a, inl);
-            return hipGetLastError();
+        // (every depth is routed here and nowhere else: the first tier's unit, which forwards to the eager one, or the far tier's)
+        if (a.spinless && !a.any_inst && a.fused) {
+            if (!rec) return hipErrorInvalidValue;
+            if (a.fused > FW_FUSE_MAX) return fw_unit_update_fifo_far(s, g, a, inl, rec->fz, rec->far, grid.x, nt, e0, e1);  // (fw_k_rings_far.hip)
+            return fw_unit_update_fifo2(s, g, a, inl, rec->fz, grid.x, nt, e0, e1);  // (fw_k_rings_fuse2.hip)
         }
+        if (a.spinless && !a.any_inst)
+            return fw_launch_spinless_form(nt, a.write_mask, [&](auto WM, auto NT) {
+                FW_LAUNCH_T((fw_k_update_fifo<false, decltype(WM)::value, decltype(NT)::value, 0, FW_ROUNDS, true, true>), grid, block, s, e0, e1, g, a, inl);
+            });
     }
     if (nt) {  // non-temporal forms (fw_ld4w): the generic write mask only -- beyond the Infinity Cache the compile-time one buys nothing
         if (a.any_inst && nt == 2)
@@ -1386,7 +1400,7 @@ static hipError_t fw_launch_update_fifo_plain(hipStream_t s, const FwGlobals &g,
 }
 
 hipError_t fw_launch_update_fifo(hipStream_t s, const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl,
-                                 uint32_t total_tiles, int nt, hipEvent_t e0, hipEvent_t e1, const FwFuseArgs *fz) {
+                                 uint32_t total_tiles, int nt, hipEvent_t e0, hipEvent_t e1, const FwFuseRecords *rec) {
     if (!total_tiles || !a.n_segs) return hipErrorInvalidValue;
     const dim3 grid(total_tiles), block(FW_BLOCK);
     if (a.q0pl && (a.n_nest || a.any_coll)) return hipErrorInvalidValue;  // (the host launches rings with Q0 in planes by themselves)
@@ -1426,7 +1440,7 @@ hipError_t fw_launch_update_fifo(hipStream_t s, const FwGlobals &g, const FwFifo
             FW_LAUNCH_T((fw_k_update_fifo<false, -1, 0, 1, 1>), grid, block, s, e0, e1, g, a, inl);
         return hipGetLastError();
     }
-    if (a.q0pl) return fw_launch_update_fifo_plain<true>(s, g, a, inl, grid, block, nt, e0, e1, fz);
+    if (a.q0pl) return fw_launch_update_fifo_plain<true>(s, g, a, inl, grid, block, nt, e0, e1, rec);
     return fw_launch_update_fifo_plain<false>(s, g, a, inl, grid, block, nt, e0, e1, nullptr);
 }
 

@@ -311,6 +311,27 @@ struct FwFarArgs {
 static_assert(sizeof(FwFarArgs) == (FW_FUSE_FAR - FW_FUSE_MAX) * 4 * (1 + 2 * FW_FIFO_PER_LAUNCH), "one dt and, per ring, two boundaries per far frame");
 static_assert(sizeof(FwGlobals) + sizeof(FwFifoArgs) + sizeof(FwInlineOps) + sizeof(FwFuseArgs) + sizeof(FwFarArgs) <= 4096,
               "the far kernels' arguments fit the 4096-byte kernel-argument limit");
+// The two records' one owner on the host (FwFifoLaunch; fw_launch_update_fifo passes each kernel the record it takes): withheld frame w of a
+// group -- 0 .. FW_FUSE_FAR - 2 -- through one accessor, whichever record holds it.  (The kernel has its own, by the frame's compile-time
+// index: dt_w, spawn_end_w, dead_w, fw_k_rings.hip.)
+struct FwFuseRecords {
+    FwFuseArgs fz;
+    FwFarArgs far;
+    float &dt(uint32_t w) { return w < FW_FAR_FIRST ? fz.dt_pre[w] : far.dt[w - FW_FAR_FIRST]; }
+    uint32_t &spawn_end(uint32_t j, uint32_t w) { return w < FW_FAR_FIRST ? fz.spawn_end[j][w] : far.spawn_end[j][w - FW_FAR_FIRST]; }
+    uint32_t &dead(uint32_t j, uint32_t w) { return w < FW_FAR_FIRST ? fz.dead[j][w] : far.dead[j][w - FW_FAR_FIRST]; }
+    float dt(uint32_t w) const { return const_cast<FwFuseRecords *>(this)->dt(w); }
+    uint32_t spawn_end(uint32_t j, uint32_t w) const { return const_cast<FwFuseRecords *>(this)->spawn_end(j, w); }
+    uint32_t dead(uint32_t j, uint32_t w) const { return const_cast<FwFuseRecords *>(this)->dead(j, w); }
+    // what a frame that joins a group carries: the group's tables so far (null: no withheld frame has written one yet -- zeros) and the rings'
+    // constants, which every frame's launch brings itself: its own `move` rows
+    void continue_from(const FwFuseRecords *group) {
+        FwFuseRecords r = group ? *group : FwFuseRecords{};
+        for (uint32_t j = 0; j < FW_FIFO_PER_LAUNCH; j++)
+            for (uint32_t c = 0; c < 4; c++) r.fz.move[j][c] = fz.move[j][c];
+        *this = r;
+    }
+};
 
 // ---- range rings: particle types whose lifetime is a RANGE, updated in place ---------------------------------------
 // Ages never increase along the particle list (everybody is born with age 0 behind all older particles and every update
@@ -413,21 +434,20 @@ hipError_t fw_launch_spawn(hipStream_t s, const FwGlobals &g, const FwOp *d_ops,
 hipError_t fw_launch_fc_resolve(hipStream_t s, const FwGlobals &g, const FwResolveArgs &a);
 hipError_t fw_launch_update(hipStream_t s, const FwGlobals &g, const FwUpdateArgs &a, const FwInlineOps *inl,
                             int spawn_form, int mode, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr);
-// in-place update of up to FW_FIFO_PER_LAUNCH FIFO segments (their spawn ops in `inl`)
-// (the spin-less launch that runs FwFifoArgs::fused = 2 .. FW_FUSE_MAX frames: fw_k_rings_fuse2.hip; reached through fw_launch_update_fifo,
-// which wants `fz` for such a launch and for no other)
-hipError_t fw_launch_update_fifo2(hipStream_t s, const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl, const FwFuseArgs &fz,
-                                  uint32_t total_tiles, int nt, hipEvent_t e0, hipEvent_t e1);
-// (... and its forms whose spawning workgroups find out whether they spin what they spawn: fw_k_rings_fuse2_eager.hip, round 27)
-hipError_t fw_launch_update_fifo2_eager(hipStream_t s, const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl, const FwFuseArgs &fz,
-                                        uint32_t total_tiles, int nt, hipEvent_t e0, hipEvent_t e1);
-// (the far tier, FwFifoArgs::fused = FW_FUSE_MAX + 1 .. FW_FUSE_FAR: fw_k_rings_far.hip; the host calls it for such a launch itself --
-// enqueue_fifo --, so fw_launch_update_fifo and the units behind it compile to what they compiled to.  No eager forms: under
-// FW_NEWBORN_SPIN=1 the host closes its groups at FW_FUSE_MAX)
-hipError_t fw_launch_update_fifo_far(hipStream_t s, const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl, const FwFuseArgs &fz,
-                                     const FwFarArgs &far, uint32_t total_tiles, int nt, hipEvent_t e0, hipEvent_t e1);
+// in-place update of up to FW_FIFO_PER_LAUNCH FIFO segments (their spawn ops in `inl`): the one entry of every FIFO launch.  `rec`: the
+// withheld frames of a fused launch (FwFifoArgs::fused >= 2), wanted for such a launch and for no other; null: an unfused one
 hipError_t fw_launch_update_fifo(hipStream_t s, const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl,
-                                 uint32_t total_tiles, int nt, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, const FwFuseArgs *fz = nullptr);
+                                 uint32_t total_tiles, int nt, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, const FwFuseRecords *rec = nullptr);
+// The units behind it, one per set of fused kernels -- fw_launch_update_fifo routes by FwFifoArgs::fused, nobody else calls them:
+// fused = 2 .. FW_FUSE_MAX, fw_k_rings_fuse2.hip -- which forwards to fw_k_rings_fuse2_eager.hip, the forms whose spawning workgroups spin
+// what they spawn (round 27), where FwFifoArgs::fuse_pad[FW_FIFO_NEWBORN] is 0 --; fused = FW_FUSE_MAX + 1 .. FW_FUSE_FAR, fw_k_rings_far.hip
+// (no eager forms: under FW_NEWBORN_SPIN=1 the host closes its groups at FW_FUSE_MAX, and a launch that says otherwise is refused)
+hipError_t fw_unit_update_fifo2(hipStream_t s, const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl, const FwFuseArgs &fz,
+                                uint32_t total_tiles, int nt, hipEvent_t e0, hipEvent_t e1);
+hipError_t fw_unit_update_fifo2_eager(hipStream_t s, const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl, const FwFuseArgs &fz,
+                                      uint32_t total_tiles, int nt, hipEvent_t e0, hipEvent_t e1);
+hipError_t fw_unit_update_fifo_far(hipStream_t s, const FwGlobals &g, const FwFifoArgs &a, const FwInlineOps &inl, const FwFuseArgs &fz,
+                                   const FwFarArgs &far, uint32_t total_tiles, int nt, hipEvent_t e0, hipEvent_t e1);
 uint32_t fw_range_young_tile(void);  // ring slots a YOUNG workgroup of fw_k_update_range covers (a build-time choice)
 // in-place update of every range ring of the context (all_nospin: no segment of the launch keeps a rotation plane)
 // nt: which form of the kernel (fw_dev.h: fw_ld4w): 0 plain, 1 the write-only planes non-temporal, 2 every plane access

@@ -2,7 +2,8 @@
 // group, or for somebody who reads (fw_fuse2.h: the rules).  A value with three transitions -- offer, take, drop -- and the
 // one type everything that reaches the stream goes through, FwFifoLaunch.  Nothing outside this header writes a field of the group.
 // Plain host C++: no HIP call, nothing of the engine (fw_ctx, SegHost).  The engine (fw_engine_launch.cpp: launch_fifo, flush_withheld)
-// and a host test that drives the group through random hosts beside a model of its own (tests/test_cpp_host_withheld.py) compile the same lines.
+// and two host tests that drive the group through random hosts beside a model of their own (tests/test_cpp_host_withheld.py,
+// test_cpp_host_withheld_far.py; the model: tests/fuse_model.py) compile the same lines.
 #pragma once
 #include <string.h>
 #include "fw_kernels.h"
@@ -11,8 +12,8 @@
 struct FwFifoLaunch {
     FwFifoArgs fa;   // depth 1: the frame's launch as built (fa.fused == 0); deeper: the fused launch (fa.fused == depth, fa.dt the last frame's)
     FwInlineOps fio;
-    FwFuseArgs fz;   // depth >= 2: the fused kernels' fourth argument, the dt and boundaries of frames 0 .. depth - 2; depth 1: unused
-    FwFarArgs far;   // depth > FW_FUSE_MAX: the far kernels' fifth argument, the same of frames FW_FUSE_MAX - 1 .. depth - 2; else unused
+    FwFuseRecords rec;  // depth >= 2: the dt and boundaries of the withheld frames 0 .. depth - 2, in the records the fused kernels take; depth 1: unused
+                        // (but for the rings' constants, rec.fz.move, which every frame's launch carries)
     uint32_t tiles, n_ops;
     int nt;          // the non-temporal form the LAST frame's launch would have taken
     uint32_t depth;  // frames the launch runs: 1 .. FW_FUSE_MAX, the far tier's up to FW_FUSE_FAR
@@ -66,7 +67,7 @@ public:
         }
         at_ ^= 1u;  // (what `first` points at stays as it is)
         keep(slot_[at_], B);
-        for (uint32_t j = 0; j < B.fa.n_segs; j++) grp_[j] = fw_far_begin(FwFifoFrame{B.fa.s[j].head, B.fa.s[j].n_in, B.fa.s[j].n_spawn, B.fa.s[j].dead});
+        for (uint32_t j = 0; j < B.fa.n_segs; j++) grp_[j] = fw_fuse_begin(FwFifoFrame{B.fa.s[j].head, B.fa.s[j].n_in, B.fa.s[j].n_spawn, B.fa.s[j].dead});
         on_ = true, o.withheld = true;
         return o;
     }
@@ -92,7 +93,7 @@ private:
     // (fw_fuse_push: the pair rule between the fused frame so far and B) and the ops of all frames fit (FW_INLINE_OPS = 8: one ring with one
     // op per frame reaches FW_FUSE_MAX frames, a launch that carries two ops per frame closes its groups at four).  The fused launch is B's
     // with the group's head, live count and input row in front; the group's ops first, in frame order, B's behind them (rel_base shifted by
-    // the new particles in front of them); `fz`: the withheld frames' dt and boundaries -- from withheld frame FW_FAR_FIRST on in `far`.
+    // the new particles in front of them); `rec`: the withheld frames' dt and boundaries (FwFuseRecords: whichever record holds the frame).
     // merge: B's first op of a ring may become part of the group's last op of that ring.  false: declined, nothing changed.
     bool join(FwFifoLaunch &B, bool merge) {
         const FwFifoLaunch &P = slot_[at_];
@@ -100,7 +101,7 @@ private:
         const uint32_t d = P.depth;  // (withheld frames: B is frame d of the group)
         if (d < 1u || d >= FW_FUSE_FAR) return false;
         if (P.fa.n_segs != fa.n_segs || P.fa.write_mask != fa.write_mask || P.n_ops > FW_INLINE_OPS || B.n_ops > FW_INLINE_OPS) return false;
-        FwFarGroup grp[FW_FIFO_PER_LAUNCH];
+        FwFuseGroup grp[FW_FIFO_PER_LAUNCH];
         uint32_t merged = 0;  // ops of B that become part of an op of the group
         for (uint32_t j = 0; j < fa.n_segs; j++) {
             const FwFifoSeg &A = P.fa.s[j], &F = fa.s[j];
@@ -108,7 +109,7 @@ private:
                 A.keys_len != F.keys_len || A.life != F.life || A.mat || F.mat || A.destroyed || F.destroyed || A.nest || F.nest)
                 return false;
             grp[j] = grp_[j];
-            if (!fw_far_push(F.capacity, grp[j], FwFifoFrame{F.head, F.n_in, F.n_spawn, F.dead})) return false;
+            if (!fw_fuse_push(F.capacity, grp[j], FwFifoFrame{F.head, F.n_in, F.n_spawn, F.dead}, FW_FUSE_FAR)) return false;
             if (merge && A.op0 < A.op1 && F.op0 < F.op1) {
                 FwOp b = B.fio.ops[F.op0];
                 b.rel_base += grp[j].spawn_end[d - 1u];
@@ -116,14 +117,9 @@ private:
             }
         }
         if (P.n_ops + B.n_ops - merged > FW_INLINE_OPS) return false;
-        {
-            FwFuseArgs fz = d >= 2u ? P.fz : FwFuseArgs{};  // (one withheld frame: its record is unused, whatever it holds)
-            memcpy(fz.move, B.fz.move, sizeof fz.move);     // (... but for the rings' constants, which every frame's launch carries: B's own)
-            B.fz = fz;
-            B.far = d > FW_FAR_FIRST ? P.far : FwFarArgs{};  // (likewise: frames from FW_FAR_FIRST on)
-        }
+        B.rec.continue_from(d >= 2u ? &P.rec : nullptr);  // (one withheld frame: its records are unused, whatever they hold)
         const uint32_t w = d - 1u;  // (the withheld frame this join adds: the group's latest)
-        (w < FW_FAR_FIRST ? B.fz.dt_pre[w] : B.far.dt[w - FW_FAR_FIRST]) = P.fa.dt;
+        B.rec.dt(w) = P.fa.dt;
         FwInlineOps ops;
         uint32_t n = 0, t = 0;
         for (uint32_t j = 0; j < fa.n_segs; j++) {
@@ -140,8 +136,7 @@ private:
             }
             const FwFifoLayout L = fw_fifo_layout(F.capacity, FW_TILE, FW_BLOCK, U.head, U.dead, U.n_in, U.n_in, U.n_spawn);
             F.head = U.head, F.n_in = U.n_in, F.n_spawn = U.n_spawn, F.dead = U.dead;
-            (w < FW_FAR_FIRST ? B.fz.spawn_end[j][w] : B.far.spawn_end[j][w - FW_FAR_FIRST]) = grp[j].spawn_end[w];
-            (w < FW_FAR_FIRST ? B.fz.dead[j][w] : B.far.dead[j][w - FW_FAR_FIRST]) = grp[j].dead[w];
+            B.rec.spawn_end(j, w) = grp[j].spawn_end[w], B.rec.dead(j, w) = grp[j].dead[w];
             F.op0 = o0, F.op1 = n;
             F.spawn_a = L.spawn_a, F.n_vt_a = L.n_vt_a, F.n_vt_b = L.n_vt_b, F.tile0 = L.tile0, F.n_tiles = L.n_tiles;
             F.tile_first = t;
@@ -160,5 +155,5 @@ private:
     bool on_ = false;
     uint32_t at_ = 0;      // the slot the group lives in; the other one keeps what the latest offer sent out as `first`
     FwFifoLaunch slot_[2] = {};
-    FwFarGroup grp_[FW_FIFO_PER_LAUNCH];   // per ring of the group: the fused frame and every frame's share (fw_fuse2.h)
+    FwFuseGroup grp_[FW_FIFO_PER_LAUNCH];   // per ring of the group: the fused frame and every frame's share (fw_fuse2.h)
 };
